@@ -19,6 +19,11 @@ ranks itself and refuses to run on fewer devices; windows are independent so ran
                         bounded sample of the step's windows, for the headline model and (events_only.cpu_baseline) the
                         events-only one
   image_branch          the dense ResNet-50 branch's time, GFLOP and rate against the fp32 matrix peak (library code)
+
+`--dump-outputs DIR` writes what the headline's last timed step returned on rank 0 (detections and survivor counts) as
+DIR/*.npy.  The inputs and weights are seeded, so the same arguments give the same inputs on every run and two builds can
+be compared output for output.  The events-only path repeats bit for bit; with the image branch (library convolutions in
+benchmark mode) the values move in the last bits from run to run, so compare those with a tolerance.
 """
 import argparse
 import glob
@@ -76,7 +81,34 @@ def parse():
     ap.add_argument("--dry-run-gloo", action="store_true",
                     help="no device: the launch logic, rendezvous, barrier-bracketed timed region, detection gather and "
                          "per-rank report over gloo on CPU with a stand-in rig (value is null)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline's timed steps, write what its last step returned (rank 0) as DIR/*.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, det, n_keep):
+    """The caller's view of one step, ``(det[B, A, 6], n_keep[B])``, as ``detections.npy`` (float32) and ``n_keep.npy``
+    (float64).  Rows at and beyond ``n_keep[b]`` are never written by the post-processing (their contents are whatever the
+    allocator left there), so they are stored as zeros.  Above DUMP_MAX_BYTES a fixed, seeded sample of the windows is kept
+    and ``window_index.npy`` names them."""
+    os.makedirs(out_dir, exist_ok=True)
+    det = det.detach().float().cpu().numpy().copy()
+    n = n_keep.detach().cpu().numpy().astype(np.int64)
+    B, A, _ = det.shape
+    det[np.arange(A)[None, :] >= n[:, None]] = 0.0
+    per_window = det[0].nbytes + 2 * 8          # its rows + its n_keep and window_index entries
+    if B * per_window > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(B, size=max(1, DUMP_MAX_BYTES // per_window), replace=False))
+        det, n = det[idx], n[idx]
+        np.save(os.path.join(out_dir, "window_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "detections.npy"), det)
+    np.save(os.path.join(out_dir, "n_keep.npy"), n.astype(np.float64))
 
 
 def source_stamp():
@@ -386,8 +418,9 @@ def detections_rows(results, rank, B):
     return rows[mask]
 
 
-def timed_run(rig, slots, steps, warmup, dist, world, rank):
-    """W untimed warm-up steps, then exactly `steps` steps between barrier + synchronize brackets; MAX over ranks."""
+def timed_run(rig, slots, steps, warmup, dist, world, rank, dump_dir=None):
+    """W untimed warm-up steps, then exactly `steps` steps between barrier + synchronize brackets; MAX over ranks.
+    ``dump_dir``: rank 0 writes its last step's outputs there once the timed region is over (`dump_outputs`)."""
     from dagr_amd import parallel
     dev = rig.dev
     warm = [rig.step(i, slots) for i in range(warmup)]
@@ -429,6 +462,8 @@ def timed_run(rig, slots, steps, warmup, dist, world, rank):
         dist.all_gather(every, mine)
         per_rank = [[float(v) for v in t.tolist()] for t in every]
     rig.engines[0].check_status()
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, *results[-1])
     return dict(elapsed=elapsed, t_compute=t_compute, t_gather=t_gather, per_rank=per_rank, ranks_seen=ranks_seen,
                 n_detections=int(allrows.shape[0]))
 
@@ -621,7 +656,7 @@ def dry_run(a, world, rank, rank_env, t_start):
     envs = [None] * world
     dist.all_gather_object(envs, dict(rank=rank, miopen_db=rank_env["miopen_db"], cores=rank_env["cores"],
                                       startup_s=round(time.perf_counter() - t_start, 3)))
-    run = timed_run(DryRunRig(rank), None, a.steps, a.warmup, dist, world, rank)
+    run = timed_run(DryRunRig(rank), None, a.steps, a.warmup, dist, world, rank, dump_dir=a.dump_outputs)
     if rank == 0:
         print(json.dumps({"metric": "events_per_sec", "value": None, "unit": "events/s", "n_gpus": world, "world": world,
                           "ranks_seen": run["ranks_seen"], "steps": a.steps, "warmup": a.warmup,
@@ -744,7 +779,7 @@ def main():
     # ---- headline: the configuration BASELINE.json quotes the metric on
     rig = Rig(W, H, B, use_image, a.img_net, n_eng, dev)
     slots = rig.make_slots(gen, NPW, 4, seed=1234 + 1000 * rank)
-    run = timed_run(rig, slots, a.steps, a.warmup, dist, world, rank)
+    run = timed_run(rig, slots, a.steps, a.warmup, dist, world, rank, dump_dir=a.dump_outputs)
 
     # ---- the hand-written path alone: same steps on the events-only model
     ev_leg = ev_rig = ev_slots = None

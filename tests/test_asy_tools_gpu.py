@@ -1,7 +1,8 @@
 """The masked row operators of the asynchronous update (1:1 replacements of the reference's `asy_tools`,
 src/dagr/asynchronous/asy_tools/main.cu) and DAGR.forward(reset=False):
-  * libdagr_hip's kernels vs the reference's OWN kernels (oracle/_ref/libasy_tools_ref.so, compiled from
-    /root/reference by oracle/Makefile) -- bit for bit -- and vs the numpy restatement (oracle/asy.py);
+  * libdagr_hip's kernels vs the reference's OWN kernels -- bit for bit; run live where oracle/_ref/libasy_tools_ref.so is
+    built (oracle/Makefile), else against their stored digests (tests/ref_golden.py) -- and vs the numpy restatement
+    (oracle/asy.py);
   * events fed in micro-batches with reset=False give exactly the outputs of one reset=True call on all of them (the
     equality the reference's asynchronous model guarantees, evaluate_flops.py:139-147)."""
 import numpy as np
@@ -15,6 +16,7 @@ from dagr_amd.data import Batch, Data
 from dagr_amd.utils import synthetic as syn
 from dagr_amd.utils.buffers import format_data
 from dagr_amd.utils.testing_weights import randomize_
+from tests.ref_golden import digest, reference
 
 pytestmark = pytest.mark.gpu
 
@@ -46,14 +48,17 @@ def test_masked_lin_matches_reference_kernels_and_oracle(n_rows, K, Cin, Cout, a
         untouched = np.setdiff1d(np.arange(n_rows), c["idx"])
         assert np.array_equal(got[untouched], c["x_out"][untouched])                 # only the masked rows move
         assert np.abs(got - want).max() <= 1e-5 * max(1.0, np.abs(want).max())
-        if ref_harness.asy_available():
+
+        def ref_lin():
             R = ref_harness.asy_lib()
             ro, ri, rx, rw, rb = T(c["x_out"]), T(c["idx"]), T(c["x_in"]), T(c["w"]), T(c["b"])
             if with_bias:
                 assert R.ref_masked_lin(P(ri), K, P(rx), P(ro), n_rows, P(rw), P(rb), Cin, Cout, int(add)) == 0
             else:
                 assert R.ref_masked_lin_no_bias(P(ri), K, P(rx), P(ro), n_rows, P(rw), Cin, Cout, int(add)) == 0
-            assert torch.equal(ro, out), "differs from the reference's own kernel"
+            return ro
+        key = f"asy/masked_lin/{n_rows}-{K}-{Cin}-{Cout}-add{int(add)}-bias{int(with_bias)}"
+        assert digest(out) == reference(key, ref_harness.asy_available(), ref_lin), "differs from the reference's own kernel"
 
 
 def test_masked_isdiff_and_bn_match_reference_kernels_and_oracle():
@@ -72,21 +77,27 @@ def test_masked_isdiff_and_bn_match_reference_kernels_and_oracle():
         kept = asy_tools.masked_isdiff(ti, T(x_old), T(x_new), atol, rtol)
         marked, want = oasy.masked_isdiff(idx, x_old, x_new, atol, rtol)
         assert np.array_equal(ti.cpu().numpy(), marked) and np.array_equal(kept.cpu().numpy(), want)
-        if ref_harness.asy_available():
+
+        def ref_isdiff():
             ri = T(idx)
             assert ref_harness.asy_lib().ref_masked_isdiff(P(ri), K, P(T(x_old)), P(T(x_new)), n_rows, C, atol, rtol) == 0
-            assert torch.equal(ri, ti)
+            return ri
+        assert digest(ti) == reference(f"asy/masked_isdiff/atol{atol:g}-rtol{rtol:g}", ref_harness.asy_available(),
+                                       ref_isdiff)
     mean, var = rng.standard_normal(C).astype(np.float32), rng.uniform(0.5, 1.5, C).astype(np.float32)
     w, b = rng.uniform(0.5, 1.5, C).astype(np.float32), rng.standard_normal(C).astype(np.float32)
     out = T(x_new)
     asy_tools.masked_inplace_BN(T(idx), T(x_old), out, T(mean), T(var), T(w), T(b), 1e-5)
     want = oasy.masked_inplace_BN(idx, x_old, x_new, mean, var, w, b, 1e-5)
     assert np.abs(out.cpu().numpy() - want).max() <= 1e-5
-    if ref_harness.asy_available():
+
+    def ref_bn():
         ro = T(x_new)
         assert ref_harness.asy_lib().ref_masked_inplace_BN(P(T(idx)), K, P(T(x_old)), P(ro), n_rows, C, P(T(mean)), P(T(var)),
                                                            P(T(w)), P(T(b)), 1e-5) == 0
-        assert torch.equal(ro, out), "differs from the reference's own kernel"
+        return ro
+    assert digest(out) == reference("asy/masked_inplace_BN", ref_harness.asy_available(), ref_bn), \
+        "differs from the reference's own kernel"
     with pytest.raises(RuntimeError):
         asy_tools.masked_lin(torch.from_numpy(idx), T(x_old), T(x_new), T(w[:, None]), T(b), False)   # host tensor
 

@@ -80,6 +80,54 @@ def test_gpus_flag_launches_the_ranks_itself():
     assert line["gather"]["detections"] == sum((r + i + b) % 4 for r in range(2) for i in range(4) for b in range(3))
 
 
+def test_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` writes what rank 0's last timed step returned: with --steps 4 that is step 3, whose image b keeps
+    (3 + b) % 4 rows.  Rows past n_keep are zeros; the line still reports ms_per_step over exactly --steps steps."""
+    import numpy as np
+    out = tmp_path / "dump"
+    p = _bench("--gpus", "2", "--dry-run-gloo", "--steps", "4", "--warmup", "1", "--dump-outputs", str(out))
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 4 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(out)) == ["detections.npy", "n_keep.npy"]
+    det, n = np.load(out / "detections.npy"), np.load(out / "n_keep.npy")
+    assert det.dtype == np.float32 and det.shape == (_FakeRig.B, _FakeRig.A, 6)
+    assert n.dtype == np.float64 and n.tolist() == [(3 + b) % 4 for b in range(_FakeRig.B)]
+    want, _ = _FakeRig(0).step(3, None)
+    np.testing.assert_array_equal(det, want.numpy())
+    for b in range(_FakeRig.B):
+        assert not det[b, int(n[b]):].any()
+
+
+def test_dump_outputs_samples_windows_beyond_the_size_cap(tmp_path, monkeypatch):
+    """Above the cap a seeded sample of whole windows is written, with their indices; the same sample every time.
+    Rows past n_keep (never written by the post-processing) are zeroed whatever they held."""
+    import numpy as np
+    B, A = 50, 8
+    det = torch.arange(B * A * 6, dtype=torch.float32).view(B, A, 6)
+    n = torch.tensor([b % (A + 1) for b in range(B)], dtype=torch.int32)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * (A * 6 * 4 + 16))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), det, n)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["detections.npy", "n_keep.npy", "window_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in files) <= bench.DUMP_MAX_BYTES   # (128: .npy header)
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    idx = np.load(tmp_path / "a" / "window_index.npy").astype(np.int64)
+    got, kept = np.load(tmp_path / "a" / "detections.npy"), np.load(tmp_path / "a" / "n_keep.npy")
+    assert len(idx) == 10 and np.all(np.diff(idx) > 0)
+    for j, b in enumerate(idx):
+        assert kept[j] == int(n[b])
+        np.testing.assert_array_equal(got[j, :int(n[b])], det[b, :int(n[b])].numpy())
+        assert not got[j, int(n[b]):].any()
+
+
+def test_steps_must_be_positive():
+    p = _bench("--gpus", "1", "--dry-run-gloo", "--steps", "0")
+    assert p.returncode != 0 and "--steps must be at least 1" in p.stderr
+
+
 def test_gpus_flag_refuses_fewer_devices_than_ranks():
     """No silent single-rank run: on a box with fewer devices than --gpus (here: none) the command fails loudly."""
     p = _bench("--gpus", "2", "--steps", "1", "--warmup", "0", "--no-latency", "--no-cpu-baseline")

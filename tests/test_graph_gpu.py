@@ -245,9 +245,9 @@ def _search_counters(case):
 @pytest.mark.parametrize("case", heavy_cases(), ids=lambda c: c["name"])
 def test_heavy_neighbourhoods_bit_exact(case):
     """Event-dense neighbourhoods -- the row kernel's ring-limited passes (inner window first, then the parts left and right
-    of it) and the position-centric walk of the deferred ones -- == the oracle == (where oracle/_ref is built) the
-    reference's own insert_in_queue + fill_edges kernels run on this GPU, edge for edge; the counters show that the
-    intended path ran."""
+    of it) and the position-centric walk of the deferred ones -- == the oracle == the reference's own insert_in_queue +
+    fill_edges kernels (run on this GPU where oracle/_ref is built, else their stored digests: tests/ref_golden.py), edge
+    for edge; the counters show that the intended path ran."""
     ei, nbr_src, nbr_code, deg, ne, flags = _run_hip(case)
     ref = _oracle(case)
     assert flags == 0
@@ -256,10 +256,13 @@ def test_heavy_neighbourhoods_bit_exact(case):
     assert ne == ref.shape[1] and deg.max() <= case["K"]
     _check_codes(case, nbr_src, nbr_code, deg)
     from oracle import ref_harness
-    if ref_harness.available():
-        own = ref_harness.reference_window_graph(case["x"], case["y"], case["t"], case["b"], case["W"], case["H"], case["B"],
-                                                 case["r"], case["dt"], K=case["K"], Q=case["Q"])
-        assert own.shape == ei.shape and (own == ei).all()
+    from tests.ref_golden import digest, reference
+
+    def own():
+        return np.asarray(ref_harness.reference_window_graph(case["x"], case["y"], case["t"], case["b"], case["W"], case["H"],
+                                                             case["B"], case["r"], case["dt"], K=case["K"], Q=case["Q"]),
+                          np.int64)
+    assert digest(np.asarray(ei, np.int64)) == reference(f"graph/heavy/{case['name']}", ref_harness.available(), own)
     cnt = _search_counters(case)
     assert cnt["unsorted"] == 0
     if case["name"].startswith(("walk", "blob", "uniform_dense", "stale")):

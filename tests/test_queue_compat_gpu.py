@@ -1,8 +1,8 @@
 """GPU parity of the 1:1 `ev_graph_cuda` replacements (dagr_fill_edges / dagr_insert_in_queue*):
   * the mirrored SlidingWindowGraph against the CPU oracle over multi-call sequences, including
     reset=False incremental calls with delete_nodes (min_index > 0) and a single-event call;
-  * directly against the reference's OWN kernels (oracle/_ref, compiled from /root/reference) when that
-    library travelled to the box: identical FIFO volume and edge buffer, bit for bit."""
+  * directly against the reference's OWN kernels: identical FIFO volume and edge buffer, bit for bit (run live where
+    oracle/_ref is built, else against their stored digests: tests/ref_golden.py)."""
 import ctypes
 
 import numpy as np
@@ -12,6 +12,7 @@ import torch
 from oracle import graph as og
 from oracle import ref_harness
 from dagr_amd.utils import synthetic as syn
+from tests.ref_golden import digest, reference
 
 pytestmark = pytest.mark.gpu
 
@@ -54,11 +55,9 @@ def test_sliding_window_graph_incremental_matches_oracle(delete_nodes):
     assert (e1 == o.forward(b, pos, delete_nodes=False)).all()
 
 
-@pytest.mark.skipif(not ref_harness.available(), reason="oracle/_ref (reference kernels) not on this box")
 def test_kernels_match_reference_kernels_bit_exact():
     from dagr_amd import _lib
     L, P = _lib.lib(), _lib.ptr
-    R = ref_harness.lib()
     dev = torch.device("cuda:0")
     W, H, B, Q, K, r, dt = 64, 48, 2, 16, 16, 4, 10000
     x, y, t, p, b = syn.batch_windows(syn.edges_window, 4000, B, W, H, seed=3)
@@ -71,17 +70,28 @@ def test_kernels_match_reference_kernels_bit_exact():
     sorted_indices = indices[sort_index].int().contiguous()
     uniq, counts = torch.unique_consecutive(sorted_lin, return_counts=True)
     cumsum = torch.cumsum(counts, 0).int().contiguous(); uniq = uniq.int().contiguous()
-    q_ref = torch.full((B, Q, H, W), -1, dtype=torch.int32, device=dev); q_hip = q_ref.clone()
+    q_hip = torch.full((B, Q, H, W), -1, dtype=torch.int32, device=dev)
     st = _lib.cur_stream(dev)
-    assert R.ref_insert_in_queue(P(sorted_indices), N, P(uniq), P(cumsum), len(uniq), P(q_ref), B, Q, H, W) == 0
     _lib.check(L.dagr_insert_in_queue(P(sorted_indices), P(uniq), P(cumsum), len(uniq), P(q_hip), B, Q, H, W, st))
     torch.cuda.synchronize()
-    assert torch.equal(q_ref, q_hip)
-    e_ref = torch.full((2, K * N), -1, dtype=torch.int64, device=dev); e_hip = e_ref.clone()
+
+    def ref_queue():
+        q_ref = torch.full((B, Q, H, W), -1, dtype=torch.int32, device=dev)
+        assert ref_harness.lib().ref_insert_in_queue(P(sorted_indices), N, P(uniq), P(cumsum), len(uniq), P(q_ref), B, Q,
+                                                     H, W) == 0
+        torch.cuda.synchronize()
+        return q_ref
+    assert digest(q_hip) == reference("queue_compat/insert_in_queue", ref_harness.available(), ref_queue)
+    e_hip = torch.full((2, K * N), -1, dtype=torch.int64, device=dev)
     ts = pos[:, 2].contiguous()
-    assert R.ref_fill_edges(P(batch), P(pos), P(ts), N, P(q_ref), P(indices), K, float(r), float(dt), P(e_ref), K * N, 0,
-                            N, B, Q, H, W) == 0
     _lib.check(L.dagr_fill_edges(P(batch), P(pos), P(ts), P(q_hip), P(indices), K, float(r), float(dt), P(e_hip), K * N,
                                  0, N, B, Q, H, W, st))
     torch.cuda.synchronize()
-    assert torch.equal(e_ref, e_hip)
+
+    def ref_edges():      # on the (equal, checked above) FIFO volume
+        q_ref, e_ref = q_hip.clone(), torch.full((2, K * N), -1, dtype=torch.int64, device=dev)
+        assert ref_harness.lib().ref_fill_edges(P(batch), P(pos), P(ts), N, P(q_ref), P(indices), K, float(r), float(dt),
+                                                P(e_ref), K * N, 0, N, B, Q, H, W) == 0
+        torch.cuda.synchronize()
+        return e_ref
+    assert digest(e_hip) == reference("queue_compat/fill_edges", ref_harness.available(), ref_edges)
