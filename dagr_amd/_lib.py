@@ -209,6 +209,8 @@ SIGNATURES = {
     "dagr_bn_relu_maxpool": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dagr_gemm_bias_act": (ctypes.c_int, [c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p,
                                           c_i32, c_i32, c_i32, c_i32, c_void_p]),
+    "dagr_async_flops": (ctypes.c_int, [c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p,
+                                        c_void_p]),
 }
 
 _lib = None

@@ -25,13 +25,24 @@ from . import asy_tools  # noqa: F401
 def make_model_asynchronous(module, log_flops=False):
     """``asynchronous/__init__.py:41-110`` (used as ``model = make_model_asynchronous(model)``, then
     ``model.forward(events_initial, reset=True)`` and ``model.forward(events_new, reset=False)``,
-    evaluate_flops.py:113-118): ``reset=False`` calls update the resident window incrementally.  The reference's
-    per-layer FLOP log counts the operations of ITS update scheme (per-layer residual scatters); this stack runs another
-    one, so asking for that log is an error rather than a made-up number."""
-    if log_flops:
-        raise NotImplementedError("log_flops counts the reference's per-layer incremental updates (asynchronous/flops)")
+    evaluate_flops.py:113-118): ``reset=False`` calls update the resident window incrementally.
+
+    ``log_flops=True`` (a ``DAGR``): every module the reference converts gets an ``asy_flops_log`` list, and each
+    ``reset=True`` forward appends the module's FLOPs in the reference's scheme, counted on the device (``flops.py``).
+    A ``reset=False`` forward while logging raises ``NotImplementedError``: the update pass's count is not implemented yet
+    here (``flops.UPDATE_NOT_COUNTED``).  A module with nothing to count raises ``NotImplementedError`` too."""
     if not hasattr(module, "forward"):
         raise TypeError("module must be a torch.nn.Module")
+    if log_flops:
+        if type(module).__name__ != "DAGR" or not hasattr(module, "engine"):
+            raise NotImplementedError("log_flops counts the modules of a DAGR model (asynchronous/flops)")
+        if getattr(module, "module_path_only", False):
+            raise NotImplementedError("log_flops with --keep_temporal_ordering: that model runs module by module, "
+                                      "without the window engine whose level counts are read")
+        from .flops import logged_modules
+        for _, m, _ in logged_modules(module):
+            m.asy_flops_log = []
+        module._log_flops = True
     module.asynchronous = True
     return module
 
@@ -39,6 +50,11 @@ def make_model_asynchronous(module, log_flops=False):
 def make_model_synchronous(module):
     """``asynchronous/__init__.py:30-39``: ``reset=False`` calls evaluate the whole running window again -- the
     synchronous forward on all events so far, the side of the consistency check (evaluate_flops.py:139-147) the
-    incremental update is compared with."""
+    incremental update is compared with.  The FLOP logs are emptied and logging stops."""
     module.asynchronous = False
+    if getattr(module, "_log_flops", False):
+        from .flops import logged_modules
+        for _, m, _ in logged_modules(module):
+            m.asy_flops_log = []
+        module._log_flops = False
     return module

@@ -333,6 +333,16 @@ class DAGR(torch.nn.Module):
         self._stamp_tensors = None
         return r
 
+    def _append_flops(self, eng):
+        """make_model_asynchronous(log_flops=True): the window's count per converted module (asynchronous/flops.py)."""
+        from ...asynchronous.flops import Accountant, logged_modules
+        acc = getattr(eng, "_flops_accountant", None)
+        if acc is None:
+            acc = eng._flops_accountant = Accountant(self, eng)
+        flops = acc.count()
+        for name, m, _ in logged_modules(self):
+            m.asy_flops_log.append(flops[name])
+
     # -- dagr.py:74-103 (eval branch) ----------------------------------------------------------
     def forward(self, x, reset=True, return_targets=True, filtering=True):
         if self.training:
@@ -350,6 +360,9 @@ class DAGR(torch.nn.Module):
             return ret
         eng = self.engine()
         eng.check_batch(x)
+        if not reset and getattr(self, "_log_flops", False):
+            from ...asynchronous.flops import UPDATE_NOT_COUNTED
+            raise NotImplementedError(UPDATE_NOT_COUNTED)
         if reset:
             self._window = None                  # a new window: the running one is gone
         det_dev = None           # (det, n_keep) when forward + post-processing ran as one captured graph
@@ -392,6 +405,8 @@ class DAGR(torch.nn.Module):
             detections = postprocess_network_output(outputs, self.backbone.num_classes, self.conf_threshold,
                                                     self.nms_threshold, filtering=filtering, height=self.height,
                                                     width=self.width)
+        if reset and getattr(self, "_log_flops", False):
+            self._append_flops(eng)
         if self.check_device_status:
             # sticky device-side flags (events outside the sensor / batch range, pooled-level capacity overflows,
             # to_dense cells outside the map): a window that tripped one was computed on a truncated graph.  The

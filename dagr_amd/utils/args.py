@@ -117,6 +117,21 @@ def FLAGS(argv=None):
     return args
 
 
+def FLOPS_FLAGS(argv=None):
+    """args.py:82-101: ``BASE_FLAGS`` plus ``--check_consistency`` / ``--dense`` (scripts/count_flops.py)."""
+    p = BASE_FLAGS()
+    p.add_argument("--check_consistency", action="store_true")
+    p.add_argument("--dense", action="store_true")
+    args = p.parse_args(argv)
+    if args.config != "":
+        args = parse_config(args, args.config)
+    args.dataset_directory = Path(args.dataset_directory)
+    args.output_directory = Path(args.output_directory)
+    if "checkpoint" in args:
+        args.checkpoint = Path(args.checkpoint)
+    return args
+
+
 def SCRIPT_FLAGS(argv=None, description=None, default_config="dagr-s-dsec.yaml", extra=None):
     """``FLAGS`` for the shipped scripts: the reference's command lines parse to the reference's namespace (same parser, same
     YAML merge), plus (i) ``--config`` also takes a short name / is looked up under the repository's ``config/``, with

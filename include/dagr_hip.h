@@ -608,6 +608,24 @@ int dagr_gemm_epilogue(const float *A, int64_t M, int32_t K, int64_t lda, const 
                        const float *R, int64_t ldr, int32_t act, float *D, int64_t ldd, void *workspace,
                        size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * FLOP accounting in the reference's scheme (src/dagr/asynchronous/flops/conv.py and the per-module logs of
+ * asynchronous/conv.py, max_pool.py, linear.py, cartesian.py, batch_norm.py): the counts of the init pass (log index 0,
+ * evaluate_flops(..., dense=True)) of one window, one int64 per logged module.
+ *   deg[n_events]      level-0 in-degrees of the window's events (level-0 edges = their sum)
+ *   counts1..counts4   [n_nodes, n_edges] of pooled levels 1..4 (device)
+ *   mods[n_mods]       the modules (device): kind, graph level (0..4; a pooling's INPUT level), cin / cout, whether
+ *                      the conv has a root weight / a bias
+ *   out[n_mods]        int64 counts (device)
+ * ------------------------------------------------------------------------ */
+enum { DAGR_FLOPS_ZERO = 0, DAGR_FLOPS_CONV = 1, DAGR_FLOPS_LINEAR = 2, DAGR_FLOPS_POOL = 3, DAGR_FLOPS_CARTESIAN = 4 };
+typedef struct dagr_flops_module {
+    int32_t kind, level, cin, cout, root, bias;
+} dagr_flops_module;
+int dagr_async_flops(const int32_t *deg, int32_t n_events, const int32_t *counts1, const int32_t *counts2,
+                     const int32_t *counts3, const int32_t *counts4, const dagr_flops_module *mods, int32_t n_mods,
+                     int64_t *out, void *stream);
+
 /* Host-side helper: first n offsets of the search spiral (spiral.h:1-15), the closed form the
  * search kernel uses.  dx/dy are HOST arrays.  Lets CPU-only tests pin the visiting order. */
 int dagr_spiral_offsets(int32_t n, int32_t *dx_host, int32_t *dy_host);
