@@ -85,10 +85,15 @@ __global__ __launch_bounds__(kBlock) void k_tap_aggregate(
 // gx[src] += sum_{taps of the edge} basis * gA[dst][tap], plus the root copy gx[n] += gA[n][25 cin + .].
 // One wave per destination node, lanes stride the channels.  The scatter is DETERMINISTIC: contributions are added as
 // 64-bit fixed-point integers (integer addition is associative, so the order in which the atomics land does not
-// matter), scaled by 2^50 / max|gA| -- every contribution is a convex combination of gA entries, so |term| <= max|gA|,
-// a node has far fewer than 2^12 out-edges, and the resolution max|gA| * 2^-50 is 2^-26 of an fp32 ulp at the
-// tensor's own scale.  k_fixed_to_float turns the sums into fp32.  acc must be zero-initialised by the caller.
-constexpr double kFixedOne = 1125899906842624.0;     // 2^50
+// matter), in units of max|gA| (E + 1) / 2^62 with E = rowptr[n_nodes] the graph's edge count.  Every contribution is a
+// convex combination of gA entries, so |term| <= max|gA|, and a node's sum has at most E + 1 terms (its out-edges and its
+// root copy): it stays below 2^62 for every CSR, however many out-edges one node has (a hot spot gives a single level-0
+// node more than 10^4; a fixed 2^50 / max|gA| scale wrapped past 2^13 of them).  The scale is read on the device (no
+// host sync); at E = 2^23 (a 400 k-event step) the resolution is about 2^-16 of an fp32 ulp at max|gA|.  k_fixed_to_float
+// turns the sums into fp32 with the same unit.  acc must be zero-initialised by the caller.
+__device__ inline double fixed_unit(float amax, const int32_t *__restrict__ rowptr, int n_nodes) {
+    return (double)amax * ((double)rowptr[n_nodes] + 1.0) * 0x1p-62;
+}
 
 template <int LPN>      // lanes per node, as k_tap_aggregate
 __global__ __launch_bounds__(kBlock) void k_tap_scatter_grad(const int32_t *__restrict__ n_nodes_ptr, int n_nodes_max,
@@ -104,8 +109,8 @@ __global__ __launch_bounds__(kBlock) void k_tap_scatter_grad(const int32_t *__re
     const int n = blockIdx.x * (kAggWaves * NPW) + threadIdx.x / LPN;
     const int n_nodes = n_nodes_ptr ? min(*n_nodes_ptr, n_nodes_max) : n_nodes_max;
     if (n >= n_nodes) return;
-    const float m = *amax;
-    const double scale = m > 0.0f ? kFixedOne / (double)m : 0.0;
+    const double unit = fixed_unit(*amax, rowptr, n_nodes);
+    const double scale = unit > 0.0 ? 1.0 / unit : 0.0;
     auto add = [&](size_t at, float v) {
         atomicAdd(reinterpret_cast<unsigned long long *>(acc + at), (unsigned long long)__double2ll_rn((double)v * scale));
     };
@@ -172,8 +177,8 @@ __global__ __launch_bounds__(kBlock) void k_tap_scatter_grad_w(const int32_t *__
     }
     __syncthreads();
     if (!active) return;
-    const float m = *amax;
-    const double scale = m > 0.0f ? kFixedOne / (double)m : 0.0;
+    const double unit = fixed_unit(*amax, rowptr, n_nodes);
+    const double scale = unit > 0.0 ? 1.0 / unit : 0.0;
     auto add = [&](size_t at, float v) {
         atomicAdd(reinterpret_cast<unsigned long long *>(acc + at), (unsigned long long)__double2ll_rn((double)v * scale));
     };
@@ -195,6 +200,7 @@ __global__ __launch_bounds__(kBlock) void k_tap_scatter_grad_w(const int32_t *__
 }
 
 __global__ __launch_bounds__(kBlock) void k_fixed_to_float(const int32_t *__restrict__ n_nodes_ptr, int n_nodes_max, int cin,
+                                                          const int32_t *__restrict__ rowptr,
                                                           const float *__restrict__ amax,
                                                           const long long *__restrict__ acc, float *__restrict__ gx,
                                                           int ldg) {
@@ -202,7 +208,7 @@ __global__ __launch_bounds__(kBlock) void k_fixed_to_float(const int32_t *__rest
     const int n_nodes = n_nodes_ptr ? min(*n_nodes_ptr, n_nodes_max) : n_nodes_max;
     if (i >= (int64_t)n_nodes * cin) return;
     const int n = (int)(i / cin), c = (int)(i - (int64_t)n * cin);
-    gx[(size_t)n * ldg + c] = (float)((double)acc[i] * ((double)*amax / kFixedOne));
+    gx[(size_t)n * ldg + c] = (float)((double)acc[i] * fixed_unit(*amax, rowptr, n_nodes));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -576,7 +582,7 @@ int dagr_spline_tap_scatter_grad(const int32_t *n_nodes_ptr, int32_t n_nodes_max
             (long long *)acc);
     DAGR_CHECK_LAUNCH();
     k_fixed_to_float<<<(unsigned)ceil_div((int64_t)n_nodes_max * cin, kBlock), kBlock, 0, (hipStream_t)stream>>>(
-        n_nodes_ptr, n_nodes_max, cin, grad_A_absmax, (const long long *)acc, grad_x, ldg);
+        n_nodes_ptr, n_nodes_max, cin, rowptr, grad_A_absmax, (const long long *)acc, grad_x, ldg);
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
 }
@@ -597,7 +603,7 @@ int dagr_spline_tap_scatter_grad_w(const int32_t *n_nodes_ptr, int32_t n_nodes_m
         (long long *)acc);
     DAGR_CHECK_LAUNCH();
     k_fixed_to_float<<<(unsigned)ceil_div((int64_t)n_nodes_max * cin, kBlock), kBlock, 0, (hipStream_t)stream>>>(
-        n_nodes_ptr, n_nodes_max, cin, grad_A_bound, (const long long *)acc, grad_x, ldgx);
+        n_nodes_ptr, n_nodes_max, cin, rowptr, grad_A_bound, (const long long *)acc, grad_x, ldgx);
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
 }

@@ -52,8 +52,13 @@ def resolve_config(config):
 
 
 def model_args(name="dagr-s", **over):
-    """Namespace equivalent to ``FLAGS()`` with ``--config config/<name>-dsec.yaml``: every key of that file."""
-    path = name if str(name).endswith((".yaml", ".yml")) else CONFIG_DIR / f"{name}-dsec.yaml"
+    """Namespace equivalent to ``FLAGS()`` with ``--config config/<name>.yaml`` when that file exists (``dagr-l-ncaltech``),
+    else ``config/<name>-dsec.yaml`` (``dagr-s``): every key of that file."""
+    path = name
+    if not str(name).endswith((".yaml", ".yml")):
+        path = CONFIG_DIR / f"{name}.yaml"
+        if not path.is_file():
+            path = CONFIG_DIR / f"{name}-dsec.yaml"
     cfg = dict(_load_yaml(resolve_config(path)), use_image=False, no_events=False, pretrain_cnn=False,
                keep_temporal_ordering=False)
     cfg.pop("dataset_directory", None)

@@ -260,9 +260,10 @@ int dagr_spline_tap_aggregate(const int32_t *n_nodes_ptr, int32_t n_nodes_max, c
                               int32_t rx, int32_t ry, float den_x, float den_y,
                               float *A, int32_t lda, void *stream);
 /* backward of step 1 w.r.t. x (training path): grad_x[src] = sum over its out-edges of basis * grad_A[dst][tap], plus
- * grad_A[n][25 cin ..] (root copy).  Deterministic: the scatter adds 64-bit fixed-point integers (scale 2^50 /
- * *grad_A_absmax, a device scalar >= max |grad_A|; acc int64[n_nodes_max * cin], zeroed by the caller), so the result
- * does not depend on the order in which the atomics land; grad_x is overwritten.  The weight gradient of the
+ * grad_A[n][25 cin ..] (root copy).  Deterministic: the scatter adds 64-bit fixed-point integers (unit *grad_A_absmax *
+ * (E + 1) / 2^62 with E = rowptr[n_nodes] -- no sum can wrap, whatever a node's out-degree; *grad_A_absmax is a device
+ * scalar >= max |grad_A|; acc int64[n_nodes_max * cin], zeroed by the caller), so the result does not depend on the
+ * order in which the atomics land; grad_x is overwritten.  The weight gradient of the
  * contraction is a plain GEMM (A^T . grad_out) on the A matrix of dagr_spline_tap_aggregate. */
 int dagr_spline_tap_scatter_grad(const int32_t *n_nodes_ptr, int32_t n_nodes_max, const int32_t *rowptr,
                                  const int32_t *col, const int32_t *code, const float *grad_A, int32_t lda, int32_t cin,

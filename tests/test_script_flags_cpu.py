@@ -84,6 +84,24 @@ def test_short_names_and_defaults_still_work():
         C.flags("", ["--config", "config/no-such.yaml"])
 
 
+def test_model_args_short_names_resolve_to_the_shipped_files():
+    """``model_args(<name>)``: ``config/<name>.yaml`` when it exists (dagr-l-ncaltech), else ``config/<name>-dsec.yaml``;
+    every key of the file, the caller's overrides on top."""
+    from dagr_amd.utils.args import model_args
+    for name, path in (("dagr-l-ncaltech", "dagr-l-ncaltech.yaml"), ("dagr-s", "dagr-s-dsec.yaml"),
+                       ("dagr-l", "dagr-l-dsec.yaml"), ("config/dagr-l-ncaltech.yaml", "dagr-l-ncaltech.yaml")):
+        cfg = yaml.safe_load(open(os.path.join(ROOT, "config", path)))
+        a = vars(model_args(name, batch_size=3))
+        assert a["batch_size"] == 3 and not a["use_image"], name
+        for k, v in cfg.items():
+            if k not in ("batch_size", "dataset_directory", "output_directory"):
+                assert a[k] == v, (name, k, a[k], v)
+    a = model_args("dagr-l-ncaltech")
+    assert (a.dataset, a.num_scales, a.net_stem_width, a.yolo_stem_width) == ("ncaltech101", 1, 1, 1)
+    with pytest.raises(FileNotFoundError):
+        model_args("dagr-x")
+
+
 def test_yaml_keys_reach_the_model(tmp_path):
     """``DAGR(args, ...)`` is built from the parsed namespace: a YAML with different radius / max_neighbors / num_scales /
     pooling_dim_at_output / widths changes the model accordingly (constructor only: no GPU work)."""

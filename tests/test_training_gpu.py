@@ -36,11 +36,12 @@ def _graph(W, H, B, n, seed):
     return pos, torch.from_numpy(b.astype(np.int64)), ei
 
 
+@pytest.mark.parametrize("C", [8, 64, 128])
 @pytest.mark.parametrize("aggr", ["max", "mean"])
-def test_pooling_backward_matches_scatter_autograd(aggr):
+def test_pooling_backward_matches_scatter_autograd(aggr, C):
     from dagr_amd.model.layers.components import Cartesian
     from dagr_amd.model.layers.pooling import Pooling
-    W, H, B, C = 240, 180, 2, 8
+    W, H, B = 240, 180, 2
     pos, batch, ei = _graph(W, H, B, 1500, seed=11)
     size = torch.tensor([1 / 14.0, 1 / 10.0, 1.0])
     cart_max = float(2 * size[:2].max())
@@ -61,9 +62,113 @@ def test_pooling_backward_matches_scatter_autograd(aggr):
     assert _rel(xh.grad, xo.grad) < 1e-5
 
 
-def test_to_dense_backward_gathers_every_written_row():
+def _quantised(n, C, seed):
+    """Features on {-2, ..., 2}: ties at every nonzero level, and zeros of both signs (-0.0 == +0.0)."""
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.randint(-2, 3, (n, C), generator=gen).float()
+    neg = (x == 0) & (torch.rand((n, C), generator=gen) < 0.5)
+    x[neg] = -0.0
+    assert bool(torch.signbit(x[x == 0]).any()) and not bool(torch.signbit(x[x == 0]).all())
+    return x
+
+
+def _pool_grad_by_hand(x, cluster, nc, g, aggr):
+    """torch_scatter's gradients, written out: max hands the whole (cluster, channel) gradient to the LOWEST node index among
+    the members equal to the maximum (scatter_max's arg; ``scatter_reduce("amax")`` would split a tie evenly); mean
+    divides it by the member count; nodes outside the grid (cluster -1) get exactly 0."""
+    n, C = x.shape
+    inside = cluster >= 0
+    c = torch.where(inside, cluster, torch.zeros_like(cluster)).long()
+    gx = torch.zeros((n, C))
+    if aggr == "max":
+        top = torch.full((nc, C), float("-inf")).scatter_reduce(0, c[inside].view(-1, 1).expand(-1, C), x[inside], "amax")
+        at_top = (x == top[c]) & inside.view(-1, 1)
+        node = torch.arange(n).view(-1, 1).expand(-1, C)
+        first = torch.full((nc, C), n).scatter_reduce(0, c.view(-1, 1).expand(-1, C), torch.where(at_top, node, n), "amin")
+        win = (first[c] == node) & inside.view(-1, 1)
+        gx[win] = g[c][win]
+    else:
+        count = torch.bincount(c[inside], minlength=nc).float()
+        gx[inside] = g[c[inside]] / count[c[inside]].view(-1, 1)
+    return gx
+
+
+@pytest.mark.parametrize("aggr", ["max", "mean"])
+def test_pool_feature_backward_routes_ties_to_the_lowest_member(aggr):
+    """``PoolFeatFn`` directly, at C = 128 on quantised features: nonzero ties everywhere, -0.0 next to +0.0, nodes outside
+    the grid, single-member clusters."""
+    from dagr_amd.model.layers.autograd import PoolFeatFn
+    n, C, ngroups, nsingle = 3000, 128, 150, 40
+    rng = np.random.default_rng(8)
+    raw = rng.integers(0, ngroups, n)
+    raw[rng.choice(n, nsingle, replace=False)] = ngroups + np.arange(nsingle)          # clusters of one node
+    raw[rng.random(n) < 0.1] = -1                                                      # outside the grid
+    ids, inv = np.unique(raw[raw >= 0], return_inverse=True)
+    cluster = np.full(n, -1, np.int64)
+    cluster[raw >= 0] = inv
+    nc = len(ids)
+    cluster = torch.from_numpy(cluster)
+    counts = torch.bincount(cluster[cluster >= 0], minlength=nc)
+    assert int((cluster < 0).sum()) > 0 and int((counts == 1).sum()) >= 20
+    x = _quantised(n, C, seed=8)
+    inside = cluster >= 0
+    c = cluster[inside].view(-1, 1).expand(-1, C)
+    if aggr == "max":
+        pooled = torch.full((nc, C), float("-inf")).scatter_reduce(0, c, x[inside], "amax")
+    else:
+        pooled = torch.zeros((nc, C)).index_add(0, cluster[inside], x[inside]) / counts.view(-1, 1).float()
+
+    class Holder:
+        pass
+    holder = Holder()
+    holder.pooled = pooled.cuda()
+    g = torch.from_numpy(rng.standard_normal((nc, C)).astype(np.float32))
+    xh = x.cuda().requires_grad_(True)
+    out = PoolFeatFn.apply(xh, cluster.int().cuda(), 0 if aggr == "max" else 1, holder)
+    (out * g.cuda()).sum().backward()
+    want = _pool_grad_by_hand(x, cluster, nc, g, aggr)
+    got = xh.grad.cpu()
+    assert torch.equal(got[~inside], torch.zeros_like(got[~inside])) and not bool(torch.signbit(got[~inside]).any())
+    if aggr == "max":
+        assert torch.equal(got, want)
+        # every (cluster, channel) gradient lands once, whole
+        assert torch.equal(torch.zeros((nc, C)).index_add(0, cluster[inside], got[inside]), g)
+    else:
+        assert torch.allclose(got, want, rtol=1e-6, atol=0)
+
+
+@pytest.mark.parametrize("aggr", ["max", "mean"])
+def test_pooling_backward_on_tied_features(aggr):
+    """The same rule through ``Pooling`` (graph, voxel grid and cluster order of the pooling kernels) at C = 64."""
+    from dagr_amd.model.layers.components import Cartesian
+    from dagr_amd.model.layers.pooling import Pooling
+    W, H, B, C = 240, 180, 2, 64
+    pos, batch, ei = _graph(W, H, B, 1500, seed=12)
+    size = torch.tensor([1 / 14.0, 1 / 10.0, 1.0])
+    cart_max = float(2 * size[:2].max())
+    pool = Pooling(size, width=W, height=H, batch_size=B, transform=Cartesian(True, False, cart_max), aggr=aggr).cuda()
+    x = _quantised(len(pos), C, seed=12)
+    pp = oo.PoolingParams(size, W, H, B, cart_max, aggr=aggr)
+    x_ref = oo.pooling(pp, x, pos, batch, ei, exact_mean=True)[0]
+    _, cluster, _, _ = oo.consecutive_cluster(oo.grid_cluster(torch.cat([pos, batch.float().view(-1, 1)], -1),
+                                                              pp.voxel_size, pp.start, pp.end))
+    nc = x_ref.shape[0]
+    assert int(torch.bincount(cluster, minlength=nc).max()) > 5            # many-member voxels: ties at every level
+    g = torch.randn((nc, C), generator=torch.Generator().manual_seed(13))
+    xh = x.clone().cuda().requires_grad_(True)
+    out = pool(Data(x=xh, pos=pos.cuda(), batch=batch.cuda(), edge_index=ei.cuda()))
+    assert out.x.shape == x_ref.shape and _rel(out.x, x_ref) < 1e-6
+    (out.x * g.cuda()).sum().backward()
+    want = _pool_grad_by_hand(x, cluster, nc, g, aggr)
+    if aggr == "max":
+        assert torch.equal(xh.grad.cpu(), want)
+    else:
+        assert torch.allclose(xh.grad.cpu(), want, rtol=1e-6, atol=0)
+
+
+@pytest.mark.parametrize("B,C", [(2, 5), (3, 1), (3, 4), (3, 100)])     # 1 / 4 / 100: obj / reg / cls of dagr-l-ncaltech
+def test_to_dense_backward_gathers_every_written_row(B, C):
     from dagr_amd.model.layers import _ops
-    B, C = 2, 5
     pooling = torch.tensor([1 / 7.0, 1 / 5.0, 1.0])
     torch.manual_seed(5)
     cells = torch.randperm(35 * B)[:40]
@@ -85,10 +190,14 @@ def test_to_dense_backward_gathers_every_written_row():
     assert torch.equal(xh.grad[:3], xh.grad[40:43]) and float(xh.grad[:3].abs().sum()) > 0
 
 
-def _training_case(W, H, B, n, seed, **over):
+def _training_case(W, H, B, n, seed, config=None, **over):
+    """A randomised model in training mode and B synthetic samples with boxes of every class the model knows.  ``config``:
+    a shipped configuration read by the product's loader (``model_args``); default: the dagr-s network keys."""
     from dagr_amd.model.networks.dagr import DAGR
+    from dagr_amd.utils.args import model_args
     torch.manual_seed(seed)
-    args = om.default_args(batch_size=B, **over)
+    args = model_args(config, batch_size=B, **over) if config else om.default_args(batch_size=B, **over)
+    num_classes = om.NetConstants(args, H, W).num_classes
     model = randomize_(DAGR(args, height=H, width=W), seed=seed)
     sd = {k: (v.detach().clone().requires_grad_(True) if v.is_floating_point() and "running" not in k
               else v.detach().clone()) for k, v in model.state_dict().items()}
@@ -101,7 +210,7 @@ def _training_case(W, H, B, n, seed, **over):
         raw.append((x, y, t, p))
         nb = 1 + s % 2
         boxes = np.stack([rng.uniform(5, W / 2, nb), rng.uniform(5, H / 2, nb), rng.uniform(20, W / 3, nb),
-                          rng.uniform(20, H / 3, nb), rng.integers(0, 2, nb), np.ones(nb), np.zeros(nb)], 1)
+                          rng.uniform(20, H / 3, nb), rng.integers(0, num_classes, nb), np.ones(nb), np.zeros(nb)], 1)
         samples.append(Data(x=torch.from_numpy(p.reshape(-1, 1)), pos=torch.from_numpy(np.stack([x, y], -1)),
                             t=torch.from_numpy(t), width=W, height=H, time_window=1000000,
                             bbox=torch.from_numpy(boxes.astype(np.float32)), sequence=f"s{s}"))
@@ -112,12 +221,18 @@ def _training_case(W, H, B, n, seed, **over):
 
 
 @pytest.mark.parametrize("case", [dict(W=240, H=180, B=2, n=2500, seed=1),
-                                  dict(W=320, H=215, B=3, n=1500, seed=2, over=dict(num_scales=1))],
-                         ids=["two_scales", "one_scale"])
+                                  dict(W=320, H=215, B=3, n=1500, seed=2, over=dict(num_scales=1)),
+                                  # BASELINE config 5: dagr-l widths (128 channels), one scale, 100 classes
+                                  dict(W=240, H=180, B=3, n=2500, seed=7, config="dagr-l-ncaltech", min_checked=70)],
+                         ids=["two_scales", "one_scale", "dagr_l_ncaltech"])
 def test_training_loss_and_gradients_match_the_oracle(case):
     from oracle import train as otr
     W, H, B = case["W"], case["H"], case["B"]
-    args, model, sd, batch, ev, b = _training_case(W, H, B, case["n"], case["seed"], **case.get("over", {}))
+    args, model, sd, batch, ev, b = _training_case(W, H, B, case["n"], case["seed"], config=case.get("config"),
+                                                   **case.get("over", {}))
+    if case.get("config") == "dagr-l-ncaltech":
+        assert (args.net_stem_width, args.num_scales, args.dataset) == (1, 1, "ncaltech101")
+        assert len(set(batch.bbox[:, 4].long().tolist())) > 2          # classes beyond 0 / 1
     # the oracle's training forward is pinned to the reference's own training branch (tests/test_oracle_refpy.py)
     ref = otr.training_losses(sd, args, H, W, ev[0], ev[1], ev[2], ev[3], b, B, batch.bbox, batch.bbox_batch)
     ref[0].backward()
@@ -137,7 +252,7 @@ def test_training_loss_and_gradients_match_the_oracle(case):
         assert gh is not None, f"no gradient reached {k}"
         errs.append((_rel(gh, v.grad), k))
         checked += 1
-    assert checked >= 60
+    assert checked >= case.get("min_checked", 60)
     # every tensor within 2e-3 of its own scale (typically 1e-5); the backward is deterministic (fixed-point scatter in
     # dagr_spline_tap_scatter_grad, gathers everywhere else), so this does not depend on the run
     errs.sort()
@@ -147,11 +262,13 @@ def test_training_loss_and_gradients_match_the_oracle(case):
     assert int(bn.num_batches_tracked) == 1 and float(bn.running_mean.abs().sum()) > 0
 
 
-def test_training_backward_is_deterministic():
+@pytest.mark.parametrize("config", [None, "dagr-l-ncaltech"], ids=["dagr_s", "dagr_l_ncaltech"])
+def test_training_backward_is_deterministic(config):
     """Two forward + backward passes over the same batch give bit-identical losses and gradients: the SplineConv input
-    gradient is a fixed-point scatter (integer atomics: order-free), pooling / to_dense backwards are gathers."""
+    gradient is a fixed-point scatter (integer atomics: order-free), pooling / to_dense backwards are gathers.  dagr-l:
+    the 128-channel convs scatter through k_tap_scatter_grad<64>."""
     W, H, B = 240, 180, 2
-    args, model, _, batch, _, _ = _training_case(W, H, B, 3000, seed=6)
+    args, model, _, batch, _, _ = _training_case(W, H, B, 3000, seed=6, config=config)
     snaps = []
     for _ in range(2):
         model.zero_grad(set_to_none=True)
@@ -253,9 +370,11 @@ def test_a_few_optimizer_steps_reduce_the_loss():
     assert all(np.isfinite(losses)) and losses[-1] < losses[0], losses
 
 
-def test_train_script_on_the_hip_layers_then_evaluate_the_checkpoint(tmp_path):
-    """scripts/train_ncaltech101.py for a few iterations on SyntheticObjects (dagr-s widths, one scale), then the
-    checkpoint's ``ema`` state into a fresh model and an eval-mode forward through the window engine (run_test.py:54-62)."""
+@pytest.mark.parametrize("config", ["dagr-s", "config/dagr-l-ncaltech.yaml"], ids=["dagr_s", "dagr_l_ncaltech"])
+def test_train_script_on_the_hip_layers_then_evaluate_the_checkpoint(tmp_path, config):
+    """scripts/train_ncaltech101.py for a few iterations on SyntheticObjects (dagr-s widths or the shipped dagr-l-ncaltech
+    configuration, one scale), then the checkpoint's ``ema`` state into a fresh model and an eval-mode forward through the
+    window engine (run_test.py:54-62)."""
     import os
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -267,7 +386,7 @@ def test_train_script_on_the_hip_layers_then_evaluate_the_checkpoint(tmp_path):
     from dagr_amd.data.synthetic_data import SyntheticObjects
     from dagr_amd.model.networks.dagr import DAGR
     from dagr_amd.model.networks.ema import ModelEMA
-    out_dir, log = T.main(["--config", "dagr-s", "--epochs", "1", "--samples", "12", "--val_samples", "4", "--batch_size", "4",
+    out_dir, log = T.main(["--config", config, "--epochs", "1", "--samples", "12", "--val_samples", "4", "--batch_size", "4",
                            "--n_nodes", "3000", "--output_directory", str(tmp_path), "--l_r", "0.002"])
     assert len(log) == 3 and all(np.isfinite(r["loss"]) for r in log)
     state = torch.load(out_dir / "last_model.pth", weights_only=False)
