@@ -24,7 +24,7 @@ class PoolDesc(ctypes.Structure):
     _fields_ = [("batch_size", c_i32), ("channels", c_i32), ("gx", c_i32), ("gy", c_i32), ("vx", c_float),
                 ("vy", c_float), ("inv_w", c_float), ("inv_h", c_float), ("two_max", c_float), ("r00", c_float),
                 ("r02", c_float), ("r11", c_float), ("r12", c_float), ("rx", c_i32), ("ry", c_i32), ("aggr", c_i32),
-                ("append_pos", c_i32)]
+                ("append_pos", c_i32), ("keep_order", c_i32)]
 
 
 class GraphDesc(ctypes.Structure):

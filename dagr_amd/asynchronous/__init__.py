@@ -36,9 +36,9 @@ def make_model_asynchronous(module, log_flops=False):
     if log_flops:
         if type(module).__name__ != "DAGR" or not hasattr(module, "engine"):
             raise NotImplementedError("log_flops counts the modules of a DAGR model (asynchronous/flops)")
-        if getattr(module, "module_path_only", False):
-            raise NotImplementedError("log_flops with --keep_temporal_ordering: that model runs module by module, "
-                                      "without the window engine whose level counts are read")
+        if getattr(getattr(module, "args", None), "keep_temporal_ordering", False):
+            raise NotImplementedError("log_flops with --keep_temporal_ordering: the FLOP count of a model whose coarse "
+                                      "edges are filtered is not implemented")
         from .flops import logged_modules
         for _, m, _ in logged_modules(module):
             m.asy_flops_log = []

@@ -27,6 +27,9 @@ struct PoolWs {
     unsigned long long *nbmask;  // [T] level 0: 5x5 bitmaps of source cells, zero between calls: bits 0-24 cells of the
                                  // slot's own sample plane, bits 32-56 cells of the plane below (sources of the slot's
                                  // t == 1.0 members, QUIRK-1)
+    // keep_order = 1 only (NULL otherwise; carved after everything above, so the layout of the rest does not change):
+    int32_t *tmax;       // [T] enc_f of the largest pos[:, 2] of the slot's members, kEncMin = empty
+    unsigned long long *nbmask_f;   // [T] level 0: nbmask without the sources whose tmax is not below the slot's
     int T;
 };
 
@@ -51,6 +54,12 @@ __host__ __device__ inline size_t pool_carve(const dagr_pool_desc &d, char *base
     w.status = (int32_t *)take(32);
     w.tile_state = (unsigned long long *)take(((T + 1 + kPoolScanTile - 1) / kPoolScanTile + 8) * 8);
     w.nbmask = (unsigned long long *)take((T + 9) * 8);
+    w.tmax = nullptr;
+    w.nbmask_f = nullptr;
+    if (d.keep_order) {
+        w.tmax = (int32_t *)take((T + 32) * 4);
+        w.nbmask_f = (unsigned long long *)take((T + 9) * 8);
+    }
     w.T = (int)T;
     if (ws) *ws = w;
     return off;
@@ -111,6 +120,7 @@ __device__ __forceinline__ void pool_merge_node(const dagr_pool_desc &d, const P
         ws.occupied[raw] = 1;
         atomicAdd(&ws_cnt(ws, pair)[raw], 1);
         atomicMax(&ws.perm[raw], n);
+        if (ws.tmax) atomicMax(&ws.tmax[raw], enc_f(pos[3 * n + 2]));   // keep_order: the cluster's newest member
 #pragma unroll
         for (int k = 0; k < 3; k++)
             atomicAdd(reinterpret_cast<unsigned long long *>(ws_possum(ws, pair) + (size_t)raw * 3 + k),

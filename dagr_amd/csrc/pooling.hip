@@ -110,16 +110,19 @@ __global__ __launch_bounds__(kBlock) void k_pool_accumulate(dagr_pool_desc d, co
 constexpr int kPoolL0Block = 1024;
 
 template <int AGGR>
-__host__ __device__ inline size_t pool_l0_lds_bytes(int VW, int C, int W, int H) {
+__host__ __device__ inline size_t pool_l0_lds_bytes(int VW, int C, int W, int H, bool ord = false) {
     size_t b = ((size_t)VW * C * (AGGR == 0 ? 4 : 8) + 7) / 8 * 8;   // feature accumulators
     b += (size_t)VW * (24 + 4 + 4 + 4);                                 // position sums, count, largest id, bitmap
     b += (kPoolL0Block / 64) * 64 * 2;                                  // per wave: window slot of the step's nodes
     b += ((size_t)(W + H) * 2 + 7) / 8 * 8;                             // pixel -> voxel column / row
+    if (ord) b += (size_t)VW * 4;                                       // keep_order: newest member (enc_f of t)
     return b + 64;
 }
 
-template <int AGGR, int VEC>   // 0 = max, 1 = mean; VEC = floats per piece (4: rows are 16-byte aligned, 1: any layout)
-__global__ __launch_bounds__(kPoolL0Block) void k_pool_l0_slots(dagr_pool_desc d, int W, int H, int n_cap, int VW,
+// ORD (keep_order = 1): the window also keeps every slot's t_max (LDS max of enc_f(t)), merged like the other words; the
+// two forms are separate kernels (k_pool_l0_slots / k_pool_l0_slots_ord below) around this one body
+template <int AGGR, int VEC, bool ORD>   // 0 = max, 1 = mean; VEC = floats per piece (4: rows are 16-byte aligned, 1: any layout)
+__device__ __forceinline__ void pool_l0_slots_body(dagr_pool_desc d, int W, int H, int n_cap, int VW,
                                                                const int32_t *__restrict__ n_ptr,
                                                                const int32_t *__restrict__ xlo,  // [gx+1] pixel bounds
                                                                const int32_t *__restrict__ ylo,  // [gy+1]
@@ -144,6 +147,7 @@ __global__ __launch_bounds__(kPoolL0Block) void k_pool_l0_slots(dagr_pool_desc d
     const int C = d.channels;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int *l_acc; unsigned long long *l_ps; int *l_cnt, *l_perm; unsigned *l_nbm; short *l_sv; unsigned short *l_xlut, *l_ylut;
+    int *l_tmax = nullptr;
     {
         unsigned char *p = lds_raw;
         l_acc = reinterpret_cast<int *>(p); p += ((size_t)VW * C * (AGGR == 0 ? 4 : 8) + 7) / 8 * 8;
@@ -154,6 +158,7 @@ __global__ __launch_bounds__(kPoolL0Block) void k_pool_l0_slots(dagr_pool_desc d
         l_sv = reinterpret_cast<short *>(p); p += NW * 64 * 2;
         l_xlut = reinterpret_cast<unsigned short *>(p); p += (size_t)W * 2;
         l_ylut = reinterpret_cast<unsigned short *>(p);
+        if (ORD) l_tmax = reinterpret_cast<int *>(l_xlut + ((size_t)(W + H) * 2 + 7) / 8 * 4);
     }
     auto arm_window = [&]() {
         for (int i = threadIdx.x; i < VW * C; i += kPoolL0Block) {
@@ -162,6 +167,7 @@ __global__ __launch_bounds__(kPoolL0Block) void k_pool_l0_slots(dagr_pool_desc d
         }
         for (int i = threadIdx.x; i < VW; i += kPoolL0Block) {
             l_cnt[i] = 0; l_perm[i] = -1; l_nbm[i] = 0u;
+            if (ORD) l_tmax[i] = kEncMin;
             l_ps[3 * i] = 0ull; l_ps[3 * i + 1] = 0ull; l_ps[3 * i + 2] = 0ull;
         }
     };
@@ -256,6 +262,10 @@ __global__ __launch_bounds__(kPoolL0Block) void k_pool_l0_slots(dagr_pool_desc d
             const unsigned long long q0 = (unsigned long long)(long long)llrint((double)px * kPosScale);
             const unsigned long long q1 = (unsigned long long)(long long)llrint((double)py * kPosScale);
             const unsigned long long q2 = (unsigned long long)(long long)llrint((double)pt * kPosScale);
+            if (ORD) {     // keep_order: t_max here, so that t is not held through the bitmap below
+                if (inwin) atomicMax(&l_tmax[rel], enc_f(pt));
+                else atomicMax(&ws.tmax[leak ? raw + cells : raw], enc_f(pt));
+            }
             // source cells of the node's in-edges: a source lies within r pixels of its destination, r <= 2 cells (checked
             // by the caller), so they form a 5x5 bitmap around the node's voxel.  Lower pixel bounds of the cells
             // cx-1 .. cx+2 (and rows): the source's cell = cx-2 + #(bounds <= its pixel).
@@ -389,6 +399,7 @@ __global__ __launch_bounds__(kPoolL0Block) void k_pool_l0_slots(dagr_pool_desc d
             atomicAdd(reinterpret_cast<unsigned long long *>(w_possum + (size_t)raw * 3 + 1), l_ps[3 * v + 1]);
             atomicAdd(reinterpret_cast<unsigned long long *>(w_possum + (size_t)raw * 3 + 2), l_ps[3 * v + 2]);
             if (l_nbm[v]) atomicOr(&ws.nbmask[raw], (unsigned long long)l_nbm[v]);
+            if (ORD) atomicMax(&ws.tmax[raw], l_tmax[v]);
         }
     }
     seg_begin = seg_end;
@@ -406,6 +417,21 @@ __global__ __launch_bounds__(kPoolL0Block) void k_pool_l0_slots(dagr_pool_desc d
         if (lane == 0 && tot) atomicAdd(&ws.status[5], tot);
     }
 }
+
+#define DAGR_POOL_L0_SLOTS_KERNEL(NAME, ORD)                                                                          \
+    template <int AGGR, int VEC>                                                                                       \
+    __global__ __launch_bounds__(kPoolL0Block) void NAME(                                                              \
+        dagr_pool_desc d, int W, int H, int n_cap, int VW, const int32_t *__restrict__ n_ptr,                          \
+        const int32_t *__restrict__ xlo, const int32_t *__restrict__ ylo, const int32_t *__restrict__ start, int row_keys, \
+        const int2 *__restrict__ slot_it, const int32_t *__restrict__ slot_xyb, const float *__restrict__ x, int ldx,   \
+        const float *__restrict__ pos, PoolWs ws, const int16_t *__restrict__ nbr_code,                                \
+        const int32_t *__restrict__ nbr_src, const int32_t *__restrict__ deg, int K, int r) {                          \
+        pool_l0_slots_body<AGGR, VEC, ORD>(d, W, H, n_cap, VW, n_ptr, xlo, ylo, start, row_keys, slot_it, slot_xyb, x, \
+                                           ldx, pos, ws, nbr_code, nbr_src, deg, K, r);                                \
+    }
+DAGR_POOL_L0_SLOTS_KERNEL(k_pool_l0_slots, false)
+DAGR_POOL_L0_SLOTS_KERNEL(k_pool_l0_slots_ord, true)
+#undef DAGR_POOL_L0_SLOTS_KERNEL
 
 // level 0: cluster of every event (for the coarse edges)
 __global__ __launch_bounds__(kBlock) void k_pool_l0_event_cluster(dagr_pool_desc d, int N,
@@ -494,6 +520,7 @@ __global__ __launch_bounds__(kBlock) void k_pool_rearm(int T, PoolWs ws) {
     ws_cnt(ws, ws_pair(ws))[raw] = 0;
     ws.perm[raw] = -1;
     ws.nbmask[raw] = 0ull;
+    if (ws.tmax) ws.tmax[raw] = kEncMin;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -505,7 +532,7 @@ __global__ __launch_bounds__(kBlock) void k_coarse_edges_ell(int N, int K, const
                                                             const int32_t *__restrict__ deg,
                                                             const int32_t *__restrict__ cluster_raw_in,
                                                             const int32_t *__restrict__ newid, int32_t *rows,
-                                                            int32_t *status) {
+                                                            int32_t *status, const int32_t *__restrict__ tmax) {
     __shared__ unsigned long long seen[256];
     seen[threadIdx.x] = ~0ull;
     __syncthreads();
@@ -526,6 +553,9 @@ __global__ __launch_bounds__(kBlock) void k_coarse_edges_ell(int N, int K, const
             rs = cluster_raw_in[nbr_src[(size_t)n * K + j]];
         }
         bool has = (rd != rs) && rd >= 0 && rs >= 0;
+        // keep_order: the accumulation launch before this one has completed every slot's t_max, so the filter applies
+        // at insertion and the generic path needs no launch of its own for it
+        if (tmax && has && !(tmax[rs] < tmax[rd])) has = false;
         const unsigned long long key = ((unsigned long long)(unsigned)rd << 32) | (unsigned)rs;
         const unsigned h = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 56);
         if (has && seen[h] == key) has = false;
@@ -811,7 +841,10 @@ __global__ __launch_bounds__(kBlock) void k_pool_emit(dagr_pool_desc d, PoolWs w
             x_out[(size_t)c * ldo + xoff + C] = p[0];
             x_out[(size_t)c * ldo + xoff + C + 1] = p[1];
         }
-        if (!KEEP) ws.perm[raw] = -1;
+        if (!KEEP) {
+            ws.perm[raw] = -1;
+            if (ws.tmax) ws.tmax[raw] = kEncMin;   // read only by the pruning launch before this one
+        }
     }
     // the slot's sources in ascending raw id (= ascending new id), one per lane
     int v = -1, rank = 0;
@@ -848,6 +881,50 @@ __global__ __launch_bounds__(kBlock) void k_pool_emit(dagr_pool_desc d, PoolWs w
     if (ix < 0 || ix > 2 * d.rx || iy < 0 || iy > 2 * d.ry) atomicOr(ws.status, 8);
     col[o] = ws.newid[v];
     code[o] = (ix & 0xffff) | (iy << 16);
+}
+
+// ---------------------------------------------------------------------------------------------
+// keep_order = 1 (--keep_temporal_ordering, pooling.py:69-72): launch (P) between (A) and (S) drops every coarse edge
+// src -> dst whose t_max[dst] > t_max[src] fails.  t_max is complete only when (A) has finished, hence a launch of its
+// own; (S) and (C) then see only the surviving sources (row sizes / bitmap populations, ranks) and are unchanged.
+// Level 0: one thread per table slot writes the filtered copy nbmask_f of its bitmap.  The copy leaves nbmask as it is
+// for KEEP (the resident bitmaps of the asynchronous mode receive later micro-batches); otherwise nbmask is cleared
+// here, as (C) would have done.
+template <bool KEEP>
+__global__ __launch_bounds__(kBlock) void k_pool_order_masks(dagr_pool_desc d, PoolWs ws) {
+    const int raw = blockIdx.x * kBlock + threadIdx.x;
+    if (raw >= ws.T) return;
+    const unsigned long long m = ws.nbmask[raw];
+    unsigned long long f = 0ull;
+    if (m) {
+        if (!KEEP) ws.nbmask[raw] = 0ull;
+        const int td = ws.tmax[raw];
+        const int cells = d.gx * d.gy;
+        for (unsigned long long r = m; r; r &= r - 1ull) {
+            const int bit = __ffsll((long long)r) - 1;
+            const int k = bit & 31;        // bits 0-24: cells of the slot's plane, 32-56: of the plane below (k_pool_emit)
+            const int v = raw + (k % 5 - 2) + d.gx * (k / 5 - 2) - (bit >= 32 ? cells : 0);
+            if (v >= 0 && v < ws.T && ws.tmax[v] < td) f |= 1ull << bit;
+        }
+    }
+    ws.nbmask_f[raw] = f;
+}
+
+// pooled levels: one wave per table slot; a failing source leaves the hashed set (-1, which (C)'s ranks skip) and the
+// slot's row size is recounted
+__global__ __launch_bounds__(kBlock) void k_pool_order_rows(PoolWs ws) {
+    const int lane = threadIdx.x & 63;
+    const int raw = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (raw >= ws.T || ws.rowcnt[raw] == 0) return;
+    int32_t *row = ws.rows + (size_t)raw * kRowSlots;
+    const int v = row[lane];
+    bool keep = v >= 0;
+    if (keep && !(ws.tmax[v] < ws.tmax[raw])) {
+        row[lane] = -1;
+        keep = false;
+    }
+    const int n = __popcll(__ballot(keep));
+    if (lane == 0) ws.rowcnt[raw] = n;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -890,6 +967,7 @@ __global__ __launch_bounds__(kBlock) void k_pool_l0_add_rows(dagr_pool_desc d, i
         ws.occupied[raw] = 1;
         atomicAdd(&ws_cnt(ws, pair)[raw], 1);
         atomicMax(&ws.perm[raw], ((b + 1) << 26) | s);
+        if (ws.tmax) atomicMax(&ws.tmax[raw], enc_f(pt));
         atomicAdd(reinterpret_cast<unsigned long long *>(ws_possum(ws, pair) + (size_t)raw * 3 + 0),
                   (unsigned long long)(long long)llrint((double)px * kPosScale));
         atomicAdd(reinterpret_cast<unsigned long long *>(ws_possum(ws, pair) + (size_t)raw * 3 + 1),
@@ -947,6 +1025,7 @@ int validate_pool(const dagr_pool_desc *d) {
     DAGR_CHECK_ARG(d != nullptr, "desc is NULL");
     DAGR_CHECK_ARG(d->gx > 0 && d->gy > 0 && d->batch_size > 0 && d->channels > 0, "bad sizes");
     DAGR_CHECK_ARG((int64_t)d->gx * d->gy * (d->batch_size + 1) < (1 << 22), "voxel table too large");
+    DAGR_CHECK_ARG(d->keep_order == 0 || d->keep_order == 1, "keep_order must be 0 or 1");
     DAGR_CHECK_ARG(d->aggr == 0 || d->aggr == 1, "aggr must be 0 (max) or 1 (mean)");
     DAGR_CHECK_ARG(d->vx > 0 && d->vy > 0 && d->two_max > 0, "bad voxel size / cartesian max");
     return DAGR_OK;
@@ -968,11 +1047,12 @@ int launch_pool_l0_slots(const dagr_pool_desc *desc, const dagr_graph_desc *gdes
     const int C = desc->channels, W = gdesc->width, H = gdesc->height, K = gdesc->max_neighbors;
     const bool vec4 = C % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)x & 15) == 0;
     // LDS window: up to 60 KB of accumulators per (16-wave) workgroup, at least one voxel row, at most 1024 table slots
-    const size_t per_slot = (size_t)C * (desc->aggr == 0 ? 4 : 8) + 36;
+    const bool ord = desc->keep_order != 0;
+    const size_t per_slot = (size_t)C * (desc->aggr == 0 ? 4 : 8) + 36 + (ord ? 4 : 0);
     const size_t budget = (size_t)60 * 1024 - (size_t)(W + H) * 2 - 2048 - 1024;
     int VW = (int)std::min<size_t>(1024, budget / per_slot);
     VW = std::max(VW, desc->gx) / 2 * 2 + 2;
-    const size_t lds = desc->aggr == 0 ? pool_l0_lds_bytes<0>(VW, C, W, H) : pool_l0_lds_bytes<1>(VW, C, W, H);
+    const size_t lds = desc->aggr == 0 ? pool_l0_lds_bytes<0>(VW, C, W, H, ord) : pool_l0_lds_bytes<1>(VW, C, W, H, ord);
     DAGR_CHECK_ARG(lds <= 64 * 1024, "level-0 pooling: one voxel row of accumulators does not fit the LDS window");
     DAGR_CHECK_ARG(desc->gx < 65536 && desc->gy < 65536 && VW < 32768, "voxel grid too large for the level-0 pooling kernel");
     // one 16-wave workgroup per CU is resident at a time (114 registers); wide rows run two rounds of shorter runs, which
@@ -982,13 +1062,26 @@ int launch_pool_l0_slots(const dagr_pool_desc *desc, const dagr_graph_desc *gdes
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)gmult * device_cu_count(),
                                                                           ceil_div(n_cap, kPoolL0Block)));
 #define DAGR_POOL_L0_LAUNCH(AG, VEC)                                                                                  \
-    k_pool_l0_slots<AG, VEC><<<grid, kPoolL0Block, lds, stream>>>(*desc, W, H, (int)n_cap, VW, n_ptr, xlo, ylo, start, row_keys, slot_it, \
+    if (ord) DAGR_POOL_L0_LAUNCH_ORD(k_pool_l0_slots_ord, AG, VEC); else DAGR_POOL_L0_LAUNCH_ORD(k_pool_l0_slots, AG, VEC)
+#define DAGR_POOL_L0_LAUNCH_ORD(KERNEL, AG, VEC)                                                                      \
+    KERNEL<AG, VEC><<<grid, kPoolL0Block, lds, stream>>>(*desc, W, H, (int)n_cap, VW, n_ptr, xlo, ylo, start, row_keys, slot_it, \
                                                                    slot_xyb, x, ldx, pos, ws, nbr_code, nbr_src, deg, K, \
                                                                    gdesc->radius)
     if (desc->aggr == 0) { if (vec4) DAGR_POOL_L0_LAUNCH(0, 4); else DAGR_POOL_L0_LAUNCH(0, 1); }
     else                 { if (vec4) DAGR_POOL_L0_LAUNCH(1, 4); else DAGR_POOL_L0_LAUNCH(1, 1); }
 #undef DAGR_POOL_L0_LAUNCH
+#undef DAGR_POOL_L0_LAUNCH_ORD
     DAGR_CHECK_LAUNCH();
+    return DAGR_OK;
+}
+// keep_order: launch (P) of a bitmap (level-0) step; returns the workspace view (S) and (C) read -- the filtered bitmaps
+template <bool KEEP>
+int pool_order_masks(const dagr_pool_desc *d, const PoolWs &ws, PoolWs *view, hipStream_t stream) {
+    *view = ws;
+    if (!d->keep_order) return DAGR_OK;
+    k_pool_order_masks<KEEP><<<(unsigned)ceil_div(ws.T, kBlock), kBlock, 0, stream>>>(*d, ws);
+    DAGR_CHECK_LAUNCH();
+    view->nbmask = ws.nbmask_f;
     return DAGR_OK;
 }
 }  // namespace
@@ -1021,6 +1114,10 @@ int dagr_pool_workspace_init(const dagr_pool_desc *desc, void *workspace, size_t
     DAGR_CHECK_HIP(hipMemsetAsync(ws.status, 0, 32, stream));
     DAGR_CHECK_HIP(hipMemsetAsync(ws.tile_state, 0, ((T + 1 + kPoolScanTile - 1) / kPoolScanTile + 8) * 8, stream));
     DAGR_CHECK_HIP(hipMemsetAsync(ws.nbmask, 0, (T + 9) * 8, stream));
+    if (desc->keep_order) {
+        DAGR_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)ws.tmax, kEncMin, (size_t)T + 32, stream));
+        DAGR_CHECK_HIP(hipMemsetAsync(ws.nbmask_f, 0, (T + 9) * 8, stream));
+    }
     // feature accumulators: ordered-int minimum for max, 0 for mean
     {
         const size_t n = T * (size_t)desc->channels;
@@ -1036,8 +1133,9 @@ int dagr_pool_workspace_init(const dagr_pool_desc *desc, void *workspace, size_t
 
 
 // launch (S): one workgroup per 2048 table slots
-#define DAGR_POOL_SCAN(MASKS, KEEP)                                                                                   \
-    k_pool_scan_chained<MASKS, KEEP><<<(unsigned)ceil_div(T + 1, kPoolScanTile), kBlock, 0, stream>>>(ws, n_out, rowptr_out, e_out)
+#define DAGR_POOL_SCAN(MASKS, KEEP, WS)                                                                               \
+    k_pool_scan_chained<MASKS, KEEP><<<(unsigned)ceil_div(T + 1, kPoolScanTile), kBlock, 0, stream>>>(WS, n_out, rowptr_out, e_out)
+
 
 static int pool_tail(const dagr_pool_desc *d, PoolWs &ws, const int32_t *batch32, const int64_t *batch64,
                      float *x_out, int ldo, int xoff, float *pos_out, int32_t *batch_out, int32_t *n_out,
@@ -1089,11 +1187,14 @@ int dagr_pool_l0(const dagr_pool_desc *desc, void *pool_ws, const dagr_graph_des
         if (rc != DAGR_OK) return rc;
     }
     if (fast_edges) {
-        // (S) ids + row pointers from the occupancy flags and the bitmap populations, (C) nodes + CSR rows
-        DAGR_POOL_SCAN(true, false);
+        // [(P) keep_order,] (S) ids + row pointers from the occupancy flags and the bitmap populations, (C) nodes + CSR rows
+        PoolWs wv;
+        rc = pool_order_masks<false>(desc, ws, &wv, stream);
+        if (rc != DAGR_OK) return rc;
+        DAGR_POOL_SCAN(true, false, wv);
         DAGR_CHECK_LAUNCH();
         k_pool_emit<true><<<(unsigned)ceil_div(T, kBlock / 64), kBlock, 0, stream>>>(
-            *desc, ws, b32, b64, x_out, ldo, xoff, pos_out, batch_out, rowptr_out, col_out, code_out, e_cap);
+            *desc, wv, b32, b64, x_out, ldo, xoff, pos_out, batch_out, rowptr_out, col_out, code_out, e_cap);
         DAGR_CHECK_LAUNCH();
         return DAGR_OK;
     }
@@ -1109,7 +1210,7 @@ int dagr_pool_l0(const dagr_pool_desc *desc, void *pool_ws, const dagr_graph_des
         DAGR_CHECK_ARG(K <= kBlock, "max_neighbors too large");
         const unsigned gE = round_grid8(std::min<int64_t>(ceil_div(N, kBlock / K), 256 * 8));
         k_coarse_edges_ell<<<gE, kBlock, 0, stream>>>((int)N, K, nbr_src, deg, cluster_scratch, ws.newid, ws.rows,
-                                                      ws.status);
+                                                      ws.status, ws.tmax);
         DAGR_CHECK_LAUNCH();
     }
     return pool_tail(desc, ws, b32, b64, x_out, ldo, xoff, pos_out, batch_out, n_out, rowptr_out, col_out, code_out,
@@ -1175,10 +1276,13 @@ int dagr_pool_l0_stream(const dagr_pool_desc *desc, void *pool_ws, int32_t rebui
             nbr_src, deg, K, gdesc->radius);
         DAGR_CHECK_LAUNCH();
     }
-    DAGR_POOL_SCAN(true, true);
+    PoolWs wv;
+    rc = pool_order_masks<true>(desc, ws, &wv, stream);
+    if (rc != DAGR_OK) return rc;
+    DAGR_POOL_SCAN(true, true, wv);
     DAGR_CHECK_LAUNCH();
     k_pool_emit<true, true><<<(unsigned)ceil_div(T, kBlock / 64), kBlock, 0, stream>>>(
-        *desc, ws, batch_events, nullptr, x_out, ldo, xoff, pos_out, batch_out, rowptr_out, col_out, code_out, e_cap);
+        *desc, wv, batch_events, nullptr, x_out, ldo, xoff, pos_out, batch_out, rowptr_out, col_out, code_out, e_cap);
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
 }
@@ -1202,7 +1306,12 @@ int dagr_pool_csr(const dagr_pool_desc *desc, void *pool_ws, const int32_t *n_pt
             *desc, n_ptr, n_max, x, ldx, pos, batch, rowptr, col, ws, cluster_scratch);
         DAGR_CHECK_LAUNCH();
     }
-    DAGR_POOL_SCAN(false, false);
+    if (desc->keep_order) {
+        // (P): the sources whose t_max is not below the slot's leave its set (also after dagr_spline_conv_fused_pool)
+        k_pool_order_rows<<<(unsigned)ceil_div(T, kBlock / 64), kBlock, 0, stream>>>(ws);
+        DAGR_CHECK_LAUNCH();
+    }
+    DAGR_POOL_SCAN(false, false, ws);
     DAGR_CHECK_LAUNCH();
     k_pool_emit<false><<<(unsigned)ceil_div(T, kBlock / 64), kBlock, 0, stream>>>(
         *desc, ws, batch, nullptr, x_out, ldo, xoff, pos_out, batch_out, rowptr_out, col_out, code_out, e_cap);

@@ -449,7 +449,10 @@ class WindowEngine:
                                  vy=float(vs[1]), inv_w=float(pool.wh_inv[0, 0]), inv_h=float(pool.wh_inv[0, 1]),
                                  two_max=_f32(2 * pool.transform.max), r00=float(remap[0, 0]),
                                  r02=float(remap[0, 2]), r11=float(remap[1, 1]), r12=float(remap[1, 2]),
-                                 rx=nd["rx"], ry=nd["ry"], aggr=0 if pool.aggr == "max" else 1, append_pos=1)
+                                 rx=nd["rx"], ry=nd["ry"], aggr=0 if pool.aggr == "max" else 1, append_pos=1,
+                                 # --keep_temporal_ordering (pooling.py:69-72): the kernels drop the coarse edges that do
+                                 # not point forward in time (one launch more per pooling step; every path and capture)
+                                 keep_order=1 if getattr(pool, "keep_temporal_ordering", False) else 0)
             nbytes = L.dagr_pool_workspace_bytes(ctypes.byref(desc))
             if nbytes == 0:
                 raise RuntimeError("libdagr_hip: " + L.dagr_last_error().decode())

@@ -237,8 +237,11 @@ class DAGR(torch.nn.Module):
         self.asynchronous = True     # reset=False calls update incrementally (asynchronous.make_model_synchronous: off)
         if bool(args.no_events) and not bool(args.use_image):
             raise ValueError("--no_events returns the image branch's detections (dagr.py:283-284): it needs --use_image")
-        # --keep_temporal_ordering (pooling.py:69-72): the coarse-edge filter lives in the Pooling modules; the window
-        # engine's fused pooling does not apply it, so eval forwards of such a model run module by module
+        # --keep_temporal_ordering (pooling.py:69-72): by default eval forwards of such a model run module by module (each
+        # Pooling module filters its coarse edges on the host).  The window engine honours the flag too (dagr_pool_desc
+        # keep_order: the filter runs in the pooling kernels); setting this attribute to False sends a flagged model
+        # through the engine -- reset=True, reset=False (incremental update) and make_model_synchronous alike.  Making
+        # the engine the default for flagged models is a follow-up once that path has a GPU record.
         self.module_path_only = bool(getattr(args, "keep_temporal_ordering", False))
         if "img_net_checkpoint" in vars(args):
             from ..utils import init_subnetwork
@@ -317,14 +320,19 @@ class DAGR(torch.nn.Module):
             self._stamp_tensors = None
         return super().train(mode)
 
+    def _pool_flags(self):
+        """Pooling options the engine bakes into its plan (dagr_pool_desc.keep_order): toggling one rebuilds it."""
+        b = self.backbone
+        return tuple(bool(getattr(p, "keep_temporal_ordering", False)) for p in (b.pool1, b.pool2, b.pool3, b.pool4))
+
     def engine(self):
-        stamp = self._weights_stamp()
+        stamp = (self._weights_stamp(), self._pool_flags())
         if self._engine is None or self._engine_stamp != stamp:
             from ...engine import WindowEngine
             self._engine = None
             self._stamp_tensors = None
             self._engine = WindowEngine(self)
-            self._engine_stamp = self._weights_stamp()
+            self._engine_stamp = (self._weights_stamp(), self._pool_flags())
         return self._engine
 
     def load_state_dict(self, *a, **kw):
@@ -349,7 +357,9 @@ class DAGR(torch.nn.Module):
             return self.forward_training(x)
         if self.module_path_only:
             if not reset:
-                raise NotImplementedError("reset=False with --keep_temporal_ordering: the module path evaluates whole windows")
+                raise NotImplementedError("reset=False with --keep_temporal_ordering: the module path evaluates whole windows; "
+                                          "set model.module_path_only = False to run the window engine, which updates "
+                                          "incrementally")
             outputs = self.forward_modules(x, reset=True)
             detections = postprocess_network_output(outputs, self.backbone.num_classes, self.conf_threshold,
                                                     self.nms_threshold, filtering=filtering, height=self.height,

@@ -347,6 +347,12 @@ typedef struct {
     int32_t rx, ry;       /* their LUT offset domain                                    */
     int32_t aggr;         /* 0 = max, 1 = mean                                          */
     int32_t append_pos;   /* also write pos[:, :2] into columns C, C+1 of each output row (net.py:137-138) */
+    int32_t keep_order;   /* --keep_temporal_ordering (pooling.py:69-72).  0: every coarse edge.  1: a coarse edge
+                           * src -> dst is emitted only if t_max[dst] > t_max[src] (strict: equal t_max drops it both
+                           * ways), t_max = largest pos[:, 2] over the cluster's INPUT nodes (level 0: the events' t,
+                           * t == 1.0 nodes included; pooled levels: the mean t the previous pooling emitted).  One
+                           * extra launch per pooling step (none on the generic level-0 path), none with 0.  A larger
+                           * workspace only when set.  C callers must zero this field.                            */
 } dagr_pool_desc;
 
 size_t dagr_pool_workspace_bytes(const dagr_pool_desc *desc);
