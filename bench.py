@@ -6,10 +6,16 @@ decoded detection-head outputs [B,175,5+C] -> device-side confidence mask + NMS)
 event windows already resident in HBM.  `python bench.py --gpus N --steps K --warmup W`; for N > 1 the driver launches
 it under torch.distributed.run (one rank per GPU) -- run by hand without that environment, `--gpus N` starts the N
 ranks itself and refuses to run on fewer devices; windows are independent so ranks share nothing on the data path
-(weak scaling) and RCCL is used once, to gather the run's detections (variable length).  Prints ONE JSON line on rank 0:
+(weak scaling) and RCCL is used once, to gather the run's detections (variable length).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline:
 
   value / ms_per_step   BASELINE config 2 on the synthetic 640x480 stream (dagr-s + resnet50 image branch), K steps
+
+`--full` adds, after the headline's timed steps (each leg can still be left out with its --no-* option):
+
   events_only           the same K steps on the events-only model (config 1 shape): the hand-written path alone
+  value_edges / h2d     the same K steps on the other synthetic stream, and with every window batch starting in host memory
   latency_ms            per-window latency (HIP events, one window batch at a time through the captured window graph, 20
                         warm-up + 100 timed windows): median / p95 for B in {1, 8}, N in {25k..400k} events per window,
                         S-uniform and S-edges
@@ -55,6 +61,9 @@ def parse():
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--stream", choices=["uniform", "edges"], default="uniform")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the events-only, other-stream and H2D legs, the stage timings and "
+                         "roofline, the latency sweep, the asynchronous-update leg and the CPU baselines")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true", help="skip the per-window latency sweep")
     ap.add_argument("--no-rccl", action="store_true", help="world 1: no one-rank process group (plain barriers, local gather)")
@@ -783,7 +792,7 @@ def main():
 
     # ---- the hand-written path alone: same steps on the events-only model
     ev_leg = ev_rig = ev_slots = None
-    if use_image and not a.no_events_only_leg:
+    if a.full and use_image and not a.no_events_only_leg:
         ev_rig = Rig(W, H, B, False, a.img_net, n_eng, dev)
         ev_slots = ev_rig.make_slots(gen, NPW, 4, seed=1234 + 1000 * rank)
         ev_leg = timed_run(ev_rig, ev_slots, a.steps, a.warmup, dist, world, rank)
@@ -794,7 +803,7 @@ def main():
     # ---- the same step on the other synthetic stream (S-edges when the line is S-uniform and vice versa) and with the
     # window batches starting in host memory (what the reference's loop pays per batch, utils/testing.py:29)
     other = h2d = None
-    if world == 1 and not a.no_side_legs:
+    if a.full and world == 1 and not a.no_side_legs:
         other_gen = syn.edges_window if a.stream == "uniform" else syn.uniform_window
         o_slots = rig.make_slots(other_gen, NPW, 4, seed=1234 + 1000 * rank)
         other = timed_run(rig, o_slots, a.steps, a.warmup, None, 1, rank)
@@ -805,26 +814,28 @@ def main():
     if rank == 0:
         ms_per_step = 1e3 * run["elapsed"] / a.steps
         value = world * n_events_step * a.steps / run["elapsed"]
-        st = stage_timings(rig, slots, n_events_step)
         result = {
             "metric": "events_per_sec", "value": round(value, 1), "unit": "events/s", "n_gpus": world,
             "world": world, "ranks_seen": run["ranks_seen"], "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": ("dagr-s + --use_image --img_net " + a.img_net if use_image else "dagr-s events-only")
                                    + f", {W}x{H} synthetic S-{a.stream}, B={B} windows/step x {NPW} events (50 ms "
-                                   f"each), r={st['radius']}, K=16, events->graph->GNN(+image fusion)->decoded head "
-                                   "outputs->confidence mask + NMS (device)",
+                                   f"each), r={rig.engines[0].graph.params['radius']}, K=16, events->graph->GNN(+image "
+                                   "fusion)->decoded head outputs->confidence mask + NMS (device)",
                        "image_branch": ("in-line" if use_image else None), "engines": n_eng,
-                       "events_per_step_per_gpu": n_events_step, "edges_per_step": st["edges_per_step"],
-                       "level_nodes_edges": st["levels"],
-                       # one batch through one engine, stages run back to back (sum of the isolated stage timings
-                       # below; the measured per-window latency is `latency_ms`)
-                       "stage_sum_ms": st["batch_latency_ms"]},
+                       "events_per_step_per_gpu": n_events_step},
             "gather": {"detections": run["n_detections"], "gather_ms_rank0": round(1e3 * run["t_gather"], 3),
                        "compute_ms_rank0": round(1e3 * run["t_compute"], 3),
                        "backend": ("nccl (RCCL)" if dist is not None else "none"), "note": rccl_note},
-            "roofline": st["roofline"], "stages": st["stages"],
         }
+        st = None
+        if a.full:
+            st = stage_timings(rig, slots, n_events_step)
+            # one batch through one engine, stages run back to back (sum of the isolated stage timings; the measured
+            # per-window latency is `latency_ms`)
+            result["config"].update(edges_per_step=st["edges_per_step"], level_nodes_edges=st["levels"],
+                                    stage_sum_ms=st["batch_latency_ms"])
+            result.update(roofline=st["roofline"], stages=st["stages"])
         if repeats:
             result["repeat_ms_per_step"] = [round(ms_per_step, 4)] + [round(1e3 * r / a.steps, 4) for r in repeats]
         if other is not None:
@@ -838,7 +849,7 @@ def main():
                              "engines": n_eng, "protocol": "pinned host batches in the loader's dtypes (int16 xy, int32 t, int8 "
                              "polarity, int64 sample index, uint8 frames) -> non_blocking copies on a copy stream into two "
                              "staging sets -> format_data on the device -> forward + post-processing; copy i+1 under compute i"}
-        if st["image_branch"] is not None:
+        if st is not None and st["image_branch"] is not None:
             ib = dict(st["image_branch"])
             ib["share_of_step"] = round(ib["ms"] / ms_per_step, 3)     # one engine's isolated stage time over the step time
             result["image_branch"] = ib
@@ -852,7 +863,7 @@ def main():
                 "ms_per_step": round(1e3 * ev_leg["elapsed"] / a.steps, 4), "steps": a.steps, "engines": n_eng,
                 "workload": f"dagr-s events-only, {W}x{H} S-{a.stream}, B={B} x {NPW} events",
                 "roofline": est["roofline"], "stages": est["stages"], "stage_sum_ms": est["batch_latency_ms"]}
-    want_cpu = rank == 0 and world == 1 and not a.no_cpu_baseline
+    want_cpu = a.full and rank == 0 and world == 1 and not a.no_cpu_baseline
     sd_cpu = rig.sd_cpu
     ev_sd_cpu = ev_rig.sd_cpu if ev_rig is not None else None
     model_cpu = None
@@ -862,7 +873,7 @@ def main():
     del slots, ev_slots, rig, ev_rig
     torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not a.no_latency:
+    if a.full and rank == 0 and world == 1 and not a.no_latency:
         Ns = [int(v) for v in a.latency_n.split(",") if v]
         lat = {"protocol": f"one window batch at a time on one engine in latency mode (the caller's events staged by one "
                            f"launch, the whole window -- image branch, graph build, level 0, tail, heads, decode -- replayed "

@@ -17,7 +17,7 @@ pass() {   # pass <name> <counters...>
   echo "pass $name:$have"
   [ -z "$have" ] && return
   timeout 400 rocprofv3 --kernel-trace --pmc $have --output-format csv -d "$OUT/$name" -- \
-      python "$ROOT/bench.py" --no-cpu-baseline --no-latency --no-rccl --steps 3 --warmup 1 --engines 1 $( [ "${EVONLY:-0}" = 1 ] && echo --events-only || echo --no-events-only-leg ) > "$OUT/$name.log" 2>&1 < /dev/null
+      python "$ROOT/bench.py" --full --no-cpu-baseline --no-latency --no-rccl --steps 3 --warmup 1 --engines 1 $( [ "${EVONLY:-0}" = 1 ] && echo --events-only || echo --no-events-only-leg ) > "$OUT/$name.log" 2>&1 < /dev/null
   echo "rc=$?"
   local f=$(find "$OUT/$name" -name "*counter_collection.csv" 2>/dev/null | head -1)
   if [ -n "$f" ]; then python "$ROOT/tools/pmc_agg.py" "$f" > "$OUT/pmc_$name.csv"; grep -E "^kernel|conv_l0|search_rows|conv_fused" "$OUT/pmc_$name.csv" | cut -c1-400; else tail -5 "$OUT/$name.log"; fi
@@ -33,5 +33,5 @@ cd "$ROOT"
     "tests/test_training_gpu.py::test_train_script_under_distributed_data_parallel_on_one_gpu" \
     "tests/test_engine_gpu.py::test_vga_b8_dense_windows" "tests/test_engine_gpu.py::test_bench_workload_dagr_s_resnet50_vga_b8_100k_edges" ) > "$OUT/pytest_new.log" 2>&1
 tail -15 "$OUT/pytest_new.log"
-timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-latency > "$OUT/bench_short.json" 2> "$OUT/bench_short.err"
+timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-latency > "$OUT/bench_short.json" 2> "$OUT/bench_short.err"
 tail -c 1500 "$OUT/bench_short.json"; tail -3 "$OUT/bench_short.err"

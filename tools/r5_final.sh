@@ -25,7 +25,7 @@ export DAGR_PARITY_LOG=$OUT/parity_stage_errors.jsonl
 ( time timeout 1500 python -m pytest tests/ -q -m gpu ) > "$OUT/pytest_gpu.log" 2>&1
 grep -E "passed|failed" "$OUT/pytest_gpu.log" | tail -1
 unset DAGR_PARITY_LOG
-timeout 900 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+timeout 900 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 tail -c 400 "$OUT/bench_default.json"; tail -2 "$OUT/bench_default.err"
 timeout 200 python tools/pool_probe.py uniform:8:100000:0 uniform:8:100000:1 edges:8:100000:0 edges:8:100000:1 uniform:1:25000:0 2>&1 | grep spec > "$OUT/pool_probe.jsonl"
 timeout 200 python tools/img_branch_probe.py 2>&1 | grep lt_residual > "$OUT/img_branch_probe.jsonl"
