@@ -7,22 +7,8 @@ HIPFLAGS   ?= --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wal
 SRC        := $(wildcard dagr_amd/csrc/*.hip)
 OBJ        := $(patsubst dagr_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB        := dagr_amd/lib/libdagr_hip.so
-# the same sources with the measurement knobs compiled in (common.hpp:knob -- A/B switches read from the environment;
-# some make results wrong on purpose).  Loaded only by the probes under tools/ (DAGR_HIP_LIB=<this file>), never by default.
-OBJ_M      := $(patsubst dagr_amd/csrc/%.hip,build/measure/%.o,$(SRC))
-LIB_M      := dagr_amd/lib/libdagr_hip_measure.so
 
-all: $(LIB) $(LIB_M) oracle
-
-measure: $(LIB_M)
-
-$(LIB_M): $(OBJ_M)
-	@mkdir -p dagr_amd/lib
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJ_M) -L/opt/rocm/lib -lhipblaslt
-
-build/measure/%.o: dagr_amd/csrc/%.hip dagr_amd/csrc/common.hpp dagr_amd/csrc/pool_common.hpp include/dagr_hip.h
-	@mkdir -p build/measure
-	$(HIPCC) $(HIPFLAGS) -DDAGR_MEASURE -c $< -o $@
+all: $(LIB) oracle
 
 $(LIB): $(OBJ)
 	@mkdir -p dagr_amd/lib
@@ -36,7 +22,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf build $(LIB) $(LIB_M)
+	rm -rf build $(LIB)
 	$(MAKE) -C oracle clean
 
-.PHONY: all measure oracle clean
+.PHONY: all oracle clean

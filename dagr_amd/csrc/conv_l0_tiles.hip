@@ -23,8 +23,6 @@
 // Exact fp32 throughout (the f32 MFMA is a k-ordered fmaf chain); only the summation order differs from the oracle.
 #include "common.hpp"
 
-#include <stdlib.h>
-
 namespace dagr {
 namespace {
 
@@ -64,12 +62,17 @@ struct L0Steps {
 
 constexpr int kTileWaves = 4;   // waves per workgroup (each owns its tiles; they share the weight image in LDS)
 
-template <int CM, int CE, int CS, int TX, int TY, bool LEAN>
-__global__ __launch_bounds__(kTileWaves * 64, LEAN ? 3 : 2) void k_conv_l0_tiles(
+// Three waves per SIMD (<= 168 registers): -4 % on the 16 -> 16 + skip and 3 -> 16 convs against two waves (0.179 -> 0.171,
+// 0.090 -> 0.087 ms at 800 k nodes).  The 19 -> 16 conv (main block + extras) used to spill at that budget (+7 %) and ran at
+// two waves until the per-offset weight rows and the packed offset codes freed the registers (166, no scratch).  PMC
+// (profiles/r3_*_pmc_sq.csv): the SIMDs' issue slots are ~77 % busy at two waves -- the kernel is bound by instruction issue
+// (packed FMAs already), which is why a third wave buys so little.
+template <int CM, int CE, int CS, int TX, int TY>
+__global__ __launch_bounds__(kTileWaves * 64, 3) void k_conv_l0_tiles(
     int n_first, int N, const int32_t *__restrict__ n_ptr, int rx, int ry, float den_x, float den_y, int win_x, int win_y, const int32_t *__restrict__ nbr_src,
     const int16_t *__restrict__ nbr_code, const int32_t *__restrict__ deg, const float *__restrict__ x, int ldx,
     const float *__restrict__ xskip, int ldskip, const float *__restrict__ wpack, const float *__restrict__ shift,
-    int relu, float *__restrict__ out, int ldo, int ablate) {
+    int relu, float *__restrict__ out, int ldo) {
     using S = L0Steps<CM, CE, CS, TX, TY>;
     constexpr int NT = S::NT;
     extern __shared__ __align__(16) float lds[];
@@ -140,10 +143,8 @@ __global__ __launch_bounds__(kTileWaves * 64, LEAN ? 3 : 2) void k_conv_l0_tiles
     const int n_begin = n_first + xcd * chunk + lb * 16 * kTileWaves;
     const int n_end = n_first + min(N, (xcd + 1) * chunk);
 
-    // Software pipeline over this wave's tiles.  Per tile the dependent chain is {degree, neighbour row} -> source rows ->
-    // FMAs; with ~200 registers per lane only two waves share a SIMD, so the chain is shortened instead of hidden: the
-    // neighbour row of the NEXT tile is requested while this tile's source rows are in flight, and all (<= 16) source
-    // rows of a tile are requested before the first one is consumed (two batches of 8).
+    // Per tile the dependent chain is {degree, neighbour row} -> source rows -> FMAs.  The source rows come in two batches
+    // of 8 through the same registers; the waits are hidden by the third wave on the SIMD.
     auto load_meta = [&](int n0_, int &d_, int4(&s_)[4], int2(&c_)[4]) {
         const int n_ = n0_ + c;
         const bool ok_ = n0_ < n_end && n_ < n_end;
@@ -155,60 +156,47 @@ __global__ __launch_bounds__(kTileWaves * 64, LEAN ? 3 : 2) void k_conv_l0_tiles
             c_[k] = *reinterpret_cast<const int2 *>(nbr_code + (size_t)nn_ * 16 + 4 * k);
         }
     };
-    int d_nx;
-    int4 s_nx[4];
-    int2 c_nx[4];
-    // LEAN: three waves per SIMD instead of two (<= 170 registers): the next tile's neighbour row is not held across the tile
-    // and the source rows come in two batches of 8 through the same registers -- the waits are hidden by the third wave
-    // instead of being shortened
-    if (!LEAN && n_begin + 16 * wv < n_end) load_meta(n_begin + 16 * wv, d_nx, s_nx, c_nx);
     for (int n0 = n_begin + 16 * wv; n0 < n_end; n0 += stride) {
-        if (LEAN) load_meta(n0, d_nx, s_nx, c_nx);
+        int d;
+        int4 s4[4];
+        int2 c2[4];
+        load_meta(n0, d, s4, c2);
         const int n = n0 + c;
         const bool valid = n < n_end;
         const int nn = valid ? n : n0;                  // a row that exists, for the predicated-off lanes
-        const int d = d_nx;
         // offset codes: with a main channel block (register-bound instantiations) they stay packed two per register until
         // their edge; the 3 -> 16 conv has registers to spare and unpacks them once (measured: 0.085 vs 0.090 ms)
         int srcs[16], cpk[8], cun[CM ? 1 : 16];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            srcs[4 * k] = s_nx[k].x; srcs[4 * k + 1] = s_nx[k].y; srcs[4 * k + 2] = s_nx[k].z; srcs[4 * k + 3] = s_nx[k].w;
-            cpk[2 * k] = c_nx[k].x; cpk[2 * k + 1] = c_nx[k].y;
+            srcs[4 * k] = s4[k].x; srcs[4 * k + 1] = s4[k].y; srcs[4 * k + 2] = s4[k].z; srcs[4 * k + 3] = s4[k].w;
+            cpk[2 * k] = c2[k].x; cpk[2 * k + 1] = c2[k].y;
             if (!CM) {
-                cun[(4 * k) % (CM ? 1 : 16)] = c_nx[k].x & 0xffff; cun[(4 * k + 1) % (CM ? 1 : 16)] = (c_nx[k].x >> 16) & 0xffff;
-                cun[(4 * k + 2) % (CM ? 1 : 16)] = c_nx[k].y & 0xffff; cun[(4 * k + 3) % (CM ? 1 : 16)] = (c_nx[k].y >> 16) & 0xffff;
+                cun[(4 * k) % (CM ? 1 : 16)] = c2[k].x & 0xffff; cun[(4 * k + 1) % (CM ? 1 : 16)] = (c2[k].x >> 16) & 0xffff;
+                cun[(4 * k + 2) % (CM ? 1 : 16)] = c2[k].y & 0xffff; cun[(4 * k + 3) % (CM ? 1 : 16)] = (c2[k].y >> 16) & 0xffff;
             }
         }
         auto code_of = [&](int u) { return CM ? ((cpk[u >> 1] >> (16 * (u & 1))) & 0xffff) : cun[u % (CM ? 1 : 16)]; };
         int dmax = d;
 #pragma unroll
         for (int off = 1; off < 16; off <<= 1) dmax = max(dmax, __shfl_xor(dmax, off, 16));
-        // source rows: first batch of 8, and the second one when any node of the tile has more than 8 in-edges
-        float4 xv[LEAN ? 8 : 16];
-        float xe[LEAN ? 8 : 16];
+        // source rows: first batch of 8 (the second one, when any node of the tile has more than 8 in-edges, after phase 1
+        // of the first)
+        float4 xv[8];
+        float xe[8];
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             const int src = (u < d) ? srcs[u] : nn;
             if (CM) xv[u] = *reinterpret_cast<const float4 *>(x + (size_t)src * ldx + 4 * q);
             if (CE) xe[u] = (q < CE) ? x[(size_t)src * ldx + CM + q] : 0.f;
         }
-        if (!LEAN && dmax > 8) {
-#pragma unroll
-            for (int u = 8; u < 16; u++) {
-                const int src = (u < d) ? srcs[u] : nn;
-                if (CM) xv[u % (LEAN ? 8 : 16)] = *reinterpret_cast<const float4 *>(x + (size_t)src * ldx + 4 * q);
-                if (CE) xe[u % (LEAN ? 8 : 16)] = (q < CE) ? x[(size_t)src * ldx + CM + q] : 0.f;
-            }
-        }
-        // root / skip operands of phase 2 and the next tile's neighbour row: requested now, consumed later
+        // root / skip operands of phase 2: requested now, consumed later
         float4 xr = make_float4(0.f, 0.f, 0.f, 0.f), xs = make_float4(0.f, 0.f, 0.f, 0.f);
         float xre = 0.f, xse = 0.f;
         if (CM) xr = *reinterpret_cast<const float4 *>(x + (size_t)nn * ldx + 4 * q);
         if (CE) xre = (q < CE) ? x[(size_t)nn * ldx + CM + q] : 0.f;
         if (S::SKF) xs = *reinterpret_cast<const float4 *>(xskip + (size_t)nn * ldskip + 4 * q);
         if (S::SKE) xse = (q < S::SKE) ? xskip[(size_t)nn * ldskip + 16 * S::SKF + q] : 0.f;
-        if (!LEAN) load_meta(n0 + stride, d_nx, s_nx, c_nx);
 
         // A[tap][4 channels] as two packed pairs: the 60 FMAs of an edge issue as 30 v_pk_fma_f32 (two fp32 FMAs per lane
         // and instruction -- the rate the 157 TFLOP/s fp32 peak is quoted for; scalar v_fma_f32 tops out at half of it).
@@ -223,14 +211,13 @@ __global__ __launch_bounds__(kTileWaves * 64, LEAN ? 3 : 2) void k_conv_l0_tiles
         // ---- phase 1: this lane's node, its <= 16 in-edges.  (Requesting the basis rows of edge u+1 before the FMAs of edge
         // u was measured: 3-10 % slower -- more live registers, no shorter chain.)
         auto edge = [&](int u) {
-            constexpr int NX = LEAN ? 8 : 16;
             auto tap = [&](int t, float w) {
                 if (CM) {
                     const f32x2_t w2 = {w, w};
-                    acc[t][0] = __builtin_elementwise_fma(w2, f32x2_t{xv[u % NX].x, xv[u % NX].y}, acc[t][0]);
-                    acc[t][1] = __builtin_elementwise_fma(w2, f32x2_t{xv[u % NX].z, xv[u % NX].w}, acc[t][1]);
+                    acc[t][0] = __builtin_elementwise_fma(w2, f32x2_t{xv[u % 8].x, xv[u % 8].y}, acc[t][0]);
+                    acc[t][1] = __builtin_elementwise_fma(w2, f32x2_t{xv[u % 8].z, xv[u % 8].w}, acc[t][1]);
                 }
-                if (CE) acce[t] = fmaf(w, xe[u % NX], acce[t]);
+                if (CE) acce[t] = fmaf(w, xe[u % 8], acce[t]);
             };
             if constexpr (PRE) {
                 const int code = (u < d) ? code_of(u) : n_codes;      // absent edge: the all-zero row
@@ -262,18 +249,15 @@ __global__ __launch_bounds__(kTileWaves * 64, LEAN ? 3 : 2) void k_conv_l0_tiles
             }
             __builtin_amdgcn_sched_barrier(0);   // one edge's weights live at a time (register pressure)
         };
-        if (ablate & 1) dmax = min(dmax, 1);     // (measurement only, DAGR_L0_ABLATE: phase 1 cut to one edge)
 #pragma unroll
         for (int u = 0; u < 8; u++)
             if (u < dmax) edge(u);               // group-uniform
-        if (dmax > 8) {
-            if (LEAN) {       // second batch of source rows, through the registers of the first
+        if (dmax > 8) {       // second batch of source rows, through the registers of the first
 #pragma unroll
-                for (int u = 8; u < 16; u++) {
-                    const int src = (u < d) ? srcs[u] : nn;
-                    if (CM) xv[u - 8] = *reinterpret_cast<const float4 *>(x + (size_t)src * ldx + 4 * q);
-                    if (CE) xe[u - 8] = (q < CE) ? x[(size_t)src * ldx + CM + q] : 0.f;
-                }
+            for (int u = 8; u < 16; u++) {
+                const int src = (u < d) ? srcs[u] : nn;
+                if (CM) xv[u - 8] = *reinterpret_cast<const float4 *>(x + (size_t)src * ldx + 4 * q);
+                if (CE) xe[u - 8] = (q < CE) ? x[(size_t)src * ldx + CM + q] : 0.f;
             }
 #pragma unroll
             for (int u = 8; u < 16; u++)
@@ -290,17 +274,6 @@ __global__ __launch_bounds__(kTileWaves * 64, LEAN ? 3 : 2) void k_conv_l0_tiles
         else o0 = __builtin_amdgcn_mfma_f32_16x16x4f32((aval), wb[(s) * 64], o0, 0, 0, 0);       \
         s++;                                                                                   \
     } while (0)
-        if (ablate & 2) {                        // (measurement only: phase 2 cut to the root / skip steps)
-            if (CM) {
-#pragma unroll
-                for (int t = 0; t < NT; t++) { o0[0] += acc[t][0][0] + acc[t][0][1]; o1[0] += acc[t][1][0] + acc[t][1][1]; }
-            }
-            if (CE) {
-#pragma unroll
-                for (int t = 0; t < NT; t++) o0[1] += acce[t];
-            }
-            s = S::kMain + S::kExtra;
-        } else {
         if (CM) {
 #pragma unroll
             for (int t = 0; t < NT; t++) {
@@ -310,7 +283,6 @@ __global__ __launch_bounds__(kTileWaves * 64, LEAN ? 3 : 2) void k_conv_l0_tiles
         if (CE) {
 #pragma unroll
             for (int t = 0; t < NT; t++) DAGR_STEP(acce[t]);
-        }
         }
         if (CM) { DAGR_STEP(xr.x); DAGR_STEP(xr.y); DAGR_STEP(xr.z); DAGR_STEP(xr.w); }
         if (CE) DAGR_STEP(xre);
@@ -330,17 +302,18 @@ __global__ __launch_bounds__(kTileWaves * 64, LEAN ? 3 : 2) void k_conv_l0_tiles
     }
 }
 
-template <int CM, int CE, int CS, int TX, int TY, bool LEAN>
-int launch_tiles_v(int64_t n_first, int64_t N, const int32_t *n_ptr, int rx, int ry, float den_x, float den_y, int win_x, int win_y, const int32_t *nbr_src,
-                 const int16_t *nbr_code, const int32_t *deg, const float *x, int ldx, const float *xskip, int ldskip,
-                 const float *wpack, const float *shift, int relu, float *out, int ldo, hipStream_t stream) {
+template <int CM, int CE, int CS, int TX, int TY>
+int launch_tiles(int64_t n_first, int64_t N, const int32_t *n_ptr, int rx, int ry, float den_x, float den_y, int win_x, int win_y,
+                 const int32_t *nbr_src, const int16_t *nbr_code, const int32_t *deg, const float *x, int ldx,
+                 const float *xskip, int ldskip, const float *wpack, const float *shift, int relu, float *out, int ldo,
+                 hipStream_t stream) {
     using S = L0Steps<CM, CE, CS, TX, TY>;
     constexpr int WS = (S::NT + 3) / 4 * 4 + 4;
     constexpr bool PRE = CM > 0;     // per-offset weight rows / per-axis tables (see the kernel)
     const size_t lds_bytes = ((size_t)S::N * 64 + (PRE ? ((size_t)(2 * rx + 1) * (2 * ry + 1) + 1) * WS
                                                        : (size_t)(2 * rx + 1) * 4 + (size_t)(2 * ry + 1) * 8)) * 4;
     DAGR_CHECK_ARG(lds_bytes <= 64 * 1024, "offset domain too large for the per-offset weight table");
-    auto kern = k_conv_l0_tiles<CM, CE, CS, TX, TY, LEAN>;
+    auto kern = k_conv_l0_tiles<CM, CE, CS, TX, TY>;
     {
         static thread_local size_t set_for = 0;
         if (set_for < lds_bytes) {
@@ -351,26 +324,10 @@ int launch_tiles_v(int64_t n_first, int64_t N, const int32_t *n_ptr, int rx, int
     }
     const int64_t tiles = ceil_div(N, 16);
     const unsigned grid = round_grid8(persistent_grid(kern, kTileWaves * 64, lds_bytes, ceil_div(tiles, kTileWaves)));
-    static const int ablate = (int)knob("DAGR_L0_ABLATE", 0);   // measurement build only (results are wrong when set)
     kern<<<grid, kTileWaves * 64, lds_bytes, stream>>>((int)n_first, (int)N, n_ptr, rx, ry, den_x, den_y, win_x, win_y, nbr_src, nbr_code, deg,
-                                                       x, ldx, xskip, ldskip, wpack, shift, relu, out, ldo, ablate);
+                                                       x, ldx, xskip, ldskip, wpack, shift, relu, out, ldo);
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
-}
-
-template <int CM, int CE, int CS, int TX, int TY>
-int launch_tiles(int64_t n_first, int64_t N, const int32_t *n_ptr, int rx, int ry, float den_x, float den_y, int win_x, int win_y,
-                 const int32_t *nbr_src, const int16_t *nbr_code, const int32_t *deg, const float *x, int ldx,
-                 const float *xskip, int ldskip, const float *wpack, const float *shift, int relu, float *out, int ldo,
-                 hipStream_t stream) {
-    // three waves per SIMD (LEAN: <= 168 registers, source rows in two batches of 8): -4 % on the 16 -> 16 + skip and
-    // 3 -> 16 convs (0.179 -> 0.171, 0.090 -> 0.087 ms at 800 k nodes).  The 19 -> 16 conv (main block + extras) used to
-    // spill at that budget (+7 %) and ran at two waves until the per-offset weight rows and the packed offset codes freed
-    // the registers (166, no scratch).  PMC (profiles/r3_*_pmc_sq.csv): the SIMDs' issue slots are ~77 % busy at two waves
-    // -- the kernel is bound by instruction issue (packed FMAs already), which is why a third wave buys so little.
-    constexpr bool kLean = true;
-    return launch_tiles_v<CM, CE, CS, TX, TY, kLean>(n_first, N, n_ptr, rx, ry, den_x, den_y, win_x, win_y, nbr_src, nbr_code,
-                                                     deg, x, ldx, xskip, ldskip, wpack, shift, relu, out, ldo, stream);
 }
 
 }  // namespace

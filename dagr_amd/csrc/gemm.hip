@@ -18,10 +18,6 @@
 #include "common.hpp"
 #include "pool_common.hpp"
 
-#ifndef DAGR_TRACE          // tools/microbench/conv_trace.hip defines it to time the stages of k_conv_fused
-#define DAGR_TRACE(i)
-#endif
-
 namespace dagr {
 namespace {
 
@@ -240,7 +236,6 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(U 
     const int m0 = blockIdx.x * 16;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: loop bounds below stay in SGPRs
-    DAGR_TRACE(0);
     // rowptr has n_max + 1 entries: read it before the device-side bound is known (one latency, not two)
     const int n_spec = min(m0 + wv, n_max - 1);
     const int e0 = rowptr[n_spec], e1s = rowptr[n_spec + 1];
@@ -259,13 +254,11 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(U 
         }
         if (lane == 0) s_raw[wv] = my_raw;
     }
-    DAGR_TRACE(1);
     // ---- phase A: wave wv aggregates node m0 + wv (edge order and arithmetic of k_tap_aggregate)
     {
         const int n = m0 + wv;
         float *row = At + wv * KP;
         for (int i = lane; i < KP; i += 64) row[i] = 0.0f;
-        DAGR_TRACE(7);
         if (n < M) {
             const int ne = e1s - e0;
             const float *xn = x + (size_t)n * ldx;
@@ -274,7 +267,6 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(U 
                 const float *sn = xskip + (size_t)n * ldskip;
                 for (int i = lane; i < cskip; i += 64) row[26 * cin + i] = sn[i];
             }
-            DAGR_TRACE(8);
             for (int base = 0; base < ne; base += 64) {
                 const int cnt = min(64, ne - base);
                 int my_src = 0, my_cd = 0;
@@ -282,7 +274,6 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(U 
                     my_src = col[e0 + base + lane];
                     my_cd = code[e0 + base + lane];
                 }
-                DAGR_TRACE(2);
                 for (int c0 = 0; c0 < cin; c0 += 64) {
                     const int ch = c0 + lane;
                     const bool ch_ok = ch < cin;
@@ -305,7 +296,6 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(U 
                             v[u] = ch_ok ? x[(size_t)src * ldx + ch] : 0.0f;
                             v2[u] = ch2_ok ? x[(size_t)src * ldx + ch2] : 0.0f;
                         }
-                        DAGR_TRACE(9);
 #pragma unroll
                         for (int u = 0; u < UA; u++) {
                             if (j + u < cnt && ch_ok) {
@@ -341,9 +331,7 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(U 
     // fused pooling: the node's bookkeeping and in-edges (one column workgroup per node tile does it)
     if (pf.on && my_raw >= 0 && blockIdx.y == 0)
         pool_merge_node(pf.d, pf.ws, m0 + wv, my_raw, pf.pos, pf.batch, col, e0, e1s, lane, 64, pf.cluster_raw_out);
-    DAGR_TRACE(3);
     __syncthreads();
-    DAGR_TRACE(4);
     // ---- phase B: [16 x K] . [K x N].  Wave (ks, w): K quarter ks, 16-column tile w of a 64-column block.
     // No weight staging: every weight element is used by exactly one wave of the block, so the B operands
     // come straight from L2 in the host-packed MFMA operand order Wq[col tile][k group of 16][lane][4]
@@ -396,7 +384,6 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(U 
                 }
                 g += 2 * U;
             }
-            DAGR_TRACE(10);
             {   // < U left-over groups: all of their operands are requested before the first is used (on the small
                 // levels K / 16 splits into 7 groups per wave: one full batch + 3 left-overs, which used to be three
                 // dependent load -> MFMA round trips)
@@ -418,12 +405,10 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(U 
             }
         }
         const f32x4 acc = {acc0[0] + acc1[0], acc0[1] + acc1[1], acc0[2] + acc1[2], acc0[3] + acc1[3]};
-        DAGR_TRACE(5);
         float *rd = red + ks * 16 * NBc;
 #pragma unroll
         for (int q = 0; q < 4; q++) rd[(kk * 4 + q) * NBc + w * 16 + nn] = acc[q];
         __syncthreads();
-        DAGR_TRACE(11);
         if (tid < 16 * NBc) {
             const int idx = tid;
             const int orow = m0 + idx / NBc, ocol = n0 + idx % NBc;
@@ -445,7 +430,6 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(U 
             }
         }
         __syncthreads();
-        DAGR_TRACE(6);
     }
 }
 
@@ -936,7 +920,7 @@ static int launch_conv_jobs(const HostConvJob *hj, int count, const dagr::PoolFu
         lds_max = std::max(lds_max, ((size_t)16 * KP + (size_t)KSPLIT * 16 * NB) * 4);
         // Column tiles per workgroup (4, 2 or 1): the tile leaves room for one workgroup per CU, so the launch runs in
         // ceil(workgroups / CUs) rounds.  A round costs the edge walk + prologue (~5 us, repeated by every workgroup of a
-        // node tile) plus ~1.5 us per column tile (measured, tools/microbench/conv_trace.hip); few nodes -> spread the
+        // node tile) plus ~1.5 us per column tile (measured with per-stage timestamps); few nodes -> spread the
         // columns over workgroups, but never into an extra round: 71 node tiles x 4 column workgroups ran 284 workgroups
         // on 256 CUs, 18.5 us where 141 node tiles took 16.9.
         const int row_blocks = ceil_div(h.n_max, 16);
@@ -965,9 +949,8 @@ static int launch_conv_jobs(const HostConvJob *hj, int count, const dagr::PoolFu
     const bool mp = mp_all == 1;
     DAGR_CHECK_ARG(!(pool && (mp || dev[0].gy == 0)), "the fused pooling merge needs the single-pass form of the conv");
     // two workgroups per CU (the 62-register form) when the launch takes more than one round of workgroups and two tiles
-    // fit the LDS; builder knob DAGR_CONV_DENSE=0: never
-    static const bool dense_ok = knob("DAGR_CONV_DENSE", 1) != 0;
-    const bool dense = dense_ok && !mp && lds_max <= 80 * 1024 && (int64_t)gx * gy * count > device_cu_count();
+    // fit the LDS
+    const bool dense = !mp && lds_max <= 80 * 1024 && (int64_t)gx * gy * count > device_cu_count();
     const int which = mp ? 1 : (dense ? 2 : 0);
     static thread_local size_t set_max[3] = {0, 0, 0};
     if (lds_max > set_max[which]) {
@@ -1005,9 +988,8 @@ extern "C" int dagr_spline_conv_fused(const int32_t *n_nodes_ptr, int32_t n_node
                                       int32_t ldc, int32_t N, int32_t relu, void *stream) {
     using namespace dagr;
     // narrow inputs on a level of several workgroup rounds: 48- / 80-node tiles, three nodes per wave and pass
-    // (k_conv_fused_narrow).  Measurement knob DAGR_CONV_NARROW: 0 = never, 3 / 5 = force that tile form
-    static const int narrow = (int)knob("DAGR_CONV_NARROW", 1);
-    if (narrow && cin >= 1 && cin <= kNarrowSub && cskip == 0 && N >= 1 &&
+    // (k_conv_fused_narrow)
+    if (cin >= 1 && cin <= kNarrowSub && cskip == 0 && N >= 1 &&
         (int64_t)n_nodes_max >= (int64_t)48 * device_cu_count()) {
         DAGR_CHECK_ARG(rowptr && col && code && x && Wq && C, "NULL pointer");
         DAGR_CHECK_ARG(((uintptr_t)Wq % 16) == 0, "packed weights must be 16-byte aligned");
@@ -1016,8 +998,7 @@ extern "C" int dagr_spline_conv_fused(const int32_t *n_nodes_ptr, int32_t n_node
             // 80-node tiles when that makes the level one round of workgroups and the tile fits (the aliased partials serve
             // ONE 64-column block)
             const size_t tile5 = (size_t)16 * 5 * KP * 4, part5 = (size_t)KSPLIT * 16 * 5 * NB * 4;
-            const bool two = narrow != 3 && N <= NB && std::max(tile5, part5) <= 160 * 1024 &&
-                             (narrow == 5 || ceil_div(n_nodes_max, 80) <= device_cu_count());
+            const bool two = N <= NB && std::max(tile5, part5) <= 160 * 1024 && ceil_div(n_nodes_max, 80) <= device_cu_count();
             const int rt = two ? 5 : 3;
             const size_t tile = (size_t)16 * rt * KP * 4, part = (size_t)KSPLIT * 16 * rt * NB * 4;
             const size_t lds = two ? std::max(tile, part) : tile + part;

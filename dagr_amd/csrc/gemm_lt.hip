@@ -91,10 +91,9 @@ extern "C" int dagr_gemm_epilogue(const float *A, int64_t M, int32_t K, int64_t 
         int best = 0;
         // The library ranks its kernels by a model; the first time a shape is seen (a warm-up call, never inside a stream
         // capture) the candidates are timed on the caller's own operands and the fastest is kept for the shape.
-        static const bool tune = knob("DAGR_LT_TUNE", 1) != 0;
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing((hipStream_t)stream, &cap);
-        if (tune && found > 1 && cap == hipStreamCaptureStatusNone) {
+        if (found > 1 && cap == hipStreamCaptureStatusNone) {
             hipEvent_t e0, e1;
             if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
                 const float alpha = 1.0f, beta = R ? 1.0f : 0.0f;

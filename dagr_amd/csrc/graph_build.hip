@@ -166,8 +166,8 @@ __global__ __launch_bounds__(kBlock) void k_count(const void *__restrict__ pos_,
                                                  int N, int W, int H, int B, float fW,
                                                  float fH, float fT, int32_t *__restrict__ cnt,
                                                  int32_t *__restrict__ ev_xyb, int32_t *__restrict__ ev_t,
-                                                 int32_t *__restrict__ ev_rank, int32_t *__restrict__ status, int xcd_remap) {
-    const int lb = xcd_block((N + kBlock - 1) / kBlock, xcd_remap);
+                                                 int32_t *__restrict__ ev_rank, int32_t *__restrict__ status) {
+    const int lb = xcd_block((N + kBlock - 1) / kBlock);
     const int e = lb * kBlock + threadIdx.x;
     if (lb < 0 || e >= N) return;
     count_event<BatchT, kIntPos>(e, pos_, batch, W, H, B, fW, fH, fT, cnt, ev_xyb, ev_t, ev_rank, status + 1, status + 6);
@@ -185,13 +185,13 @@ __global__ __launch_bounds__(kBlock) void k_scatter(int N, const int32_t *__rest
                                                    const int32_t *__restrict__ ev_rank,
                                                    const int32_t *__restrict__ start,
                                                    int32_t *__restrict__ slot_tmp, int32_t *__restrict__ ev_slot,
-                                                   int32_t *__restrict__ status, int xcd_remap) {
+                                                   int32_t *__restrict__ status) {
     if (n_dev && blockIdx.x == 0 && threadIdx.x == 0) {
         if (status[8]) { atomicOr(&status[1], 1); status[8] = 0; }
         if (status[9]) { status[6] = 1; status[9] = 0; }
     }
     const int Nw = n_dev ? min(N, *n_dev) : N;       // (a captured launch is sized for the capacity)
-    const int lb = xcd_block((Nw + kBlock - 1) / kBlock, xcd_remap);
+    const int lb = xcd_block((Nw + kBlock - 1) / kBlock);
     const int e = lb * kBlock + threadIdx.x;
     if (lb < 0 || e >= Nw) return;
     const int c = ev_xyb[e];
@@ -209,9 +209,9 @@ __global__ __launch_bounds__(kBlock) void k_order(int N, int64_t PK, int W, int 
                                                  const int32_t *__restrict__ slot_tmp, int2 *__restrict__ slot_it,
                                                  int32_t *__restrict__ slot_xyb, int32_t *__restrict__ ev_slot,
                                                  int32_t *__restrict__ hot_list, int hot_cap,
-                                                 int32_t *__restrict__ status, int xcd_remap) {
+                                                 int32_t *__restrict__ status) {
     const int M = min(N, start[PK]);       // start[PK] = number of indexed events (<= N)
-    const int lb = xcd_block((M + kBlock - 1) / kBlock, xcd_remap);
+    const int lb = xcd_block((M + kBlock - 1) / kBlock);
     const int s = lb * kBlock + threadIdx.x;
     if (lb < 0 || s >= M) return;  // start[PK] = number of indexed events (<= N)
     const int e = slot_tmp[s];
@@ -1116,30 +1116,19 @@ static int launch_search(const dagr_graph_desc *desc, const GraphWs &ws, int64_t
         // fast path: candidate-centric row kernel; dense neighbourhoods are deferred (list in ev_rank, which is dead
         // after k_scatter; counter in status[5]) to the position-centric walk of k_search_dense
         constexpr size_t rows_lds = (size_t)(kBlock / 16) * (kRowCap + 4) * 4;
-        // measurement knob DAGR_ROWS_VARIANT = 10 * rounds + waves per SIMD (16 candidates per round)
-        static const int variant = (int)knob("DAGR_ROWS_VARIANT", 46);
-        // neighbourhoods beyond this many candidates go to the position-centric walk (measurement knob DAGR_DEFER_CAP)
-        static const int defer_cap = std::min(kRowCap, std::max(16, (int)knob("DAGR_DEFER_CAP", kRowCap)));
         // candidates from which a neighbourhood is searched in its inner rings first (k_search_rows; 0 = never) and
         // candidates wanted per source.  Measured in round 5 (whole build in us, profiles/r5_ring_sweep.txt): S-edges
         // 8 x 100 k 833 -> 748, 8 x 200 k 1631 -> 1511, S-uniform 8 x 400 k 2761 -> 2449 at (200, 6); wanting 4 per source
         // makes the inner pass fall short three times in four on uniform streams, thresholds below 200 cost sparse windows
         // two loads for nothing
-        static const int ring_thr = (int)knob("DAGR_RING_THR", 200) | ((int)knob("DAGR_RING_WANT", 6) << 16);
-        auto launch_rows = [&](auto kern) {
-            static thread_local unsigned res_rows = 0;
-            if (!res_rows) res_rows = persistent_grid(kern, kBlock, rows_lds, 1 << 30);
-            const unsigned gR = round_grid8(std::min<int64_t>(ceil_div(N * 16, kBlock), res_rows));
-            kern<<<gR, kBlock, rows_lds, stream>>>(ws.start + ws.PK, W, H, K, r, (float)desc->delta_t_us, defer_cap, ring_thr,
-                                                   ws.slot_xyb, ws.start, ws.slot_it, nbr_src, nbr_code, deg, ws.status,
-                                                   ws.ev_rank, ws.status + 5);
-        };
-        switch (variant) {
-            case 47: launch_rows(k_search_rows<kRowCap, 4, 7>); break;
-            case 45: launch_rows(k_search_rows<kRowCap, 4, 5>); break;
-            case 36: launch_rows(k_search_rows<kRowCap, 3, 6>); break;
-            default: launch_rows(k_search_rows<kRowCap, 4, 6>); break;
-        }
+        constexpr int kRingThr = 200, kRingWant = 6;
+        auto kern = k_search_rows<kRowCap, 4, 6>;
+        static thread_local unsigned res_rows = 0;
+        if (!res_rows) res_rows = persistent_grid(kern, kBlock, rows_lds, 1 << 30);
+        const unsigned gR = round_grid8(std::min<int64_t>(ceil_div(N * 16, kBlock), res_rows));
+        kern<<<gR, kBlock, rows_lds, stream>>>(ws.start + ws.PK, W, H, K, r, (float)desc->delta_t_us, kRowCap,
+                                               kRingThr | (kRingWant << 16), ws.slot_xyb, ws.start, ws.slot_it, nbr_src,
+                                               nbr_code, deg, ws.status, ws.ev_rank, ws.status + 5);
         DAGR_CHECK_LAUNCH();
     }
     const size_t dense_lds = dense_lds_bytes(K, r);
@@ -1174,7 +1163,6 @@ static int build_window(const dagr_graph_desc *desc, void *workspace, const void
     DAGR_CHECK_ARG(pos && batch && nbr_src && nbr_code && deg, "NULL pointer");
     const int n = (int)N;
     const unsigned gN = xcd_grid(ceil_div(N, kBlock));
-    const int xr = xcd_remap_on();
     const int W = desc->width, H = desc->height, B = desc->batch_size;
     // (device-count form: dagr_stage_window, the launch in front of the captured window, has cleared the status words and
     // run K1 on the window it staged)
@@ -1183,7 +1171,7 @@ static int build_window(const dagr_graph_desc *desc, void *workspace, const void
 #define DAGR_LAUNCH_COUNT(BT, IP)                                                                          \
     k_count<BT, IP><<<gN, kBlock, 0, stream>>>(pos, (const BT *)batch, n, W, H, B, (float)W, (float)H,        \
                                                (float)desc->time_window, ws.cnt, ws.ev_xyb, ws.ev_t,         \
-                                               ws.ev_rank, ws.status, xr)
+                                               ws.ev_rank, ws.status)
         if (batch_is_int64) { if (pos_is_int32) DAGR_LAUNCH_COUNT(int64_t, true); else DAGR_LAUNCH_COUNT(int64_t, false); }
         else                { if (pos_is_int32) DAGR_LAUNCH_COUNT(int32_t, true); else DAGR_LAUNCH_COUNT(int32_t, false); }
 #undef DAGR_LAUNCH_COUNT
@@ -1192,7 +1180,7 @@ static int build_window(const dagr_graph_desc *desc, void *workspace, const void
     // start = exclusive_scan(cnt); cnt is re-zeroed in the same pass (invariant for the next window)
     DAGR_CHECK_HIP(exclusive_scan_i32_chained(ws.cnt, ws.start, ws.PK + 1, ws.scan_tmp, true, stream));
     k_scatter<<<gN, kBlock, 0, stream>>>(n, n_dev, W, H, ws.ev_xyb, ws.ev_rank, ws.start, ws.slot_tmp,
-                                         ws.ev_slot, ws.status, xr);
+                                         ws.ev_slot, ws.status);
     DAGR_CHECK_LAUNCH();
     // number of occupied CSR slots M = start[PK] <= N (dropped events excluded); slots are a
     // prefix [0, M) so launching N threads with an in-kernel bound read would need M on the host.
@@ -1200,7 +1188,7 @@ static int build_window(const dagr_graph_desc *desc, void *workspace, const void
     const int hot_cap = (int)(desc->max_events + 1);
     const int hot_thr = std::min(kShortSeg, desc->queue_size);
     k_order<<<gN, kBlock, 0, stream>>>(n, ws.PK, W, H, hot_thr, ws.ev_xyb, ws.ev_t, ws.start, ws.slot_tmp, ws.slot_it,
-                                       ws.slot_xyb, ws.ev_slot, ws.hot_list, hot_cap, ws.status, xr);
+                                       ws.slot_xyb, ws.ev_slot, ws.hot_list, hot_cap, ws.status);
     DAGR_CHECK_LAUNCH();
     k_fix_pixels<<<1024, kBlock, 0, stream>>>(desc->queue_size, ws.ev_xyb, ws.slot_xyb, ws.ev_slot, ws.ev_t, ws.start,
                                             ws.slot_tmp, ws.slot_it, ws.hot_list, hot_cap, ws.status);

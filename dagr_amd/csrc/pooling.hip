@@ -1057,8 +1057,7 @@ int launch_pool_l0_slots(const dagr_pool_desc *desc, const dagr_graph_desc *gdes
     DAGR_CHECK_ARG(desc->gx < 65536 && desc->gy < 65536 && VW < 32768, "voxel grid too large for the level-0 pooling kernel");
     // one 16-wave workgroup per CU is resident at a time (114 registers); wide rows run two rounds of shorter runs, which
     // overlaps one round's merge with the other's streaming (measured: 112 vs 127 us at 80 channels, 47 vs 44 us at 16)
-    static const int gmult_env = (int)knob("DAGR_POOL_GRID_MULT", 0);
-    const int gmult = gmult_env > 0 ? gmult_env : (C > 32 ? 2 : 1);
+    const int gmult = C > 32 ? 2 : 1;
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)gmult * device_cu_count(),
                                                                           ceil_div(n_cap, kPoolL0Block)));
 #define DAGR_POOL_L0_LAUNCH(AG, VEC)                                                                                  \

@@ -9,7 +9,6 @@ GEMM) per pooled conv -> dense head maps.  PyTorch supplies memory and the strea
 import contextlib
 import ctypes
 import gc
-import os
 import types
 
 import numpy as np
@@ -17,6 +16,10 @@ import torch
 
 from . import _lib
 from .graph.ev_graph import WindowGraphBuilder
+
+# convs whose rows are wider than the fused kernel's LDS tile run it in passes over the edges on levels of at most this
+# many node slots (it pays on small levels only); larger levels take tap aggregation + GEMM as two launches
+FUSED_PASSES_MAX_NODES = 1600
 
 
 def _f32(v):
@@ -168,7 +171,7 @@ class _Conv1x1Gemm(torch.nn.Module):
         return y.view(B, H, W, -1).permute(0, 3, 1, 2)
 
 
-_LT = {"ok": os.environ.get("DAGR_LT_RESIDUAL", "1") != "0", "ws": {}}
+_LT = {"ok": True, "ws": {}}
 
 
 def _lt_workspace(device):
@@ -258,7 +261,7 @@ def _resnet_features_forward(net, x, emit=None):
     mp = net.maxpool
     ok = (c1.is_cuda and c1.dtype == torch.float32 and c1.is_contiguous(memory_format=torch.channels_last)
           and c1.shape[1] % 4 == 0 and mp.kernel_size == 3 and mp.stride == 2 and mp.padding == 1
-          and mp.dilation == 1 and not mp.ceil_mode and hasattr(net, "_stem_affine"))
+          and mp.dilation == 1 and not mp.ceil_mode)
     if ok:
         B, C, H, W = c1.shape
         scale, shift = net._stem_affine
@@ -345,24 +348,18 @@ class WindowEngine:
         self._wg_post = self._graph_post = (None, None)
         self._post_fresh = False
         self._cnn_ready = None
-        # captured --use_image windows: graph levels start when THEIR feature map exists (builder knob to A/B)
-        self.pipeline_image = os.environ.get("DAGR_PIPELINE_IMAGE", "1") != "0"
         self._net_f = self._cnn_f = None
-        self.fuse_convs = os.environ.get("DAGR_FUSE_CONVS", "1") != "0"
-        # head scale 1's convs ride in the launches of layer5 / head scale 2 (dagr_spline_conv_fused_multi)
-        self.merge_heads = os.environ.get("DAGR_MERGE_HEADS", "1") != "0"
         self._tail_jobs = None
         self._inputs_gathered = False
-        self.fast_coarse_edges = os.environ.get("DAGR_FAST_COARSE_EDGES", "1") != "0"
-        self.fuse_pool_accumulate = os.environ.get("DAGR_FUSE_POOL", "1") != "0"
+        # level-0 pooling on the graph builder's offset codes (bitmap coarse edges); False: the generic coarse-edge path
+        self.fast_coarse_edges = True
         self._pool_accumulated = [False] * 4
-        self.fuse_image_epilogues = os.environ.get("DAGR_IMG_EPILOGUES", "1") != "0"
         # Latency mode (one window batch at a time, e.g. DAGR.forward): head scale 1 runs beside pool4 / layer5 / head scale
         # 2 and everything after pool1 is replayed as one HIP graph -- the host issues one launch instead of ~70.  When
         # several engines keep the GPU full on their own streams (bench.py's throughput rigs) both cost throughput
         # (measured, events-only, 3 engines: 696 M events/s plain, 620 M with the side stream, 594 M with graph replay),
         # so such callers switch it off with set_low_latency(False).
-        self.set_low_latency(os.environ.get("DAGR_LOW_LATENCY", "1") != "0")
+        self.set_low_latency(True)
         self._head_stream = self._head_join = self._graph = self._graph_out = None
         self._graph_warm = 0
         self._wg = self._wg_out = None       # the whole window as one captured HIP graph (latency mode)
@@ -412,8 +409,8 @@ class WindowEngine:
         # tiled kernel (csrc/conv_l0_tiles.hip) reads a 16-channel main block as 16-byte pieces, so with --use_image the
         # row is laid out [16 image feats | polarity | pos_xy | pad] (80 B); events-only [polarity | pos_xy | pad] (16 B).
         c0 = 1 + self.feat_ch[0] + 2
-        self.l0_tiles = (os.environ.get("DAGR_L0_TILES", "1") != "0" and (win[1], win[3]) in ((3, 3), (3, 5), (5, 3))
-                         and int(self.args.max_neighbors) == 16 and self.feat_ch[0] in (0, 16))
+        self.l0_tiles = ((win[1], win[3]) in ((3, 3), (3, 5), (5, 3)) and int(self.args.max_neighbors) == 16
+                         and self.feat_ch[0] in (0, 16))
         if self.l0_tiles:
             nf = self.feat_ch[0]
             self.x0_cols = list(range(1, 1 + nf)) + [0, 1 + nf, 2 + nf]      # reference channel of every x0 column
@@ -516,9 +513,6 @@ class WindowEngine:
                 pred=torch.zeros((T, 5 + self.num_classes), dtype=torch.float32, device=dev),
                 dense=torch.zeros((self.B, 5 + self.num_classes, Hc, Wc), dtype=torch.float32, device=dev)))
         self.status = torch.zeros((4,), dtype=torch.int32, device=dev)
-        self.fused_passes_max_nodes = int(os.environ.get("DAGR_FUSED_PASSES_MAX_NODES", "1600"))
-        # builder knob: levels with more node slots than this take tap aggregation + GEMM as two launches
-        self.fuse_max_nodes = int(os.environ.get("DAGR_FUSE_MAX_NODES", str(10 ** 9)))
         # a head whose table domain is not its input level's (num_scales = 1: head "1" on out4 with the pool3
         # table) gets its own LUT coordinates (dagr_pool_recode)
         self.head_code = []
@@ -536,11 +530,10 @@ class WindowEngine:
         self.stride_cache = torch.cat(strides, dim=1).float().to(dev)
 
     def set_low_latency(self, on):
-        self.overlap_heads = bool(on) and os.environ.get("DAGR_OVERLAP_HEADS", "1") != "0"
-        self.tail_graph = bool(on) and os.environ.get("DAGR_TAIL_GRAPH", "1") != "0"
+        self.overlap_heads = self.tail_graph = bool(on)
         # the WHOLE window (image branch, graph build, level 0, tail, heads, decode) as one HIP graph: every launch is sized
         # for the engine's event capacity and bounded by counts that live in device memory
-        self.window_graph = bool(on) and os.environ.get("DAGR_WINDOW_GRAPH", "1") != "0"
+        self.window_graph = bool(on)
         return self
 
     def _alloc_events(self, n):
@@ -746,8 +739,7 @@ class WindowEngine:
         code = lvl.code if code is None else code
         scratch = self.A if scratch is None else scratch
         passes = L.dagr_spline_conv_fused_passes(pack.cin, pack.cskip)
-        if self.fuse_convs and lvl.T <= self.fuse_max_nodes and \
-                (passes == 1 or (passes > 1 and lvl.T <= self.fused_passes_max_nodes)):
+        if passes == 1 or (passes > 1 and lvl.T <= FUSED_PASSES_MAX_NODES):
             # tap aggregation + contraction in one launch (A tile lives in LDS; rows wider than the tile in passes over
             # the edges, which pays on small levels only: tools/microbench/head_ab.hip)
             _lib.check(L.dagr_spline_conv_fused(P(lvl.counts), lvl.T, P(lvl.rowptr), P(lvl.col), P(code), x, ldx,
@@ -830,8 +822,7 @@ class WindowEngine:
             if hasattr(m, "conv") and hasattr(m, "bn") and isinstance(m.bn, torch.nn.BatchNorm2d):
                 m.conv = fuse_conv_bn_eval(m.conv, m.bn)
                 m.bn = torch.nn.Identity()
-                if self.fuse_image_epilogues and isinstance(getattr(m, "act", None), torch.nn.SiLU) \
-                        and m.conv.bias is not None:
+                if isinstance(getattr(m, "act", None), torch.nn.SiLU) and m.conv.bias is not None:
                     m._bias = m.conv.bias.detach().clone().contiguous()
                     m.conv.bias = None
                     m.forward = types.MethodType(_baseconv_forward, m)
@@ -841,22 +832,20 @@ class WindowEngine:
             _gemmify_1x1(getattr(net.module, blkname))
             for blk in getattr(net.module, blkname):
                 relu_convs = ("conv1", "conv2") if hasattr(blk, "conv3") else ("conv1",)
-                if self.fuse_image_epilogues:
-                    for cname in relu_convs:
-                        conv = getattr(blk, cname)
-                        if isinstance(conv, _Conv1x1Gemm):
-                            conv.relu = True                      # ReLU in the hipBLASLt epilogue
-                        elif isinstance(conv, torch.nn.Conv2d) and conv.bias is not None:
-                            setattr(blk, "_" + cname + "_bias", conv.bias.detach().clone().contiguous())
-                            conv.bias = None                      # bias + ReLU in one pass after the conv
+                for cname in relu_convs:
+                    conv = getattr(blk, cname)
+                    if isinstance(conv, _Conv1x1Gemm):
+                        conv.relu = True                      # ReLU in the hipBLASLt epilogue
+                    elif isinstance(conv, torch.nn.Conv2d) and conv.bias is not None:
+                        setattr(blk, "_" + cname + "_bias", conv.bias.detach().clone().contiguous())
+                        conv.bias = None                      # bias + ReLU in one pass after the conv
                 blk.forward = types.MethodType(_bottleneck_forward if hasattr(blk, "conv3") else _basicblock_forward,
                                                blk)
-        if self.fuse_image_epilogues:
-            bn = net.module.bn1
-            scale = (bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)).contiguous()
-            shift = (bn.bias.detach().float() - bn.running_mean.detach().float() * scale).contiguous()
-            net.module._stem_affine = (scale, shift)
-            net.module.forward_features = types.MethodType(_resnet_features_forward, net.module)
+        bn = net.module.bn1
+        scale = (bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)).contiguous()
+        shift = (bn.bias.detach().float() - bn.running_mean.detach().float() * scale).contiguous()
+        net.module._stem_affine = (scale, shift)
+        net.module.forward_features = types.MethodType(_resnet_features_forward, net.module)
         _gemmify_1x1(net.feature_dconv)
         _gemmify_1x1(net.output_dconv)
         self._net_f, self._cnn_f = net, cnn
@@ -869,7 +858,7 @@ class WindowEngine:
         bb, head = types.SimpleNamespace(net=self._net_f), types.SimpleNamespace(cnn_head=self._cnn_f)
         x = image.contiguous(memory_format=torch.channels_last)
         net = self._net_f
-        if on_feature is not None and hasattr(net.module, "_stem_affine"):
+        if on_feature is not None:
             feats = [None] * len(net.feature_layers)
 
             def emit(name, t):
@@ -883,9 +872,6 @@ class WindowEngine:
                 outs = [dconv(o) for o, dconv in zip(outs, net.output_dconv)]
         else:
             feats, outs = bb.net(x)
-            if on_feature is not None:              # unfolded trunk (DAGR_IMG_EPILOGUES=0): all maps exist only now
-                for j, f in enumerate(feats):
-                    on_feature(j, f)
         outs = outs[-self.num_scales:]
         resized = [torch.nn.functional.interpolate(f, o) for f, o in zip(outs, self.out_sizes)]
         return feats, head.cnn_head(resized)
@@ -1012,8 +998,7 @@ class WindowEngine:
         ldh = lvl.hp.shape[1]
         # events-only levels that are pooled next: launch (A) of that pooling (merge of every node into its cluster's
         # accumulators, coarse-edge sets) rides in this conv's epilogue -- one launch less per level
-        fuse_pool = (k < 3 and not self.use_image and self.fuse_convs and self.fuse_pool_accumulate
-                     and L.dagr_spline_conv_fused_passes(c2.cin, c2.cskip) == 1
+        fuse_pool = (k < 3 and not self.use_image and L.dagr_spline_conv_fused_passes(c2.cin, c2.cskip) == 1
                      and self.pool_desc[k + 1].channels == c2.N)
         self._pool_accumulated[k] = fuse_pool
         if fuse_pool:
@@ -1087,7 +1072,7 @@ class WindowEngine:
         five launches where the stream fork ran eight (three of them beside the others, + a fork and a join).  None when
         a conv of the plan needs the pass form (dagr-m / dagr-l heads) or a single scale exists."""
         L = self.L
-        if not (self.fuse_convs and self.merge_heads and len(self.head_levels) == 2 and self.head_levels[0] == 3):
+        if not (len(self.head_levels) == 2 and self.head_levels[0] == 3):
             return None
         c1, c2 = self.packs[3]
         packs = [c1, c2] + [p for hp in self.head_packs for p in hp]
@@ -1145,8 +1130,8 @@ class WindowEngine:
         # pred columns: [reg(4) | obj(1) | cls(num_classes)] = order of collect_outputs (dagr.py:300-302)
         x_reg, x_cls = ctypes.c_void_p(hb["cr"].data_ptr() + 4 * nr), P(hb["cr"])
         o_reg, o_cls = P(pred), ctypes.c_void_p(pred.data_ptr() + 4 * 5)
-        if self.fuse_convs and L.dagr_spline_conv_fused_passes(ro.cin, 0) >= 1 and \
-                (L.dagr_spline_conv_fused_passes(ro.cin, 0) == 1 or lvl.T <= self.fused_passes_max_nodes):
+        if L.dagr_spline_conv_fused_passes(ro.cin, 0) >= 1 and \
+                (L.dagr_spline_conv_fused_passes(ro.cin, 0) == 1 or lvl.T <= FUSED_PASSES_MAX_NODES):
             kcode = lvl.code if code is None else code
             _lib.check(L.dagr_spline_conv_fused_pair(P(lvl.counts), lvl.T, P(lvl.rowptr), P(lvl.col), P(kcode), 2 * nr, ro.cin,
                                                      dom["rx"], dom["ry"], dom["den_x"], dom["den_y"], npred, 0, x_reg,
@@ -1346,32 +1331,29 @@ class WindowEngine:
                     self.stage_graph(self.in_pos, self.in_batch, self.in_feat)
                     join = torch.cuda.Event()
                     join.record(self._head_stream)
-                if self.pipeline_image:
-                    # The graph levels do not wait for the whole image branch: level k samples feature map k (+ 1), which
-                    # exists as soon as ResNet stage k has run (net.py:110-184: the reference calls the CNN first, but its
-                    # outputs are consumed level by level).  The branch gets a stream of its own and records an event per
-                    # map; a B = 1 window is two chains of small dependent kernels, and the shorter one (the graph levels,
-                    # ~0.4 ms) now runs UNDER the longer one (the CNN, ~1.3 ms) instead of after it.
-                    if self._img_stream is None:
-                        self._img_stream = torch.cuda.Stream(self.device)
-                    s_img = self._img_stream
-                    s_img.wait_event(fork)
-                    self._feat_ready = {}
-                    self._keep = []
-                    with torch.cuda.stream(s_img):
-                        def on_feature(j, fmap):
-                            ev = torch.cuda.Event()
-                            ev.record(s_img)
-                            self._feat_ready[id(fmap)] = ev
-                            fmap.record_stream(cur)
-                        self._img_feats, self._cnn_out = self._image_branch(self.in_image, on_feature)
-                        for v in self._cnn_out.values():
-                            for o in v:
-                                o.record_stream(cur)
-                        self._cnn_ready = torch.cuda.Event()
-                        self._cnn_ready.record(s_img)
-                else:
-                    self.stage_image(self.in_image)
+                # The graph levels do not wait for the whole image branch: level k samples feature map k (+ 1), which
+                # exists as soon as ResNet stage k has run (net.py:110-184: the reference calls the CNN first, but its
+                # outputs are consumed level by level).  The branch gets a stream of its own and records an event per
+                # map; a B = 1 window is two chains of small dependent kernels, and the shorter one (the graph levels,
+                # ~0.4 ms) now runs UNDER the longer one (the CNN, ~1.3 ms) instead of after it.
+                if self._img_stream is None:
+                    self._img_stream = torch.cuda.Stream(self.device)
+                s_img = self._img_stream
+                s_img.wait_event(fork)
+                self._feat_ready = {}
+                self._keep = []
+                with torch.cuda.stream(s_img):
+                    def on_feature(j, fmap):
+                        ev = torch.cuda.Event()
+                        ev.record(s_img)
+                        self._feat_ready[id(fmap)] = ev
+                        fmap.record_stream(cur)
+                    self._img_feats, self._cnn_out = self._image_branch(self.in_image, on_feature)
+                    for v in self._cnn_out.values():
+                        for o in v:
+                            o.record_stream(cur)
+                    self._cnn_ready = torch.cuda.Event()
+                    self._cnn_ready.record(s_img)
                 cur.wait_event(join)
             else:
                 self.stage_graph(self.in_pos, self.in_batch, self.in_feat)
@@ -1480,8 +1462,8 @@ class WindowEngine:
         if self.l0_tiles:
             tx, ty = self.win0[1], self.win0[3]
             cm = 16 if c0 >= 16 else 0
-            return {"l0_conv1": f"k_conv_l0_tiles<{cm}, {c0 - cm}, 0, {tx}, {ty}, true>",     # (LEAN: csrc/conv_l0_tiles.hip:launch_tiles)
-                    "l0_conv2": f"k_conv_l0_tiles<16, 0, {c0}, {tx}, {ty}, true>"}
+            return {"l0_conv1": f"k_conv_l0_tiles<{cm}, {c0 - cm}, 0, {tx}, {ty}>",
+                    "l0_conv2": f"k_conv_l0_tiles<16, 0, {c0}, {tx}, {ty}>"}
         return {"l0_conv1": f"k_conv_l0<{c0}, 0, {nt}>", "l0_conv2": f"k_conv_l0<16, {c0}, {nt}>"}
 
     def check_status(self):

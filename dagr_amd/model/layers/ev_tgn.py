@@ -6,8 +6,6 @@ batch's (width, height, time_window, num_graphs), resets it on ``reset=True`` ca
 attach to the running graph.  ``DAGR.forward`` on whole ``reset=True`` windows does not go through it: the engine asks
 ``window_builder()`` for the fused single-window builder (csrc/graph_build.hip), which produces the same edge set as
 fixed-stride neighbour lists without the FIFO volume."""
-import os
-
 import torch
 
 from ...graph.ev_graph import SlidingWindowGraph, WindowGraphBuilder
@@ -84,7 +82,7 @@ class EV_TGN(torch.nn.Module):
     def forward(self, events, reset=True):
         if getattr(events, "batch", None) is None:
             events.batch = torch.zeros(events.pos.shape[0], dtype=torch.long, device=events.pos.device)
-        if self.training and reset and events.pos.is_cuda and os.environ.get("DAGR_TRAIN_FAST_GRAPH", "1") != "0":
+        if self.training and reset and events.pos.is_cuda:
             return self._training_graph(events)
         if self.graph_creators is None:
             self.init_graph_creator(events)

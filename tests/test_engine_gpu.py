@@ -698,21 +698,19 @@ def test_window_graph_with_the_image_branch():
     assert _decoded_err(eng, runs[-1][0], runs[-1][1].cpu()) > 1e-3      # the two windows are different windows
 
 
-def test_window_graph_with_the_unfolded_image_trunk(monkeypatch):
-    """``DAGR_IMG_EPILOGUES=0`` keeps torchvision's own trunk forward: the feature maps then exist only after the whole
-    branch, and the pipelined window must still order every sampler behind the image stream (the fallback
-    recorded no per-map event, so the graph levels read the maps without a dependency).  Same outputs as the default
-    (epilogue-folded) engine to the library kernels' rounding, and every sampled map had its event."""
+def test_pipelined_image_window_samples_every_map_after_its_event():
+    """In a captured --use_image window the image branch runs on a stream of its own and the graph levels start when
+    THEIR feature map exists: every sampler must be ordered behind the event of the map it reads (a trunk
+    forward that recorded no per-map event let the graph levels read the maps without a dependency).  Same outputs as
+    the launch-by-launch engine to the library kernels' rounding, and every sampled map had its event."""
     W, H, B = 320, 215, 2
     args, model, sd = _setup(W, H, B, seed=13, use_image=True, img_net="resnet18")
     win = _dev_window(syn.uniform_window, 4000, B, W, H, 51)
     img = torch.rand((B, 3, H, W), generator=torch.Generator().manual_seed(7)).cuda()
     with torch.no_grad():
         want = model.engine().forward_raw(*win, image=img, trace={}).clone()
-        monkeypatch.setenv("DAGR_IMG_EPILOGUES", "0")
         from dagr_amd.engine import WindowEngine
         eng = WindowEngine(model).set_low_latency(True)
-        assert not eng.fuse_image_epilogues and eng.pipeline_image
         seen = []
         sample0 = eng._sample
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """tools/graph_probe.py -- the window graph builder alone: time per build (HIP events) for a list of (stream, B, N)
-workloads and, with PROBE_CHECK=1, a digest of the event-ordered edge_index + offset codes (to A/B two builds of the
-library: DAGR_HIP_LIB=<path>; tools/graph_vs_oracle.py checks a build against the C oracle at full size).
+workloads and, with PROBE_CHECK=1, a digest of the event-ordered edge_index + offset codes (tools/graph_vs_oracle.py checks
+a build against the C oracle at full size).
 Builder tool: python tools/graph_probe.py uniform:8:100000 edges:8:100000 ..."""
 import hashlib
 import json

@@ -25,4 +25,4 @@ with torch.no_grad():
         out[f"B{B}_graph_ms"] = round(bench.time_gpu(g.replay, 10, warm=2), 4)
         del rig, eng, g
         torch.cuda.empty_cache()
-print(json.dumps(dict(lt_residual=os.environ.get("DAGR_LT_RESIDUAL", "1"), **out)))
+print(json.dumps(out))

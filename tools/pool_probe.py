@@ -22,7 +22,6 @@ with torch.no_grad():
         acc = bench.time_gpu(eng.pool1_accumulate_again, 30)
         eng.stage_pool1()
         full = bench.time_gpu(eng.stage_pool1, 30)
-        print(json.dumps({"spec": spec, "exp": os.environ.get("DAGR_POOL_EXP", "0"), "grid_mult": os.environ.get("DAGR_POOL_GRID_MULT", "4"),
-                          "accumulate_us": round(1e3 * acc, 1), "pool1_us": round(1e3 * full, 1)}), flush=True)
+        print(json.dumps({"spec": spec, "accumulate_us": round(1e3 * acc, 1), "pool1_us": round(1e3 * full, 1)}), flush=True)
         del rig, eng
         torch.cuda.empty_cache()
