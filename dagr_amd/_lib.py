@@ -210,6 +210,10 @@ SIGNATURES = {
                                           c_i32, c_i32, c_i32, c_i32, c_void_p]),
     "dagr_async_flops": (ctypes.c_int, [c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p,
                                         c_void_p]),
+    "dagr_viz_workspace_bytes": (c_size_t, [c_i32, c_i32, c_i32]),
+    "dagr_viz_render": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32,
+                                       c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

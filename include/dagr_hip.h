@@ -633,6 +633,34 @@ int dagr_async_flops(const int32_t *deg, int32_t n_events, const int32_t *counts
                      const int32_t *counts3, const int32_t *counts4, const dagr_flops_module *mods, int32_t n_mods,
                      int64_t *out, void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * Visualisation frames -- visualization/event_viz.py:3-10, the outlines of visualization/bbox_viz.py:11-53,
+ * scripts/visualize_detections.py:58-78.  F independent frames in one call; frame f is:
+ *   images[frame_image[f]]  its base image, uint8 BGR [H, W, 3], one of n_images stacked images
+ *   events [ev_ptr[f], ev_ptr[f+1])  of the concatenated ev_x / ev_y (int32) and ev_p (int8); ev_ptr[F + 1] (device),
+ *                           n_events = ev_ptr[F]
+ *   alpha[f]                float64 in [0, 1] (device)
+ *   boxes [box_ptr[f], box_ptr[f+1])  of boxes[n_boxes, 5] int32 (x0, y0, x1, y1, class id); box_ptr NULL = no boxes
+ * out[F, H, W, 3] uint8.  Events, exactly as the reference's loop: a pixel hit by at least one event of the frame becomes
+ * trunc(alpha * base) on every channel, then channel p - 1 (wrapped like a Python index: p = 0 -> 2, p = 1 -> 0,
+ * p = -1 -> 1) of the LAST such event, in array order, becomes trunc(that + 255 * (1 - alpha)); float64 arithmetic.
+ * Events with y >= H are skipped as in the reference; so are x >= W (unchecked there) and negative coordinates.
+ * Outlines, this project's own rule (OpenCV's thick-line rasteriser is not reproduced): pixel q lies on a box's outline
+ * when its Chebyshev distance to the border of the rectangle [min(x0, x1), max(x0, x1)] x [min(y0, y1), max(y0, y1)] is
+ * <= linewidth / 2 (integer division): linewidth 1 = the one-pixel border, 2 and 3 = a three-pixel band centred on it.
+ * Clipped to the image; painted in colors[3 * class id ..] after the events; a later box of the frame wins.
+ * workspace: dagr_viz_workspace_bytes(F, H, W) (per-pixel last event index).  status (device int32, zeroed here):
+ * bit0 an event's p - 1 outside [-3, 2] (the event is dropped), bit1 a drawn class id outside [0, n_colors), bit2 a
+ * frame_image entry outside [0, n_images) (the frame is not written), bit3 an alpha outside [0, 1] (events not drawn).
+ * `out` may alias `images` only when frame_image[f] == f for every f (each thread reads its pixel before writing it).
+ * ------------------------------------------------------------------------ */
+size_t dagr_viz_workspace_bytes(int32_t F, int32_t H, int32_t W);
+int dagr_viz_render(const uint8_t *images, int32_t n_images, int32_t H, int32_t W, const int32_t *frame_image, int32_t F,
+                    const int32_t *ev_x, const int32_t *ev_y, const int8_t *ev_p, const int32_t *ev_ptr, int32_t n_events,
+                    const double *alpha, const int32_t *boxes, const int32_t *box_ptr, int32_t n_boxes, int32_t linewidth,
+                    const uint8_t *colors, int32_t n_colors, uint8_t *out, int32_t *status, void *workspace,
+                    size_t workspace_bytes, void *stream);
+
 /* Host-side helper: first n offsets of the search spiral (spiral.h:1-15), the closed form the
  * search kernel uses.  dx/dy are HOST arrays.  Lets CPU-only tests pin the visiting order. */
 int dagr_spiral_offsets(int32_t n, int32_t *dx_host, int32_t *dy_host);
