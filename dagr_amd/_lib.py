@@ -214,6 +214,15 @@ SIGNATURES = {
     "dagr_viz_render": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32,
                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dagr_augment_workspace_bytes": (c_size_t, [c_i64]),
+    "dagr_augment_events": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_i32,
+                                           c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_size_t, c_void_p]),
+    "dagr_augment_status": (ctypes.c_int, [c_void_p, c_void_p]),
+    "dagr_augment_frames": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p,
+                                           c_void_p]),
+    "dagr_augment_boxes": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_i32, c_i32, c_void_p,
+                                          c_void_p]),
 }
 
 _lib = None

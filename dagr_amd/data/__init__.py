@@ -152,7 +152,12 @@ class DataLoader:
                 rank, world = self.shard
                 per = len(idx) // world
                 idx = idx[rank * per:(rank + 1) * per]
-            yield Batch.from_data_list([self._fetch(i) for i in idx], follow_batch=self.follow_batch)
+            batch = Batch.from_data_list([self._fetch(i) for i in idx], follow_batch=self.follow_batch)
+            if self.shuffle:
+                # what seeded each sample's augmentations: a transform applied to the collated batch instead
+                # (DeviceAugmentations) draws from the same per-sample states, whatever the rank and the batch
+                batch._sample_seeds = [self.sample_seed(i) for i in idx]
+            yield batch
 
     def image_ids(self, step):
         """Global positions, in the run, of the images of the ``step``-th batch THIS loader yields: batch k of the run
@@ -166,6 +171,10 @@ class DataLoader:
             ids = ids[rank * per:(rank + 1) * per]
         return ids
 
+    def sample_seed(self, i):
+        """Seed of sample i's random augmentations in the current epoch: a function of (seed, epoch, i) alone."""
+        return (self.seed * 1000003 + self.epoch) * 1000003 + int(i)
+
     def _fetch(self, i):
         """Sample i of this epoch.  Shuffled (training) loaders draw the sample's random augmentations from a generator
         state derived from (seed, epoch, i), inside a forked RNG scope: the same sample is augmented the same way whatever
@@ -173,5 +182,5 @@ class DataLoader:
         if not self.shuffle:
             return self.dataset[i]
         with torch.random.fork_rng(devices=[]):
-            torch.manual_seed((self.seed * 1000003 + self.epoch) * 1000003 + int(i))
+            torch.manual_seed(self.sample_seed(i))
             return self.dataset[i]

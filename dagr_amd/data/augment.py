@@ -3,6 +3,8 @@
 flip (:90-112), random crop with probability 0.2 (:201-243), random zoom (:148-198), random translation (:246-279), then
 the crop to the sensor.  All of them act on the per-sample ``Data`` BEFORE the graph exists (host side, integer pixel
 coordinates), exactly where the reference applies them (the loaders' ``transform``)."""
+import copy
+
 import numpy as np
 import torch
 
@@ -260,11 +262,155 @@ class RandomTranslate:
         return data
 
 
+# ``dagr_aug_params`` (include/dagr_hip.h): one record per sample, drawn on the host, read by the kernels on the device
+AUG_PARAMS = np.dtype([("flip", "<i4"), ("crop_on", "<i4"), ("crop_lo", "<i4", 2), ("crop_hi", "<i4", 2), ("zoom", "<f4"),
+                       ("move", "<i4", 2)])
+
+
+class DeviceAugmentations:
+    """The training chain of ``Augmentations`` (flip, random crop, zoom, translate, crop to the sensor) applied to a
+    collated ``Batch`` that is already on the device (``dagr_augment_events`` / ``_frames`` / ``_boxes``, csrc/augment.hip).
+    The random numbers still come from torch's RNG on the host, drawn call for call as the host chain draws them for one
+    sample after another, so under one seed both chains make the same decisions and leave the same RNG state.  A batch
+    from a shuffling ``DataLoader`` carries the per-sample seeds the loader gives the host chain (``_sample_seeds``, a
+    function of (seed, epoch, sample) alone); its records are drawn from those, each in a forked RNG scope: a sample is
+    augmented the same way whatever the rank, the world size or the batch it arrives in, and as the host chain in the
+    loader would have augmented it.
+
+    ``RandomZoom(subsample=True)`` with a factor below 1 (a sequential integrate-and-fire pass over the events) has no
+    device form: ``aug_zoom < 1`` raises here; use the host chain (``Augmentations(args).transform_training``) for it."""
+
+    def __init__(self, args):
+        if float(args.aug_zoom) < 1:
+            raise ValueError(f"DeviceAugmentations: aug_zoom = {args.aug_zoom} < 1 needs RandomZoom's event subsampling, "
+                             "which only the host chain (Augmentations.transform_training) implements")
+        self.p_flip = float(args.aug_p_flip)
+        self.zoom = [1, args.aug_zoom]
+        # the host transforms own the pixel sizes (their ``init``): the same roundings by construction
+        self._crop = RandomCrop([0.75, 0.75], p=0.2)
+        self._translate = RandomTranslate([args.aug_trans, args.aug_trans, 0])
+        self.height = self.width = None
+
+    def init(self, height, width):
+        self._crop.init(height, width)
+        self._translate.init(height, width)
+        self.height, self.width = int(height), int(width)
+
+    def draw(self, n, seeds=None):
+        """``n`` parameter records (numpy, dtype ``AUG_PARAMS``) from torch's global RNG: per sample ``rand(1)`` (flip),
+        ``rand(1)`` (crop coin) and ``rand(2)`` only when it hits, ``rand(1)`` (zoom), ``rand(2)`` (shift) -- the calls, order,
+        dtypes and roundings of RandomHFlip / RandomCrop / RandomZoom / RandomTranslate.  With ``seeds`` (n ints) record k
+        is drawn after ``manual_seed(seeds[k])`` inside a forked RNG scope, as ``DataLoader._fetch`` runs the host chain;
+        the global stream is then left untouched."""
+        if self.width is None:
+            raise RuntimeError("DeviceAugmentations.init(height, width) has not been called")
+        if seeds is not None:
+            if len(seeds) != int(n):
+                raise ValueError(f"{len(seeds)} seeds for {n} records")
+            out = np.zeros(int(n), dtype=AUG_PARAMS)
+            for k, s in enumerate(seeds):
+                with torch.random.fork_rng(devices=[]):
+                    torch.manual_seed(int(s))
+                    out[k] = self.draw(1)[0]
+            return out
+        out = np.zeros(int(n), dtype=AUG_PARAMS)
+        size = self._crop.size.to(torch.int16)
+        for rec in out:
+            rec["flip"] = 0 if float(torch.rand(1)) > self.p_flip else 1
+            if not float(torch.rand(1)) > self._crop.p:
+                left = (torch.rand(len(self._crop.dim)) * self._crop.left_max).to(torch.int16)
+                rec["crop_on"], rec["crop_lo"], rec["crop_hi"] = 1, left.numpy(), (left + size).numpy()
+            rec["zoom"] = (torch.rand(1) * (self.zoom[1] - self.zoom[0]) + self.zoom[0]).numpy()[0]
+            rec["move"] = (self._translate.px * (torch.rand(2) * 2 - 1)).to(torch.int16).numpy()
+        return out
+
+    def __call__(self, batch, params=None):
+        """A new ``Batch`` with the fields of ``batch`` (``pos`` int16 / int32 ``[N, 2]`` pixels, ``x``, ``t``, ``batch``,
+        optionally ``image`` ``[B, C, H, W]`` uint8 / fp32 and ``bbox`` / ``bbox0`` with their ``*_batch`` vectors), augmented;
+        ``pos`` comes back int16 as from the host chain.  ``params``: records of ``draw`` (default: ``draw(B)`` now, from the
+        batch's per-sample seeds when a shuffling ``DataLoader`` made it, else from the global RNG).
+        Everything is queued on the current stream; the call synchronises once, to read ``out_ptr[B]`` (the number of
+        surviving events, which sizes the outputs) together with the status word."""
+        if self.width is None:
+            geo = getattr(batch, "_geometry", None)
+            if geo is None:
+                raise RuntimeError("DeviceAugmentations.init(height, width) has not been called")
+            self.init(geo[1], geo[0])
+        W, H = self.width, self.height
+        pos, t, x = batch.pos, batch.t, batch.x
+        if not pos.is_cuda:
+            raise RuntimeError("DeviceAugmentations works on a batch that is on the GPU (batch.cuda() first); the host "
+                               "chain is Augmentations.transform_training")
+        if pos.dtype not in (torch.int16, torch.int32) or pos.dim() != 2 or pos.shape[1] != 2:
+            raise TypeError(f"pos must be int16 / int32 [N, 2] pixel coordinates, got {pos.dtype} {tuple(pos.shape)}")
+        dev, N, B = pos.device, int(pos.shape[0]), int(batch.num_graphs)
+        if t.shape[0] != N or x.shape[0] != N or x.numel() != N or t.numel() != N:
+            raise ValueError("pos, x and t must describe the same N events, one value each")
+        if t.element_size() not in (4, 8):
+            raise TypeError(f"t must have 4- or 8-byte entries, got {t.dtype}")
+        if params is None:
+            params = self.draw(B, getattr(batch, "_sample_seeds", None))
+        params = np.ascontiguousarray(params, dtype=AUG_PARAMS)
+        if len(params) != B:
+            raise ValueError(f"{len(params)} parameter records for a batch of {B} samples")
+        par = torch.from_numpy(params.view(np.int32).reshape(B, -1)).to(dev, non_blocking=True)
+        # the segment bounds from the (sorted) sample vector, on the device: no read-back, and right for any batch
+        ptr = torch.searchsorted(batch.batch.contiguous(), torch.arange(B + 1, device=dev)).to(torch.int32)
+        return self._run(batch, par, ptr, pos.contiguous(), t.contiguous(), x.contiguous(), B, W, H)
+
+    def _run(self, batch, par, ptr, pos, t, x, B, W, H):
+        from .. import _lib
+        L, dev, N = _lib.lib(), pos.device, int(pos.shape[0])
+        stream = _lib.cur_stream(dev)
+        out_pos, out_t, out_x = torch.empty((N, 2), dtype=torch.int16, device=dev), torch.empty_like(t), torch.empty_like(x)
+        out_batch = torch.empty(N, dtype=torch.long, device=dev)
+        meta = torch.empty(B + 2, dtype=torch.int32, device=dev)           # out_ptr[B + 1], then the status word
+        status = meta[B + 1:]
+        ws_bytes = L.dagr_augment_workspace_bytes(N)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.dagr_augment_events(_lib.ptr(par), B, W, H, _lib.ptr(pos), pos.element_size(), _lib.ptr(t),
+                                             t.element_size(), _lib.ptr(x), x.element_size(), _lib.ptr(ptr), N,
+                                             _lib.ptr(out_pos), _lib.ptr(out_t), _lib.ptr(out_x), _lib.ptr(out_batch),
+                                             _lib.ptr(meta), _lib.ptr(status), _lib.ptr(ws), ws_bytes, stream),
+                       "augment_events")
+            out = copy.copy(batch)
+            image = getattr(batch, "image", None)
+            if torch.is_tensor(image):
+                if image.dim() != 4 or image.shape[0] != B or tuple(image.shape[-2:]) != (H, W) \
+                        or image.dtype not in (torch.uint8, torch.float32):
+                    raise TypeError(f"image must be uint8 / float32 [{B}, C, {H}, {W}], got {image.dtype} {tuple(image.shape)}")
+                image = image.contiguous()
+                out.image = torch.empty_like(image)
+                _lib.check(L.dagr_augment_frames(_lib.ptr(par), B, int(image.shape[1]), H, W, image.element_size(),
+                                                 1 if REFERENCE_FRAME_CROP else 0, _lib.ptr(image), _lib.ptr(out.image),
+                                                 stream), "augment_frames")
+            for name in ("bbox", "bbox0"):
+                b = getattr(batch, name, None)
+                if not torch.is_tensor(b) or b.shape[0] == 0:
+                    continue
+                rows = b.to(torch.float32).contiguous()
+                new = torch.empty_like(rows)
+                _lib.check(L.dagr_augment_boxes(_lib.ptr(par), B, W, H, _lib.ptr(rows),
+                                                _lib.ptr(getattr(batch, name + "_batch").to(torch.long).contiguous()),
+                                                int(rows.shape[0]), int(rows.shape[1]), _lib.ptr(new), stream),
+                           "augment_boxes")
+                setattr(out, name, new.to(b.dtype))
+            n_out, st = meta[B:].tolist()                                  # the one synchronisation of the call
+            if st:
+                _lib.check(L.dagr_augment_status(_lib.ptr(status), stream), "augment_events")
+        out.pos, out.t, out.x, out.batch = out_pos[:n_out], out_t[:n_out], out_x[:n_out], out_batch[:n_out]
+        out.__dict__["_event_ptr"] = meta[:B + 1]
+        return out
+
+
 class Augmentations:
     transform_testing = Compose([Crop([0, 0], [1, 1])])
 
     def __init__(self, args):
         """augment.py:287-294: the training chain, parameterised by ``aug_p_flip`` / ``aug_zoom`` / ``aug_trans``."""
+        self._args = args
+        self._device_chain = None
         self.transform_training = Compose([
             RandomHFlip(p=args.aug_p_flip),
             RandomCrop([0.75, 0.75], p=0.2),
@@ -272,3 +418,10 @@ class Augmentations:
             RandomTranslate([args.aug_trans, args.aug_trans, 0]),
             Crop([0, 0], [1, 1]),
         ])
+
+    @property
+    def transform_training_device(self):
+        """The same chain for a collated batch on the GPU (``DeviceAugmentations``; built on first use)."""
+        if self._device_chain is None:
+            self._device_chain = DeviceAugmentations(self._args)
+        return self._device_chain

@@ -661,6 +661,54 @@ int dagr_viz_render(const uint8_t *images, int32_t n_images, int32_t H, int32_t 
                     const uint8_t *colors, int32_t n_colors, uint8_t *out, int32_t *status, void *workspace,
                     size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * Training augmentations on a collated batch on the device -- src/dagr/data/augment.py: RandomHFlip :90-112,
+ * RandomZoom :148-198, RandomCrop(p = 0.2) :201-243, RandomTranslate :246-279, Crop([0, 0], [1, 1]) :115-145, chained as
+ * Augmentations.__init__ :287-294 chains them.  The random draws are made on the host; the kernels read one record per
+ * sample from DEVICE memory:
+ *   flip            != 0: x = W - 1 - x
+ *   crop_on         != 0: only events with crop_lo <= (x, y) <= crop_hi (both ends inclusive) stay; not shifted
+ *   zoom            fp32 factor about (W / 2, H / 2): (float(x) - cx) * zoom + cx, two roundings, truncated to int16.
+ *                   zoom < 1 shrinks without the reference's integrate-and-fire subsampling (subsample = False).
+ *   move            whole-pixel shift added after the zoom; then only 0 <= x < W, 0 <= y < H stays.
+ *
+ * dagr_augment_events: pos[N, 2] (int16: pos_width 2, int32: pos_width 4), t[N] (t_width bytes per entry, 4 or 8) and
+ * p[N] (p_width bytes, 1 / 2 / 4 / 8); t and p are copied as they are and carry no range check; sample b owns [sample_ptr[b], sample_ptr[b + 1]),
+ * sample_ptr[B + 1] int32 on the device.  Survivors are written densely in their input order: out_pos[., 2] int16, out_t,
+ * out_p (the input widths), out_batch (int64 sample index, may be NULL), out_ptr[B + 1] their segment bounds.  All
+ * outputs hold N entries; out_ptr[B] tells how many are used.  Two launches up to 4 M events (beyond: a scan of the
+ * per-tile counts between them), no host synchronisation.  workspace: dagr_augment_workspace_bytes(N) bytes, no initial
+ * state.  status (device int32, zeroed here): bit0 sample_ptr does not run from 0 to N without decreasing (nothing is
+ * written but zeros to out_ptr), bit1 an int32 coordinate outside int16 (that event is dropped).
+ * dagr_augment_status reads it (synchronises the stream) and returns DAGR_ERR_INVALID_ARG with a message if a bit is set.
+ *
+ * dagr_augment_frames: out[B, C, H, W] from in[B, C, H, W] (elem_bytes 1: uint8, 4: fp32; in != out), one thread per output
+ * pixel walking the chain backwards: undo the shift (black outside), undo the zoom (torch's `nearest` source index of a
+ * resize to (ceil(H zoom), ceil(W zoom)), centre-cropped or centre-padded to the sensor), blank by the crop window, undo
+ * the flip.  reference_crop != 0 blanks as augment.py:51-58 does (the window indexes the batch and channel dimensions
+ * of the sample's [1, C, H, W] frame: crop_lo[1] > 0 blanks the frame, crop_lo[0] = c blanks channels < c, crop_hi[0]
+ * bounds them above); 0 blanks rows outside [crop_lo[1], crop_hi[1]) and columns outside [crop_lo[0], crop_hi[0]).
+ *
+ * dagr_augment_boxes: rows of `ld` >= 4 fp32 columns (x, y, w, h first; the others are copied), box_batch[M] int64 their
+ * samples: mirrored, clamped to the window, scaled, shifted and clamped to the sensor as the boxes of the chain are.
+ * ------------------------------------------------------------------------ */
+typedef struct dagr_aug_params {
+    int32_t flip, crop_on;
+    int32_t crop_lo[2], crop_hi[2];
+    float zoom;
+    int32_t move[2];
+} dagr_aug_params;
+size_t dagr_augment_workspace_bytes(int64_t N);
+int dagr_augment_events(const dagr_aug_params *params, int32_t B, int32_t W, int32_t H, const void *pos, int32_t pos_width,
+                        const void *t, int32_t t_width, const void *p, int32_t p_width, const int32_t *sample_ptr, int64_t N,
+                        int16_t *out_pos, void *out_t, void *out_p, int64_t *out_batch, int32_t *out_ptr,
+                        int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+int dagr_augment_status(const int32_t *status, void *stream);
+int dagr_augment_frames(const dagr_aug_params *params, int32_t B, int32_t C, int32_t H, int32_t W, int32_t elem_bytes,
+                        int32_t reference_crop, const void *in, void *out, void *stream);
+int dagr_augment_boxes(const dagr_aug_params *params, int32_t B, int32_t W, int32_t H, const float *boxes,
+                       const int64_t *box_batch, int32_t M, int32_t ld, float *out, void *stream);
+
 /* Host-side helper: first n offsets of the search spiral (spiral.h:1-15), the closed form the
  * search kernel uses.  dx/dy are HOST arrays.  Lets CPU-only tests pin the visiting order. */
 int dagr_spiral_offsets(int32_t n, int32_t *dx_host, int32_t *dy_host);

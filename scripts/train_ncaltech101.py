@@ -56,6 +56,9 @@ def flags(argv=None, preset="ncaltech101"):
         g.add_argument("--val_samples", type=int, default=64)
         g.add_argument("--max_iters", type=int, default=-1, help="stop after this many iterations (smoke runs)")
         g.add_argument("--resume_checkpoint", type=Path, default=None)
+        # (absent from the namespace unless given: the reference's command lines parse to the reference's namespaces)
+        g.add_argument("--augment_on_device", action="store_true", default=argparse.SUPPRESS,
+                       help="run the training augmentations on the GPU, on each collated batch, instead of in the loader")
     argv = list(sys.argv[1:] if argv is None else argv)
     widths = {}
     if preset == "ncaltech101" and "--config" in argv:
@@ -86,10 +89,13 @@ def fix_gradients(model):
             torch.nan_to_num_(p.grad, nan=0.0)
 
 
-def train_epoch(loader, net, module, ema, scheduler, optimizer, clip, dev, log, max_iters=-1):
+def train_epoch(loader, net, module, ema, scheduler, optimizer, clip, dev, log, max_iters=-1, device_aug=None):
     net.train()
     for data in loader:
-        data = format_data(data.to(dev, non_blocking=True))
+        data = data.to(dev, non_blocking=True)
+        if device_aug is not None:            # --augment_on_device: the loader's samples are untransformed
+            data = device_aug(data)
+        data = format_data(data)
         optimizer.zero_grad(set_to_none=True)
         out = net(data)
         loss = out["total_loss"]
@@ -150,20 +156,23 @@ def build(a, world, rank, dev, model_factory=None, preset="ncaltech101"):
     # batch_size is this replica's share of the global batch
     args = argparse.Namespace(**dict(vars(a), batch_size=per_rank))
     aug = Augmentations(args)
+    # --augment_on_device: no host transform at all on the training samples; main() runs aug.transform_training_device
+    # (which ends in the same crop to the sensor) on every collated batch
+    train_tf = None if getattr(a, "augment_on_device", False) else aug.transform_training
     real = C.real_data_available(a, "DSEC" if preset == "dsec" else "N-Caltech101")
     if real and preset == "dsec":
         from dagr.data.dsec_data import DSEC                    # train_dsec.py:122,125-128
         root = a.dataset_directory / args.dataset
-        train_ds = DSEC(root=root, split="train", transform=aug.transform_training, min_bbox_diag=15, min_bbox_height=10)
+        train_ds = DSEC(root=root, split="train", transform=train_tf, min_bbox_diag=15, min_bbox_height=10)
         val_ds = DSEC(root=root, split="val", transform=aug.transform_testing, min_bbox_diag=15, min_bbox_height=10)
     elif real:
         from dagr.data.ncaltech101_data import NCaltech101      # train_ncaltech101.py:122-125
         root = a.dataset_directory / args.dataset
-        train_ds = NCaltech101(root, "training", aug.transform_training, num_events=args.n_nodes)
+        train_ds = NCaltech101(root, "training", train_tf, num_events=args.n_nodes)
         val_ds = NCaltech101(root, "validation", aug.transform_testing, num_events=args.n_nodes)
     else:
         size = dict(width=320, height=215, use_image=a.use_image) if preset == "dsec" else {}
-        train_ds = SyntheticObjects(a.samples, min(args.n_nodes, 20000), seed=7, transform=aug.transform_training, **size)
+        train_ds = SyntheticObjects(a.samples, min(args.n_nodes, 20000), seed=7, transform=train_tf, **size)
         val_ds = SyntheticObjects(a.val_samples, min(args.n_nodes, 20000), seed=100007, transform=aug.transform_testing,
                                   **size)
     follow = ["bbox", "bbox0"]
@@ -191,6 +200,12 @@ def main(argv=None, model_factory=None, preset="ncaltech101"):
     if rank == 0:
         log_hparams(args)
         print(f"Training with {sum(p.numel() for p in model.parameters())} number of parameters.")
+    device_aug = None
+    if getattr(a, "augment_on_device", False):
+        if dev.type != "cuda":
+            raise RuntimeError("--augment_on_device needs a GPU; without the flag the augmentations run in the loader")
+        device_aug = Augmentations(args).transform_training_device
+        device_aug.init(train_loader.dataset.height, train_loader.dataset.width)
     ema = ModelEMA(model)
     # (DAGR_FORCE_DDP=1 wraps a single process too: exercises the reducer on one GPU)
     ddp = world > 1 or (os.environ.get("DAGR_FORCE_DDP") == "1" and torch.distributed.is_initialized())
@@ -213,7 +228,7 @@ def main(argv=None, model_factory=None, preset="ncaltech101"):
     log = []
     t0 = time.perf_counter()
     for epoch in range(start_epoch, args.tot_num_epochs):
-        stop = train_epoch(train_loader, net, model, ema, scheduler, optimizer, args.clip, dev, log, a.max_iters)
+        stop = train_epoch(train_loader, net, model, ema, scheduler, optimizer, args.clip, dev, log, a.max_iters, device_aug)
         if rank == 0:
             ckpt.checkpoint(epoch, name="last_model")
             tail = log[-len(train_loader):] or log
