@@ -245,6 +245,8 @@ __device__ __forceinline__ void postprocess_image(const float *__restrict__ p, i
     __syncthreads();
     greedy_suppress(A, s_box, s_keep, nms_thr, s_mask);
     // front-compaction: thread t owns the 4 consecutive sorted positions 4t .. 4t+3
+    // block_exclusive_scan adds up the first four waves' totals only: every position must belong to one of their 256 threads
+    static_assert(kMaxAnchors <= 4 * kBlock, "positions beyond 4 * 256 would fall to waves the scan does not add up");
     int mine[4], cnt = 0;
 #pragma unroll
     for (int u = 0; u < 4; u++) {
