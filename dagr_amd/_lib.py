@@ -182,6 +182,16 @@ SIGNATURES = {
                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
                                                c_i32, c_i32, c_void_p]),
     "dagr_async_update": (ctypes.c_int, [ctypes.POINTER(AsyncUpdateArgs), c_void_p]),
+    # the level-0 widths 8 / 16 / 32: the width leads the argument list of the 16-column entry points
+    "dagr_spline_conv_l0_tiles_w": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                                   c_float, c_float, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_i32,
+                                                   c_void_p, c_void_p]),
+    "dagr_spline_conv_l0_tiles_rows_w": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                                        c_float, c_float, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_void_p,
+                                                        c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p,
+                                                        c_i32, c_void_p, c_void_p]),
+    "dagr_async_update_w": (ctypes.c_int, [ctypes.POINTER(AsyncUpdateArgs), c_i32, c_void_p]),
     "dagr_pool_l0_stream": (ctypes.c_int, [ctypes.POINTER(PoolDesc), c_void_p, c_i32, ctypes.POINTER(GraphDesc), c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_i64, c_i64,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p,

@@ -21,6 +21,15 @@ from .graph.ev_graph import WindowGraphBuilder
 # many node slots (it pays on small levels only); larger levels take tap aggregation + GEMM as two launches
 FUSED_PASSES_MAX_NODES = 1600
 
+# level-0 widths the engine's kernels exist for: Net's int(base_width * 32) (csrc/conv_l0_tiles.hip)
+L0_WIDTHS = (8, 16, 32)
+
+
+def _l0_block(c):
+    """Split a level-0 row of ``c`` channels into the tiled kernel's (main block, extras): the block is 0, 8, 16 or 32."""
+    cm = max(b for b in (0,) + L0_WIDTHS if b <= c)
+    return cm, c - cm
+
 
 def _f32(v):
     """Value of ``v`` (python float or 0-dim tensor) as the fp32 torch would compute with."""
@@ -100,14 +109,15 @@ def _pack_generic(convs, norms, skip=None, relu=True, device="cuda"):
 
 
 def _pack_l0(conv, norm, win, skip=None, device="cuda", cols_in=None, cols_skip=None):
-    """Level-0 packing: rows [(a + tx*b)*cin + i | root | skip] x 16 over the tx x ty tap window.
+    """Level-0 packing: rows [(a + tx*b)*cin + i | root | skip] x cout over the tx x ty tap window.
     ``cols_in`` / ``cols_skip``: reference channel behind every column of the input / skip-input rows as the engine
     lays them out (identity when None)."""
     win_x, tx, win_y, ty = win
     W = conv.weight.detach().float()
     cin, cout = W.shape[1], W.shape[2]
-    if cout != 16:
-        raise NotImplementedError("the level-0 kernels are specialised for 16 output channels (base_width = 0.5)")
+    if cout not in L0_WIDTHS:
+        raise NotImplementedError(f"the level-0 kernels exist for {', '.join(map(str, L0_WIDTHS))} output channels "
+                                  f"(base_width = 0.25, 0.5, 1.0), not {cout}")
     cols_in = list(range(cin)) if cols_in is None else list(cols_in)
     scale, shift = _bn_affine(norm)
     rows = []
@@ -406,11 +416,16 @@ class WindowEngine:
             raise RuntimeError("level-0 offset table: an offset needs a kernel tap outside the chosen window")
         l0 = layers[0]
         # Input row of level 0.  Reference channel order (net.py:118,124-125): [polarity | image feats | pos_xy].  The
-        # tiled kernel (csrc/conv_l0_tiles.hip) reads a 16-channel main block as 16-byte pieces, so with --use_image the
-        # row is laid out [16 image feats | polarity | pos_xy | pad] (80 B); events-only [polarity | pos_xy | pad] (16 B).
+        # tiled kernel (csrc/conv_l0_tiles.hip) reads a main block of cout0 channels as 16-byte (8-byte: cout0 = 8) pieces,
+        # so with --use_image the row is laid out [cout0 image feats | polarity | pos_xy | pad] (80 B at 16); events-only
+        # [polarity | pos_xy | pad] (16 B).
         c0 = 1 + self.feat_ch[0] + 2
+        self.cout0 = int(l0.conv_block1.conv.weight.shape[2])     # Net: int(base_width * 32)
         self.l0_tiles = ((win[1], win[3]) in ((3, 3), (3, 5), (5, 3)) and int(self.args.max_neighbors) == 16
-                         and self.feat_ch[0] in (0, 16))
+                         and self.feat_ch[0] in (0, self.cout0))
+        if self.cout0 != 16 and not self.l0_tiles:
+            raise NotImplementedError("level-0 widths other than 16 run on the tiled level-0 conv only (16 neighbours, "
+                                      "3x3 / 3x5 / 5x3 tap window); supported widths: " + ", ".join(map(str, L0_WIDTHS)))
         if self.l0_tiles:
             nf = self.feat_ch[0]
             self.x0_cols = list(range(1, 1 + nf)) + [0, 1 + nf, 2 + nf]      # reference channel of every x0 column
@@ -424,6 +439,8 @@ class WindowEngine:
         self.l0_conv2 = _pack_l0(l0.conv_block2.conv, l0.conv_block2.norm, self.win0,
                                  skip=(l0.conv_block2.lin, l0.conv_block2.norm_skip), device=dev,
                                  cols_skip=self.x0_cols)
+        # (main block, extras) of both convs' input rows, looked up per launch
+        self._l0_blocks = {p[0]: _l0_block(p[0]) for p in (self.l0_conv1, self.l0_conv2)}
         # ---- pooled levels 1..4
         self.packs = []
         for layer in layers[1:]:
@@ -549,8 +566,8 @@ class WindowEngine:
         self.nbr_src = torch.zeros((n, K), dtype=torch.int32, device=dev)
         self.nbr_code = torch.zeros((n, K), dtype=torch.int16, device=dev)
         self.deg = torch.zeros((n,), dtype=torch.int32, device=dev)
-        self.h1 = torch.zeros((n, 16), dtype=torch.float32, device=dev)
-        self.hp0 = torch.zeros((n, 16 + self.feat_ch[1]), dtype=torch.float32, device=dev)  # [h2 | image feats]
+        self.h1 = torch.zeros((n, self.cout0), dtype=torch.float32, device=dev)
+        self.hp0 = torch.zeros((n, self.cout0 + self.feat_ch[1]), dtype=torch.float32, device=dev)  # [h2 | image feats]
         self.x0buf = torch.zeros((n, self.x0_ld), dtype=torch.float32, device=dev)
         self.cluster0 = torch.zeros((n,), dtype=torch.int32, device=dev)
         self.pos_n = torch.zeros((n, 3), dtype=torch.float32, device=dev)     # node (slot) order
@@ -645,11 +662,11 @@ class WindowEngine:
         cin, cskip, w, s = pack
         d0 = self.dom[0]
         wx, tx, wy, ty = self.win0
-        cm = 16 if cin >= 16 else 0
-        _lib.check(L.dagr_spline_conv_l0_tiles_rows(cm, cin - cm, cskip, wx, tx, wy, ty, d0["rx"], d0["ry"], d0["den_x"],
-                                                    d0["den_y"], first, n, self.graph.K, P(self.nbr_src), P(self.nbr_code),
-                                                    P(self.deg), x, ldx, xskip, ldskip, P(w), P(s), 1, out, ldo, None,
-                                                    _lib.cur_stream(self.device)), "conv_l0_tiles_rows")
+        cm, ce = self._l0_blocks[cin]
+        _lib.check(L.dagr_spline_conv_l0_tiles_rows_w(self.cout0, cm, ce, cskip, wx, tx, wy, ty, d0["rx"], d0["ry"],
+                                                      d0["den_x"], d0["den_y"], first, n, self.graph.K, P(self.nbr_src),
+                                                      P(self.nbr_code), P(self.deg), x, ldx, xskip, ldskip, P(w), P(s), 1, out,
+                                                      ldo, None, _lib.cur_stream(self.device)), "conv_l0_tiles_rows")
 
     def _async_call(self, a, first, n, pos, feat, batch, stream):
         """Fill / refresh the argument block of ``dagr_async_update`` and issue the update."""
@@ -668,7 +685,7 @@ class WindowEngine:
             u.rx, u.ry, u.den_x, u.den_y = d0["rx"], d0["ry"], d0["den_x"], d0["den_y"]
             cin1, _, w1, s1 = self.l0_conv1
             _, _, w2, s2 = self.l0_conv2
-            u.cin1, u.w1, u.s1, u.h1, u.ldh1 = cin1, P(w1), P(s1), P(self.h1), 16
+            u.cin1, u.w1, u.s1, u.h1, u.ldh1 = cin1, P(w1), P(s1), P(self.h1), self.cout0
             u.w2, u.s2, u.hp0, u.ldhp0 = P(w2), P(s2), P(self.hp0), self.hp0.shape[1]
             u.pdesc, u.pool_ws, u.xlo, u.ylo = ctypes.pointer(self.pool_desc[0]), P(a["pool_ws"]), P(self.xlo), P(self.ylo)
             u.x_out, u.ldo, u.pos_out, u.batch_out = P(l1.x), l1.x.shape[1], P(l1.pos), P(l1.batch)
@@ -678,7 +695,7 @@ class WindowEngine:
         u.n_static, u.first_id, u.n_new = self._N, first, n
         u.pos, u.feat, u.batch = P(pos), P(feat), P(batch)
         u.batch_is_int64 = 1 if (batch is not None and batch.dtype == torch.int64) else 0
-        _lib.check(self.L.dagr_async_update(ctypes.byref(u), stream), "async_update")
+        _lib.check(self.L.dagr_async_update_w(ctypes.byref(u), self.cout0, stream), "async_update")
 
     def forward_append(self, pos, feat, batch, static_out=False):
         """``reset=False``: the n events of a micro-batch attach to the resident window (EV_TGN.forward, ev_tgn.py:45-56).
@@ -722,10 +739,11 @@ class WindowEngine:
                 rows = slice(first, first + n)
                 self._sample(None, n, self.pos_n[rows], self.batch_n[rows], 0, self._img_feats[0], self.x0buf[rows],
                              self.x0_img_col)
-                self._conv_l0_rows(self.l0_conv1, first, n, P(self.x0buf), self.x0_ld, None, 0, P(self.h1), 16)
-                self._conv_l0_rows(self.l0_conv2, first, n, P(self.h1), 16, P(self.x0buf), self.x0_ld, P(self.hp0),
+                c = self.cout0
+                self._conv_l0_rows(self.l0_conv1, first, n, P(self.x0buf), self.x0_ld, None, 0, P(self.h1), c)
+                self._conv_l0_rows(self.l0_conv2, first, n, P(self.h1), c, P(self.x0buf), self.x0_ld, P(self.hp0),
                                    self.hp0.shape[1])
-                self._sample(None, n, self.pos_n[rows], self.batch_n[rows], 0, self._img_feats[1], self.hp0[rows], 16)
+                self._sample(None, n, self.pos_n[rows], self.batch_n[rows], 0, self._img_feats[1], self.hp0[rows], c)
                 self._n_rows = first + n
             self._pool1_stream(rebuild=False, first=first, n=n)
         if self.tail_graph and not self.use_image:
@@ -931,33 +949,35 @@ class WindowEngine:
         wx, tx, wy, ty = self.win0
         stream = _lib.cur_stream(self.device)
         if self.l0_tiles:
-            cm = 16 if cin >= 16 else 0
-            _lib.check(L.dagr_spline_conv_l0_tiles(cm, cin - cm, cskip, wx, tx, wy, ty, d0["rx"], d0["ry"], d0["den_x"],
-                                                   d0["den_y"], self._N, self.graph.K, P(nbr_src), P(nbr_code), P(deg),
-                                                   x, ldx, xskip, ldskip, P(w), P(s), 1, out, ldo, self._nptr(), stream),
-                       "conv_l0_tiles")
+            cm, ce = self._l0_blocks[cin]
+            _lib.check(L.dagr_spline_conv_l0_tiles_w(self.cout0, cm, ce, cskip, wx, tx, wy, ty, d0["rx"], d0["ry"],
+                                                     d0["den_x"], d0["den_y"], self._N, self.graph.K, P(nbr_src), P(nbr_code),
+                                                     P(deg), x, ldx, xskip, ldskip, P(w), P(s), 1, out, ldo, self._nptr(),
+                                                     stream), "conv_l0_tiles")
         else:
             _lib.check(L.dagr_spline_conv_l0(cin, cskip, self.ntaps0, self._N, self.graph.K, self.ncodes0, P(nbr_src),
                                              P(nbr_code), P(deg), x, ldx, xskip, ldskip, P(self.tab0), P(w), P(s), 1,
                                              out, ldo, stream), "conv_l0")
 
     def stage_l0_conv1(self):
-        """conv_block1.conv_block1: SplineConv(3|19 -> 16)+BN+ReLU (conv.py:23-28)."""
+        """conv_block1.conv_block1: SplineConv(3|cout0+3 -> cout0)+BN+ReLU (conv.py:23-28); cout0 = 16 by default."""
         P = _lib.ptr
         assert self.l0_conv1[0] == len(self.x0_cols)
-        self._conv_l0(self.l0_conv1, P(self._x0), self.x0_ld, None, 0, P(self.h1), 16)
+        self._conv_l0(self.l0_conv1, P(self._x0), self.x0_ld, None, 0, P(self.h1), self.cout0)
 
     def stage_l0_conv2(self, sample=True):
-        """conv_block1.conv_block2: SplineConv(16->16)+BN + skip Linear+BN, ReLU (conv.py:47-56);
+        """conv_block1.conv_block2: SplineConv(cout0->cout0)+BN + skip Linear+BN, ReLU (conv.py:47-56);
         with --use_image followed by sampling_skip(image_feat[1]) (net.py:129)."""
         P = _lib.ptr
-        self._conv_l0(self.l0_conv2, P(self.h1), 16, P(self._x0), self.x0_ld, P(self.hp0), self.hp0.shape[1])
+        self._conv_l0(self.l0_conv2, P(self.h1), self.cout0, P(self._x0), self.x0_ld, P(self.hp0), self.hp0.shape[1])
         if self.use_image and sample:
-            self._sample(self._nptr(), self._N, self.pos_n, self.batch_n, 0, self._img_feats[1], self.hp0[:self._N], 16)
+            self._sample(self._nptr(), self._N, self.pos_n, self.batch_n, 0, self._img_feats[1], self.hp0[:self._N],
+                         self.cout0)
 
     def stage_l0_sample1(self):
-        """sampling_skip(image_feat[1]) (net.py:129) alone: the level-0 nodes' features of the second map into hp0[:, 16:]."""
-        self._sample(None, self._N, self.pos_n, self.batch_n, 0, self._img_feats[1], self.hp0[:self._N], 16)
+        """sampling_skip(image_feat[1]) (net.py:129) alone: the level-0 nodes' features of the second map into
+        hp0[:, cout0:]."""
+        self._sample(None, self._N, self.pos_n, self.batch_n, 0, self._img_feats[1], self.hp0[:self._N], self.cout0)
 
     def stage_pool1(self):
         """pool1 (net.py:131) on the event graph."""
@@ -1300,7 +1320,7 @@ class WindowEngine:
             trace["nbr"] = tuple(t.clone() for t in self._nbr)
             _, ev_slot = self.graph.node_order(self._N)     # traces are reported in event order
             ev_slot = ev_slot.long()
-            trace["layer1"] = self.hp0[:self._N, :16][ev_slot].clone()
+            trace["layer1"] = self.hp0[:self._N, :self.cout0][ev_slot].clone()
             if self.use_image:
                 back = [self.x0_cols.index(k) for k in range(len(self.x0_cols))]   # reference channel order
                 trace["x0"] = self._x0[ev_slot][:, back].clone()
@@ -1461,7 +1481,11 @@ class WindowEngine:
         nt = self.ntaps0
         if self.l0_tiles:
             tx, ty = self.win0[1], self.win0[3]
-            cm = 16 if c0 >= 16 else 0
+            cm, ce = _l0_block(c0)
+            c = self.cout0
+            if c != 16:     # the other widths are instantiations of the width-parametrised template
+                return {"l0_conv1": f"k_conv_l0_tiles_w<{c}, {cm}, {ce}, 0, {tx}, {ty}>",
+                        "l0_conv2": f"k_conv_l0_tiles_w<{c}, {c}, 0, {c0}, {tx}, {ty}>"}
             return {"l0_conv1": f"k_conv_l0_tiles<{cm}, {c0 - cm}, 0, {tx}, {ty}>",
                     "l0_conv2": f"k_conv_l0_tiles<16, 0, {c0}, {tx}, {ty}>"}
         return {"l0_conv1": f"k_conv_l0<{c0}, 0, {nt}>", "l0_conv2": f"k_conv_l0<16, {c0}, {nt}>"}

@@ -251,6 +251,25 @@ int dagr_spline_conv_l0_tiles_rows(int32_t cmain, int32_t cextra, int32_t cskip,
                                    const int32_t *deg, const float *x, int32_t ldx, const float *xskip, int32_t ldskip,
                                    const float *wpack, const float *shift, int32_t relu, float *out, int32_t ldo,
                                    const int32_t *n_ptr, void *stream);
+/* The same two entry points for the other level-0 widths: cout = int(base_width * 32) in {8, 16, 32}; anything else returns
+ * DAGR_ERR_UNSUPPORTED.  cout = 16 IS dagr_spline_conv_l0_tiles[_rows].  wpack rows are cout wide, out[n, 0:cout] is
+ * written (ldo >= cout).  The input row is [cmain | cextra (<= 4)] with cmain in {0, cout} -- 8-byte pieces per lane when
+ * cmain = 8, two 16-channel passes when cmain = 32 -- and cskip = (0 or cout) + (<= 4).  Instantiated: (cmain, cextra,
+ * cskip) in {(0,3,0), (cout,0,3), (cout,3,0), (cout,0,cout+3)}: the events-only and --use_image conv pairs of Net.
+ * The kernel's LDS (packed weights + per-offset tap rows, all dynamic) is checked here against 64 KB (cout 8, 16) or the
+ * CU's 160 KB (cout 32): DAGR_ERR_INVALID_ARG instead of a launch past it. */
+int dagr_spline_conv_l0_tiles_w(int32_t cout, int32_t cmain, int32_t cextra, int32_t cskip, int32_t win_x, int32_t tx,
+                                int32_t win_y, int32_t ty, int32_t rx, int32_t ry, float den_x, float den_y, int64_t N,
+                                int32_t K, const int32_t *nbr_src, const int16_t *nbr_code, const int32_t *deg,
+                                const float *x, int32_t ldx, const float *xskip, int32_t ldskip, const float *wpack,
+                                const float *shift, int32_t relu, float *out, int32_t ldo, const int32_t *n_ptr,
+                                void *stream);
+int dagr_spline_conv_l0_tiles_rows_w(int32_t cout, int32_t cmain, int32_t cextra, int32_t cskip, int32_t win_x, int32_t tx,
+                                     int32_t win_y, int32_t ty, int32_t rx, int32_t ry, float den_x, float den_y,
+                                     int64_t first_node, int64_t N, int32_t K, const int32_t *nbr_src,
+                                     const int16_t *nbr_code, const int32_t *deg, const float *x, int32_t ldx,
+                                     const float *xskip, int32_t ldskip, const float *wpack, const float *shift,
+                                     int32_t relu, float *out, int32_t ldo, const int32_t *n_ptr, void *stream);
 /* generic step 1: A[n] = [sum_j basis*x_j per tap (25*cin) | x[n] (cin) | xskip[n] (cskip)] over a
  * CSR-by-destination graph; code[e] = ix | iy<<16.  n_nodes_ptr (device, may be NULL) bounds the
  * rows actually processed (<= n_nodes_max) without a host sync. */
@@ -414,6 +433,9 @@ typedef struct dagr_async_update_args {
     int32_t e_cap;
 } dagr_async_update_args;
 int dagr_async_update(const dagr_async_update_args *args, void *stream);
+/* the same at a level-0 width cout0 in {8, 16, 32} (h1 rows are cout0 wide, hp0's first cout0 columns are written);
+ * dagr_async_update is cout0 = 16 */
+int dagr_async_update_w(const dagr_async_update_args *args, int32_t cout0, void *stream);
 /* Launch (A) of dagr_pool_l0 alone: the level-0 accumulation kernel over the window last built on `graph_ws`, into the
  * accumulators of `pool_ws` (max / fixed-point sums: repeating it leaves max accumulators unchanged and scales the sums;
  * the next dagr_pool_l0 call re-arms everything).  For measurement (bench.py times the kernel on its own with HIP
