@@ -233,6 +233,10 @@ SIGNATURES = {
                                            c_void_p]),
     "dagr_augment_boxes": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_i32, c_i32, c_void_p,
                                           c_void_p]),
+    "dagr_coco_match_bounds": (None, [ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
+    "dagr_coco_match": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i64,
+                                       c_i64, c_i64, c_i32, c_i32, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -123,19 +123,166 @@ def evaluated_images(gt_boxes_list, dt_boxes_list):
     return images
 
 
+class JobList:
+    """The matcher's work as one flat list.  A job is one (image, class, area range) with at least one ground-truth box
+    or one detection of that class: the calls of ``_evaluate_image`` that do not return None.  The boxes of an
+    (image, class) are stored once and shared by its four area ranges.
+
+    ``gt`` [NG, 4], ``dt`` [ND, 4] (x, y, w, h), ``scores`` [ND] float64; ``table`` [J, 4] int64 = (first ground-truth
+    row, G, first detection row, D); ``rng`` [J, 2] float64; ``key`` [J, 3] int64 = (class, area range, index of the image
+    in ``evaluated_images``' list), ascending."""
+
+    def __init__(self, gt, dt, scores, table, rng, key):
+        self.gt, self.dt, self.scores, self.table, self.rng, self.key = gt, dt, scores, table, rng, key
+
+    def __len__(self):
+        return len(self.table)
+
+    def arrays(self, j):
+        """Job j as ``_evaluate_image``'s arguments."""
+        g0, g, d0, d = (int(v) for v in self.table[j])
+        return self.gt[g0:g0 + g], self.dt[d0:d0 + d], self.scores[d0:d0 + d], self.rng[j]
+
+
+def build_jobs(images, n_classes):
+    """``evaluated_images``' list -> ``JobList``."""
+    gt, dt, sc, table, rng, key = [], [], [], [], [], []
+    n_g = n_d = 0
+    for c in range(n_classes):
+        groups = []
+        for i, (g, gl, d, dl, s) in enumerate(images):
+            gm, dm = gl == c, dl == c
+            g_c, d_c = g[gm], d[dm]
+            if len(g_c) == 0 and len(d_c) == 0:
+                continue
+            gt.append(g_c), dt.append(d_c), sc.append(s[dm])
+            groups.append((i, n_g, len(g_c), n_d, len(d_c)))
+            n_g, n_d = n_g + len(g_c), n_d + len(d_c)
+        for ai, r in enumerate(AREA_RNG):
+            for i, g0, g_n, d0, d_n in groups:
+                table.append((g0, g_n, d0, d_n)), rng.append(r), key.append((c, ai, i))
+
+    def cat(parts, shape):
+        return np.concatenate(parts, 0) if parts else np.zeros(shape)
+    return JobList(cat(gt, (0, 4)), cat(dt, (0, 4)), cat(sc, (0,)), np.asarray(table, dtype=np.int64).reshape(-1, 4),
+                   np.asarray(rng, dtype=np.float64).reshape(-1, 2), np.asarray(key, dtype=np.int64).reshape(-1, 3))
+
+
+def match_jobs_host(jobs, which=None):
+    """``_evaluate_image`` job by job: ``{job: (scores sorted, dtm, dt_ign, g_ign)}`` for the jobs ``which`` (all)."""
+    return {int(j): _evaluate_image(*jobs.arrays(int(j))) for j in (range(len(jobs)) if which is None else which)}
+
+
+def device_bounds():
+    """(G, D) one job of ``dagr_coco_match`` takes (include/dagr_hip.h: DAGR_COCO_MAX_GT, DAGR_COCO_MAX_DT)."""
+    import ctypes
+    from .. import _lib
+    g, d, m = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    _lib.lib().dagr_coco_match_bounds(ctypes.byref(g), ctypes.byref(d), ctypes.byref(m))
+    if m.value < MAX_DETS:
+        raise RuntimeError(f"dagr_coco_match matches {m.value} detections per job, the protocol needs {MAX_DETS}")
+    return g.value, d.value
+
+
+def coco_match_device(jobs, which, device):
+    """``dagr_coco_match`` for the jobs ``which`` (all within the kernel's bounds): two copies to the device (one float64,
+    one int64 array), ONE launch, ONE copy back.  ``{job: (order, dtm, dt_ign, g_ign)}`` with ``order`` the indices of the
+    job's detections by descending score, cut to ``MAX_DETS``."""
+    import torch
+    from .. import _lib
+    tab = jobs.table[which]
+    T, J = len(IOU_THRS), len(which)
+    kept = np.minimum(tab[:, 3], MAX_DETS)
+    o_off, gi_off = np.cumsum(kept) - kept, np.cumsum(tab[:, 1]) - tab[:, 1]
+    n_out, n_gign = int(kept.sum()), int(tab[:, 1].sum())
+    n_gt, n_dt = len(jobs.gt), len(jobs.dt)
+    f64 = np.concatenate([jobs.gt.reshape(-1), jobs.dt.reshape(-1), jobs.scores, jobs.rng[which].reshape(-1), IOU_THRS])
+    i64 = np.concatenate([tab, o_off[:, None], gi_off[:, None]], 1)
+    # one output buffer = one copy back: status int32 | order int32[n_out] | dtm, dt_ign uint8[T, n_out] | g_ign uint8
+    at_order, at_dtm = 4, 4 + 4 * n_out
+    at_ign, at_gign = at_dtm + T * n_out, at_dtm + 2 * T * n_out
+    with torch.cuda.device(device):
+        fd = torch.from_numpy(np.ascontiguousarray(f64, dtype=np.float64)).to(device)
+        jd = torch.from_numpy(np.ascontiguousarray(i64, dtype=np.int64)).to(device)
+        res = torch.empty((at_gign + n_gign,), dtype=torch.uint8, device=device)
+        base, f0 = res.data_ptr(), fd.data_ptr()
+
+        def f64_at(n_doubles):
+            return _lib.c_void_p(f0 + 8 * n_doubles)
+        _lib.check(_lib.lib().dagr_coco_match(
+            f64_at(0), f64_at(4 * n_gt), f64_at(4 * n_gt + 4 * n_dt), _lib.ptr(jd), f64_at(4 * n_gt + 5 * n_dt),
+            f64_at(4 * n_gt + 5 * n_dt + 2 * J), T, MAX_DETS, J, n_gt, n_dt, int(tab[:, 1].max()), int(tab[:, 3].max()),
+            n_out, n_gign, _lib.c_void_p(base + at_order), _lib.c_void_p(base + at_dtm), _lib.c_void_p(base + at_ign),
+            _lib.c_void_p(base + at_gign), _lib.c_void_p(base), _lib.cur_stream(device)), "coco_match")
+        host = res.cpu().numpy()
+    if host[:4].view(np.int32)[0] != 0:
+        raise RuntimeError("dagr_coco_match: a job did not fit its arrays (status 1)")
+    order = host[at_order:at_dtm].view(np.int32)
+    dtm = host[at_dtm:at_ign].view(np.bool_).reshape(T, n_out)
+    dt_ign = host[at_ign:at_gign].view(np.bool_).reshape(T, n_out)
+    g_ign = host[at_gign:].view(np.bool_)
+    out = {}
+    for n, j in enumerate(which):
+        o, k, gi, g_n = int(o_off[n]), int(kept[n]), int(gi_off[n]), int(tab[n, 1])
+        out[int(j)] = (order[o:o + k], dtm[:, o:o + k], dt_ign[:, o:o + k], g_ign[gi:gi + g_n])
+    return out
+
+
+def match_jobs_device(jobs, device=None, stats=None):
+    """``match_jobs_host`` with the matcher on the GPU (``coco_match_device``).  A job beyond the kernel's per-job bounds
+    is matched on the host; the four area ranges of an (image, class) share their boxes, so they go together, and
+    ``stats["host_fallback_jobs"]`` counts such an (image, class) once."""
+    import torch
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"match_jobs_device: the matcher runs on a GPU, not on {device}")
+    max_g, max_d = device_bounds()
+    fits = (jobs.table[:, 1] <= max_g) & (jobs.table[:, 3] <= max_d)
+    on_dev, on_host = np.flatnonzero(fits), np.flatnonzero(~fits)
+    out = match_jobs_host(jobs, on_host)
+    if stats is not None:
+        stats["host_fallback_jobs"] = len({(int(c), int(i)) for c, _, i in jobs.key[on_host]})
+        stats["device_jobs"] = int(len(on_dev))
+    if len(on_dev):
+        for j, (order, dtm, dt_ign, g_ign) in coco_match_device(jobs, on_dev, device).items():
+            out[j] = (jobs.scores[jobs.table[j, 2] + order], dtm, dt_ign, g_ign)
+    return out
+
+
+def _precision_from_jobs(images, n_classes, matcher):
+    """Job list -> matcher -> per (class, area range) the per-image tuples, in image order, -> ``_accumulate``."""
+    jobs = build_jobs(images, n_classes)
+    matched = matcher(jobs)
+    per_image = {}
+    for j, (c, ai, _) in enumerate(jobs.key):                        # ascending image index inside a (class, area range)
+        per_image.setdefault((int(c), int(ai)), []).append(matched[j])
+    prec = -np.ones((len(IOU_THRS), len(REC_THRS), n_classes, len(AREA_RNG)))
+    for (c, ai), entries in per_image.items():
+        p = _accumulate(entries)
+        if p is not None:
+            prec[:, :, c, ai] = p
+    return prec
+
+
 def evaluate_detection(gt_boxes_list, dt_boxes_list, classes=("car", "pedestrian"), height=240, width=304,
-                       time_tol=50000):
-    """gt / dt: one dict per image, ``boxes`` [n, 4] (x1, y1, x2, y2), ``labels`` [n], detections also ``scores`` [n]."""
+                       time_tol=50000, on_device=False, device=None, stats=None):
+    """gt / dt: one dict per image, ``boxes`` [n, 4] (x1, y1, x2, y2), ``labels`` [n], detections also ``scores`` [n].
+    ``on_device``: the greedy matcher runs as ``dagr_coco_match`` on ``device`` (default: the current GPU) instead of
+    ``_evaluate_image``; the same booleans reach the same ``_accumulate``, so the result is the same floats.
+    ``stats`` (a dict) then receives ``host_fallback_jobs`` and ``device_jobs``."""
     images = evaluated_images(gt_boxes_list, dt_boxes_list)
     if sum(len(im[2]) for im in images) == 0:
         return {k: 0 for k in OUT_KEYS}
-    prec = -np.ones((len(IOU_THRS), len(REC_THRS), len(classes), len(AREA_RNG)))
-    for c in range(len(classes)):
-        for ai, rng in enumerate(AREA_RNG):
-            per_image = [_evaluate_image(g[gl == c], d[dl == c], s[dl == c], rng) for g, gl, d, dl, s in images]
-            p = _accumulate(per_image)
-            if p is not None:
-                prec[:, :, c, ai] = p
+    if on_device:
+        prec = _precision_from_jobs(images, len(classes), lambda jobs: match_jobs_device(jobs, device, stats))
+    else:
+        prec = -np.ones((len(IOU_THRS), len(REC_THRS), len(classes), len(AREA_RNG)))
+        for c in range(len(classes)):
+            for ai, rng in enumerate(AREA_RNG):
+                per_image = [_evaluate_image(g[gl == c], d[dl == c], s[dl == c], rng) for g, gl, d, dl, s in images]
+                p = _accumulate(per_image)
+                if p is not None:
+                    prec[:, :, c, ai] = p
 
     def mean(sel):
         v = sel[sel > -1]

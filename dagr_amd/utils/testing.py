@@ -27,13 +27,28 @@ def format_detections(sequences, t, detections):
     return out
 
 
+_EVALUATE_ON_DEVICE = False
+
+
+def evaluate_on_device(enabled):
+    """What ``run_test_with_visualization(on_device=None)`` does in this process (the scripts' ``--evaluate_on_device``:
+    they call the driver with the reference's arguments only)."""
+    global _EVALUATE_ON_DEVICE
+    _EVALUATE_ON_DEVICE = bool(enabled)
+
+
 def run_test_with_visualization(loader, model, dataset: str, log_every_n_batch=-1, name="", compile_detections=False,
-                                no_eval=False):
+                                no_eval=False, on_device=None):
+    """``on_device`` (no counterpart in the reference): the mAP buffer keeps the boxes on the GPU and matches them there
+    (``DetectionBuffer(on_device=True)``); the metrics are the same floats.  None: the process default
+    (``evaluate_on_device``, off unless set)."""
+    if on_device is None:
+        on_device = _EVALUATE_ON_DEVICE
     model.eval()
     scorer = None
     if not no_eval:
         ds = loader.dataset
-        scorer = DetectionBuffer(height=ds.height, width=ds.width, classes=ds.classes)
+        scorer = DetectionBuffer(height=ds.height, width=ds.width, classes=ds.classes, on_device=on_device)
     collected = [] if compile_detections else None
     # global index of an image in the run (``DataLoader.image_ids``: right for both ways of sharding a loader); a foreign
     # loader numbers its images in order of arrival

@@ -731,6 +731,46 @@ int dagr_augment_frames(const dagr_aug_params *params, int32_t B, int32_t C, int
 int dagr_augment_boxes(const dagr_aug_params *params, int32_t B, int32_t W, int32_t H, const float *boxes,
                        const int64_t *box_batch, int32_t M, int32_t ld, float *out, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * COCO-protocol matching (csrc/coco_match.hip): utils/coco_eval.py:_evaluate_image for a flat list of jobs in one launch.
+ * A job is one (image, class, area range) with at least one ground-truth box or one detection of that class; one
+ * workgroup matches it, one wave per IoU threshold.  All arrays are DEVICE memory.
+ *
+ *   gt_xywh[n_gt, 4], dt_xywh[n_dt, 4]   float64 (x, y, w, h): the float32 corner boxes with w = x2 - x1, h = y2 - y1
+ *                                        subtracted in float32 and then widened, as _xywh does
+ *   dt_score[n_dt]                       float64
+ *   jobs[n_jobs, 6]                      int64: {first ground-truth row, G, first detection row, D,
+ *                                        first column of the job in order / dtm / dt_ign, first entry of the job in g_ign}
+ *   area_rng[n_jobs, 2]                  float64 [lo, hi]: boxes with area < lo or > hi are ignored
+ *   iou_thrs[n_thr]                      float64, 1 <= n_thr <= 16: the host's IOU_THRS, never recomputed here
+ *
+ * Outputs, with D' = min(D, max_dets) columns per job and n_out = sum of D', n_gign = sum of G over the jobs:
+ *   order[n_out]            int32: the job's detections (index inside the job) by descending score, equal scores in
+ *                           input order, NaN last (numpy's argsort(-scores, kind="mergesort")), cut to max_dets
+ *   dtm[n_thr, n_out]       uint8: the detection of that column is matched at that threshold
+ *   dt_ign[n_thr, n_out]    uint8: ... matched to ignored ground truth, or unmatched and outside the area range
+ *   g_ign[n_gign]           uint8: the job's ground truth, evaluated boxes first (stable), 1 = ignored
+ *   status                  int32, zeroed here; 1 afterwards if a job's offsets or counts did not fit the arrays or the
+ *                           bounds below (that job wrote nothing)
+ *
+ * Per-job bounds (dagr_coco_match_bounds reports them): G <= DAGR_COCO_MAX_GT = 256 -- the sorted ground truth of a job
+ * sits in an LDS tile of 32 bytes a box, under 12 KiB per workgroup with the detections, so the LDS of a CU holds a dozen
+ * jobs, and each lane keeps the matched flags of its G / 64 boxes in one register; the training targets of this
+ * project hold at most 100 boxes an image.  D <= DAGR_COCO_MAX_DT = 4096 before the cut (the rank of a score is counted
+ * against all others).  max_dets <= DAGR_COCO_MAX_DETS = 100.  The caller states the largest G and D of its jobs
+ * (max_gt_per_job, max_dt_per_job); beyond the bounds the call fails with DAGR_ERR_INVALID_ARG before any device work,
+ * and such a job is to be matched on the host.  No host synchronisation.
+ * ------------------------------------------------------------------------ */
+#define DAGR_COCO_MAX_GT 256
+#define DAGR_COCO_MAX_DT 4096
+#define DAGR_COCO_MAX_DETS 100
+void dagr_coco_match_bounds(int32_t *max_gt, int32_t *max_dt, int32_t *max_dets);
+int dagr_coco_match(const double *gt_xywh, const double *dt_xywh, const double *dt_score, const int64_t *jobs,
+                    const double *area_rng, const double *iou_thrs, int32_t n_thr, int32_t max_dets, int64_t n_jobs,
+                    int64_t n_gt, int64_t n_dt, int32_t max_gt_per_job, int32_t max_dt_per_job, int64_t n_out,
+                    int64_t n_gign, int32_t *order, uint8_t *dtm, uint8_t *dt_ign, uint8_t *g_ign, int32_t *status,
+                    void *stream);
+
 /* Host-side helper: first n offsets of the search spiral (spiral.h:1-15), the closed form the
  * search kernel uses.  dx/dy are HOST arrays.  Lets CPU-only tests pin the visiting order. */
 int dagr_spiral_offsets(int32_t n, int32_t *dx_host, int32_t *dy_host);

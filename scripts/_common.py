@@ -17,6 +17,7 @@ from dagr.model.networks.dagr import DAGR                        # noqa: E402
 from dagr.model.networks.ema import ModelEMA                     # noqa: E402
 from dagr.utils.args import SCRIPT_FLAGS                         # noqa: E402
 from dagr.utils.buffers import detections_to_records             # noqa: E402
+from dagr.utils import testing                                   # noqa: E402
 from dagr.utils.testing_weights import randomize_                # noqa: E402
 
 
@@ -35,14 +36,26 @@ def _synthetic_options(p):
                         "(COCO-protocol mAP of the whole run, also when it is sharded over several GPUs)")
 
 
+def _evaluation_options(p):
+    """Options of the scoring (no counterpart in the reference's ``FLAGS()``; absent from the namespace unless given)."""
+    g = p.add_argument_group("evaluation")
+    g.add_argument("--evaluate_on_device", action="store_true", default=argparse.SUPPRESS,
+                   help="run_test.py / run_test_interframe.py: keep detections and ground truth on the GPU until the end "
+                        "of the run and match them there (dagr_coco_match); the metrics are the same numbers")
+
+
 def flags(description, argv=None, extra=None, default_config="dagr-s-dsec.yaml"):
     """The reference's ``FLAGS()`` (``dagr.utils.args``: same parser, ``--config <yaml>`` merged under the command line --
     run_test.py:31, readme.md:107-113) plus the synthetic-data options.  Returns the namespace the model is built from."""
     def more(p):
         _synthetic_options(p)
+        _evaluation_options(p)
         if extra:
             extra(p)
     a = SCRIPT_FLAGS(argv, description=description, default_config=default_config, extra=more)
+    # the test scripts call run_test_with_visualization as the reference's scripts do, without the option: it reaches the
+    # driver as the process default
+    testing.evaluate_on_device(bool(getattr(a, "evaluate_on_device", False)))
     if a.windows is None:
         a.windows = max(32, 4 * a.batch_size)
     return a
