@@ -95,6 +95,8 @@ SIGNATURES = {
                                          ctypes.POINTER(c_i32), c_void_p]),
     "dagr_graph_counters": (ctypes.c_int, [ctypes.POINTER(GraphDesc), c_void_p, c_void_p, c_void_p]),
     "dagr_scan_scratch_elems": (c_size_t, [c_i64]),
+    "dagr_scan_chained_state_bytes": (c_size_t, [c_i64]),
+    "dagr_exclusive_scan_i32": (ctypes.c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_size_t, c_i32, c_i32, c_void_p]),
     "dagr_graph_edge_index": (ctypes.c_int, [ctypes.POINTER(GraphDesc), c_void_p, c_void_p, c_void_p, c_i64, c_void_p,
                                              c_void_p, c_void_p, c_i64, c_void_p]),
     "dagr_graph_node_order": (ctypes.c_int, [ctypes.POINTER(GraphDesc), c_void_p, c_i64, c_void_p, c_void_p, c_void_p]),

@@ -37,7 +37,8 @@ hipblasLtHandle_t lt_handle() {
 using namespace dagr;
 
 // D[M, N] = act(A[M, K] . Wt[K, N] + bias[N] (+ R[M, N])), row-major, fp32.  act: 0 none, 1 ReLU.  R may alias nothing else;
-// D may not alias A.  workspace: device scratch for the library (>= dagr_gemm_epilogue_workspace_bytes()).
+// D may alias neither A nor R (rejected: the first call of a shape runs the GEMM several times to time the library's
+// candidates, which with R == D would accumulate into D every time).  workspace: device scratch for the library (>= dagr_gemm_epilogue_workspace_bytes()).
 extern "C" size_t dagr_gemm_epilogue_workspace_bytes(void) { return (size_t)64 << 20; }
 
 extern "C" int dagr_gemm_epilogue(const float *A, int64_t M, int32_t K, int64_t lda, const float *Wt, int32_t N,
@@ -46,6 +47,8 @@ extern "C" int dagr_gemm_epilogue(const float *A, int64_t M, int32_t K, int64_t 
     DAGR_CHECK_ARG(M >= 0 && K >= 1 && N >= 1 && lda >= K && ldd >= N && (!R || ldr >= N) && (act == 0 || act == 1), "bad sizes");
     if (M == 0) return DAGR_OK;
     DAGR_CHECK_ARG(A && Wt && D, "NULL pointer");
+    DAGR_CHECK_ARG((const float *)D != A, "D aliases A");
+    DAGR_CHECK_ARG((const float *)D != R, "D aliases R");
     hipblasLtHandle_t h = lt_handle();
     if (!h) { set_error("dagr_gemm_epilogue: hipblasLtCreate failed"); return DAGR_ERR_HIP; }
     // column-major view: D^T[N x M] = Wt^T[N x K] . A^T[K x M]; the bias runs along the rows of D^T (= output channels)

@@ -375,3 +375,31 @@ hipError_t exclusive_scan_i32(int32_t *in, int32_t *out, int64_t n, int32_t *scr
 }
 
 }  // namespace dagr
+
+using namespace dagr;
+
+extern "C" size_t dagr_scan_chained_state_bytes(int64_t n) {
+    if (n < 0) { set_error("dagr_scan_chained_state_bytes: bad size"); return 0; }
+    return scan_chained_state_bytes(n);
+}
+
+// exclusive_scan_i32 (chained == 0: one workgroup up to 64 Ki entries, three launches beyond) and
+// exclusive_scan_i32_chained (chained != 0: one launch) as the product's callers reach them
+extern "C" int dagr_exclusive_scan_i32(int32_t *in, int32_t *out, int64_t n, void *scratch, size_t scratch_bytes,
+                                       int32_t chained, int32_t zero_input, void *stream) {
+    DAGR_CHECK_ARG(n >= 0, "bad size");
+    if (n == 0) return DAGR_OK;
+    DAGR_CHECK_ARG(in && out && scratch, "NULL pointer");
+    DAGR_CHECK_ARG(((uintptr_t)in % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)scratch % 16) == 0,
+                   "buffers must be 16-byte aligned");
+    DAGR_CHECK_ARG(!(zero_input && in == out), "in may alias out only without zero_input");
+    if (chained) {
+        DAGR_CHECK_ARG(scratch_bytes >= scan_chained_state_bytes(n), "state smaller than dagr_scan_chained_state_bytes(n)");
+        DAGR_CHECK_HIP(exclusive_scan_i32_chained(in, out, n, scratch, zero_input != 0, (hipStream_t)stream));
+    } else {
+        DAGR_CHECK_ARG(scratch_bytes >= scan_scratch_elems(n) * sizeof(int32_t),
+                       "scratch smaller than dagr_scan_scratch_elems(n) ints");
+        DAGR_CHECK_HIP(exclusive_scan_i32(in, out, n, (int32_t *)scratch, zero_input != 0, (hipStream_t)stream));
+    }
+    return DAGR_OK;
+}

@@ -166,6 +166,16 @@ int dagr_graph_counters(const dagr_graph_desc *desc, void *workspace, int32_t *o
  * per-event in-degree.
  * Asynchronous; E = rowptr[N]. scratch: int32[dagr_scan_scratch_elems(N+1)]. */
 size_t dagr_scan_scratch_elems(int64_t n);
+/* The int32 exclusive prefix sum behind the row pointers, per-pixel offsets and voxel relabelling, on its own:
+ * out[i] = in[0] + ... + in[i-1] over n entries (16-byte aligned buffers).  in may be out unless zero_input, which
+ * clears in[] once it is consumed.  chained == 0: one workgroup up to 65 536 entries, three launches beyond; scratch =
+ * int32[dagr_scan_scratch_elems(n)], no initial state.  chained != 0: one launch (decoupled look-back; tiles of 2048
+ * entries up to 320 of them, then tiles of 1024 x 8 / 16 / 32 / 48); scratch = dagr_scan_chained_state_bytes(n) bytes,
+ * ALL ZERO before the first call and then left to the calls (any n the state is large enough for, one stream).
+ * scratch_bytes: what the caller allocated.  Asynchronous. */
+size_t dagr_scan_chained_state_bytes(int64_t n);
+int dagr_exclusive_scan_i32(int32_t *in, int32_t *out, int64_t n, void *scratch, size_t scratch_bytes, int32_t chained,
+                            int32_t zero_input, void *stream);
 int dagr_graph_edge_index(const dagr_graph_desc *desc, void *workspace, const int32_t *nbr_src, const int32_t *deg,
                           int64_t N, int32_t *rowptr, int32_t *scan_scratch,
                           int64_t *edge_index, int64_t row_stride, void *stream);
@@ -630,7 +640,8 @@ int dagr_downsample_events(const int32_t *order, const int32_t *run_cell, const 
 /* The 1x1 convolutions of the channels-last image branch (src/dagr/model/networks/net_img.py:42-48, BatchNorm folded) as
  * library GEMMs (hipBLASLt, fp32 in / fp32 accumulate) with the whole epilogue in the kernel:
  *   D[M, N] = act(A[M, K] . Wt[K, N] + bias[N] (+ R[M, N])),  row-major, row strides lda / ldr / ldd; act 0 = none, 1 = ReLU;
- * bias and R may be NULL.  The residual join + ReLU of a bottleneck (relu(bn3(conv3(x)) + identity)) is one launch.
+ * bias and R may be NULL; D may alias neither A nor R (DAGR_ERR_INVALID_ARG).  The residual join + ReLU of a bottleneck
+ * (relu(bn3(conv3(x)) + identity)) is one launch.
  * workspace: device scratch of at least dagr_gemm_epilogue_workspace_bytes() bytes (caller-owned, no hidden allocation). */
 size_t dagr_gemm_epilogue_workspace_bytes(void);
 int dagr_gemm_epilogue(const float *A, int64_t M, int32_t K, int64_t lda, const float *Wt, int32_t N, const float *bias,

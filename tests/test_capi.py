@@ -74,3 +74,28 @@ def test_argument_validation_of_the_conv_and_elementwise_entry_points():
     assert L.dagr_bias_silu(one, one, 0, 8, None) == 0
     assert L.dagr_bn_relu_maxpool(one, 1, 8, 8, 6, one, one, one, None) != 0
     assert b"multiple of 4" in L.dagr_last_error()
+    # library GEMM with fused epilogue: D over one of its own inputs is refused before anything is launched
+    two = ctypes.c_void_p(32)
+    ws = L.dagr_gemm_epilogue_workspace_bytes()
+    assert L.dagr_gemm_epilogue(one, 4, 8, 8, two, 8, None, None, 8, 0, one, 8, None, ws, None) == -1
+    assert b"D aliases A" in L.dagr_last_error()
+    assert L.dagr_gemm_epilogue(one, 4, 8, 8, two, 8, None, ctypes.c_void_p(64), 8, 1, ctypes.c_void_p(64), 8, None, ws,
+                                None) == -1
+    assert b"D aliases R" in L.dagr_last_error()
+    # the scan on its own
+    assert L.dagr_scan_chained_state_bytes(-1) == 0 and b"bad size" in L.dagr_last_error()
+    assert L.dagr_scan_chained_state_bytes(2049) == (2 + 8) * 8 + 64
+    assert L.dagr_exclusive_scan_i32(one, two, -1, two, 1 << 20, 0, 0, None) != 0 and b"bad size" in L.dagr_last_error()
+    assert L.dagr_exclusive_scan_i32(one, two, 0, None, 0, 0, 0, None) == 0
+    for args in ((None, two, one), (one, None, two), (one, two, None)):
+        assert L.dagr_exclusive_scan_i32(args[0], args[1], 8, args[2], 1 << 20, 0, 0, None) != 0
+        assert b"NULL" in L.dagr_last_error()
+    assert L.dagr_exclusive_scan_i32(ctypes.c_void_p(20), two, 8, two, 1 << 20, 0, 0, None) != 0
+    assert b"aligned" in L.dagr_last_error()
+    assert L.dagr_exclusive_scan_i32(one, one, 8, two, 1 << 20, 0, 1, None) != 0 and b"alias" in L.dagr_last_error()
+    n = 100000
+    small = 4 * L.dagr_scan_scratch_elems(n) - 1
+    assert L.dagr_exclusive_scan_i32(one, two, n, two, small, 0, 0, None) != 0
+    assert b"dagr_scan_scratch_elems" in L.dagr_last_error()
+    assert L.dagr_exclusive_scan_i32(one, two, n, two, L.dagr_scan_chained_state_bytes(n) - 1, 1, 0, None) != 0
+    assert b"dagr_scan_chained_state_bytes" in L.dagr_last_error()
