@@ -239,6 +239,11 @@ SIGNATURES = {
     "dagr_coco_match": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i64,
                                        c_i64, c_i64, c_i32, c_i32, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
+    "dagr_coco_accumulate_tile": (c_i32, []),
+    "dagr_coco_accumulate_workspace_bytes": (c_size_t, [c_i32, c_i64]),
+    "dagr_coco_accumulate": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
+                                            ctypes.c_double, c_i32, c_i32, c_i64, c_void_p, c_size_t, c_void_p, c_void_p,
+                                            c_void_p]),
 }
 
 _lib = None

@@ -132,11 +132,21 @@ class DetectionBuffer:
     append into growing device arrays without a copy to the host and without a synchronisation, ONE copy brings
     everything back, and the greedy matcher of the evaluation runs as ``dagr_coco_match``.  The metrics are the floats the
     host path returns.  ``last_host_fallback_jobs``: after ``compute``, how many (image, class) pairs were beyond the
-    kernel's per-job bounds and were matched on the host instead."""
+    kernel's per-job bounds and were matched on the host instead.
 
-    def __init__(self, height, width, classes, on_device=False):
+    ``accumulate_on_device`` (with ``on_device=True`` only): the accumulation of the evaluation runs on the GPU as well
+    (``dagr_coco_accumulate``) and only the precision array comes back -- the same floats again.  None: the process default
+    (``utils.testing.accumulate_on_device``, off unless set) when ``on_device``, else off."""
+
+    def __init__(self, height, width, classes, on_device=False, accumulate_on_device=None):
         self.height, self.width, self.classes = height, width, classes
         self.on_device = bool(on_device)
+        if accumulate_on_device is None:
+            from . import testing
+            accumulate_on_device = self.on_device and testing.accumulate_on_device_default()
+        if accumulate_on_device and not self.on_device:
+            raise ValueError("DetectionBuffer: accumulate_on_device=True needs on_device=True")
+        self.accumulate_on_device = bool(accumulate_on_device)
         self.last_host_fallback_jobs = 0
         self._reset()
 
@@ -249,7 +259,7 @@ class DetectionBuffer:
         if self.on_device:
             stats = {}
             out = evaluate_detection(gts, dets, height=self.height, width=self.width, classes=self.classes, on_device=True,
-                                     device=self._device, stats=stats)
+                                     device=self._device, stats=stats, accumulate_on_device=self.accumulate_on_device)
             self.last_host_fallback_jobs = stats.get("host_fallback_jobs", 0)
         else:
             out = evaluate_detection(gts, dets, height=self.height, width=self.width, classes=self.classes)

@@ -184,17 +184,45 @@ def device_bounds():
     return g.value, d.value
 
 
-def coco_match_device(jobs, which, device):
+class DeviceMatches:
+    """What ``coco_match_device(to_host=False)`` leaves on the device: ``order`` int32 [n_out], ``dtm`` / ``dt_ign`` uint8
+    [T, n_out], ``g_ign`` uint8 [n_gign] and ``status`` int32 [1] -- views of ONE buffer, in the columns ``o_off`` / entries
+    ``gi_off`` of the jobs ``which`` -- plus ``scores`` float64 [ND] (``jobs.scores``) and ``table`` int64 [len(which), 6]
+    (first ground-truth row, G, first detection row, D, first column, first ``g_ign`` entry)."""
+
+    def __init__(self, which, o_off, kept, gi_off, order, dtm, dt_ign, g_ign, status, scores, table):
+        self.which, self.o_off, self.kept, self.gi_off = which, o_off, kept, gi_off
+        self.order, self.dtm, self.dt_ign, self.g_ign, self.status = order, dtm, dt_ign, g_ign, status
+        self.scores, self.table = scores, table
+
+
+def column_layout(jobs):
+    """Where every job of the list keeps its results when ALL jobs share the output arrays: (kept [J] = min(D, MAX_DETS),
+    first column [J], number of columns, first ``g_ign`` entry [J], number of entries)."""
+    kept = np.minimum(jobs.table[:, 3], MAX_DETS)
+    return kept, np.cumsum(kept) - kept, int(kept.sum()), np.cumsum(jobs.table[:, 1]) - jobs.table[:, 1], int(jobs.table[:, 1].sum())
+
+
+def coco_match_device(jobs, which, device, to_host=True, all_columns=False):
     """``dagr_coco_match`` for the jobs ``which`` (all within the kernel's bounds): two copies to the device (one float64,
     one int64 array), ONE launch, ONE copy back.  ``{job: (order, dtm, dt_ign, g_ign)}`` with ``order`` the indices of the
-    job's detections by descending score, cut to ``MAX_DETS``."""
+    job's detections by descending score, cut to ``MAX_DETS``.
+
+    ``to_host=False``: no copy back and no synchronisation -- a ``DeviceMatches``; its ``status`` is for the caller to
+    read.  ``all_columns``: the output arrays have the columns of every job of the list (``column_layout``), those of the
+    jobs outside ``which`` zeroed, instead of the columns of ``which`` alone."""
     import torch
     from .. import _lib
+    which = np.asarray(which, dtype=np.int64)
     tab = jobs.table[which]
     T, J = len(IOU_THRS), len(which)
-    kept = np.minimum(tab[:, 3], MAX_DETS)
-    o_off, gi_off = np.cumsum(kept) - kept, np.cumsum(tab[:, 1]) - tab[:, 1]
-    n_out, n_gign = int(kept.sum()), int(tab[:, 1].sum())
+    if all_columns:
+        kept, o_off, n_out, gi_off, n_gign = column_layout(jobs)
+        kept, o_off, gi_off = kept[which], o_off[which], gi_off[which]
+    else:
+        kept = np.minimum(tab[:, 3], MAX_DETS)
+        o_off, gi_off = np.cumsum(kept) - kept, np.cumsum(tab[:, 1]) - tab[:, 1]
+        n_out, n_gign = int(kept.sum()), int(tab[:, 1].sum())
     n_gt, n_dt = len(jobs.gt), len(jobs.dt)
     f64 = np.concatenate([jobs.gt.reshape(-1), jobs.dt.reshape(-1), jobs.scores, jobs.rng[which].reshape(-1), IOU_THRS])
     i64 = np.concatenate([tab, o_off[:, None], gi_off[:, None]], 1)
@@ -204,16 +232,21 @@ def coco_match_device(jobs, which, device):
     with torch.cuda.device(device):
         fd = torch.from_numpy(np.ascontiguousarray(f64, dtype=np.float64)).to(device)
         jd = torch.from_numpy(np.ascontiguousarray(i64, dtype=np.int64)).to(device)
-        res = torch.empty((at_gign + n_gign,), dtype=torch.uint8, device=device)
+        res = (torch.zeros if all_columns else torch.empty)((at_gign + n_gign,), dtype=torch.uint8, device=device)
         base, f0 = res.data_ptr(), fd.data_ptr()
 
         def f64_at(n_doubles):
             return _lib.c_void_p(f0 + 8 * n_doubles)
-        _lib.check(_lib.lib().dagr_coco_match(
-            f64_at(0), f64_at(4 * n_gt), f64_at(4 * n_gt + 4 * n_dt), _lib.ptr(jd), f64_at(4 * n_gt + 5 * n_dt),
-            f64_at(4 * n_gt + 5 * n_dt + 2 * J), T, MAX_DETS, J, n_gt, n_dt, int(tab[:, 1].max()), int(tab[:, 3].max()),
-            n_out, n_gign, _lib.c_void_p(base + at_order), _lib.c_void_p(base + at_dtm), _lib.c_void_p(base + at_ign),
-            _lib.c_void_p(base + at_gign), _lib.c_void_p(base), _lib.cur_stream(device)), "coco_match")
+        if J:
+            _lib.check(_lib.lib().dagr_coco_match(
+                f64_at(0), f64_at(4 * n_gt), f64_at(4 * n_gt + 4 * n_dt), _lib.ptr(jd), f64_at(4 * n_gt + 5 * n_dt),
+                f64_at(4 * n_gt + 5 * n_dt + 2 * J), T, MAX_DETS, J, n_gt, n_dt, int(tab[:, 1].max()), int(tab[:, 3].max()),
+                n_out, n_gign, _lib.c_void_p(base + at_order), _lib.c_void_p(base + at_dtm), _lib.c_void_p(base + at_ign),
+                _lib.c_void_p(base + at_gign), _lib.c_void_p(base), _lib.cur_stream(device)), "coco_match")
+        if not to_host:
+            return DeviceMatches(which, o_off, kept, gi_off, res[at_order:at_dtm].view(torch.int32),
+                                 res[at_dtm:at_ign].view(T, n_out), res[at_ign:at_gign].view(T, n_out), res[at_gign:],
+                                 res[:4].view(torch.int32), fd[4 * n_gt + 4 * n_dt:4 * n_gt + 5 * n_dt], jd)
         host = res.cpu().numpy()
     if host[:4].view(np.int32)[0] != 0:
         raise RuntimeError("dagr_coco_match: a job did not fit its arrays (status 1)")
@@ -249,6 +282,138 @@ def match_jobs_device(jobs, device=None, stats=None):
     return out
 
 
+def accumulate_groups(jobs, n_classes):
+    """The groups of ``_accumulate`` in ``column_layout``'s columns.  ``build_jobs`` orders the jobs by (class, area range,
+    image), so the columns of a (class, area range) are ONE contiguous run, images ascending and the matcher's order inside
+    an image: the order ``_accumulate`` concatenates in.  Returns (group = class * len(AREA_RNG) + area range of every
+    job [J], group_ptr [n_groups + 1] over the columns)."""
+    kept = column_layout(jobs)[0]
+    n_groups = n_classes * len(AREA_RNG)
+    group = jobs.key[:, 0] * len(AREA_RNG) + jobs.key[:, 1]
+    if np.any(np.diff(group) < 0):
+        raise RuntimeError("accumulate_groups: the job list is not ordered by (class, area range)")
+    cols = np.zeros(n_groups, dtype=np.int64)
+    np.add.at(cols, group, kept)
+    return group.astype(np.int64), np.concatenate([[0], np.cumsum(cols)]).astype(np.int64)
+
+
+def score_order(scores, col_group):
+    """``perm`` of ``dagr_coco_accumulate`` (torch, on the tensors' device): the columns group after group and inside a
+    group as ``np.argsort(-scores, kind="mergesort")`` leaves them -- descending score, equal scores in column order, NaN
+    last.  Two stable sorts: by score over everything, then by group."""
+    import torch
+    by_score = torch.sort(0.0 - scores, stable=True).indices             # 0 - s: -0.0 and 0.0 are one key
+    by_group = torch.sort(col_group[by_score], stable=True).indices
+    return by_score[by_group].to(torch.int32)
+
+
+def accumulate_tile():
+    """Positions one workgroup of ``dagr_coco_accumulate`` takes at a time (DAGR_COCO_ACC_TILE)."""
+    from .. import _lib
+    return int(_lib.lib().dagr_coco_accumulate_tile())
+
+
+def accumulate_workspace_bytes(n_thr, n_cols):
+    """Bytes of workspace ``dagr_coco_accumulate`` needs (dagr_coco_accumulate_workspace_bytes)."""
+    from .. import _lib
+    need = int(_lib.lib().dagr_coco_accumulate_workspace_bytes(n_thr, n_cols))
+    if need == 0:
+        _lib.check(-1, "coco_accumulate_workspace_bytes")
+    return need
+
+
+def coco_accumulate_device(dtm, dt_ign, perm, group_ptr, group_ngt, precision=None, workspace_bytes=None):
+    """``dagr_coco_accumulate`` on device tensors: ``dtm`` / ``dt_ign`` uint8 or bool [T, n_cols], ``perm`` int32 [n_cols],
+    ``group_ptr`` int64 [n_groups + 1], ``group_ngt`` int64 [n_groups].  Returns (precision float64 [T, len(REC_THRS),
+    n_groups], status int32 [1]), both on the device and not synchronised; status 1: a bad ``perm`` / ``group_ptr``,
+    ``precision`` untouched.  ``precision`` / ``workspace_bytes``: a caller's output array / another workspace size."""
+    import torch
+    from .. import _lib
+    device = dtm.device
+    T, n_cols = dtm.shape
+    n_groups = group_ngt.shape[0]
+    if dt_ign.shape != dtm.shape or perm.shape != (n_cols,) or group_ptr.shape != (n_groups + 1,):
+        raise ValueError(f"coco_accumulate_device: dtm {tuple(dtm.shape)}, dt_ign {tuple(dt_ign.shape)}, perm "
+                         f"{tuple(perm.shape)}, group_ptr {tuple(group_ptr.shape)}, group_ngt {tuple(group_ngt.shape)}")
+
+    def flags(x):
+        return (x.view(torch.uint8) if x.dtype == torch.bool else x.to(torch.uint8)).contiguous()
+    dtm, dt_ign = flags(dtm), flags(dt_ign)
+    perm, group_ptr = perm.to(torch.int32).contiguous(), group_ptr.to(torch.int64).contiguous()
+    group_ngt = group_ngt.to(torch.int64).contiguous()
+    L = _lib.lib()
+    with torch.cuda.device(device):
+        ws_bytes = accumulate_workspace_bytes(T, n_cols) if workspace_bytes is None else int(workspace_bytes)
+        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=device)
+        rec = torch.from_numpy(REC_THRS).to(device)
+        if precision is None:
+            precision = torch.empty((T, len(REC_THRS), n_groups), dtype=torch.float64, device=device)
+        status = torch.zeros((1,), dtype=torch.int32, device=device)
+        _lib.check(L.dagr_coco_accumulate(_lib.ptr(dtm), _lib.ptr(dt_ign), _lib.ptr(perm), _lib.ptr(group_ptr),
+                                          _lib.ptr(group_ngt), _lib.ptr(rec), len(REC_THRS), float(np.spacing(1)), T, n_groups,
+                                          n_cols, _lib.ptr(ws), ws_bytes, _lib.ptr(precision), _lib.ptr(status),
+                                          _lib.cur_stream(device)), "coco_accumulate")
+    return precision, status
+
+
+def accumulate_device(scores, dtm, dt_ign, col_group, group_ptr, group_ngt):
+    """``_accumulate`` of every group at once, on the device arrays of the matcher (``coco_match_device(to_host=False,
+    all_columns=True)``): ``scores`` float64 [n_cols] and ``col_group`` int64 [n_cols] per column, ``dtm`` / ``dt_ign``
+    [T, n_cols].  -> ``coco_accumulate_device``'s (precision, status)."""
+    return coco_accumulate_device(dtm, dt_ign, score_order(scores, col_group), group_ptr, group_ngt)
+
+
+def precision_on_device(jobs, n_classes, device=None, stats=None):
+    """Job list -> ``dagr_coco_match`` -> ``dagr_coco_accumulate`` -> the precision array [T, R, classes, area ranges], the
+    only thing copied back (with the two status words).  A job beyond the matcher's bounds is matched on the host, as in
+    ``match_jobs_device``, and uploaded into its columns."""
+    import torch
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"precision_on_device: the evaluation runs on a GPU, not on {device}")
+    T, A = len(IOU_THRS), len(AREA_RNG)
+    max_g, max_d = device_bounds()
+    fits = (jobs.table[:, 1] <= max_g) & (jobs.table[:, 3] <= max_d)
+    on_dev, on_host = np.flatnonzero(fits), np.flatnonzero(~fits)
+    from_host = match_jobs_host(jobs, on_host)
+    kept, o_off, n_cols, gi_off, n_gign = column_layout(jobs)
+    group, group_ptr = accumulate_groups(jobs, n_classes)
+    n_groups = n_classes * A
+    if stats is not None:
+        stats["host_fallback_jobs"] = len({(int(c), int(i)) for c, _, i in jobs.key[on_host]})
+        stats["device_jobs"] = int(len(on_dev))
+        stats["accumulate_device_groups"] = int(len(np.unique(group)))
+    m = coco_match_device(jobs, on_dev, device, to_host=False, all_columns=True)
+    with torch.cuda.device(device):
+        per_job = np.stack([group, kept, jobs.table[:, 1], jobs.table[:, 2]], 1).reshape(-1)
+        i64 = torch.from_numpy(np.concatenate([per_job, group_ptr]).astype(np.int64)).to(device)
+        per_job, group_ptr_d = i64[:4 * len(jobs)].view(-1, 4), i64[4 * len(jobs):]
+        col_group = torch.repeat_interleave(per_job[:, 0], per_job[:, 1], output_size=n_cols)
+        col_first = torch.repeat_interleave(per_job[:, 3], per_job[:, 1], output_size=n_cols)
+        entry_group = torch.repeat_interleave(per_job[:, 0], per_job[:, 2], output_size=n_gign)
+        scores = m.scores[col_first + m.order.long()] if n_cols else m.scores[:0]
+        if len(on_host):                                              # host-matched jobs: into their columns / entries
+            cols = np.concatenate([o_off[j] + np.arange(kept[j]) for j in on_host])
+            entries = np.concatenate([gi_off[j] + np.arange(jobs.table[j, 1]) for j in on_host])
+            at = torch.from_numpy(np.concatenate([cols, entries]).astype(np.int64)).to(device)
+            cols_d, entries_d = at[:len(cols)], at[len(cols):]
+            scores[cols_d] = torch.from_numpy(np.concatenate([from_host[int(j)][0] for j in on_host])).to(device)
+            flag = np.concatenate([np.concatenate([from_host[int(j)][k] for j in on_host], 1) for k in (1, 2)], 0)
+            flag = torch.from_numpy(flag.astype(np.uint8)).to(device)
+            m.dtm[:, cols_d], m.dt_ign[:, cols_d] = flag[:T], flag[T:]
+            m.g_ign[entries_d] = torch.from_numpy(np.concatenate([from_host[int(j)][3] for j in on_host]).astype(np.uint8)).to(device)
+        group_ngt = torch.zeros((n_groups,), dtype=torch.int64, device=device)
+        group_ngt.index_add_(0, entry_group, (m.g_ign == 0).to(torch.int64))
+        precision, status = accumulate_device(scores, m.dtm, m.dt_ign, col_group, group_ptr_d, group_ngt)
+        back = torch.cat((precision.reshape(-1).view(torch.uint8), status.view(torch.uint8), m.status.view(torch.uint8))).cpu().numpy()
+    acc_status, match_status = back[-8:].view(np.int32)
+    if match_status != 0:
+        raise RuntimeError("dagr_coco_match: a job did not fit its arrays (status 1)")
+    if acc_status != 0:
+        raise RuntimeError("dagr_coco_accumulate: perm or group_ptr outside the arrays (status 1)")
+    return back[:-8].view(np.float64).reshape(T, len(REC_THRS), n_classes, A).copy()
+
+
 def _precision_from_jobs(images, n_classes, matcher):
     """Job list -> matcher -> per (class, area range) the per-image tuples, in image order, -> ``_accumulate``."""
     jobs = build_jobs(images, n_classes)
@@ -265,15 +430,22 @@ def _precision_from_jobs(images, n_classes, matcher):
 
 
 def evaluate_detection(gt_boxes_list, dt_boxes_list, classes=("car", "pedestrian"), height=240, width=304,
-                       time_tol=50000, on_device=False, device=None, stats=None):
+                       time_tol=50000, on_device=False, device=None, stats=None, accumulate_on_device=False):
     """gt / dt: one dict per image, ``boxes`` [n, 4] (x1, y1, x2, y2), ``labels`` [n], detections also ``scores`` [n].
     ``on_device``: the greedy matcher runs as ``dagr_coco_match`` on ``device`` (default: the current GPU) instead of
     ``_evaluate_image``; the same booleans reach the same ``_accumulate``, so the result is the same floats.
-    ``stats`` (a dict) then receives ``host_fallback_jobs`` and ``device_jobs``."""
+    ``stats`` (a dict) then receives ``host_fallback_jobs`` and ``device_jobs``.
+    ``accumulate_on_device`` (needs ``on_device``): ``_accumulate`` runs on the device too, as ``dagr_coco_accumulate`` on
+    the matcher's arrays where they are, and only the precision array [10, 101, classes, 4] comes back -- again the same
+    floats.  ``stats`` also receives ``accumulate_device_groups``, the (class, area range) groups that had a job."""
+    if accumulate_on_device and not on_device:
+        raise ValueError("evaluate_detection: accumulate_on_device=True needs on_device=True")
     images = evaluated_images(gt_boxes_list, dt_boxes_list)
     if sum(len(im[2]) for im in images) == 0:
         return {k: 0 for k in OUT_KEYS}
-    if on_device:
+    if accumulate_on_device:
+        prec = precision_on_device(build_jobs(images, len(classes)), len(classes), device, stats)
+    elif on_device:
         prec = _precision_from_jobs(images, len(classes), lambda jobs: match_jobs_device(jobs, device, stats))
     else:
         prec = -np.ones((len(IOU_THRS), len(REC_THRS), len(classes), len(AREA_RNG)))

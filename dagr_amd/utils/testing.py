@@ -37,6 +37,20 @@ def evaluate_on_device(enabled):
     _EVALUATE_ON_DEVICE = bool(enabled)
 
 
+_ACCUMULATE_ON_DEVICE = False
+
+
+def accumulate_on_device(enabled):
+    """What ``DetectionBuffer(on_device=True, accumulate_on_device=None)`` does in this process: whether the accumulation
+    of the evaluation runs on the GPU too (the scripts' ``--evaluate_on_device`` turns it on with ``evaluate_on_device``)."""
+    global _ACCUMULATE_ON_DEVICE
+    _ACCUMULATE_ON_DEVICE = bool(enabled)
+
+
+def accumulate_on_device_default():
+    return _ACCUMULATE_ON_DEVICE
+
+
 def run_test_with_visualization(loader, model, dataset: str, log_every_n_batch=-1, name="", compile_detections=False,
                                 no_eval=False, on_device=None):
     """``on_device`` (no counterpart in the reference): the mAP buffer keeps the boxes on the GPU and matches them there

@@ -782,6 +782,44 @@ int dagr_coco_match(const double *gt_xywh, const double *dt_xywh, const double *
                     int64_t n_gign, int32_t *order, uint8_t *dtm, uint8_t *dt_ign, uint8_t *g_ign, int32_t *status,
                     void *stream);
 
+/* ---------------------------------------------------------------------------
+ * COCO-protocol accumulation (csrc/coco_accumulate.hip): utils/coco_eval.py:_accumulate after its sort, for every
+ * (class, area range) group and every IoU threshold in one call -- cumulative counts of the counted true and false
+ * positives along the score order, precision, its envelope, and the envelope at the first position whose recall reaches
+ * each recall point.  All arrays are DEVICE memory.
+ *
+ *   dtm[n_thr, n_cols], dt_ign[n_thr, n_cols]   uint8, as dagr_coco_match wrote them (non-zero = true)
+ *   perm[n_cols]                                int32: the column visited k-th.  The positions of a group are contiguous, and
+ *                                               inside a group they run by descending score, equal scores in the order of
+ *                                               _accumulate's concatenation (image, then the matcher's order)
+ *   group_ptr[n_groups + 1]                     int64: group g owns the positions group_ptr[g] .. group_ptr[g + 1] of perm
+ *   group_ngt[n_groups]                         int64: the group's ground truth that is not ignored
+ *   rec_thrs[n_rec]                             float64, 1 <= n_rec <= DAGR_COCO_ACC_MAX_REC = 128: the host's REC_THRS
+ *   eps                                         the host's numpy.spacing(1), > 0
+ *
+ * Outputs:
+ *   precision[n_thr, n_rec, n_groups]   float64: -1 for a group with group_ngt <= 0; otherwise, per threshold and recall
+ *                           point r, max over i >= idx of tp[i] / ((fp[i] + tp[i]) + eps), idx the first position with
+ *                           tp[idx] / group_ngt >= rec_thrs[r] (both float64 divisions), and 0 when no position qualifies
+ *                           (a group without positions included).  The same bits as the host's.
+ *   status                  int32, zeroed here; 1 afterwards if an entry of perm lies outside [0, n_cols) or group_ptr is
+ *                           not non-decreasing inside [0, n_cols]: `precision` is then left untouched
+ *
+ * One workgroup per (group, threshold) walks its segment in tiles of DAGR_COCO_ACC_TILE positions (dagr_coco_accumulate_tile
+ * reports it) with the counts carried as integers, so a segment may be of any length up to n_cols <= 2^31 - 1.  The
+ * workspace (dagr_coco_accumulate_workspace_bytes; 0 and an error message for sizes out of range) holds one byte per
+ * (threshold, position): the flags gathered through perm.  A workspace that is too small, n_thr > 16 or n_rec beyond its
+ * bound fail with DAGR_ERR_INVALID_ARG before any device work.  No host synchronisation.
+ * ------------------------------------------------------------------------ */
+#define DAGR_COCO_ACC_TILE 1024
+#define DAGR_COCO_ACC_MAX_REC 128
+int32_t dagr_coco_accumulate_tile(void);
+size_t dagr_coco_accumulate_workspace_bytes(int32_t n_thr, int64_t n_cols);
+int dagr_coco_accumulate(const uint8_t *dtm, const uint8_t *dt_ign, const int32_t *perm, const int64_t *group_ptr,
+                         const int64_t *group_ngt, const double *rec_thrs, int32_t n_rec, double eps, int32_t n_thr,
+                         int32_t n_groups, int64_t n_cols, void *workspace, size_t workspace_bytes, double *precision,
+                         int32_t *status, void *stream);
+
 /* Host-side helper: first n offsets of the search spiral (spiral.h:1-15), the closed form the
  * search kernel uses.  dx/dy are HOST arrays.  Lets CPU-only tests pin the visiting order. */
 int dagr_spiral_offsets(int32_t n, int32_t *dx_host, int32_t *dy_host);

@@ -41,7 +41,8 @@ def _evaluation_options(p):
     g = p.add_argument_group("evaluation")
     g.add_argument("--evaluate_on_device", action="store_true", default=argparse.SUPPRESS,
                    help="run_test.py / run_test_interframe.py: keep detections and ground truth on the GPU until the end "
-                        "of the run and match them there (dagr_coco_match); the metrics are the same numbers")
+                        "of the run, match them there (dagr_coco_match) and accumulate the precision there "
+                        "(dagr_coco_accumulate); the metrics are the same numbers")
 
 
 def flags(description, argv=None, extra=None, default_config="dagr-s-dsec.yaml"):
@@ -56,6 +57,7 @@ def flags(description, argv=None, extra=None, default_config="dagr-s-dsec.yaml")
     # the test scripts call run_test_with_visualization as the reference's scripts do, without the option: it reaches the
     # driver as the process default
     testing.evaluate_on_device(bool(getattr(a, "evaluate_on_device", False)))
+    testing.accumulate_on_device(bool(getattr(a, "evaluate_on_device", False)))
     if a.windows is None:
         a.windows = max(32, 4 * a.batch_size)
     return a
