@@ -18,7 +18,9 @@ import torch
 
 from .. import _lib
 
-ZERO, CONV, LINEAR, POOL, CARTESIAN = 0, 1, 2, 3, 4
+# ``dagr_flops_module`` and the DAGR_FLOPS_* kinds, as include/dagr_hip.h declares them
+FlopsModule = _lib.FlopsModule
+ZERO, CONV, LINEAR, POOL, CARTESIAN = (_lib.ENUMS["DAGR_FLOPS_" + k] for k in ("ZERO", "CONV", "LINEAR", "POOL", "CARTESIAN"))
 
 _LEAVES = ("MySplineConv", "SplineConvToDense", "Pooling", "BatchNormData", "Cartesian", "Linear")
 _CONTAINERS = ("DAGR", "Net", "GNNHead", "Layer", "ConvBlock", "ConvBlockWithSkip", "EV_TGN")
@@ -26,12 +28,6 @@ _CONTAINERS = ("DAGR", "Net", "GNNHead", "Layer", "ConvBlock", "ConvBlockWithSki
 UPDATE_NOT_COUNTED = ("the update pass's FLOP log (log index 1, evaluate_flops(dense=False); the reference's per-layer "
                       "incremental sets, asynchronous/conv.py:94-227, max_pool.py:389-509) is not implemented yet -- "
                       "only the init pass is counted: pass dense=True (count_flops.py --dense)")
-
-
-class FlopsModule(ctypes.Structure):
-    """``dagr_flops_module`` (include/dagr_hip.h)."""
-    _fields_ = [("kind", ctypes.c_int32), ("level", ctypes.c_int32), ("cin", ctypes.c_int32), ("cout", ctypes.c_int32),
-                ("root", ctypes.c_int32), ("bias", ctypes.c_int32)]
 
 
 def logged_modules(model):
@@ -115,6 +111,7 @@ class Accountant:
         table = (FlopsModule * max(1, len(rows)))(*rows)
         host = torch.frombuffer(bytearray(bytes(table)), dtype=torch.int32)
         self.mods = host.to(eng.device)
+        self.mods_ptr = ctypes.cast(_lib.ptr(self.mods), ctypes.POINTER(FlopsModule))      # the table on the device
         self.out = torch.zeros(len(rows), dtype=torch.int64, device=eng.device)
 
     def count(self):
@@ -124,7 +121,7 @@ class Accountant:
         deg = eng._nbr[2]
         lv = eng.levels
         _lib.check(L.dagr_async_flops(P(deg), int(eng._N), P(lv[0].counts), P(lv[1].counts), P(lv[2].counts),
-                                      P(lv[3].counts), P(self.mods), len(self.leaf_names), P(self.out),
+                                      P(lv[3].counts), self.mods_ptr, len(self.leaf_names), P(self.out),
                                       _lib.cur_stream(eng.device)), "async_flops")
         leaf = dict(zip(self.leaf_names, self.out.tolist()))
         flops = {}

@@ -4,9 +4,12 @@ flip (:90-112), random crop with probability 0.2 (:201-243), random zoom (:148-1
 the crop to the sensor.  All of them act on the per-sample ``Data`` BEFORE the graph exists (host side, integer pixel
 coordinates), exactly where the reference applies them (the loaders' ``transform``)."""
 import copy
+import ctypes
 
 import numpy as np
 import torch
+
+from .. import _lib
 
 
 class Compose:
@@ -263,8 +266,7 @@ class RandomTranslate:
 
 
 # ``dagr_aug_params`` (include/dagr_hip.h): one record per sample, drawn on the host, read by the kernels on the device
-AUG_PARAMS = np.dtype([("flip", "<i4"), ("crop_on", "<i4"), ("crop_lo", "<i4", 2), ("crop_hi", "<i4", 2), ("zoom", "<f4"),
-                       ("move", "<i4", 2)])
+AUG_PARAMS = np.dtype(_lib.AugParams)
 
 
 class DeviceAugmentations:
@@ -359,9 +361,9 @@ class DeviceAugmentations:
         return self._run(batch, par, ptr, pos.contiguous(), t.contiguous(), x.contiguous(), B, W, H)
 
     def _run(self, batch, par, ptr, pos, t, x, B, W, H):
-        from .. import _lib
         L, dev, N = _lib.lib(), pos.device, int(pos.shape[0])
         stream = _lib.cur_stream(dev)
+        par_ptr = ctypes.cast(_lib.ptr(par), ctypes.POINTER(_lib.AugParams))        # the records on the device
         out_pos, out_t, out_x = torch.empty((N, 2), dtype=torch.int16, device=dev), torch.empty_like(t), torch.empty_like(x)
         out_batch = torch.empty(N, dtype=torch.long, device=dev)
         meta = torch.empty(B + 2, dtype=torch.int32, device=dev)           # out_ptr[B + 1], then the status word
@@ -369,7 +371,7 @@ class DeviceAugmentations:
         ws_bytes = L.dagr_augment_workspace_bytes(N)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.dagr_augment_events(_lib.ptr(par), B, W, H, _lib.ptr(pos), pos.element_size(), _lib.ptr(t),
+            _lib.check(L.dagr_augment_events(par_ptr, B, W, H, _lib.ptr(pos), pos.element_size(), _lib.ptr(t),
                                              t.element_size(), _lib.ptr(x), x.element_size(), _lib.ptr(ptr), N,
                                              _lib.ptr(out_pos), _lib.ptr(out_t), _lib.ptr(out_x), _lib.ptr(out_batch),
                                              _lib.ptr(meta), _lib.ptr(status), _lib.ptr(ws), ws_bytes, stream),
@@ -382,7 +384,7 @@ class DeviceAugmentations:
                     raise TypeError(f"image must be uint8 / float32 [{B}, C, {H}, {W}], got {image.dtype} {tuple(image.shape)}")
                 image = image.contiguous()
                 out.image = torch.empty_like(image)
-                _lib.check(L.dagr_augment_frames(_lib.ptr(par), B, int(image.shape[1]), H, W, image.element_size(),
+                _lib.check(L.dagr_augment_frames(par_ptr, B, int(image.shape[1]), H, W, image.element_size(),
                                                  1 if REFERENCE_FRAME_CROP else 0, _lib.ptr(image), _lib.ptr(out.image),
                                                  stream), "augment_frames")
             for name in ("bbox", "bbox0"):
@@ -391,7 +393,7 @@ class DeviceAugmentations:
                     continue
                 rows = b.to(torch.float32).contiguous()
                 new = torch.empty_like(rows)
-                _lib.check(L.dagr_augment_boxes(_lib.ptr(par), B, W, H, _lib.ptr(rows),
+                _lib.check(L.dagr_augment_boxes(par_ptr, B, W, H, _lib.ptr(rows),
                                                 _lib.ptr(getattr(batch, name + "_batch").to(torch.long).contiguous()),
                                                 int(rows.shape[0]), int(rows.shape[1]), _lib.ptr(new), stream),
                            "augment_boxes")

@@ -292,13 +292,14 @@ def test_status_word_reports_a_non_monotone_sample_ptr():
     ws_bytes = L.dagr_augment_workspace_bytes(N)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     stream = _lib.cur_stream(dev)
+    par_ptr = ctypes.cast(_lib.ptr(par), ctypes.POINTER(_lib.AugParams))
 
     def run(ptr_host):
         ptr = torch.tensor(ptr_host, dtype=torch.int32, device=dev)
         out_pos, out_t, out_p = torch.full_like(pos, -7), torch.full_like(t, -7), torch.full_like(p, -7)
         out_ptr = torch.full((B + 1,), -7, dtype=torch.int32, device=dev)
         status = torch.full((1,), 5, dtype=torch.int32, device=dev)
-        _lib.check(L.dagr_augment_events(_lib.ptr(par), B, W, H, _lib.ptr(pos), 2, _lib.ptr(t), 4, _lib.ptr(p), 1,
+        _lib.check(L.dagr_augment_events(par_ptr, B, W, H, _lib.ptr(pos), 2, _lib.ptr(t), 4, _lib.ptr(p), 1,
                                          _lib.ptr(ptr), N, _lib.ptr(out_pos), _lib.ptr(out_t), _lib.ptr(out_p), None,
                                          _lib.ptr(out_ptr), _lib.ptr(status), _lib.ptr(ws), ws_bytes, stream))
         return out_pos, out_t, out_p, out_ptr, status
@@ -315,9 +316,10 @@ def test_status_word_reports_a_non_monotone_sample_ptr():
         assert bool((out_pos == -7).all()) and bool((out_t == -7).all()) and bool((out_p == -7).all())   # nothing written
     # host-side argument checks never reach the device
     one = ctypes.c_void_p(16)
-    assert L.dagr_augment_events(one, B, W, H, one, 3, one, 4, one, 1, one, N, one, one, one, None, one, one, one,
+    par_one = ctypes.cast(one, ctypes.POINTER(_lib.AugParams))
+    assert L.dagr_augment_events(par_one, B, W, H, one, 3, one, 4, one, 1, one, N, one, one, one, None, one, one, one,
                                  ws_bytes, None) != 0 and b"pos_width" in L.dagr_last_error()
-    assert L.dagr_augment_frames(one, 1, 3, H, W, 2, 1, one, one, None) != 0 and b"elem_bytes" in L.dagr_last_error()
+    assert L.dagr_augment_frames(par_one, 1, 3, H, W, 2, 1, one, one, None) != 0 and b"elem_bytes" in L.dagr_last_error()
 
 
 def test_train_script_with_augment_on_device(tmp_path):
