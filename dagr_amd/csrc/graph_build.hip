@@ -114,6 +114,29 @@ int validate(const dagr_graph_desc *d) {
     return DAGR_OK;
 }
 
+// the part of K1 behind the loads: (x, y, t) denormalised, b the sample, `prev_later`: the event before this one belongs
+// to the same sample and carries a later timestamp
+__device__ __forceinline__ void count_event_at(int e, int x, int y, int t, int b, bool prev_later, int W, int H, int B,
+                                               int32_t *__restrict__ cnt, int32_t *__restrict__ ev_xyb,
+                                               int32_t *__restrict__ ev_t, int32_t *__restrict__ ev_rank,
+                                               int32_t *__restrict__ flag_fov, int32_t *__restrict__ flag_time) {
+    ev_t[e] = t;
+    // time flag: set when timestamps are not non-decreasing in event order inside a sample.  Ids then do not order time:
+    // the search takes its generic form (every candidate tested on its own, ids instead of positions as recency).
+    if (prev_later) *flag_time = 1;
+    if (x < 0 || x >= W || y < 0 || y >= H || b < 0 || b >= B) {
+        // The reference would index its FIFO volume out of bounds here; we flag and drop the
+        // event from the index (it keeps its self loop).
+        atomicOr(flag_fov, 1);
+        ev_xyb[e] = -1;
+        ev_rank[e] = 0;
+        return;
+    }
+    ev_xyb[e] = x | (y << 12) | (b << 24);
+    const int key = x + W * (y + H * b);
+    ev_rank[e] = atomicAdd(&cnt[key], 1);
+}
+
 // ---------------------------------------------------------------------------------------------
 // K1: denormalise (ev_tgn.py:11-16) + per-key count.  One thread per event.
 //   int(pos * [W,H,T] + 1e-3): fp32 multiply, fp32 add (separately rounded -- this TU is built with
@@ -139,26 +162,14 @@ __device__ __forceinline__ void count_event(int e, const void *__restrict__ pos_
         t = (int)(fT * pt + 1e-3f);
     }
     const int b = (int)batch[e];
-    ev_t[e] = t;
-    // time flag: set when timestamps are not non-decreasing in event order inside a sample.  Ids then do not order time:
-    // the search takes its generic form (every candidate tested on its own, ids instead of positions as recency).
+    bool prev_later = false;
     if (e > 0 && (int)batch[e - 1] == b) {
         int tp;
         if (kIntPos) tp = static_cast<const int32_t *>(pos_)[3 * (int64_t)(e - 1) + 2];
         else tp = (int)(fT * static_cast<const float *>(pos_)[3 * (int64_t)(e - 1) + 2] + 1e-3f);
-        if (tp > t) *flag_time = 1;
+        prev_later = tp > t;
     }
-    if (x < 0 || x >= W || y < 0 || y >= H || b < 0 || b >= B) {
-        // The reference would index its FIFO volume out of bounds here; we flag and drop the
-        // event from the index (it keeps its self loop).
-        atomicOr(flag_fov, 1);
-        ev_xyb[e] = -1;
-        ev_rank[e] = 0;
-        return;
-    }
-    ev_xyb[e] = x | (y << 12) | (b << 24);
-    const int key = x + W * (y + H * b);
-    ev_rank[e] = atomicAdd(&cnt[key], 1);
+    count_event_at(e, x, y, t, b, prev_later, W, H, B, cnt, ev_xyb, ev_t, ev_rank, flag_fov, flag_time);
 }
 
 template <typename BatchT, bool kIntPos>
@@ -1035,6 +1046,231 @@ __global__ __launch_bounds__(kBlock) void k_stage_window(const float *__restrict
     if (i + 2 * gridDim.x * kBlock < 3 * N) pos_out[i + 2 * gridDim.x * kBlock] = pos[i + 2 * gridDim.x * kBlock];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Event stream (dagr_stream_stage): the raw events of the running window stay on the device, in one of two raw sets; a
+// step reads the survivors from one set and the new events from the caller, writes the next window into the other set and,
+// formatted, into the static input buffers, and runs K1 on it -- what k_stage_window does for a caller's window.
+constexpr int kStreamLanes = 128;           // validate(): batch_size <= 127
+constexpr int64_t kNever = INT64_MIN;       // t_ref / t_last of a lane that has none yet
+
+struct StreamState {
+    int32_t *hdr;       // [8]: 0 raw set holding the current window, 1 its event count, 2 events of the step being staged,
+                        //      3 raw set that step reads
+    int64_t *t_ref;     // [B]  reference instant of the last step
+    int64_t *t_last;    // [B]  newest event ever pushed to the lane
+    int32_t *seg;       // [2B] {start, count} of each lane's segment in the current set
+    int32_t *plan;      // [5B] per lane {output start, count, first survivor, survivors, first new event kept}
+    int64_t *t0, *t1;   // [cap] raw sets: timestamps,
+    int32_t *xy0, *xy1; // [cap] pixels (x | y << 16, two int16),
+    int8_t *p0, *p1;    // [cap] polarities
+    size_t head_bytes;  // everything in front of the raw sets
+};
+
+size_t carve_stream(int B, int64_t cap, char *base, StreamState *st) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        size_t o = off;
+        off = align_up(off + bytes, 256);
+        return base ? base + o : nullptr;
+    };
+    StreamState s;
+    s.hdr = (int32_t *)take(8 * 4);
+    s.t_ref = (int64_t *)take((size_t)B * 8);
+    s.t_last = (int64_t *)take((size_t)B * 8);
+    s.seg = (int32_t *)take((size_t)B * 2 * 4);
+    s.plan = (int32_t *)take((size_t)B * 5 * 4);
+    s.head_bytes = off;
+    s.t0 = (int64_t *)take((size_t)cap * 8);
+    s.t1 = (int64_t *)take((size_t)cap * 8);
+    s.xy0 = (int32_t *)take((size_t)cap * 4);
+    s.xy1 = (int32_t *)take((size_t)cap * 4);
+    s.p0 = (int8_t *)take((size_t)cap);
+    s.p1 = (int8_t *)take((size_t)cap);
+    if (st) *st = s;
+    return off;
+}
+
+__global__ __launch_bounds__(kStreamLanes) void k_stream_reset(StreamState st, int B) {
+    const int b = threadIdx.x;
+    if (b < 8) st.hdr[b] = 0;
+    if (b < B) {
+        st.t_ref[b] = kNever;
+        st.t_last[b] = kNever;
+        st.seg[2 * b] = st.seg[2 * b + 1] = 0;
+        for (int k = 0; k < 5; ++k) st.plan[5 * b + k] = 0;
+    }
+}
+
+template <typename BatchT>
+__device__ __forceinline__ int first_lane_at_least(const BatchT *__restrict__ a, int n, int key) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)a[mid] < (int64_t)key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ int first_later(const int64_t *__restrict__ t, int n, int64_t thr) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (t[mid] <= thr) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// Launch 1 of a stream step, one block, one thread per lane: the new events' segment in batch_new, t_ref, the cut in the
+// resident segment and in the new one (binary searches on t), the prefix sum over the lanes, and the plan launch 2 follows.
+// The lane bounds of the NEXT window are written here too: launch 2 reads the plan only.
+template <typename BatchT>
+__global__ __launch_bounds__(kStreamLanes) void k_stream_plan(StreamState st, int B, int cap,
+                                                              const BatchT *__restrict__ batch_new,
+                                                              const int64_t *__restrict__ t_new, int n_new,
+                                                              const int64_t *__restrict__ t_now, int64_t window_us,
+                                                              int32_t *__restrict__ n_dev,
+                                                              int32_t *__restrict__ lane_count,
+                                                              int32_t *__restrict__ status) {
+    __shared__ int s_cnt[kStreamLanes], s_start[kStreamLanes];
+    const int b = threadIdx.x;
+    const int src = st.hdr[0] & 1;
+    int flags = 0, first_old = 0, keep_old = 0, first_new = 0, keep_new = 0;
+    if (b < B) {
+        const int ns = first_lane_at_least(batch_new, n_new, b);
+        const int ne = max(ns, first_lane_at_least(batch_new, n_new, b + 1));
+        const int64_t last = st.t_last[b], ref_prev = st.t_ref[b];
+        int64_t newest = last;
+        if (ne > ns) {
+            if (last != kNever && t_new[ns] < last) flags |= 1;
+            newest = max(last, t_new[ne - 1]);
+        }
+        const int64_t ref = t_now ? t_now[b] : (newest != kNever ? newest : ref_prev);   // (no event yet: t_ref stays)
+        if ((newest != kNever && ref < newest) || (ref_prev != kNever && ref < ref_prev)) flags |= 2;
+        // an event stays while 0 <= ref - t < window_us: t > thr (nothing is later than ref, or bit 1 is up)
+        const int64_t thr = ref < INT64_MIN + window_us ? INT64_MIN : ref - window_us;
+        const int s0 = min(max(st.seg[2 * b], 0), cap);
+        const int c0 = min(max(st.seg[2 * b + 1], 0), cap - s0);
+        const int cut = first_later((src ? st.t1 : st.t0) + s0, c0, thr);
+        first_old = s0 + cut;
+        keep_old = c0 - cut;
+        const int cut_new = first_later(t_new + ns, ne - ns, thr);
+        first_new = ns + cut_new;
+        keep_new = ne - ns - cut_new;
+        st.t_ref[b] = ref;
+        st.t_last[b] = newest;
+        s_cnt[b] = keep_old + keep_new;      // <= 2 cap < 2^26
+    }
+    __syncthreads();
+    if (b == 0) {       // at most 127 lanes: a serial prefix sum, clamped to the capacity as it goes
+        int run = 0, over = 0;
+        for (int l = 0; l < B; ++l) {
+            const int c = min(s_cnt[l], cap - run);
+            over |= c < s_cnt[l];
+            s_start[l] = run;
+            s_cnt[l] = c;
+            run += c;
+        }
+        if (over) flags |= 4;
+        st.hdr[0] = src ^ 1;
+        st.hdr[1] = run;
+        st.hdr[2] = run;
+        st.hdr[3] = src;
+        *n_dev = run;
+    }
+    __syncthreads();
+    if (b < B) {
+        const int start = s_start[b], c = s_cnt[b];
+        int32_t *pl = st.plan + 5 * b;
+        pl[0] = start; pl[1] = c; pl[2] = first_old; pl[3] = min(keep_old, c); pl[4] = first_new;
+        st.seg[2 * b] = start;
+        st.seg[2 * b + 1] = c;
+        lane_count[b] = c;
+    }
+    if (flags) atomicOr(status, flags);
+}
+
+// Launch 2: one thread per event of the next window (grid sized for the capacity, bounded by the count launch 1 left).  The
+// plan sits in LDS; a thread finds its lane there, gathers its raw event from the survivors or from the new events, writes
+// it to the other raw set and, formatted (dagr_format_events' fp32 divisions), to the static input buffers, and runs K1 on
+// the formatted row.  Thread i < n_new also checks new event i against its predecessor (status bits 0 and 3).
+template <typename BatchT>
+__global__ __launch_bounds__(kBlock) void k_stream_gather(StreamState st, int B, int cap,
+                                                         const int32_t *__restrict__ xy_new,
+                                                         const int64_t *__restrict__ t_new,
+                                                         const int8_t *__restrict__ p_new,
+                                                         const BatchT *__restrict__ batch_new, int n_new,
+                                                         int time_window, float *__restrict__ pos_out,
+                                                         float *__restrict__ feat_out, int32_t *__restrict__ batch_out,
+                                                         int32_t *__restrict__ status8, int32_t *__restrict__ status,
+                                                         int W, int H, int32_t *__restrict__ cnt,
+                                                         int32_t *__restrict__ ev_xyb, int32_t *__restrict__ ev_t,
+                                                         int32_t *__restrict__ ev_rank) {
+    __shared__ int s_plan[5 * kStreamLanes];
+    __shared__ int64_t s_ref[kStreamLanes];
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < 8) status8[i] = 0;     // the builder's status words start over (dagr_graph_build_window_dev)
+    if (i < n_new) {
+        const int64_t bi = (int64_t)batch_new[i];
+        int f = (bi < 0 || bi >= B) ? 8 : 0;
+        if (i > 0) {
+            const int64_t bp = (int64_t)batch_new[i - 1];
+            if (bp > bi) f |= 8;
+            else if (bp == bi && t_new[i - 1] > t_new[i]) f |= 1;
+        }
+        if (f) atomicOr(status, f);
+    }
+    const int n_out = min(st.hdr[2], cap);
+    if ((int)(blockIdx.x * kBlock) >= n_out) return;        // (the whole block)
+    for (int k = threadIdx.x; k < 5 * B; k += kBlock) s_plan[k] = st.plan[k];
+    if ((int)threadIdx.x < B) s_ref[threadIdx.x] = st.t_ref[threadIdx.x];
+    __syncthreads();
+    if (i >= n_out) return;
+    int b = 0, hi = B;             // the last lane that starts at or before i (an empty lane is never that one)
+    while (hi - b > 1) {
+        const int mid = (b + hi) >> 1;
+        if (s_plan[5 * mid] <= i) b = mid; else hi = mid;
+    }
+    const int k = min(max(i - s_plan[5 * b], 0), max(s_plan[5 * b + 1] - 1, 0));
+    const int first_old = s_plan[5 * b + 2], keep_old = s_plan[5 * b + 3], first_new = s_plan[5 * b + 4];
+    const int64_t ref = s_ref[b];
+    const bool src = st.hdr[3] & 1;
+    const int64_t *t_src = src ? st.t1 : st.t0;
+    const int32_t *xy_src = src ? st.xy1 : st.xy0;
+    const int8_t *p_src = src ? st.p1 : st.p0;
+    const bool old = k < keep_old;
+    if (!old && n_new <= 0) return;
+    const int j = old ? min(max(first_old + k, 0), cap - 1) : min(max(first_new + k - keep_old, 0), n_new - 1);
+    const int64_t t = (old ? t_src : t_new)[j];
+    const int32_t xy = (old ? xy_src : xy_new)[j];
+    const int8_t p = (old ? p_src : p_new)[j];
+    int64_t t_prev = t;            // the event before this one in the lane, for K1's time flag
+    if (k > 0) {
+        const bool old_p = k - 1 < keep_old;
+        const int jp = old_p ? min(max(first_old + k - 1, 0), cap - 1) : min(max(first_new + k - 1 - keep_old, 0), n_new - 1);
+        t_prev = (old_p ? t_src : t_new)[jp];
+    }
+    (src ? st.t0 : st.t1)[i] = t;
+    (src ? st.xy0 : st.xy1)[i] = xy;
+    (src ? st.p0 : st.p1)[i] = p;
+    // t_rel = time_window - (t_ref - t); a flagged step's differences are clamped so that the int32 holds them
+    const int64_t lim = (int64_t)1 << 30, big = (int64_t)1 << 60;
+    const int64_t ref_c = min(max(ref, -big), big);
+    const int t_rel = time_window - (int)min(max(ref_c - min(max(t, -big), big), -lim), lim);
+    const int t_rel_prev = time_window - (int)min(max(ref_c - min(max(t_prev, -big), big), -lim), lim);
+    const float fW = (float)W, fH = (float)H, fT = (float)time_window;
+    const float px = (float)(int16_t)(xy & 0xffff) / fW;    // IEEE fp32 division (buffers.py:43), as k_format_events
+    const float py = (float)(int16_t)(xy >> 16) / fH;
+    const float pt = (float)t_rel / fT;
+    pos_out[3 * (int64_t)i + 0] = px;
+    pos_out[3 * (int64_t)i + 1] = py;
+    pos_out[3 * (int64_t)i + 2] = pt;
+    feat_out[i] = (float)p;
+    batch_out[i] = b;
+    const int tq = (int)(fT * pt + 1e-3f);
+    const int tq_prev = (int)(fT * ((float)t_rel_prev / fT) + 1e-3f);
+    count_event_at(i, (int)(fW * px + 1e-3f), (int)(fH * py + 1e-3f), tq, b, tq_prev > tq, W, H, B, cnt, ev_xyb, ev_t,
+                   ev_rank, status8 + 8, status8 + 9);
+}
+
 __global__ void k_format_events(const int16_t *__restrict__ xy, const int32_t *__restrict__ t,
                                 const int8_t *__restrict__ p, int64_t N, float fW, float fH, float fT,
                                 float *__restrict__ pos, float *__restrict__ feat) {
@@ -1245,6 +1481,86 @@ int dagr_stage_window(const dagr_graph_desc *desc, void *workspace, const float 
         k_stage_window<int32_t><<<grid, kBlock, 0, (hipStream_t)stream>>>(
             pos, feat, (const int32_t *)batch, (int)N, pos_out, feat_out, batch_out, n_dev, ws.status, W, H, B,
             (float)desc->time_window, ws.cnt, ws.ev_xyb, ws.ev_t, ws.ev_rank);
+    DAGR_CHECK_LAUNCH();
+    return DAGR_OK;
+}
+
+static int stream_args(int32_t B, int64_t capacity, StreamState *st, void *state) {
+    DAGR_CHECK_ARG(B >= 1 && B < kStreamLanes, "stream: B must be in 1..127");
+    DAGR_CHECK_ARG(capacity >= 1 && capacity < (1ll << 31) / 64, "stream: capacity out of range");
+    carve_stream(B, capacity, (char *)state, st);
+    return DAGR_OK;
+}
+
+size_t dagr_stream_state_bytes(int32_t B, int64_t capacity) {
+    if (B < 1 || B >= kStreamLanes || capacity < 1 || capacity >= (1ll << 31) / 64) return 0;
+    return carve_stream(B, capacity, nullptr, nullptr);
+}
+
+int dagr_stream_reset(void *state, int32_t B, int64_t capacity, void *stream) {
+    DAGR_CHECK_ARG(state != nullptr, "stream: state is NULL");
+    StreamState st;
+    int rc = stream_args(B, capacity, &st, state);
+    if (rc != DAGR_OK) return rc;
+    k_stream_reset<<<1, kStreamLanes, 0, (hipStream_t)stream>>>(st, B);
+    DAGR_CHECK_LAUNCH();
+    return DAGR_OK;
+}
+
+int dagr_stream_grow(const void *state, int64_t capacity, void *state_new, int64_t capacity_new, int32_t B, void *stream_) {
+    DAGR_CHECK_ARG(state && state_new && state != state_new && capacity_new >= capacity, "stream: bad arguments to grow");
+    StreamState a, b;
+    int rc = stream_args(B, capacity, &a, const_cast<void *>(state));
+    if (rc == DAGR_OK) rc = stream_args(B, capacity_new, &b, state_new);
+    if (rc != DAGR_OK) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t n = (size_t)capacity;
+    DAGR_CHECK_HIP(hipMemcpyAsync(b.hdr, a.hdr, a.head_bytes, hipMemcpyDeviceToDevice, stream));
+    DAGR_CHECK_HIP(hipMemcpyAsync(b.t0, a.t0, n * 8, hipMemcpyDeviceToDevice, stream));
+    DAGR_CHECK_HIP(hipMemcpyAsync(b.t1, a.t1, n * 8, hipMemcpyDeviceToDevice, stream));
+    DAGR_CHECK_HIP(hipMemcpyAsync(b.xy0, a.xy0, n * 4, hipMemcpyDeviceToDevice, stream));
+    DAGR_CHECK_HIP(hipMemcpyAsync(b.xy1, a.xy1, n * 4, hipMemcpyDeviceToDevice, stream));
+    DAGR_CHECK_HIP(hipMemcpyAsync(b.p0, a.p0, n, hipMemcpyDeviceToDevice, stream));
+    DAGR_CHECK_HIP(hipMemcpyAsync(b.p1, a.p1, n, hipMemcpyDeviceToDevice, stream));
+    return DAGR_OK;
+}
+
+int dagr_stream_stage(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                      const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const void *batch_new,
+                      int32_t batch_is_int64, int64_t n_new, const int64_t *t_now, int64_t window_us, float *pos_out,
+                      float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status,
+                      void *stream_) {
+    int rc = validate(desc);
+    if (rc != DAGR_OK) return rc;
+    DAGR_CHECK_ARG(workspace && state && pos_out && feat_out && batch_out && n_dev && lane_count && status,
+                   "stream: NULL pointer");
+    DAGR_CHECK_ARG(B == desc->batch_size, "stream: B differs from desc.batch_size");
+    DAGR_CHECK_ARG(window_us > 0 && window_us <= desc->time_window, "stream: window_us must be in 1..time_window");
+    DAGR_CHECK_ARG(capacity <= desc->max_events, "stream: capacity exceeds desc.max_events (the size of the outputs)");
+    DAGR_CHECK_ARG(n_new >= 0 && n_new <= capacity, "stream: capacity < n_new");
+    DAGR_CHECK_ARG(n_new == 0 || (xy_new && t_new && p_new && batch_new), "stream: NULL input");
+    DAGR_CHECK_ARG(((uintptr_t)xy_new & 3) == 0, "stream: xy_new must be 4-byte aligned");
+    StreamState st;
+    rc = stream_args(B, capacity, &st, state);
+    if (rc != DAGR_OK) return rc;
+    GraphWs ws;
+    carve(*desc, (char *)workspace, &ws);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int cap = (int)capacity, n = (int)n_new;
+    const unsigned grid = (unsigned)ceil_div(capacity, kBlock);
+    if (batch_is_int64) {
+        k_stream_plan<int64_t><<<1, kStreamLanes, 0, stream>>>(st, B, cap, (const int64_t *)batch_new, t_new, n, t_now,
+                                                              window_us, n_dev, lane_count, status);
+        k_stream_gather<int64_t><<<grid, kBlock, 0, stream>>>(
+            st, B, cap, (const int32_t *)xy_new, t_new, p_new, (const int64_t *)batch_new, n, desc->time_window, pos_out,
+            feat_out, batch_out, ws.status, status, desc->width, desc->height, ws.cnt, ws.ev_xyb, ws.ev_t, ws.ev_rank);
+    } else {
+        k_stream_plan<int32_t><<<1, kStreamLanes, 0, stream>>>(st, B, cap, (const int32_t *)batch_new, t_new, n, t_now,
+                                                              window_us, n_dev, lane_count, status);
+        k_stream_gather<int32_t><<<grid, kBlock, 0, stream>>>(
+            st, B, cap, (const int32_t *)xy_new, t_new, p_new, (const int32_t *)batch_new, n, desc->time_window, pos_out,
+            feat_out, batch_out, ws.status, status, desc->width, desc->height, ws.cnt, ws.ev_xyb, ws.ev_t, ws.ev_rank);
+    }
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
 }

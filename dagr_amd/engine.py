@@ -298,6 +298,75 @@ def _basicblock_forward(blk, x):
     return _add_relu_(blk.conv2(out), identity)
 
 
+class StreamState:
+    """Device-side state of one event stream (``dagr_stream_stage``): the raw events of the running window in two sets
+    written alternately, the lanes' bounds and reference instants, the stream's status word, the per-lane counts of the
+    last step -- and what the host knows of the window's size, which is an upper bound until a count has been read.
+    Owned by the stream (``dagr.streaming.EventStream``), handed to ``WindowEngine.forward_stream`` on every step: the
+    engine keeps no pointer into it, so a buffer that grew leaves nothing stale; an engine rebuilt with a smaller
+    capacity than the stream's is grown to it on the stream's next step."""
+
+    def __init__(self, batch_size, window_us, device):
+        self.B, self.window_us, self.device = int(batch_size), int(window_us), torch.device(device)
+        self.cap = 0
+        self.state = None
+        self.status = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self.lane_count = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        self.image = None                     # the last frame given (--use_image)
+        # the counts come back with every step, into pinned memory; the host reads them only after a synchronisation it
+        # makes anyway (the detections' read-back)
+        self._host = torch.zeros((self.B,), dtype=torch.int32).pin_memory()
+        self._known = np.zeros((self.B,), np.int64)     # the last counts read
+        self._since = 0                                 # events pushed since
+        self._fresh = True                              # _known belongs to the last step staged
+
+    def _alloc(self, cap):
+        L = _lib.lib()
+        nbytes = L.dagr_stream_state_bytes(self.B, cap)
+        if nbytes == 0:
+            raise RuntimeError(f"dagr_stream_state_bytes({self.B}, {cap}): out of range")
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
+    def reset(self):
+        if self.state is not None:
+            _lib.check(_lib.lib().dagr_stream_reset(_lib.ptr(self.state), self.B, self.cap, _lib.cur_stream(self.device)),
+                       "stream_reset")
+        self.status.zero_()
+        self.lane_count.zero_()
+        torch.cuda.current_stream(self.device).synchronize()       # (a count copy may still be on its way)
+        self._host.zero_()
+        self._known, self._since, self._fresh = np.zeros((self.B,), np.int64), 0, True
+
+    def grow(self, cap):
+        """Raw sets of ``cap`` events; the resident events are copied over on the device."""
+        if cap <= self.cap:
+            return
+        new = self._alloc(cap)
+        L, stream = _lib.lib(), _lib.cur_stream(self.device)
+        if self.state is None:
+            _lib.check(L.dagr_stream_reset(_lib.ptr(new), self.B, cap, stream), "stream_reset")
+        else:
+            _lib.check(L.dagr_stream_grow(_lib.ptr(self.state), self.cap, _lib.ptr(new), cap, self.B, stream), "stream_grow")
+        self.state, self.cap = new, cap
+
+    def read_counts(self):
+        """The stream has just been drained: the last step's counts are in the pinned buffer."""
+        self._known, self._since, self._fresh = self._host.numpy().astype(np.int64), 0, True
+
+    def bound(self):
+        """Upper bound of the resident count: the last count read plus every event pushed since."""
+        return int(self._known.sum()) + self._since
+
+    def counts_known(self):
+        """Per-lane counts of the last step if they have been read, else None."""
+        return self._known.copy() if self._fresh else None
+
+    def _pushed_now(self, n_new):
+        self._since += int(n_new)
+        self._fresh = False
+        self._host.copy_(self.lane_count, non_blocking=True)
+
+
 class _Level:
     """Device buffers of one pooled graph level (capacity T = gx*gy*(B+1) nodes)."""
 
@@ -380,6 +449,7 @@ class WindowEngine:
         self._app = None
         self._n_rows = 0
         self._N = 0                  # events of the resident window (0: none yet)
+        self._stream_pending = None  # the stream whose step is the resident window, until its count has been read
         self._prepare(bb, head)
         self.max_events = 0
         self._alloc_events(int(max_events))
@@ -1432,6 +1502,88 @@ class WindowEngine:
         self._nbr = (self.nbr_src[:N], self.nbr_code[:N], self.deg[:N])
         self._x0 = self.x0buf[:N]
         return out if static_out else out.clone()   # the graph's output buffer is rewritten by the next window
+
+    def forward_stream(self, st, xy, t, p, batch, t_now=None, image=None):
+        """One step of an event stream (``StreamState`` ``st``): ``_forward_window_graph`` with ``dagr_stream_stage`` in
+        place of ``dagr_stage_window``.  The new raw events (``xy`` int16[n,2], ``t`` int64[n] absolute us, ``p`` int8[n],
+        ``batch`` int32/int64[n] sorted lanes, ``t_now`` int64[B] or None; all on the device) join the window kept in
+        ``st``; two launches write the next window into the static input buffers and its count to device memory, and
+        the window runs on them -- the captured graph in latency mode, the same body launch by launch otherwise.  No host
+        synchronisation: the host knows an upper bound of the window's size only (``st.bound()``), which is what the
+        buffers are sized by.  Returns ``(out, (det, n_keep))``, both valid until the engine's next call."""
+        from .model.utils import postprocess_device
+        if not self.l0_tiles or self.no_events:
+            raise RuntimeError("forward_stream runs the captured window's body: it needs the tiled level-0 conv "
+                               "(l0_tiles) and the event path (no --no_events)")
+        L, P = self.L, _lib.ptr
+        n_new = int(t.shape[0])
+        need = max(st.bound() + n_new, st.cap)       # (a stream that grew on another engine keeps its capacity)
+        if need > self.max_events:
+            self._alloc_events(max(need, 2 * self.max_events))       # (re-captures, as a large window does)
+        if st.state is None or need > st.cap:
+            st.grow(self.max_events)
+        if self.use_image:
+            if image is not None:
+                st.image = image.to(device=self.device, dtype=torch.float32).clone()
+            if st.image is None:
+                raise RuntimeError("model was built with --use_image: the stream needs a frame (image=) on its first step")
+            if self.in_image is None or self.in_image.shape != st.image.shape:
+                self.in_image = torch.empty(tuple(st.image.shape), dtype=torch.float32, device=self.device)
+                self._wg = None
+                self._wg_warm = 0
+            self.in_image.copy_(st.image)
+        key = (float(self.model.conf_threshold), float(self.model.nms_threshold))
+        if key != self._post_key:                   # (re)capture with these thresholds
+            self._post_key = key
+            self._wg = None
+            self._wg_warm = 0
+            self._graph = None
+            self._graph_warm = 0
+        self._post_fresh = False
+        g = self.graph
+        _lib.check(L.dagr_stream_stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(xy), P(t), P(p),
+                                       P(batch), 1 if batch.dtype == torch.int64 else 0, n_new, P(t_now), st.window_us,
+                                       P(self.in_pos), P(self.in_feat), P(self.in_batch), P(self.n_dev), P(st.lane_count),
+                                       P(st.status), _lib.cur_stream(self.device)), "stream_stage")
+        if not self.window_graph:                    # throughput mode: the body of the captured window, launch by launch
+            out = self._forward_static()
+        elif self._wg is None:
+            if self._wg_warm < 2:
+                self._wg_warm += 1
+                out = self._forward_static()
+            else:
+                cg = torch.cuda.CUDAGraph()
+                with _capture(cg):
+                    out = self._forward_static()
+                self._wg, self._wg_out, self._wg_post = cg, out, (self._det, self._n_keep)
+                cg.replay()
+        else:
+            self._wg.replay()
+            out = self._wg_out
+            self._det, self._n_keep = self._wg_post
+            self._post_fresh = True
+        st._pushed_now(n_new)
+        # the resident window is this step's, but its size is on the device: nothing may attach to it (can_append) until
+        # the count has been read (stream_counted)
+        self._N = self._n_rows = 0
+        self._async_on = False
+        self._pos = self._batch = None
+        self._stream_pending = st
+        det = (self._det, self._n_keep) if self._post_fresh else \
+            postprocess_device(out, self.num_classes, key[0], key[1], self.H, self.W)
+        return out, det
+
+    def stream_counted(self, st):
+        """The stream has been drained (the detections' read-back): take the last step's counts, and if that step is still
+        the engine's resident window, describe it as ``_forward_window_graph`` describes a caller's."""
+        st.read_counts()
+        if self._stream_pending is st and self._pos is None and st.counts_known() is not None:
+            N = int(st.counts_known().sum())
+            self._N = self._n_rows = N
+            self._pos, self._batch = self.in_pos[:N], self.in_batch[:N]
+            self._nbr = (self.nbr_src[:N], self.nbr_code[:N], self.deg[:N])
+            self._x0 = self.x0buf[:N]
+        self._stream_pending = None
 
     def _replay_tail(self, static_out=False):
         """Everything after pool1 has launch shapes that do not depend on the window (node / edge counts stay on the

@@ -1,0 +1,228 @@
+"""Event streams: detections on a sliding window that is kept on the device.
+
+The engine detects on a window (``model(x, reset=True)``) and can attach events to one (``reset=False``); an
+``EventStream`` moves the window forward.  The raw events of the running window stay in device memory; a step uploads the
+NEW events only, two launches (``dagr_stream_stage``) retire what has left the window and write the next window into the
+static input buffers of the engine's captured window, and the window replays unchanged.  The host does no cutting, no
+``format_data`` and does not learn the window's size.
+
+What a step computes -- the definition, which ``StreamDefinition`` below states once in numpy (the yardstick of the
+documentation and of the tests; nothing on the device path calls it):
+
+* lanes ``b = 0 .. B-1`` are the samples of the model's ``batch_size``; each lane is an endless sequence of events
+  ``(x, y)`` int16 pixels, ``t`` int64 absolute microseconds, ``p`` int8 in {-1, +1}; inside a lane ``t`` is
+  non-decreasing, within a push and across pushes;
+* after a push ``t_ref[b]`` is ``t_now[b]`` when the caller gives ``t_now``, else the ``t`` of the lane's newest event;
+  it must not be older than the lane's newest event nor than the lane's previous ``t_ref``;
+* the lane's window is every event ever pushed to it with ``0 <= t_ref[b] - t < window_us``, in arrival order (a suffix of
+  the lane: what has left never comes back);
+* ``t_rel = time_window - (t_ref[b] - t)`` as int32 -- without ``t_now`` the newest event sits at ``time_window``, where
+  ``DSEC.preprocess_events`` puts it (data/dsec_data.py:157-163); ``window_us <= time_window``;
+* the batch window is the lanes' windows concatenated in lane order, the model input is ``format_data`` of
+  ``(x, y, t_rel, p)`` under the engine's ``(W, H, time_window)``, and the step's result is, bit for bit, what
+  ``model(that batch, reset=True)`` returns.
+"""
+import numpy as np
+
+from .utils.synthetic import format_data_np
+
+STATUS_BITS = ((1, "a timestamp goes backwards inside a lane (within a push or against the lane's newest event)"),
+               (2, "t_now is behind the lane's newest event or behind its previous t_ref"),
+               (4, "survivors plus new events exceed the stream's capacity"),
+               (8, "batch is not sorted or is outside [0, batch_size)"))
+
+
+class StreamDefinition:
+    """The definition above in numpy: ``push`` new events, read ``window()`` / ``formatted()`` / ``counts()``.  Malformed
+    pushes raise ``ValueError`` (the device path reports them in its status word instead)."""
+
+    def __init__(self, batch_size, width, height, time_window=1000000, window_us=50000):
+        if not 0 < int(window_us) <= int(time_window):
+            raise ValueError(f"window_us = {window_us} must be in 1..time_window = {time_window}")
+        self.B, self.W, self.H = int(batch_size), int(width), int(height)
+        self.time_window, self.window_us = int(time_window), int(window_us)
+        self.reset()
+
+    def reset(self):
+        self.lanes = [dict(x=np.zeros(0, np.int16), y=np.zeros(0, np.int16), t=np.zeros(0, np.int64), p=np.zeros(0, np.int8))
+                      for _ in range(self.B)]
+        self.t_ref = [None] * self.B
+        self.t_last = [None] * self.B
+
+    def push(self, x, y, t, p, batch=None, t_now=None):
+        x, y, p = np.asarray(x, np.int16), np.asarray(y, np.int16), np.asarray(p, np.int8)
+        t = np.asarray(t, np.int64)
+        batch = np.zeros(len(t), np.int64) if batch is None else np.asarray(batch, np.int64)
+        if len(batch) and (np.any(np.diff(batch) < 0) or batch[0] < 0 or batch[-1] >= self.B):
+            raise ValueError("batch is not sorted or is outside [0, batch_size)")
+        if t_now is not None:
+            t_now = np.broadcast_to(np.asarray(t_now, np.int64).reshape(-1), (self.B,))
+        parts, refs = [], []
+        for b in range(self.B):                           # everything is checked before anything is changed
+            m = batch == b
+            tb = t[m]
+            if len(tb) and (np.any(np.diff(tb) < 0) or (self.t_last[b] is not None and tb[0] < self.t_last[b])):
+                raise ValueError(f"lane {b}: a timestamp goes backwards")
+            newest = int(tb[-1]) if len(tb) else self.t_last[b]
+            ref = int(t_now[b]) if t_now is not None else (newest if newest is not None else self.t_ref[b])
+            if ref is not None and ((newest is not None and ref < newest) or
+                                    (self.t_ref[b] is not None and ref < self.t_ref[b])):
+                raise ValueError(f"lane {b}: t_now is behind the lane's newest event or behind its previous t_ref")
+            parts.append((m, newest))
+            refs.append(ref)
+        for b, ((m, newest), ref) in enumerate(zip(parts, refs)):
+            lane = self.lanes[b]
+            lane.update(x=np.concatenate([lane["x"], x[m]]), y=np.concatenate([lane["y"], y[m]]),
+                        t=np.concatenate([lane["t"], t[m]]), p=np.concatenate([lane["p"], p[m]]))
+            self.t_last[b], self.t_ref[b] = newest, ref
+            if ref is not None:
+                age = ref - lane["t"]
+                keep = (age >= 0) & (age < self.window_us)
+                for k in lane:
+                    lane[k] = lane[k][keep]
+
+    def counts(self):
+        return np.array([len(lane["t"]) for lane in self.lanes], np.int64)
+
+    def window(self):
+        """``(x, y, t_rel int32, p, batch int64)`` of the batch window."""
+        t_rel = [(self.time_window - (self.t_ref[b] - lane["t"])).astype(np.int32) if len(lane["t"]) else
+                 np.zeros(0, np.int32) for b, lane in enumerate(self.lanes)]
+        cat = {k: np.concatenate([lane[k] for lane in self.lanes]) for k in ("x", "y", "p")}
+        return cat["x"], cat["y"], np.concatenate(t_rel), cat["p"], np.repeat(np.arange(self.B, dtype=np.int64), self.counts())
+
+    def formatted(self):
+        """``(pos fp32[n,3], feat fp32[n,1], batch int64[n])``: the model input (``format_data``)."""
+        x, y, t_rel, p, batch = self.window()
+        return format_data_np(x, y, t_rel, self.W, self.H, self.time_window), p.astype(np.float32).reshape(-1, 1), batch
+
+
+def _flag_names(flag):
+    return "; ".join(text for bit, text in STATUS_BITS if flag & bit)
+
+
+class EventStream:
+    """Detections every step from an endless event stream, on the last ``window_us`` microseconds of every lane.
+
+    ``model``: an eval-mode ``DAGR`` on the GPU whose window engine runs the captured window: the tiled level-0 conv
+    (``l0_tiles``), the event path (no ``--no_events``), the engine path (``model.module_path_only`` False).
+    """
+
+    def __init__(self, model, window_us=50000):
+        import torch
+        self.model = model
+        self.window_us = int(window_us)
+        time_window = int(getattr(model.args, "time_window_us", 1000000))
+        if not 0 < self.window_us <= time_window:
+            raise ValueError(f"EventStream: window_us = {window_us} must be in 1..time_window = {time_window} "
+                             "(t_rel = time_window - age has to stay inside the model's time axis)")
+        if model.training:
+            raise RuntimeError("EventStream needs an eval-mode model (model.eval())")
+        dev = next(model.parameters()).device
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError(f"EventStream needs the model on the GPU (it is on {dev}): the stream lives in device "
+                               "memory and there is no CPU path")
+        if model.module_path_only:
+            raise RuntimeError("EventStream: module_path_only is set (--keep_temporal_ordering models run module by module); "
+                               "set model.module_path_only = False to run the window engine")
+        if bool(getattr(model.args, "no_events", False)):
+            raise RuntimeError("EventStream: --no_events returns the image branch's detections; there is no event window to slide")
+        eng = model.engine()
+        if not eng.l0_tiles:
+            raise RuntimeError("EventStream: l0_tiles is off for this model (the captured window needs the tiled level-0 "
+                               "conv: a 3x3 / 3x5 / 5x3 tap window and max_neighbors = 16)")
+        from .engine import StreamState
+        self.device = dev
+        self.B = eng.B
+        self.state = StreamState(eng.B, self.window_us, dev)
+        self._zeros = None
+
+    # ------------------------------------------------------------------------------------ inputs
+    def _upload(self, xy, t, p, batch, t_now):
+        """The new events on the device as (xy int16[n,2], t int64[n], p int8[n], batch int32/int64[n], t_now int64[B] or
+        None).  Host inputs are packed into one buffer: ONE upload, of the new events only."""
+        import torch
+        tensors = [v for v in (xy, t, p, batch, t_now) if v is not None]
+        if all(torch.is_tensor(v) and v.is_cuda for v in tensors):
+            n = int(t.shape[0])
+            if batch is None:
+                if self._zeros is None or self._zeros.shape[0] < n:
+                    self._zeros = torch.zeros((max(n, 4096),), dtype=torch.int32, device=self.device)
+                batch = self._zeros[:n]
+            elif batch.dtype not in (torch.int32, torch.int64):
+                batch = batch.to(torch.int32)
+            return (xy.to(torch.int16).reshape(-1, 2).contiguous(), t.to(torch.int64).contiguous(),
+                    p.to(torch.int8).reshape(-1).contiguous(), batch.contiguous(),
+                    None if t_now is None else t_now.to(torch.int64).reshape(-1).contiguous())
+
+        def host(v, dtype):
+            return np.ascontiguousarray((v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)).astype(dtype, copy=False))
+        t = host(t, np.int64)
+        n = len(t)
+        xy = host(xy, np.int16).reshape(-1, 2)
+        p = host(p, np.int8).reshape(-1)
+        batch = np.zeros(n, np.int32) if batch is None else host(batch, np.int32)
+        if not (len(xy) == len(p) == len(batch) == n):
+            raise ValueError("EventStream: xy, t, p and batch differ in length")
+        now = None if t_now is None else np.broadcast_to(host(t_now, np.int64).reshape(-1), (self.B,))
+        o_xy, o_b, o_p = 8 * n, 12 * n, 16 * n
+        o_now = (17 * n + 7) // 8 * 8
+        buf = np.empty(o_now + 8 * self.B, np.uint8)
+        buf[:o_xy] = t.view(np.uint8)
+        buf[o_xy:o_b] = xy.reshape(-1).view(np.uint8)
+        buf[o_b:o_p] = batch.view(np.uint8)
+        buf[o_p:o_p + n] = p.view(np.uint8)
+        if now is not None:
+            buf[o_now:] = np.ascontiguousarray(now).view(np.uint8)
+        d = torch.from_numpy(buf).to(self.device)
+        return (d[o_xy:o_b].view(torch.int16).view(-1, 2), d[:o_xy].view(torch.int64), d[o_p:o_p + n].view(torch.int8),
+                d[o_b:o_p].view(torch.int32), None if now is None else d[o_now:].view(torch.int64))
+
+    # ------------------------------------------------------------------------------------ steps
+    def step_device(self, xy, t, p, batch=None, t_now=None, image=None):
+        """One step without a host synchronisation: ``(det[B, A, 6], n_keep[B])`` as ``forward_detections`` returns them,
+        valid until the engine's next call."""
+        import torch
+        if t_now is not None and not torch.is_tensor(t_now) and np.ndim(t_now) == 0:
+            t_now = np.full((self.B,), int(t_now), np.int64)
+        elif torch.is_tensor(t_now) and t_now.numel() == 1 and self.B > 1:
+            t_now = t_now.reshape(1).expand(self.B)
+        xy, t, p, batch, t_now = self._upload(xy, t, p, batch, t_now)
+        if t_now is not None and t_now.numel() != self.B:
+            raise ValueError(f"EventStream: t_now needs one instant per lane ({self.B})")
+        eng = self.model.engine()
+        with torch.no_grad():
+            _, det = eng.forward_stream(self.state, xy, t, p, batch, t_now=t_now, image=image)
+        self.model._window = None            # a reset=False call then starts from a window of its own
+        return det
+
+    def step(self, xy, t, p, batch=None, t_now=None, image=None):
+        """One step: the detections list ``model(x, reset=True)[0]`` returns for the stream's window."""
+        from .model.utils import detections_from_device
+        det, n_keep = self.step_device(xy, t, p, batch=batch, t_now=t_now, image=image)
+        detections = detections_from_device(det, n_keep)        # the step's one synchronisation
+        self.model.engine().stream_counted(self.state)          # the counts came back with it
+        if self.model.check_device_status:
+            self.check_status()
+        return detections
+
+    def counts(self):
+        """Events per lane of the current window (synchronises)."""
+        import torch
+        torch.cuda.current_stream(self.device).synchronize()
+        self.model.engine().stream_counted(self.state)
+        known = self.state.counts_known()
+        return known if known is not None else np.zeros((self.B,), np.int64)
+
+    def reset(self):
+        """Empty the stream: no resident events, no reference instants, a clear status word."""
+        self.state.reset()
+
+    def check_status(self):
+        """Raise ``RuntimeError`` naming the stream's flag if a step raised one (the word is cleared: the stream goes on
+        from whatever the flagged step left), then the engine's own ``check_status``.  Synchronises."""
+        flag = int(self.state.status.item())
+        if flag:
+            self.state.status.zero_()
+            raise RuntimeError(f"event stream flagged {flag:#x}: {_flag_names(flag)}")
+        self.model.engine().check_status()

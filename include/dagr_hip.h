@@ -142,6 +142,52 @@ int dagr_stage_window(const dagr_graph_desc *desc, void *workspace, const float 
                       int32_t batch_is_int64, int64_t N, float *pos_out, float *feat_out, int32_t *batch_out,
                       int32_t *n_dev, void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * Event stream: a sliding window kept on the device
+ *   The raw events of the running window stay in caller-owned device memory (`state`); a step takes the NEW raw events,
+ *   retires what has left the window and writes the next window straight into the static input buffers of a captured
+ *   window -- what dagr_stage_window does for a caller's window -- with the event count left in device memory.
+ *
+ * What a step computes.  Lanes b = 0..B-1 are the samples of desc.batch_size; each lane is an endless event sequence of
+ * (x, y) int16 pixels, t int64 absolute microseconds, p int8 in {-1, +1}; inside a lane t is non-decreasing, within a
+ * push and across pushes.  After a push
+ *   t_ref[b] = t_now[b] when t_now is given, else the t of the lane's newest event; it must not be older than the lane's
+ *              newest event nor than the lane's previous t_ref;
+ *   the lane's window is every event ever pushed to it with 0 <= t_ref[b] - t < window_us, in arrival order (a suffix of
+ *              the lane: what has left never comes back);
+ *   t_rel    = time_window - (t_ref[b] - t) as int32 (without t_now the newest event sits at time_window, where
+ *              DSEC.preprocess_events puts it, data/dsec_data.py:157-163);
+ *   the batch window is the lanes' windows concatenated in lane order, and the outputs are dagr_format_events of
+ *              (x, y, t_rel, p) under (width, height, time_window): pos_out fp32[n,3], feat_out fp32[n], batch_out
+ *              int32[n] = the lane, *n_dev = n, lane_count[b] = events of lane b.
+ * The stage also clears the builder's status words and runs the build's first step on the formatted rows, exactly as
+ * dagr_stage_window does: dagr_graph_build_window_dev continues from either.  Two launches, no host synchronisation.
+ *
+ * state: dagr_stream_state_bytes(B, capacity) bytes, dagr_stream_reset before the first step (and to empty the stream).
+ *        It holds two raw sets of `capacity` events written alternately (13 bytes per event each), the lanes' segment
+ *        bounds and t_ref[B].  capacity <= desc.max_events, which sizes the outputs.
+ * xy_new int16[n_new,2] (4-byte aligned), t_new int64[n_new], p_new int8[n_new], batch_new int32/int64[n_new] sorted, in
+ * [0, B); t_now int64[B] or NULL; all in device memory.
+ * status: one int32 in device memory, bits are OR-ed in and never acted on by faulting (every index is clamped to the
+ * buffers; a flagged step's outputs are unspecified):
+ *   bit 0: a timestamp goes backwards inside a lane, within a push or against the lane's newest event;
+ *   bit 1: t_ref is behind the lane's newest event or behind its previous t_ref;
+ *   bit 2: survivors plus new events exceed `capacity`;
+ *   bit 3: batch_new is not sorted or is outside [0, B).
+ * Events outside the sensor raise the builder's own flag (dagr_graph_status).
+ * DAGR_ERR_INVALID_ARG before any launch: window_us <= 0, window_us > desc.time_window, capacity < n_new,
+ * capacity > desc.max_events, B != desc.batch_size, NULL pointers.
+ * dagr_stream_grow copies a state into a larger one (capacity_new >= capacity) on the device.
+ * ------------------------------------------------------------------------ */
+size_t dagr_stream_state_bytes(int32_t B, int64_t capacity);
+int dagr_stream_reset(void *state, int32_t B, int64_t capacity, void *stream);
+int dagr_stream_grow(const void *state, int64_t capacity, void *state_new, int64_t capacity_new, int32_t B, void *stream);
+int dagr_stream_stage(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                      const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const void *batch_new,
+                      int32_t batch_is_int64, int64_t n_new, const int64_t *t_now /* [B] or NULL */, int64_t window_us,
+                      float *pos_out, float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count /* [B] */,
+                      int32_t *status, void *stream);
+
 /* The neighbour search alone, again, on the pixel index the last dagr_graph_build_window left in `workspace` (same N):
  * rewrites nbr_src / nbr_code / deg and the edge count.  For measurement (bench.py times the search kernels on their own
  * stream with HIP events); a product caller has no use for it. */

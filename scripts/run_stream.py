@@ -1,0 +1,122 @@
+#!/usr/bin/env python
+"""Play one event sequence through a ``dagr.streaming.EventStream``: a detection every ``--step_us`` microseconds on the
+events of the last ``--window_us``.  Every step uploads only the events that arrived since the step before; the window
+slides on the device.  The detections are written as ``detections_<sequence>.npy`` with the rows
+``run_test_interframe.py`` writes, sorted by timestamp, so ``visualize_detections.py`` draws them.
+
+The sequence is the synthetic stand-in stream the other scripts fall back to (``--stream``, ``--events_per_window`` events
+per 50 ms, ``--width`` x ``--height``); ``main(argv, source=...)`` takes any object with ``t_range()`` and
+``events(t0, t1)`` (a dict of ``x``, ``y``, ``t``, ``p`` with ``t0 <= t < t1``) -- and, for ``--use_image`` models,
+``image_timestamps`` and ``image(i)`` (BGR uint8) -- in its place, as ``visualize_detections.main`` does.  Reading DSEC
+files is not part of this script."""
+import time
+import types
+
+import numpy as np
+import torch
+
+import _common as C
+from dagr.streaming import EventStream
+from dagr.utils.buffers import detections_to_records
+from dagr.utils.logging import set_up_logging_directory
+from dagr.utils import synthetic as syn
+
+
+def stream_options(p):
+    g = p.add_argument_group("event stream")
+    g.add_argument("--step_us", type=int, default=1000, help="microseconds between two detections")
+    g.add_argument("--window_us", type=int, default=50000, help="length of the sliding event window")
+    g.add_argument("--steps", type=int, default=100, help="number of steps to play (synthetic sequence)")
+    g.add_argument("--sequence", type=str, default="synthetic_stream", help="name the detections are written under")
+
+
+class SyntheticStream:
+    """``--steps`` x ``--step_us`` microseconds of the synthetic stand-in stream, ``events_per_window`` events per 50 ms,
+    with absolute timestamps (and one synthetic frame every 50 ms for ``--use_image`` models)."""
+
+    def __init__(self, a, t0=1 << 33):
+        self.duration = max(1, a.steps * a.step_us)
+        n = max(1, int(a.events_per_window * self.duration / 50000))
+        gen = syn.edges_window if a.stream == "edges" else syn.uniform_window
+        x, y, t, p = gen(n, a.width, a.height, seed=7, window_us=self.duration, time_window=self.duration)
+        self.x, self.y, self.p = x, y, p
+        self.t = t.astype(np.int64) + np.int64(t0)
+        self.t0, self.width, self.height = int(t0), a.width, a.height
+        self.image_timestamps = np.arange(self.t0, self.t0 + self.duration + 1, 50000, dtype=np.int64)
+
+    def t_range(self):
+        return self.t0, self.t0 + self.duration
+
+    def events(self, t0, t1):
+        i0, i1 = np.searchsorted(self.t, [t0, t1], side="left")
+        return dict(x=self.x[i0:i1], y=self.y[i0:i1], t=self.t[i0:i1], p=self.p[i0:i1])
+
+    def image(self, i):
+        rng = np.random.Generator(np.random.PCG64(1000 + int(i)))
+        return rng.integers(0, 256, (self.height, self.width, 3), dtype=np.uint8)
+
+
+def _frame(source, t, dev):
+    """The newest frame at or before ``t`` as the model's image batch (fp32 [1,3,H,W] in [0,1], RGB)."""
+    ts = np.asarray(source.image_timestamps)
+    i = int(np.clip(np.searchsorted(ts, t, side="right") - 1, 0, len(ts) - 1))
+    img = np.ascontiguousarray(np.asarray(source.image(i), dtype=np.uint8)[..., ::-1])
+    return i, torch.from_numpy(img).to(dev).permute(2, 0, 1).unsqueeze(0).float() / 255.0
+
+
+def play(a, model, source, dev):
+    """One detections list per step: ``[(t_step, detections of lane 0), ...]``."""
+    stream = EventStream(model, window_us=a.window_us)
+    t0, t1 = source.t_range()
+    out, last_frame = [], None
+    for t_step in range(int(t0) + a.step_us, int(t1) + 1, a.step_us):
+        ev = source.events(t_step - a.step_us, t_step)
+        xy = np.stack([np.asarray(ev["x"], np.int16), np.asarray(ev["y"], np.int16)], -1)
+        image = None
+        if model.backbone.use_image:
+            i, frame = _frame(source, t_step, dev)
+            if i != last_frame:
+                image, last_frame = frame, i
+        # every event of the step is older than t_step, the instant the detections are for
+        det = stream.step(xy, np.asarray(ev["t"], np.int64), np.asarray(ev["p"], np.int8), t_now=t_step, image=image)
+        out.append((t_step, det[0]))
+    return out
+
+
+def main(argv=None, model_factory=None, source=None):
+    a = C.flags(__doc__, argv, extra=stream_options)
+    if a.step_us <= 0 or a.window_us <= 0:
+        raise SystemExit("run_stream.py: --step_us and --window_us must be positive")
+    a.batch_size = 1                       # one sequence: one lane
+    world, rank, dev = C.distributed()
+    torch.manual_seed(42)
+    np.random.seed(42)
+    if source is None:
+        if a.dataset_directory is not None and rank == 0:
+            print(f"NOTICE: --dataset_directory {a.dataset_directory}: run_stream.py does not read DSEC files; playing the "
+                  "SYNTHETIC stand-in stream instead.", flush=True)
+        source = SyntheticStream(a)
+    geometry = types.SimpleNamespace(width=int(getattr(source, "width", a.width)), height=int(getattr(source, "height", a.height)))
+    args, net = (model_factory or C.build_model)(a, geometry, dev)
+    net = net.eval()
+    out_dir = set_up_logging_directory("synthetic", a.task, a.output_directory,
+                                       exp_name=getattr(a, "exp_name", "run_stream"))
+    t_start = time.perf_counter()
+    steps = play(a, net, source, dev)
+    seconds = time.perf_counter() - t_start
+    rec = [detections_to_records({k: v.cpu() for k, v in det.items()}, np.uint64(t)) for t, det in steps]
+    rec = np.concatenate(rec) if rec else detections_to_records(dict(boxes=np.zeros((0, 4)), labels=np.zeros(0), scores=np.zeros(0)), 0)
+    rec = rec[np.argsort(rec["t"], kind="stable")]
+    path = None
+    if rank == 0:
+        out_dir.mkdir(parents=True, exist_ok=True)
+        path = out_dir / f"detections_{a.sequence}.npy"
+        np.save(path, rec)
+        print(f"{len(steps)} steps of {a.step_us} us on a {a.window_us} us window in {seconds:.2f} s "
+              f"({1e3 * seconds / max(1, len(steps)):.2f} ms per step) -> {path}: {len(rec)} detections")
+    C.finish(world)
+    return path
+
+
+if __name__ == "__main__":
+    main()
