@@ -150,17 +150,25 @@ class _Conv1x1Gemm(torch.nn.Module):
         self.relu = relu       # ReLU in the GEMM epilogue (hipBLASLt) instead of a separate pass
         self.register_buffer("wt", conv.weight.detach().reshape(cout, cin).t().contiguous())
         self.register_buffer("b", conv.bias.detach().clone() if conv.bias is not None else torch.zeros(cout, device=conv.weight.device))
+        self.planes = None     # the weights as three bf16 planes (_split_pack), where _split_min_rows selects the layer
+        self.path = None       # "split" / "library": what the last forward ran
 
     def forward(self, x, residual=None):
         """``residual`` (a channels-last map of the output's shape): relu(conv(x) + bias + residual) in ONE library GEMM
         (dagr_gemm_epilogue: hipBLASLt with beta = 1 on the residual, bias and ReLU in the epilogue) -- the join of a
         bottleneck (net_img.py:47-48) without a pass of its own."""
+        N = self.wt.shape[1]
+        r = None if residual is None else residual.permute(0, 2, 3, 1)
+        if self.planes is not None:
+            y = _split_conv(x, self.planes, 1, self.stride, N, self.b, r, self.relu or r is not None)
+            if y is not None:
+                self.path = "split"
+                return y
+        self.path = "library"
         if self.stride != 1:
             x = x[:, :, ::self.stride, ::self.stride]
         B, C, H, W = x.shape
         a = x.permute(0, 2, 3, 1).reshape(-1, C)
-        N = self.wt.shape[1]
-        r = None if residual is None else residual.permute(0, 2, 3, 1)
         if _LT["ok"] and a.is_cuda and a.dtype == torch.float32 and a.stride(1) == 1 \
                 and (r is None or (r.is_contiguous() and tuple(r.shape) == (B, H, W, N))):
             # every 1x1 conv of the branch through the same entry: bias (+ residual) (+ ReLU) in the GEMM's epilogue, the
@@ -190,6 +198,67 @@ def _lt_workspace(device):
     if key not in _LT["ws"]:
         _LT["ws"][key] = torch.empty(int(_lib.lib().dagr_gemm_epilogue_workspace_bytes()), dtype=torch.uint8, device=device)
     return _LT["ws"][key]
+
+
+def _split_min_rows(K, N, taps):
+    """The selection rule of the split-bf16 MFMA kernel (csrc/gemm_split_bf16.hip): the fewest output rows M = B * Ho * Wo
+    from which a convolution with K input channels (per tap), N output channels and ``taps`` in (1, 9) runs on it instead
+    of the library, or None where the library keeps the layer at every size.  Written from the measured table
+    profiles/split_bf16_shapes.md (B = 8 at 640 x 480, and the B = 2, 320 x 215 rows): a class is in only where the kernel
+    beat the library by more than the run-to-run spread of the medians.  No timing at run time: the same shapes take the
+    same path in every run.
+      1x1, K 128..256: won at every M measured, 560 to 153 600 (13 - 39 % faster).
+      1x1, K 257..512: with N >= 256 won from M = 9 600 up (12 - 25 %), tied at 2 400; with N = 128 the gain (1 - 4 us of
+        48) did not clear the spread in one of three sessions.
+      1x1, K > 512: lost (the K loop of the few tiles a small M leaves is too long for one block per CU).
+      1x1, K < 128 or N < 128 (layer1, the dconvs): at the fp32 ridge, memory-bound; not measured, not selected.
+      3x3 stride 1: C = 128 won at M = 38 400 (23 %) and lost at 2 160; C = 64, 256, 512 lost."""
+    if taps == 1:
+        if K < 128 or N < 128 or K > 512:
+            return None
+        if K <= 256:
+            return 512
+        return 8192 if N >= 256 else None
+    if taps == 9 and K == 128 and N == 128:
+        return 32768
+    return None
+
+
+def _split_pack(wt):
+    """Wt[K, N] (fp32, dense, on the device) as the kernel's three bf16 planes; once per layer, at folding time."""
+    L = _lib.lib()
+    K, N = wt.shape
+    nbytes = int(L.dagr_gemm_split_bf16_packed_bytes(K, N))
+    if nbytes == 0 or not wt.is_cuda:
+        return None
+    out = torch.empty(nbytes, dtype=torch.uint8, device=wt.device)
+    _lib.check(L.dagr_gemm_split_bf16_pack(_lib.ptr(wt), K, N, _lib.ptr(out), nbytes, _lib.cur_stream(wt.device)),
+               "gemm_split_bf16_pack")
+    return out
+
+
+def _split_conv(x, planes, taps, stride, N, bias, r, relu):
+    """act(conv(x) + bias (+ r)) of a channels-last map on the split-bf16 kernel: a 1x1 with ``stride`` (read in place) or
+    a 3x3 / stride 1 / pad 1.  ``r``: the residual as an NHWC tensor.  Returns the channels-last result, or None where the
+    rule or the layout leaves the layer to the library; a failing launch raises."""
+    B, C, H, W = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    M = B * Ho * Wo
+    rows = _split_min_rows(C, N, taps)
+    xn = x.permute(0, 2, 3, 1)
+    if rows is None or M < rows or not (x.is_cuda and x.dtype == torch.float32 and xn.is_contiguous()) \
+            or (r is not None and not (r.is_contiguous() and tuple(r.shape) == (B, Ho, Wo, N))):
+        return None
+    y = torch.empty((B, Ho, Wo, N), dtype=torch.float32, device=x.device)
+    L, st = _lib.lib(), _lib.cur_stream(x.device)
+    if taps == 1:
+        rc = L.dagr_gemm_split_bf16(_lib.ptr(xn), M, C, C, _lib.ptr(planes), N, _lib.ptr(bias), _lib.ptr(r), N, int(relu),
+                                    _lib.ptr(y), N, B, H, W, stride, 0, st)
+    else:
+        rc = L.dagr_conv3x3_split_bf16(_lib.ptr(xn), B, H, W, C, C, _lib.ptr(planes), N, _lib.ptr(bias), _lib.ptr(r), N,
+                                       int(relu), _lib.ptr(y), N, 0, st)
+    _lib.check(rc, "gemm_split_bf16")
+    return y.permute(0, 3, 1, 2)
 
 
 def _gemmify_1x1(module):
@@ -242,6 +311,14 @@ def _conv_bias_relu(blk, name, x):
     260 ms per B = 8 forward instead of 4.7; profiles/r5_conv_phases.md.)"""
     conv = getattr(blk, name)
     b = getattr(blk, "_" + name + "_bias", None)
+    planes = getattr(conv, "_split_planes", None)
+    if planes is not None:          # a stride-1 3x3 the rule selects: bias + ReLU in the kernel's epilogue
+        out = _split_conv(x, planes, 9, 1, conv.out_channels, b, None, True)
+        if out is not None:
+            conv._split_path = "split"
+            return out
+    if isinstance(conv, torch.nn.Conv2d):
+        conv._split_path = "library"
     out = conv(x)
     if b is not None:
         return _bias_relu_(out, b)
@@ -923,10 +1000,19 @@ class WindowEngine:
                 for cname in relu_convs:
                     conv = getattr(blk, cname)
                     if isinstance(conv, _Conv1x1Gemm):
-                        conv.relu = True                      # ReLU in the hipBLASLt epilogue
+                        conv.relu = True                      # ReLU in the GEMM's epilogue
                     elif isinstance(conv, torch.nn.Conv2d) and conv.bias is not None:
                         setattr(blk, "_" + cname + "_bias", conv.bias.detach().clone().contiguous())
                         conv.bias = None                      # bias + ReLU in one pass after the conv
+                        if conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) \
+                                and conv.dilation == (1, 1) and conv.groups == 1 \
+                                and _split_min_rows(conv.in_channels, conv.out_channels, 9) is not None:
+                            # K runs over (tap, channel): row (3 ky + kx) C + c of Wt[9 C, N]
+                            conv._split_planes = _split_pack(conv.weight.detach().permute(2, 3, 1, 0).reshape(
+                                9 * conv.in_channels, conv.out_channels).contiguous())
+                for m in blk.modules():
+                    if isinstance(m, _Conv1x1Gemm) and _split_min_rows(m.wt.shape[0], m.wt.shape[1], 1) is not None:
+                        m.planes = _split_pack(m.wt)          # the three bf16 planes, once per layer
                 blk.forward = types.MethodType(_bottleneck_forward if hasattr(blk, "conv3") else _basicblock_forward,
                                                blk)
         bn = net.module.bn1
@@ -937,6 +1023,18 @@ class WindowEngine:
         _gemmify_1x1(net.feature_dconv)
         _gemmify_1x1(net.output_dconv)
         self._net_f, self._cnn_f = net, cnn
+
+    def image_branch_paths(self):
+        """Which kernel every folded convolution of the ResNet trunk ran in the last image branch: name -> "split" (the
+        split-bf16 MFMA kernel) or "library" (hipBLASLt / MIOpen); layers that have not run yet are left out."""
+        if self._net_f is None:
+            return {}
+        out = {}
+        for name, m in self._net_f.named_modules():
+            path = m.path if isinstance(m, _Conv1x1Gemm) else getattr(m, "_split_path", None)
+            if path is not None:
+                out[name] = path
+        return out
 
     def _image_branch(self, image, on_feature=None):
         """``on_feature(j, map)``: called when feature map j (feature_layers[j] through its 1x1 dconv) has been issued --

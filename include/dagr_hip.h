@@ -694,6 +694,30 @@ int dagr_gemm_epilogue(const float *A, int64_t M, int32_t K, int64_t lda, const 
                        const float *R, int64_t ldr, int32_t act, float *D, int64_t ldd, void *workspace,
                        size_t workspace_bytes, void *stream);
 
+/* The same GEMM on the bf16 matrix pipe at fp32 accuracy (gemm_split_bf16.hip): every operand is split into three bf16
+ * pieces and six of the nine piece products are accumulated in fp32 (the three dropped ones are <= 2^-24 relative each).
+ * fp32 in memory on both sides, no split-K and no atomics (same operands, same bits), nothing allocated, synchronised or
+ * initialised at launch (capturable).
+ *   dagr_gemm_split_bf16_packed_bytes(K, N): size of the packed weights; 0 for a shape the kernel does not take.
+ *   dagr_gemm_split_bf16_pack: Wt[K, N] (row-major, dense) -> packed (three bf16 planes, K-tile major, N padded to the
+ *     128-column tile).  Once per layer: the kernel never reads Wt.
+ *   dagr_gemm_split_bf16: D[M, N] = act(A . W + bias[N] (+ R[M, N])), arguments as dagr_gemm_epilogue.  stride == 1: A
+ *     is M rows of K floats at pitch lda (B, H, W unused).  stride > 1: a 1x1 convolution with that spatial stride on a
+ *     channels-last map A[B, H, W, K] (pixel pitch lda), read in place; M must be B * ceil(H/stride) * ceil(W/stride).
+ *   dagr_conv3x3_split_bf16: D[B*H*W, N] = act(conv3x3(X) + bias (+ R)), stride 1, pad 1, X[B, H, W, C] channels-last with
+ *     pixel pitch ldx; packed from Wt[9 C, N] with row (3 ky + kx) C + c.
+ *   tile: 0 = chosen from the shape, 1 = 64 x 128, 2 = 32 x 128 (the same result bits whichever runs).
+ * DAGR_ERR_UNSUPPORTED: K (C for the 3x3) not a multiple of 32, N not a multiple of 16.  DAGR_ERR_INVALID_ARG: row
+ * strides not multiples of 4 floats, pointers not 16-byte aligned, D aliasing A or R, a packed buffer too small. */
+size_t dagr_gemm_split_bf16_packed_bytes(int32_t K, int32_t N);
+int dagr_gemm_split_bf16_pack(const float *Wt, int32_t K, int32_t N, void *packed, size_t packed_bytes, void *stream);
+int dagr_gemm_split_bf16(const float *A, int64_t M, int32_t K, int64_t lda, const void *packed, int32_t N,
+                         const float *bias, const float *R, int64_t ldr, int32_t act, float *D, int64_t ldd, int32_t B,
+                         int32_t H, int32_t W, int32_t stride, int32_t tile, void *stream);
+int dagr_conv3x3_split_bf16(const float *X, int32_t B, int32_t H, int32_t W, int32_t C, int64_t ldx, const void *packed,
+                            int32_t N, const float *bias, const float *R, int64_t ldr, int32_t act, float *D, int64_t ldd,
+                            int32_t tile, void *stream);
+
 /* ------------------------------------------------------------------------ *
  * FLOP accounting in the reference's scheme (src/dagr/asynchronous/flops/conv.py and the per-module logs of
  * asynchronous/conv.py, max_pool.py, linear.py, cartesian.py, batch_norm.py): the counts of the init pass (log index 0,
