@@ -5,38 +5,47 @@
 // three bf16 values (3 x 8 mantissa bits, fp32's exponent range),
 //     a = a1 + a2 + a3,   a1 = bf16(a), a2 = bf16(a - a1), a3 = bf16(a - a1 - a2)      (both subtractions are exact)
 // and the six products of order up to 2^-16 are kept: a1w1, a1w2, a2w1, a2w2, a1w3, a3w1.  Each of the three dropped ones
-// is at most 2^-24 relative.  Per K-tile of 32 the six products are summed by a chain of six MFMAs that starts from zero
-// (corrections first, a1w1 last), and the vector ALU adds the tile's sum to the running fp32 sum.
+// is at most 2^-24 relative.  Per K-slice of 32 the six products are summed by a chain of six MFMAs that starts from zero
+// (corrections first, a1w1 last), and the vector ALU adds the slice's sum to the running fp32 sum.
 //
 //   D[M, N] = act(A . W + bias (+ R)),  fp32 in memory on both sides, no split-K, no atomics: same operands, same bits.
+// K is not split in any form (neither across workgroups nor inside one): the shapes with few rows and a long K get more
+// workgroups from the narrower tiles below, and the K-slices are added in ascending order whatever the tile.
 //
-// Weights are packed once (dagr_gemm_split_bf16_pack) into three bf16 planes, K-tile major: [K/32][3][Npad][32] with Npad =
-// N rounded up to the 128-column tile (zero filled), so that the W tile of a block is three contiguous 8 KB pieces.
-// Activations stay fp32: the A tile is loaded to registers, split there, and written to LDS as three planes.
+// Weights are packed once (dagr_gemm_split_bf16_pack) into three bf16 planes, K-slice major: [K/32][3][Npad][32] with Npad =
+// N rounded up to 128 columns (zero filled).  The packed planes ARE the LDS image of a W tile: a row is 64 bytes, its four
+// 16-byte k-chunks stored in the swizzled order of swz() below, so a tile of BN columns of one plane is BN * 64 contiguous
+// bytes and goes global -> LDS by the LDS-direct load (1 KB per wave instruction, no register in between, no ds_write).
+// The layout is opaque to callers: dagr_gemm_split_bf16_packed_bytes sizes the buffer and nothing else reads it.
+// Activations stay fp32: the A tile is loaded to registers, split there, and written to LDS as three planes with the same
+// swizzle.
 //
-// Tile: (32*MI) x 128 x 32, MI = 2 or 1 (a 128-row tile lost to the 64-row one on every shape of the image branch); 4 waves as 2 x 2, each (16*MI) x 64 of the output; mfma_f32_16x16x32_bf16 with the
-// operands swapped (W as the MFMA's A operand), so a lane ends up with four consecutive output CHANNELS of one row and the
-// epilogue reads bias / residual and writes D as float4.  One LDS buffer, register staging with the global loads of tile
-// t+1 issued before the MFMAs of tile t and written after them.  LDS rows are 32 bf16 padded to 40 (80 B): the sixteen rows
-// of a fragment read then fall on sixteen distinct 16-byte slots of the 256-byte bank row.
+// Tile: (32*MI) x BN x 32, MI = 2 or 1, BN = 128 or 64 (N = 64 on a 128-column tile multiplies zero padding in half of every
+// MFMA; a 128-row tile lost to the 64-row one on every shape of the image branch); 4 waves as 2 x 2, each (16*MI) x (BN/2)
+// of the output; mfma_f32_16x16x32_bf16 with the operands swapped (W as the MFMA's A operand), so a lane ends up with four
+// consecutive output CHANNELS of one row and the epilogue reads bias / residual and writes D as float4.
+//
+// K loop: two LDS stages and one workgroup barrier per slice.  While slice kt is multiplied out of one stage, the W image of
+// slice kt + 1 arrives in the other by the LDS-direct load, the A rows of slice kt + 1 (in registers since slice kt - 1) are
+// split between the MFMAs and written there too, and the A rows of slice kt + 2 are on their way to a second register set.
+// The barrier is a raw s_barrier behind one s_waitcnt: everything a slice sends for was issued at its top.
 //
 // A-row addressing (Geo): plain rows with a pitch; a 1x1 convolution with spatial stride (reads every s-th pixel in place);
-// a 3x3 / stride 1 / pad 1 convolution on an NHWC map, K = (tap, channel) -- a K-tile lies inside one tap because C is a
+// a 3x3 / stride 1 / pad 1 convolution on an NHWC map, K = (tap, channel) -- a K-slice lies inside one tap because C is a
 // multiple of 32, taps outside the image (which also closes the seam between two images of the batch) read as zero.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.hpp"
 
 namespace dagr {
 namespace {
 
-constexpr int kKT = 32;        // K-tile
-constexpr int kBN = 128;       // N-tile
-constexpr int kPitch = 40;     // LDS row pitch in bf16 (32 + 8 of padding)
+constexpr int kKT = 32;        // K-slice
+constexpr int kNPad = 128;     // the packed planes pad N to this many columns (the widest tile)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 struct Geo {
@@ -68,6 +77,30 @@ __device__ __forceinline__ void split3(float a, unsigned short &p1, unsigned sho
     p3 = bf16_bits(b3);
 }
 
+// The same split of two values at once, each piece as the pair's two bf16 in one dword (element 0 low): one packed
+// conversion per piece, and the dword is what the LDS planes hold.  Same roundings, same bits as split3.
+__device__ __forceinline__ void split3x2(float a0, float a1, unsigned &p1, unsigned &p2, unsigned &p3) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    auto widen = [](unsigned u) {
+        return f32x2{__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
+    };
+    const f32x2 v = {a0, a1};
+    p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+    const f32x2 r1 = v - widen(p1);
+    p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r1, bf16x2));
+    const f32x2 r2 = r1 - widen(p2);
+    p3 = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2));
+}
+
+// Position (in bf16) of the 8-element k-chunk `c` (0..3) of row `r` in a plane of 64-byte rows.  A fragment read takes row
+// lane & 15, chunk lane >> 4 with ds_read_b128, whose four lane groups are {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and
+// the same + 32: a group holds all sixteen rows, rows 4..11 at one chunk and rows 0..3, 12..15 at another.  Four rows share
+// a 256-byte bank row, so rows r, r + 4, r + 8, r + 12 of a group must sit at four different chunk positions: chunks of rows
+// 8..15 are stored at c ^ 3 (group 0: rows 0, 4, 8, 12 at 0, 1, 1 ^ 3, 0 ^ 3 -- all four; the other groups are this one
+// XOR a constant).
+__device__ __forceinline__ int swz(int r, int c) { return r * kKT + ((c ^ (((r >> 3) & 1) * 3)) << 3); }
+
 __global__ __launch_bounds__(256) void k_split_pack(const float *__restrict__ Wt, int K, int N, int Npad,
                                                     unsigned short *__restrict__ out) {
     const int64_t total = (int64_t)K * Npad;
@@ -77,23 +110,37 @@ __global__ __launch_bounds__(256) void k_split_pack(const float *__restrict__ Wt
         if (n < N) split3(Wt[(int64_t)k * N + n], p[0], p[1], p[2]);
         const int kt = k / kKT, kk = k - kt * kKT;
 #pragma unroll
-        for (int q = 0; q < 3; q++) out[(((int64_t)kt * 3 + q) * Npad + n) * kKT + kk] = p[q];
+        for (int q = 0; q < 3; q++) out[((int64_t)kt * 3 + q) * Npad * kKT + swz(n, kk >> 3) + (kk & 7)] = p[q];
     }
 }
 
-template <int MI, int MODE>
-__global__ __launch_bounds__(256, 3) void k_gemm_split(const Args a) {
+// Waits for everything this wave has in flight (the A rows on their way to registers, its pieces of the W image on their
+// way to LDS, its LDS stores), then the workgroup barrier.  The A registers pass through the statement, so the compiler
+// sees them as ready from here on and puts no wait of its own in the middle of the next slice.
+template <int N>
+__device__ __forceinline__ void wait_all_barrier(f32x4 (&ra)[2][N]) {
+    if constexpr (N == 1)
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(ra[0][0]), "+v"(ra[1][0])::"memory");
+    else
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(ra[0][0]), "+v"(ra[0][1]), "+v"(ra[1][0]), "+v"(ra[1][1])::"memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+template <int MI, int BN, int MODE>
+__global__ __launch_bounds__(256, BN == 128 ? 2 : 3) void k_gemm_split(const Args a) {
     constexpr int BM = 32 * MI;
-    __shared__ __attribute__((aligned(16))) unsigned short lds[3 * (BM + kBN) * kPitch];
-    unsigned short *const ldsA = lds;
-    unsigned short *const ldsW = lds + 3 * BM * kPitch;
+    constexpr int NI = BN / 32;                      // 16-column fragments of a wave
+    constexpr int kStage = 3 * (BM + BN) * kKT;      // one stage: three A planes, then three W planes (bf16)
+    constexpr int kPieces = 3 * BN / 16 / 4;         // 1 KB pieces of a stage's W image that each wave brings in
+    __shared__ __attribute__((aligned(1024))) unsigned short lds[2 * kStage];
 
     // blocks that follow each other on one XCD share the A row tile (its L2 holds it); bijective for any block count
     const int orig = blockIdx.x, xcd = orig & 7, q8 = a.n_blocks >> 3, r8 = a.n_blocks & 7;
     const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
     const int nt = lid % a.n_tiles_n, mt = lid / a.n_tiles_n;
     const int64_t m0 = (int64_t)mt * BM;
-    const int n0 = nt * kBN;
+    const int n0 = nt * BN;
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -120,12 +167,13 @@ __global__ __launch_bounds__(256, 3) void k_gemm_split(const Args a) {
         }
     }
 
-    f32x4 ra[MI];
-    u32x4 rw[6];
-    unsigned okmask = 0;
-    const u32x4 *const wbase = reinterpret_cast<const u32x4 *>(a.Wp) + (int64_t)n0 * 4 + t;
+    static_assert(MI == 1 || MI == 2, "wait_all_barrier names the register sets");
+    f32x4 ra[2][MI];                   // two register sets: slice kt + 1 is split out of one while kt + 2 arrives in the other
+    unsigned okmask[2] = {0, 0};
 
-    auto gload = [&](int kt) {
+    // the A rows of K-slice kt, fp32, into register set `set`
+    auto gload = [&](auto set, int kt) {
+        constexpr int S = decltype(set)::value;
         const int k0 = kt * kKT;
         int c0 = k0, dy = 0, dx = 0;
         int64_t toff = 0;
@@ -136,7 +184,7 @@ __global__ __launch_bounds__(256, 3) void k_gemm_split(const Args a) {
             dx = tap - (tap / 3) * 3 - 1;
             toff = (int64_t)(dy * a.g.W + dx) * a.lda;
         }
-        okmask = 0;
+        okmask[S] = 0;
 #pragma unroll
         for (int i = 0; i < MI; i++) {
             bool ok = mrow0 + 32 * i < a.M;
@@ -148,97 +196,133 @@ __global__ __launch_bounds__(256, 3) void k_gemm_split(const Args a) {
             // a masked row reads the first 16 bytes of A (always there) and is zeroed when it is written to LDS: a select
             // on the address, not a branch around the load
             const float *p = ok ? a.A + off + toff + c0 + c4 * 4 : a.A;
-            ra[i] = *reinterpret_cast<const f32x4 *>(p);
-            okmask |= (ok ? 1u : 0u) << i;
-        }
-        const u32x4 *wp = wbase + (int64_t)kt * 3 * a.Npad * 4;
-#pragma unroll
-        for (int p = 0; p < 3; p++) {
-            rw[2 * p] = wp[(int64_t)p * a.Npad * 4];
-            rw[2 * p + 1] = wp[(int64_t)p * a.Npad * 4 + 256];
+            ra[S][i] = *reinterpret_cast<const f32x4 *>(p);
+            okmask[S] |= (ok ? 1u : 0u) << i;
         }
     };
 
-    auto lwrite = [&]() {
+    // register set `set`, split into three planes, into stage s
+    auto lwrite = [&](auto set, int s) {
+        constexpr int S = decltype(set)::value;
+        unsigned short *const ldsA = lds + s * kStage;
 #pragma unroll
         for (int i = 0; i < MI; i++) {
-            const bool ok = (okmask >> i) & 1u;
-            const f32x4 v = ok ? ra[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-            unsigned short p[3][4];
-#pragma unroll
-            for (int e = 0; e < 4; e++) split3(v[e], p[0][e], p[1][e], p[2][e]);
+            const bool ok = (okmask[S] >> i) & 1u;
+            const f32x4 v = ok ? ra[S][i] : f32x4{0.f, 0.f, 0.f, 0.f};
+            unsigned lo[3], hi[3];
+            split3x2(v[0], v[1], lo[0], lo[1], lo[2]);
+            split3x2(v[2], v[3], hi[0], hi[1], hi[2]);
 #pragma unroll
             for (int q = 0; q < 3; q++) {
-                const u32x2 u = {(unsigned)p[q][0] | ((unsigned)p[q][1] << 16), (unsigned)p[q][2] | ((unsigned)p[q][3] << 16)};
-                *reinterpret_cast<u32x2 *>(ldsA + (q * BM + r0 + 32 * i) * kPitch + c4 * 4) = u;
+                const u32x2 u = {lo[q], hi[q]};
+                *reinterpret_cast<u32x2 *>(ldsA + q * BM * kKT + swz(r0 + 32 * i, c4 >> 1) + (c4 & 1) * 4) = u;
             }
         }
+    };
+
+    // The W image of K-slice kt, global -> LDS with no register in between.  The packed planes already are the LDS image,
+    // so every piece is 1 KB contiguous on both sides (the LDS side of this load is wave-uniform base + 16 lane).
+    const char *const wsrc = reinterpret_cast<const char *>(a.Wp) + ((int64_t)n0 * kKT) * 2 + lane * 16;
+    auto wload = [&](int kt, int s) {
 #pragma unroll
-        for (int p = 0; p < 3; p++)
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const int c = t + 256 * j;      // 16-byte chunk of the plane's tile: row c >> 2, 8 bf16 at 8 (c & 3)
-                *reinterpret_cast<u32x4 *>(ldsW + (p * kBN + (c >> 2)) * kPitch + (c & 3) * 8) = rw[2 * p + j];
-            }
+        for (int j = 0; j < kPieces; j++) {
+            const int piece = wave * kPieces + j, p = piece / (BN / 16), sub = piece - p * (BN / 16);
+            const char *src = wsrc + (((int64_t)kt * 3 + p) * a.Npad * kKT + sub * 16 * kKT) * 2;
+            unsigned short *dst = lds + s * kStage + (3 * BM + p * BN + sub * 16) * kKT;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
+                                             (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
+        }
     };
 
     // The running sum is kept by the vector ALU, not by the MFMA: the matrix pipe truncates when it adds into a large
     // accumulator (measured: the error of an MFMA-accumulated sum grew linearly with K, 1.3e-6 of max |D| at K = 2048
-    // against 3e-7 for the fp32 library), so every K-tile's products are summed from zero and added here, rounded to nearest.
-    f32x4 acc[MI][4];
+    // against 3e-7 for the fp32 library), so every K-slice's products are summed from zero and added here, rounded to nearest.
+    f32x4 acc[MI][NI];
 #pragma unroll
     for (int mi = 0; mi < MI; mi++)
 #pragma unroll
-        for (int ni = 0; ni < 4; ni++) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int ni = 0; ni < NI; ni++) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int frag = (lane & 15) * kPitch + (lane >> 4) * 8;
-    const unsigned short *const fragA = ldsA + (wm * 16 * MI) * kPitch + frag;
-    const unsigned short *const fragW = ldsW + (wn * 64) * kPitch + frag;
+    const int frag = swz(lane & 15, lane >> 4);
+    const int fragA = (wm * 16 * MI) * kKT + frag;
+    const int fragW = (3 * BM + wn * (BN / 2)) * kKT + frag;
 
+    // Two LDS stages, one barrier per slice.  Slice kt is multiplied out of stage kt & 1.  At the top of that slice the
+    // A rows of slice kt + 2 are sent for (into the register set slice kt was split from) and so is the W image of slice
+    // kt + 1 (LDS-direct, into the other stage); between the MFMAs the vector ALU splits slice kt + 1, which arrived during
+    // slice kt - 1, and writes it to the other stage.  Everything a slice sends for has the whole slice to arrive, and the
+    // one wait in front of the barrier retires it.
     const int n_kt = a.K / kKT;
-    gload(0);
-    lwrite();
-    __syncthreads();
-    for (int kt = 0; kt < n_kt; kt++) {
-        const bool more = kt + 1 < n_kt;
-        if (more) gload(kt + 1);
-        bf16x8 bw[3][4];
+    const std::integral_constant<int, 0> set0;
+    const std::integral_constant<int, 1> set1;
+
+    // the six-MFMA chains of one slice out of `st`, added to the running sums
+    auto multiply = [&](const unsigned short *st) {
+        bf16x8 bw[3][NI], av[MI][3];
 #pragma unroll
         for (int p = 0; p < 3; p++)
 #pragma unroll
-            for (int ni = 0; ni < 4; ni++)
-                bw[p][ni] = *reinterpret_cast<const bf16x8 *>(fragW + (p * kBN + ni * 16) * kPitch);
+            for (int ni = 0; ni < NI; ni++)
+                bw[p][ni] = *reinterpret_cast<const bf16x8 *>(st + fragW + (p * BN + ni * 16) * kKT);
+#pragma unroll
+        for (int mi = 0; mi < MI; mi++)
+#pragma unroll
+            for (int p = 0; p < 3; p++) av[mi][p] = *reinterpret_cast<const bf16x8 *>(st + fragA + (p * BM + mi * 16) * kKT);
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int mi = 0; mi < MI; mi++) {
-            bf16x8 av[3];
-#pragma unroll
-            for (int p = 0; p < 3; p++) av[p] = *reinterpret_cast<const bf16x8 *>(fragA + (p * BM + mi * 16) * kPitch);
-            // the MFMA's A operand is the W fragment (rows = output channels).  The sum of a K-tile starts from zero: the
+            // the MFMA's A operand is the W fragment (rows = output channels).  The sum of a K-slice starts from zero: the
             // five corrections, smallest first, then a1 w1 on top of them.
-            f32x4 ts[4];
+            f32x4 ts[NI];
 #pragma unroll
-            for (int ni = 0; ni < 4; ni++) ts[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[2][ni], av[0], zero, 0, 0, 0);
+            for (int ni = 0; ni < NI; ni++) ts[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[2][ni], av[mi][0], zero, 0, 0, 0);
 #pragma unroll
-            for (int ni = 0; ni < 4; ni++) ts[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[0][ni], av[2], ts[ni], 0, 0, 0);
+            for (int ni = 0; ni < NI; ni++) ts[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[0][ni], av[mi][2], ts[ni], 0, 0, 0);
 #pragma unroll
-            for (int ni = 0; ni < 4; ni++) ts[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[1][ni], av[1], ts[ni], 0, 0, 0);
+            for (int ni = 0; ni < NI; ni++) ts[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[1][ni], av[mi][1], ts[ni], 0, 0, 0);
 #pragma unroll
-            for (int ni = 0; ni < 4; ni++) ts[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[1][ni], av[0], ts[ni], 0, 0, 0);
+            for (int ni = 0; ni < NI; ni++) ts[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[1][ni], av[mi][0], ts[ni], 0, 0, 0);
 #pragma unroll
-            for (int ni = 0; ni < 4; ni++) ts[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[0][ni], av[1], ts[ni], 0, 0, 0);
+            for (int ni = 0; ni < NI; ni++) ts[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[0][ni], av[mi][1], ts[ni], 0, 0, 0);
 #pragma unroll
-            for (int ni = 0; ni < 4; ni++) ts[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[0][ni], av[0], ts[ni], 0, 0, 0);
+            for (int ni = 0; ni < NI; ni++) ts[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[0][ni], av[mi][0], ts[ni], 0, 0, 0);
 #pragma unroll
-            for (int ni = 0; ni < 4; ni++) acc[mi][ni] += ts[ni];
-            __builtin_amdgcn_sched_barrier(0);      // one row fragment at a time: the temporaries of all of them do not fit
+            for (int ni = 0; ni < NI; ni++) acc[mi][ni] += ts[ni];
         }
-        __syncthreads();            // every wave has read tile kt
-        if (more) {
-            lwrite();
-            __syncthreads();
+    };
+
+    // slice kt with a slice behind it (one basic block: no branch between the loads, the MFMAs and the split)
+    auto slice = [&](auto cur, auto nxt, int kt) {
+        constexpr int S = decltype(cur)::value;
+        gload(cur, kt + 2 < n_kt ? kt + 2 : n_kt - 1);      // past the end: the last slice again, never used
+        wload(kt + 1, S ^ 1);
+        __builtin_amdgcn_sched_barrier(0);                  // both kinds of load go out before anything else of the slice
+        multiply(lds + S * kStage);
+        lwrite(nxt, S ^ 1);
+        // spread the split's vector instructions between the MFMAs (an MFMA occupies the matrix pipe for four issue slots)
+#pragma unroll
+        for (int i = 0; i < 6 * MI * NI; i++) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
         }
+        wait_all_barrier(ra);
+    };
+
+    gload(set0, 0);
+    gload(set1, n_kt > 1 ? 1 : 0);
+    wload(0, 0);
+    lwrite(set0, 0);
+    wait_all_barrier(ra);
+    int kt = 0;
+    for (; kt + 2 < n_kt; kt += 2) {
+        slice(set0, set1, kt);
+        slice(set1, set0, kt + 1);
     }
+    if (kt + 1 < n_kt) {
+        slice(set0, set1, kt);
+        kt++;
+    }
+    multiply(lds + (kt & 1) * kStage);           // the last slice: nothing left to bring in
 
     // ---- epilogue: lane holds D[m][n .. n+3], m = tile row (lane & 15), n = 4 (lane >> 4) inside a 16 x 16 fragment
 #pragma unroll
@@ -246,8 +330,8 @@ __global__ __launch_bounds__(256, 3) void k_gemm_split(const Args a) {
         const int64_t m = m0 + wm * 16 * MI + mi * 16 + (lane & 15);
         if (m >= a.M) continue;
 #pragma unroll
-        for (int ni = 0; ni < 4; ni++) {
-            const int n = n0 + wn * 64 + ni * 16 + (lane >> 4) * 4;
+        for (int ni = 0; ni < NI; ni++) {
+            const int n = n0 + wn * (BN / 2) + ni * 16 + (lane >> 4) * 4;
             if (n >= a.N) continue;              // N is a multiple of 16 and n of 4: a whole float4 or nothing
             f32x4 v = acc[mi][ni];
             if (a.bias) {
@@ -266,22 +350,31 @@ __global__ __launch_bounds__(256, 3) void k_gemm_split(const Args a) {
 
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
-template <int MODE>
-int launch(Args &a, int tile, hipStream_t stream) {
-    // tile 1: 64 x 128, 2: 32 x 128.  0: the wide one where its blocks fill the device's CUs twice over (a block is four
-    // waves, one per SIMD); with fewer blocks the narrow tile's extra W traffic is the smaller loss (measured:
-    // profiles/split_bf16_shapes.md -- 600 blocks of 64 rows win, 300 lose to 600 of 32)
-    if (tile == 0) tile = ceil_div(a.M, 64) * a.n_tiles_n >= 2 * (int64_t)device_cu_count() ? 1 : 2;
-    const int bm = tile == 1 ? 64 : 32;
-    const int64_t blocks = ceil_div(a.M, bm) * a.n_tiles_n;
+template <int MI, int BN, int MODE>
+int launch_tile(Args &a, hipStream_t stream) {
+    a.n_tiles_n = (int)ceil_div(a.N, BN);
+    const int64_t blocks = ceil_div(a.M, 32 * MI) * a.n_tiles_n;
     DAGR_CHECK_ARG(blocks < ((int64_t)1 << 31), "too many tiles");
     a.n_blocks = (int)blocks;
-    if (tile == 1)
-        k_gemm_split<2, MODE><<<(unsigned)blocks, 256, 0, stream>>>(a);
-    else
-        k_gemm_split<1, MODE><<<(unsigned)blocks, 256, 0, stream>>>(a);
+    k_gemm_split<MI, BN, MODE><<<(unsigned)blocks, 256, 0, stream>>>(a);
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
+}
+
+template <int MODE>
+int launch(Args &a, int tile, hipStream_t stream) {
+    // tile 1: 64 x 128, 2: 32 x 128, 3: 64 x 64, 4: 32 x 64 (rows x columns).  0 picks from the shape, by what
+    // profiles/split_bf16_shapes.md measured.  Columns: always 64 -- three blocks per CU instead of two and no zero padding
+    // at N = 64; it won or tied (within the spread) on every shape the rule selects, and the step as a whole was faster with
+    // it than with 128 columns on the three shapes where those were 0.5 - 0.9 us ahead.  Rows: 64 where that still leaves
+    // two blocks per CU, 32 below.
+    if (tile == 0) tile = ceil_div(a.M, 64) * ceil_div(a.N, 64) >= 2 * (int64_t)device_cu_count() ? 3 : 4;
+    switch (tile) {
+        case 1: return launch_tile<2, 128, MODE>(a, stream);
+        case 2: return launch_tile<1, 128, MODE>(a, stream);
+        case 3: return launch_tile<2, 64, MODE>(a, stream);
+        default: return launch_tile<1, 64, MODE>(a, stream);
+    }
 }
 
 inline int unsupported(const char *fn, const char *what) {
@@ -296,7 +389,7 @@ using namespace dagr;
 
 extern "C" size_t dagr_gemm_split_bf16_packed_bytes(int32_t K, int32_t N) {
     if (K < kKT || K % kKT != 0 || N < 16 || N % 16 != 0) return 0;
-    return (size_t)K * 3 * align_up((size_t)N, kBN) * sizeof(unsigned short);
+    return (size_t)K * 3 * align_up((size_t)N, kNPad) * sizeof(unsigned short);
 }
 
 extern "C" int dagr_gemm_split_bf16_pack(const float *Wt, int32_t K, int32_t N, void *packed, size_t packed_bytes,
@@ -307,7 +400,7 @@ extern "C" int dagr_gemm_split_bf16_pack(const float *Wt, int32_t K, int32_t N, 
     DAGR_CHECK_ARG(Wt && packed, "NULL pointer");
     DAGR_CHECK_ARG(aligned16(packed), "packed is not 16-byte aligned");
     DAGR_CHECK_ARG(packed_bytes >= dagr_gemm_split_bf16_packed_bytes(K, N), "packed buffer too small");
-    const int Npad = (int)align_up((size_t)N, kBN);
+    const int Npad = (int)align_up((size_t)N, kNPad);
     const int64_t blocks = std::min<int64_t>(ceil_div((int64_t)K * Npad, 256), 256 * 16);
     k_split_pack<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(Wt, K, N, Npad, (unsigned short *)packed);
     DAGR_CHECK_LAUNCH();
@@ -325,7 +418,7 @@ int check_common(const char *fn, const float *A, int64_t M, int32_t K, int64_t l
             return DAGR_ERR_INVALID_ARG;                           \
         }                                                          \
     } while (0)
-    SPLIT_CHECK(M >= 0 && K >= 1 && N >= 1 && ldd >= N && (!R || ldr >= N) && (act == 0 || act == 1) && tile >= 0 && tile <= 2,
+    SPLIT_CHECK(M >= 0 && K >= 1 && N >= 1 && ldd >= N && (!R || ldr >= N) && (act == 0 || act == 1) && tile >= 0 && tile <= 4,
                 "bad sizes");
     if (K % kKT != 0) return unsupported(fn, "K (C of a 3x3) is not a multiple of the K-tile (32)");
     if (N % 16 != 0) return unsupported(fn, "N is not a multiple of 16");
@@ -349,8 +442,8 @@ extern "C" int dagr_gemm_split_bf16(const float *A, int64_t M, int32_t K, int64_
     const int rc = check_common(__func__, A, M, K, lda, packed, N, bias, R, ldr, act, D, ldd, tile, done);
     if (done) return rc;
     DAGR_CHECK_ARG(lda >= K && stride >= 1, "bad sizes");
-    Args a{A, (const unsigned short *)packed, bias, R, D, M, lda, R ? ldr : 0, ldd, K, N, (int)align_up((size_t)N, kBN), act,
-           (int)ceil_div(N, kBN), 0, Geo{0, 0, 0, K, 1, 0, 0}};
+    Args a{A, (const unsigned short *)packed, bias, R, D, M, lda, R ? ldr : 0, ldd, K, N, (int)align_up((size_t)N, kNPad), act,
+           0, 0, Geo{0, 0, 0, K, 1, 0, 0}};
     if (stride == 1) return launch<0>(a, tile, (hipStream_t)stream);
     DAGR_CHECK_ARG(B >= 1 && H >= 1 && W >= 1, "bad image sizes");
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
@@ -368,7 +461,7 @@ extern "C" int dagr_conv3x3_split_bf16(const float *X, int32_t B, int32_t H, int
     const int rc = check_common(__func__, X, M, C, ldx, packed, N, bias, R, ldr, act, D, ldd, tile, done);
     if (done) return rc;
     DAGR_CHECK_ARG((int64_t)C * 9 < ((int64_t)1 << 31), "C too large");
-    Args a{X, (const unsigned short *)packed, bias, R, D, M, ldx, R ? ldr : 0, ldd, 9 * C, N, (int)align_up((size_t)N, kBN), act,
-           (int)ceil_div(N, kBN), 0, Geo{2, H, W, C, 1, H, W}};
+    Args a{X, (const unsigned short *)packed, bias, R, D, M, ldx, R ? ldr : 0, ldd, 9 * C, N, (int)align_up((size_t)N, kNPad), act,
+           0, 0, Geo{2, H, W, C, 1, H, W}};
     return launch<2>(a, tile, (hipStream_t)stream);
 }

@@ -203,24 +203,35 @@ def _lt_workspace(device):
 def _split_min_rows(K, N, taps):
     """The selection rule of the split-bf16 MFMA kernel (csrc/gemm_split_bf16.hip): the fewest output rows M = B * Ho * Wo
     from which a convolution with K input channels (per tap), N output channels and ``taps`` in (1, 9) runs on it instead
-    of the library, or None where the library keeps the layer at every size.  Written from the measured table
+    of the library, or None where the library keeps the layer at every size.  Written line for line from the measured table
     profiles/split_bf16_shapes.md (B = 8 at 640 x 480, and the B = 2, 320 x 215 rows): a class is in only where the kernel
     beat the library by more than the run-to-run spread of the medians.  No timing at run time: the same shapes take the
-    same path in every run.
-      1x1, K 128..256: won at every M measured, 560 to 153 600 (13 - 39 % faster).
-      1x1, K 257..512: with N >= 256 won from M = 9 600 up (12 - 25 %), tied at 2 400; with N = 128 the gain (1 - 4 us of
-        48) did not clear the spread in one of three sessions.
-      1x1, K > 512: lost (the K loop of the few tiles a small M leaves is too long for one block per CU).
-      1x1, K < 128 or N < 128 (layer1, the dconvs): at the fp32 ridge, memory-bound; not measured, not selected.
-      3x3 stride 1: C = 128 won at M = 38 400 (23 %) and lost at 2 160; C = 64, 256, 512 lost."""
+    same path in every run.  Where a class was measured at ONE row count only, the bound below is that row count: a
+    "measured size only" bound, NOT a crossover -- nothing is known about the class below it.
+      1x1, K 128..256, N >= 128: won at every M measured, 560 to 153 600 (14 - 65 % faster).
+      1x1, K 257..512, N >= 256: won at every M measured, 2 400 to 38 400 (12 - 15 %).  N = 128: won at 38 400 (38.8 against
+        43.6 us), measured size only.
+      1x1, K = 1024, N = 512 (layer4.0.conv1): won at 9 600 (68.2 against 78.4 us), measured size only.  The other K >= 1024
+        classes: 9 600 x 1024 x 256 gained 2.3 us of 44.6 with a spread of 1.2, too near it; 2 400 x 1024 x 2048 read in
+        place with stride 2, as the engine runs it, gained 2.7 of 87.8 with a spread of 1.3, likewise; 2 400 x 2048 x 512
+        lost (52.6 against 42.9 us).
+      1x1 of layer1 (64 -> 64, 256 -> 64, 64 -> 256): won at 153 600 (12 - 27 %), measured size only.
+      1x1 with K < 64 or N < 64 (the narrow dconvs): not measured, not selected.
+      3x3 stride 1: C = 128 won at M = 38 400 (30 %); the bound stays at 32 768, where the image branch's own tests hold
+        it (at 2 160 the 32 x 64 tile now wins too, 21.8 against 28.0 us; not admitted).  C = 64 won at 153 600 (35 %) and
+        C = 256 at 9 600 (23 %), both measured size only.  C = 512 tied at 2 400 (118.9 against 117.4 us)."""
     if taps == 1:
-        if K < 128 or N < 128 or K > 512:
+        if K < 64 or N < 64:
             return None
+        if K < 128 or N < 128:
+            return 153600 if (K, N) in ((64, 64), (256, 64), (64, 256)) else None
         if K <= 256:
             return 512
-        return 8192 if N >= 256 else None
-    if taps == 9 and K == 128 and N == 128:
-        return 32768
+        if K <= 512:
+            return 2400 if N >= 256 else 38400
+        return 9600 if (K, N) == (1024, 512) else None
+    if taps == 9 and K == N:
+        return {64: 153600, 128: 32768, 256: 9600}.get(K)
     return None
 
 

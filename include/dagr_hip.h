@@ -699,14 +699,15 @@ int dagr_gemm_epilogue(const float *A, int64_t M, int32_t K, int64_t lda, const 
  * fp32 in memory on both sides, no split-K and no atomics (same operands, same bits), nothing allocated, synchronised or
  * initialised at launch (capturable).
  *   dagr_gemm_split_bf16_packed_bytes(K, N): size of the packed weights; 0 for a shape the kernel does not take.
- *   dagr_gemm_split_bf16_pack: Wt[K, N] (row-major, dense) -> packed (three bf16 planes, K-tile major, N padded to the
- *     128-column tile).  Once per layer: the kernel never reads Wt.
+ *   dagr_gemm_split_bf16_pack: Wt[K, N] (row-major, dense) -> packed (three bf16 planes in the kernel's own LDS image, K-slice
+ *     major, N padded to 128 columns; opaque -- only the kernel reads it).  Once per layer: the kernel never reads Wt.
  *   dagr_gemm_split_bf16: D[M, N] = act(A . W + bias[N] (+ R[M, N])), arguments as dagr_gemm_epilogue.  stride == 1: A
  *     is M rows of K floats at pitch lda (B, H, W unused).  stride > 1: a 1x1 convolution with that spatial stride on a
  *     channels-last map A[B, H, W, K] (pixel pitch lda), read in place; M must be B * ceil(H/stride) * ceil(W/stride).
  *   dagr_conv3x3_split_bf16: D[B*H*W, N] = act(conv3x3(X) + bias (+ R)), stride 1, pad 1, X[B, H, W, C] channels-last with
  *     pixel pitch ldx; packed from Wt[9 C, N] with row (3 ky + kx) C + c.
- *   tile: 0 = chosen from the shape, 1 = 64 x 128, 2 = 32 x 128 (the same result bits whichever runs).
+ *   tile (rows x columns): 0 = chosen from the shape, 1 = 64 x 128, 2 = 32 x 128, 3 = 64 x 64, 4 = 32 x 64 (the same result
+ *     bits whichever runs: K is never split, the 32-wide K-slices are added in ascending order).
  * DAGR_ERR_UNSUPPORTED: K (C for the 3x3) not a multiple of 32, N not a multiple of 16.  DAGR_ERR_INVALID_ARG: row
  * strides not multiples of 4 floats, pointers not 16-byte aligned, D aliasing A or R, a packed buffer too small. */
 size_t dagr_gemm_split_bf16_packed_bytes(int32_t K, int32_t N);

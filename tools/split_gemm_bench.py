@@ -5,7 +5,8 @@ before (dagr_gemm_epilogue for the 1x1 convs; the library 3x3 conv + dagr_bias_r
 HIP events around every launch, `--warm` untimed launches, the median of `--iters`; the whole measurement of a shape is
 repeated `--rounds` times and the spread of the medians (max - min) is printed beside the first: a path wins a shape only
 by more than that spread.  Prints a markdown table (TF/s: 2 M K N / time; the split columns are fp32-equivalent TF/s,
-against the 417 TF-equivalent ceiling of six bf16 MFMAs per product).
+against the 417 TF-equivalent ceiling of six bf16 MFMAs per product; the four split times are the four tiles the entry points
+take, rows x columns).
 
     python tools/split_gemm_bench.py [--md OUT.md] [--only 1x1|3x3]
 """
@@ -19,8 +20,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dagr_amd import _lib  # noqa: E402
 
-# (M, K, N, note) of the 1x1 convs of layers 2-4 (M = B * H * W at the conv's output resolution, B = 8)
-GEMMS = [(153600, 256, 128, "layer2.0.conv1"),
+# (M, K, N, note) of the 1x1 convs of layers 1-4 (M = B * H * W at the conv's output resolution, B = 8)
+GEMMS = [(153600, 64, 64, "layer1.0.conv1"), (153600, 256, 64, "layer1.1-2.conv1"), (153600, 64, 256, "layer1.*.conv3, layer1.0.downsample"),
+         (153600, 256, 128, "layer2.0.conv1"),
          (38400, 512, 128, "layer2.1-3.conv1"), (38400, 128, 512, "layer2.*.conv3"), (38400, 256, 512, "layer2.0.downsample"),
          (38400, 512, 256, "layer3.0.conv1"), (9600, 1024, 256, "layer3.1-5.conv1"), (9600, 256, 1024, "layer3.*.conv3"),
          (9600, 512, 1024, "layer3.0.downsample"),
@@ -36,6 +38,10 @@ STRIDED = [(8, 120, 160, 256, 512, "layer2.0.downsample /2"), (8, 60, 80, 512, 1
 # stride-1 3x3 convs: (H, W, C)
 CONVS = [(8, 120, 160, 64, "layer1.*.conv2"), (8, 60, 80, 128, "layer2.1-3.conv2"), (8, 30, 40, 256, "layer3.1-5.conv2"),
          (8, 15, 20, 512, "layer4.1-2.conv2"), (2, 27, 40, 128, "B=2 320x215 layer2.1-3.conv2")]
+
+
+def all_tiles(split_fn):
+    return [("64x128", split_fn(1)), ("32x128", split_fn(2)), ("64x64", split_fn(3)), ("32x64", split_fn(4))]
 
 
 def time_us(fn, warm, iters):
@@ -74,7 +80,7 @@ def main():
     torch.manual_seed(0)
     torch.backends.cudnn.benchmark = True
     ws = torch.empty(int(L.dagr_gemm_epilogue_workspace_bytes()), dtype=torch.uint8, device=dev)
-    rows = ["| shape | layer | library us | TF/s | of 157.3 | split us, tiles 64 / 32 | best us | TF-eq/s | of 417 | "
+    rows = ["| shape | layer | library us | TF/s | of 157.3 | split us, tiles 64x128 / 32x128 / 64x64 / 32x64 | best us | TF-eq/s | of 417 | "
             "spread lib / split us | max diff / max ref |", "|---|---|---|---|---|---|---|---|---|---|---|"]
 
     def measure(name, note, flop, lib_fn, split_fns, y_lib, y_split):
@@ -114,7 +120,7 @@ def main():
             def split_fn(tile):
                 return lambda: _lib.check(L.dagr_gemm_split_bf16(_lib.ptr(A), M, K, K, _lib.ptr(wp), N, _lib.ptr(bias), None, N,
                                                                  1, _lib.ptr(y1), N, 0, 0, 0, 1, tile, st()), "gemm_split")
-            measure(f"{M} x {K} x {N}", note, 2.0 * M * K * N, lib_fn, [("64", split_fn(1)), ("32", split_fn(2))], y0, y1)
+            measure(f"{M} x {K} x {N}", note, 2.0 * M * K * N, lib_fn, all_tiles(split_fn), y0, y1)
             del A, wt, wp, y0, y1
         for B, H, W, K, N, note in STRIDED:
             x = torch.relu(torch.randn(B, H, W, K, device=dev))
@@ -134,7 +140,7 @@ def main():
                 return lambda: _lib.check(L.dagr_gemm_split_bf16(_lib.ptr(x), M, K, K, _lib.ptr(wp), N, _lib.ptr(bias), None, N,
                                                                  0, _lib.ptr(y1), N, B, H, W, 2, tile, st()), "gemm_split")
             measure(f"{M} x {K} x {N} (/2 of {H}x{W})", note, 2.0 * M * K * N, lib_fn,
-                    [("64", split_fn(1)), ("32", split_fn(2))], y0, y1)
+                    all_tiles(split_fn), y0, y1)
             del x, wt, wp, y0, y1
     if a.only in (None, "3x3"):
         for B, H, W, C, note in CONVS:
@@ -158,7 +164,7 @@ def main():
             y0 = hold["y"].permute(0, 2, 3, 1).reshape(M, C)
             # (every lib_fn() makes a new map from the same operands; the first one is what the split result is set against)
             measure(f"3x3 {H}x{W} C={C} (M {M}, K {9 * C}, N {C})", note, 2.0 * M * 9 * C * C, lib_fn,
-                    [("64", split_fn(1)), ("32", split_fn(2))], y0, y1)
+                    all_tiles(split_fn), y0, y1)
             del x, w, wp, y1
     text = "\n".join(rows) + "\n"
     if a.md:
