@@ -420,7 +420,11 @@ typedef struct {
     float two_max;        /* fp32(2*max_value) of this pooling's Cartesian transform    */
     float r00, r02, r11, r12; /* attr_remapping_matrix of the consuming convs (spline_conv.py:23-24) */
     int32_t rx, ry;       /* their LUT offset domain                                    */
-    int32_t aggr;         /* 0 = max, 1 = mean                                          */
+    int32_t aggr;         /* 0 = max, 1 = mean.  max: any non-NaN fp32, -0.0 ranks below +0.0.  mean: every term is
+                           * rounded to a multiple of 2^-32 and summed in 64-bit fixed point (exact, order-free), so a
+                           * cluster's features must satisfy |v| * members < 2^31 (|v| < 2^20 with up to 2048 members)
+                           * and values below 2^-33 count as 0; the result is within 2^-33 + one fp32 rounding of the
+                           * exact mean                                                    */
     int32_t append_pos;   /* also write pos[:, :2] into columns C, C+1 of each output row (net.py:137-138) */
     int32_t keep_order;   /* --keep_temporal_ordering (pooling.py:69-72).  0: every coarse edge.  1: a coarse edge
                            * src -> dst is emitted only if t_max[dst] > t_max[src] (strict: equal t_max drops it both
