@@ -5,10 +5,26 @@
 // between cells, so: events grouped by output cell in time order (stable sort by cell, done by the caller with one
 // torch.sort -- the same preparation the reference's graph builder asks for, graph/utils.py:9-13), then one thread per
 // occupied cell walks its run.  `change_map` carries the integrator state from chunk to chunk as in the reference.
+//
+// The stream front (dagr_stream_downsample) runs the same integrator in front of dagr_stream_stage_dev on raw sensor events
+// of several lanes: cell keys, a stable radix sort by key, one thread per run head, a chained scan over the keep flags and
+// an order-preserving compaction that leaves the survivors and their count in device memory.
 #include "common.hpp"
+
+#include <rocprim/device/device_radix_sort.hpp>
 
 namespace dagr {
 namespace {
+
+// One event through a cell's integrator; both kernels below call it.
+// downsample_events.py:117: change_map += p * 1.0 / (fx * fy) -- a float64 product rounded into the fp32 map;
+// :119 passes when |state| >= 1; :121 subtracts the polarity of an event that passed.
+__device__ __forceinline__ bool integrate_event(float &state, float pol, float inc) {
+    state = (float)((double)state + (double)pol * (double)inc);
+    const bool pass = fabsf(state) >= 1.0f;
+    if (pass) state -= pol;
+    return pass;
+}
 
 __global__ __launch_bounds__(kBlock) void k_downsample_cells(const int32_t *__restrict__ order,       // event ids by (cell, time)
                                                             const int32_t *__restrict__ cell_of,     // [n_runs] cell id
@@ -22,14 +38,147 @@ __global__ __launch_bounds__(kBlock) void k_downsample_cells(const int32_t *__re
     float state = change_map[cell];
     for (int k = a; k < b; k++) {
         const int e = order[k];
-        const float pol = (float)p[e];
-        // downsample_events.py:117: change_map += p * 1.0 / (fx * fy) -- a float64 product rounded into the fp32 map
-        state = (float)((double)state + (double)pol * (double)inc);
-        bool pass = fabsf(state) >= 1.0f;                                  // :119
-        keep[e] = pass ? 1 : 0;
-        if (pass) state -= pol;                                            // :121
+        keep[e] = integrate_event(state, (float)p[e], inc) ? 1 : 0;
     }
     change_map[cell] = state;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Stream front.  Caller-owned state: the lanes' change maps first (offset 0, fp32 [B, cells_h, cells_w]), then the scan's
+// look-back state, then keys / run order / flags / offsets for a largest push and the sort's temporary storage.
+struct StreamFront {
+    float *maps;
+    void *scan_state;
+    uint32_t *key_in, *key_out;     // [max_push] cell keys in arrival order / grouped
+    int32_t *idx_in, *idx_out;      // [max_push] event ids in arrival order / grouped by key, arrival order inside a key
+    int32_t *flag, *offs;           // [max_push] keep flags in arrival order and their exclusive prefix sum
+    void *sort_tmp;
+    size_t sort_tmp_bytes, tmp_offset;
+    size_t head_bytes;              // maps + scan state: what a reset zeroes
+};
+
+int key_bits(int64_t sentinel) {
+    int bits = 1;
+    while (bits < 32 && (sentinel >> bits) != 0) ++bits;
+    return bits;
+}
+
+// the sort's temporary storage for a push of n events (0 if the library cannot say, e.g. without a device)
+size_t sort_tmp_bytes(int64_t n, int bits) {
+    size_t bytes = 0;
+    if (rocprim::radix_sort_pairs(nullptr, bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr,
+                                  (int32_t *)nullptr, (size_t)n, 0u, (unsigned)bits, (hipStream_t)0) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return bytes;
+}
+
+// sort_storage: also size the sort's temporary storage (dagr_stream_front_bytes); the other callers take what is left of
+// the caller's buffer behind `sort_tmp`.
+size_t carve_front(int B, int64_t cells, int64_t max_push, char *base, StreamFront *out, bool sort_storage) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        size_t o = off;
+        off = align_up(off + bytes, 256);
+        return base ? base + o : nullptr;
+    };
+    StreamFront f;
+    f.maps = (float *)take((size_t)B * cells * 4);
+    f.scan_state = take(scan_chained_state_bytes(max_push));
+    f.head_bytes = off;
+    f.key_in = (uint32_t *)take((size_t)max_push * 4);
+    f.key_out = (uint32_t *)take((size_t)max_push * 4);
+    f.idx_in = (int32_t *)take((size_t)max_push * 4);
+    f.idx_out = (int32_t *)take((size_t)max_push * 4);
+    f.flag = (int32_t *)take((size_t)max_push * 4);
+    f.offs = (int32_t *)take((size_t)max_push * 4);
+    f.sort_tmp_bytes = 256;
+    if (sort_storage) {
+        // the library picks its algorithm by size, so the largest push need not ask for the most: max_push and every
+        // power of two below it
+        const int bits = key_bits((int64_t)B * cells);
+        for (int64_t n = max_push; n >= 1; n = (n & (n - 1)) ? (int64_t)1 << (63 - __builtin_clzll((unsigned long long)n)) : n / 2)
+            f.sort_tmp_bytes = std::max(f.sort_tmp_bytes, sort_tmp_bytes(n, bits));
+    }
+    f.tmp_offset = off;
+    f.sort_tmp = take(f.sort_tmp_bytes);
+    if (out) *out = f;
+    return off;
+}
+
+bool front_sizes_ok(int32_t B, int32_t cells_w, int32_t cells_h, int64_t max_push) {
+    return B >= 1 && B < 128 && cells_w >= 1 && cells_h >= 1 && max_push >= 1 && max_push < (1ll << 31) / 64 &&
+           (int64_t)B * cells_w * cells_h < (1ll << 31) - 1;
+}
+
+// Launch 1: the key of every raw event, lane * cells + cell, and its id.  An event outside the sensor (status bit 4), in the
+// strip right of / below the last whole cell, or with a lane outside [0, B) (dagr_stream_stage_dev flags that one) gets the
+// sentinel key B * cells: it sorts behind every cell and is never kept.
+template <typename BatchT>
+__global__ __launch_bounds__(kBlock) void k_front_keys(const int32_t *__restrict__ xy, const BatchT *__restrict__ batch, int n,
+                                                      int B, int fx, int fy, int sensor_w, int sensor_h, int cells_w,
+                                                      int cells_h, uint32_t *__restrict__ key, int32_t *__restrict__ idx,
+                                                      int32_t *__restrict__ status) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int32_t v = xy[i];
+    const int x = (int16_t)(v & 0xffff), y = (int16_t)(v >> 16);
+    const int64_t b = (int64_t)batch[i];
+    const bool outside = x < 0 || x >= sensor_w || y < 0 || y >= sensor_h;
+    if (outside) atomicOr(status, 16);
+    const int cx = outside ? 0 : x / fx, cy = outside ? 0 : y / fy;
+    const uint32_t cells = (uint32_t)cells_w * (uint32_t)cells_h;
+    const bool none = outside || cx >= cells_w || cy >= cells_h || b < 0 || b >= B;
+    key[i] = none ? (uint32_t)B * cells : (uint32_t)b * cells + (uint32_t)(cy * cells_w + cx);
+    idx[i] = i;
+}
+
+// Launch 3 (after the sort): one thread per grouped position.  A position whose key differs from its predecessor's is a run
+// head and walks its run in arrival order through the cell's integrator; a cell outside the model's width x height
+// integrates as every other (the reference downsamples the whole sensor and crops afterwards) but keeps nothing.
+__global__ __launch_bounds__(kBlock) void k_front_integrate(const uint32_t *__restrict__ key, const int32_t *__restrict__ idx,
+                                                           int n, uint32_t sentinel, int cells_w, int cells_h, int width,
+                                                           int height, const int8_t *__restrict__ p, float inc,
+                                                           float *__restrict__ maps, int32_t *__restrict__ flag) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t mine = key[k];
+    if (mine >= sentinel) {
+        flag[idx[k]] = 0;
+        return;
+    }
+    if (k > 0 && key[k - 1] == mine) return;
+    const int cell = (int)(mine % ((uint32_t)cells_w * (uint32_t)cells_h));
+    const bool inside = cell % cells_w < width && cell / cells_w < height;
+    float state = maps[mine];
+    for (int j = k; j < n && key[j] == mine; ++j) {
+        const int e = idx[j];
+        const bool pass = integrate_event(state, (float)p[e], inc);
+        flag[e] = pass && inside ? 1 : 0;
+    }
+    maps[mine] = state;
+}
+
+// Launch 5 (after the scan): the survivors, in arrival order, at the cells' coordinates, and their count.
+template <typename BatchT>
+__global__ __launch_bounds__(kBlock) void k_front_compact(const int32_t *__restrict__ flag, const int32_t *__restrict__ offs,
+                                                         int n, const int32_t *__restrict__ xy, const int64_t *__restrict__ t,
+                                                         const int8_t *__restrict__ p, const BatchT *__restrict__ batch,
+                                                         int fx, int fy, int32_t *__restrict__ xy_out,
+                                                         int64_t *__restrict__ t_out, int8_t *__restrict__ p_out,
+                                                         int32_t *__restrict__ batch_out, int32_t *__restrict__ n_out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int keep = flag[i], j = offs[i];
+    if (i == n - 1) *n_out = j + keep;
+    if (!keep || j < 0 || j > i) return;
+    const int32_t v = xy[i];
+    const int x = (int16_t)(v & 0xffff) / fx, y = (int16_t)(v >> 16) / fy;
+    xy_out[j] = (x & 0xffff) | (y << 16);
+    t_out[j] = t[i];
+    p_out[j] = p[i];
+    batch_out[j] = (int32_t)batch[i];
 }
 
 }  // namespace
@@ -46,6 +195,82 @@ extern "C" int dagr_downsample_events(const int32_t *order, const int32_t *run_c
     const float inc = (float)(1.0 / (double)(fx * fy));
     k_downsample_cells<<<(unsigned)ceil_div(n_runs, kBlock), kBlock, 0, (hipStream_t)stream>>>(
         order, run_cell, run_end, n_runs, polarity, inc, change_map, keep);
+    DAGR_CHECK_LAUNCH();
+    return DAGR_OK;
+}
+
+extern "C" size_t dagr_stream_front_bytes(int32_t B, int32_t cells_w, int32_t cells_h, int64_t max_push) {
+    if (!front_sizes_ok(B, cells_w, cells_h, max_push)) return 0;
+    return carve_front(B, (int64_t)cells_w * cells_h, max_push, nullptr, nullptr, true);
+}
+
+extern "C" int dagr_stream_front_reset(void *front, size_t front_bytes, int32_t B, int32_t cells_w, int32_t cells_h,
+                                       int64_t max_push, void *stream) {
+    DAGR_CHECK_ARG(front != nullptr, "stream front: state is NULL");
+    DAGR_CHECK_ARG(front_sizes_ok(B, cells_w, cells_h, max_push), "stream front: sizes out of range");
+    StreamFront f;
+    carve_front(B, (int64_t)cells_w * cells_h, max_push, (char *)front, &f, false);
+    DAGR_CHECK_ARG(front_bytes >= f.tmp_offset + 256, "stream front: state smaller than dagr_stream_front_bytes");
+    DAGR_CHECK_HIP(hipMemsetAsync(front, 0, f.head_bytes, (hipStream_t)stream));
+    return DAGR_OK;
+}
+
+extern "C" int dagr_stream_downsample(void *front, size_t front_bytes, int32_t B, int64_t max_push, int32_t fx, int32_t fy, int32_t sensor_w,
+                                      int32_t sensor_h, int32_t width, int32_t height, const int16_t *xy_raw,
+                                      const int64_t *t_raw, const int8_t *p_raw, const void *batch_raw,
+                                      int32_t batch_is_int64, int64_t n_raw, int16_t *xy_out, int64_t *t_out, int8_t *p_out,
+                                      int32_t *batch_out, int32_t *n_out, int32_t *status, void *stream_) {
+    DAGR_CHECK_ARG(fx >= 1 && fy >= 1 && sensor_w >= fx && sensor_h >= fy && sensor_w <= 32767 && sensor_h <= 32767,
+                   "stream front: bad factors or sensor size");
+    const int32_t cells_w = sensor_w / fx, cells_h = sensor_h / fy;
+    DAGR_CHECK_ARG(front_sizes_ok(B, cells_w, cells_h, max_push), "stream front: sizes out of range");
+    DAGR_CHECK_ARG(width >= 1 && height >= 1 && width <= cells_w && height <= cells_h,
+                   "stream front: the cell grid does not cover width x height");
+    DAGR_CHECK_ARG(front && n_out && status, "stream front: NULL pointer");
+    DAGR_CHECK_ARG(n_raw >= 0 && n_raw <= max_push, "stream front: max_push < n_raw");
+    DAGR_CHECK_ARG(n_raw == 0 || (xy_raw && t_raw && p_raw && batch_raw && xy_out && t_out && p_out && batch_out),
+                   "stream front: NULL input or output");
+    DAGR_CHECK_ARG(((uintptr_t)xy_raw & 3) == 0 && ((uintptr_t)xy_out & 3) == 0, "stream front: xy must be 4-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_raw == 0) {
+        DAGR_CHECK_HIP(hipMemsetAsync(n_out, 0, 4, stream));
+        return DAGR_OK;
+    }
+    StreamFront f;
+    const int64_t cells = (int64_t)cells_w * cells_h;
+    carve_front(B, cells, max_push, (char *)front, &f, false);
+    DAGR_CHECK_ARG(front_bytes >= f.tmp_offset + 256, "stream front: state smaller than dagr_stream_front_bytes");
+    f.sort_tmp_bytes = front_bytes - f.tmp_offset;
+    const int n = (int)n_raw, bits = key_bits((int64_t)B * cells);
+    const unsigned grid = (unsigned)ceil_div(n_raw, kBlock);
+    const uint32_t sentinel = (uint32_t)((int64_t)B * cells);
+    const float inc = (float)(1.0 / (double)(fx * fy));
+    size_t tmp = 0;
+    DAGR_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, tmp, f.key_in, f.key_out, f.idx_in, f.idx_out, (size_t)n, 0u,
+                                             (unsigned)bits, stream));
+    DAGR_CHECK_ARG(tmp <= f.sort_tmp_bytes, "stream front: the sort asks for more temporary storage than the state holds");
+    tmp = f.sort_tmp_bytes;
+    if (batch_is_int64)
+        k_front_keys<int64_t><<<grid, kBlock, 0, stream>>>((const int32_t *)xy_raw, (const int64_t *)batch_raw, n, B, fx, fy,
+                                                          sensor_w, sensor_h, cells_w, cells_h, f.key_in, f.idx_in, status);
+    else
+        k_front_keys<int32_t><<<grid, kBlock, 0, stream>>>((const int32_t *)xy_raw, (const int32_t *)batch_raw, n, B, fx, fy,
+                                                          sensor_w, sensor_h, cells_w, cells_h, f.key_in, f.idx_in, status);
+    DAGR_CHECK_LAUNCH();
+    DAGR_CHECK_HIP(rocprim::radix_sort_pairs(f.sort_tmp, tmp, f.key_in, f.key_out, f.idx_in, f.idx_out, (size_t)n, 0u,
+                                             (unsigned)bits, stream));
+    k_front_integrate<<<grid, kBlock, 0, stream>>>(f.key_out, f.idx_out, n, sentinel, cells_w, cells_h, width, height, p_raw,
+                                                   inc, f.maps, f.flag);
+    DAGR_CHECK_LAUNCH();
+    DAGR_CHECK_HIP(exclusive_scan_i32_chained(f.flag, f.offs, n_raw, f.scan_state, false, stream));
+    if (batch_is_int64)
+        k_front_compact<int64_t><<<grid, kBlock, 0, stream>>>(f.flag, f.offs, n, (const int32_t *)xy_raw, t_raw, p_raw,
+                                                             (const int64_t *)batch_raw, fx, fy, (int32_t *)xy_out, t_out,
+                                                             p_out, batch_out, n_out);
+    else
+        k_front_compact<int32_t><<<grid, kBlock, 0, stream>>>(f.flag, f.offs, n, (const int32_t *)xy_raw, t_raw, p_raw,
+                                                             (const int32_t *)batch_raw, fx, fy, (int32_t *)xy_out, t_out,
+                                                             p_out, batch_out, n_out);
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
 }

@@ -1122,10 +1122,16 @@ __device__ __forceinline__ int first_later(const int64_t *__restrict__ t, int n,
 // Launch 1 of a stream step, one block, one thread per lane: the new events' segment in batch_new, t_ref, the cut in the
 // resident segment and in the new one (binary searches on t), the prefix sum over the lanes, and the plan launch 2 follows.
 // The lane bounds of the NEXT window are written here too: launch 2 reads the plan only.
-template <typename BatchT>
+// The clock (t_clock / batch_clock, n_clock events) is what the lanes' newest timestamps and the order check come from:
+// the new events themselves, or -- dagr_stream_stage_dev -- the raw events they were selected from.  n_new_dev, when given,
+// holds the number of new events (at most n_new).
+template <typename BatchT, typename ClockT>
 __global__ __launch_bounds__(kStreamLanes) void k_stream_plan(StreamState st, int B, int cap,
                                                               const BatchT *__restrict__ batch_new,
                                                               const int64_t *__restrict__ t_new, int n_new,
+                                                              const int32_t *__restrict__ n_new_dev,
+                                                              const ClockT *__restrict__ batch_clock,
+                                                              const int64_t *__restrict__ t_clock, int n_clock,
                                                               const int64_t *__restrict__ t_now, int64_t window_us,
                                                               int32_t *__restrict__ n_dev,
                                                               int32_t *__restrict__ lane_count,
@@ -1134,14 +1140,17 @@ __global__ __launch_bounds__(kStreamLanes) void k_stream_plan(StreamState st, in
     const int b = threadIdx.x;
     const int src = st.hdr[0] & 1;
     int flags = 0, first_old = 0, keep_old = 0, first_new = 0, keep_new = 0;
+    if (n_new_dev) n_new = min(max(*n_new_dev, 0), n_new);
     if (b < B) {
         const int ns = first_lane_at_least(batch_new, n_new, b);
         const int ne = max(ns, first_lane_at_least(batch_new, n_new, b + 1));
+        const int cs = first_lane_at_least(batch_clock, n_clock, b);
+        const int ce = max(cs, first_lane_at_least(batch_clock, n_clock, b + 1));
         const int64_t last = st.t_last[b], ref_prev = st.t_ref[b];
         int64_t newest = last;
-        if (ne > ns) {
-            if (last != kNever && t_new[ns] < last) flags |= 1;
-            newest = max(last, t_new[ne - 1]);
+        if (ce > cs) {
+            if (last != kNever && t_clock[cs] < last) flags |= 1;
+            newest = max(last, t_clock[ce - 1]);
         }
         const int64_t ref = t_now ? t_now[b] : (newest != kNever ? newest : ref_prev);   // (no event yet: t_ref stays)
         if ((newest != kNever && ref < newest) || (ref_prev != kNever && ref < ref_prev)) flags |= 2;
@@ -1191,13 +1200,16 @@ __global__ __launch_bounds__(kStreamLanes) void k_stream_plan(StreamState st, in
 // Launch 2: one thread per event of the next window (grid sized for the capacity, bounded by the count launch 1 left).  The
 // plan sits in LDS; a thread finds its lane there, gathers its raw event from the survivors or from the new events, writes
 // it to the other raw set and, formatted (dagr_format_events' fp32 divisions), to the static input buffers, and runs K1 on
-// the formatted row.  Thread i < n_new also checks new event i against its predecessor (status bits 0 and 3).
-template <typename BatchT>
+// the formatted row.  Thread i < n_clock also checks clock event i against its predecessor (status bits 0 and 3).
+template <typename BatchT, typename ClockT>
 __global__ __launch_bounds__(kBlock) void k_stream_gather(StreamState st, int B, int cap,
                                                          const int32_t *__restrict__ xy_new,
                                                          const int64_t *__restrict__ t_new,
                                                          const int8_t *__restrict__ p_new,
                                                          const BatchT *__restrict__ batch_new, int n_new,
+                                                         const int32_t *__restrict__ n_new_dev,
+                                                         const ClockT *__restrict__ batch_clock,
+                                                         const int64_t *__restrict__ t_clock, int n_clock,
                                                          int time_window, float *__restrict__ pos_out,
                                                          float *__restrict__ feat_out, int32_t *__restrict__ batch_out,
                                                          int32_t *__restrict__ status8, int32_t *__restrict__ status,
@@ -1208,16 +1220,17 @@ __global__ __launch_bounds__(kBlock) void k_stream_gather(StreamState st, int B,
     __shared__ int64_t s_ref[kStreamLanes];
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i < 8) status8[i] = 0;     // the builder's status words start over (dagr_graph_build_window_dev)
-    if (i < n_new) {
-        const int64_t bi = (int64_t)batch_new[i];
+    if (i < n_clock) {
+        const int64_t bi = (int64_t)batch_clock[i];
         int f = (bi < 0 || bi >= B) ? 8 : 0;
         if (i > 0) {
-            const int64_t bp = (int64_t)batch_new[i - 1];
+            const int64_t bp = (int64_t)batch_clock[i - 1];
             if (bp > bi) f |= 8;
-            else if (bp == bi && t_new[i - 1] > t_new[i]) f |= 1;
+            else if (bp == bi && t_clock[i - 1] > t_clock[i]) f |= 1;
         }
         if (f) atomicOr(status, f);
     }
+    if (n_new_dev) n_new = min(max(*n_new_dev, 0), n_new);
     const int n_out = min(st.hdr[2], cap);
     if ((int)(blockIdx.x * kBlock) >= n_out) return;        // (the whole block)
     for (int k = threadIdx.x; k < 5 * B; k += kBlock) s_plan[k] = st.plan[k];
@@ -1525,11 +1538,28 @@ int dagr_stream_grow(const void *state, int64_t capacity, void *state_new, int64
     return DAGR_OK;
 }
 
-int dagr_stream_stage(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
-                      const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const void *batch_new,
-                      int32_t batch_is_int64, int64_t n_new, const int64_t *t_now, int64_t window_us, float *pos_out,
-                      float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status,
-                      void *stream_) {
+// Both entries: the new events (n_new of them, or *n_new_dev <= n_new) and the clock they are checked and timed by.
+extern "C++" template <typename BatchT, typename ClockT>
+static void launch_stream_stage(const dagr_graph_desc *desc, const GraphWs &ws, const StreamState &st, int B, int cap,
+                                const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const void *batch_new,
+                                int n, const int32_t *n_new_dev, const void *batch_clock, const int64_t *t_clock,
+                                int n_clock, const int64_t *t_now, int64_t window_us, float *pos_out, float *feat_out,
+                                int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status,
+                                hipStream_t stream) {
+    const unsigned grid = (unsigned)ceil_div(std::max(cap, n_clock), kBlock);
+    k_stream_plan<BatchT, ClockT><<<1, kStreamLanes, 0, stream>>>(st, B, cap, (const BatchT *)batch_new, t_new, n, n_new_dev,
+                                                                  (const ClockT *)batch_clock, t_clock, n_clock, t_now,
+                                                                  window_us, n_dev, lane_count, status);
+    k_stream_gather<BatchT, ClockT><<<grid, kBlock, 0, stream>>>(
+        st, B, cap, (const int32_t *)xy_new, t_new, p_new, (const BatchT *)batch_new, n, n_new_dev,
+        (const ClockT *)batch_clock, t_clock, n_clock, desc->time_window, pos_out, feat_out, batch_out, ws.status, status,
+        desc->width, desc->height, ws.cnt, ws.ev_xyb, ws.ev_t, ws.ev_rank);
+}
+
+static int stream_stage_args(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                             const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const void *batch_new,
+                             int64_t n_new, int64_t window_us, float *pos_out, float *feat_out, int32_t *batch_out,
+                             int32_t *n_dev, int32_t *lane_count, int32_t *status, StreamState *st, GraphWs *ws) {
     int rc = validate(desc);
     if (rc != DAGR_OK) return rc;
     DAGR_CHECK_ARG(workspace && state && pos_out && feat_out && batch_out && n_dev && lane_count && status,
@@ -1540,27 +1570,58 @@ int dagr_stream_stage(const dagr_graph_desc *desc, void *workspace, void *state,
     DAGR_CHECK_ARG(n_new >= 0 && n_new <= capacity, "stream: capacity < n_new");
     DAGR_CHECK_ARG(n_new == 0 || (xy_new && t_new && p_new && batch_new), "stream: NULL input");
     DAGR_CHECK_ARG(((uintptr_t)xy_new & 3) == 0, "stream: xy_new must be 4-byte aligned");
-    StreamState st;
-    rc = stream_args(B, capacity, &st, state);
+    rc = stream_args(B, capacity, st, state);
     if (rc != DAGR_OK) return rc;
+    carve(*desc, (char *)workspace, ws);
+    return DAGR_OK;
+}
+
+int dagr_stream_stage(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                      const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const void *batch_new,
+                      int32_t batch_is_int64, int64_t n_new, const int64_t *t_now, int64_t window_us, float *pos_out,
+                      float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status,
+                      void *stream_) {
+    StreamState st;
     GraphWs ws;
-    carve(*desc, (char *)workspace, &ws);
-    hipStream_t stream = (hipStream_t)stream_;
+    int rc = stream_stage_args(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, n_new, window_us,
+                               pos_out, feat_out, batch_out, n_dev, lane_count, status, &st, &ws);
+    if (rc != DAGR_OK) return rc;
     const int cap = (int)capacity, n = (int)n_new;
-    const unsigned grid = (unsigned)ceil_div(capacity, kBlock);
-    if (batch_is_int64) {
-        k_stream_plan<int64_t><<<1, kStreamLanes, 0, stream>>>(st, B, cap, (const int64_t *)batch_new, t_new, n, t_now,
-                                                              window_us, n_dev, lane_count, status);
-        k_stream_gather<int64_t><<<grid, kBlock, 0, stream>>>(
-            st, B, cap, (const int32_t *)xy_new, t_new, p_new, (const int64_t *)batch_new, n, desc->time_window, pos_out,
-            feat_out, batch_out, ws.status, status, desc->width, desc->height, ws.cnt, ws.ev_xyb, ws.ev_t, ws.ev_rank);
-    } else {
-        k_stream_plan<int32_t><<<1, kStreamLanes, 0, stream>>>(st, B, cap, (const int32_t *)batch_new, t_new, n, t_now,
-                                                              window_us, n_dev, lane_count, status);
-        k_stream_gather<int32_t><<<grid, kBlock, 0, stream>>>(
-            st, B, cap, (const int32_t *)xy_new, t_new, p_new, (const int32_t *)batch_new, n, desc->time_window, pos_out,
-            feat_out, batch_out, ws.status, status, desc->width, desc->height, ws.cnt, ws.ev_xyb, ws.ev_t, ws.ev_rank);
-    }
+    if (batch_is_int64)
+        launch_stream_stage<int64_t, int64_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, nullptr, batch_new,
+                                              t_new, n, t_now, window_us, pos_out, feat_out, batch_out, n_dev, lane_count,
+                                              status, (hipStream_t)stream_);
+    else
+        launch_stream_stage<int32_t, int32_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, nullptr, batch_new,
+                                              t_new, n, t_now, window_us, pos_out, feat_out, batch_out, n_dev, lane_count,
+                                              status, (hipStream_t)stream_);
+    DAGR_CHECK_LAUNCH();
+    return DAGR_OK;
+}
+
+int dagr_stream_stage_dev(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                          const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const int32_t *batch_new,
+                          const int32_t *n_new_dev, int64_t n_new_max, const int64_t *t_clock, const void *batch_clock,
+                          int32_t clock_is_int64, int64_t n_clock, const int64_t *t_now, int64_t window_us, float *pos_out,
+                          float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status,
+                          void *stream_) {
+    StreamState st;
+    GraphWs ws;
+    int rc = stream_stage_args(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, n_new_max, window_us,
+                               pos_out, feat_out, batch_out, n_dev, lane_count, status, &st, &ws);
+    if (rc != DAGR_OK) return rc;
+    DAGR_CHECK_ARG(n_new_dev != nullptr, "stream: n_new_dev is NULL");
+    DAGR_CHECK_ARG(n_clock >= 0 && n_clock <= capacity, "stream: capacity < n_clock");
+    DAGR_CHECK_ARG(n_clock == 0 || (t_clock && batch_clock), "stream: NULL clock");
+    const int cap = (int)capacity, n = (int)n_new_max, nc = (int)n_clock;
+    if (clock_is_int64)
+        launch_stream_stage<int32_t, int64_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, n_new_dev, batch_clock,
+                                              t_clock, nc, t_now, window_us, pos_out, feat_out, batch_out, n_dev, lane_count,
+                                              status, (hipStream_t)stream_);
+    else
+        launch_stream_stage<int32_t, int32_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, n_new_dev, batch_clock,
+                                              t_clock, nc, t_now, window_us, pos_out, feat_out, batch_out, n_dev, lane_count,
+                                              status, (hipStream_t)stream_);
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
 }

@@ -1,7 +1,12 @@
 """Event-stream downsampling on the device: ``downsample_events`` of ``scripts/downsample_events.py:91-106`` (the step
 that turns DSEC's 640x480 ``events.h5`` into the half-resolution ``events_2x.h5`` the reference trains and tests on).
 Same contract: events as a dict of arrays (here device tensors ``x, y`` integer, ``t``, ``p`` in {-1, +1}), the
-``change_map`` integrator state carried from chunk to chunk, returns the surviving events with ``x // fx``, ``y // fy``."""
+``change_map`` integrator state carried from chunk to chunk, returns the surviving events with ``x // fx``, ``y // fy``.
+
+This is the file-conversion route: it builds its runs with ``torch.unique_consecutive`` and cuts its result with a boolean
+mask, both of which wait for the device.  A LIVE stream of raw sensor events goes through
+``dagr.streaming.EventStream(model, downsample=...)`` instead, which runs the same integrator per lane in front of the
+stream's stage without a host synchronisation, carries the change maps itself and applies the row cut and the clock."""
 import torch
 
 from .. import _lib

@@ -392,7 +392,11 @@ class StreamState:
     last step -- and what the host knows of the window's size, which is an upper bound until a count has been read.
     Owned by the stream (``dagr.streaming.EventStream``), handed to ``WindowEngine.forward_stream`` on every step: the
     engine keeps no pointer into it, so a buffer that grew leaves nothing stale; an engine rebuilt with a smaller
-    capacity than the stream's is grown to it on the stream's next step."""
+    capacity than the stream's is grown to it on the stream's next step.
+
+    A stream of raw sensor events (``enable_front``) also owns the front's state (``dagr_stream_downsample``): the lanes'
+    change maps and the scratch of a largest push, grown with the push size, and the survivors' buffers.  The host's bound
+    is then "last count read + RAW events pushed since"."""
 
     def __init__(self, batch_size, window_us, device):
         self.B, self.window_us, self.device = int(batch_size), int(window_us), torch.device(device)
@@ -407,6 +411,60 @@ class StreamState:
         self._known = np.zeros((self.B,), np.int64)     # the last counts read
         self._since = 0                                 # events pushed since
         self._fresh = True                              # _known belongs to the last step staged
+        self.front = None                               # (fx, fy, W_in, H_in, W, H) of a downsampling stream
+        self.front_state, self.front_cap, self.front_out = None, 0, None
+
+    # ------------------------------------------------------------------------------------ raw sensor events
+    def enable_front(self, fx, fy, sensor_w, sensor_h, width, height):
+        """Pushes carry raw events of a ``sensor_w x sensor_h`` sensor, downsampled ``fx x fy`` on the device."""
+        self.front = tuple(int(v) for v in (fx, fy, sensor_w, sensor_h, width, height))
+        self.front_state, self.front_cap, self.front_out = None, 0, None
+        self.grow_front(4096)
+
+    def _cells(self):
+        fx, fy, sensor_w, sensor_h = self.front[:4]
+        return sensor_w // fx, sensor_h // fy
+
+    def grow_front(self, n):
+        """Scratch and survivors' buffers for pushes of ``n`` raw events; the change maps are carried over."""
+        if n <= self.front_cap:
+            return
+        L, stream = _lib.lib(), _lib.cur_stream(self.device)
+        cells_w, cells_h = self._cells()
+        nbytes = L.dagr_stream_front_bytes(self.B, cells_w, cells_h, n)
+        if nbytes == 0:
+            raise RuntimeError(f"dagr_stream_front_bytes({self.B}, {cells_w}, {cells_h}, {n}): out of range")
+        new = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _lib.check(L.dagr_stream_front_reset(_lib.ptr(new), nbytes, self.B, cells_w, cells_h, n, stream), "stream_front_reset")
+        if self.front_state is not None:
+            maps = 4 * self.B * cells_w * cells_h
+            new[:maps].copy_(self.front_state[:maps])
+        self.front_state, self.front_cap = new, n
+        dev = self.device
+        self.front_out = (torch.empty((n, 2), dtype=torch.int16, device=dev), torch.empty((n,), dtype=torch.int64, device=dev),
+                          torch.empty((n,), dtype=torch.int8, device=dev), torch.empty((n,), dtype=torch.int32, device=dev),
+                          torch.zeros((1,), dtype=torch.int32, device=dev))
+
+    def downsample(self, xy, t, p, batch):
+        """``dagr_stream_downsample`` on a raw push: ``(xy, t, p, batch int32, count int32[1])`` of the survivors, on the
+        device, valid until the next push."""
+        n = int(t.shape[0])
+        if n > self.front_cap:
+            self.grow_front(max(n, 2 * self.front_cap))
+        fx, fy, sensor_w, sensor_h, width, height = self.front
+        P, o = _lib.ptr, self.front_out
+        _lib.check(_lib.lib().dagr_stream_downsample(
+            P(self.front_state), self.front_state.numel(), self.B, self.front_cap, fx, fy, sensor_w, sensor_h, width, height,
+            P(xy), P(t), P(p), P(batch), 1 if batch.dtype == torch.int64 else 0, n, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]),
+            P(self.status), _lib.cur_stream(self.device)), "stream_downsample")
+        return o
+
+    def change_maps(self):
+        """The lanes' change maps fp32[B, cells_h, cells_w] (a copy; synchronises)."""
+        if self.front is None:
+            raise RuntimeError("this stream does not downsample: it has no change maps")
+        cells_w, cells_h = self._cells()
+        return self.front_state[:4 * self.B * cells_w * cells_h].view(torch.float32).view(self.B, cells_h, cells_w).cpu().numpy()
 
     def _alloc(self, cap):
         L = _lib.lib()
@@ -419,6 +477,11 @@ class StreamState:
         if self.state is not None:
             _lib.check(_lib.lib().dagr_stream_reset(_lib.ptr(self.state), self.B, self.cap, _lib.cur_stream(self.device)),
                        "stream_reset")
+        if self.front_state is not None:
+            cells_w, cells_h = self._cells()
+            _lib.check(_lib.lib().dagr_stream_front_reset(_lib.ptr(self.front_state), self.front_state.numel(), self.B, cells_w,
+                                                          cells_h, self.front_cap, _lib.cur_stream(self.device)),
+                       "stream_front_reset")
         self.status.zero_()
         self.lane_count.zero_()
         torch.cuda.current_stream(self.device).synchronize()       # (a count copy may still be on its way)
@@ -1616,7 +1679,7 @@ class WindowEngine:
         """One step of an event stream (``StreamState`` ``st``): ``_forward_window_graph`` with ``dagr_stream_stage`` in
         place of ``dagr_stage_window``.  The new raw events (``xy`` int16[n,2], ``t`` int64[n] absolute us, ``p`` int8[n],
         ``batch`` int32/int64[n] sorted lanes, ``t_now`` int64[B] or None; all on the device) join the window kept in
-        ``st``; two launches write the next window into the static input buffers and its count to device memory, and
+        ``st`` -- through ``dagr_stream_downsample`` first when the stream carries raw sensor events (``st.front``) --; two launches write the next window into the static input buffers and its count to device memory, and
         the window runs on them -- the captured graph in latency mode, the same body launch by launch otherwise.  No host
         synchronisation: the host knows an upper bound of the window's size only (``st.bound()``), which is what the
         buffers are sized by.  Returns ``(out, (det, n_keep))``, both valid until the engine's next call."""
@@ -1650,10 +1713,22 @@ class WindowEngine:
             self._graph_warm = 0
         self._post_fresh = False
         g = self.graph
-        _lib.check(L.dagr_stream_stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(xy), P(t), P(p),
-                                       P(batch), 1 if batch.dtype == torch.int64 else 0, n_new, P(t_now), st.window_us,
-                                       P(self.in_pos), P(self.in_feat), P(self.in_batch), P(self.n_dev), P(st.lane_count),
-                                       P(st.status), _lib.cur_stream(self.device)), "stream_stage")
+        if st.front is None:
+            _lib.check(L.dagr_stream_stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(xy), P(t), P(p),
+                                           P(batch), 1 if batch.dtype == torch.int64 else 0, n_new, P(t_now), st.window_us,
+                                           P(self.in_pos), P(self.in_feat), P(self.in_batch), P(self.n_dev),
+                                           P(st.lane_count), P(st.status), _lib.cur_stream(self.device)), "stream_stage")
+        else:       # raw sensor events: the front leaves the survivors and their count on the device, the raw push is the clock
+            if st.front[4:] != (self.W, self.H):
+                raise RuntimeError(f"the stream downsamples to {st.front[4]} x {st.front[5]}, the engine runs "
+                                   f"{self.W} x {self.H}")
+            s_xy, s_t, s_p, s_batch, s_n = st.downsample(xy, t, p, batch)
+            _lib.check(L.dagr_stream_stage_dev(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(s_xy),
+                                               P(s_t), P(s_p), P(s_batch), P(s_n), n_new, P(t), P(batch),
+                                               1 if batch.dtype == torch.int64 else 0, n_new, P(t_now), st.window_us,
+                                               P(self.in_pos), P(self.in_feat), P(self.in_batch), P(self.n_dev),
+                                               P(st.lane_count), P(st.status), _lib.cur_stream(self.device)),
+                       "stream_stage_dev")
         if not self.window_graph:                    # throughput mode: the body of the captured window, launch by launch
             out = self._forward_static()
         elif self._wg is None:

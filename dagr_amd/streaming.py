@@ -21,6 +21,21 @@ documentation and of the tests; nothing on the device path calls it):
 * the batch window is the lanes' windows concatenated in lane order, the model input is ``format_data`` of
   ``(x, y, t_rel, p)`` under the engine's ``(W, H, time_window)``, and the step's result is, bit for bit, what
   ``model(that batch, reset=True)`` returns.
+
+Raw sensor events (``downsample=f`` or ``(fx, fy)``): the models read ``events_2x`` streams, the sensor's events through
+the integrate-and-fire loop of ``scripts/downsample_events.py:91-124`` and cut to the model's rows
+(``DSEC.preprocess_events``).  A push then carries sensor pixels of a ``sensor_size = (W_in, H_in)`` sensor (default
+``(fx * W, fy * H)``), and in front of everything above:
+
+* the cell grid is ``(W_in // fx, H_in // fy)`` and covers the model's ``(W, H)``; every lane owns an fp32 change map over
+  it, zero after construction and after ``reset()``, carried from push to push;
+* a lane's raw events go through their cells in arrival order: the cell adds ``p / (fx * fy)`` (a float64 product rounded
+  into the fp32 cell, ``fp32(1 / (fx * fy))`` being the increment, as ``k_downsample_cells`` has it); when ``|cell| >= 1``
+  the event survives at ``(x // fx, y // fy)`` and ``p`` is subtracted;
+* a survivor with ``x >= W`` or ``y >= H`` is dropped (the dataset's row cut), and so is an event right of / below the last
+  whole cell; a raw event outside ``[0, W_in) x [0, H_in)`` is malformed (status bit of value 16);
+* what is left is pushed as above, but the clock is the sensor's: the order checks run on the raw arrays, and the lane's
+  newest event -- ``t_last``, and ``t_ref`` without ``t_now`` -- is its newest RAW event.
 """
 import numpy as np
 
@@ -29,18 +44,37 @@ from .utils.synthetic import format_data_np
 STATUS_BITS = ((1, "a timestamp goes backwards inside a lane (within a push or against the lane's newest event)"),
                (2, "t_now is behind the lane's newest event or behind its previous t_ref"),
                (4, "survivors plus new events exceed the stream's capacity"),
-               (8, "batch is not sorted or is outside [0, batch_size)"))
+               (8, "batch is not sorted or is outside [0, batch_size)"),
+               (16, "a raw event is outside the sensor (downsampling streams)"))
+
+
+def _factors(downsample, width, height, sensor_size, who):
+    """``(fx, fy, W_in, H_in)`` of a downsampling stream over a ``width x height`` model; refusals by name."""
+    f = (downsample, downsample) if np.ndim(downsample) == 0 else tuple(downsample)
+    if len(f) != 2 or any(int(v) != v or int(v) < 1 for v in f):
+        raise ValueError(f"{who}: downsample = {downsample!r} must be an integer factor >= 1 or a pair (fx, fy) of them")
+    fx, fy = int(f[0]), int(f[1])
+    w_in, h_in = (fx * width, fy * height) if sensor_size is None else (int(sensor_size[0]), int(sensor_size[1]))
+    if w_in // fx < width or h_in // fy < height:
+        raise ValueError(f"{who}: the cell grid {w_in // fx} x {h_in // fy} (sensor_size {w_in} x {h_in} over downsample "
+                         f"{fx} x {fy}) is smaller than the model's {width} x {height}")
+    if w_in > 32767 or h_in > 32767:
+        raise ValueError(f"{who}: sensor_size {w_in} x {h_in} does not fit the int16 pixel coordinates")
+    return fx, fy, w_in, h_in
 
 
 class StreamDefinition:
     """The definition above in numpy: ``push`` new events, read ``window()`` / ``formatted()`` / ``counts()``.  Malformed
     pushes raise ``ValueError`` (the device path reports them in its status word instead)."""
 
-    def __init__(self, batch_size, width, height, time_window=1000000, window_us=50000):
+    def __init__(self, batch_size, width, height, time_window=1000000, window_us=50000, downsample=None, sensor_size=None):
         if not 0 < int(window_us) <= int(time_window):
             raise ValueError(f"window_us = {window_us} must be in 1..time_window = {time_window}")
         self.B, self.W, self.H = int(batch_size), int(width), int(height)
         self.time_window, self.window_us = int(time_window), int(window_us)
+        self.front = None if downsample is None else _factors(downsample, self.W, self.H, sensor_size, "StreamDefinition")
+        if self.front is None and sensor_size is not None:
+            raise ValueError("StreamDefinition: sensor_size is given without downsample")
         self.reset()
 
     def reset(self):
@@ -48,6 +82,28 @@ class StreamDefinition:
                       for _ in range(self.B)]
         self.t_ref = [None] * self.B
         self.t_last = [None] * self.B
+        if self.front is not None:
+            fx, fy, w_in, h_in = self.front
+            self.change_map = np.zeros((self.B, h_in // fy, w_in // fx), np.float32)
+
+    def _downsample(self, x, y, t, p, batch):
+        """The survivors of a checked raw push, at the cells' coordinates and cut to the model's ``W x H``."""
+        fx, fy, w_in, h_in = self.front
+        inc = np.float64(np.float32(1.0 / (fx * fy)))
+        cells_h, cells_w = self.change_map.shape[1:]
+        keep = np.zeros(len(t), bool)
+        cx, cy = x.astype(np.int64) // fx, y.astype(np.int64) // fy
+        for i in range(len(t)):                            # a lane's events meet their cells in arrival order
+            if cx[i] >= cells_w or cy[i] >= cells_h:
+                continue
+            cell = (int(batch[i]), int(cy[i]), int(cx[i]))
+            pol = np.float32(p[i])
+            state = np.float32(np.float64(self.change_map[cell]) + np.float64(pol) * inc)
+            if np.abs(state) >= np.float32(1):
+                keep[i] = cx[i] < self.W and cy[i] < self.H
+                state = np.float32(state - pol)
+            self.change_map[cell] = state
+        return cx[keep].astype(np.int16), cy[keep].astype(np.int16), t[keep], p[keep], batch[keep]
 
     def push(self, x, y, t, p, batch=None, t_now=None):
         x, y, p = np.asarray(x, np.int16), np.asarray(y, np.int16), np.asarray(p, np.int8)
@@ -57,10 +113,11 @@ class StreamDefinition:
             raise ValueError("batch is not sorted or is outside [0, batch_size)")
         if t_now is not None:
             t_now = np.broadcast_to(np.asarray(t_now, np.int64).reshape(-1), (self.B,))
+        if self.front is not None and np.any((x < 0) | (x >= self.front[2]) | (y < 0) | (y >= self.front[3])):
+            raise ValueError("a raw event is outside the sensor")
         parts, refs = [], []
-        for b in range(self.B):                           # everything is checked before anything is changed
-            m = batch == b
-            tb = t[m]
+        for b in range(self.B):                           # everything is checked before anything is changed (on the RAW
+            tb = t[batch == b]                            # arrays of a downsampling stream: the clock is the sensor's)
             if len(tb) and (np.any(np.diff(tb) < 0) or (self.t_last[b] is not None and tb[0] < self.t_last[b])):
                 raise ValueError(f"lane {b}: a timestamp goes backwards")
             newest = int(tb[-1]) if len(tb) else self.t_last[b]
@@ -68,9 +125,12 @@ class StreamDefinition:
             if ref is not None and ((newest is not None and ref < newest) or
                                     (self.t_ref[b] is not None and ref < self.t_ref[b])):
                 raise ValueError(f"lane {b}: t_now is behind the lane's newest event or behind its previous t_ref")
-            parts.append((m, newest))
+            parts.append(newest)
             refs.append(ref)
-        for b, ((m, newest), ref) in enumerate(zip(parts, refs)):
+        if self.front is not None:
+            x, y, t, p, batch = self._downsample(x, y, t, p, batch)
+        for b, (newest, ref) in enumerate(zip(parts, refs)):
+            m = batch == b
             lane = self.lanes[b]
             lane.update(x=np.concatenate([lane["x"], x[m]]), y=np.concatenate([lane["y"], y[m]]),
                         t=np.concatenate([lane["t"], t[m]]), p=np.concatenate([lane["p"], p[m]]))
@@ -106,9 +166,12 @@ class EventStream:
 
     ``model``: an eval-mode ``DAGR`` on the GPU whose window engine runs the captured window: the tiled level-0 conv
     (``l0_tiles``), the event path (no ``--no_events``), the engine path (``model.module_path_only`` False).
+    ``downsample`` (``f`` or ``(fx, fy)``) and ``sensor_size`` (``(W_in, H_in)``, default ``(fx * W, fy * H)``): the
+    pushes carry raw sensor events, which ``dagr_stream_downsample`` turns into the model's on the device (module
+    docstring); ``change_maps()`` reads the integrators back.
     """
 
-    def __init__(self, model, window_us=50000):
+    def __init__(self, model, window_us=50000, downsample=None, sensor_size=None):
         import torch
         self.model = model
         self.window_us = int(window_us)
@@ -135,6 +198,11 @@ class EventStream:
         self.device = dev
         self.B = eng.B
         self.state = StreamState(eng.B, self.window_us, dev)
+        if downsample is not None:
+            fx, fy, w_in, h_in = _factors(downsample, eng.W, eng.H, sensor_size, "EventStream")
+            self.state.enable_front(fx, fy, w_in, h_in, eng.W, eng.H)
+        elif sensor_size is not None:
+            raise ValueError("EventStream: sensor_size is given without downsample")
         self._zeros = None
 
     # ------------------------------------------------------------------------------------ inputs
@@ -214,8 +282,12 @@ class EventStream:
         known = self.state.counts_known()
         return known if known is not None else np.zeros((self.B,), np.int64)
 
+    def change_maps(self):
+        """The lanes' change maps fp32[B, H_in // fy, W_in // fx] of a downsampling stream (a copy; synchronises)."""
+        return self.state.change_maps()
+
     def reset(self):
-        """Empty the stream: no resident events, no reference instants, a clear status word."""
+        """Empty the stream: no resident events, no reference instants, zero change maps, a clear status word."""
         self.state.reset()
 
     def check_status(self):

@@ -173,7 +173,8 @@ int dagr_stage_window(const dagr_graph_desc *desc, void *workspace, const float 
  *   bit 0: a timestamp goes backwards inside a lane, within a push or against the lane's newest event;
  *   bit 1: t_ref is behind the lane's newest event or behind its previous t_ref;
  *   bit 2: survivors plus new events exceed `capacity`;
- *   bit 3: batch_new is not sorted or is outside [0, B).
+ *   bit 3: batch_new is not sorted or is outside [0, B);
+ *   bit 4: (dagr_stream_downsample) a raw event outside the sensor.
  * Events outside the sensor raise the builder's own flag (dagr_graph_status).
  * DAGR_ERR_INVALID_ARG before any launch: window_us <= 0, window_us > desc.time_window, capacity < n_new,
  * capacity > desc.max_events, B != desc.batch_size, NULL pointers.
@@ -187,6 +188,50 @@ int dagr_stream_stage(const dagr_graph_desc *desc, void *workspace, void *state,
                       int32_t batch_is_int64, int64_t n_new, const int64_t *t_now /* [B] or NULL */, int64_t window_us,
                       float *pos_out, float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count /* [B] */,
                       int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------ *
+ * Event stream front: raw sensor events, downsampled on the device
+ *   The models read events_2x streams: the sensor's events through the integrate-and-fire loop of
+ *   scripts/downsample_events.py:91-124 (every cell of fx x fy sensor pixels adds p / (fx * fy) to its fp32 state; an event
+ *   that brings |state| to 1 survives at (x / fx, y / fy) and its polarity is subtracted), then cut to the model's rows
+ *   (DSEC.preprocess_events).  dagr_stream_downsample does this to a push of raw events of B lanes and leaves the survivors
+ *   and their count in device memory; dagr_stream_stage_dev is dagr_stream_stage reading that count from the device.
+ *   Five launches and a library radix sort, no host synchronisation.
+ *
+ * The cell grid is cells_w x cells_h = (sensor_w / fx) x (sensor_h / fy) and must cover the model's width x height.  Every
+ * lane owns a change map fp32[cells_h, cells_w], carried from push to push.  A lane's raw events pass through their cells'
+ * integrators in arrival order -- the arithmetic of dagr_downsample_events, one device function --; a survivor whose cell is
+ * outside width x height is dropped silently (its cell integrates all the same), and so is an event in the strip right of /
+ * below the last whole cell.  A raw event outside [0, sensor_w) x [0, sensor_h) is dropped and raises bit 4 (value 16) of
+ * `status`, the stream's status word.  The survivors keep the order of the push.
+ *
+ * front: dagr_stream_front_bytes(B, cells_w, cells_h, max_push) bytes (0: sizes out of range), dagr_stream_front_reset
+ *        before the first push, after a change of max_push and to zero the maps.  The change maps are its first
+ *        B * cells_h * cells_w floats (a caller that needs a larger max_push copies them into the new state after its
+ *        reset); keys, run order, keep flags, their prefix sums and the sort's storage for max_push events follow.
+ * xy_raw int16[n_raw,2] (4-byte aligned) sensor pixels, t_raw int64[n_raw], p_raw int8[n_raw] in {-1, +1}, batch_raw
+ * int32/int64[n_raw]; outputs for n_raw events: xy_out int16[.,2] (4-byte aligned), t_out int64, p_out int8, batch_out
+ * int32, *n_out = the number of survivors.  All in device memory.
+ *
+ * dagr_stream_stage_dev: the new events are the first *n_new_dev (clamped to 0..n_new_max) of xy_new / t_new / p_new /
+ * batch_new (int32); the clock is t_clock / batch_clock (int32/int64, n_clock events) -- the raw push --, which the order
+ * checks (bits 0 and 3) run on and the lanes' newest timestamps (t_last, and t_ref without t_now) come from.  Everything
+ * else as dagr_stream_stage, which is this entry with the new events as their own clock.  n_new_max, n_clock <= capacity.
+ * ------------------------------------------------------------------------ */
+size_t dagr_stream_front_bytes(int32_t B, int32_t cells_w, int32_t cells_h, int64_t max_push);
+int dagr_stream_front_reset(void *front, size_t front_bytes, int32_t B, int32_t cells_w, int32_t cells_h, int64_t max_push,
+                            void *stream);
+int dagr_stream_downsample(void *front, size_t front_bytes, int32_t B, int64_t max_push, int32_t fx, int32_t fy,
+                           int32_t sensor_w, int32_t sensor_h, int32_t width, int32_t height, const int16_t *xy_raw,
+                           const int64_t *t_raw, const int8_t *p_raw, const void *batch_raw, int32_t batch_is_int64,
+                           int64_t n_raw, int16_t *xy_out, int64_t *t_out, int8_t *p_out, int32_t *batch_out,
+                           int32_t *n_out, int32_t *status, void *stream);
+int dagr_stream_stage_dev(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                          const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const int32_t *batch_new,
+                          const int32_t *n_new_dev, int64_t n_new_max, const int64_t *t_clock, const void *batch_clock,
+                          int32_t clock_is_int64, int64_t n_clock, const int64_t *t_now /* [B] or NULL */,
+                          int64_t window_us, float *pos_out, float *feat_out, int32_t *batch_out, int32_t *n_dev,
+                          int32_t *lane_count /* [B] */, int32_t *status, void *stream);
 
 /* The neighbour search alone, again, on the pixel index the last dagr_graph_build_window left in `workspace` (same N):
  * rewrites nbr_src / nbr_code / deg and the edge count.  For measurement (bench.py times the search kernels on their own

@@ -8,7 +8,11 @@ The sequence is the synthetic stand-in stream the other scripts fall back to (``
 per 50 ms, ``--width`` x ``--height``); ``main(argv, source=...)`` takes any object with ``t_range()`` and
 ``events(t0, t1)`` (a dict of ``x``, ``y``, ``t``, ``p`` with ``t0 <= t < t1``) -- and, for ``--use_image`` models,
 ``image_timestamps`` and ``image(i)`` (BGR uint8) -- in its place, as ``visualize_detections.main`` does.  Reading DSEC
-files is not part of this script."""
+files is not part of this script.
+
+``--downsample F``: the source delivers RAW sensor events, in the pixels of a ``--sensor_width`` x ``--sensor_height``
+sensor (default ``F * width`` x ``F * height``), and the stream downsamples them ``F`` x ``F`` on the device, as
+``scripts/downsample_events.py`` does for the ``events_2x`` files the models read."""
 import time
 import types
 
@@ -28,17 +32,32 @@ def stream_options(p):
     g.add_argument("--window_us", type=int, default=50000, help="length of the sliding event window")
     g.add_argument("--steps", type=int, default=100, help="number of steps to play (synthetic sequence)")
     g.add_argument("--sequence", type=str, default="synthetic_stream", help="name the detections are written under")
+    g.add_argument("--downsample", type=int, default=None, help="the source delivers raw sensor events: downsample them "
+                   "by this factor on the device")
+    g.add_argument("--sensor_width", type=int, default=None, help="sensor width with --downsample (default F * width)")
+    g.add_argument("--sensor_height", type=int, default=None, help="sensor height with --downsample (default F * height)")
+
+
+def sensor_size(a):
+    """``(W_in, H_in)`` the flags describe, or None without ``--downsample``."""
+    if a.downsample is None:
+        if a.sensor_width is not None or a.sensor_height is not None:
+            raise SystemExit("run_stream.py: --sensor_width / --sensor_height need --downsample")
+        return None
+    return (a.sensor_width or a.downsample * a.width, a.sensor_height or a.downsample * a.height)
 
 
 class SyntheticStream:
     """``--steps`` x ``--step_us`` microseconds of the synthetic stand-in stream, ``events_per_window`` events per 50 ms,
-    with absolute timestamps (and one synthetic frame every 50 ms for ``--use_image`` models)."""
+    with absolute timestamps (and one synthetic frame every 50 ms for ``--use_image`` models).  With ``--downsample`` the
+    events are drawn over the sensor, ``width`` / ``height`` stay the model's."""
 
     def __init__(self, a, t0=1 << 33):
         self.duration = max(1, a.steps * a.step_us)
         n = max(1, int(a.events_per_window * self.duration / 50000))
         gen = syn.edges_window if a.stream == "edges" else syn.uniform_window
-        x, y, t, p = gen(n, a.width, a.height, seed=7, window_us=self.duration, time_window=self.duration)
+        self.sensor_width, self.sensor_height = sensor_size(a) or (a.width, a.height)
+        x, y, t, p = gen(n, self.sensor_width, self.sensor_height, seed=7, window_us=self.duration, time_window=self.duration)
         self.x, self.y, self.p = x, y, p
         self.t = t.astype(np.int64) + np.int64(t0)
         self.t0, self.width, self.height = int(t0), a.width, a.height
@@ -66,7 +85,7 @@ def _frame(source, t, dev):
 
 def play(a, model, source, dev):
     """One detections list per step: ``[(t_step, detections of lane 0), ...]``."""
-    stream = EventStream(model, window_us=a.window_us)
+    stream = EventStream(model, window_us=a.window_us, downsample=a.downsample, sensor_size=sensor_size(a))
     t0, t1 = source.t_range()
     out, last_frame = [], None
     for t_step in range(int(t0) + a.step_us, int(t1) + 1, a.step_us):
