@@ -404,7 +404,9 @@ class StreamState:
         self.state = None
         self.status = torch.zeros((1,), dtype=torch.int32, device=self.device)
         self.lane_count = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
-        self.image = None                     # the last frame given (--use_image)
+        self.image = None                     # the frame in force, fp32 [B, 3, H, W] (--use_image)
+        self.frame_new = True                 # a frame has arrived since the stream's last frame body
+        self.frame_steps = self.held_steps = 0      # bodies run (forward_stream)
         # the counts come back with every step, into pinned memory; the host reads them only after a synchronisation it
         # makes anyway (the detections' read-back)
         self._host = torch.zeros((self.B,), dtype=torch.int32).pin_memory()
@@ -487,6 +489,22 @@ class StreamState:
         torch.cuda.current_stream(self.device).synchronize()       # (a count copy may still be on its way)
         self._host.zero_()
         self._known, self._since, self._fresh = np.zeros((self.B,), np.int64), 0, True
+        self.frame_steps = self.held_steps = 0
+        self.frame_new = True                 # the frame in force stays; the next step runs it through the branch again
+
+    def write_frames(self, frames, lanes, fx, fy, width, height, bgr):
+        """``dagr_stream_frame``: raw frames (uint8 [n, H_f, W_f, 3] on the device; rows may be padded) into the named
+        lanes (int32 [n] on the device) of the frame in force; the other lanes keep theirs (zeros before their first).
+        Counts as a new frame for the whole batch."""
+        if self.image is None or tuple(self.image.shape) != (self.B, 3, height, width):
+            self.image = torch.zeros((self.B, 3, height, width), dtype=torch.float32, device=self.device)
+        n, frame_h, frame_w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        img = self.image
+        _lib.check(_lib.lib().dagr_stream_frame(
+            _lib.ptr(frames), frames.stride(0), frames.stride(1), n, _lib.ptr(lanes), frame_w, frame_h, fx, fy, width, height,
+            1 if bgr else 0, _lib.ptr(img), self.B, img.stride(0), img.stride(1), img.stride(2), img.stride(3),
+            _lib.ptr(self.status), _lib.cur_stream(self.device)), "stream_frame")
+        self.frame_new = True
 
     def grow(self, cap):
         """Raw sets of ``cap`` events; the resident events are copied over on the device."""
@@ -584,6 +602,13 @@ class WindowEngine:
         # level-0 pooling on the graph builder's offset codes (bitmap coarse edges); False: the generic coarse-edge path
         self.fast_coarse_edges = True
         self._pool_accumulated = [False] * 4
+        # The stream (StreamState) whose last frame body left the maps ``_img_feats`` / ``_cnn_out`` now hold, or None:
+        # forward_stream runs the held body -- the window without the image branch -- only for that stream, and everything
+        # that rewrites the maps' memory or replaces them clears it.
+        self._held_for = None
+        self._hg = self._hg_out = self._wg_maps = None   # the held body's captured graph; the maps _wg's capture allocated
+        self._hg_post = (None, None)
+        self._hg_warm = 0
         # Latency mode (one window batch at a time, e.g. DAGR.forward): head scale 1 runs beside pool4 / layer5 / head scale
         # 2 and everything after pool1 is replayed as one HIP graph -- the host issues one launch instead of ~70.  When
         # several engines keep the GPU full on their own streams (bench.py's throughput rigs) both cost throughput
@@ -772,7 +797,17 @@ class WindowEngine:
         # the WHOLE window (image branch, graph build, level 0, tail, heads, decode) as one HIP graph: every launch is sized
         # for the engine's event capacity and bounded by counts that live in device memory
         self.window_graph = bool(on)
+        self._held_for = None                # the other mode's frame body keeps its maps elsewhere
         return self
+
+    def _drop_window_graph(self):
+        """Forget the captured window -- both bodies, and the maps the frame body's capture allocated -- and with it any
+        hold on a frame's maps: the next window runs eagerly (two warm-up runs) and is captured anew."""
+        self._wg = self._wg_out = None
+        self._wg_warm = 0
+        self._hg = self._hg_out = self._wg_maps = None
+        self._hg_warm = 0
+        self._held_for = None
 
     def _alloc_events(self, n):
         if n <= self.max_events:
@@ -798,8 +833,7 @@ class WindowEngine:
         self.in_feat = torch.zeros((n,), dtype=torch.float32, device=dev)
         self.in_batch = torch.zeros((n,), dtype=torch.int32, device=dev)
         self.n_dev = torch.zeros((1,), dtype=torch.int32, device=dev)
-        self._wg = self._wg_out = None       # captured on the old buffers
-        self._wg_warm = 0
+        self._drop_window_graph()            # captured on the old buffers
         self.rows_cap = n
         self._async_on = False
         self._app = None
@@ -1139,6 +1173,7 @@ class WindowEngine:
     def stage_image(self, image):
         """HookModule + CNNHead on PyTorch-ROCm (net.py:110, dagr.py:205-206)."""
         self._keep = []
+        self._held_for = None
         self._img_feats, self._cnn_out = self._image_branch(image)
 
     def image_async(self, image, stream=None):
@@ -1159,6 +1194,21 @@ class WindowEngine:
             ev.record(s)
         return feats, cnn_out, ev
 
+    def image_handle_from(self, feats, cnn_out):
+        """A handle for ``forward_raw(..., image_handle=h)`` / ``forward_detections`` from maps the caller holds (the
+        feature maps and CNN-head outputs of an image branch, e.g. clones of ``EventStream.held_maps()``), ready as of the
+        current stream."""
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        return list(feats), cnn_out, ev
+
+    def held_maps(self, st):
+        """The live ``(feats, cnn_out)`` tensors the stream ``st``'s next held step would read, or None when its next
+        step is a frame body (no hold, an invalidated hold, or a frame the branch has not seen yet)."""
+        if not self.use_image or self._held_for is not st or st.frame_new:
+            return None
+        return self._img_feats, self._cnn_out
+
     def _consume_image_handle(self, handle):
         feats, cnn_out, ev = handle
         cur = torch.cuda.current_stream(self.device)
@@ -1166,6 +1216,7 @@ class WindowEngine:
         for t in list(feats) + [o for v in cnn_out.values() for o in v]:
             t.record_stream(cur)   # allocated on the side stream, read on this one
         self._keep = []
+        self._held_for = None
         self._img_feats, self._cnn_out = feats, cnn_out
 
     def stage_l0_input(self, feat):
@@ -1510,23 +1561,23 @@ class WindowEngine:
                                            _lib.cur_stream(self.device)), "postprocess")
         self._post_fresh = True
 
-    def forward_detections(self, pos, feat, batch, image=None, append=False):
+    def forward_detections(self, pos, feat, batch, image=None, append=False, image_handle=None):
         """One window (``append``: one asynchronous update) through forward + post-processing: ``(det[B, A, 6], n_keep[B])``
         as ``model.utils.postprocess_device`` returns them, valid until the engine's next call.  In latency mode the
-        post-processing is part of the captured graph: no launch, and no host time, between the heads and the NMS."""
+        post-processing is part of the captured graph: no launch, and no host time, between the heads and the NMS.
+        ``image_handle``: as ``forward_raw`` takes it (the window then runs launch by launch)."""
         from .model.utils import postprocess_device
         key = (float(self.model.conf_threshold), float(self.model.nms_threshold))
         if key != self._post_key:                   # (re)capture with these thresholds
             self._post_key = key
-            self._wg = None
-            self._wg_warm = 0
+            self._drop_window_graph()
             self._graph = None
             self._graph_warm = 0
         self._post_fresh = False
         if append:
             out = self.forward_append(pos, feat, batch, static_out=True)
         else:
-            out = self.forward_raw(pos, feat, batch, image=image, static_out=True)
+            out = self.forward_raw(pos, feat, batch, image=image, image_handle=image_handle, static_out=True)
         if self._post_fresh:
             return self._det, self._n_keep
         return postprocess_device(out, self.num_classes, key[0], key[1], self.H, self.W)
@@ -1574,13 +1625,22 @@ class WindowEngine:
             trace["head_dense"] = [o.clone() for o in self._fused_dense]
         return out
 
-    def _forward_static(self):
+    def _forward_static(self, held=False):
         """One window on the engine's static input buffers with every launch sized for the event capacity and bounded by
-        the device-side counts: the body of the captured window graph (and of its eager warm-up runs)."""
+        the device-side counts: the body of the captured window graph (and of its eager warm-up runs).
+
+        ``held`` (``--use_image``): the held body -- the same launch sequence without the fork for the image branch.
+        Every ``_sample`` call and ``_heads_finish`` read the feature maps and CNN-head outputs the last frame body left
+        in ``_img_feats`` / ``_cnn_out``; it waits on none of that body's events (they belong to another capture, and
+        replays on one stream are ordered)."""
         self._dev_mode = True
         try:
-            self._cnn_out = None
-            if self.use_image:
+            if held:
+                self._feat_ready = self._cnn_ready = None
+                self.stage_graph(self.in_pos, self.in_batch, self.in_feat)
+            elif self.use_image:
+                self._held_for = None                 # the maps are rewritten: whoever runs this body takes the hold anew
+                self._cnn_out = None
                 # the graph build needs nothing from the frame: it runs beside the image branch (a fork inside the captured
                 # window; the level-0 input rows are the first stage that needs both)
                 cur = torch.cuda.current_stream(self.device)
@@ -1618,6 +1678,7 @@ class WindowEngine:
                     self._cnn_ready.record(s_img)
                 cur.wait_event(join)
             else:
+                self._cnn_out = None
                 self.stage_graph(self.in_pos, self.in_batch, self.in_feat)
             self.stage_l0_input(self.in_feat)
             self.stage_l0_conv1()
@@ -1628,6 +1689,48 @@ class WindowEngine:
             return out
         finally:
             self._dev_mode = False
+
+    def _capture_window(self):
+        """Capture the frame body (the full window) as ``_wg`` and replay it once; the feature maps and CNN-head outputs its
+        capture allocated stay referenced for as long as either captured body lives (the held body reads them)."""
+        cg = torch.cuda.CUDAGraph()
+        with _capture(cg):
+            out = self._forward_static()
+        self._wg, self._wg_out, self._wg_post = cg, out, (self._det, self._n_keep)
+        self._wg_maps = (self._img_feats, self._cnn_out) if self.use_image else None
+        cg.replay()
+        return out
+
+    def _replay_window(self):
+        """Replay the captured frame body: its outputs, its post-processing buffers and (``--use_image``) its maps are the
+        engine's current ones again."""
+        self._wg.replay()
+        self._det, self._n_keep = self._wg_post
+        if self._wg_maps is not None:
+            self._img_feats, self._cnn_out = self._wg_maps
+        return self._wg_out
+
+    def _held_window(self):
+        """The held body in latency mode: a second captured graph beside ``_wg``, on the maps ``_wg``'s capture allocated
+        and with output and post-processing buffers of its own.  It is captured only while ``_wg`` exists (after one eager
+        run, as every capture here); until then -- the frame body's own warm-up runs -- the held body runs launch by
+        launch on the maps the last eager frame body left."""
+        if self._wg is None or self._wg_maps is None or self._img_feats is not self._wg_maps[0]:
+            return self._forward_static(held=True)
+        if self._hg is None:
+            if self._hg_warm < 1:
+                self._hg_warm += 1
+                return self._forward_static(held=True)
+            cg = torch.cuda.CUDAGraph()
+            with _capture(cg):
+                out = self._forward_static(held=True)
+            self._hg, self._hg_out, self._hg_post = cg, out, (self._det, self._n_keep)
+            cg.replay()
+            return out
+        self._hg.replay()
+        self._det, self._n_keep = self._hg_post
+        self._post_fresh = True
+        return self._hg_out
 
     def _forward_window_graph(self, pos, feat, batch, image, static_out=False):
         """Latency mode: the caller's window is staged into the static buffers by ONE launch (which also writes the event
@@ -1645,26 +1748,20 @@ class WindowEngine:
         _lib.check(L.dagr_stage_window(ctypes.byref(g.desc), P(g.workspace), P(pos), P(feat), P(batch),
                                        1 if batch.dtype == torch.int64 else 0, N, P(self.in_pos), P(self.in_feat),
                                        P(self.in_batch), P(self.n_dev), _lib.cur_stream(self.device)), "stage_window")
+        self._held_for = None                        # this window's frame body rewrites the maps a stream may hold
         if self.use_image:
             if self.in_image is None or self.in_image.shape != image.shape:
                 self.in_image = torch.empty(tuple(image.shape), dtype=torch.float32, device=self.device)
-                self._wg = None
-                self._wg_warm = 0
+                self._drop_window_graph()
             self.in_image.copy_(image)
         if self._wg is None:
             if self._wg_warm < 2:                    # lazy one-time work (kernel attributes, MIOpen's search) stays eager
                 self._wg_warm += 1
                 out = self._forward_static()
             else:
-                g = torch.cuda.CUDAGraph()
-                with _capture(g):
-                    out = self._forward_static()
-                self._wg, self._wg_out, self._wg_post = g, out, (self._det, self._n_keep)
-                g.replay()
+                out = self._capture_window()
         else:
-            self._wg.replay()
-            out = self._wg_out
-            self._det, self._n_keep = self._wg_post
+            out = self._replay_window()
             self._post_fresh = self._post_key is not None
         # the resident window (what check_status / an asynchronous update / the probes look at): the actual count
         self._N = N
@@ -1682,7 +1779,13 @@ class WindowEngine:
         ``st`` -- through ``dagr_stream_downsample`` first when the stream carries raw sensor events (``st.front``) --; two launches write the next window into the static input buffers and its count to device memory, and
         the window runs on them -- the captured graph in latency mode, the same body launch by launch otherwise.  No host
         synchronisation: the host knows an upper bound of the window's size only (``st.bound()``), which is what the
-        buffers are sized by.  Returns ``(out, (det, n_keep))``, both valid until the engine's next call."""
+        buffers are sized by.  Returns ``(out, (det, n_keep))``, both valid until the engine's next call.
+
+        ``--use_image``: the window has two bodies.  The frame body runs the image branch on the stream's frame
+        (``st.image``; ``image=`` replaces it) and leaves its feature maps and CNN-head outputs; the held body samples
+        those and skips the branch.  A step runs the held body only if the stream has had no new frame since its last
+        frame body and nothing has rewritten the maps since (``_held_for``); ``st.frame_steps`` / ``st.held_steps`` count
+        the bodies.  Either way the step returns what ``reset=True`` gives on the window with the frame in force."""
         from .model.utils import postprocess_device
         if not self.l0_tiles or self.no_events:
             raise RuntimeError("forward_stream runs the captured window's body: it needs the tiled level-0 conv "
@@ -1697,21 +1800,26 @@ class WindowEngine:
         if self.use_image:
             if image is not None:
                 st.image = image.to(device=self.device, dtype=torch.float32).clone()
+                st.frame_new = True                  # (contents are not compared)
             if st.image is None:
-                raise RuntimeError("model was built with --use_image: the stream needs a frame (image=) on its first step")
+                raise RuntimeError("model was built with --use_image: the stream needs a frame (image= or frame=) on its "
+                                   "first step")
             if self.in_image is None or self.in_image.shape != st.image.shape:
                 self.in_image = torch.empty(tuple(st.image.shape), dtype=torch.float32, device=self.device)
-                self._wg = None
-                self._wg_warm = 0
-            self.in_image.copy_(st.image)
+                self._drop_window_graph()
         key = (float(self.model.conf_threshold), float(self.model.nms_threshold))
         if key != self._post_key:                   # (re)capture with these thresholds
             self._post_key = key
-            self._wg = None
-            self._wg_warm = 0
+            self._drop_window_graph()
             self._graph = None
             self._graph_warm = 0
         self._post_fresh = False
+        # Which body this step runs: the held body if and only if the stream has had no new frame since its last frame body
+        # AND nothing has rewritten or replaced the maps since (_held_for: cleared by every other frame body, capture,
+        # re-allocation and threshold change).  In doubt the frame body runs: that is only a needless image branch.
+        held = self.use_image and self._held_for is st and not st.frame_new
+        if self.use_image and not held:
+            self.in_image.copy_(st.image)
         g = self.graph
         if st.front is None:
             _lib.check(L.dagr_stream_stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(xy), P(t), P(p),
@@ -1730,22 +1838,24 @@ class WindowEngine:
                                                P(st.lane_count), P(st.status), _lib.cur_stream(self.device)),
                        "stream_stage_dev")
         if not self.window_graph:                    # throughput mode: the body of the captured window, launch by launch
-            out = self._forward_static()
+            out = self._forward_static(held)
+        elif held:
+            out = self._held_window()
         elif self._wg is None:
             if self._wg_warm < 2:
                 self._wg_warm += 1
                 out = self._forward_static()
             else:
-                cg = torch.cuda.CUDAGraph()
-                with _capture(cg):
-                    out = self._forward_static()
-                self._wg, self._wg_out, self._wg_post = cg, out, (self._det, self._n_keep)
-                cg.replay()
+                out = self._capture_window()
         else:
-            self._wg.replay()
-            out = self._wg_out
-            self._det, self._n_keep = self._wg_post
+            out = self._replay_window()
             self._post_fresh = True
+        if held:
+            st.held_steps += 1
+        else:
+            st.frame_steps += 1
+            if self.use_image:                       # the maps are this stream's frame now
+                self._held_for, st.frame_new = st, False
         st._pushed_now(n_new)
         # the resident window is this step's, but its size is on the device: nothing may attach to it (can_append) until
         # the count has been read (stream_counted)

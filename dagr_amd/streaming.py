@@ -36,6 +36,11 @@ the integrate-and-fire loop of ``scripts/downsample_events.py:91-124`` and cut t
   whole cell; a raw event outside ``[0, W_in) x [0, H_in)`` is malformed (status bit of value 16);
 * what is left is pushed as above, but the clock is the sensor's: the order checks run on the raw arrays, and the lane's
   newest event -- ``t_last``, and ``t_ref`` without ``t_now`` -- is its newest RAW event.
+
+Frames (``--use_image`` models): every lane has a frame in force, the last one a step gave it -- as the model's image
+(``image=``, fp32 [B, 3, H, W]) or as a raw sensor frame (``frame=``, uint8 [H_f, W_f, 3], which ``dagr_stream_frame``
+prepares on the device; ``frame_definition`` below states what that is).  A step's result is what ``model(..., reset=True)``
+returns on the window with the frames in force, whether the step ran the image branch or sampled the maps it held.
 """
 import numpy as np
 
@@ -45,7 +50,8 @@ STATUS_BITS = ((1, "a timestamp goes backwards inside a lane (within a push or a
                (2, "t_now is behind the lane's newest event or behind its previous t_ref"),
                (4, "survivors plus new events exceed the stream's capacity"),
                (8, "batch is not sorted or is outside [0, batch_size)"),
-               (16, "a raw event is outside the sensor (downsampling streams)"))
+               (16, "a raw event is outside the sensor (downsampling streams)"),
+               (32, "a frame's lane is outside [0, batch_size)"))
 
 
 def _factors(downsample, width, height, sensor_size, who):
@@ -61,6 +67,48 @@ def _factors(downsample, width, height, sensor_size, who):
     if w_in > 32767 or h_in > 32767:
         raise ValueError(f"{who}: sensor_size {w_in} x {h_in} does not fit the int16 pixel coordinates")
     return fx, fy, w_in, h_in
+
+
+def frame_definition(raw, fx, fy, W, H, bgr=False):
+    """The model's image of one raw sensor frame (``uint8 [H_f, W_f, 3]``), stated once: ``DSEC.preprocess_image`` plus
+    ``format_data`` for a top-left crop.  Rows ``[0, fy * H)`` and columns ``[0, fx * W)`` of the frame go through
+    ``_resize_area_free`` to ``W x H`` (torch's bicubic interpolation, rounded back to uint8), the channels are reversed if
+    ``bgr``, and ``.float() / 255.0`` gives the result, a torch ``fp32 [3, H, W]`` on the CPU.  The yardstick of
+    ``dagr_stream_frame`` (``EventStream.step(frame=...)``); nothing on the device path calls it."""
+    from .data.dsec_data import _resize_area_free
+    raw = np.asarray(raw)
+    if raw.dtype != np.uint8 or raw.ndim != 3 or raw.shape[2] != 3:
+        raise ValueError(f"frame_definition: a frame is uint8 [H_f, W_f, 3], got {raw.dtype} {raw.shape}")
+    if raw.shape[0] < fy * H or raw.shape[1] < fx * W:
+        raise ValueError(f"frame_definition: the frame {raw.shape[1]} x {raw.shape[0]} is smaller than the crop "
+                         f"{fx * W} x {fy * H}")
+    small = _resize_area_free(raw[:fy * H, :fx * W], W, H)[0]           # uint8 [3, H, W]
+    if bgr:
+        small = small.flip(0)
+    return small.float() / 255.0
+
+
+def frame_closed_form(raw, fx, fy, W, H, bgr=False):
+    """``frame_definition`` in closed form, in numpy integers: what ``dagr_stream_frame`` computes.  A factor ``f`` has
+    four taps per axis at ``base - 1 .. base + 2``, ``base = f * d + (f - 1) // 2``, clamped to the CROP, with the weights
+    ``(-3, 19, 19, -3) / 32`` for even ``f`` and ``(0, 1, 0, 0)`` for odd ``f``; the 16-tap sum is an exact integer over
+    1024, rounded half to even, clamped to ``[0, 255]`` and divided by ``255`` in fp32.  Returns ``(image fp32 [3, H, W],
+    sums int64 [H, W, 3])`` -- the sums (over 1024, before rounding) let a test see which ties and overshoots a frame has."""
+    raw = np.asarray(raw)
+
+    def taps(f, n):
+        base = f * np.arange(n, dtype=np.int64) + (f - 1) // 2
+        idx = np.clip(base[:, None] + np.arange(-1, 3, dtype=np.int64)[None, :], 0, f * n - 1)
+        return idx, np.array([-3, 19, 19, -3] if f % 2 == 0 else [0, 32, 0, 0], np.int64)
+    (iy, wy), (ix, wx) = taps(fy, H), taps(fx, W)
+    crop = raw[:fy * H, :fx * W].astype(np.int64)
+    rows = (crop[iy] * wy[None, :, None, None]).sum(1)                  # [H, fx * W, 3]
+    sums = (rows[:, ix] * wx[None, None, :, None]).sum(2)               # [H, W, 3]
+    q, r = sums >> 10, sums & 1023
+    q = np.clip(q + ((r > 512) | ((r == 512) & (q & 1 == 1))), 0, 255)
+    if bgr:
+        q = q[..., ::-1]
+    return np.ascontiguousarray(q.transpose(2, 0, 1)).astype(np.float32) / np.float32(255.0), sums
 
 
 class StreamDefinition:
@@ -169,9 +217,20 @@ class EventStream:
     ``downsample`` (``f`` or ``(fx, fy)``) and ``sensor_size`` (``(W_in, H_in)``, default ``(fx * W, fy * H)``): the
     pushes carry raw sensor events, which ``dagr_stream_downsample`` turns into the model's on the device (module
     docstring); ``change_maps()`` reads the integrators back.
+    ``frame_size`` (``(W_f, H_f)``) and ``frame_bgr``: the steps may carry raw sensor frames (``frame=``), which
+    ``dagr_stream_frame`` turns into the model's image on the device (``frame_definition``) with the stream's
+    ``downsample`` factors, or 1 without ``downsample``.
+
+    ``--use_image`` models: the image branch runs once per frame.  A step runs the frame body (image branch included)
+    when it brings a frame (``image=`` or ``frame=``; contents are not compared), on the stream's first step, and whenever
+    something has rewritten the memory the frame's maps live in since the stream's last frame body -- any other window on
+    the same engine (a plain ``model(...)`` / ``forward_detections`` call, another stream), a buffer that grew, a change of
+    thresholds or of the frame's shape, a switch between latency and throughput mode.  Every other step runs the held
+    body, which samples the maps the last frame body left.  The engine tracks this itself; ``frame_steps`` /
+    ``held_steps`` count the bodies run, and the result is what ``reset=True`` gives with the frame in force either way.
     """
 
-    def __init__(self, model, window_us=50000, downsample=None, sensor_size=None):
+    def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False):
         import torch
         self.model = model
         self.window_us = int(window_us)
@@ -204,6 +263,57 @@ class EventStream:
         elif sensor_size is not None:
             raise ValueError("EventStream: sensor_size is given without downsample")
         self._zeros = None
+        self.outputs = None      # the last step's decoded head outputs [B, A, 5 + classes], valid until the engine's next call
+        self._frame = None
+        if frame_size is not None:
+            fx, fy = self.state.front[:2] if self.state.front is not None else (1, 1)
+            w_f, h_f = int(frame_size[0]), int(frame_size[1])
+            if w_f < fx * eng.W or h_f < fy * eng.H:
+                raise ValueError(f"EventStream: frame_size {w_f} x {h_f} is smaller than the crop {fx * eng.W} x {fy * eng.H} "
+                                 f"(downsample {fx} x {fy} over the model's {eng.W} x {eng.H})")
+            self._frame = (w_f, h_f, fx, fy, eng.W, eng.H, bool(frame_bgr))
+        self._lanes_all = None
+
+    # ------------------------------------------------------------------------------------ frames
+    frame_steps = property(lambda self: self.state.frame_steps, doc="steps that ran the frame body (the full window)")
+    held_steps = property(lambda self: self.state.held_steps, doc="steps that ran the held body (no image branch)")
+
+    def held_maps(self):
+        """The live ``(feats, cnn_out)`` tensors of the frame in force -- what the next held step samples -- or None when
+        the next step runs the frame body whatever it brings."""
+        return self.model.engine().held_maps(self.state)
+
+    def _push_frame(self, frame, frame_lanes):
+        """``frame=`` of a step: raw uint8 frames into the named lanes of the stream's frame buffer, on the device."""
+        import torch
+        if not self.model.engine().use_image:
+            raise ValueError("EventStream: frame= is given to an events-only model (no --use_image): it reads no frame")
+        if self._frame is None:
+            raise ValueError("EventStream: frame= needs a stream built with frame_size=(W_f, H_f)")
+        w_f, h_f, fx, fy, width, height, bgr = self._frame
+        if not torch.is_tensor(frame):
+            frame = torch.from_numpy(np.ascontiguousarray(np.asarray(frame)))
+        if frame.dim() == 3:
+            frame = frame[None]
+        if frame.dtype != torch.uint8 or frame.dim() != 4 or tuple(frame.shape[1:]) != (h_f, w_f, 3):
+            raise ValueError(f"EventStream: frame= is uint8 [n, {h_f}, {w_f}, 3] or [{h_f}, {w_f}, 3] (frame_size), got "
+                             f"{frame.dtype} {tuple(frame.shape)}")
+        frame = frame.to(self.device)
+        if frame.stride(3) != 1 or frame.stride(2) != 3 or frame.stride(1) < 3 * w_f or \
+                (frame.shape[0] > 1 and frame.stride(0) < frame.stride(1) * h_f):
+            frame = frame.contiguous()                  # (padded rows are taken as they are)
+        n = int(frame.shape[0])
+        if frame_lanes is None:
+            if n != self.B:
+                raise ValueError(f"EventStream: frame= holds {n} frames for {self.B} lanes; name their lanes (frame_lanes=)")
+            if self._lanes_all is None:
+                self._lanes_all = torch.arange(self.B, dtype=torch.int32, device=self.device)
+            lanes = self._lanes_all
+        else:
+            lanes = torch.as_tensor(frame_lanes).to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+            if lanes.numel() != n:
+                raise ValueError(f"EventStream: frame_lanes names {lanes.numel()} lanes for {n} frames")
+        self.state.write_frames(frame, lanes, fx, fy, width, height, bgr)
 
     # ------------------------------------------------------------------------------------ inputs
     def _upload(self, xy, t, p, batch, t_now):
@@ -247,10 +357,19 @@ class EventStream:
                 d[o_b:o_p].view(torch.int32), None if now is None else d[o_now:].view(torch.int64))
 
     # ------------------------------------------------------------------------------------ steps
-    def step_device(self, xy, t, p, batch=None, t_now=None, image=None):
+    def step_device(self, xy, t, p, batch=None, t_now=None, image=None, frame=None, frame_lanes=None):
         """One step without a host synchronisation: ``(det[B, A, 6], n_keep[B])`` as ``forward_detections`` returns them,
-        valid until the engine's next call."""
+        valid until the engine's next call.  ``image``: the model's image batch fp32 [B, 3, H, W]; ``frame``: raw sensor
+        frames uint8 ``[n, H_f, W_f, 3]`` or ``[H_f, W_f, 3]`` (host or device) for the lanes ``frame_lanes`` (default: all
+        lanes in order) -- the other lanes keep their frame; either makes the step a frame step for the whole batch."""
         import torch
+        if frame is not None:
+            if image is not None:
+                raise ValueError("EventStream: image= and frame= are both given; a step takes the model's image batch OR raw "
+                                 "frames")
+            self._push_frame(frame, frame_lanes)
+        elif frame_lanes is not None:
+            raise ValueError("EventStream: frame_lanes= is given without frame=")
         if t_now is not None and not torch.is_tensor(t_now) and np.ndim(t_now) == 0:
             t_now = np.full((self.B,), int(t_now), np.int64)
         elif torch.is_tensor(t_now) and t_now.numel() == 1 and self.B > 1:
@@ -260,14 +379,15 @@ class EventStream:
             raise ValueError(f"EventStream: t_now needs one instant per lane ({self.B})")
         eng = self.model.engine()
         with torch.no_grad():
-            _, det = eng.forward_stream(self.state, xy, t, p, batch, t_now=t_now, image=image)
+            self.outputs, det = eng.forward_stream(self.state, xy, t, p, batch, t_now=t_now, image=image)
         self.model._window = None            # a reset=False call then starts from a window of its own
         return det
 
-    def step(self, xy, t, p, batch=None, t_now=None, image=None):
+    def step(self, xy, t, p, batch=None, t_now=None, image=None, frame=None, frame_lanes=None):
         """One step: the detections list ``model(x, reset=True)[0]`` returns for the stream's window."""
         from .model.utils import detections_from_device
-        det, n_keep = self.step_device(xy, t, p, batch=batch, t_now=t_now, image=image)
+        det, n_keep = self.step_device(xy, t, p, batch=batch, t_now=t_now, image=image, frame=frame,
+                                       frame_lanes=frame_lanes)
         detections = detections_from_device(det, n_keep)        # the step's one synchronisation
         self.model.engine().stream_counted(self.state)          # the counts came back with it
         if self.model.check_device_status:
@@ -287,7 +407,8 @@ class EventStream:
         return self.state.change_maps()
 
     def reset(self):
-        """Empty the stream: no resident events, no reference instants, zero change maps, a clear status word."""
+        """Empty the stream: no resident events, no reference instants, zero change maps, a clear status word, zero step
+        counters.  The frame in force stays, and the next step runs it through the image branch again."""
         self.state.reset()
 
     def check_status(self):

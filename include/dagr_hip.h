@@ -174,7 +174,8 @@ int dagr_stage_window(const dagr_graph_desc *desc, void *workspace, const float 
  *   bit 1: t_ref is behind the lane's newest event or behind its previous t_ref;
  *   bit 2: survivors plus new events exceed `capacity`;
  *   bit 3: batch_new is not sorted or is outside [0, B);
- *   bit 4: (dagr_stream_downsample) a raw event outside the sensor.
+ *   bit 4: (dagr_stream_downsample) a raw event outside the sensor;
+ *   bit 5: (dagr_stream_frame) a frame's lane is outside [0, B).
  * Events outside the sensor raise the builder's own flag (dagr_graph_status).
  * DAGR_ERR_INVALID_ARG before any launch: window_us <= 0, window_us > desc.time_window, capacity < n_new,
  * capacity > desc.max_events, B != desc.batch_size, NULL pointers.
@@ -232,6 +233,29 @@ int dagr_stream_stage_dev(const dagr_graph_desc *desc, void *workspace, void *st
                           int32_t clock_is_int64, int64_t n_clock, const int64_t *t_now /* [B] or NULL */,
                           int64_t window_us, float *pos_out, float *feat_out, int32_t *batch_out, int32_t *n_dev,
                           int32_t *lane_count /* [B] */, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------ *
+ * Event stream frames: raw sensor frames, prepared on the device
+ *   DSEC.preprocess_image (crop, bicubic shrink by a whole factor, back to uint8) and format_data's `/ 255` in one launch,
+ *   for n frames at once: rows [0, fy * height) and columns [0, fx * width) of every uint8 [frame_h, frame_w, 3] frame are
+ *   shrunk to width x height, the channels reversed if `bgr`, and written as fp32 in [0, 1] into lane lanes[k] of `out`.
+ *
+ * Per axis with factor f, output pixel d reads the four taps base - 1 .. base + 2, base = f * d + (f - 1) / 2, clamped to the
+ * CROP (not to the frame), with the weights (-3, 19, 19, -3) / 32 for even f and (0, 1, 0, 0) for odd f: torch's bicubic
+ * interpolation (A = -0.75, align_corners off) at these factors.  The 16-tap sum is an exact integer over 1024; it is
+ * rounded half to even, clamped to [0, 255] and divided by 255.0f (a correctly rounded division).
+ *
+ * frames: frame k starts at frames + k * frame_stride, its rows are row_stride >= 3 * frame_w bytes apart, a pixel is three
+ * consecutive bytes.  lanes int32[n] in device memory.  out: element (b, c, y, x) at b * stride_b + c * stride_c +
+ * y * stride_y + x * stride_x floats, b in [0, B).  A lane outside [0, B) writes nothing and raises bit 5 (value 32) of
+ * `status`, the stream's status word.  One thread per output pixel; n <= 65535, height <= 65535, fx * width and
+ * fy * height <= 32767.  DAGR_ERR_INVALID_ARG before the launch: a frame smaller than the crop, strides smaller than the
+ * frame, sizes out of range, NULL pointers.
+ * ------------------------------------------------------------------------ */
+int dagr_stream_frame(const uint8_t *frames, int64_t frame_stride, int64_t row_stride, int32_t n, const int32_t *lanes,
+                      int32_t frame_w, int32_t frame_h, int32_t fx, int32_t fy, int32_t width, int32_t height, int32_t bgr,
+                      float *out, int32_t B, int64_t stride_b, int64_t stride_c, int64_t stride_y, int64_t stride_x,
+                      int32_t *status, void *stream);
 
 /* The neighbour search alone, again, on the pixel index the last dagr_graph_build_window left in `workspace` (same N):
  * rewrites nbr_src / nbr_code / deg and the edge count.  For measurement (bench.py times the search kernels on their own

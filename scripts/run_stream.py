@@ -12,7 +12,12 @@ files is not part of this script.
 
 ``--downsample F``: the source delivers RAW sensor events, in the pixels of a ``--sensor_width`` x ``--sensor_height``
 sensor (default ``F * width`` x ``F * height``), and the stream downsamples them ``F`` x ``F`` on the device, as
-``scripts/downsample_events.py`` does for the ``events_2x`` files the models read."""
+``scripts/downsample_events.py`` does for the ``events_2x`` files the models read.
+
+``--raw_frames`` (``--use_image`` models): the source's ``image(i)`` is a sensor-size BGR uint8 frame and goes to the stream
+as it is (``frame=``); the stream crops, shrinks and scales it on the device (``dagr.streaming.frame_definition``) with the
+``--downsample`` factor, or 1 without.  A frame is handed over when the source's frame index changes; every step between
+two frames samples the maps the image branch left for the last one."""
 import time
 import types
 
@@ -36,6 +41,8 @@ def stream_options(p):
                    "by this factor on the device")
     g.add_argument("--sensor_width", type=int, default=None, help="sensor width with --downsample (default F * width)")
     g.add_argument("--sensor_height", type=int, default=None, help="sensor height with --downsample (default F * height)")
+    g.add_argument("--raw_frames", action="store_true", help="the source's frames are sensor-size BGR uint8 frames: prepare "
+                   "them on the device (crop, shrink by the --downsample factor, / 255)")
 
 
 def sensor_size(a):
@@ -62,6 +69,8 @@ class SyntheticStream:
         self.t = t.astype(np.int64) + np.int64(t0)
         self.t0, self.width, self.height = int(t0), a.width, a.height
         self.image_timestamps = np.arange(self.t0, self.t0 + self.duration + 1, 50000, dtype=np.int64)
+        raw = getattr(a, "raw_frames", False)         # frames as the sensor delivers them
+        self.frame_width, self.frame_height = (self.sensor_width, self.sensor_height) if raw else (a.width, a.height)
 
     def t_range(self):
         return self.t0, self.t0 + self.duration
@@ -72,33 +81,50 @@ class SyntheticStream:
 
     def image(self, i):
         rng = np.random.Generator(np.random.PCG64(1000 + int(i)))
-        return rng.integers(0, 256, (self.height, self.width, 3), dtype=np.uint8)
+        return rng.integers(0, 256, (self.frame_height, self.frame_width, 3), dtype=np.uint8)
+
+
+def _frame_index(source, t):
+    """The index of the newest frame at or before ``t``."""
+    ts = np.asarray(source.image_timestamps)
+    return int(np.clip(np.searchsorted(ts, t, side="right") - 1, 0, len(ts) - 1))
 
 
 def _frame(source, t, dev):
     """The newest frame at or before ``t`` as the model's image batch (fp32 [1,3,H,W] in [0,1], RGB)."""
-    ts = np.asarray(source.image_timestamps)
-    i = int(np.clip(np.searchsorted(ts, t, side="right") - 1, 0, len(ts) - 1))
+    i = _frame_index(source, t)
     img = np.ascontiguousarray(np.asarray(source.image(i), dtype=np.uint8)[..., ::-1])
     return i, torch.from_numpy(img).to(dev).permute(2, 0, 1).unsqueeze(0).float() / 255.0
 
 
 def play(a, model, source, dev):
     """One detections list per step: ``[(t_step, detections of lane 0), ...]``."""
-    stream = EventStream(model, window_us=a.window_us, downsample=a.downsample, sensor_size=sensor_size(a))
+    use_image = bool(model.backbone.use_image)
+    raw_size = None
+    if getattr(a, "raw_frames", False) and use_image:
+        h_f, w_f = np.asarray(source.image(0)).shape[:2]
+        raw_size = (int(w_f), int(h_f))
+    stream = EventStream(model, window_us=a.window_us, downsample=a.downsample, sensor_size=sensor_size(a),
+                         frame_size=raw_size, frame_bgr=True)
     t0, t1 = source.t_range()
     out, last_frame = [], None
     for t_step in range(int(t0) + a.step_us, int(t1) + 1, a.step_us):
         ev = source.events(t_step - a.step_us, t_step)
         xy = np.stack([np.asarray(ev["x"], np.int16), np.asarray(ev["y"], np.int16)], -1)
-        image = None
-        if model.backbone.use_image:
+        image = raw = None
+        if raw_size is not None:
+            i = _frame_index(source, t_step)
+            if i != last_frame:
+                raw, last_frame = np.asarray(source.image(i), dtype=np.uint8), i
+        elif use_image:
             i, frame = _frame(source, t_step, dev)
             if i != last_frame:
                 image, last_frame = frame, i
         # every event of the step is older than t_step, the instant the detections are for
-        det = stream.step(xy, np.asarray(ev["t"], np.int64), np.asarray(ev["p"], np.int8), t_now=t_step, image=image)
+        det = stream.step(xy, np.asarray(ev["t"], np.int64), np.asarray(ev["p"], np.int8), t_now=t_step, image=image,
+                          frame=raw)
         out.append((t_step, det[0]))
+    a.stream_steps = (stream.frame_steps, stream.held_steps)      # (frame bodies, held bodies) of the run
     return out
 
 
@@ -132,7 +158,8 @@ def main(argv=None, model_factory=None, source=None):
         path = out_dir / f"detections_{a.sequence}.npy"
         np.save(path, rec)
         print(f"{len(steps)} steps of {a.step_us} us on a {a.window_us} us window in {seconds:.2f} s "
-              f"({1e3 * seconds / max(1, len(steps)):.2f} ms per step) -> {path}: {len(rec)} detections")
+              f"({1e3 * seconds / max(1, len(steps)):.2f} ms per step; {a.stream_steps[0]} with the full window, "
+              f"{a.stream_steps[1]} on held image maps) -> {path}: {len(rec)} detections")
     C.finish(world)
     return path
 
