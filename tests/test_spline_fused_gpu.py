@@ -1,12 +1,12 @@
 """Kernel-level parity of the pooled-level SplineConv entry points on random CSR graphs:
-dagr_spline_conv_fused and dagr_spline_tap_aggregate + dagr_gemm_bias_act against a float64 evaluation
-built on the oracle's torch_spline_conv basis (oracle/ops.py:spline_basis).  Tolerance 1e-4 relative to the
-output scale (fp32 accumulation over K <= 6700 terms)."""
+dagr_spline_conv_fused and dagr_spline_tap_aggregate + dagr_gemm_bias_act against the float64 evaluation
+of tests/spline_refs.py (pinned to the oracle's torch_spline_conv basis by tests/test_spline_refs_cpu.py).  Tolerance 1e-4
+relative to the output scale (fp32 accumulation over K <= 6700 terms)."""
 import numpy as np
 import pytest
 import torch
 
-from oracle import ops as oo
+from tests.spline_refs import conv_csr as _reference
 
 pytestmark = pytest.mark.gpu
 
@@ -17,25 +17,6 @@ def _pack_wq(Wm):
     Wp = torch.zeros((K16, N16), dtype=Wm.dtype, device=Wm.device)
     Wp[:K, :N] = Wm
     return Wp.view(K16 // 16, 4, 4, N16 // 16, 16).permute(3, 0, 2, 4, 1).contiguous()
-
-
-def _reference(rowptr, col, code, x, xs, Wm, bias, relu, r, den):
-    T = len(rowptr) - 1
-    cin = x.shape[1]
-    dst = np.repeat(np.arange(T), np.diff(rowptr))
-    ix, iy = code & 0xFFFF, code >> 16
-    pseudo = torch.stack([torch.from_numpy((ix - r).astype(np.float32)) / np.float32(den[0]) + 0.5,
-                          torch.from_numpy((iy - r).astype(np.float32)) / np.float32(den[1]) + 0.5], 1)
-    basis, index = oo.spline_basis(pseudo)
-    A = np.zeros((T, 25, cin), dtype=np.float64)
-    xj = x[col].astype(np.float64)
-    for s in range(4):
-        np.add.at(A, (dst, index[:, s].numpy()), basis[:, s].numpy().astype(np.float64)[:, None] * xj)
-    full = [A.reshape(T, 25 * cin), x.astype(np.float64)]
-    if xs is not None:
-        full.append(xs.astype(np.float64))
-    out = np.concatenate(full, 1) @ Wm.astype(np.float64) + bias.astype(np.float64)
-    return np.maximum(out, 0) if relu else out
 
 
 CASES = [  # T, cin, cskip, N, max_deg, relu
