@@ -1125,6 +1125,9 @@ __device__ __forceinline__ int first_later(const int64_t *__restrict__ t, int n,
 // The clock (t_clock / batch_clock, n_clock events) is what the lanes' newest timestamps and the order check come from:
 // the new events themselves, or -- dagr_stream_stage_dev -- the raw events they were selected from.  n_new_dev, when given,
 // holds the number of new events (at most n_new).
+// max_lane > 0 (the capped entries) adds the count rule: a lane keeps the newest max_lane events of what the time rule
+// left, so the oldest go -- survivors first, then the front of the push -- and lane_dropped[b] grows by their number.  With
+// B * max_lane <= cap the prefix sum below then never clamps, and a push may be larger than cap.
 template <typename BatchT, typename ClockT>
 __global__ __launch_bounds__(kStreamLanes) void k_stream_plan(StreamState st, int B, int cap,
                                                               const BatchT *__restrict__ batch_new,
@@ -1133,6 +1136,7 @@ __global__ __launch_bounds__(kStreamLanes) void k_stream_plan(StreamState st, in
                                                               const ClockT *__restrict__ batch_clock,
                                                               const int64_t *__restrict__ t_clock, int n_clock,
                                                               const int64_t *__restrict__ t_now, int64_t window_us,
+                                                              int max_lane, int64_t *__restrict__ lane_dropped,
                                                               int32_t *__restrict__ n_dev,
                                                               int32_t *__restrict__ lane_count,
                                                               int32_t *__restrict__ status) {
@@ -1164,9 +1168,18 @@ __global__ __launch_bounds__(kStreamLanes) void k_stream_plan(StreamState st, in
         const int cut_new = first_later(t_new + ns, ne - ns, thr);
         first_new = ns + cut_new;
         keep_new = ne - ns - cut_new;
+        if (max_lane > 0) {
+            const int64_t drop = (int64_t)keep_old + keep_new - max_lane;       // (a push may be far larger than cap)
+            if (drop > 0) {
+                const int d_old = (int)min(drop, (int64_t)keep_old), d_new = (int)(drop - d_old);
+                first_old += d_old; keep_old -= d_old;
+                first_new += d_new; keep_new -= d_new;
+                if (lane_dropped) lane_dropped[b] += drop;
+            }
+        }
         st.t_ref[b] = ref;
         st.t_last[b] = newest;
-        s_cnt[b] = keep_old + keep_new;      // <= 2 cap < 2^26
+        s_cnt[b] = keep_old + keep_new;      // <= 2 cap < 2^26, or <= max_lane
     }
     __syncthreads();
     if (b == 0) {       // at most 127 lanes: a serial prefix sum, clamped to the capacity as it goes
@@ -1543,23 +1556,26 @@ extern "C++" template <typename BatchT, typename ClockT>
 static void launch_stream_stage(const dagr_graph_desc *desc, const GraphWs &ws, const StreamState &st, int B, int cap,
                                 const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const void *batch_new,
                                 int n, const int32_t *n_new_dev, const void *batch_clock, const int64_t *t_clock,
-                                int n_clock, const int64_t *t_now, int64_t window_us, float *pos_out, float *feat_out,
-                                int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status,
-                                hipStream_t stream) {
+                                int n_clock, const int64_t *t_now, int64_t window_us, int max_lane, int64_t *lane_dropped,
+                                float *pos_out, float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count,
+                                int32_t *status, hipStream_t stream) {
     const unsigned grid = (unsigned)ceil_div(std::max(cap, n_clock), kBlock);
     k_stream_plan<BatchT, ClockT><<<1, kStreamLanes, 0, stream>>>(st, B, cap, (const BatchT *)batch_new, t_new, n, n_new_dev,
                                                                   (const ClockT *)batch_clock, t_clock, n_clock, t_now,
-                                                                  window_us, n_dev, lane_count, status);
+                                                                  window_us, max_lane, lane_dropped, n_dev, lane_count,
+                                                                  status);
     k_stream_gather<BatchT, ClockT><<<grid, kBlock, 0, stream>>>(
         st, B, cap, (const int32_t *)xy_new, t_new, p_new, (const BatchT *)batch_new, n, n_new_dev,
         (const ClockT *)batch_clock, t_clock, n_clock, desc->time_window, pos_out, feat_out, batch_out, ws.status, status,
         desc->width, desc->height, ws.cnt, ws.ev_xyb, ws.ev_t, ws.ev_rank);
 }
 
+// max_lane_events = 0: the uncapped entries, whose window can be as large as everything resident plus the push.
 static int stream_stage_args(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
                              const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const void *batch_new,
-                             int64_t n_new, int64_t window_us, float *pos_out, float *feat_out, int32_t *batch_out,
-                             int32_t *n_dev, int32_t *lane_count, int32_t *status, StreamState *st, GraphWs *ws) {
+                             int64_t n_new, int64_t max_lane_events, int64_t window_us, float *pos_out, float *feat_out,
+                             int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status, StreamState *st,
+                             GraphWs *ws) {
     int rc = validate(desc);
     if (rc != DAGR_OK) return rc;
     DAGR_CHECK_ARG(workspace && state && pos_out && feat_out && batch_out && n_dev && lane_count && status,
@@ -1567,7 +1583,13 @@ static int stream_stage_args(const dagr_graph_desc *desc, void *workspace, void 
     DAGR_CHECK_ARG(B == desc->batch_size, "stream: B differs from desc.batch_size");
     DAGR_CHECK_ARG(window_us > 0 && window_us <= desc->time_window, "stream: window_us must be in 1..time_window");
     DAGR_CHECK_ARG(capacity <= desc->max_events, "stream: capacity exceeds desc.max_events (the size of the outputs)");
-    DAGR_CHECK_ARG(n_new >= 0 && n_new <= capacity, "stream: capacity < n_new");
+    if (max_lane_events == 0) {
+        DAGR_CHECK_ARG(n_new >= 0 && n_new <= capacity, "stream: capacity < n_new");
+    } else {        // a push may be larger than the capacity: only its newest max_lane_events per lane can stay
+        DAGR_CHECK_ARG(max_lane_events >= 1 && max_lane_events <= capacity && (int64_t)B * max_lane_events <= capacity,
+                       "stream: capacity < B * max_lane_events (or max_lane_events < 1)");
+        DAGR_CHECK_ARG(n_new >= 0 && n_new < (1ll << 30), "stream: n_new out of range");
+    }
     DAGR_CHECK_ARG(n_new == 0 || (xy_new && t_new && p_new && batch_new), "stream: NULL input");
     DAGR_CHECK_ARG(((uintptr_t)xy_new & 3) == 0, "stream: xy_new must be 4-byte aligned");
     rc = stream_args(B, capacity, st, state);
@@ -1576,27 +1598,78 @@ static int stream_stage_args(const dagr_graph_desc *desc, void *workspace, void 
     return DAGR_OK;
 }
 
+static int stream_stage(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                        const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const void *batch_new,
+                        int32_t batch_is_int64, int64_t n_new, const int64_t *t_now, int64_t window_us,
+                        int64_t max_lane_events, int64_t *lane_dropped, float *pos_out, float *feat_out, int32_t *batch_out,
+                        int32_t *n_dev, int32_t *lane_count, int32_t *status, void *stream_) {
+    StreamState st;
+    GraphWs ws;
+    int rc = stream_stage_args(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, n_new, max_lane_events,
+                               window_us, pos_out, feat_out, batch_out, n_dev, lane_count, status, &st, &ws);
+    if (rc != DAGR_OK) return rc;
+    const int cap = (int)capacity, n = (int)n_new, max_lane = (int)max_lane_events;
+    if (batch_is_int64)
+        launch_stream_stage<int64_t, int64_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, nullptr, batch_new,
+                                              t_new, n, t_now, window_us, max_lane, lane_dropped, pos_out, feat_out,
+                                              batch_out, n_dev, lane_count, status, (hipStream_t)stream_);
+    else
+        launch_stream_stage<int32_t, int32_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, nullptr, batch_new,
+                                              t_new, n, t_now, window_us, max_lane, lane_dropped, pos_out, feat_out,
+                                              batch_out, n_dev, lane_count, status, (hipStream_t)stream_);
+    DAGR_CHECK_LAUNCH();
+    return DAGR_OK;
+}
+
+static int stream_stage_dev(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                            const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const int32_t *batch_new,
+                            const int32_t *n_new_dev, int64_t n_new_max, const int64_t *t_clock, const void *batch_clock,
+                            int32_t clock_is_int64, int64_t n_clock, const int64_t *t_now, int64_t window_us,
+                            int64_t max_lane_events, int64_t *lane_dropped, float *pos_out, float *feat_out,
+                            int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status, void *stream_) {
+    StreamState st;
+    GraphWs ws;
+    int rc = stream_stage_args(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, n_new_max,
+                               max_lane_events, window_us, pos_out, feat_out, batch_out, n_dev, lane_count, status, &st, &ws);
+    if (rc != DAGR_OK) return rc;
+    DAGR_CHECK_ARG(n_new_dev != nullptr, "stream: n_new_dev is NULL");
+    if (max_lane_events == 0) {
+        DAGR_CHECK_ARG(n_clock >= 0 && n_clock <= capacity, "stream: capacity < n_clock");
+    } else {
+        DAGR_CHECK_ARG(n_clock >= 0 && n_clock < (1ll << 30), "stream: n_clock out of range");
+    }
+    DAGR_CHECK_ARG(n_clock == 0 || (t_clock && batch_clock), "stream: NULL clock");
+    const int cap = (int)capacity, n = (int)n_new_max, nc = (int)n_clock, max_lane = (int)max_lane_events;
+    if (clock_is_int64)
+        launch_stream_stage<int32_t, int64_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, n_new_dev, batch_clock,
+                                              t_clock, nc, t_now, window_us, max_lane, lane_dropped, pos_out, feat_out,
+                                              batch_out, n_dev, lane_count, status, (hipStream_t)stream_);
+    else
+        launch_stream_stage<int32_t, int32_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, n_new_dev, batch_clock,
+                                              t_clock, nc, t_now, window_us, max_lane, lane_dropped, pos_out, feat_out,
+                                              batch_out, n_dev, lane_count, status, (hipStream_t)stream_);
+    DAGR_CHECK_LAUNCH();
+    return DAGR_OK;
+}
+
 int dagr_stream_stage(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
                       const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const void *batch_new,
                       int32_t batch_is_int64, int64_t n_new, const int64_t *t_now, int64_t window_us, float *pos_out,
                       float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status,
-                      void *stream_) {
-    StreamState st;
-    GraphWs ws;
-    int rc = stream_stage_args(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, n_new, window_us,
-                               pos_out, feat_out, batch_out, n_dev, lane_count, status, &st, &ws);
-    if (rc != DAGR_OK) return rc;
-    const int cap = (int)capacity, n = (int)n_new;
-    if (batch_is_int64)
-        launch_stream_stage<int64_t, int64_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, nullptr, batch_new,
-                                              t_new, n, t_now, window_us, pos_out, feat_out, batch_out, n_dev, lane_count,
-                                              status, (hipStream_t)stream_);
-    else
-        launch_stream_stage<int32_t, int32_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, nullptr, batch_new,
-                                              t_new, n, t_now, window_us, pos_out, feat_out, batch_out, n_dev, lane_count,
-                                              status, (hipStream_t)stream_);
-    DAGR_CHECK_LAUNCH();
-    return DAGR_OK;
+                      void *stream) {
+    return stream_stage(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, batch_is_int64, n_new, t_now,
+                        window_us, 0, nullptr, pos_out, feat_out, batch_out, n_dev, lane_count, status, stream);
+}
+
+int dagr_stream_stage_capped(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                             const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const void *batch_new,
+                             int32_t batch_is_int64, int64_t n_new, const int64_t *t_now, int64_t window_us,
+                             int64_t max_lane_events, int64_t *lane_dropped, float *pos_out, float *feat_out,
+                             int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status, void *stream) {
+    DAGR_CHECK_ARG(max_lane_events >= 1, "stream: max_lane_events < 1");
+    return stream_stage(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, batch_is_int64, n_new, t_now,
+                        window_us, max_lane_events, lane_dropped, pos_out, feat_out, batch_out, n_dev, lane_count, status,
+                        stream);
 }
 
 int dagr_stream_stage_dev(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
@@ -1604,26 +1677,23 @@ int dagr_stream_stage_dev(const dagr_graph_desc *desc, void *workspace, void *st
                           const int32_t *n_new_dev, int64_t n_new_max, const int64_t *t_clock, const void *batch_clock,
                           int32_t clock_is_int64, int64_t n_clock, const int64_t *t_now, int64_t window_us, float *pos_out,
                           float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status,
-                          void *stream_) {
-    StreamState st;
-    GraphWs ws;
-    int rc = stream_stage_args(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, n_new_max, window_us,
-                               pos_out, feat_out, batch_out, n_dev, lane_count, status, &st, &ws);
-    if (rc != DAGR_OK) return rc;
-    DAGR_CHECK_ARG(n_new_dev != nullptr, "stream: n_new_dev is NULL");
-    DAGR_CHECK_ARG(n_clock >= 0 && n_clock <= capacity, "stream: capacity < n_clock");
-    DAGR_CHECK_ARG(n_clock == 0 || (t_clock && batch_clock), "stream: NULL clock");
-    const int cap = (int)capacity, n = (int)n_new_max, nc = (int)n_clock;
-    if (clock_is_int64)
-        launch_stream_stage<int32_t, int64_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, n_new_dev, batch_clock,
-                                              t_clock, nc, t_now, window_us, pos_out, feat_out, batch_out, n_dev, lane_count,
-                                              status, (hipStream_t)stream_);
-    else
-        launch_stream_stage<int32_t, int32_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, n_new_dev, batch_clock,
-                                              t_clock, nc, t_now, window_us, pos_out, feat_out, batch_out, n_dev, lane_count,
-                                              status, (hipStream_t)stream_);
-    DAGR_CHECK_LAUNCH();
-    return DAGR_OK;
+                          void *stream) {
+    return stream_stage_dev(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, n_new_dev, n_new_max,
+                            t_clock, batch_clock, clock_is_int64, n_clock, t_now, window_us, 0, nullptr, pos_out, feat_out,
+                            batch_out, n_dev, lane_count, status, stream);
+}
+
+int dagr_stream_stage_dev_capped(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                                 const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const int32_t *batch_new,
+                                 const int32_t *n_new_dev, int64_t n_new_max, const int64_t *t_clock,
+                                 const void *batch_clock, int32_t clock_is_int64, int64_t n_clock, const int64_t *t_now,
+                                 int64_t window_us, int64_t max_lane_events, int64_t *lane_dropped, float *pos_out,
+                                 float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status,
+                                 void *stream) {
+    DAGR_CHECK_ARG(max_lane_events >= 1, "stream: max_lane_events < 1");
+    return stream_stage_dev(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, n_new_dev, n_new_max,
+                            t_clock, batch_clock, clock_is_int64, n_clock, t_now, window_us, max_lane_events, lane_dropped,
+                            pos_out, feat_out, batch_out, n_dev, lane_count, status, stream);
 }
 
 int dagr_graph_search_window(const dagr_graph_desc *desc, void *workspace, int64_t N, int32_t *nbr_src, int16_t *nbr_code,

@@ -396,10 +396,16 @@ class StreamState:
 
     A stream of raw sensor events (``enable_front``) also owns the front's state (``dagr_stream_downsample``): the lanes'
     change maps and the scratch of a largest push, grown with the push size, and the survivors' buffers.  The host's bound
-    is then "last count read + RAW events pushed since"."""
+    is then "last count read + RAW events pushed since".
 
-    def __init__(self, batch_size, window_us, device):
+    A capped stream (``max_lane_events = N``, ``dagr_stream_stage_capped``) keeps the newest ``N`` events of every lane at
+    most: no window exceeds ``B * N``, which bounds the host's bound too, and ``lane_dropped`` accumulates on the device
+    what the count rule removed."""
+
+    def __init__(self, batch_size, window_us, device, max_lane_events=None):
         self.B, self.window_us, self.device = int(batch_size), int(window_us), torch.device(device)
+        self.max_lane_events = None if max_lane_events is None else int(max_lane_events)
+        self.lane_dropped = torch.zeros((self.B,), dtype=torch.int64, device=self.device)
         self.cap = 0
         self.state = None
         self.status = torch.zeros((1,), dtype=torch.int32, device=self.device)
@@ -486,6 +492,7 @@ class StreamState:
                        "stream_front_reset")
         self.status.zero_()
         self.lane_count.zero_()
+        self.lane_dropped.zero_()
         torch.cuda.current_stream(self.device).synchronize()       # (a count copy may still be on its way)
         self._host.zero_()
         self._known, self._since, self._fresh = np.zeros((self.B,), np.int64), 0, True
@@ -523,8 +530,14 @@ class StreamState:
         self._known, self._since, self._fresh = self._host.numpy().astype(np.int64), 0, True
 
     def bound(self):
-        """Upper bound of the resident count: the last count read plus every event pushed since."""
-        return int(self._known.sum()) + self._since
+        """Upper bound of the resident count: the last count read plus every event pushed since -- and, with a cap,
+        ``B * max_lane_events``."""
+        bound = int(self._known.sum()) + self._since
+        return bound if self.max_lane_events is None else min(bound, self.B * self.max_lane_events)
+
+    def dropped(self):
+        """Per-lane events the count rule has removed, int64 [B] (synchronises)."""
+        return self.lane_dropped.cpu().numpy()
 
     def counts_known(self):
         """Per-lane counts of the last step if they have been read, else None."""
@@ -1779,7 +1792,9 @@ class WindowEngine:
         ``st`` -- through ``dagr_stream_downsample`` first when the stream carries raw sensor events (``st.front``) --; two launches write the next window into the static input buffers and its count to device memory, and
         the window runs on them -- the captured graph in latency mode, the same body launch by launch otherwise.  No host
         synchronisation: the host knows an upper bound of the window's size only (``st.bound()``), which is what the
-        buffers are sized by.  Returns ``(out, (det, n_keep))``, both valid until the engine's next call.
+        buffers are sized by.  A capped stream (``st.max_lane_events = N``) goes through ``dagr_stream_stage_capped``; its
+        windows never exceed ``B * N``, which the buffers meet once -- no growth and no re-capture after its first step.
+        Returns ``(out, (det, n_keep))``, both valid until the engine's next call.
 
         ``--use_image``: the window has two bodies.  The frame body runs the image branch on the stream's frame
         (``st.image``; ``image=`` replaces it) and leaves its feature maps and CNN-head outputs; the held body samples
@@ -1792,9 +1807,15 @@ class WindowEngine:
                                "(l0_tiles) and the event path (no --no_events)")
         L, P = self.L, _lib.ptr
         n_new = int(t.shape[0])
-        need = max(st.bound() + n_new, st.cap)       # (a stream that grew on another engine keeps its capacity)
-        if need > self.max_events:
-            self._alloc_events(max(need, 2 * self.max_events))       # (re-captures, as a large window does)
+        N = st.max_lane_events
+        if N is None:
+            need = max(st.bound() + n_new, st.cap)   # (a stream that grew on another engine keeps its capacity)
+            if need > self.max_events:
+                self._alloc_events(max(need, 2 * self.max_events))   # (re-captures, as a large window does)
+        else:       # a capped stream: no window exceeds B * N, whatever is pushed -- a constant, met on the first step
+            need = max(self.B * N, st.cap)
+            if need > self.max_events:
+                self._alloc_events(need)
         if st.state is None or need > st.cap:
             st.grow(self.max_events)
         if self.use_image:
@@ -1821,22 +1842,23 @@ class WindowEngine:
         if self.use_image and not held:
             self.in_image.copy_(st.image)
         g = self.graph
+        outputs = (P(self.in_pos), P(self.in_feat), P(self.in_batch), P(self.n_dev), P(st.lane_count), P(st.status),
+                   _lib.cur_stream(self.device))
+        cap_args = () if N is None else (N, P(st.lane_dropped))
         if st.front is None:
-            _lib.check(L.dagr_stream_stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(xy), P(t), P(p),
-                                           P(batch), 1 if batch.dtype == torch.int64 else 0, n_new, P(t_now), st.window_us,
-                                           P(self.in_pos), P(self.in_feat), P(self.in_batch), P(self.n_dev),
-                                           P(st.lane_count), P(st.status), _lib.cur_stream(self.device)), "stream_stage")
+            stage = L.dagr_stream_stage if N is None else L.dagr_stream_stage_capped
+            _lib.check(stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(xy), P(t), P(p),
+                             P(batch), 1 if batch.dtype == torch.int64 else 0, n_new, P(t_now), st.window_us, *cap_args,
+                             *outputs), "stream_stage")
         else:       # raw sensor events: the front leaves the survivors and their count on the device, the raw push is the clock
             if st.front[4:] != (self.W, self.H):
                 raise RuntimeError(f"the stream downsamples to {st.front[4]} x {st.front[5]}, the engine runs "
                                    f"{self.W} x {self.H}")
             s_xy, s_t, s_p, s_batch, s_n = st.downsample(xy, t, p, batch)
-            _lib.check(L.dagr_stream_stage_dev(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(s_xy),
-                                               P(s_t), P(s_p), P(s_batch), P(s_n), n_new, P(t), P(batch),
-                                               1 if batch.dtype == torch.int64 else 0, n_new, P(t_now), st.window_us,
-                                               P(self.in_pos), P(self.in_feat), P(self.in_batch), P(self.n_dev),
-                                               P(st.lane_count), P(st.status), _lib.cur_stream(self.device)),
-                       "stream_stage_dev")
+            stage = L.dagr_stream_stage_dev if N is None else L.dagr_stream_stage_dev_capped      # (the cap counts survivors)
+            _lib.check(stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(s_xy), P(s_t), P(s_p),
+                             P(s_batch), P(s_n), n_new, P(t), P(batch), 1 if batch.dtype == torch.int64 else 0, n_new,
+                             P(t_now), st.window_us, *cap_args, *outputs), "stream_stage_dev")
         if not self.window_graph:                    # throughput mode: the body of the captured window, launch by launch
             out = self._forward_static(held)
         elif held:

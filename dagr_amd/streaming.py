@@ -22,6 +22,21 @@ documentation and of the tests; nothing on the device path calls it):
   ``(x, y, t_rel, p)`` under the engine's ``(W, H, time_window)``, and the step's result is, bit for bit, what
   ``model(that batch, reset=True)`` returns.
 
+A cap on the count (``max_lane_events = N >= 1``): after the time rule a lane keeps its LAST ``N`` events in arrival order
+when it has more -- the newest stay, equal timestamps are cut by arrival order -- and ``dropped[b]`` (int64, cumulative,
+zero after construction and after ``reset()``) grows at every step by the number the count rule removed beyond the time
+rule, ``max(0, survivors + new events after the time cut - N)``.  ``t_ref``, ``t_rel``, the clock, the status bits, the lane
+order and the frames are as above.  Both rules keep a suffix of the lane, so the capped window is "the time rule applied to
+everything ever pushed to the lane, then the last ``N``": the same event sequence in any chunking, with the same final
+``t_now``, ends in the same window.  The stream's capacity is then the constant ``B * N``: nothing grows after the first
+step, a push may be larger than the capacity, and a burst costs its own lane's oldest events only.  ``window_us=None`` --
+allowed only with a cap -- means ``window_us = time_window``, a pure count window.  N-Caltech101's samples are such
+windows ("the last ``num_events`` events", newest at ``time_window - 1``, ``data/ncaltech101_data.py``): feed a recording to
+a stream with ``window_us=None, max_lane_events=num_events`` and give the last step ``t_now = t_last + 1``; the staged
+window is then ``NCaltech101.preprocess`` + ``format_data`` of the last ``num_events`` events, because
+``t - (t_last - time_window + 1) = time_window - ((t_last + 1) - t)``.  With ``downsample=`` the cap counts the survivors,
+the model's events.
+
 Raw sensor events (``downsample=f`` or ``(fx, fy)``): the models read ``events_2x`` streams, the sensor's events through
 the integrate-and-fire loop of ``scripts/downsample_events.py:91-124`` and cut to the model's rows
 (``DSEC.preprocess_events``).  A push then carries sensor pixels of a ``sensor_size = (W_in, H_in)`` sensor (default
@@ -52,6 +67,26 @@ STATUS_BITS = ((1, "a timestamp goes backwards inside a lane (within a push or a
                (8, "batch is not sorted or is outside [0, batch_size)"),
                (16, "a raw event is outside the sensor (downsampling streams)"),
                (32, "a frame's lane is outside [0, batch_size)"))
+
+
+def _window_and_cap(window_us, max_lane_events, time_window, batch_size, who):
+    """``(window_us, max_lane_events or None)`` of a stream, checked; ``window_us=None`` is the pure count window."""
+    N = max_lane_events
+    if N is not None:
+        if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or int(N) < 1:
+            raise ValueError(f"{who}: max_lane_events = {N!r} must be a positive int (or None: no cap)")
+        N = int(N)
+        if int(batch_size) * N >= (1 << 31) // 64:
+            raise ValueError(f"{who}: batch_size * max_lane_events = {int(batch_size) * N} is outside the stream's capacity "
+                             f"range (below {(1 << 31) // 64})")
+    if window_us is None:
+        if N is None:
+            raise ValueError(f"{who}: window_us=None (a pure count window) needs max_lane_events")
+        window_us = time_window
+    if not 0 < int(window_us) <= int(time_window):
+        raise ValueError(f"{who}: window_us = {window_us} must be in 1..time_window = {time_window} "
+                         "(t_rel = time_window - age has to stay inside the model's time axis)")
+    return int(window_us), N
 
 
 def _factors(downsample, width, height, sensor_size, who):
@@ -115,11 +150,12 @@ class StreamDefinition:
     """The definition above in numpy: ``push`` new events, read ``window()`` / ``formatted()`` / ``counts()``.  Malformed
     pushes raise ``ValueError`` (the device path reports them in its status word instead)."""
 
-    def __init__(self, batch_size, width, height, time_window=1000000, window_us=50000, downsample=None, sensor_size=None):
-        if not 0 < int(window_us) <= int(time_window):
-            raise ValueError(f"window_us = {window_us} must be in 1..time_window = {time_window}")
+    def __init__(self, batch_size, width, height, time_window=1000000, window_us=50000, downsample=None, sensor_size=None,
+                 max_lane_events=None):
         self.B, self.W, self.H = int(batch_size), int(width), int(height)
-        self.time_window, self.window_us = int(time_window), int(window_us)
+        self.time_window = int(time_window)
+        self.window_us, self.max_lane_events = _window_and_cap(window_us, max_lane_events, time_window, batch_size,
+                                                               "StreamDefinition")
         self.front = None if downsample is None else _factors(downsample, self.W, self.H, sensor_size, "StreamDefinition")
         if self.front is None and sensor_size is not None:
             raise ValueError("StreamDefinition: sensor_size is given without downsample")
@@ -130,6 +166,7 @@ class StreamDefinition:
                       for _ in range(self.B)]
         self.t_ref = [None] * self.B
         self.t_last = [None] * self.B
+        self.dropped = np.zeros(self.B, np.int64)
         if self.front is not None:
             fx, fy, w_in, h_in = self.front
             self.change_map = np.zeros((self.B, h_in // fy, w_in // fx), np.float32)
@@ -188,6 +225,11 @@ class StreamDefinition:
                 keep = (age >= 0) & (age < self.window_us)
                 for k in lane:
                     lane[k] = lane[k][keep]
+            N = self.max_lane_events
+            if N is not None and len(lane["t"]) > N:      # the count rule: the last N in arrival order
+                self.dropped[b] += len(lane["t"]) - N
+                for k in lane:
+                    lane[k] = lane[k][-N:]
 
     def counts(self):
         return np.array([len(lane["t"]) for lane in self.lanes], np.int64)
@@ -210,7 +252,12 @@ def _flag_names(flag):
 
 
 class EventStream:
-    """Detections every step from an endless event stream, on the last ``window_us`` microseconds of every lane.
+    """Detections every step from an endless event stream, on the last ``window_us`` microseconds of every lane --
+    with ``max_lane_events=N`` on the newest ``N`` events of them at most (``window_us=None``: on the newest ``N`` events of
+    the model's time window).  A capped stream has the constant capacity ``B * N``: after its first step no buffer grows
+    and no graph is captured again, however many ``step_device`` calls follow without a read-back, and a burst costs its
+    own lane's oldest events only; ``dropped()`` counts them.  (A downsampling stream's front still sizes its scratch by
+    the largest raw push.)
 
     ``model``: an eval-mode ``DAGR`` on the GPU whose window engine runs the captured window: the tiled level-0 conv
     (``l0_tiles``), the event path (no ``--no_events``), the engine path (``model.module_path_only`` False).
@@ -230,14 +277,13 @@ class EventStream:
     ``held_steps`` count the bodies run, and the result is what ``reset=True`` gives with the frame in force either way.
     """
 
-    def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False):
+    def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
+                 max_lane_events=None):
         import torch
         self.model = model
-        self.window_us = int(window_us)
         time_window = int(getattr(model.args, "time_window_us", 1000000))
-        if not 0 < self.window_us <= time_window:
-            raise ValueError(f"EventStream: window_us = {window_us} must be in 1..time_window = {time_window} "
-                             "(t_rel = time_window - age has to stay inside the model's time axis)")
+        self.window_us, self.max_lane_events = _window_and_cap(window_us, max_lane_events, time_window,
+                                                               getattr(model.args, "batch_size", 1), "EventStream")
         if model.training:
             raise RuntimeError("EventStream needs an eval-mode model (model.eval())")
         dev = next(model.parameters()).device
@@ -256,7 +302,9 @@ class EventStream:
         from .engine import StreamState
         self.device = dev
         self.B = eng.B
-        self.state = StreamState(eng.B, self.window_us, dev)
+        if self.max_lane_events is not None:
+            _window_and_cap(self.window_us, self.max_lane_events, time_window, eng.B, "EventStream")
+        self.state = StreamState(eng.B, self.window_us, dev, max_lane_events=self.max_lane_events)
         if downsample is not None:
             fx, fy, w_in, h_in = _factors(downsample, eng.W, eng.H, sensor_size, "EventStream")
             self.state.enable_front(fx, fy, w_in, h_in, eng.W, eng.H)
@@ -402,13 +450,18 @@ class EventStream:
         known = self.state.counts_known()
         return known if known is not None else np.zeros((self.B,), np.int64)
 
+    def dropped(self):
+        """Events per lane the count rule has removed beyond the time rule since construction / ``reset()``: int64 [B],
+        zeros for a stream without ``max_lane_events`` (synchronises)."""
+        return self.state.dropped()
+
     def change_maps(self):
         """The lanes' change maps fp32[B, H_in // fy, W_in // fx] of a downsampling stream (a copy; synchronises)."""
         return self.state.change_maps()
 
     def reset(self):
-        """Empty the stream: no resident events, no reference instants, zero change maps, a clear status word, zero step
-        counters.  The frame in force stays, and the next step runs it through the image branch again."""
+        """Empty the stream: no resident events, no reference instants, zero change maps, zero dropped counts, a clear
+        status word, zero step counters.  The frame in force stays, and the next step runs it through the image branch again."""
         self.state.reset()
 
     def check_status(self):

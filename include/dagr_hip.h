@@ -180,6 +180,17 @@ int dagr_stage_window(const dagr_graph_desc *desc, void *workspace, const float 
  * DAGR_ERR_INVALID_ARG before any launch: window_us <= 0, window_us > desc.time_window, capacity < n_new,
  * capacity > desc.max_events, B != desc.batch_size, NULL pointers.
  * dagr_stream_grow copies a state into a larger one (capacity_new >= capacity) on the device.
+ *
+ * dagr_stream_stage_capped: the same step with a cap on every lane's event count, max_lane_events = N >= 1.  The lane's
+ * window is what the rule above leaves, cut to its LAST N events in arrival order when there are more (equal timestamps
+ * are cut by arrival order): the newest events stay.  The cut takes the oldest events away, the lane's survivors first,
+ * then the front of its push, and adds their number -- max(0, survivors + new events after the time cut - N) -- to
+ * lane_dropped[b] (int64[B] in device memory, accumulated by plain stores of the lane's thread; the caller zeroes it; may
+ * be NULL).  t_ref, t_rel, the clock, the status bits and the lane order are unchanged.  The capped window equals the time
+ * rule applied to everything ever pushed to the lane, then the last N, whatever the chunking of the pushes.
+ * Capacity: capacity >= B * max_lane_events replaces capacity >= n_new; a push may be larger than the capacity (only its
+ * newest N per lane can stay; n_new < 2^30), no window can exceed it, and bit 2 is never raised.  A state can change
+ * between the capped and the uncapped entry from step to step.
  * ------------------------------------------------------------------------ */
 size_t dagr_stream_state_bytes(int32_t B, int64_t capacity);
 int dagr_stream_reset(void *state, int32_t B, int64_t capacity, void *stream);
@@ -189,6 +200,13 @@ int dagr_stream_stage(const dagr_graph_desc *desc, void *workspace, void *state,
                       int32_t batch_is_int64, int64_t n_new, const int64_t *t_now /* [B] or NULL */, int64_t window_us,
                       float *pos_out, float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count /* [B] */,
                       int32_t *status, void *stream);
+int dagr_stream_stage_capped(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                             const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const void *batch_new,
+                             int32_t batch_is_int64, int64_t n_new, const int64_t *t_now /* [B] or NULL */,
+                             int64_t window_us, int64_t max_lane_events,
+                             int64_t *lane_dropped /* [B], device, accumulated; may be NULL */, float *pos_out,
+                             float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count /* [B] */,
+                             int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------ *
  * Event stream front: raw sensor events, downsampled on the device
@@ -218,6 +236,9 @@ int dagr_stream_stage(const dagr_graph_desc *desc, void *workspace, void *state,
  * batch_new (int32); the clock is t_clock / batch_clock (int32/int64, n_clock events) -- the raw push --, which the order
  * checks (bits 0 and 3) run on and the lanes' newest timestamps (t_last, and t_ref without t_now) come from.  Everything
  * else as dagr_stream_stage, which is this entry with the new events as their own clock.  n_new_max, n_clock <= capacity.
+ * dagr_stream_stage_dev_capped is to it what dagr_stream_stage_capped is to dagr_stream_stage: the cap counts the new
+ * events it is given (behind dagr_stream_downsample: the survivors), capacity >= B * max_lane_events replaces the bounds on
+ * n_new_max and n_clock (both < 2^30).
  * ------------------------------------------------------------------------ */
 size_t dagr_stream_front_bytes(int32_t B, int32_t cells_w, int32_t cells_h, int64_t max_push);
 int dagr_stream_front_reset(void *front, size_t front_bytes, int32_t B, int32_t cells_w, int32_t cells_h, int64_t max_push,
@@ -233,6 +254,14 @@ int dagr_stream_stage_dev(const dagr_graph_desc *desc, void *workspace, void *st
                           int32_t clock_is_int64, int64_t n_clock, const int64_t *t_now /* [B] or NULL */,
                           int64_t window_us, float *pos_out, float *feat_out, int32_t *batch_out, int32_t *n_dev,
                           int32_t *lane_count /* [B] */, int32_t *status, void *stream);
+int dagr_stream_stage_dev_capped(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                                 const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const int32_t *batch_new,
+                                 const int32_t *n_new_dev, int64_t n_new_max, const int64_t *t_clock,
+                                 const void *batch_clock, int32_t clock_is_int64, int64_t n_clock,
+                                 const int64_t *t_now /* [B] or NULL */, int64_t window_us, int64_t max_lane_events,
+                                 int64_t *lane_dropped /* [B], device, accumulated; may be NULL */, float *pos_out,
+                                 float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count /* [B] */,
+                                 int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------ *
  * Event stream frames: raw sensor frames, prepared on the device

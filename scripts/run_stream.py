@@ -17,7 +17,11 @@ sensor (default ``F * width`` x ``F * height``), and the stream downsamples them
 ``--raw_frames`` (``--use_image`` models): the source's ``image(i)`` is a sensor-size BGR uint8 frame and goes to the stream
 as it is (``frame=``); the stream crops, shrinks and scales it on the device (``dagr.streaming.frame_definition``) with the
 ``--downsample`` factor, or 1 without.  A frame is handed over when the source's frame index changes; every step between
-two frames samples the maps the image branch left for the last one."""
+two frames samples the maps the image branch left for the last one.
+
+``--max_lane_events N``: the window holds the newest ``N`` events of the last ``--window_us`` at most, and the stream's
+buffers have the constant size ``N``; ``--window_us 0`` then means the model's whole time window, a pure count window.  The
+number of events the cap removed is printed with the summary."""
 import time
 import types
 
@@ -34,7 +38,9 @@ from dagr.utils import synthetic as syn
 def stream_options(p):
     g = p.add_argument_group("event stream")
     g.add_argument("--step_us", type=int, default=1000, help="microseconds between two detections")
-    g.add_argument("--window_us", type=int, default=50000, help="length of the sliding event window")
+    g.add_argument("--window_us", type=int, default=50000, help="length of the sliding event window (0 with "
+                   "--max_lane_events: the model's time window)")
+    g.add_argument("--max_lane_events", type=int, default=None, help="keep the newest N events of the window at most")
     g.add_argument("--steps", type=int, default=100, help="number of steps to play (synthetic sequence)")
     g.add_argument("--sequence", type=str, default="synthetic_stream", help="name the detections are written under")
     g.add_argument("--downsample", type=int, default=None, help="the source delivers raw sensor events: downsample them "
@@ -104,8 +110,9 @@ def play(a, model, source, dev):
     if getattr(a, "raw_frames", False) and use_image:
         h_f, w_f = np.asarray(source.image(0)).shape[:2]
         raw_size = (int(w_f), int(h_f))
-    stream = EventStream(model, window_us=a.window_us, downsample=a.downsample, sensor_size=sensor_size(a),
-                         frame_size=raw_size, frame_bgr=True)
+    cap = getattr(a, "max_lane_events", None)
+    stream = EventStream(model, window_us=a.window_us or None, downsample=a.downsample, sensor_size=sensor_size(a),
+                         frame_size=raw_size, frame_bgr=True, max_lane_events=cap)
     t0, t1 = source.t_range()
     out, last_frame = [], None
     for t_step in range(int(t0) + a.step_us, int(t1) + 1, a.step_us):
@@ -125,13 +132,18 @@ def play(a, model, source, dev):
                           frame=raw)
         out.append((t_step, det[0]))
     a.stream_steps = (stream.frame_steps, stream.held_steps)      # (frame bodies, held bodies) of the run
+    a.stream_dropped = int(stream.dropped().sum()) if cap is not None else None
     return out
 
 
 def main(argv=None, model_factory=None, source=None):
     a = C.flags(__doc__, argv, extra=stream_options)
-    if a.step_us <= 0 or a.window_us <= 0:
-        raise SystemExit("run_stream.py: --step_us and --window_us must be positive")
+    capped = getattr(a, "max_lane_events", None) is not None
+    if capped and a.max_lane_events < 1:
+        raise SystemExit("run_stream.py: --max_lane_events must be positive")
+    if a.step_us <= 0 or a.window_us < 0 or (a.window_us == 0 and not capped):
+        raise SystemExit("run_stream.py: --step_us and --window_us must be positive (--window_us 0: the model's time "
+                         "window, with --max_lane_events only)")
     a.batch_size = 1                       # one sequence: one lane
     world, rank, dev = C.distributed()
     torch.manual_seed(42)
@@ -157,7 +169,10 @@ def main(argv=None, model_factory=None, source=None):
         out_dir.mkdir(parents=True, exist_ok=True)
         path = out_dir / f"detections_{a.sequence}.npy"
         np.save(path, rec)
-        print(f"{len(steps)} steps of {a.step_us} us on a {a.window_us} us window in {seconds:.2f} s "
+        window = f"a {a.window_us} us window" if a.window_us else "the model's time window"
+        if capped:
+            window += f" capped at {a.max_lane_events} events ({a.stream_dropped} dropped by the cap)"
+        print(f"{len(steps)} steps of {a.step_us} us on {window} in {seconds:.2f} s "
               f"({1e3 * seconds / max(1, len(steps)):.2f} ms per step; {a.stream_steps[0]} with the full window, "
               f"{a.stream_steps[1]} on held image maps) -> {path}: {len(rec)} detections")
     C.finish(world)
