@@ -10,8 +10,7 @@
 // of several lanes: cell keys, a stable radix sort by key, one thread per run head, a chained scan over the keep flags and
 // an order-preserving compaction that leaves the survivors and their count in device memory.
 #include "common.hpp"
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "stream_sort.hpp"
 
 namespace dagr {
 namespace {
@@ -57,23 +56,6 @@ struct StreamFront {
     size_t head_bytes;              // maps + scan state: what a reset zeroes
 };
 
-int key_bits(int64_t sentinel) {
-    int bits = 1;
-    while (bits < 32 && (sentinel >> bits) != 0) ++bits;
-    return bits;
-}
-
-// the sort's temporary storage for a push of n events (0 if the library cannot say, e.g. without a device)
-size_t sort_tmp_bytes(int64_t n, int bits) {
-    size_t bytes = 0;
-    if (rocprim::radix_sort_pairs(nullptr, bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr,
-                                  (int32_t *)nullptr, (size_t)n, 0u, (unsigned)bits, (hipStream_t)0) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    return bytes;
-}
-
 // sort_storage: also size the sort's temporary storage (dagr_stream_front_bytes); the other callers take what is left of
 // the caller's buffer behind `sort_tmp`.
 size_t carve_front(int B, int64_t cells, int64_t max_push, char *base, StreamFront *out, bool sort_storage) {
@@ -93,14 +75,7 @@ size_t carve_front(int B, int64_t cells, int64_t max_push, char *base, StreamFro
     f.idx_out = (int32_t *)take((size_t)max_push * 4);
     f.flag = (int32_t *)take((size_t)max_push * 4);
     f.offs = (int32_t *)take((size_t)max_push * 4);
-    f.sort_tmp_bytes = 256;
-    if (sort_storage) {
-        // the library picks its algorithm by size, so the largest push need not ask for the most: max_push and every
-        // power of two below it
-        const int bits = key_bits((int64_t)B * cells);
-        for (int64_t n = max_push; n >= 1; n = (n & (n - 1)) ? (int64_t)1 << (63 - __builtin_clzll((unsigned long long)n)) : n / 2)
-            f.sort_tmp_bytes = std::max(f.sort_tmp_bytes, sort_tmp_bytes(n, bits));
-    }
+    f.sort_tmp_bytes = sort_storage ? sort_tmp_bytes_upto(max_push, key_bits((int64_t)B * cells)) : 256;
     f.tmp_offset = off;
     f.sort_tmp = take(f.sort_tmp_bytes);
     if (out) *out = f;

@@ -398,6 +398,10 @@ class StreamState:
     change maps and the scratch of a largest push, grown with the push size, and the survivors' buffers.  The host's bound
     is then "last count read + RAW events pushed since".
 
+    A filtering stream (``enable_denoise``) owns the noise filter's state (``dagr_stream_denoise``): the lanes' int64 stamp
+    maps and the scratch of a largest push, grown with the push size, the survivors' buffers, and ``lane_filtered``, which
+    accumulates on the device what the filter removed.  Its bound counts the UNFILTERED events pushed.
+
     A capped stream (``max_lane_events = N``, ``dagr_stream_stage_capped``) keeps the newest ``N`` events of every lane at
     most: no window exceeds ``B * N``, which bounds the host's bound too, and ``lane_dropped`` accumulates on the device
     what the count rule removed."""
@@ -421,6 +425,68 @@ class StreamState:
         self._fresh = True                              # _known belongs to the last step staged
         self.front = None                               # (fx, fy, W_in, H_in, W, H) of a downsampling stream
         self.front_state, self.front_cap, self.front_out = None, 0, None
+        self.noise = None                               # (W_in, H_in, denoise_us or 0, refractory_us or 0) of a filtering stream
+        self.noise_state, self.noise_cap, self.noise_out, self.lane_filtered = None, 0, None, None
+
+    # ------------------------------------------------------------------------------------ sensor noise
+    def enable_denoise(self, sensor_w, sensor_h, denoise_us=None, refractory_us=None):
+        """Pushes go through ``dagr_stream_denoise`` first: a ``sensor_w x sensor_h`` stamp map per lane, ``denoise_us`` /
+        ``refractory_us`` positive or None (off; not both)."""
+        if denoise_us is None and refractory_us is None:
+            raise ValueError("enable_denoise: denoise_us and refractory_us are both None")
+        self.noise = (int(sensor_w), int(sensor_h), int(denoise_us or 0), int(refractory_us or 0))
+        self.noise_state, self.noise_cap, self.noise_out = None, 0, None
+        self.lane_filtered = torch.zeros((self.B,), dtype=torch.int64, device=self.device)
+        self.grow_denoise(4096)
+
+    def grow_denoise(self, n):
+        """Scratch and survivors' buffers for pushes of ``n`` events; the stamp maps are carried over."""
+        if n <= self.noise_cap:
+            return
+        L, stream = _lib.lib(), _lib.cur_stream(self.device)
+        sensor_w, sensor_h = self.noise[:2]
+        nbytes = L.dagr_stream_denoise_bytes(self.B, sensor_w, sensor_h, n)
+        if nbytes == 0:
+            raise RuntimeError(f"dagr_stream_denoise_bytes({self.B}, {sensor_w}, {sensor_h}, {n}): out of range")
+        new = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _lib.check(L.dagr_stream_denoise_reset(_lib.ptr(new), nbytes, self.B, sensor_w, sensor_h, n, stream),
+                   "stream_denoise_reset")
+        if self.noise_state is not None:
+            maps = 8 * self.B * sensor_w * sensor_h
+            new[:maps].copy_(self.noise_state[:maps])
+        self.noise_state, self.noise_cap = new, n
+        dev = self.device
+        self.noise_out = (torch.empty((n, 2), dtype=torch.int16, device=dev), torch.empty((n,), dtype=torch.int64, device=dev),
+                          torch.empty((n,), dtype=torch.int8, device=dev), torch.empty((n,), dtype=torch.int32, device=dev),
+                          torch.zeros((1,), dtype=torch.int32, device=dev))
+
+    def denoise(self, xy, t, p, batch):
+        """``dagr_stream_denoise`` on a push: ``(xy, t, p, batch int32, count int32[1])`` of the survivors, on the device,
+        valid until the next push; rows from the count up to the push's size are lane-less (lane -1 at pixel (0, 0))."""
+        n = int(t.shape[0])
+        if n > self.noise_cap:
+            self.grow_denoise(max(n, 2 * self.noise_cap))
+        sensor_w, sensor_h, denoise_us, refractory_us = self.noise
+        P, o = _lib.ptr, self.noise_out
+        _lib.check(_lib.lib().dagr_stream_denoise(
+            P(self.noise_state), self.noise_state.numel(), self.B, self.noise_cap, sensor_w, sensor_h, denoise_us, refractory_us,
+            P(xy), P(t), P(p), P(batch), 1 if batch.dtype == torch.int64 else 0, n, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]),
+            P(self.lane_filtered), P(self.status), _lib.cur_stream(self.device)), "stream_denoise")
+        return o
+
+    def filtered(self):
+        """Per-lane events the noise filter has removed, int64 [B]; zeros without the filter (synchronises)."""
+        if self.noise is None:
+            torch.cuda.current_stream(self.device).synchronize()
+            return np.zeros((self.B,), np.int64)
+        return self.lane_filtered.cpu().numpy()
+
+    def last_stamps(self):
+        """The lanes' stamp maps int64[B, sensor_h, sensor_w], never = INT64_MIN (a copy; synchronises)."""
+        if self.noise is None:
+            raise RuntimeError("this stream does not filter noise (denoise_us / refractory_us): it has no stamp maps")
+        sensor_w, sensor_h = self.noise[:2]
+        return self.noise_state[:8 * self.B * sensor_w * sensor_h].view(torch.int64).view(self.B, sensor_h, sensor_w).cpu().numpy()
 
     # ------------------------------------------------------------------------------------ raw sensor events
     def enable_front(self, fx, fy, sensor_w, sensor_h, width, height):
@@ -490,6 +556,11 @@ class StreamState:
             _lib.check(_lib.lib().dagr_stream_front_reset(_lib.ptr(self.front_state), self.front_state.numel(), self.B, cells_w,
                                                           cells_h, self.front_cap, _lib.cur_stream(self.device)),
                        "stream_front_reset")
+        if self.noise_state is not None:
+            _lib.check(_lib.lib().dagr_stream_denoise_reset(_lib.ptr(self.noise_state), self.noise_state.numel(), self.B,
+                                                            self.noise[0], self.noise[1], self.noise_cap,
+                                                            _lib.cur_stream(self.device)), "stream_denoise_reset")
+            self.lane_filtered.zero_()
         self.status.zero_()
         self.lane_count.zero_()
         self.lane_dropped.zero_()
@@ -1794,6 +1865,8 @@ class WindowEngine:
         synchronisation: the host knows an upper bound of the window's size only (``st.bound()``), which is what the
         buffers are sized by.  A capped stream (``st.max_lane_events = N``) goes through ``dagr_stream_stage_capped``; its
         windows never exceed ``B * N``, which the buffers meet once -- no growth and no re-capture after its first step.
+        A filtering stream (``st.noise``) runs ``dagr_stream_denoise`` on the push before anything else and stages what is
+        left through the ``_dev`` entries, with the unfiltered push as the clock.
         Returns ``(out, (det, n_keep))``, both valid until the engine's next call.
 
         ``--use_image``: the window has two bodies.  The frame body runs the image branch on the stream's frame
@@ -1845,7 +1918,24 @@ class WindowEngine:
         outputs = (P(self.in_pos), P(self.in_feat), P(self.in_batch), P(self.n_dev), P(st.lane_count), P(st.status),
                    _lib.cur_stream(self.device))
         cap_args = () if N is None else (N, P(st.lane_dropped))
-        if st.front is None:
+        if st.noise is not None:    # the noise filter first; the unfiltered push stays the clock
+            sensor = (self.W, self.H) if st.front is None else st.front[2:4]
+            if st.noise[:2] != sensor:
+                raise RuntimeError(f"the stream filters a {st.noise[0]} x {st.noise[1]} sensor, its pushes carry "
+                                   f"{sensor[0]} x {sensor[1]} pixels")
+            s_xy, s_t, s_p, s_batch, s_n = st.denoise(xy, t, p, batch)
+            if st.front is not None:
+                if st.front[4:] != (self.W, self.H):
+                    raise RuntimeError(f"the stream downsamples to {st.front[4]} x {st.front[5]}, the engine runs "
+                                       f"{self.W} x {self.H}")
+                # the front takes its count from the host: all n_new rows, of which those behind the filter's count are
+                # lane-less and integrate nowhere
+                s_xy, s_t, s_p, s_batch, s_n = st.downsample(s_xy[:n_new], s_t[:n_new], s_p[:n_new], s_batch[:n_new])
+            stage = L.dagr_stream_stage_dev if N is None else L.dagr_stream_stage_dev_capped
+            _lib.check(stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(s_xy), P(s_t), P(s_p),
+                             P(s_batch), P(s_n), n_new, P(t), P(batch), 1 if batch.dtype == torch.int64 else 0, n_new,
+                             P(t_now), st.window_us, *cap_args, *outputs), "stream_stage_dev")
+        elif st.front is None:
             stage = L.dagr_stream_stage if N is None else L.dagr_stream_stage_capped
             _lib.check(stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(xy), P(t), P(p),
                              P(batch), 1 if batch.dtype == torch.int64 else 0, n_new, P(t_now), st.window_us, *cap_args,

@@ -52,6 +52,31 @@ the integrate-and-fire loop of ``scripts/downsample_events.py:91-124`` and cut t
 * what is left is pushed as above, but the clock is the sensor's: the order checks run on the raw arrays, and the lane's
   newest event -- ``t_last``, and ``t_ref`` without ``t_now`` -- is its newest RAW event.
 
+Sensor noise (``denoise_us=D`` and / or ``refractory_us=R``, each ``None`` = off or a positive int; with both ``None``
+nothing changes anywhere): a background-activity filter and a refractory filter on what a push carries, before anything
+else -- sensor pixels of the ``sensor_size`` sensor with ``downsample=``, the model's ``W x H`` pixels without it (the sensor
+is then ``(W, H)``).  Every lane owns a stamp map ``last_t``, int64 ``[H_in, W_in]``, "never" after construction and after
+``reset()``, carried from push to push.  A lane's events are taken in arrival order; for an event ``(x, y, t)`` inside the
+sensor:
+
+* supported: with ``denoise_us = D`` the event is supported if some pixel of its 8-neighbourhood has a stamp
+  ``s != never`` with ``t - s <= D`` -- the centre pixel is excluded, neighbours outside the sensor do not exist, nothing
+  wraps into the next row or the next lane; with ``denoise_us=None`` every event is supported;
+* refractory: with ``refractory_us = R`` the event is refractory if its own pixel has a stamp ``s != never`` with
+  ``t - s < R``; with ``refractory_us=None`` no event is refractory;
+* kept: iff supported and not refractory;
+* stamp: then ``last_t[y, x] = t``, whether the event was kept or not.
+
+Every event stamps, so a decision depends on the timestamps of earlier events only, never on earlier decisions: the filter
+is parallel (``dagr_stream_denoise``: one thread per event), and the same sequence in any chunking leaves the same
+survivors and the same map.  A hot pixel with a period below ``R`` passes once and then stays silent.  "Earlier" means
+arrival order: of two events with one timestamp the second sees the first (``t - s = 0``: supported, and refractory).  A raw
+event outside the sensor is dropped, does not stamp and is malformed (status bit of value 16).  The survivors keep the order
+of the push and go on to the integrator of ``downsample=``, or straight to the window.  The clock stays the sensor's: the
+order checks run on the unfiltered push, and the lane's newest event -- ``t_last``, and ``t_ref`` without ``t_now`` -- is
+its newest UNFILTERED event.  ``max_lane_events`` counts what reaches the window.  ``filtered[b]`` (int64, cumulative, zero
+after construction and after ``reset()``) counts the events inside the sensor that the filter removed.
+
 Frames (``--use_image`` models): every lane has a frame in force, the last one a step gave it -- as the model's image
 (``image=``, fp32 [B, 3, H, W]) or as a raw sensor frame (``frame=``, uint8 [H_f, W_f, 3], which ``dagr_stream_frame``
 prepares on the device; ``frame_definition`` below states what that is).  A step's result is what ``model(..., reset=True)``
@@ -104,6 +129,48 @@ def _factors(downsample, width, height, sensor_size, who):
     return fx, fy, w_in, h_in
 
 
+NEVER = np.iinfo(np.int64).min          # a stamp map's "no event yet"
+
+
+def _noise_options(denoise_us, refractory_us, batch_size, w_in, h_in, who):
+    """``(D or None, R or None)`` of a filtering stream over a ``w_in x h_in`` sensor, checked; refusals by name."""
+    out = []
+    for name, v in (("denoise_us", denoise_us), ("refractory_us", refractory_us)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1):
+            raise ValueError(f"{who}: {name} = {v!r} must be a positive int of microseconds (or None: off)")
+        out.append(None if v is None else int(v))
+    if (out[0] is not None or out[1] is not None) and int(batch_size) * int(w_in) * int(h_in) >= 1 << 31:
+        raise ValueError(f"{who}: batch_size * W_in * H_in = {int(batch_size) * int(w_in) * int(h_in)} stamps are outside the "
+                         f"noise filter's range (below {1 << 31})")
+    return tuple(out)
+
+
+def denoise_definition(last_t, x, y, t, batch, denoise_us=None, refractory_us=None):
+    """The noise filter of the module docstring on one push, stated once: ``last_t`` int64 ``[B, H_in, W_in]`` is read and
+    stamped in place, the result is the push's keep mask.  An event outside the sensor or with a lane outside ``[0, B)`` is
+    not kept and does not stamp.  The yardstick of ``dagr_stream_denoise``; nothing on the device path calls it."""
+    B, h_in, w_in = last_t.shape
+    keep = np.zeros(len(t), bool)
+    D, R = denoise_us, refractory_us
+    for i in range(len(t)):
+        xi, yi, ti, b = int(x[i]), int(y[i]), int(t[i]), int(batch[i])
+        if not (0 <= xi < w_in and 0 <= yi < h_in and 0 <= b < B):
+            continue
+        lane = last_t[b]
+        supported = D is None
+        if not supported:
+            near = lane[max(yi - 1, 0):yi + 2, max(xi - 1, 0):xi + 2]
+            stamped = near != NEVER
+            ok = stamped & (ti - np.where(stamped, near, ti) <= D)          # (int64 throughout; never is not subtracted)
+            ok[min(yi, 1), min(xi, 1)] = False                              # the centre pixel
+            supported = bool(ok.any())
+        own = int(lane[yi, xi])
+        refractory = R is not None and own != NEVER and ti - own < R
+        keep[i] = supported and not refractory
+        lane[yi, xi] = ti
+    return keep
+
+
 def frame_definition(raw, fx, fy, W, H, bgr=False):
     """The model's image of one raw sensor frame (``uint8 [H_f, W_f, 3]``), stated once: ``DSEC.preprocess_image`` plus
     ``format_data`` for a top-left crop.  Rows ``[0, fy * H)`` and columns ``[0, fx * W)`` of the frame go through
@@ -151,7 +218,7 @@ class StreamDefinition:
     pushes raise ``ValueError`` (the device path reports them in its status word instead)."""
 
     def __init__(self, batch_size, width, height, time_window=1000000, window_us=50000, downsample=None, sensor_size=None,
-                 max_lane_events=None):
+                 max_lane_events=None, denoise_us=None, refractory_us=None):
         self.B, self.W, self.H = int(batch_size), int(width), int(height)
         self.time_window = int(time_window)
         self.window_us, self.max_lane_events = _window_and_cap(window_us, max_lane_events, time_window, batch_size,
@@ -159,6 +226,10 @@ class StreamDefinition:
         self.front = None if downsample is None else _factors(downsample, self.W, self.H, sensor_size, "StreamDefinition")
         if self.front is None and sensor_size is not None:
             raise ValueError("StreamDefinition: sensor_size is given without downsample")
+        self.sensor = (self.W, self.H) if self.front is None else self.front[2:]
+        self.denoise_us, self.refractory_us = _noise_options(denoise_us, refractory_us, self.B, *self.sensor,
+                                                             "StreamDefinition")
+        self.noise = self.denoise_us is not None or self.refractory_us is not None
         self.reset()
 
     def reset(self):
@@ -167,6 +238,9 @@ class StreamDefinition:
         self.t_ref = [None] * self.B
         self.t_last = [None] * self.B
         self.dropped = np.zeros(self.B, np.int64)
+        self.filtered = np.zeros(self.B, np.int64)
+        if self.noise:
+            self.last_t = np.full((self.B, self.sensor[1], self.sensor[0]), NEVER, np.int64)
         if self.front is not None:
             fx, fy, w_in, h_in = self.front
             self.change_map = np.zeros((self.B, h_in // fy, w_in // fx), np.float32)
@@ -198,7 +272,8 @@ class StreamDefinition:
             raise ValueError("batch is not sorted or is outside [0, batch_size)")
         if t_now is not None:
             t_now = np.broadcast_to(np.asarray(t_now, np.int64).reshape(-1), (self.B,))
-        if self.front is not None and np.any((x < 0) | (x >= self.front[2]) | (y < 0) | (y >= self.front[3])):
+        if (self.front is not None or self.noise) and \
+                np.any((x < 0) | (x >= self.sensor[0]) | (y < 0) | (y >= self.sensor[1])):
             raise ValueError("a raw event is outside the sensor")
         parts, refs = [], []
         for b in range(self.B):                           # everything is checked before anything is changed (on the RAW
@@ -212,6 +287,10 @@ class StreamDefinition:
                 raise ValueError(f"lane {b}: t_now is behind the lane's newest event or behind its previous t_ref")
             parts.append(newest)
             refs.append(ref)
+        if self.noise:                                    # the filter comes first; the clock above is the unfiltered push's
+            keep = denoise_definition(self.last_t, x, y, t, batch, self.denoise_us, self.refractory_us)
+            self.filtered += np.bincount(batch[~keep], minlength=self.B)
+            x, y, t, p, batch = x[keep], y[keep], t[keep], p[keep], batch[keep]
         if self.front is not None:
             x, y, t, p, batch = self._downsample(x, y, t, p, batch)
         for b, (newest, ref) in enumerate(zip(parts, refs)):
@@ -264,6 +343,10 @@ class EventStream:
     ``downsample`` (``f`` or ``(fx, fy)``) and ``sensor_size`` (``(W_in, H_in)``, default ``(fx * W, fy * H)``): the
     pushes carry raw sensor events, which ``dagr_stream_downsample`` turns into the model's on the device (module
     docstring); ``change_maps()`` reads the integrators back.
+    ``denoise_us`` and ``refractory_us`` (positive ints of microseconds, ``None``: off): ``dagr_stream_denoise`` removes
+    background activity and hot pixels from every push on the device, before anything else (module docstring);
+    ``filtered()`` counts what it removed, ``last_stamps()`` reads the stamp maps back.  A stream built without them issues
+    exactly the launches it issues without the filter.
     ``frame_size`` (``(W_f, H_f)``) and ``frame_bgr``: the steps may carry raw sensor frames (``frame=``), which
     ``dagr_stream_frame`` turns into the model's image on the device (``frame_definition``) with the stream's
     ``downsample`` factors, or 1 without ``downsample``.
@@ -278,7 +361,7 @@ class EventStream:
     """
 
     def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
-                 max_lane_events=None):
+                 max_lane_events=None, denoise_us=None, refractory_us=None):
         import torch
         self.model = model
         time_window = int(getattr(model.args, "time_window_us", 1000000))
@@ -305,11 +388,16 @@ class EventStream:
         if self.max_lane_events is not None:
             _window_and_cap(self.window_us, self.max_lane_events, time_window, eng.B, "EventStream")
         self.state = StreamState(eng.B, self.window_us, dev, max_lane_events=self.max_lane_events)
+        w_in, h_in = eng.W, eng.H
         if downsample is not None:
             fx, fy, w_in, h_in = _factors(downsample, eng.W, eng.H, sensor_size, "EventStream")
-            self.state.enable_front(fx, fy, w_in, h_in, eng.W, eng.H)
         elif sensor_size is not None:
             raise ValueError("EventStream: sensor_size is given without downsample")
+        self.denoise_us, self.refractory_us = _noise_options(denoise_us, refractory_us, eng.B, w_in, h_in, "EventStream")
+        if downsample is not None:
+            self.state.enable_front(fx, fy, w_in, h_in, eng.W, eng.H)
+        if self.denoise_us is not None or self.refractory_us is not None:
+            self.state.enable_denoise(w_in, h_in, self.denoise_us, self.refractory_us)
         self._zeros = None
         self.outputs = None      # the last step's decoded head outputs [B, A, 5 + classes], valid until the engine's next call
         self._frame = None
@@ -459,9 +547,19 @@ class EventStream:
         """The lanes' change maps fp32[B, H_in // fy, W_in // fx] of a downsampling stream (a copy; synchronises)."""
         return self.state.change_maps()
 
+    def filtered(self):
+        """Events per lane the noise filter has removed since construction / ``reset()``: int64 [B], zeros for a stream
+        without ``denoise_us`` / ``refractory_us`` (synchronises)."""
+        return self.state.filtered()
+
+    def last_stamps(self):
+        """The lanes' stamp maps int64[B, H_in, W_in] of a filtering stream, "never" as ``np.iinfo(np.int64).min`` (a copy;
+        synchronises)."""
+        return self.state.last_stamps()
+
     def reset(self):
-        """Empty the stream: no resident events, no reference instants, zero change maps, zero dropped counts, a clear
-        status word, zero step counters.  The frame in force stays, and the next step runs it through the image branch again."""
+        """Empty the stream: no resident events, no reference instants, zero change maps, empty stamp maps, zero dropped and
+        filtered counts, a clear status word, zero step counters.  The frame in force stays, and the next step runs it through the image branch again."""
         self.state.reset()
 
     def check_status(self):

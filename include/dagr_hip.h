@@ -264,6 +264,49 @@ int dagr_stream_stage_dev_capped(const dagr_graph_desc *desc, void *workspace, v
                                  int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------ *
+ * Event stream noise filter: background activity and hot pixels, removed on the device
+ *   A raw sensor stream carries isolated background-activity events and hot pixels.  dagr_stream_denoise filters a push of
+ *   raw events of B lanes in front of dagr_stream_downsample / dagr_stream_stage_dev and leaves the survivors and their count
+ *   in device memory.  Three launches of its own, the project's one-launch scan and a library radix sort, no host
+ *   synchronisation.
+ *
+ * Every lane owns a stamp map int64[sensor_h, sensor_w], carried from push to push: the t of the last event on the pixel,
+ * or "never" = INT64_MIN.  A lane's events are taken in arrival order.  An event (x, y, t) inside the sensor is
+ *   supported  (denoise_us = D > 0) if a pixel of its 8-neighbourhood -- the centre excluded, pixels outside the sensor do
+ *              not exist, nothing wraps into the next row or lane -- has a stamp s != never with t - s <= D; with D = 0
+ *              (off) every event is supported;
+ *   refractory (refractory_us = R > 0) if its own pixel has a stamp s != never with t - s < R; with R = 0 (off) none is;
+ *   kept       iff supported and not refractory; then stamp[y, x] = t, kept or not.
+ * Every event stamps, so a decision depends on the timestamps of earlier events only: the same sequence in any chunking
+ * leaves the same survivors and the same maps.  "Earlier" is arrival order: of two events with one timestamp the second sees
+ * the first.  All time arithmetic is int64.  An event outside [0, sensor_w) x [0, sensor_h) is dropped, does not stamp and
+ * raises bit 4 (value 16) of `status`, the stream's status word; an event whose lane is outside [0, B) is dropped and does
+ * not stamp (dagr_stream_stage_dev flags it on the clock).  The survivors keep the order of the push.
+ *
+ * state: dagr_stream_denoise_bytes(B, sensor_w, sensor_h, max_push) bytes (0: sizes out of range -- B in 1..127,
+ *        B * sensor_w * sensor_h < 2^31, max_push in 1..2^25 - 1), dagr_stream_denoise_reset before the first push, after a
+ *        change of max_push and to empty the maps.  The stamps are its first B * sensor_h * sensor_w int64 (a caller that
+ *        needs a larger max_push copies them into the new state after its reset); keys, sorted order, keep flags, their
+ *        prefix sums and the sort's storage for max_push events follow.
+ * xy_raw int16[n_raw,2] (4-byte aligned) sensor pixels, t_raw int64[n_raw] non-decreasing inside a lane, p_raw int8[n_raw],
+ * batch_raw int32/int64[n_raw] sorted; outputs for n_raw events, none of them an input: xy_out int16[.,2] (4-byte aligned),
+ * t_out int64, p_out int8, batch_out int32, *n_out = the number of survivors.  Rows *n_out .. n_raw - 1 of xy_out are (0, 0)
+ * and of batch_out -1: dagr_stream_downsample, which takes its count from the host, can be given all n_raw rows and drops
+ * those silently.  lane_filtered int64[B] (may be NULL): the lane's events inside the sensor that were not kept are added
+ * to it by plain stores of the lane's thread; the caller zeroes it.  All in device memory.
+ * DAGR_ERR_INVALID_ARG before any launch: sizes out of range, negative denoise_us / refractory_us or both 0,
+ * n_raw > max_push, a state smaller than dagr_stream_denoise_bytes, NULL pointers.
+ * ------------------------------------------------------------------------ */
+size_t dagr_stream_denoise_bytes(int32_t B, int32_t sensor_w, int32_t sensor_h, int64_t max_push);
+int dagr_stream_denoise_reset(void *state, size_t state_bytes, int32_t B, int32_t sensor_w, int32_t sensor_h,
+                              int64_t max_push, void *stream);
+int dagr_stream_denoise(void *state, size_t state_bytes, int32_t B, int64_t max_push, int32_t sensor_w, int32_t sensor_h,
+                        int64_t denoise_us /* 0: off */, int64_t refractory_us /* 0: off */, const int16_t *xy_raw,
+                        const int64_t *t_raw, const int8_t *p_raw, const void *batch_raw, int32_t batch_is_int64,
+                        int64_t n_raw, int16_t *xy_out, int64_t *t_out, int8_t *p_out, int32_t *batch_out, int32_t *n_out,
+                        int64_t *lane_filtered /* [B], device, accumulated; may be NULL */, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * Event stream frames: raw sensor frames, prepared on the device
  *   DSEC.preprocess_image (crop, bicubic shrink by a whole factor, back to uint8) and format_data's `/ 255` in one launch,
  *   for n frames at once: rows [0, fy * height) and columns [0, fx * width) of every uint8 [frame_h, frame_w, 3] frame are

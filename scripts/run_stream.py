@@ -21,7 +21,11 @@ two frames samples the maps the image branch left for the last one.
 
 ``--max_lane_events N``: the window holds the newest ``N`` events of the last ``--window_us`` at most, and the stream's
 buffers have the constant size ``N``; ``--window_us 0`` then means the model's whole time window, a pure count window.  The
-number of events the cap removed is printed with the summary."""
+number of events the cap removed is printed with the summary.
+
+``--denoise_us D`` / ``--refractory_us R``: the stream's noise filter, on the device and in front of everything else
+(``dagr.streaming``): an event is kept if one of its 8 neighbours saw an event in the last ``D`` microseconds and its own
+pixel saw none in the last ``R``.  The number of events the filter removed is printed with the summary."""
 import time
 import types
 
@@ -47,6 +51,10 @@ def stream_options(p):
                    "by this factor on the device")
     g.add_argument("--sensor_width", type=int, default=None, help="sensor width with --downsample (default F * width)")
     g.add_argument("--sensor_height", type=int, default=None, help="sensor height with --downsample (default F * height)")
+    g.add_argument("--denoise_us", type=int, default=None, help="noise filter: keep an event only if one of its 8 "
+                   "neighbours saw an event in the last D microseconds")
+    g.add_argument("--refractory_us", type=int, default=None, help="noise filter: drop an event whose own pixel saw an "
+                   "event less than R microseconds ago")
     g.add_argument("--raw_frames", action="store_true", help="the source's frames are sensor-size BGR uint8 frames: prepare "
                    "them on the device (crop, shrink by the --downsample factor, / 255)")
 
@@ -112,7 +120,8 @@ def play(a, model, source, dev):
         raw_size = (int(w_f), int(h_f))
     cap = getattr(a, "max_lane_events", None)
     stream = EventStream(model, window_us=a.window_us or None, downsample=a.downsample, sensor_size=sensor_size(a),
-                         frame_size=raw_size, frame_bgr=True, max_lane_events=cap)
+                         frame_size=raw_size, frame_bgr=True, max_lane_events=cap,
+                         denoise_us=getattr(a, "denoise_us", None), refractory_us=getattr(a, "refractory_us", None))
     t0, t1 = source.t_range()
     out, last_frame = [], None
     for t_step in range(int(t0) + a.step_us, int(t1) + 1, a.step_us):
@@ -133,6 +142,7 @@ def play(a, model, source, dev):
         out.append((t_step, det[0]))
     a.stream_steps = (stream.frame_steps, stream.held_steps)      # (frame bodies, held bodies) of the run
     a.stream_dropped = int(stream.dropped().sum()) if cap is not None else None
+    a.stream_filtered = int(stream.filtered().sum()) if stream.state.noise is not None else None
     return out
 
 
@@ -141,6 +151,9 @@ def main(argv=None, model_factory=None, source=None):
     capped = getattr(a, "max_lane_events", None) is not None
     if capped and a.max_lane_events < 1:
         raise SystemExit("run_stream.py: --max_lane_events must be positive")
+    for name in ("denoise_us", "refractory_us"):
+        if getattr(a, name, None) is not None and getattr(a, name) < 1:
+            raise SystemExit(f"run_stream.py: --{name} must be positive")
     if a.step_us <= 0 or a.window_us < 0 or (a.window_us == 0 and not capped):
         raise SystemExit("run_stream.py: --step_us and --window_us must be positive (--window_us 0: the model's time "
                          "window, with --max_lane_events only)")
@@ -172,6 +185,8 @@ def main(argv=None, model_factory=None, source=None):
         window = f"a {a.window_us} us window" if a.window_us else "the model's time window"
         if capped:
             window += f" capped at {a.max_lane_events} events ({a.stream_dropped} dropped by the cap)"
+        if a.stream_filtered is not None:
+            window += f" behind the noise filter ({a.stream_filtered} events filtered)"
         print(f"{len(steps)} steps of {a.step_us} us on {window} in {seconds:.2f} s "
               f"({1e3 * seconds / max(1, len(steps)):.2f} ms per step; {a.stream_steps[0]} with the full window, "
               f"{a.stream_steps[1]} on held image maps) -> {path}: {len(rec)} detections")
