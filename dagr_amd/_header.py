@@ -29,6 +29,9 @@ class Header:
         self._types = dict(SCALARS)
         text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)          # comments sit inside argument lists too
         text = re.sub(r"//[^\n]*", " ", text)
+        # ``#define NAME <integer>``: the bounds the header states (DAGR_COCO_MAX_GT, DAGR_TRACK_MAX_TRACKS, ...)
+        self.defines = {m.group(1): int(m.group(2), 0)
+                        for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*$", text, re.M)}
         text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)     # include guard, includes, #define, #ifdef __cplusplus
         text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
         for decl in _BLOCK.sub(self._block, text).split(";"):

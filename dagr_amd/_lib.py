@@ -33,6 +33,7 @@ _HEADER = _read_header()
 ENUMS = _HEADER.enums                   # enumerator -> int, e.g. ENUMS["DAGR_FLOPS_CONV"]
 STRUCTS = _HEADER.structs               # C name -> ctypes.Structure, e.g. STRUCTS["dagr_pool_desc"] is PoolDesc
 SIGNATURES = _HEADER.functions          # name -> (restype, argtypes)
+DEFINES = _HEADER.defines               # integer #defines, e.g. DEFINES["DAGR_TRACK_MAX_TRACKS"]
 # PoolDesc, GraphDesc, HeadScale, ConvJob, L0Inputs, AsyncUpdateArgs, FlopsModule, AugParams: dagr_<x_y> is class XY
 globals().update({cls.__name__: cls for cls in STRUCTS.values()})
 

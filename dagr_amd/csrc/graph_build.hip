@@ -1523,6 +1523,14 @@ size_t dagr_stream_state_bytes(int32_t B, int64_t capacity) {
     return carve_stream(B, capacity, nullptr, nullptr);
 }
 
+// where the lanes' reference instants live inside a state: pointer arithmetic, nothing is launched or read
+const int64_t *dagr_stream_t_ref(const void *state, int32_t B, int64_t capacity) {
+    if (!state || dagr_stream_state_bytes(B, capacity) == 0) return nullptr;
+    StreamState st;
+    carve_stream(B, capacity, (char *)const_cast<void *>(state), &st);
+    return st.t_ref;
+}
+
 int dagr_stream_reset(void *state, int32_t B, int64_t capacity, void *stream) {
     DAGR_CHECK_ARG(state != nullptr, "stream: state is NULL");
     StreamState st;

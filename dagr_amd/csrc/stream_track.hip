@@ -1,0 +1,290 @@
+// stream_track.hip -- the event stream's tracker (dagr_stream_track): the detections of a step are associated with the
+// tracks the lane carries from step to step, by greedy IoU matching inside a label, and get a track id.
+//
+// One workgroup of ONE wave per lane.  A thread holds the slots `lane`, `lane + 64`, ... of its lane's max_tracks slots in
+// registers (kMaxTracks / 64 = 4 at most).  The walk over the rows is serial, as greedy matching is; the work of a row is
+// parallel over the slots, and the (largest IoU, lowest id) choice is a ballot in the usual case of one candidate and a
+// shuffle reduction otherwise: the row loop has no barrier.  Spawning pairs the k-th unmatched row with the k-th free slot,
+// both counted by ballot + popcount.  Every float decision repeats the numpy definition (dagr_amd/streaming.py:
+// TrackDefinition) operation by operation; this library is built with -ffp-contract=off, and the fp32 division is correctly
+// rounded.
+#include "common.hpp"
+
+namespace dagr {
+namespace {
+
+constexpr int kMaxTracks = DAGR_TRACK_MAX_TRACKS;
+constexpr int kMaxDets = DAGR_TRACK_MAX_DETS;
+constexpr int kSlots = kMaxTracks / kWave;          // slots of one thread
+constexpr int64_t kNever = INT64_MIN;
+static_assert(kMaxTracks % kWave == 0 && kMaxDets % kWave == 0 && kMaxDets / kWave <= 32, "one flag word per thread");
+
+// The caller-owned state, as include/dagr_hip.h documents it: five arrays over [B, max_tracks] and next_id[B].
+struct Tracks {
+    int64_t *id;        // 0: the slot is free
+    int64_t *t_last;
+    float4 *box;
+    int32_t *label, *hits;
+    int64_t *next_id;
+};
+
+size_t carve_tracks(int B, int M, char *base, Tracks *out) {
+    const size_t n = (size_t)B * M;
+    Tracks t;
+    t.id = (int64_t *)base;
+    t.t_last = (int64_t *)(base + 8 * n);
+    t.box = (float4 *)(base + 16 * n);
+    t.label = (int32_t *)(base + 32 * n);
+    t.hits = (int32_t *)(base + 36 * n);
+    t.next_id = (int64_t *)(base + 40 * n);
+    if (out) *out = t;
+    return 40 * n + 8 * (size_t)B;
+}
+
+bool track_sizes_ok(int32_t B, int32_t M) { return B >= 1 && B <= 65535 && M >= 1 && M <= kMaxTracks; }
+
+__global__ __launch_bounds__(kBlock) void k_track_first_ids(int64_t *__restrict__ next_id, int B) {
+    const int b = blockIdx.x * kBlock + threadIdx.x;
+    if (b < B) next_id[b] = 1;
+}
+
+// numpy.minimum / numpy.maximum: a NaN operand comes back
+__device__ __forceinline__ float np_min(float a, float b) { return (a < b || a != a) ? a : b; }
+__device__ __forceinline__ float np_max(float a, float b) { return (a > b || a != a) ? a : b; }
+
+// TrackDefinition.iou, operation by operation: a is the row, b the track
+__device__ __forceinline__ float iou_xyxy(const float4 &a, const float4 &b) {
+    const float iw = np_min(a.z, b.z) - np_max(a.x, b.x);
+    const float ih = np_min(a.w, b.w) - np_max(a.y, b.y);
+    const float inter = (iw > 0.0f && ih > 0.0f) ? iw * ih : 0.0f;
+    const float uni = ((a.z - a.x) * (a.w - a.y) + (b.z - b.x) * (b.w - b.y)) - inter;
+    return inter / uni;
+}
+
+__device__ __forceinline__ int lanes_below(uint64_t mask, int lane) { return __popcll(mask & ((1ull << lane) - 1ull)); }
+
+__global__ __launch_bounds__(kWave) void k_stream_track(Tracks st, int M, float iou_thr, int64_t max_age, float min_score,
+                                                        const float *__restrict__ det, const int32_t *__restrict__ n_keep,
+                                                        int A, const int64_t *__restrict__ t_ref,
+                                                        int64_t *__restrict__ track_id, int32_t *__restrict__ track_hits,
+                                                        int64_t *__restrict__ untracked) {
+    __shared__ float4 s_box[kMaxDets];          // the participating rows, in row order
+    __shared__ int32_t s_label[kMaxDets];
+    __shared__ int32_t s_row[kMaxDets];         // their row in det
+    __shared__ int32_t s_spawn[kMaxDets];       // k-th unmatched participating row
+
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int n = min(max(n_keep[b], 0), A);
+    const int64_t now = t_ref[b];
+    const float *rows = det + (int64_t)b * A * 6;
+    int64_t *out_id = track_id + (int64_t)b * A;
+    int32_t *out_hits = track_hits + (int64_t)b * A;
+    if (now == kNever) {                        // no reference instant yet: nothing is tracked, nothing changes
+        for (int i = lane; i < n; i += kWave) {
+            out_id[i] = 0;
+            out_hits[i] = 0;
+        }
+        return;
+    }
+
+    // ---- the lane's slots; retire what has not been seen for more than max_age
+    int64_t id[kSlots], seen[kSlots];
+    float4 box[kSlots];
+    int32_t label[kSlots], hits[kSlots];
+    const int64_t base = (int64_t)b * M;
+#pragma unroll
+    for (int k = 0; k < kSlots; k++) {
+        const int slot = k * kWave + lane;
+        id[k] = 0, seen[k] = 0, label[k] = 0, hits[k] = 0;
+        box[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (slot < M) {
+            id[k] = st.id[base + slot];
+            seen[k] = st.t_last[base + slot];
+            box[k] = st.box[base + slot];
+            label[k] = st.label[base + slot];
+            hits[k] = st.hits[base + slot];
+            if (id[k] != 0 && now - seen[k] > max_age) id[k] = 0;
+        }
+    }
+
+    // ---- the eligible rows, 64 at a time: the first kMaxDets of them take part and go to the LDS in row order
+    int n_eligible = 0;
+    for (int first = 0; first < n; first += kWave) {
+        const int i = first + lane;
+        float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float score = 0.0f, cls = 0.0f;
+        if (i < n) {
+            const float *p = rows + (int64_t)i * 6;
+            r = make_float4(p[0], p[1], p[2], p[3]);
+            score = p[4];
+            cls = p[5];
+        }
+        const bool eligible = i < n && score >= min_score;         // (a NaN score compares false)
+        const uint64_t mask = __ballot(eligible);
+        const int rank = n_eligible + lanes_below(mask, lane);
+        n_eligible += __popcll(mask);
+        if (eligible && rank < kMaxDets) {
+            s_box[rank] = r;
+            s_label[rank] = (int32_t)cls;
+            s_row[rank] = i;
+        } else if (i < n) {
+            out_id[i] = 0;
+            out_hits[i] = 0;
+        }
+    }
+    const int P = min(n_eligible, kMaxDets);
+    __syncthreads();
+
+    // ---- match: the rows in order, every thread against its own slots; thread r % 64 remembers the unmatched row r
+    uint32_t taken = 0, unmatched = 0;
+    for (int r = 0; r < P; r++) {
+        const float4 d = s_box[r];
+        const int32_t cls = s_label[r];
+        float best = 0.0f;
+        int64_t best_id = 0;
+        int best_k = -1;
+#pragma unroll
+        for (int k = 0; k < kSlots; k++) {
+            if (id[k] == 0 || label[k] != cls || ((taken >> k) & 1u)) continue;
+            const float v = iou_xyxy(d, box[k]);
+            if (!(v >= iou_thr)) continue;                             // (a NaN IoU never matches)
+            if (best_k < 0 || v > best || (v == best && id[k] < best_id)) {
+                best = v;
+                best_id = id[k];
+                best_k = k;
+            }
+        }
+        uint64_t cand = __ballot(best_k >= 0);
+        if (cand == 0) {
+            if (lane == (r & 63)) unmatched |= 1u << (r >> 6);
+            continue;
+        }
+        if (cand & (cand - 1)) {                                      // several threads have one: largest IoU, lowest id
+            float top = best_k >= 0 ? best : -1.0f;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) top = fmaxf(top, __shfl_xor(top, off, kWave));
+            cand = __ballot(best_k >= 0 && best == top);
+            if (cand & (cand - 1)) {
+                int64_t low = (best_k >= 0 && best == top) ? best_id : INT64_MAX;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    const int64_t o = __shfl_xor(low, off, kWave);
+                    low = o < low ? o : low;
+                }
+                cand = __ballot(best_k >= 0 && best == top && best_id == low);
+            }
+        }
+        if (lane == __ffsll((unsigned long long)cand) - 1) {
+            const int row = s_row[r];
+#pragma unroll
+            for (int k = 0; k < kSlots; k++) {
+                if (k != best_k) continue;
+                box[k] = d;
+                seen[k] = now;
+                hits[k] += 1;
+                taken |= 1u << k;
+                out_id[row] = id[k];
+                out_hits[row] = hits[k];
+            }
+        }
+    }
+
+    // ---- spawn: the k-th unmatched row takes the k-th free slot and the id next_id + k
+    int n_unmatched = 0;
+#pragma unroll
+    for (int q = 0; q < kMaxDets / kWave; q++) {
+        const bool mine = (unmatched >> q) & 1u;
+        const uint64_t mask = __ballot(mine);
+        if (mine) s_spawn[n_unmatched + lanes_below(mask, lane)] = q * kWave + lane;
+        n_unmatched += __popcll(mask);
+    }
+    __syncthreads();
+    const int64_t first_id = st.next_id[b];
+    int n_free = 0;
+    int free_rank[kSlots];
+#pragma unroll
+    for (int k = 0; k < kSlots; k++) {
+        const bool is_free = k * kWave + lane < M && id[k] == 0;
+        const uint64_t mask = __ballot(is_free);
+        free_rank[k] = is_free ? n_free + lanes_below(mask, lane) : -1;
+        n_free += __popcll(mask);
+    }
+    const int n_spawn = min(n_unmatched, n_free);
+#pragma unroll
+    for (int k = 0; k < kSlots; k++) {
+        if (free_rank[k] < 0 || free_rank[k] >= n_spawn) continue;
+        const int r = s_spawn[free_rank[k]];
+        id[k] = first_id + free_rank[k];
+        seen[k] = now;
+        box[k] = s_box[r];
+        label[k] = s_label[r];
+        hits[k] = 1;
+    }
+    for (int k = lane; k < n_unmatched; k += kWave) {              // the rows' own outputs; past the free slots: untracked
+        const int row = s_row[s_spawn[k]];
+        out_id[row] = k < n_spawn ? first_id + k : 0;
+        out_hits[row] = k < n_spawn ? 1 : 0;
+    }
+
+    // ---- the state goes back
+#pragma unroll
+    for (int k = 0; k < kSlots; k++) {
+        const int slot = k * kWave + lane;
+        if (slot < M) {
+            st.id[base + slot] = id[k];
+            st.t_last[base + slot] = seen[k];
+            st.box[base + slot] = box[k];
+            st.label[base + slot] = label[k];
+            st.hits[base + slot] = hits[k];
+        }
+    }
+    if (lane == 0) {
+        st.next_id[b] = first_id + n_spawn;
+        const int lost = (n_eligible - P) + (n_unmatched - n_spawn);
+        if (untracked && lost > 0) untracked[b] += lost;
+    }
+}
+
+}  // namespace
+}  // namespace dagr
+
+using namespace dagr;
+
+extern "C" size_t dagr_stream_track_bytes(int32_t B, int32_t max_tracks) {
+    if (!track_sizes_ok(B, max_tracks)) return 0;
+    return carve_tracks(B, max_tracks, nullptr, nullptr);
+}
+
+extern "C" int dagr_stream_track_reset(void *tracks, size_t bytes, int32_t B, int32_t max_tracks, void *stream) {
+    DAGR_CHECK_ARG(tracks != nullptr, "stream track: tracks is NULL");
+    DAGR_CHECK_ARG(track_sizes_ok(B, max_tracks), "stream track: B or max_tracks out of range (1 .. DAGR_TRACK_MAX_TRACKS)");
+    DAGR_CHECK_ARG(((uintptr_t)tracks & 15) == 0, "stream track: tracks must be 16-byte aligned");
+    Tracks st;
+    const size_t need = carve_tracks(B, max_tracks, (char *)tracks, &st);
+    DAGR_CHECK_ARG(bytes >= need, "stream track: state smaller than dagr_stream_track_bytes");
+    DAGR_CHECK_HIP(hipMemsetAsync(tracks, 0, need, (hipStream_t)stream));
+    k_track_first_ids<<<(unsigned)ceil_div(B, kBlock), kBlock, 0, (hipStream_t)stream>>>(st.next_id, B);
+    DAGR_CHECK_LAUNCH();
+    return DAGR_OK;
+}
+
+extern "C" int dagr_stream_track(void *tracks, size_t bytes, int32_t B, int32_t max_tracks, float iou, int64_t max_age_us,
+                                 float min_score, const float *det, const int32_t *n_keep, int32_t A, const int64_t *t_ref,
+                                 int64_t *track_id, int32_t *track_hits, int64_t *untracked, void *stream) {
+    DAGR_CHECK_ARG(track_sizes_ok(B, max_tracks), "stream track: B or max_tracks out of range (1 .. DAGR_TRACK_MAX_TRACKS)");
+    DAGR_CHECK_ARG(iou > 0.0f && iou <= 1.0f, "stream track: iou must be in (0, 1]");
+    DAGR_CHECK_ARG(max_age_us >= 0, "stream track: max_age_us must not be negative");
+    DAGR_CHECK_ARG(A >= 0 && A <= (1 << 24), "stream track: A out of range");
+    DAGR_CHECK_ARG(tracks && n_keep && t_ref, "stream track: NULL pointer");
+    DAGR_CHECK_ARG(A == 0 || (det && track_id && track_hits), "stream track: NULL detections or outputs");
+    DAGR_CHECK_ARG(((uintptr_t)tracks & 15) == 0 && (((uintptr_t)t_ref | (uintptr_t)track_id | (uintptr_t)untracked) & 7) == 0 &&
+                       (((uintptr_t)det | (uintptr_t)n_keep | (uintptr_t)track_hits) & 3) == 0,
+                   "stream track: tracks must be 16-byte aligned, int64 arrays 8-byte, fp32 / int32 arrays 4-byte");
+    Tracks st;
+    DAGR_CHECK_ARG(bytes >= carve_tracks(B, max_tracks, (char *)tracks, &st),
+                   "stream track: state smaller than dagr_stream_track_bytes");
+    k_stream_track<<<(unsigned)B, kWave, 0, (hipStream_t)stream>>>(st, max_tracks, iou, max_age_us, min_score, det, n_keep, A,
+                                                                 t_ref, track_id, track_hits, untracked);
+    DAGR_CHECK_LAUNCH();
+    return DAGR_OK;
+}

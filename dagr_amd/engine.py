@@ -404,7 +404,10 @@ class StreamState:
 
     A capped stream (``max_lane_events = N``, ``dagr_stream_stage_capped``) keeps the newest ``N`` events of every lane at
     most: no window exceeds ``B * N``, which bounds the host's bound too, and ``lane_dropped`` accumulates on the device
-    what the count rule removed."""
+    what the count rule removed.
+
+    A tracking stream (``enable_track``) owns the tracker's state (``dagr_stream_track``): the lanes' track slots,
+    ``lane_untracked``, and the step's ``track_ids`` / ``track_hits``."""
 
     def __init__(self, batch_size, window_us, device, max_lane_events=None):
         self.B, self.window_us, self.device = int(batch_size), int(window_us), torch.device(device)
@@ -427,6 +430,63 @@ class StreamState:
         self.front_state, self.front_cap, self.front_out = None, 0, None
         self.noise = None                               # (W_in, H_in, denoise_us or 0, refractory_us or 0) of a filtering stream
         self.noise_state, self.noise_cap, self.noise_out, self.lane_filtered = None, 0, None, None
+        self.track = None                               # the options of a tracking stream (dagr.streaming._track_options)
+        self.track_state, self.lane_untracked, self.track_ids, self.track_hits = None, None, None, None
+        self._t_ref = None                              # (state pointer, capacity, where its t_ref[B] lives)
+
+    # ------------------------------------------------------------------------------------ track ids
+    def enable_track(self, options):
+        """Every step ends with ``dagr_stream_track``: ``options`` as ``dagr.streaming._track_options`` returns them.
+        Allocates the lanes' slots, empty, and ``lane_untracked``."""
+        self.track = dict(options)
+        L, M = _lib.lib(), self.track["max_tracks"]
+        nbytes = L.dagr_stream_track_bytes(self.B, M)
+        if nbytes == 0:
+            raise RuntimeError(f"dagr_stream_track_bytes({self.B}, {M}): out of range")
+        self.track_state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.lane_untracked = torch.zeros((self.B,), dtype=torch.int64, device=self.device)
+        _lib.check(L.dagr_stream_track_reset(_lib.ptr(self.track_state), nbytes, self.B, M, _lib.cur_stream(self.device)),
+                   "stream_track_reset")
+
+    def run_track(self, det, n_keep):
+        """``dagr_stream_track`` on a step's detections, at the reference instants the step's staging left in the stream
+        state: ``track_ids`` int64 [B, A] and ``track_hits`` int32 [B, A], valid until the next step."""
+        B, A = int(det.shape[0]), int(det.shape[1])
+        if B != self.B or det.dtype != torch.float32 or not det.is_contiguous() or n_keep.dtype != torch.int32:
+            raise RuntimeError(f"run_track: det must be contiguous fp32 [{self.B}, A, 6] and n_keep int32 [{self.B}]")
+        if self.track_ids is None or tuple(self.track_ids.shape) != (B, A):
+            self.track_ids = torch.zeros((B, A), dtype=torch.int64, device=self.device)
+            self.track_hits = torch.zeros((B, A), dtype=torch.int32, device=self.device)
+        L, P, o = _lib.lib(), _lib.ptr, self.track
+        if self._t_ref is None or self._t_ref[:2] != (self.state.data_ptr(), self.cap):     # (the state has grown)
+            where = L.dagr_stream_t_ref(P(self.state), self.B, self.cap)
+            if not where:
+                raise RuntimeError(f"dagr_stream_t_ref(B = {self.B}, capacity = {self.cap}): out of range")
+            self._t_ref = (self.state.data_ptr(), self.cap, ctypes.c_void_p(where))
+        _lib.check(L.dagr_stream_track(P(self.track_state), self.track_state.numel(), self.B, o["max_tracks"], o["iou"],
+                                       o["max_age_us"], o["min_score"], P(det), P(n_keep), A, self._t_ref[2],
+                                       P(self.track_ids), P(self.track_hits), P(self.lane_untracked),
+                                       _lib.cur_stream(self.device)), "stream_track")
+
+    def untracked(self):
+        """Per-lane eligible rows that got no track id, int64 [B] (synchronises)."""
+        if self.track is None:
+            raise RuntimeError("this stream does not track (track=): it has no untracked count")
+        return self.lane_untracked.cpu().numpy()
+
+    def track_slots(self):
+        """The lanes' slots read back as ``(id int64, t_last int64, box fp32[., 4], label int32, hits int32)`` over
+        ``[B, max_tracks]`` and ``next_id int64 [B]`` -- the layout include/dagr_hip.h documents (copies; synchronises)."""
+        if self.track is None:
+            raise RuntimeError("this stream does not track (track=): it has no tracks")
+        B, M = self.B, self.track["max_tracks"]
+        n, raw = B * M, self.track_state
+        return (raw[:8 * n].view(torch.int64).view(B, M).cpu().numpy(),
+                raw[8 * n:16 * n].view(torch.int64).view(B, M).cpu().numpy(),
+                raw[16 * n:32 * n].view(torch.float32).view(B, M, 4).cpu().numpy(),
+                raw[32 * n:36 * n].view(torch.int32).view(B, M).cpu().numpy(),
+                raw[36 * n:40 * n].view(torch.int32).view(B, M).cpu().numpy(),
+                raw[40 * n:40 * n + 8 * B].view(torch.int64).cpu().numpy())
 
     # ------------------------------------------------------------------------------------ sensor noise
     def enable_denoise(self, sensor_w, sensor_h, denoise_us=None, refractory_us=None):
@@ -561,6 +621,11 @@ class StreamState:
                                                             self.noise[0], self.noise[1], self.noise_cap,
                                                             _lib.cur_stream(self.device)), "stream_denoise_reset")
             self.lane_filtered.zero_()
+        if self.track_state is not None:
+            _lib.check(_lib.lib().dagr_stream_track_reset(_lib.ptr(self.track_state), self.track_state.numel(), self.B,
+                                                          self.track["max_tracks"], _lib.cur_stream(self.device)),
+                       "stream_track_reset")
+            self.lane_untracked.zero_()
         self.status.zero_()
         self.lane_count.zero_()
         self.lane_dropped.zero_()
@@ -1867,6 +1932,9 @@ class WindowEngine:
         windows never exceed ``B * N``, which the buffers meet once -- no growth and no re-capture after its first step.
         A filtering stream (``st.noise``) runs ``dagr_stream_denoise`` on the push before anything else and stages what is
         left through the ``_dev`` entries, with the unfiltered push as the clock.
+        A tracking stream (``st.track``) ends the step with ``dagr_stream_track`` on the step's detections and the reference
+        instants the staging left: one plain launch on the same stream, outside the captured graphs, so every mode and
+        body is covered without a re-capture; ``st.track_ids`` / ``st.track_hits`` hold the result.
         Returns ``(out, (det, n_keep))``, both valid until the engine's next call.
 
         ``--use_image``: the window has two bodies.  The frame body runs the image branch on the stream's frame
@@ -1977,6 +2045,8 @@ class WindowEngine:
         self._stream_pending = st
         det = (self._det, self._n_keep) if self._post_fresh else \
             postprocess_device(out, self.num_classes, key[0], key[1], self.H, self.W)
+        if st.track is not None:                     # a plain launch behind the window, captured or not: the track ids
+            st.run_track(*det)
         return out, det
 
     def stream_counted(self, st):

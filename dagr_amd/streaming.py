@@ -81,9 +81,38 @@ Frames (``--use_image`` models): every lane has a frame in force, the last one a
 (``image=``, fp32 [B, 3, H, W]) or as a raw sensor frame (``frame=``, uint8 [H_f, W_f, 3], which ``dagr_stream_frame``
 prepares on the device; ``frame_definition`` below states what that is).  A step's result is what ``model(..., reset=True)``
 returns on the window with the frames in force, whether the step ran the image branch or sampled the maps it held.
+
+Track ids (``track=``: ``None`` is off, ``True`` takes the defaults, a dict sets ``iou`` (fp32 in (0, 1], default 0.3),
+``max_age_us`` (int >= 0, default 20000), ``min_score`` (float, default 0.0) and ``max_tracks`` (1 ..
+``DAGR_TRACK_MAX_TRACKS = 256``, default 64)): a step's detections are associated with the lane's tracks of the step
+before, on the device, behind everything above and without changing any of it.  ``TrackDefinition`` below states it once in
+numpy.  Every lane owns ``max_tracks`` slots, each free or holding a track -- ``box`` fp32[4] (x1, y1, x2, y2), ``label``
+int32, ``id`` int64, ``t_last`` int64, ``hits`` int32 --, ``next_id`` int64, which starts at 1 (id 0 means "no track"), and
+``untracked`` int64, cumulative; after construction and after ``reset()`` every slot is free, ``next_id = 1`` and
+``untracked = 0``.  One step of lane ``b`` takes the rows ``det[b, :n_keep[b]]`` in the order ``dagr_postprocess`` leaves
+them, by descending score, and the lane's ``t_ref[b]``:
+
+1. a lane without a reference instant yet (``t_ref`` is "never"): every row gets id 0 and hits 0, nothing else happens;
+2. retire: a track with ``t_ref - t_last > max_age_us`` is freed; an age equal to ``max_age_us`` stays;
+3. eligible rows have ``score >= min_score`` (a NaN score is not eligible); the first ``DAGR_TRACK_MAX_DETS = 256`` eligible
+   rows in row order take part, every further eligible row gets id 0 and adds 1 to ``untracked``, a row that is not eligible
+   gets id 0 and is not counted;
+4. match: the participating rows in row order, greedily -- among the live tracks with the row's label that no earlier row
+   of this step has matched, the one with the largest IoU, the LOWEST id on a tie; if that IoU is ``>= iou`` the track takes
+   the row's box, ``t_last = t_ref``, ``hits += 1``, and the row's id and hits are the track's.  A NaN IoU never matches;
+5. spawn: when every row has been through 4, the participating rows that did not match take, in row order, the free slots
+   in ascending slot order (slots freed in 2 count), each with ``id = next_id++`` and ``hits = 1``; without a free slot the
+   row gets id 0 and adds 1 to ``untracked``.
+
+The IoU is fp32, operation by operation: ``iw = min(ax2, bx2) - max(ax1, bx1)``, ``ih = min(ay2, by2) - max(ay1, by1)``
+(``numpy.minimum`` / ``maximum``), ``inter = iw * ih if iw > 0 and ih > 0 else 0``,
+``union = ((ax2 - ax1) * (ay2 - ay1) + (bx2 - bx1) * (by2 - by1)) - inter``, ``iou = inter / union`` -- the device repeats
+exactly these without contraction, with a correctly rounded division.  Lanes are independent; there is no motion model and
+no matching across labels.
 """
 import numpy as np
 
+from ._lib import DEFINES
 from .utils.synthetic import format_data_np
 
 STATUS_BITS = ((1, "a timestamp goes backwards inside a lane (within a push or against the lane's newest event)"),
@@ -169,6 +198,154 @@ def denoise_definition(last_t, x, y, t, batch, denoise_us=None, refractory_us=No
         keep[i] = supported and not refractory
         lane[yi, xi] = ti
     return keep
+
+
+DAGR_TRACK_MAX_TRACKS = DEFINES["DAGR_TRACK_MAX_TRACKS"]       # include/dagr_hip.h states them; the binding reads it
+DAGR_TRACK_MAX_DETS = DEFINES["DAGR_TRACK_MAX_DETS"]
+TRACK_DEFAULTS = dict(iou=0.3, max_age_us=20000, min_score=0.0, max_tracks=64)
+TRACK_DTYPE = [("id", "<i8"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("label", "<i4"),
+               ("t_last", "<i8"), ("hits", "<i4")]
+
+
+def _track_options(track, who):
+    """``track=`` of a stream, checked: None (off) or the dict of ``iou``, ``max_age_us``, ``min_score`` and ``max_tracks``
+    with the defaults filled in; refusals by name."""
+    if track is None:
+        return None
+    if track is True:
+        track = {}
+    if not isinstance(track, dict):
+        raise ValueError(f"{who}: track = {track!r} must be None (off), True (the defaults) or a dict of "
+                         f"{', '.join(TRACK_DEFAULTS)}")
+    unknown = sorted(set(track) - set(TRACK_DEFAULTS))
+    if unknown:
+        raise ValueError(f"{who}: track has no option {unknown[0]!r} (it has {', '.join(TRACK_DEFAULTS)})")
+    opt = dict(TRACK_DEFAULTS, **track)
+
+    def is_int(v):
+        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+    def is_real(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and v == v
+    if not is_real(opt["iou"]) or not 0 < np.float32(opt["iou"]) <= 1:
+        raise ValueError(f"{who}: track iou = {opt['iou']!r} must be a float in (0, 1] (as fp32)")
+    if not is_int(opt["max_age_us"]) or not 0 <= int(opt["max_age_us"]) < 1 << 63:
+        raise ValueError(f"{who}: track max_age_us = {opt['max_age_us']!r} must be an int of microseconds >= 0")
+    if not is_real(opt["min_score"]):
+        raise ValueError(f"{who}: track min_score = {opt['min_score']!r} must be a float (not NaN)")
+    if not is_int(opt["max_tracks"]) or not 1 <= int(opt["max_tracks"]) <= DAGR_TRACK_MAX_TRACKS:
+        raise ValueError(f"{who}: track max_tracks = {opt['max_tracks']!r} must be an int in 1..DAGR_TRACK_MAX_TRACKS = "
+                         f"{DAGR_TRACK_MAX_TRACKS}")
+    return dict(iou=float(np.float32(opt["iou"])), max_age_us=int(opt["max_age_us"]),
+                min_score=float(np.float32(opt["min_score"])), max_tracks=int(opt["max_tracks"]))
+
+
+class TrackDefinition:
+    """The tracker of the module docstring in numpy: ``step(det, n_keep, t_ref)`` is one step of every lane and returns
+    ``(track_id int64 [B, A], track_hits int32 [B, A])`` with the rows at and behind ``n_keep[b]`` zero.  The state is the
+    slots' arrays ``id`` (0: free), ``t_last``, ``box``, ``label``, ``hits`` over ``[B, max_tracks]``, ``next_id`` and
+    ``untracked`` over ``[B]``.  ``events`` counts what has happened so far (matches, spawns, retirements, slots taken
+    again, untracked rows) so that a test can tell a run that exercises the rules from one that does not.  The yardstick of
+    ``dagr_stream_track``; nothing on the device path calls it."""
+
+    def __init__(self, batch_size, track=True):
+        self.B = int(batch_size)
+        self.options = _track_options(track, "TrackDefinition")
+        if self.options is None:
+            raise ValueError("TrackDefinition: track = None is a stream that does not track")
+        self.reset()
+
+    def reset(self):
+        B, M = self.B, self.options["max_tracks"]
+        self.id, self.t_last = np.zeros((B, M), np.int64), np.zeros((B, M), np.int64)
+        self.box = np.zeros((B, M, 4), np.float32)
+        self.label, self.hits = np.zeros((B, M), np.int32), np.zeros((B, M), np.int32)
+        self.next_id, self.untracked = np.ones(B, np.int64), np.zeros(B, np.int64)
+        self._used = np.zeros((B, M), bool)
+        self.events = dict(matched=0, spawned=0, retired=0, reused=0, untracked=0)
+
+    @staticmethod
+    def iou(a, b):
+        """fp32, operation by operation as ``dagr_stream_track`` repeats them; ``a`` the row, ``b`` the track."""
+        f = np.float32
+        a, b = [f(v) for v in a], [f(v) for v in b]
+        with np.errstate(all="ignore"):
+            iw = f(np.minimum(a[2], b[2]) - np.maximum(a[0], b[0]))
+            ih = f(np.minimum(a[3], b[3]) - np.maximum(a[1], b[1]))
+            inter = f(iw * ih) if iw > 0 and ih > 0 else f(0)
+            union = f(f(f(f(a[2] - a[0]) * f(a[3] - a[1])) + f(f(b[2] - b[0]) * f(b[3] - b[1]))) - inter)
+            return f(inter / union)
+
+    def step(self, det, n_keep, t_ref):
+        det = np.asarray(det, np.float32)
+        B, A = det.shape[:2]
+        if B != self.B or det.shape[2] != 6:
+            raise ValueError(f"TrackDefinition: det is fp32 [{self.B}, A, 6], got {det.shape}")
+        n_keep = np.broadcast_to(np.asarray(n_keep, np.int64).reshape(-1), (B,))
+        t_ref = np.broadcast_to(np.asarray(t_ref, np.int64).reshape(-1), (B,))
+        o = self.options
+        thr, min_score = np.float32(o["iou"]), np.float32(o["min_score"])
+        ids, hits = np.zeros((B, A), np.int64), np.zeros((B, A), np.int32)
+        for b in range(B):
+            n, now = min(max(int(n_keep[b]), 0), A), int(t_ref[b])
+            if now == NEVER:
+                continue
+            for s in np.flatnonzero(self.id[b]):                   # retire
+                if now - int(self.t_last[b, s]) > o["max_age_us"]:
+                    self.id[b, s] = 0
+                    self.events["retired"] += 1
+            eligible = [i for i in range(n) if det[b, i, 4] >= min_score]         # (a NaN score compares false)
+            lost = max(0, len(eligible) - DAGR_TRACK_MAX_DETS)
+            unmatched, taken = [], set()
+            for i in eligible[:DAGR_TRACK_MAX_DETS]:               # match
+                with np.errstate(all="ignore"):
+                    label = int(det[b, i, 5].astype(np.int32))
+                best, best_s = None, None
+                for s in np.flatnonzero(self.id[b]):
+                    if int(s) in taken or int(self.label[b, s]) != label:
+                        continue
+                    v = self.iou(det[b, i, :4], self.box[b, s])
+                    if not v >= thr:                               # (a NaN IoU never matches)
+                        continue
+                    if best is None or v > best or (v == best and self.id[b, s] < self.id[b, best_s]):
+                        best, best_s = v, int(s)
+                if best_s is None:
+                    unmatched.append((i, label))
+                    continue
+                taken.add(best_s)
+                self.box[b, best_s], self.t_last[b, best_s] = det[b, i, :4], now
+                self.hits[b, best_s] += 1
+                ids[b, i], hits[b, i] = self.id[b, best_s], self.hits[b, best_s]
+                self.events["matched"] += 1
+            free = [int(s) for s in np.flatnonzero(self.id[b] == 0)]
+            for (i, label), s in zip(unmatched, free):             # spawn
+                self.id[b, s], self.t_last[b, s], self.box[b, s] = self.next_id[b], now, det[b, i, :4]
+                self.label[b, s], self.hits[b, s] = label, 1
+                ids[b, i], hits[b, i] = self.next_id[b], 1
+                self.next_id[b] += 1
+                self.events["spawned"] += 1
+                self.events["reused"] += int(self._used[b, s])
+                self._used[b, s] = True
+            lost += max(0, len(unmatched) - len(free))
+            self.untracked[b] += lost
+            self.events["untracked"] += lost
+        return ids, hits
+
+    def tracks(self):
+        """Per lane the live tracks as a ``TRACK_DTYPE`` array sorted by id (what ``EventStream.tracks()`` returns)."""
+        return [tracks_from_arrays(self.id[b], self.t_last[b], self.box[b], self.label[b], self.hits[b])
+                for b in range(self.B)]
+
+
+def tracks_from_arrays(ids, t_last, box, label, hits):
+    """One lane's slots -> its live tracks, a ``TRACK_DTYPE`` array sorted by id."""
+    live = np.flatnonzero(ids)
+    live = live[np.argsort(ids[live], kind="stable")]
+    out = np.zeros(len(live), TRACK_DTYPE)
+    out["id"], out["t_last"], out["label"], out["hits"] = ids[live], t_last[live], label[live], hits[live]
+    for k, name in enumerate(("x1", "y1", "x2", "y2")):
+        out[name] = box[live, k]
+    return out
 
 
 def frame_definition(raw, fx, fy, W, H, bgr=False):
@@ -347,6 +524,12 @@ class EventStream:
     background activity and hot pixels from every push on the device, before anything else (module docstring);
     ``filtered()`` counts what it removed, ``last_stamps()`` reads the stamp maps back.  A stream built without them issues
     exactly the launches it issues without the filter.
+    ``track`` (``None``: off, ``True``: the defaults, or a dict of ``iou``, ``max_age_us``, ``min_score``, ``max_tracks``):
+    every step ends with ``dagr_stream_track``, one more launch and no host wait, which gives every detection the id of
+    the track it continues (module docstring).  ``track_ids`` / ``track_hits`` are the step's device tensors, ``step()``
+    adds ``"track_ids"`` / ``"track_hits"`` to every lane's dict, ``tracks()`` reads the live tracks back and
+    ``untracked()`` counts the rows that got no id.  A stream built without it issues exactly the launches it issues
+    without the tracker.
     ``frame_size`` (``(W_f, H_f)``) and ``frame_bgr``: the steps may carry raw sensor frames (``frame=``), which
     ``dagr_stream_frame`` turns into the model's image on the device (``frame_definition``) with the stream's
     ``downsample`` factors, or 1 without ``downsample``.
@@ -361,9 +544,10 @@ class EventStream:
     """
 
     def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
-                 max_lane_events=None, denoise_us=None, refractory_us=None):
+                 max_lane_events=None, denoise_us=None, refractory_us=None, track=None):
         import torch
         self.model = model
+        self.track = _track_options(track, "EventStream")
         time_window = int(getattr(model.args, "time_window_us", 1000000))
         self.window_us, self.max_lane_events = _window_and_cap(window_us, max_lane_events, time_window,
                                                                getattr(model.args, "batch_size", 1), "EventStream")
@@ -398,6 +582,8 @@ class EventStream:
             self.state.enable_front(fx, fy, w_in, h_in, eng.W, eng.H)
         if self.denoise_us is not None or self.refractory_us is not None:
             self.state.enable_denoise(w_in, h_in, self.denoise_us, self.refractory_us)
+        if self.track is not None:
+            self.state.enable_track(self.track)
         self._zeros = None
         self.outputs = None      # the last step's decoded head outputs [B, A, 5 + classes], valid until the engine's next call
         self._frame = None
@@ -413,6 +599,9 @@ class EventStream:
     # ------------------------------------------------------------------------------------ frames
     frame_steps = property(lambda self: self.state.frame_steps, doc="steps that ran the frame body (the full window)")
     held_steps = property(lambda self: self.state.held_steps, doc="steps that ran the held body (no image branch)")
+    track_ids = property(lambda self: self.state.track_ids, doc="the last step's track ids int64 [B, A] on the device (row "
+                         "i of lane b belongs to det[b, i]; 0: no track), valid until the next step; None without track=")
+    track_hits = property(lambda self: self.state.track_hits, doc="the last step's hit counts int32 [B, A], as track_ids")
 
     def held_maps(self):
         """The live ``(feats, cnn_out)`` tensors of the frame in force -- what the next held step samples -- or None when
@@ -525,6 +714,11 @@ class EventStream:
         det, n_keep = self.step_device(xy, t, p, batch=batch, t_now=t_now, image=image, frame=frame,
                                        frame_lanes=frame_lanes)
         detections = detections_from_device(det, n_keep)        # the step's one synchronisation
+        if self.track is not None:                              # cut by the counts that read-back brought
+            ids, hits = self.state.track_ids.clone(), self.state.track_hits.clone()
+            for b, d in enumerate(detections):
+                n = int(d["scores"].shape[0])
+                d["track_ids"], d["track_hits"] = ids[b, :n], hits[b, :n]
         self.model.engine().stream_counted(self.state)          # the counts came back with it
         if self.model.check_device_status:
             self.check_status()
@@ -557,9 +751,21 @@ class EventStream:
         synchronises)."""
         return self.state.last_stamps()
 
+    def tracks(self):
+        """Per lane the live tracks of a tracking stream, a ``TRACK_DTYPE`` array (``id, x1, y1, x2, y2, label, t_last,
+        hits``) sorted by id (copies; synchronises)."""
+        ids, t_last, box, label, hits, _ = self.state.track_slots()
+        return [tracks_from_arrays(ids[b], t_last[b], box[b], label[b], hits[b]) for b in range(self.B)]
+
+    def untracked(self):
+        """Eligible rows per lane that got no track id since construction / ``reset()`` -- beyond the first
+        ``DAGR_TRACK_MAX_DETS`` of a step, or unmatched with every slot taken: int64 [B] (synchronises)."""
+        return self.state.untracked()
+
     def reset(self):
         """Empty the stream: no resident events, no reference instants, zero change maps, empty stamp maps, zero dropped and
-        filtered counts, a clear status word, zero step counters.  The frame in force stays, and the next step runs it through the image branch again."""
+        filtered counts, a clear status word, zero step counters; no tracks, ids from 1 again, a zero untracked count.  The
+        frame in force stays, and the next step runs it through the image branch again."""
         self.state.reset()
 
     def check_status(self):

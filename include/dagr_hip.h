@@ -329,6 +329,66 @@ int dagr_stream_frame(const uint8_t *frames, int64_t frame_stride, int64_t row_s
                       float *out, int32_t B, int64_t stride_b, int64_t stride_c, int64_t stride_y, int64_t stride_x,
                       int32_t *status, void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * Event stream tracker: the detections of a step get track ids, on the device
+ *   A step's detection list says nothing about the step before.  dagr_stream_track associates the rows of every lane with
+ *   the tracks the lane carries from step to step -- greedy IoU matching inside a label -- and writes a track id and a hit
+ *   count per row.  One launch (one wave per lane), no host synchronisation.  dagr_amd/streaming.py: TrackDefinition is the
+ *   same in numpy.
+ *
+ * A lane owns max_tracks slots, each free or holding a track: box fp32[4] (x1, y1, x2, y2), label int32, id int64 >= 1,
+ * t_last int64, hits int32; and next_id int64, 1 after a reset (id 0 means "no track").  One call is one step of every
+ * lane b on the rows det[b, 0 .. n_keep[b]) -- (x1, y1, x2, y2, score, label) fp32 as dagr_postprocess leaves them,
+ * n_keep[b] clamped to 0..A -- at the instant t_ref[b]:
+ *   never:    t_ref[b] = INT64_MIN (the lane has no reference instant yet): every row gets id 0 and hits 0, nothing else
+ *             changes;
+ *   retire:   a track with t_ref[b] - t_last > max_age_us is freed (an age equal to max_age_us stays; int64 arithmetic);
+ *   eligible: rows with score >= min_score (a NaN score is not).  The first DAGR_TRACK_MAX_DETS eligible rows in row order
+ *             take part; every further eligible row gets id 0 and adds 1 to untracked[b]; a row that is not eligible gets
+ *             id 0 and is not counted;
+ *   match:    the participating rows in row order, greedily: among the live tracks with the row's label ((int32_t)label)
+ *             that no earlier row of this step has matched, the one with the largest IoU, the LOWEST id on a tie; if that
+ *             IoU is >= iou the track takes the row's box, t_last = t_ref[b], hits += 1, and the row gets the track's id and
+ *             hits.  A NaN IoU (0 / 0 of two empty boxes) never matches.  Labels are finite class indices, as
+ *             dagr_postprocess writes them: the conversion of a NaN or out-of-int32-range label is not specified (the device
+ *             gives 0 or a saturated value, numpy's astype INT32_MIN), and equality with the definition holds for finite ones;
+ *   spawn:    after all rows have been matched, the participating rows that did not match take, in row order, the free slots
+ *             in ascending slot order (slots freed by this step's retirement included): id = next_id++, hits = 1,
+ *             t_last = t_ref[b].  Without a free slot the row gets id 0 and adds 1 to untracked[b].
+ * The IoU of row a and track b, in fp32 and in this order, without contraction:
+ *   iw = min(ax2, bx2) - max(ax1, bx1);  ih = min(ay2, by2) - max(ay1, by1);  (min / max hand a NaN operand on)
+ *   inter = iw > 0 && ih > 0 ? iw * ih : 0;  uni = ((ax2 - ax1) * (ay2 - ay1) + (bx2 - bx1) * (by2 - by1)) - inter;
+ *   iou = inter / uni  (a correctly rounded division).
+ *
+ * tracks: dagr_stream_track_bytes(B, max_tracks) bytes (0: B outside 1..65535 or max_tracks outside
+ *         1..DAGR_TRACK_MAX_TRACKS), 16-byte aligned, dagr_stream_track_reset before the first step and to empty it.  With
+ *         n = B * max_tracks it holds, back to back, slot s of lane b at index b * max_tracks + s:
+ *           id     int64 [n]    at byte 0        (0: the slot is free, and its other fields mean nothing)
+ *           t_last int64 [n]    at byte  8 * n
+ *           box    fp32  [n, 4] at byte 16 * n
+ *           label  int32 [n]    at byte 32 * n
+ *           hits   int32 [n]    at byte 36 * n
+ *           next_id int64 [B]   at byte 40 * n
+ * track_id int64[B, A] and track_hits int32[B, A]: rows < n_keep[b] are written, the rest are left as they are.
+ * untracked int64[B] (may be NULL): accumulated by plain stores of one thread per lane; the caller zeroes it.
+ * det fp32[B, A, 6], n_keep int32[B], t_ref int64[B]; all in device memory.
+ * DAGR_ERR_INVALID_ARG before any launch: B or max_tracks out of range, iou outside (0, 1], max_age_us < 0, A < 0, a state
+ * smaller than dagr_stream_track_bytes, NULL or misaligned pointers.
+ *
+ * dagr_stream_t_ref: where t_ref[B] lives inside a dagr_stream_stage state (device memory; pointer arithmetic on the host,
+ * nothing is launched or read), or NULL when B / capacity are out of range: the instants the last step left, which is what
+ * a stream hands to dagr_stream_track after its step.
+ * ------------------------------------------------------------------------ */
+#define DAGR_TRACK_MAX_TRACKS 256
+#define DAGR_TRACK_MAX_DETS 256
+size_t dagr_stream_track_bytes(int32_t B, int32_t max_tracks);
+int dagr_stream_track_reset(void *tracks, size_t bytes, int32_t B, int32_t max_tracks, void *stream);
+int dagr_stream_track(void *tracks, size_t bytes, int32_t B, int32_t max_tracks, float iou, int64_t max_age_us,
+                      float min_score, const float *det, const int32_t *n_keep, int32_t A, const int64_t *t_ref,
+                      int64_t *track_id, int32_t *track_hits, int64_t *untracked /* [B], accumulated; may be NULL */,
+                      void *stream);
+const int64_t *dagr_stream_t_ref(const void *state, int32_t B, int64_t capacity);
+
 /* The neighbour search alone, again, on the pixel index the last dagr_graph_build_window left in `workspace` (same N):
  * rewrites nbr_src / nbr_code / deg and the edge count.  For measurement (bench.py times the search kernels on their own
  * stream with HIP events); a product caller has no use for it. */

@@ -25,7 +25,13 @@ number of events the cap removed is printed with the summary.
 
 ``--denoise_us D`` / ``--refractory_us R``: the stream's noise filter, on the device and in front of everything else
 (``dagr.streaming``): an event is kept if one of its 8 neighbours saw an event in the last ``D`` microseconds and its own
-pixel saw none in the last ``R``.  The number of events the filter removed is printed with the summary."""
+pixel saw none in the last ``R``.  The number of events the filter removed is printed with the summary.
+
+``--track``: the stream gives every detection a track id on the device (``dagr.streaming``: greedy IoU matching inside a
+label against the tracks of the step before), tuned by ``--track_iou``, ``--track_max_age_us``, ``--track_min_score`` and
+``--max_tracks``.  ``detections_<sequence>.npy`` stays what it is; a second file ``tracks_<sequence>.npy`` holds the same
+rows in the same order with ``track_id`` (``<u8``, 0: no track) and ``hits`` (``<u4``) appended.  The number of distinct ids
+and of untracked detections is printed with the summary."""
 import time
 import types
 
@@ -33,8 +39,8 @@ import numpy as np
 import torch
 
 import _common as C
-from dagr.streaming import EventStream
-from dagr.utils.buffers import detections_to_records
+from dagr.streaming import EventStream, _track_options
+from dagr.utils.buffers import DETECTION_DTYPE, detections_to_records
 from dagr.utils.logging import set_up_logging_directory
 from dagr.utils import synthetic as syn
 
@@ -55,8 +61,44 @@ def stream_options(p):
                    "neighbours saw an event in the last D microseconds")
     g.add_argument("--refractory_us", type=int, default=None, help="noise filter: drop an event whose own pixel saw an "
                    "event less than R microseconds ago")
+    g.add_argument("--track", action="store_true", help="give every detection a track id, on the device")
+    g.add_argument("--track_iou", type=float, default=None, help="with --track: smallest IoU that continues a track "
+                   "(default 0.3)")
+    g.add_argument("--track_max_age_us", type=int, default=None, help="with --track: a track unseen for longer is dropped "
+                   "(default 20000)")
+    g.add_argument("--track_min_score", type=float, default=None, help="with --track: detections below this confidence get "
+                   "no id (default 0.0)")
+    g.add_argument("--max_tracks", type=int, default=None, help="with --track: tracks held at a time (default 64, at most 256)")
     g.add_argument("--raw_frames", action="store_true", help="the source's frames are sensor-size BGR uint8 frames: prepare "
                    "them on the device (crop, shrink by the --downsample factor, / 255)")
+
+
+TRACK_FLAGS = (("track_iou", "iou"), ("track_max_age_us", "max_age_us"), ("track_min_score", "min_score"),
+               ("max_tracks", "max_tracks"))
+TRACK_RECORD_DTYPE = DETECTION_DTYPE + [("track_id", "<u8"), ("hits", "<u4")]
+
+
+def track_options(a):
+    """``track=`` of the stream the flags describe: None without ``--track``, else the options that were given."""
+    given = {key: getattr(a, flag) for flag, key in TRACK_FLAGS if getattr(a, flag, None) is not None}
+    if not getattr(a, "track", False):
+        if given:
+            raise SystemExit(f"run_stream.py: --{[f for f, k in TRACK_FLAGS if k in given][0]} needs --track")
+        return None
+    try:
+        _track_options(given, "run_stream.py")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    return given
+
+
+def track_records(rec, det):
+    """``rec`` (``detections_to_records`` of ``det``) with the step's ``track_ids`` / ``track_hits`` appended."""
+    out = np.zeros(len(rec), TRACK_RECORD_DTYPE)
+    for name in rec.dtype.names:
+        out[name] = rec[name]
+    out["track_id"], out["hits"] = det["track_ids"].cpu().numpy(), det["track_hits"].cpu().numpy()
+    return out
 
 
 def sensor_size(a):
@@ -121,7 +163,8 @@ def play(a, model, source, dev):
     cap = getattr(a, "max_lane_events", None)
     stream = EventStream(model, window_us=a.window_us or None, downsample=a.downsample, sensor_size=sensor_size(a),
                          frame_size=raw_size, frame_bgr=True, max_lane_events=cap,
-                         denoise_us=getattr(a, "denoise_us", None), refractory_us=getattr(a, "refractory_us", None))
+                         denoise_us=getattr(a, "denoise_us", None), refractory_us=getattr(a, "refractory_us", None),
+                         track=track_options(a))
     t0, t1 = source.t_range()
     out, last_frame = [], None
     for t_step in range(int(t0) + a.step_us, int(t1) + 1, a.step_us):
@@ -143,6 +186,7 @@ def play(a, model, source, dev):
     a.stream_steps = (stream.frame_steps, stream.held_steps)      # (frame bodies, held bodies) of the run
     a.stream_dropped = int(stream.dropped().sum()) if cap is not None else None
     a.stream_filtered = int(stream.filtered().sum()) if stream.state.noise is not None else None
+    a.stream_untracked = int(stream.untracked().sum()) if stream.track is not None else None
     return out
 
 
@@ -157,6 +201,7 @@ def main(argv=None, model_factory=None, source=None):
     if a.step_us <= 0 or a.window_us < 0 or (a.window_us == 0 and not capped):
         raise SystemExit("run_stream.py: --step_us and --window_us must be positive (--window_us 0: the model's time "
                          "window, with --max_lane_events only)")
+    tracking = track_options(a) is not None
     a.batch_size = 1                       # one sequence: one lane
     world, rank, dev = C.distributed()
     torch.manual_seed(42)
@@ -174,9 +219,14 @@ def main(argv=None, model_factory=None, source=None):
     t_start = time.perf_counter()
     steps = play(a, net, source, dev)
     seconds = time.perf_counter() - t_start
-    rec = [detections_to_records({k: v.cpu() for k, v in det.items()}, np.uint64(t)) for t, det in steps]
-    rec = np.concatenate(rec) if rec else detections_to_records(dict(boxes=np.zeros((0, 4)), labels=np.zeros(0), scores=np.zeros(0)), 0)
-    rec = rec[np.argsort(rec["t"], kind="stable")]
+    per_step = [detections_to_records({k: v.cpu() for k, v in det.items()}, np.uint64(t)) for t, det in steps]
+    rec = np.concatenate(per_step) if per_step else \
+        detections_to_records(dict(boxes=np.zeros((0, 4)), labels=np.zeros(0), scores=np.zeros(0)), 0)
+    order = np.argsort(rec["t"], kind="stable")
+    rec = rec[order]
+    if tracking:        # the same rows in the same order, with the two fields appended
+        trk = [track_records(r, det) for r, (_, det) in zip(per_step, steps)]
+        trk = (np.concatenate(trk) if trk else np.zeros(0, TRACK_RECORD_DTYPE))[order]
     path = None
     if rank == 0:
         out_dir.mkdir(parents=True, exist_ok=True)
@@ -187,9 +237,15 @@ def main(argv=None, model_factory=None, source=None):
             window += f" capped at {a.max_lane_events} events ({a.stream_dropped} dropped by the cap)"
         if a.stream_filtered is not None:
             window += f" behind the noise filter ({a.stream_filtered} events filtered)"
+        tracked = ""
+        if tracking:
+            np.save(out_dir / f"tracks_{a.sequence}.npy", trk)
+            ids = np.unique(trk["track_id"])
+            tracked = (f"; {len(ids[ids != 0])} distinct track ids, {a.stream_untracked} detections untracked -> "
+                       f"{out_dir / f'tracks_{a.sequence}.npy'}")
         print(f"{len(steps)} steps of {a.step_us} us on {window} in {seconds:.2f} s "
               f"({1e3 * seconds / max(1, len(steps)):.2f} ms per step; {a.stream_steps[0]} with the full window, "
-              f"{a.stream_steps[1]} on held image maps) -> {path}: {len(rec)} detections")
+              f"{a.stream_steps[1]} on held image maps) -> {path}: {len(rec)} detections{tracked}")
     C.finish(world)
     return path
 
