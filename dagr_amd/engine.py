@@ -407,7 +407,9 @@ class StreamState:
     what the count rule removed.
 
     A tracking stream (``enable_track``) owns the tracker's state (``dagr_stream_track``): the lanes' track slots,
-    ``lane_untracked``, and the step's ``track_ids`` / ``track_hits``."""
+    ``lane_untracked``, and the step's ``track_ids`` / ``track_hits``.  With a motion model (``enable_track(...,
+    motion=)``) the state is ``dagr_stream_track_cv``'s, which also holds the velocities, and the stream owns the step's
+    ``track_boxes`` / ``track_vel`` and the lanes' coast lists, allocated once."""
 
     def __init__(self, batch_size, window_us, device, max_lane_events=None):
         self.B, self.window_us, self.device = int(batch_size), int(window_us), torch.device(device)
@@ -432,14 +434,33 @@ class StreamState:
         self.noise_state, self.noise_cap, self.noise_out, self.lane_filtered = None, 0, None, None
         self.track = None                               # the options of a tracking stream (dagr.streaming._track_options)
         self.track_state, self.lane_untracked, self.track_ids, self.track_hits = None, None, None, None
+        self.motion = None                              # the options of its motion model (dagr.streaming._motion_options)
+        self.track_boxes, self.track_vel, self.coast = None, None, None
         self._t_ref = None                              # (state pointer, capacity, where its t_ref[B] lives)
 
     # ------------------------------------------------------------------------------------ track ids
-    def enable_track(self, options):
+    def enable_track(self, options, motion=None):
         """Every step ends with ``dagr_stream_track``: ``options`` as ``dagr.streaming._track_options`` returns them.
-        Allocates the lanes' slots, empty, and ``lane_untracked``."""
+        Allocates the lanes' slots, empty, and ``lane_untracked``.  With ``motion`` (as ``_motion_options`` returns it)
+        the step ends with ``dagr_stream_track_cv`` instead, on a state of that layout, and the coast lists are allocated."""
         self.track = dict(options)
         L, M = _lib.lib(), self.track["max_tracks"]
+        if motion is not None:
+            self.motion = dict(motion)
+            nbytes = L.dagr_stream_track_cv_bytes(self.B, M)
+            if nbytes == 0:
+                raise RuntimeError(f"dagr_stream_track_cv_bytes({self.B}, {M}): out of range")
+            self.track_state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self.lane_untracked = torch.zeros((self.B,), dtype=torch.int64, device=self.device)
+            dev = self.device
+            self.coast = (torch.zeros((self.B,), dtype=torch.int32, device=dev),            # n_coast
+                          torch.zeros((self.B, M), dtype=torch.int64, device=dev),          # coast_id
+                          torch.zeros((self.B, M, 4), dtype=torch.float32, device=dev),     # coast_box
+                          torch.zeros((self.B, M), dtype=torch.int32, device=dev),          # coast_label
+                          torch.zeros((self.B, M), dtype=torch.int64, device=dev))          # coast_age_us
+            _lib.check(L.dagr_stream_track_cv_reset(_lib.ptr(self.track_state), nbytes, self.B, M,
+                                                    _lib.cur_stream(self.device)), "stream_track_cv_reset")
+            return
         nbytes = L.dagr_stream_track_bytes(self.B, M)
         if nbytes == 0:
             raise RuntimeError(f"dagr_stream_track_bytes({self.B}, {M}): out of range")
@@ -463,6 +484,18 @@ class StreamState:
             if not where:
                 raise RuntimeError(f"dagr_stream_t_ref(B = {self.B}, capacity = {self.cap}): out of range")
             self._t_ref = (self.state.data_ptr(), self.cap, ctypes.c_void_p(where))
+        if self.motion is not None:         # the same step with the motion model: its launch instead, never both
+            if self.track_boxes is None or tuple(self.track_boxes.shape) != (B, A, 4):
+                self.track_boxes = torch.zeros((B, A, 4), dtype=torch.float32, device=self.device)
+                self.track_vel = torch.zeros((B, A, 4), dtype=torch.float32, device=self.device)
+            n_coast, c_id, c_box, c_label, c_age = self.coast
+            _lib.check(L.dagr_stream_track_cv(P(self.track_state), self.track_state.numel(), self.B, o["max_tracks"], o["iou"],
+                                              o["max_age_us"], o["min_score"], self.motion["alpha"], self.motion["beta"],
+                                              P(det), P(n_keep), A, self._t_ref[2], P(self.track_ids), P(self.track_hits),
+                                              P(self.track_boxes), P(self.track_vel), P(c_id), P(c_box), P(c_label), P(c_age),
+                                              P(n_coast), P(self.lane_untracked), _lib.cur_stream(self.device)),
+                       "stream_track_cv")
+            return
         _lib.check(L.dagr_stream_track(P(self.track_state), self.track_state.numel(), self.B, o["max_tracks"], o["iou"],
                                        o["max_age_us"], o["min_score"], P(det), P(n_keep), A, self._t_ref[2],
                                        P(self.track_ids), P(self.track_hits), P(self.lane_untracked),
@@ -476,17 +509,32 @@ class StreamState:
 
     def track_slots(self):
         """The lanes' slots read back as ``(id int64, t_last int64, box fp32[., 4], label int32, hits int32)`` over
-        ``[B, max_tracks]`` and ``next_id int64 [B]`` -- the layout include/dagr_hip.h documents (copies; synchronises)."""
+        ``[B, max_tracks]`` and ``next_id int64 [B]`` -- the layout include/dagr_hip.h documents (copies; synchronises).
+        With a motion model ``vel fp32[., 4]`` follows ``box``: seven arrays."""
         if self.track is None:
             raise RuntimeError("this stream does not track (track=): it has no tracks")
         B, M = self.B, self.track["max_tracks"]
         n, raw = B * M, self.track_state
+        if self.motion is not None:         # dagr_stream_track_cv's layout: vel behind box
+            return (raw[:8 * n].view(torch.int64).view(B, M).cpu().numpy(),
+                    raw[8 * n:16 * n].view(torch.int64).view(B, M).cpu().numpy(),
+                    raw[16 * n:32 * n].view(torch.float32).view(B, M, 4).cpu().numpy(),
+                    raw[32 * n:48 * n].view(torch.float32).view(B, M, 4).cpu().numpy(),
+                    raw[48 * n:52 * n].view(torch.int32).view(B, M).cpu().numpy(),
+                    raw[52 * n:56 * n].view(torch.int32).view(B, M).cpu().numpy(),
+                    raw[56 * n:56 * n + 8 * B].view(torch.int64).cpu().numpy())
         return (raw[:8 * n].view(torch.int64).view(B, M).cpu().numpy(),
                 raw[8 * n:16 * n].view(torch.int64).view(B, M).cpu().numpy(),
                 raw[16 * n:32 * n].view(torch.float32).view(B, M, 4).cpu().numpy(),
                 raw[32 * n:36 * n].view(torch.int32).view(B, M).cpu().numpy(),
                 raw[36 * n:40 * n].view(torch.int32).view(B, M).cpu().numpy(),
                 raw[40 * n:40 * n + 8 * B].view(torch.int64).cpu().numpy())
+
+    def coast_device(self):
+        """``(n_coast, coast_id, coast_box, coast_label, coast_age_us)`` of the last step, the device tensors."""
+        if self.motion is None:
+            raise RuntimeError("this stream has no motion model (motion=): nothing coasts")
+        return self.coast
 
     # ------------------------------------------------------------------------------------ sensor noise
     def enable_denoise(self, sensor_w, sensor_h, denoise_us=None, refractory_us=None):
@@ -621,7 +669,13 @@ class StreamState:
                                                             self.noise[0], self.noise[1], self.noise_cap,
                                                             _lib.cur_stream(self.device)), "stream_denoise_reset")
             self.lane_filtered.zero_()
-        if self.track_state is not None:
+        if self.track_state is not None and self.motion is not None:
+            _lib.check(_lib.lib().dagr_stream_track_cv_reset(_lib.ptr(self.track_state), self.track_state.numel(), self.B,
+                                                             self.track["max_tracks"], _lib.cur_stream(self.device)),
+                       "stream_track_cv_reset")
+            self.lane_untracked.zero_()
+            self.coast[0].zero_()
+        elif self.track_state is not None:
             _lib.check(_lib.lib().dagr_stream_track_reset(_lib.ptr(self.track_state), self.track_state.numel(), self.B,
                                                           self.track["max_tracks"], _lib.cur_stream(self.device)),
                        "stream_track_reset")
@@ -1934,7 +1988,9 @@ class WindowEngine:
         left through the ``_dev`` entries, with the unfiltered push as the clock.
         A tracking stream (``st.track``) ends the step with ``dagr_stream_track`` on the step's detections and the reference
         instants the staging left: one plain launch on the same stream, outside the captured graphs, so every mode and
-        body is covered without a re-capture; ``st.track_ids`` / ``st.track_hits`` hold the result.
+        body is covered without a re-capture; ``st.track_ids`` / ``st.track_hits`` hold the result.  With a motion model
+        (``st.motion``) that launch is ``dagr_stream_track_cv``, which also leaves ``st.track_boxes`` / ``st.track_vel`` and the
+        coast lists.
         Returns ``(out, (det, n_keep))``, both valid until the engine's next call.
 
         ``--use_image``: the window has two bodies.  The frame body runs the image branch on the stream's frame

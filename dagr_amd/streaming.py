@@ -107,8 +107,39 @@ them, by descending score, and the lane's ``t_ref[b]``:
 The IoU is fp32, operation by operation: ``iw = min(ax2, bx2) - max(ax1, bx1)``, ``ih = min(ay2, by2) - max(ay1, by1)``
 (``numpy.minimum`` / ``maximum``), ``inter = iw * ih if iw > 0 and ih > 0 else 0``,
 ``union = ((ax2 - ax1) * (ay2 - ay1) + (bx2 - bx1) * (by2 - by1)) - inter``, ``iou = inter / union`` -- the device repeats
-exactly these without contraction, with a correctly rounded division.  Lanes are independent; there is no motion model and
-no matching across labels.
+exactly these without contraction, with a correctly rounded division.  Lanes are independent; there is no matching across
+labels, and the motion model is opt-in:
+
+A constant-velocity motion model (``motion=`` of a tracking stream: ``None`` is off, ``True`` takes the defaults, a dict
+sets ``alpha``, the position gain, fp32 in (0, 1], default 1.0, and ``beta``, the velocity gain, fp32 in [0, 1], default
+0.25 -- conventions of an alpha-beta filter, not measured optima).  It needs ``track=`` and ``max_age_us <= 2**24 - 1``, so
+that a live track's age is exact in fp32.  Every slot additionally holds ``vel`` fp32[4], pixels per microsecond per corner
+(x1, y1, x2, y2), zero in a free and in a freshly spawned slot.  ``TrackDefinition(batch_size, track, motion=...)`` states
+it in numpy and ``dagr_stream_track_cv`` repeats it bit for bit, in place of ``dagr_stream_track``.  Steps 1, 2, 3 and 5
+stay (a retired slot's ``vel`` is zeroed); added or replaced:
+
+* predict, after the retirement and before any row: for every live track ``dt = fp32(t_ref - t_last)``, the int64
+  difference converted as ``numpy.int64.astype(float32)`` does it -- exact inside the age bound, to the nearest even
+  outside it, which takes a clock that went backwards (status bit 2) -- and ``pred[k] = box[k] + vel[k] * dt`` for the four
+  corners: one fp32 multiply, then one fp32 add, no contraction.  Predictions depend on the state from before the step
+  only; they are computed once per slot;
+* match (replaces 4): step 4 with ``iou(row, pred)``; label rule, taken rule, largest IoU, lowest id, ``>= iou`` and NaN
+  handling unchanged.  On a match, with ``z`` the row's box and ``r[k] = z[k] - pred[k]``: if ``dt > 0``,
+  ``q[k] = r[k] / dt`` and ``vel[k] = q[k]`` when the track's ``hits`` was 1 (its first continuation), else
+  ``vel[k] = vel[k] + beta * q[k]``; if ``dt <= 0`` ``vel`` stays.  ``box = z`` when ``alpha == 1``, else
+  ``box[k] = pred[k] + alpha * r[k]``.  ``t_last = t_ref``, ``hits += 1``.  The row's outputs are the track's id and hits,
+  ``track_box = box`` and ``track_vel = vel``, both after the update;
+* spawn (5): the new track's ``vel`` is 0; the row's ``track_box`` is its own box and its ``track_vel`` 0 -- as for every
+  row that ends with id 0 (not eligible, past ``DAGR_TRACK_MAX_DETS``, no free slot);
+* coast, last: the live tracks that no row matched in this step and that were not spawned in it, in ascending slot order:
+  entry ``j`` of lane ``b`` is ``coast_id[b, j]``, ``coast_box[b, j] = pred``, ``coast_label[b, j]`` and
+  ``coast_age_us[b, j] = t_ref - t_last`` (int64); ``n_coast[b]`` counts them, entries at and behind it are left as they
+  are.  Coasting changes no state.
+
+A lane whose ``t_ref`` is "never" behaves as in 1; in addition ``n_coast = 0``, ``track_box`` is the row's box and
+``track_vel`` 0.  So a track that moves steadily survives a gap of some steps: the returning box is compared with where the
+track is predicted to be, not with where it was last seen, and in between the consumer reads the prediction from the
+coast list without a host-side extrapolation.
 """
 import numpy as np
 
@@ -240,17 +271,61 @@ def _track_options(track, who):
                 min_score=float(np.float32(opt["min_score"])), max_tracks=int(opt["max_tracks"]))
 
 
+MOTION_DEFAULTS = dict(alpha=1.0, beta=0.25)        # conventions (a plain alpha-beta filter), not measured optima
+MOTION_MAX_AGE_US = DEFINES["DAGR_TRACK_CV_MAX_AGE_US"]        # 2**24 - 1: a live track's age is exact in fp32
+TRACK_MOTION_DTYPE = TRACK_DTYPE + [("vx1", "<f4"), ("vy1", "<f4"), ("vx2", "<f4"), ("vy2", "<f4")]
+COAST_DTYPE = [("id", "<i8"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("label", "<i4"), ("age_us", "<i8")]
+
+
+def _motion_options(motion, track_options, who):
+    """``motion=`` of a tracking stream, checked: None (off) or the dict of ``alpha`` and ``beta`` (as fp32) with the
+    defaults filled in; ``track_options`` is what ``_track_options`` returned.  Refusals by name."""
+    if motion is None:
+        return None
+    if motion is True:
+        motion = {}
+    if not isinstance(motion, dict):
+        raise ValueError(f"{who}: motion = {motion!r} must be None (off), True (the defaults) or a dict of "
+                         f"{', '.join(MOTION_DEFAULTS)}")
+    if track_options is None:
+        raise ValueError(f"{who}: motion= needs track= (the motion model is the tracker's)")
+    unknown = sorted(set(motion) - set(MOTION_DEFAULTS))
+    if unknown:
+        raise ValueError(f"{who}: motion has no option {unknown[0]!r} (it has {', '.join(MOTION_DEFAULTS)})")
+    opt = dict(MOTION_DEFAULTS, **motion)
+
+    def is_real(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and v == v
+    if not is_real(opt["alpha"]) or not 0 < np.float32(opt["alpha"]) <= 1:
+        raise ValueError(f"{who}: motion alpha = {opt['alpha']!r} must be a float in (0, 1] (as fp32)")
+    if not is_real(opt["beta"]) or not 0 <= np.float32(opt["beta"]) <= 1:
+        raise ValueError(f"{who}: motion beta = {opt['beta']!r} must be a float in [0, 1] (as fp32)")
+    if track_options["max_age_us"] > MOTION_MAX_AGE_US:
+        raise ValueError(f"{who}: track max_age_us = {track_options['max_age_us']} must not exceed {MOTION_MAX_AGE_US} "
+                         "(2**24 - 1) with motion=: a live track's age has to be exact in fp32")
+    return dict(alpha=float(np.float32(opt["alpha"])), beta=float(np.float32(opt["beta"])))
+
+
 class TrackDefinition:
     """The tracker of the module docstring in numpy: ``step(det, n_keep, t_ref)`` is one step of every lane and returns
     ``(track_id int64 [B, A], track_hits int32 [B, A])`` with the rows at and behind ``n_keep[b]`` zero.  The state is the
     slots' arrays ``id`` (0: free), ``t_last``, ``box``, ``label``, ``hits`` over ``[B, max_tracks]``, ``next_id`` and
     ``untracked`` over ``[B]``.  ``events`` counts what has happened so far (matches, spawns, retirements, slots taken
     again, untracked rows) so that a test can tell a run that exercises the rules from one that does not.  The yardstick of
-    ``dagr_stream_track``; nothing on the device path calls it."""
+    ``dagr_stream_track``; nothing on the device path calls it.
 
-    def __init__(self, batch_size, track=True):
+    With ``motion`` (``True`` or a dict of ``alpha``, ``beta``) it is the constant-velocity tracker of the module docstring,
+    the yardstick of ``dagr_stream_track_cv``: the slots also hold ``vel`` fp32 ``[B, max_tracks, 4]``, and a step leaves
+    ``track_box`` / ``track_vel`` fp32 ``[B, A, 4]`` (zero at and behind ``n_keep[b]``), ``n_coast`` int32 ``[B]`` and
+    ``coast_id``, ``coast_box``, ``coast_label``, ``coast_age_us`` over ``[B, max_tracks]``, whose entries at and behind
+    ``n_coast[b]`` are left as they were.  ``events`` then also counts ``coasted`` track-steps and ``motion_only``, the
+    matches for which no free track of the row's label had an IoU ``>= iou`` with its UNPREDICTED box -- rows the plain
+    rule would have spawned.  Without ``motion`` nothing of this exists and every result is what it was."""
+
+    def __init__(self, batch_size, track=True, motion=None):
         self.B = int(batch_size)
         self.options = _track_options(track, "TrackDefinition")
+        self.motion = _motion_options(motion, self.options, "TrackDefinition")
         if self.options is None:
             raise ValueError("TrackDefinition: track = None is a stream that does not track")
         self.reset()
@@ -263,6 +338,13 @@ class TrackDefinition:
         self.next_id, self.untracked = np.ones(B, np.int64), np.zeros(B, np.int64)
         self._used = np.zeros((B, M), bool)
         self.events = dict(matched=0, spawned=0, retired=0, reused=0, untracked=0)
+        if self.motion is not None:
+            self.vel = np.zeros((B, M, 4), np.float32)
+            self.track_box = self.track_vel = None
+            self.n_coast = np.zeros(B, np.int32)
+            self.coast_id, self.coast_age_us = np.zeros((B, M), np.int64), np.zeros((B, M), np.int64)
+            self.coast_box, self.coast_label = np.zeros((B, M, 4), np.float32), np.zeros((B, M), np.int32)
+            self.events.update(coasted=0, motion_only=0)
 
     @staticmethod
     def iou(a, b):
@@ -277,6 +359,8 @@ class TrackDefinition:
             return f(inter / union)
 
     def step(self, det, n_keep, t_ref):
+        if self.motion is not None:
+            return self._step_cv(det, n_keep, t_ref)
         det = np.asarray(det, np.float32)
         B, A = det.shape[:2]
         if B != self.B or det.shape[2] != 6:
@@ -331,20 +415,127 @@ class TrackDefinition:
             self.events["untracked"] += lost
         return ids, hits
 
+    def _step_cv(self, det, n_keep, t_ref):
+        """One step with the motion model: predict, match against the predictions, filter, spawn at rest, coast."""
+        f = np.float32
+        det = np.asarray(det, np.float32)
+        B, A = det.shape[:2]
+        if B != self.B or det.shape[2] != 6:
+            raise ValueError(f"TrackDefinition: det is fp32 [{self.B}, A, 6], got {det.shape}")
+        n_keep = np.broadcast_to(np.asarray(n_keep, np.int64).reshape(-1), (B,))
+        t_ref = np.broadcast_to(np.asarray(t_ref, np.int64).reshape(-1), (B,))
+        o = self.options
+        thr, min_score = f(o["iou"]), f(o["min_score"])
+        alpha, beta = f(self.motion["alpha"]), f(self.motion["beta"])
+        ids, hits = np.zeros((B, A), np.int64), np.zeros((B, A), np.int32)
+        self.track_box, self.track_vel = np.zeros((B, A, 4), np.float32), np.zeros((B, A, 4), np.float32)
+        for b in range(B):
+            n, now = min(max(int(n_keep[b]), 0), A), int(t_ref[b])
+            self.track_box[b, :n] = det[b, :n, :4]                 # a row without a track: its own box, no velocity
+            if now == NEVER:
+                self.n_coast[b] = 0
+                continue
+            for s in np.flatnonzero(self.id[b]):                   # retire
+                if now - int(self.t_last[b, s]) > o["max_age_us"]:
+                    self.id[b, s], self.vel[b, s] = 0, 0
+                    self.events["retired"] += 1
+            live = [int(s) for s in np.flatnonzero(self.id[b])]
+            dt, pred = {}, {}
+            with np.errstate(all="ignore"):
+                for s in live:                                     # predict, once, from the state before the step
+                    dt[s] = (np.int64(now) - self.t_last[b, s]).astype(f)
+                    pred[s] = np.array([f(self.box[b, s, k] + f(self.vel[b, s, k] * dt[s])) for k in range(4)], f)
+            eligible = [i for i in range(n) if det[b, i, 4] >= min_score]         # (a NaN score compares false)
+            lost = max(0, len(eligible) - DAGR_TRACK_MAX_DETS)
+            unmatched, taken = [], set()
+            for i in eligible[:DAGR_TRACK_MAX_DETS]:               # match, against the predictions
+                with np.errstate(all="ignore"):
+                    label = int(det[b, i, 5].astype(np.int32))
+                best, best_s = None, None
+                for s in live:
+                    if s in taken or int(self.label[b, s]) != label:
+                        continue
+                    v = self.iou(det[b, i, :4], pred[s])
+                    if not v >= thr:                               # (a NaN IoU never matches)
+                        continue
+                    if best is None or v > best or (v == best and self.id[b, s] < self.id[b, best_s]):
+                        best, best_s = v, s
+                if best_s is None:
+                    unmatched.append((i, label))
+                    continue
+                s = best_s
+                if not any(self.iou(det[b, i, :4], self.box[b, c]) >= thr for c in [s] + live
+                           if c not in taken and int(self.label[b, c]) == label):
+                    self.events["motion_only"] += 1                # (the plain rule would have spawned this row)
+                taken.add(s)
+                z = det[b, i, :4]
+                with np.errstate(all="ignore"):
+                    r = np.array([f(z[k] - pred[s][k]) for k in range(4)], f)
+                    if dt[s] > 0:
+                        q = np.array([f(r[k] / dt[s]) for k in range(4)], f)
+                        self.vel[b, s] = q if self.hits[b, s] == 1 else \
+                            np.array([f(self.vel[b, s, k] + f(beta * q[k])) for k in range(4)], f)
+                    self.box[b, s] = z if alpha == 1 else np.array([f(pred[s][k] + f(alpha * r[k])) for k in range(4)], f)
+                self.t_last[b, s] = now
+                self.hits[b, s] += 1
+                ids[b, i], hits[b, i] = self.id[b, s], self.hits[b, s]
+                self.track_box[b, i], self.track_vel[b, i] = self.box[b, s], self.vel[b, s]
+                self.events["matched"] += 1
+            free = [int(s) for s in np.flatnonzero(self.id[b] == 0)]
+            for (i, label), s in zip(unmatched, free):             # spawn, at rest
+                self.id[b, s], self.t_last[b, s], self.box[b, s] = self.next_id[b], now, det[b, i, :4]
+                self.vel[b, s] = 0
+                self.label[b, s], self.hits[b, s] = label, 1
+                ids[b, i], hits[b, i] = self.next_id[b], 1
+                self.next_id[b] += 1
+                self.events["spawned"] += 1
+                self.events["reused"] += int(self._used[b, s])
+                self._used[b, s] = True
+            lost += max(0, len(unmatched) - len(free))
+            self.untracked[b] += lost
+            self.events["untracked"] += lost
+            coast = [s for s in live if s not in taken]            # coast: lived before the rows, seen by none; slot order
+            for j, s in enumerate(coast):
+                self.coast_id[b, j], self.coast_box[b, j], self.coast_label[b, j] = self.id[b, s], pred[s], self.label[b, s]
+                self.coast_age_us[b, j] = np.int64(now) - self.t_last[b, s]
+            self.n_coast[b] = len(coast)
+            self.events["coasted"] += len(coast)
+        return ids, hits
+
+    def coasting(self):
+        """Per lane the last step's coasting tracks, a ``COAST_DTYPE`` array in slot order (``EventStream.coasting()``)."""
+        if self.motion is None:
+            raise RuntimeError("TrackDefinition: no motion model (motion=): nothing coasts")
+        return [coast_from_arrays(int(self.n_coast[b]), self.coast_id[b], self.coast_box[b], self.coast_label[b],
+                                  self.coast_age_us[b]) for b in range(self.B)]
+
     def tracks(self):
-        """Per lane the live tracks as a ``TRACK_DTYPE`` array sorted by id (what ``EventStream.tracks()`` returns)."""
-        return [tracks_from_arrays(self.id[b], self.t_last[b], self.box[b], self.label[b], self.hits[b])
+        """Per lane the live tracks as a ``TRACK_DTYPE`` array sorted by id (what ``EventStream.tracks()`` returns); with
+        ``motion``, ``TRACK_MOTION_DTYPE``: the velocities appended."""
+        vel = self.vel if self.motion is not None else [None] * self.B
+        return [tracks_from_arrays(self.id[b], self.t_last[b], self.box[b], self.label[b], self.hits[b], vel[b])
                 for b in range(self.B)]
 
 
-def tracks_from_arrays(ids, t_last, box, label, hits):
-    """One lane's slots -> its live tracks, a ``TRACK_DTYPE`` array sorted by id."""
+def tracks_from_arrays(ids, t_last, box, label, hits, vel=None):
+    """One lane's slots -> its live tracks, a ``TRACK_DTYPE`` array sorted by id (``TRACK_MOTION_DTYPE`` with ``vel``)."""
     live = np.flatnonzero(ids)
     live = live[np.argsort(ids[live], kind="stable")]
-    out = np.zeros(len(live), TRACK_DTYPE)
+    out = np.zeros(len(live), TRACK_DTYPE if vel is None else TRACK_MOTION_DTYPE)
     out["id"], out["t_last"], out["label"], out["hits"] = ids[live], t_last[live], label[live], hits[live]
     for k, name in enumerate(("x1", "y1", "x2", "y2")):
         out[name] = box[live, k]
+        if vel is not None:
+            out["v" + name] = vel[live, k]
+    return out
+
+
+def coast_from_arrays(n, ids, box, label, age_us):
+    """One lane's coast list -> its first ``n`` entries as a ``COAST_DTYPE`` array, in slot order."""
+    out = np.zeros(n, COAST_DTYPE)
+    out["id"], out["label"], out["age_us"] = ids[:n], label[:n], age_us[:n]
+    for k, name in enumerate(("x1", "y1", "x2", "y2")):
+        out[name] = box[:n, k]
     return out
 
 
@@ -530,6 +721,12 @@ class EventStream:
     adds ``"track_ids"`` / ``"track_hits"`` to every lane's dict, ``tracks()`` reads the live tracks back and
     ``untracked()`` counts the rows that got no id.  A stream built without it issues exactly the launches it issues
     without the tracker.
+    ``motion`` (``None``: off, ``True``: the defaults, or a dict of ``alpha``, ``beta``; needs ``track``): the tracker
+    carries a velocity per track and matches against predicted boxes (module docstring), so a track survives a gap; the
+    step's one tracker launch is then ``dagr_stream_track_cv``.  ``track_boxes`` / ``track_vel`` are the step's filtered
+    boxes and velocities per detection row, ``step()`` adds ``"track_boxes"`` / ``"track_vel"``, ``coasting()`` reads back
+    the tracks the step did not see with their predicted boxes (``coast_device()``: the device tensors), and ``tracks()``
+    appends the velocities.  A stream built without it issues exactly the calls it issues without the motion model.
     ``frame_size`` (``(W_f, H_f)``) and ``frame_bgr``: the steps may carry raw sensor frames (``frame=``), which
     ``dagr_stream_frame`` turns into the model's image on the device (``frame_definition``) with the stream's
     ``downsample`` factors, or 1 without ``downsample``.
@@ -544,10 +741,11 @@ class EventStream:
     """
 
     def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
-                 max_lane_events=None, denoise_us=None, refractory_us=None, track=None):
+                 max_lane_events=None, denoise_us=None, refractory_us=None, track=None, motion=None):
         import torch
         self.model = model
         self.track = _track_options(track, "EventStream")
+        self.motion = _motion_options(motion, self.track, "EventStream")
         time_window = int(getattr(model.args, "time_window_us", 1000000))
         self.window_us, self.max_lane_events = _window_and_cap(window_us, max_lane_events, time_window,
                                                                getattr(model.args, "batch_size", 1), "EventStream")
@@ -583,7 +781,7 @@ class EventStream:
         if self.denoise_us is not None or self.refractory_us is not None:
             self.state.enable_denoise(w_in, h_in, self.denoise_us, self.refractory_us)
         if self.track is not None:
-            self.state.enable_track(self.track)
+            self.state.enable_track(self.track, motion=self.motion)
         self._zeros = None
         self.outputs = None      # the last step's decoded head outputs [B, A, 5 + classes], valid until the engine's next call
         self._frame = None
@@ -602,6 +800,11 @@ class EventStream:
     track_ids = property(lambda self: self.state.track_ids, doc="the last step's track ids int64 [B, A] on the device (row "
                          "i of lane b belongs to det[b, i]; 0: no track), valid until the next step; None without track=")
     track_hits = property(lambda self: self.state.track_hits, doc="the last step's hit counts int32 [B, A], as track_ids")
+    track_boxes = property(lambda self: self.state.track_boxes, doc="the last step's filtered boxes fp32 [B, A, 4] of a "
+                           "motion stream (the track's box behind the update; the row's own box without a track), as "
+                           "track_ids; None without motion=")
+    track_vel = property(lambda self: self.state.track_vel, doc="the last step's velocities fp32 [B, A, 4] in pixels per "
+                         "microsecond per corner (0 without a track), as track_boxes")
 
     def held_maps(self):
         """The live ``(feats, cnn_out)`` tensors of the frame in force -- what the next held step samples -- or None when
@@ -719,6 +922,11 @@ class EventStream:
             for b, d in enumerate(detections):
                 n = int(d["scores"].shape[0])
                 d["track_ids"], d["track_hits"] = ids[b, :n], hits[b, :n]
+            if self.motion is not None:
+                boxes, vel = self.state.track_boxes.clone(), self.state.track_vel.clone()
+                for b, d in enumerate(detections):
+                    n = int(d["scores"].shape[0])
+                    d["track_boxes"], d["track_vel"] = boxes[b, :n], vel[b, :n]
         self.model.engine().stream_counted(self.state)          # the counts came back with it
         if self.model.check_device_status:
             self.check_status()
@@ -753,9 +961,25 @@ class EventStream:
 
     def tracks(self):
         """Per lane the live tracks of a tracking stream, a ``TRACK_DTYPE`` array (``id, x1, y1, x2, y2, label, t_last,
-        hits``) sorted by id (copies; synchronises)."""
+        hits``) sorted by id (copies; synchronises).  A motion stream's arrays are ``TRACK_MOTION_DTYPE``: ``vx1, vy1, vx2,
+        vy2`` (pixels per microsecond) appended."""
+        if self.motion is not None:
+            ids, t_last, box, vel, label, hits, _ = self.state.track_slots()
+            return [tracks_from_arrays(ids[b], t_last[b], box[b], label[b], hits[b], vel[b]) for b in range(self.B)]
         ids, t_last, box, label, hits, _ = self.state.track_slots()
         return [tracks_from_arrays(ids[b], t_last[b], box[b], label[b], hits[b]) for b in range(self.B)]
+
+    def coast_device(self):
+        """The last step's coast lists of a motion stream as the raw device tensors ``(n_coast int32 [B], coast_id int64
+        [B, max_tracks], coast_box fp32 [B, max_tracks, 4], coast_label int32 [B, max_tracks], coast_age_us int64
+        [B, max_tracks])``: the first ``n_coast[b]`` entries of lane ``b`` are the step's, valid until the next step."""
+        return self.state.coast_device()
+
+    def coasting(self):
+        """Per lane the tracks the last step did not see, where they are predicted to be at the step's ``t_ref``: a
+        ``COAST_DTYPE`` array (``id, x1, y1, x2, y2, label, age_us``) in slot order (copies; synchronises)."""
+        n, ids, box, label, age = (t.cpu().numpy() for t in self.state.coast_device())
+        return [coast_from_arrays(int(n[b]), ids[b], box[b], label[b], age[b]) for b in range(self.B)]
 
     def untracked(self):
         """Eligible rows per lane that got no track id since construction / ``reset()`` -- beyond the first

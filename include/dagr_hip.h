@@ -389,6 +389,62 @@ int dagr_stream_track(void *tracks, size_t bytes, int32_t B, int32_t max_tracks,
                       void *stream);
 const int64_t *dagr_stream_t_ref(const void *state, int32_t B, int64_t capacity);
 
+/* ------------------------------------------------------------------------ *
+ * Event stream tracker with a constant-velocity motion model: tracks survive a gap, and coast
+ *   dagr_stream_track_cv is dagr_stream_track with a velocity per track: the rows are matched against the boxes the
+ *   tracks are PREDICTED to have at t_ref[b], a match filters box and velocity, every row also gets the filtered box and the
+ *   velocity of its track, and the live tracks a step did not see leave their prediction in the lane's coast list.  One
+ *   launch (one wave per lane) in place of dagr_stream_track's, no host synchronisation.  dagr_amd/streaming.py:
+ *   TrackDefinition(motion=) is the same in numpy, bit for bit.
+ *
+ * A slot additionally holds vel fp32[4], pixels per microsecond per corner (x1, y1, x2, y2); zero in a free and in a
+ * freshly spawned slot.  never / retire / eligible / spawn and the IoU are dagr_stream_track's (a retired slot's vel is
+ * zeroed; a spawned track's is 0).  Added or replaced, all fp32 arithmetic in this order and without contraction:
+ *   predict:  after the retirement and before any row, for every live track: dt = (float)(t_ref[b] - t_last) -- the int64
+ *             difference converted to the nearest fp32, ties to even; exact for a live track, whose age is at most
+ *             max_age_us <= DAGR_TRACK_CV_MAX_AGE_US, unless the clock went backwards -- and pred[k] = box[k] + vel[k] * dt
+ *             for the four corners (one multiply, then one add).  Predictions depend on the state from before the step
+ *             only; they are computed once per slot.
+ *   match:    dagr_stream_track's, with iou(row, pred) in place of iou(row, box).  On a match, with z the row's box and
+ *             r[k] = z[k] - pred[k]:  if dt > 0: q[k] = r[k] / dt (correctly rounded), and vel[k] = q[k] when the track's
+ *             hits was 1 (its first continuation), else vel[k] = vel[k] + beta * q[k];  if dt <= 0 vel stays.
+ *             box = z when alpha == 1, else box[k] = pred[k] + alpha * r[k].  t_last = t_ref[b], hits += 1.  The row gets
+ *             the track's id and hits, track_box = box and track_vel = vel, both after the update.
+ *   rows without a track (id 0) and rows that spawn one: track_box is the row's own box, track_vel is 0 -- also in a lane
+ *             whose t_ref is INT64_MIN, where additionally n_coast[b] = 0.
+ *   coast:    last.  The live tracks that no row matched in this step and that were not spawned in it, in ascending slot
+ *             order: coast_id[b, j], coast_box[b, j] = pred, coast_label[b, j], coast_age_us[b, j] = t_ref[b] - t_last
+ *             (int64), and n_coast[b] their number.  Entries at and behind n_coast[b] are left as they are.  Coasting changes
+ *             no state.
+ *
+ * tracks: dagr_stream_track_cv_bytes(B, max_tracks) bytes (0 out of range, as dagr_stream_track_bytes), 16-byte aligned,
+ *         dagr_stream_track_cv_reset before the first step and to empty it.  A layout of its own; with n = B * max_tracks,
+ *         slot s of lane b at index b * max_tracks + s:
+ *           id     int64 [n]    at byte 0        (0: the slot is free)
+ *           t_last int64 [n]    at byte  8 * n
+ *           box    fp32  [n, 4] at byte 16 * n
+ *           vel    fp32  [n, 4] at byte 32 * n
+ *           label  int32 [n]    at byte 48 * n
+ *           hits   int32 [n]    at byte 52 * n
+ *           next_id int64 [B]   at byte 56 * n      -- 56 * n + 8 * B bytes in all
+ * alpha: position gain in (0, 1]; beta: velocity gain in [0, 1].
+ * track_box, track_vel fp32[B, A, 4], 16-byte aligned: rows < n_keep[b] are written, the rest are left as they are (so are
+ * track_id and track_hits).  coast_id int64[B, max_tracks], coast_box fp32[B, max_tracks, 4] (16-byte aligned), coast_label
+ * int32[B, max_tracks], coast_age_us int64[B, max_tracks], n_coast int32[B]: all five NULL together (no coast list is
+ * written) or none.  Everything else as dagr_stream_track takes it.
+ * DAGR_ERR_INVALID_ARG before any launch: whatever dagr_stream_track refuses, alpha outside (0, 1], beta outside [0, 1]
+ * (NaN included), max_age_us > DAGR_TRACK_CV_MAX_AGE_US, a state smaller than dagr_stream_track_cv_bytes, NULL track_box /
+ * track_vel with A > 0, partly NULL coast arrays, misaligned arrays.
+ * ------------------------------------------------------------------------ */
+#define DAGR_TRACK_CV_MAX_AGE_US 16777215
+size_t dagr_stream_track_cv_bytes(int32_t B, int32_t max_tracks);
+int dagr_stream_track_cv_reset(void *tracks, size_t bytes, int32_t B, int32_t max_tracks, void *stream);
+int dagr_stream_track_cv(void *tracks, size_t bytes, int32_t B, int32_t max_tracks, float iou, int64_t max_age_us,
+                         float min_score, float alpha, float beta, const float *det, const int32_t *n_keep, int32_t A,
+                         const int64_t *t_ref, int64_t *track_id, int32_t *track_hits, float *track_box, float *track_vel,
+                         int64_t *coast_id, float *coast_box, int32_t *coast_label, int64_t *coast_age_us, int32_t *n_coast,
+                         int64_t *untracked /* [B], accumulated; may be NULL */, void *stream);
+
 /* The neighbour search alone, again, on the pixel index the last dagr_graph_build_window left in `workspace` (same N):
  * rewrites nbr_src / nbr_code / deg and the edge count.  For measurement (bench.py times the search kernels on their own
  * stream with HIP events); a product caller has no use for it. */

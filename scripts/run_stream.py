@@ -31,7 +31,15 @@ pixel saw none in the last ``R``.  The number of events the filter removed is pr
 label against the tracks of the step before), tuned by ``--track_iou``, ``--track_max_age_us``, ``--track_min_score`` and
 ``--max_tracks``.  ``detections_<sequence>.npy`` stays what it is; a second file ``tracks_<sequence>.npy`` holds the same
 rows in the same order with ``track_id`` (``<u8``, 0: no track) and ``hits`` (``<u4``) appended.  The number of distinct ids
-and of untracked detections is printed with the summary."""
+and of untracked detections is printed with the summary.
+
+``--track_motion`` (needs ``--track``): the tracker carries a constant-velocity motion model (``dagr.streaming``:
+``EventStream(motion=)``), tuned by ``--track_alpha`` (position gain, default 1.0) and ``--track_beta`` (velocity gain,
+default 0.25) -- conventions, not measured optima.  Tracks then survive steps in which the detector misses them.
+``tracks_<sequence>.npy`` also carries, per row, the track's filtered box (``tx1, ty1, tx2, ty2``) and its velocity in pixels
+per microsecond (``vx1, vy1, vx2, vy2``); a third file ``coasting_<sequence>.npy`` holds, per step, the tracks the step did
+not see with the boxes they are predicted to have (``step, lane, t, id, x1, y1, x2, y2, label, age_us``).  The number of
+coasted track-steps is printed with the summary."""
 import time
 import types
 
@@ -39,7 +47,7 @@ import numpy as np
 import torch
 
 import _common as C
-from dagr.streaming import EventStream, _track_options
+from dagr.streaming import EventStream, _motion_options, _track_options
 from dagr.utils.buffers import DETECTION_DTYPE, detections_to_records
 from dagr.utils.logging import set_up_logging_directory
 from dagr.utils import synthetic as syn
@@ -69,6 +77,10 @@ def stream_options(p):
     g.add_argument("--track_min_score", type=float, default=None, help="with --track: detections below this confidence get "
                    "no id (default 0.0)")
     g.add_argument("--max_tracks", type=int, default=None, help="with --track: tracks held at a time (default 64, at most 256)")
+    g.add_argument("--track_motion", action="store_true", help="with --track: a constant-velocity motion model; tracks "
+                   "survive a gap and coast")
+    g.add_argument("--track_alpha", type=float, default=None, help="with --track_motion: position gain in (0, 1] (default 1.0)")
+    g.add_argument("--track_beta", type=float, default=None, help="with --track_motion: velocity gain in [0, 1] (default 0.25)")
     g.add_argument("--raw_frames", action="store_true", help="the source's frames are sensor-size BGR uint8 frames: prepare "
                    "them on the device (crop, shrink by the --downsample factor, / 255)")
 
@@ -90,6 +102,51 @@ def track_options(a):
     except ValueError as e:
         raise SystemExit(str(e)) from None
     return given
+
+
+MOTION_FLAGS = (("track_alpha", "alpha"), ("track_beta", "beta"))
+MOTION_RECORD_DTYPE = TRACK_RECORD_DTYPE + [(n, "<f4") for n in ("tx1", "ty1", "tx2", "ty2", "vx1", "vy1", "vx2", "vy2")]
+COAST_RECORD_DTYPE = [("step", "<u4"), ("lane", "<u4"), ("t", "<u8"), ("id", "<u8"), ("x1", "<f4"), ("y1", "<f4"),
+                      ("x2", "<f4"), ("y2", "<f4"), ("label", "<i4"), ("age_us", "<i8")]
+
+
+def motion_options(a):
+    """``motion=`` of the stream the flags describe: None without ``--track_motion``, else the options that were given."""
+    given = {key: getattr(a, flag) for flag, key in MOTION_FLAGS if getattr(a, flag, None) is not None}
+    if not getattr(a, "track_motion", False):
+        if given:
+            raise SystemExit(f"run_stream.py: --{[f for f, k in MOTION_FLAGS if k in given][0]} needs --track_motion")
+        return None
+    if not getattr(a, "track", False):
+        raise SystemExit("run_stream.py: --track_motion needs --track")
+    try:
+        _motion_options(given, _track_options(track_options(a), "run_stream.py"), "run_stream.py")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    return given
+
+
+def motion_records(rec, det):
+    """``track_records`` with the step's ``track_boxes`` / ``track_vel`` appended."""
+    out = np.zeros(len(rec), MOTION_RECORD_DTYPE)
+    for name in rec.dtype.names:
+        out[name] = rec[name]
+    box, vel = det["track_boxes"].cpu().numpy(), det["track_vel"].cpu().numpy()
+    for k, c in enumerate(("x1", "y1", "x2", "y2")):
+        out["t" + c], out["v" + c] = box[:, k], vel[:, k]
+    return out
+
+
+def coast_records(step, t, coasting):
+    """The coast lists of one step (``EventStream.coasting()``) as ``COAST_RECORD_DTYPE`` rows."""
+    out = []
+    for lane, c in enumerate(coasting):
+        rec = np.zeros(len(c), COAST_RECORD_DTYPE)
+        rec["step"], rec["lane"], rec["t"] = step, lane, t
+        for name in c.dtype.names:
+            rec[name] = c[name]
+        out.append(rec)
+    return np.concatenate(out) if out else np.zeros(0, COAST_RECORD_DTYPE)
 
 
 def track_records(rec, det):
@@ -164,9 +221,10 @@ def play(a, model, source, dev):
     stream = EventStream(model, window_us=a.window_us or None, downsample=a.downsample, sensor_size=sensor_size(a),
                          frame_size=raw_size, frame_bgr=True, max_lane_events=cap,
                          denoise_us=getattr(a, "denoise_us", None), refractory_us=getattr(a, "refractory_us", None),
-                         track=track_options(a))
+                         track=track_options(a), motion=motion_options(a))
     t0, t1 = source.t_range()
     out, last_frame = [], None
+    a.stream_coasting = [] if stream.motion is not None else None      # per step the tracks it did not see
     for t_step in range(int(t0) + a.step_us, int(t1) + 1, a.step_us):
         ev = source.events(t_step - a.step_us, t_step)
         xy = np.stack([np.asarray(ev["x"], np.int16), np.asarray(ev["y"], np.int16)], -1)
@@ -183,6 +241,8 @@ def play(a, model, source, dev):
         det = stream.step(xy, np.asarray(ev["t"], np.int64), np.asarray(ev["p"], np.int8), t_now=t_step, image=image,
                           frame=raw)
         out.append((t_step, det[0]))
+        if stream.motion is not None:
+            a.stream_coasting.append(coast_records(len(out) - 1, t_step, stream.coasting()))
     a.stream_steps = (stream.frame_steps, stream.held_steps)      # (frame bodies, held bodies) of the run
     a.stream_dropped = int(stream.dropped().sum()) if cap is not None else None
     a.stream_filtered = int(stream.filtered().sum()) if stream.state.noise is not None else None
@@ -202,6 +262,7 @@ def main(argv=None, model_factory=None, source=None):
         raise SystemExit("run_stream.py: --step_us and --window_us must be positive (--window_us 0: the model's time "
                          "window, with --max_lane_events only)")
     tracking = track_options(a) is not None
+    moving = motion_options(a) is not None
     a.batch_size = 1                       # one sequence: one lane
     world, rank, dev = C.distributed()
     torch.manual_seed(42)
@@ -226,7 +287,9 @@ def main(argv=None, model_factory=None, source=None):
     rec = rec[order]
     if tracking:        # the same rows in the same order, with the two fields appended
         trk = [track_records(r, det) for r, (_, det) in zip(per_step, steps)]
-        trk = (np.concatenate(trk) if trk else np.zeros(0, TRACK_RECORD_DTYPE))[order]
+        if moving:      # ... and the filtered box and the velocity
+            trk = [motion_records(r, det) for r, (_, det) in zip(trk, steps)]
+        trk = (np.concatenate(trk) if trk else np.zeros(0, MOTION_RECORD_DTYPE if moving else TRACK_RECORD_DTYPE))[order]
     path = None
     if rank == 0:
         out_dir.mkdir(parents=True, exist_ok=True)
@@ -243,6 +306,10 @@ def main(argv=None, model_factory=None, source=None):
             ids = np.unique(trk["track_id"])
             tracked = (f"; {len(ids[ids != 0])} distinct track ids, {a.stream_untracked} detections untracked -> "
                        f"{out_dir / f'tracks_{a.sequence}.npy'}")
+        if moving:
+            coast = np.concatenate(a.stream_coasting) if a.stream_coasting else np.zeros(0, COAST_RECORD_DTYPE)
+            np.save(out_dir / f"coasting_{a.sequence}.npy", coast)
+            tracked += f"; {len(coast)} coasted track-steps -> {out_dir / f'coasting_{a.sequence}.npy'}"
         print(f"{len(steps)} steps of {a.step_us} us on {window} in {seconds:.2f} s "
               f"({1e3 * seconds / max(1, len(steps)):.2f} ms per step; {a.stream_steps[0]} with the full window, "
               f"{a.stream_steps[1]} on held image maps) -> {path}: {len(rec)} detections{tracked}")
