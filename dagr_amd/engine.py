@@ -439,67 +439,71 @@ class StreamState:
         self._t_ref = None                              # (state pointer, capacity, where its t_ref[B] lives)
 
     # ------------------------------------------------------------------------------------ track ids
+    # the slots' arrays in the order the state holds them over [B, max_tracks]: (name, dtype, width); next_id[B] follows
+    TRACK_FIELDS = (("id", torch.int64, 1), ("t_last", torch.int64, 1), ("box", torch.float32, 4), ("vel", torch.float32, 4),
+                    ("label", torch.int32, 1), ("hits", torch.int32, 1))
+
     def enable_track(self, options, motion=None):
         """Every step ends with ``dagr_stream_track``: ``options`` as ``dagr.streaming._track_options`` returns them.
         Allocates the lanes' slots, empty, and ``lane_untracked``.  With ``motion`` (as ``_motion_options`` returns it)
         the step ends with ``dagr_stream_track_cv`` instead, on a state of that layout, and the coast lists are allocated."""
-        self.track = dict(options)
-        L, M = _lib.lib(), self.track["max_tracks"]
+        self.track, self.motion = dict(options), None if motion is None else dict(motion)
+        # the family of entry points dagr_<family>, dagr_<family>_bytes, dagr_<family>_reset, chosen here once -- as a
+        # name: every call looks its function up on the library
+        self._track_family = "stream_track" if motion is None else "stream_track_cv"
+        M, dev = self.track["max_tracks"], self.device
+        nbytes = self._track_fn("_bytes")(self.B, M)
+        if nbytes == 0:
+            raise RuntimeError(f"dagr_{self._track_family}_bytes({self.B}, {M}): out of range")
+        self.track_state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.lane_untracked = torch.zeros((self.B,), dtype=torch.int64, device=dev)
         if motion is not None:
-            self.motion = dict(motion)
-            nbytes = L.dagr_stream_track_cv_bytes(self.B, M)
-            if nbytes == 0:
-                raise RuntimeError(f"dagr_stream_track_cv_bytes({self.B}, {M}): out of range")
-            self.track_state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self.lane_untracked = torch.zeros((self.B,), dtype=torch.int64, device=self.device)
-            dev = self.device
             self.coast = (torch.zeros((self.B,), dtype=torch.int32, device=dev),            # n_coast
                           torch.zeros((self.B, M), dtype=torch.int64, device=dev),          # coast_id
                           torch.zeros((self.B, M, 4), dtype=torch.float32, device=dev),     # coast_box
                           torch.zeros((self.B, M), dtype=torch.int32, device=dev),          # coast_label
                           torch.zeros((self.B, M), dtype=torch.int64, device=dev))          # coast_age_us
-            _lib.check(L.dagr_stream_track_cv_reset(_lib.ptr(self.track_state), nbytes, self.B, M,
-                                                    _lib.cur_stream(self.device)), "stream_track_cv_reset")
-            return
-        nbytes = L.dagr_stream_track_bytes(self.B, M)
-        if nbytes == 0:
-            raise RuntimeError(f"dagr_stream_track_bytes({self.B}, {M}): out of range")
-        self.track_state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self.lane_untracked = torch.zeros((self.B,), dtype=torch.int64, device=self.device)
-        _lib.check(L.dagr_stream_track_reset(_lib.ptr(self.track_state), nbytes, self.B, M, _lib.cur_stream(self.device)),
-                   "stream_track_reset")
+        self._reset_track()
+
+    def _track_fn(self, suffix=""):
+        return getattr(_lib.lib(), "dagr_" + self._track_family + suffix)
+
+    def _reset_track(self):
+        """Every slot free, ``next_id = 1``, nothing untracked, nothing coasting."""
+        _lib.check(self._track_fn("_reset")(_lib.ptr(self.track_state), self.track_state.numel(), self.B, self.track["max_tracks"],
+                                            _lib.cur_stream(self.device)), self._track_family + "_reset")
+        self.lane_untracked.zero_()
+        if self.motion is not None:
+            self.coast[0].zero_()
 
     def run_track(self, det, n_keep):
         """``dagr_stream_track`` on a step's detections, at the reference instants the step's staging left in the stream
-        state: ``track_ids`` int64 [B, A] and ``track_hits`` int32 [B, A], valid until the next step."""
+        state: ``track_ids`` int64 [B, A] and ``track_hits`` int32 [B, A], valid until the next step.  With a motion model
+        ``dagr_stream_track_cv`` instead, never both: it also leaves ``track_boxes`` / ``track_vel`` and the coast lists."""
         B, A = int(det.shape[0]), int(det.shape[1])
         if B != self.B or det.dtype != torch.float32 or not det.is_contiguous() or n_keep.dtype != torch.int32:
             raise RuntimeError(f"run_track: det must be contiguous fp32 [{self.B}, A, 6] and n_keep int32 [{self.B}]")
         if self.track_ids is None or tuple(self.track_ids.shape) != (B, A):
             self.track_ids = torch.zeros((B, A), dtype=torch.int64, device=self.device)
             self.track_hits = torch.zeros((B, A), dtype=torch.int32, device=self.device)
+            if self.motion is not None:
+                self.track_boxes = torch.zeros((B, A, 4), dtype=torch.float32, device=self.device)
+                self.track_vel = torch.zeros((B, A, 4), dtype=torch.float32, device=self.device)
         L, P, o = _lib.lib(), _lib.ptr, self.track
         if self._t_ref is None or self._t_ref[:2] != (self.state.data_ptr(), self.cap):     # (the state has grown)
             where = L.dagr_stream_t_ref(P(self.state), self.B, self.cap)
             if not where:
                 raise RuntimeError(f"dagr_stream_t_ref(B = {self.B}, capacity = {self.cap}): out of range")
             self._t_ref = (self.state.data_ptr(), self.cap, ctypes.c_void_p(where))
-        if self.motion is not None:         # the same step with the motion model: its launch instead, never both
-            if self.track_boxes is None or tuple(self.track_boxes.shape) != (B, A, 4):
-                self.track_boxes = torch.zeros((B, A, 4), dtype=torch.float32, device=self.device)
-                self.track_vel = torch.zeros((B, A, 4), dtype=torch.float32, device=self.device)
+        gains, outputs = [], []             # what dagr_stream_track_cv takes in addition, in their places
+        if self.motion is not None:
             n_coast, c_id, c_box, c_label, c_age = self.coast
-            _lib.check(L.dagr_stream_track_cv(P(self.track_state), self.track_state.numel(), self.B, o["max_tracks"], o["iou"],
-                                              o["max_age_us"], o["min_score"], self.motion["alpha"], self.motion["beta"],
-                                              P(det), P(n_keep), A, self._t_ref[2], P(self.track_ids), P(self.track_hits),
-                                              P(self.track_boxes), P(self.track_vel), P(c_id), P(c_box), P(c_label), P(c_age),
-                                              P(n_coast), P(self.lane_untracked), _lib.cur_stream(self.device)),
-                       "stream_track_cv")
-            return
-        _lib.check(L.dagr_stream_track(P(self.track_state), self.track_state.numel(), self.B, o["max_tracks"], o["iou"],
-                                       o["max_age_us"], o["min_score"], P(det), P(n_keep), A, self._t_ref[2],
-                                       P(self.track_ids), P(self.track_hits), P(self.lane_untracked),
-                                       _lib.cur_stream(self.device)), "stream_track")
+            gains = [self.motion["alpha"], self.motion["beta"]]
+            outputs = [P(self.track_boxes), P(self.track_vel), P(c_id), P(c_box), P(c_label), P(c_age), P(n_coast)]
+        _lib.check(self._track_fn()(P(self.track_state), self.track_state.numel(), self.B, o["max_tracks"], o["iou"],
+                                    o["max_age_us"], o["min_score"], *gains, P(det), P(n_keep), A, self._t_ref[2],
+                                    P(self.track_ids), P(self.track_hits), *outputs, P(self.lane_untracked),
+                                    _lib.cur_stream(self.device)), self._track_family)
 
     def untracked(self):
         """Per-lane eligible rows that got no track id, int64 [B] (synchronises)."""
@@ -514,21 +518,14 @@ class StreamState:
         if self.track is None:
             raise RuntimeError("this stream does not track (track=): it has no tracks")
         B, M = self.B, self.track["max_tracks"]
-        n, raw = B * M, self.track_state
-        if self.motion is not None:         # dagr_stream_track_cv's layout: vel behind box
-            return (raw[:8 * n].view(torch.int64).view(B, M).cpu().numpy(),
-                    raw[8 * n:16 * n].view(torch.int64).view(B, M).cpu().numpy(),
-                    raw[16 * n:32 * n].view(torch.float32).view(B, M, 4).cpu().numpy(),
-                    raw[32 * n:48 * n].view(torch.float32).view(B, M, 4).cpu().numpy(),
-                    raw[48 * n:52 * n].view(torch.int32).view(B, M).cpu().numpy(),
-                    raw[52 * n:56 * n].view(torch.int32).view(B, M).cpu().numpy(),
-                    raw[56 * n:56 * n + 8 * B].view(torch.int64).cpu().numpy())
-        return (raw[:8 * n].view(torch.int64).view(B, M).cpu().numpy(),
-                raw[8 * n:16 * n].view(torch.int64).view(B, M).cpu().numpy(),
-                raw[16 * n:32 * n].view(torch.float32).view(B, M, 4).cpu().numpy(),
-                raw[32 * n:36 * n].view(torch.int32).view(B, M).cpu().numpy(),
-                raw[36 * n:40 * n].view(torch.int32).view(B, M).cpu().numpy(),
-                raw[40 * n:40 * n + 8 * B].view(torch.int64).cpu().numpy())
+        out, at = [], 0
+        for name, dtype, width in self.TRACK_FIELDS:
+            if name == "vel" and self.motion is None:               # dagr_stream_track_cv's layout only
+                continue
+            size = B * M * width * torch.empty((), dtype=dtype).element_size()
+            out.append(self.track_state[at:at + size].view(dtype).view((B, M) if width == 1 else (B, M, width)).cpu().numpy())
+            at += size
+        return (*out, self.track_state[at:at + 8 * B].view(torch.int64).cpu().numpy())
 
     def coast_device(self):
         """``(n_coast, coast_id, coast_box, coast_label, coast_age_us)`` of the last step, the device tensors."""
@@ -669,17 +666,8 @@ class StreamState:
                                                             self.noise[0], self.noise[1], self.noise_cap,
                                                             _lib.cur_stream(self.device)), "stream_denoise_reset")
             self.lane_filtered.zero_()
-        if self.track_state is not None and self.motion is not None:
-            _lib.check(_lib.lib().dagr_stream_track_cv_reset(_lib.ptr(self.track_state), self.track_state.numel(), self.B,
-                                                             self.track["max_tracks"], _lib.cur_stream(self.device)),
-                       "stream_track_cv_reset")
-            self.lane_untracked.zero_()
-            self.coast[0].zero_()
-        elif self.track_state is not None:
-            _lib.check(_lib.lib().dagr_stream_track_reset(_lib.ptr(self.track_state), self.track_state.numel(), self.B,
-                                                          self.track["max_tracks"], _lib.cur_stream(self.device)),
-                       "stream_track_reset")
-            self.lane_untracked.zero_()
+        if self.track_state is not None:
+            self._reset_track()
         self.status.zero_()
         self.lane_count.zero_()
         self.lane_dropped.zero_()

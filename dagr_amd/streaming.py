@@ -238,33 +238,43 @@ TRACK_DTYPE = [("id", "<i8"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2"
                ("t_last", "<i8"), ("hits", "<i4")]
 
 
+def _is_int(v):
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+
+def _is_real(v):
+    return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and v == v
+
+
+def _options(value, name, defaults, who):
+    """``name=`` of a stream (``track=``, ``motion=``): None stays None (off), True is ``defaults``, a dict has the defaults
+    filled in; anything else, and a key that ``defaults`` does not have, is refused by name."""
+    if value is None:
+        return None
+    if value is True:
+        value = {}
+    if not isinstance(value, dict):
+        raise ValueError(f"{who}: {name} = {value!r} must be None (off), True (the defaults) or a dict of "
+                         f"{', '.join(defaults)}")
+    unknown = sorted(set(value) - set(defaults))
+    if unknown:
+        raise ValueError(f"{who}: {name} has no option {unknown[0]!r} (it has {', '.join(defaults)})")
+    return dict(defaults, **value)
+
+
 def _track_options(track, who):
     """``track=`` of a stream, checked: None (off) or the dict of ``iou``, ``max_age_us``, ``min_score`` and ``max_tracks``
     with the defaults filled in; refusals by name."""
-    if track is None:
+    opt = _options(track, "track", TRACK_DEFAULTS, who)
+    if opt is None:
         return None
-    if track is True:
-        track = {}
-    if not isinstance(track, dict):
-        raise ValueError(f"{who}: track = {track!r} must be None (off), True (the defaults) or a dict of "
-                         f"{', '.join(TRACK_DEFAULTS)}")
-    unknown = sorted(set(track) - set(TRACK_DEFAULTS))
-    if unknown:
-        raise ValueError(f"{who}: track has no option {unknown[0]!r} (it has {', '.join(TRACK_DEFAULTS)})")
-    opt = dict(TRACK_DEFAULTS, **track)
-
-    def is_int(v):
-        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
-
-    def is_real(v):
-        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and v == v
-    if not is_real(opt["iou"]) or not 0 < np.float32(opt["iou"]) <= 1:
+    if not _is_real(opt["iou"]) or not 0 < np.float32(opt["iou"]) <= 1:
         raise ValueError(f"{who}: track iou = {opt['iou']!r} must be a float in (0, 1] (as fp32)")
-    if not is_int(opt["max_age_us"]) or not 0 <= int(opt["max_age_us"]) < 1 << 63:
+    if not _is_int(opt["max_age_us"]) or not 0 <= int(opt["max_age_us"]) < 1 << 63:
         raise ValueError(f"{who}: track max_age_us = {opt['max_age_us']!r} must be an int of microseconds >= 0")
-    if not is_real(opt["min_score"]):
+    if not _is_real(opt["min_score"]):
         raise ValueError(f"{who}: track min_score = {opt['min_score']!r} must be a float (not NaN)")
-    if not is_int(opt["max_tracks"]) or not 1 <= int(opt["max_tracks"]) <= DAGR_TRACK_MAX_TRACKS:
+    if not _is_int(opt["max_tracks"]) or not 1 <= int(opt["max_tracks"]) <= DAGR_TRACK_MAX_TRACKS:
         raise ValueError(f"{who}: track max_tracks = {opt['max_tracks']!r} must be an int in 1..DAGR_TRACK_MAX_TRACKS = "
                          f"{DAGR_TRACK_MAX_TRACKS}")
     return dict(iou=float(np.float32(opt["iou"])), max_age_us=int(opt["max_age_us"]),
@@ -280,25 +290,14 @@ COAST_DTYPE = [("id", "<i8"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2"
 def _motion_options(motion, track_options, who):
     """``motion=`` of a tracking stream, checked: None (off) or the dict of ``alpha`` and ``beta`` (as fp32) with the
     defaults filled in; ``track_options`` is what ``_track_options`` returned.  Refusals by name."""
-    if motion is None:
+    opt = _options(motion, "motion", MOTION_DEFAULTS, who)
+    if opt is None:
         return None
-    if motion is True:
-        motion = {}
-    if not isinstance(motion, dict):
-        raise ValueError(f"{who}: motion = {motion!r} must be None (off), True (the defaults) or a dict of "
-                         f"{', '.join(MOTION_DEFAULTS)}")
     if track_options is None:
         raise ValueError(f"{who}: motion= needs track= (the motion model is the tracker's)")
-    unknown = sorted(set(motion) - set(MOTION_DEFAULTS))
-    if unknown:
-        raise ValueError(f"{who}: motion has no option {unknown[0]!r} (it has {', '.join(MOTION_DEFAULTS)})")
-    opt = dict(MOTION_DEFAULTS, **motion)
-
-    def is_real(v):
-        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and v == v
-    if not is_real(opt["alpha"]) or not 0 < np.float32(opt["alpha"]) <= 1:
+    if not _is_real(opt["alpha"]) or not 0 < np.float32(opt["alpha"]) <= 1:
         raise ValueError(f"{who}: motion alpha = {opt['alpha']!r} must be a float in (0, 1] (as fp32)")
-    if not is_real(opt["beta"]) or not 0 <= np.float32(opt["beta"]) <= 1:
+    if not _is_real(opt["beta"]) or not 0 <= np.float32(opt["beta"]) <= 1:
         raise ValueError(f"{who}: motion beta = {opt['beta']!r} must be a float in [0, 1] (as fp32)")
     if track_options["max_age_us"] > MOTION_MAX_AGE_US:
         raise ValueError(f"{who}: track max_age_us = {track_options['max_age_us']} must not exceed {MOTION_MAX_AGE_US} "
@@ -359,64 +358,7 @@ class TrackDefinition:
             return f(inter / union)
 
     def step(self, det, n_keep, t_ref):
-        if self.motion is not None:
-            return self._step_cv(det, n_keep, t_ref)
-        det = np.asarray(det, np.float32)
-        B, A = det.shape[:2]
-        if B != self.B or det.shape[2] != 6:
-            raise ValueError(f"TrackDefinition: det is fp32 [{self.B}, A, 6], got {det.shape}")
-        n_keep = np.broadcast_to(np.asarray(n_keep, np.int64).reshape(-1), (B,))
-        t_ref = np.broadcast_to(np.asarray(t_ref, np.int64).reshape(-1), (B,))
-        o = self.options
-        thr, min_score = np.float32(o["iou"]), np.float32(o["min_score"])
-        ids, hits = np.zeros((B, A), np.int64), np.zeros((B, A), np.int32)
-        for b in range(B):
-            n, now = min(max(int(n_keep[b]), 0), A), int(t_ref[b])
-            if now == NEVER:
-                continue
-            for s in np.flatnonzero(self.id[b]):                   # retire
-                if now - int(self.t_last[b, s]) > o["max_age_us"]:
-                    self.id[b, s] = 0
-                    self.events["retired"] += 1
-            eligible = [i for i in range(n) if det[b, i, 4] >= min_score]         # (a NaN score compares false)
-            lost = max(0, len(eligible) - DAGR_TRACK_MAX_DETS)
-            unmatched, taken = [], set()
-            for i in eligible[:DAGR_TRACK_MAX_DETS]:               # match
-                with np.errstate(all="ignore"):
-                    label = int(det[b, i, 5].astype(np.int32))
-                best, best_s = None, None
-                for s in np.flatnonzero(self.id[b]):
-                    if int(s) in taken or int(self.label[b, s]) != label:
-                        continue
-                    v = self.iou(det[b, i, :4], self.box[b, s])
-                    if not v >= thr:                               # (a NaN IoU never matches)
-                        continue
-                    if best is None or v > best or (v == best and self.id[b, s] < self.id[b, best_s]):
-                        best, best_s = v, int(s)
-                if best_s is None:
-                    unmatched.append((i, label))
-                    continue
-                taken.add(best_s)
-                self.box[b, best_s], self.t_last[b, best_s] = det[b, i, :4], now
-                self.hits[b, best_s] += 1
-                ids[b, i], hits[b, i] = self.id[b, best_s], self.hits[b, best_s]
-                self.events["matched"] += 1
-            free = [int(s) for s in np.flatnonzero(self.id[b] == 0)]
-            for (i, label), s in zip(unmatched, free):             # spawn
-                self.id[b, s], self.t_last[b, s], self.box[b, s] = self.next_id[b], now, det[b, i, :4]
-                self.label[b, s], self.hits[b, s] = label, 1
-                ids[b, i], hits[b, i] = self.next_id[b], 1
-                self.next_id[b] += 1
-                self.events["spawned"] += 1
-                self.events["reused"] += int(self._used[b, s])
-                self._used[b, s] = True
-            lost += max(0, len(unmatched) - len(free))
-            self.untracked[b] += lost
-            self.events["untracked"] += lost
-        return ids, hits
-
-    def _step_cv(self, det, n_keep, t_ref):
-        """One step with the motion model: predict, match against the predictions, filter, spawn at rest, coast."""
+        """One step of every lane.  With ``motion``: predict, match against the predictions, filter, spawn at rest, coast."""
         f = np.float32
         det = np.asarray(det, np.float32)
         B, A = det.shape[:2]
@@ -424,38 +366,48 @@ class TrackDefinition:
             raise ValueError(f"TrackDefinition: det is fp32 [{self.B}, A, 6], got {det.shape}")
         n_keep = np.broadcast_to(np.asarray(n_keep, np.int64).reshape(-1), (B,))
         t_ref = np.broadcast_to(np.asarray(t_ref, np.int64).reshape(-1), (B,))
-        o = self.options
+        o, motion = self.options, self.motion is not None
         thr, min_score = f(o["iou"]), f(o["min_score"])
-        alpha, beta = f(self.motion["alpha"]), f(self.motion["beta"])
         ids, hits = np.zeros((B, A), np.int64), np.zeros((B, A), np.int32)
-        self.track_box, self.track_vel = np.zeros((B, A, 4), np.float32), np.zeros((B, A, 4), np.float32)
+        if motion:
+            alpha, beta = f(self.motion["alpha"]), f(self.motion["beta"])
+            self.track_box, self.track_vel = np.zeros((B, A, 4), np.float32), np.zeros((B, A, 4), np.float32)
         for b in range(B):
             n, now = min(max(int(n_keep[b]), 0), A), int(t_ref[b])
-            self.track_box[b, :n] = det[b, :n, :4]                 # a row without a track: its own box, no velocity
+            if motion:
+                self.track_box[b, :n] = det[b, :n, :4]             # a row without a track: its own box, no velocity
             if now == NEVER:
-                self.n_coast[b] = 0
+                if motion:
+                    self.n_coast[b] = 0
                 continue
             for s in np.flatnonzero(self.id[b]):                   # retire
                 if now - int(self.t_last[b, s]) > o["max_age_us"]:
-                    self.id[b, s], self.vel[b, s] = 0, 0
+                    self.id[b, s] = 0
+                    if motion:
+                        self.vel[b, s] = 0
                     self.events["retired"] += 1
             live = [int(s) for s in np.flatnonzero(self.id[b])]
-            dt, pred = {}, {}
-            with np.errstate(all="ignore"):
-                for s in live:                                     # predict, once, from the state before the step
-                    dt[s] = (np.int64(now) - self.t_last[b, s]).astype(f)
-                    pred[s] = np.array([f(self.box[b, s, k] + f(self.vel[b, s, k] * dt[s])) for k in range(4)], f)
+            # what a row is compared with: the slot's box, or where the motion model predicts it.  Either is from before
+            # the step: a matched slot is taken and never compared again, and the spawns come behind the rows
+            against = self.box[b]
+            if motion:
+                dt, pred = {}, {}
+                with np.errstate(all="ignore"):
+                    for s in live:                                 # predict, once
+                        dt[s] = (np.int64(now) - self.t_last[b, s]).astype(f)
+                        pred[s] = np.array([f(self.box[b, s, k] + f(self.vel[b, s, k] * dt[s])) for k in range(4)], f)
+                against = pred
             eligible = [i for i in range(n) if det[b, i, 4] >= min_score]         # (a NaN score compares false)
             lost = max(0, len(eligible) - DAGR_TRACK_MAX_DETS)
             unmatched, taken = [], set()
-            for i in eligible[:DAGR_TRACK_MAX_DETS]:               # match, against the predictions
+            for i in eligible[:DAGR_TRACK_MAX_DETS]:               # match
                 with np.errstate(all="ignore"):
                     label = int(det[b, i, 5].astype(np.int32))
                 best, best_s = None, None
                 for s in live:
                     if s in taken or int(self.label[b, s]) != label:
                         continue
-                    v = self.iou(det[b, i, :4], pred[s])
+                    v = self.iou(det[b, i, :4], against[s])
                     if not v >= thr:                               # (a NaN IoU never matches)
                         continue
                     if best is None or v > best or (v == best and self.id[b, s] < self.id[b, best_s]):
@@ -463,28 +415,32 @@ class TrackDefinition:
                 if best_s is None:
                     unmatched.append((i, label))
                     continue
-                s = best_s
-                if not any(self.iou(det[b, i, :4], self.box[b, c]) >= thr for c in [s] + live
-                           if c not in taken and int(self.label[b, c]) == label):
+                s, z = best_s, det[b, i, :4]
+                if motion and not any(self.iou(z, self.box[b, c]) >= thr for c in live
+                                      if c not in taken and int(self.label[b, c]) == label):
                     self.events["motion_only"] += 1                # (the plain rule would have spawned this row)
                 taken.add(s)
-                z = det[b, i, :4]
-                with np.errstate(all="ignore"):
-                    r = np.array([f(z[k] - pred[s][k]) for k in range(4)], f)
-                    if dt[s] > 0:
-                        q = np.array([f(r[k] / dt[s]) for k in range(4)], f)
-                        self.vel[b, s] = q if self.hits[b, s] == 1 else \
-                            np.array([f(self.vel[b, s, k] + f(beta * q[k])) for k in range(4)], f)
-                    self.box[b, s] = z if alpha == 1 else np.array([f(pred[s][k] + f(alpha * r[k])) for k in range(4)], f)
+                if motion:                                         # filter: the row pulls box and vel off the prediction
+                    with np.errstate(all="ignore"):
+                        r = np.array([f(z[k] - pred[s][k]) for k in range(4)], f)
+                        if dt[s] > 0:
+                            q = np.array([f(r[k] / dt[s]) for k in range(4)], f)
+                            self.vel[b, s] = q if self.hits[b, s] == 1 else \
+                                np.array([f(self.vel[b, s, k] + f(beta * q[k])) for k in range(4)], f)
+                        self.box[b, s] = z if alpha == 1 else np.array([f(pred[s][k] + f(alpha * r[k])) for k in range(4)], f)
+                else:
+                    self.box[b, s] = z
                 self.t_last[b, s] = now
                 self.hits[b, s] += 1
                 ids[b, i], hits[b, i] = self.id[b, s], self.hits[b, s]
-                self.track_box[b, i], self.track_vel[b, i] = self.box[b, s], self.vel[b, s]
+                if motion:
+                    self.track_box[b, i], self.track_vel[b, i] = self.box[b, s], self.vel[b, s]
                 self.events["matched"] += 1
             free = [int(s) for s in np.flatnonzero(self.id[b] == 0)]
-            for (i, label), s in zip(unmatched, free):             # spawn, at rest
+            for (i, label), s in zip(unmatched, free):             # spawn (with motion: at rest)
                 self.id[b, s], self.t_last[b, s], self.box[b, s] = self.next_id[b], now, det[b, i, :4]
-                self.vel[b, s] = 0
+                if motion:
+                    self.vel[b, s] = 0
                 self.label[b, s], self.hits[b, s] = label, 1
                 ids[b, i], hits[b, i] = self.next_id[b], 1
                 self.next_id[b] += 1
@@ -494,12 +450,13 @@ class TrackDefinition:
             lost += max(0, len(unmatched) - len(free))
             self.untracked[b] += lost
             self.events["untracked"] += lost
-            coast = [s for s in live if s not in taken]            # coast: lived before the rows, seen by none; slot order
-            for j, s in enumerate(coast):
-                self.coast_id[b, j], self.coast_box[b, j], self.coast_label[b, j] = self.id[b, s], pred[s], self.label[b, s]
-                self.coast_age_us[b, j] = np.int64(now) - self.t_last[b, s]
-            self.n_coast[b] = len(coast)
-            self.events["coasted"] += len(coast)
+            if motion:
+                coast = [s for s in live if s not in taken]        # coast: lived before the rows, seen by none; slot order
+                for j, s in enumerate(coast):
+                    self.coast_id[b, j], self.coast_box[b, j], self.coast_label[b, j] = self.id[b, s], pred[s], self.label[b, s]
+                    self.coast_age_us[b, j] = np.int64(now) - self.t_last[b, s]
+                self.n_coast[b] = len(coast)
+                self.events["coasted"] += len(coast)
         return ids, hits
 
     def coasting(self):
@@ -918,15 +875,10 @@ class EventStream:
                                        frame_lanes=frame_lanes)
         detections = detections_from_device(det, n_keep)        # the step's one synchronisation
         if self.track is not None:                              # cut by the counts that read-back brought
-            ids, hits = self.state.track_ids.clone(), self.state.track_hits.clone()
-            for b, d in enumerate(detections):
-                n = int(d["scores"].shape[0])
-                d["track_ids"], d["track_hits"] = ids[b, :n], hits[b, :n]
-            if self.motion is not None:
-                boxes, vel = self.state.track_boxes.clone(), self.state.track_vel.clone()
+            for name in ("track_ids", "track_hits") + (("track_boxes", "track_vel") if self.motion is not None else ()):
+                rows = getattr(self.state, name).clone()
                 for b, d in enumerate(detections):
-                    n = int(d["scores"].shape[0])
-                    d["track_boxes"], d["track_vel"] = boxes[b, :n], vel[b, :n]
+                    d[name] = rows[b, :int(d["scores"].shape[0])]
         self.model.engine().stream_counted(self.state)          # the counts came back with it
         if self.model.check_device_status:
             self.check_status()
@@ -963,11 +915,9 @@ class EventStream:
         """Per lane the live tracks of a tracking stream, a ``TRACK_DTYPE`` array (``id, x1, y1, x2, y2, label, t_last,
         hits``) sorted by id (copies; synchronises).  A motion stream's arrays are ``TRACK_MOTION_DTYPE``: ``vx1, vy1, vx2,
         vy2`` (pixels per microsecond) appended."""
-        if self.motion is not None:
-            ids, t_last, box, vel, label, hits, _ = self.state.track_slots()
-            return [tracks_from_arrays(ids[b], t_last[b], box[b], label[b], hits[b], vel[b]) for b in range(self.B)]
-        ids, t_last, box, label, hits, _ = self.state.track_slots()
-        return [tracks_from_arrays(ids[b], t_last[b], box[b], label[b], hits[b]) for b in range(self.B)]
+        *slots, _ = self.state.track_slots()                    # id, t_last, box, (vel,) label, hits; next_id
+        vel = slots.pop(3) if self.motion is not None else [None] * self.B
+        return [tracks_from_arrays(*(a[b] for a in slots), vel[b]) for b in range(self.B)]
 
     def coast_device(self):
         """The last step's coast lists of a motion stream as the raw device tensors ``(n_coast int32 [B], coast_id int64
