@@ -1,13 +1,23 @@
-// stream_track.hip -- the event stream's tracker (dagr_stream_track, dagr_stream_track_cv): the detections of a step are
-// associated with the tracks the lane carries from step to step, by greedy IoU matching inside a label, and get a track id.
+// stream_track.hip -- the event stream's tracker (dagr_stream_track, dagr_stream_track_cv and their _rescue entries): the
+// detections of a step are associated with the tracks the lane carries from step to step, by greedy IoU matching inside a
+// label, and get a track id.
 //
-// ONE kernel, k_stream_track<MOTION>, instantiated twice: retirement, eligibility, the match with its tie rule and the spawn
-// are written once.  <false> is dagr_stream_track.  <true> is dagr_stream_track_cv, the same walk with a constant-velocity
+// ONE kernel, k_stream_track<MOTION, RESCUE>, instantiated four times: retirement, eligibility, the match with its tie rule
+// and the spawn are written once.  Below, <false> and <true> stand for MOTION with RESCUE = false.  <false> is dagr_stream_track.  <true> is dagr_stream_track_cv, the same walk with a constant-velocity
 // motion model (TrackDefinition(motion=)): a slot also holds `vel`; every live slot is predicted once, in front of the row
 // loop, to pred = box + vel * fp32(t_ref - t_last), the rows are compared against pred, a match filters box and vel, and
 // the live tracks that no row matched leave their prediction in the lane's coast list -- one ballot compaction per slot
 // register.  Whatever exists only with the motion model stands under `if constexpr (MOTION)`; nothing of it is left in
 // the code of <false>.  The two states have layouts of their own (include/dagr_hip.h).
+//
+// RESCUE (dagr_stream_track_rescue, dagr_stream_track_cv_rescue; TrackDefinition(rescue=)) adds a second association round
+// on the same states: the rows with low_score <= score < min_score are staged in LDS rows of their own (behind the high
+// rows', in the same arrays) while the high rows are, walk the tracks that round one left unmatched through the SAME match
+// body at an IoU threshold of their own, and never spawn.  The body is shared by making the row loop run over both rounds,
+// not by a lambda or a function: with the body in a lambda the instantiations that existed before lost their instruction
+// stream (other registers, another schedule), as a loop they keep it instruction for instruction, with their registers and
+// their LDS (profiles/stream_rescue.md).  A low row that does not match has no effect, so round two stops when a ballot
+// shows no live untaken track.  Whatever only round two has stands under `if constexpr (RESCUE)` or folds away with it.
 //
 // One workgroup of ONE wave per lane.  A thread holds the slots `lane`, `lane + 64`, ... of its lane's max_tracks slots in
 // registers (kMaxTracks / 64 = 4 at most).  The walk over the rows is serial, as greedy matching is; the work of a row is
@@ -89,17 +99,20 @@ struct MotionOut {
 // The order of the arguments is measured, not taste: what only the motion model has comes last (st.vel, alpha, beta, o), so
 // that everything <false> reads lies in the first 128 bytes of the argument segment, which is all its kernel had when it
 // was a kernel of its own.  With the state first and `vel` in its middle, <false> read a third 64-byte line of arguments
-// and a launch took 0.3 us longer (profiles/stream_track_unified.md).
-template <bool MOTION>
+// and a launch took 0.3 us longer (profiles/stream_track_unified.md).  What only RESCUE has (low_score, low_iou, rescued) comes
+// behind that again, for the same reason.
+template <bool MOTION, bool RESCUE>
 __global__ __launch_bounds__(kWave) void k_stream_track(int M, float iou_thr, int64_t max_age, float min_score,
                                                         const float *__restrict__ det, const int32_t *__restrict__ n_keep,
                                                         int A, const int64_t *__restrict__ t_ref,
                                                         int64_t *__restrict__ track_id, int32_t *__restrict__ track_hits,
                                                         int64_t *__restrict__ untracked, Tracks st, float alpha, float beta,
-                                                        MotionOut o) {
-    __shared__ float4 s_box[kMaxDets];          // the participating rows, in row order
-    __shared__ int32_t s_label[kMaxDets];
-    __shared__ int32_t s_row[kMaxDets];         // their row in det
+                                                        MotionOut o, float low_score, float low_iou,
+                                                        int64_t *__restrict__ rescued) {
+    constexpr int kRows = RESCUE ? 2 * kMaxDets : kMaxDets;     // RESCUE: the participating low rows at kMaxDets and behind
+    __shared__ float4 s_box[kRows];             // the participating rows, in row order
+    __shared__ int32_t s_label[kRows];
+    __shared__ int32_t s_row[kRows];            // their row in det
     __shared__ int32_t s_spawn[kMaxDets];       // k-th unmatched participating row
 
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -164,6 +177,7 @@ __global__ __launch_bounds__(kWave) void k_stream_track(int M, float iou_thr, in
 
     // ---- the eligible rows, 64 at a time: the first kMaxDets of them take part and go to the LDS in row order
     int n_eligible = 0;
+    int n_low = 0;                              // RESCUE only
     for (int first = 0; first < n; first += kWave) {
         const int i = first + lane;
         float4 r = zero4;
@@ -178,10 +192,21 @@ __global__ __launch_bounds__(kWave) void k_stream_track(int M, float iou_thr, in
         const uint64_t mask = __ballot(eligible);
         const int rank = n_eligible + lanes_below(mask, lane);
         n_eligible += __popcll(mask);
+        int low_rank = kMaxDets;                                   // RESCUE: the row's place among the low rows, if it is one
+        if constexpr (RESCUE) {
+            const bool low = i < n && score >= low_score && !(score >= min_score);   // (a NaN score is in neither band)
+            const uint64_t low_mask = __ballot(low);
+            if (low) low_rank = n_low + lanes_below(low_mask, lane);
+            n_low += __popcll(low_mask);
+        }
         if (eligible && rank < kMaxDets) {
             s_box[rank] = r;
             s_label[rank] = (int32_t)cls;
             s_row[rank] = i;
+        } else if (RESCUE && low_rank < kMaxDets) {                // waits for round two, which writes its outputs
+            s_box[kMaxDets + low_rank] = r;
+            s_label[kMaxDets + low_rank] = (int32_t)cls;
+            s_row[kMaxDets + low_rank] = i;
         } else if (i < n) {                                        // no id.  MOTION: the row's own box, no velocity
             out_id[i] = 0;
             out_hits[i] = 0;
@@ -194,10 +219,29 @@ __global__ __launch_bounds__(kWave) void k_stream_track(int M, float iou_thr, in
     // ---- match: the rows in order, every thread against its own slots; thread r % 64 remembers the unmatched row r.
     // MOTION compares a row with pred[k], where the track is predicted to be, and without it with box[k].  That is the
     // box from before the step in both: a matched slot is `taken` and never compared again, and spawns come after the loop.
+    //
+    // RESCUE: ONE loop is both rounds, so the body below is written once.  Behind the P high rows it walks the PL low rows,
+    // which lie at kMaxDets and behind, at their own threshold; thread r % 64 remembers the MATCHED low row r.  A low row
+    // that does not match changes nothing, so the walk ends when a ballot finds no live untaken track.
     uint32_t taken = 0, unmatched = 0;
-    for (int r = 0; r < P; r++) {
-        const float4 d = s_box[r];
-        const int32_t cls = s_label[r];
+    uint32_t low_matched = 0;                   // RESCUE only, as are PL and n_rescued
+    const int PL = RESCUE ? min(n_low, kMaxDets) : 0;
+    int n_rescued = 0;
+    for (int r = 0; r < P + PL; r++) {
+        bool second = false;
+        int at = r;
+        float thr = iou_thr;
+        if constexpr (RESCUE) {
+            if (r >= P) {
+                bool open = false;
+#pragma unroll
+                for (int k = 0; k < kSlots; k++) open |= id[k] != 0 && !((taken >> k) & 1u);
+                if (__ballot(open) == 0) break;
+                second = true, at = kMaxDets + (r - P), thr = low_iou;
+            }
+        }
+        const float4 d = s_box[at];
+        const int32_t cls = s_label[at];
         float best = 0.0f;
         int64_t best_id = 0;
         int best_k = -1;
@@ -207,7 +251,7 @@ __global__ __launch_bounds__(kWave) void k_stream_track(int M, float iou_thr, in
             float v;
             if constexpr (MOTION) v = iou_xyxy(d, pred[k]);
             else v = iou_xyxy(d, box[k]);
-            if (!(v >= iou_thr)) continue;                             // (a NaN IoU never matches)
+            if (!(v >= thr)) continue;                                 // (a NaN IoU never matches)
             if (best_k < 0 || v > best || (v == best && id[k] < best_id)) {
                 best = v;
                 best_id = id[k];
@@ -216,8 +260,14 @@ __global__ __launch_bounds__(kWave) void k_stream_track(int M, float iou_thr, in
         }
         uint64_t cand = __ballot(best_k >= 0);
         if (cand == 0) {
-            if (lane == (r & 63)) unmatched |= 1u << (r >> 6);
+            if (!second && lane == (r & 63)) unmatched |= 1u << (r >> 6);
             continue;
+        }
+        if constexpr (RESCUE) {
+            if (second) {
+                if (lane == ((r - P) & 63)) low_matched |= 1u << ((r - P) >> 6);
+                n_rescued++;
+            }
         }
         if (cand & (cand - 1)) {                                      // several threads have one: largest IoU, lowest id
             float top = best_k >= 0 ? best : -1.0f;
@@ -235,7 +285,7 @@ __global__ __launch_bounds__(kWave) void k_stream_track(int M, float iou_thr, in
             }
         }
         if (lane == __ffsll((unsigned long long)cand) - 1) {
-            const int row = s_row[r];
+            const int row = s_row[at];
 #pragma unroll
             for (int k = 0; k < kSlots; k++) {
                 if (k != best_k) continue;
@@ -261,6 +311,18 @@ __global__ __launch_bounds__(kWave) void k_stream_track(int M, float iou_thr, in
                 out_hits[row] = hits[k];
                 if constexpr (MOTION) out_box[row] = box[k], out_vel[row] = vel[k];
             }
+        }
+    }
+
+    if constexpr (RESCUE) {                     // the low rows no track took: no id.  MOTION: the row's own box, no velocity
+#pragma unroll
+        for (int q = 0; q < kMaxDets / kWave; q++) {
+            const int r = q * kWave + lane;
+            if (r >= PL || ((low_matched >> q) & 1u)) continue;
+            const int row = s_row[kMaxDets + r];
+            out_id[row] = 0;
+            out_hits[row] = 0;
+            if constexpr (MOTION) out_box[row] = s_box[kMaxDets + r], out_vel[row] = zero4;
         }
     }
 
@@ -342,6 +404,9 @@ __global__ __launch_bounds__(kWave) void k_stream_track(int M, float iou_thr, in
         st.next_id[b] = first_id + n_spawn;
         const int lost = (n_eligible - P) + (n_unmatched - n_spawn);
         if (untracked && lost > 0) untracked[b] += lost;
+        if constexpr (RESCUE) {
+            if (rescued && n_rescued > 0) rescued[b] += n_rescued;
+        }
     }
 }
 
@@ -395,6 +460,88 @@ int track_check_args(const char *entry, bool motion, void *tracks, size_t bytes,
     return DAGR_OK;
 }
 
+// A refusal by name of the entry point that was called, from a helper that several entries share.
+#define ENTRY_CHECK_ARG(cond, msg)                                             \
+    do {                                                                       \
+        if (!(cond)) {                                                         \
+            set_error(std::string(entry) + ": " + (msg));                      \
+            return DAGR_ERR_INVALID_ARG;                                       \
+        }                                                                      \
+    } while (0)
+
+// What the _rescue entries refuse in addition, behind everything their base entry refuses.
+int rescue_check_args(const char *entry, bool motion, float min_score, float low_score, float low_iou, const int64_t *rescued) {
+    const std::string who = std::string(track_prefix(motion)) + " rescue";
+    TRACK_CHECK_ARG(low_score == low_score, "low_score is NaN");
+    TRACK_CHECK_ARG(low_score < min_score, "low_score must be below min_score (no score lies in between; raise min_score)");
+    TRACK_CHECK_ARG(low_iou > 0.0f && low_iou <= 1.0f, "low_iou must be in (0, 1]");
+    TRACK_CHECK_ARG(((uintptr_t)rescued & 7) == 0, "rescued must be 8-byte aligned");
+    return DAGR_OK;
+}
+
+// dagr_stream_track (rescue = false: the three last arguments are not looked at) and dagr_stream_track_rescue
+int step_plain(const char *entry, bool rescue, void *tracks, size_t bytes, int32_t B, int32_t max_tracks, float iou,
+               int64_t max_age_us, float min_score, const float *det, const int32_t *n_keep, int32_t A, const int64_t *t_ref,
+               int64_t *track_id, int32_t *track_hits, int64_t *untracked, float low_score, float low_iou, int64_t *rescued,
+               void *stream) {
+    Tracks st;
+    if (const int rc = track_check_args(entry, false, tracks, bytes, B, max_tracks, iou, max_age_us, det, n_keep, A, t_ref,
+                                        track_id, track_hits, untracked, &st))
+        return rc;
+    if (rescue) {
+        if (const int rc = rescue_check_args(entry, false, min_score, low_score, low_iou, rescued)) return rc;
+        k_stream_track<false, true><<<(unsigned)B, kWave, 0, (hipStream_t)stream>>>(
+            max_tracks, iou, max_age_us, min_score, det, n_keep, A, t_ref, track_id, track_hits, untracked, st, 0.0f, 0.0f,
+            MotionOut{}, low_score, low_iou, rescued);
+    } else {
+        k_stream_track<false, false><<<(unsigned)B, kWave, 0, (hipStream_t)stream>>>(
+            max_tracks, iou, max_age_us, min_score, det, n_keep, A, t_ref, track_id, track_hits, untracked, st, 0.0f, 0.0f,
+            MotionOut{}, 0.0f, 0.0f, nullptr);
+    }
+    DAGR_CHECK_LAUNCH();
+    return DAGR_OK;
+}
+
+// dagr_stream_track_cv and dagr_stream_track_cv_rescue, likewise
+int step_cv(const char *entry, bool rescue, void *tracks, size_t bytes, int32_t B, int32_t max_tracks, float iou,
+            int64_t max_age_us, float min_score, float alpha, float beta, const float *det, const int32_t *n_keep, int32_t A,
+            const int64_t *t_ref, int64_t *track_id, int32_t *track_hits, float *track_box, float *track_vel,
+            int64_t *coast_id, float *coast_box, int32_t *coast_label, int64_t *coast_age_us, int32_t *n_coast,
+            int64_t *untracked, float low_score, float low_iou, int64_t *rescued, void *stream) {
+    // what the motion model adds; the rest is dagr_stream_track's
+    ENTRY_CHECK_ARG(max_age_us <= DAGR_TRACK_CV_MAX_AGE_US,
+                    "stream track cv: max_age_us must not exceed DAGR_TRACK_CV_MAX_AGE_US = 2^24 - 1 (a live track's age is exact in fp32)");
+    ENTRY_CHECK_ARG(alpha > 0.0f && alpha <= 1.0f, "stream track cv: alpha must be in (0, 1]");
+    ENTRY_CHECK_ARG(beta >= 0.0f && beta <= 1.0f, "stream track cv: beta must be in [0, 1]");
+    ENTRY_CHECK_ARG(A == 0 || (det && track_id && track_hits && track_box && track_vel),
+                    "stream track cv: NULL detections or outputs (track_id, track_hits, track_box, track_vel)");
+    const bool coast = coast_id || coast_box || coast_label || coast_age_us || n_coast;
+    ENTRY_CHECK_ARG(!coast || (coast_id && coast_box && coast_label && coast_age_us && n_coast),
+                    "stream track cv: coast_id, coast_box, coast_label, coast_age_us and n_coast are NULL together or not at all");
+    ENTRY_CHECK_ARG((((uintptr_t)track_box | (uintptr_t)track_vel | (uintptr_t)coast_box) & 15) == 0,
+                    "stream track cv: track_box, track_vel and coast_box must be 16-byte aligned (one store a box)");
+    ENTRY_CHECK_ARG((((uintptr_t)coast_id | (uintptr_t)coast_age_us) & 7) == 0 &&
+                        (((uintptr_t)coast_label | (uintptr_t)n_coast) & 3) == 0,
+                    "stream track cv: coast_id and coast_age_us must be 8-byte aligned, coast_label and n_coast 4-byte");
+    Tracks st;
+    if (const int rc = track_check_args(entry, true, tracks, bytes, B, max_tracks, iou, max_age_us, det, n_keep, A, t_ref,
+                                        track_id, track_hits, untracked, &st))
+        return rc;
+    const MotionOut o = {(float4 *)track_box, (float4 *)track_vel, coast_id, (float4 *)coast_box, coast_label, coast_age_us, n_coast};
+    if (rescue) {
+        if (const int rc = rescue_check_args(entry, true, min_score, low_score, low_iou, rescued)) return rc;
+        k_stream_track<true, true><<<(unsigned)B, kWave, 0, (hipStream_t)stream>>>(
+            max_tracks, iou, max_age_us, min_score, det, n_keep, A, t_ref, track_id, track_hits, untracked, st, alpha, beta, o,
+            low_score, low_iou, rescued);
+    } else {
+        k_stream_track<true, false><<<(unsigned)B, kWave, 0, (hipStream_t)stream>>>(
+            max_tracks, iou, max_age_us, min_score, det, n_keep, A, t_ref, track_id, track_hits, untracked, st, alpha, beta, o,
+            0.0f, 0.0f, nullptr);
+    }
+    DAGR_CHECK_LAUNCH();
+    return DAGR_OK;
+}
+
 }  // namespace
 }  // namespace dagr
 
@@ -414,15 +561,16 @@ extern "C" int dagr_stream_track_cv_reset(void *tracks, size_t bytes, int32_t B,
 extern "C" int dagr_stream_track(void *tracks, size_t bytes, int32_t B, int32_t max_tracks, float iou, int64_t max_age_us,
                                  float min_score, const float *det, const int32_t *n_keep, int32_t A, const int64_t *t_ref,
                                  int64_t *track_id, int32_t *track_hits, int64_t *untracked, void *stream) {
-    Tracks st;
-    if (const int rc = track_check_args(__func__, false, tracks, bytes, B, max_tracks, iou, max_age_us, det, n_keep, A, t_ref,
-                                        track_id, track_hits, untracked, &st))
-        return rc;
-    k_stream_track<false><<<(unsigned)B, kWave, 0, (hipStream_t)stream>>>(max_tracks, iou, max_age_us, min_score, det, n_keep, A,
-                                                                        t_ref, track_id, track_hits, untracked, st, 0.0f, 0.0f,
-                                                                        MotionOut{});
-    DAGR_CHECK_LAUNCH();
-    return DAGR_OK;
+    return step_plain(__func__, false, tracks, bytes, B, max_tracks, iou, max_age_us, min_score, det, n_keep, A, t_ref, track_id,
+                      track_hits, untracked, 0.0f, 0.0f, nullptr, stream);
+}
+
+extern "C" int dagr_stream_track_rescue(void *tracks, size_t bytes, int32_t B, int32_t max_tracks, float iou, int64_t max_age_us,
+                                        float min_score, const float *det, const int32_t *n_keep, int32_t A,
+                                        const int64_t *t_ref, int64_t *track_id, int32_t *track_hits, int64_t *untracked,
+                                        float low_score, float low_iou, int64_t *rescued, void *stream) {
+    return step_plain(__func__, true, tracks, bytes, B, max_tracks, iou, max_age_us, min_score, det, n_keep, A, t_ref, track_id,
+                      track_hits, untracked, low_score, low_iou, rescued, stream);
 }
 
 extern "C" int dagr_stream_track_cv(void *tracks, size_t bytes, int32_t B, int32_t max_tracks, float iou, int64_t max_age_us,
@@ -430,28 +578,18 @@ extern "C" int dagr_stream_track_cv(void *tracks, size_t bytes, int32_t B, int32
                                     int32_t A, const int64_t *t_ref, int64_t *track_id, int32_t *track_hits, float *track_box,
                                     float *track_vel, int64_t *coast_id, float *coast_box, int32_t *coast_label,
                                     int64_t *coast_age_us, int32_t *n_coast, int64_t *untracked, void *stream) {
-    // what the motion model adds; the rest is dagr_stream_track's
-    DAGR_CHECK_ARG(max_age_us <= DAGR_TRACK_CV_MAX_AGE_US,
-                   "stream track cv: max_age_us must not exceed DAGR_TRACK_CV_MAX_AGE_US = 2^24 - 1 (a live track's age is exact in fp32)");
-    DAGR_CHECK_ARG(alpha > 0.0f && alpha <= 1.0f, "stream track cv: alpha must be in (0, 1]");
-    DAGR_CHECK_ARG(beta >= 0.0f && beta <= 1.0f, "stream track cv: beta must be in [0, 1]");
-    DAGR_CHECK_ARG(A == 0 || (det && track_id && track_hits && track_box && track_vel),
-                   "stream track cv: NULL detections or outputs (track_id, track_hits, track_box, track_vel)");
-    const bool coast = coast_id || coast_box || coast_label || coast_age_us || n_coast;
-    DAGR_CHECK_ARG(!coast || (coast_id && coast_box && coast_label && coast_age_us && n_coast),
-                   "stream track cv: coast_id, coast_box, coast_label, coast_age_us and n_coast are NULL together or not at all");
-    DAGR_CHECK_ARG((((uintptr_t)track_box | (uintptr_t)track_vel | (uintptr_t)coast_box) & 15) == 0,
-                   "stream track cv: track_box, track_vel and coast_box must be 16-byte aligned (one store a box)");
-    DAGR_CHECK_ARG((((uintptr_t)coast_id | (uintptr_t)coast_age_us) & 7) == 0 &&
-                       (((uintptr_t)coast_label | (uintptr_t)n_coast) & 3) == 0,
-                   "stream track cv: coast_id and coast_age_us must be 8-byte aligned, coast_label and n_coast 4-byte");
-    Tracks st;
-    if (const int rc = track_check_args(__func__, true, tracks, bytes, B, max_tracks, iou, max_age_us, det, n_keep, A, t_ref,
-                                        track_id, track_hits, untracked, &st))
-        return rc;
-    const MotionOut o = {(float4 *)track_box, (float4 *)track_vel, coast_id, (float4 *)coast_box, coast_label, coast_age_us, n_coast};
-    k_stream_track<true><<<(unsigned)B, kWave, 0, (hipStream_t)stream>>>(max_tracks, iou, max_age_us, min_score, det, n_keep, A,
-                                                                       t_ref, track_id, track_hits, untracked, st, alpha, beta, o);
-    DAGR_CHECK_LAUNCH();
-    return DAGR_OK;
+    return step_cv(__func__, false, tracks, bytes, B, max_tracks, iou, max_age_us, min_score, alpha, beta, det, n_keep, A, t_ref,
+                   track_id, track_hits, track_box, track_vel, coast_id, coast_box, coast_label, coast_age_us, n_coast, untracked,
+                   0.0f, 0.0f, nullptr, stream);
+}
+
+extern "C" int dagr_stream_track_cv_rescue(void *tracks, size_t bytes, int32_t B, int32_t max_tracks, float iou,
+                                           int64_t max_age_us, float min_score, float alpha, float beta, const float *det,
+                                           const int32_t *n_keep, int32_t A, const int64_t *t_ref, int64_t *track_id,
+                                           int32_t *track_hits, float *track_box, float *track_vel, int64_t *coast_id,
+                                           float *coast_box, int32_t *coast_label, int64_t *coast_age_us, int32_t *n_coast,
+                                           int64_t *untracked, float low_score, float low_iou, int64_t *rescued, void *stream) {
+    return step_cv(__func__, true, tracks, bytes, B, max_tracks, iou, max_age_us, min_score, alpha, beta, det, n_keep, A, t_ref,
+                   track_id, track_hits, track_box, track_vel, coast_id, coast_box, coast_label, coast_age_us, n_coast, untracked,
+                   low_score, low_iou, rescued, stream);
 }

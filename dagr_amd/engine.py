@@ -409,7 +409,9 @@ class StreamState:
     A tracking stream (``enable_track``) owns the tracker's state (``dagr_stream_track``): the lanes' track slots,
     ``lane_untracked``, and the step's ``track_ids`` / ``track_hits``.  With a motion model (``enable_track(...,
     motion=)``) the state is ``dagr_stream_track_cv``'s, which also holds the velocities, and the stream owns the step's
-    ``track_boxes`` / ``track_vel`` and the lanes' coast lists, allocated once."""
+    ``track_boxes`` / ``track_vel`` and the lanes' coast lists, allocated once.  With a second association round
+    (``enable_track(..., rescue=)``) the step ends with the ``_rescue`` entry of either, on the same state, and the stream
+    owns ``lane_rescued``."""
 
     def __init__(self, batch_size, window_us, device, max_lane_events=None):
         self.B, self.window_us, self.device = int(batch_size), int(window_us), torch.device(device)
@@ -436,6 +438,7 @@ class StreamState:
         self.track_state, self.lane_untracked, self.track_ids, self.track_hits = None, None, None, None
         self.motion = None                              # the options of its motion model (dagr.streaming._motion_options)
         self.track_boxes, self.track_vel, self.coast = None, None, None
+        self.rescue, self.lane_rescued = None, None     # the options of its second round (dagr.streaming._rescue_options)
         self._t_ref = None                              # (state pointer, capacity, where its t_ref[B] lives)
 
     # ------------------------------------------------------------------------------------ track ids
@@ -443,11 +446,14 @@ class StreamState:
     TRACK_FIELDS = (("id", torch.int64, 1), ("t_last", torch.int64, 1), ("box", torch.float32, 4), ("vel", torch.float32, 4),
                     ("label", torch.int32, 1), ("hits", torch.int32, 1))
 
-    def enable_track(self, options, motion=None):
+    def enable_track(self, options, motion=None, rescue=None):
         """Every step ends with ``dagr_stream_track``: ``options`` as ``dagr.streaming._track_options`` returns them.
         Allocates the lanes' slots, empty, and ``lane_untracked``.  With ``motion`` (as ``_motion_options`` returns it)
-        the step ends with ``dagr_stream_track_cv`` instead, on a state of that layout, and the coast lists are allocated."""
+        the step ends with ``dagr_stream_track_cv`` instead, on a state of that layout, and the coast lists are allocated.
+        With ``rescue`` (as ``_rescue_options`` returns it) the step ends with the ``_rescue`` entry of the one or the
+        other, on the same state -- ``_bytes`` and ``_reset`` are the family's --, and ``lane_rescued`` is allocated."""
         self.track, self.motion = dict(options), None if motion is None else dict(motion)
+        self.rescue = None if rescue is None else dict(rescue)
         # the family of entry points dagr_<family>, dagr_<family>_bytes, dagr_<family>_reset, chosen here once -- as a
         # name: every call looks its function up on the library
         self._track_family = "stream_track" if motion is None else "stream_track_cv"
@@ -457,6 +463,8 @@ class StreamState:
             raise RuntimeError(f"dagr_{self._track_family}_bytes({self.B}, {M}): out of range")
         self.track_state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.lane_untracked = torch.zeros((self.B,), dtype=torch.int64, device=dev)
+        if rescue is not None:
+            self.lane_rescued = torch.zeros((self.B,), dtype=torch.int64, device=dev)
         if motion is not None:
             self.coast = (torch.zeros((self.B,), dtype=torch.int32, device=dev),            # n_coast
                           torch.zeros((self.B, M), dtype=torch.int64, device=dev),          # coast_id
@@ -473,13 +481,16 @@ class StreamState:
         _lib.check(self._track_fn("_reset")(_lib.ptr(self.track_state), self.track_state.numel(), self.B, self.track["max_tracks"],
                                             _lib.cur_stream(self.device)), self._track_family + "_reset")
         self.lane_untracked.zero_()
+        if self.rescue is not None:
+            self.lane_rescued.zero_()
         if self.motion is not None:
             self.coast[0].zero_()
 
     def run_track(self, det, n_keep):
         """``dagr_stream_track`` on a step's detections, at the reference instants the step's staging left in the stream
         state: ``track_ids`` int64 [B, A] and ``track_hits`` int32 [B, A], valid until the next step.  With a motion model
-        ``dagr_stream_track_cv`` instead, never both: it also leaves ``track_boxes`` / ``track_vel`` and the coast lists."""
+        ``dagr_stream_track_cv`` instead, never both: it also leaves ``track_boxes`` / ``track_vel`` and the coast lists.
+        With a second round the one launch is the ``_rescue`` entry of either, which also adds to ``lane_rescued``."""
         B, A = int(det.shape[0]), int(det.shape[1])
         if B != self.B or det.dtype != torch.float32 or not det.is_contiguous() or n_keep.dtype != torch.int32:
             raise RuntimeError(f"run_track: det must be contiguous fp32 [{self.B}, A, 6] and n_keep int32 [{self.B}]")
@@ -500,16 +511,25 @@ class StreamState:
             n_coast, c_id, c_box, c_label, c_age = self.coast
             gains = [self.motion["alpha"], self.motion["beta"]]
             outputs = [P(self.track_boxes), P(self.track_vel), P(c_id), P(c_box), P(c_label), P(c_age), P(n_coast)]
-        _lib.check(self._track_fn()(P(self.track_state), self.track_state.numel(), self.B, o["max_tracks"], o["iou"],
-                                    o["max_age_us"], o["min_score"], *gains, P(det), P(n_keep), A, self._t_ref[2],
-                                    P(self.track_ids), P(self.track_hits), *outputs, P(self.lane_untracked),
-                                    _lib.cur_stream(self.device)), self._track_family)
+        suffix, second = "", []             # what the _rescue entries take in addition, behind `untracked`
+        if self.rescue is not None:
+            suffix, second = "_rescue", [self.rescue["low_score"], self.rescue["iou"], P(self.lane_rescued)]
+        _lib.check(self._track_fn(suffix)(P(self.track_state), self.track_state.numel(), self.B, o["max_tracks"], o["iou"],
+                                          o["max_age_us"], o["min_score"], *gains, P(det), P(n_keep), A, self._t_ref[2],
+                                          P(self.track_ids), P(self.track_hits), *outputs, P(self.lane_untracked), *second,
+                                          _lib.cur_stream(self.device)), self._track_family + suffix)
 
     def untracked(self):
         """Per-lane eligible rows that got no track id, int64 [B] (synchronises)."""
         if self.track is None:
             raise RuntimeError("this stream does not track (track=): it has no untracked count")
         return self.lane_untracked.cpu().numpy()
+
+    def rescued(self):
+        """Per-lane matches of the second association round, int64 [B] (synchronises)."""
+        if self.rescue is None:
+            raise RuntimeError("this stream has no second association round (rescue=): it has no rescued count")
+        return self.lane_rescued.cpu().numpy()
 
     def track_slots(self):
         """The lanes' slots read back as ``(id int64, t_last int64, box fp32[., 4], label int32, hits int32)`` over

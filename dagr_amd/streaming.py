@@ -140,6 +140,33 @@ A lane whose ``t_ref`` is "never" behaves as in 1; in addition ``n_coast = 0``, 
 ``track_vel`` 0.  So a track that moves steadily survives a gap of some steps: the returning box is compared with where the
 track is predicted to be, not with where it was last seen, and in between the consumer reads the prediction from the
 coast list without a host-side extrapolation.
+
+A second association round for low-score rows (``rescue=`` of a tracking stream, with or without ``motion=``: ``None`` is
+off, ``True`` takes the defaults, a dict sets ``low_score``, fp32, default 0.1, and ``iou``, fp32 in (0, 1] or ``None`` for
+the tracker's own ``iou``, default ``None``).  It needs ``track=`` and ``low_score < min_score`` as fp32, so ``track``'s
+``min_score`` has to be raised above its default 0.0; 0.1, and the 0.5 ``min_score`` commonly paired with it, are
+ByteTrack's conventions, not measured optima.  A detector's score dips for a few steps; with one hard cut the track ages
+out or comes back under a new id.  With ``rescue`` the rows under the cut may CONTINUE a track, and never start one.
+``TrackDefinition(batch_size, track, motion, rescue=...)`` states it in numpy; ``dagr_stream_track_rescue`` /
+``dagr_stream_track_cv_rescue`` repeat it bit for bit on the state of ``dagr_stream_track`` / ``dagr_stream_track_cv``.
+The order of a step is: 1 (never), 2 (retire), predict, 4 (round one), round two, 5 (spawn), coast.  1, 2, 3, 4, 5 and the
+motion model's predict, filter and coast are what they are above, over the rows of 3 (the HIGH rows); added:
+
+* low rows have ``score >= low_score and not score >= min_score``: a NaN score is in neither band, ``score == low_score``
+  is low, ``score == min_score`` is high.  The first ``DAGR_TRACK_MAX_DETS`` low rows in row order take part.  Every other
+  low row, and every low row that does not match, gets what a row that is not eligible gets: id 0, hits 0, with motion its
+  own box and no velocity, and it is NOT counted in ``untracked``;
+* round two, when every high row has been through 4 and before any spawn: the participating low rows in row order,
+  greedily, by the rule of 4 -- among the live tracks with the row's label that no row of this step, of either round, has
+  matched, the one with the largest IoU (against ``box``; against ``pred`` with motion), the lowest id on a tie; a match if
+  that IoU is ``>=`` rescue's ``iou``, a NaN IoU never matches.  A match does exactly what a match of 4 does (box,
+  ``t_last``, ``hits += 1``, the row's outputs, with motion the same velocity and ``alpha`` filter; the track does not
+  coast), and ``rescued[b] += 1``;
+* spawn (5) takes the unmatched HIGH rows only: a low row never matches a track spawned in its own step and never
+  occupies a slot.  Where a row stands in ``det`` does not decide its round: a low row in front of a high row waits.
+
+``rescued`` is int64 ``[B]``, cumulative, zero after construction and after ``reset()``.  Unlike ByteTrack, round two
+considers every live unmatched track, not only those seen in the step before.  Without ``rescue`` nothing of this exists.
 """
 import numpy as np
 
@@ -305,6 +332,29 @@ def _motion_options(motion, track_options, who):
     return dict(alpha=float(np.float32(opt["alpha"])), beta=float(np.float32(opt["beta"])))
 
 
+RESCUE_DEFAULTS = dict(low_score=0.1, iou=None)     # ByteTrack's conventions, not measured optima; iou None: the tracker's
+
+
+def _rescue_options(rescue, track_options, who):
+    """``rescue=`` of a tracking stream, checked: None (off) or the dict of ``low_score`` and ``iou`` (as fp32) with the
+    defaults filled in and ``iou = None`` resolved to the tracker's own ``iou``; ``track_options`` is what
+    ``_track_options`` returned.  Refusals by name."""
+    opt = _options(rescue, "rescue", RESCUE_DEFAULTS, who)
+    if opt is None:
+        return None
+    if track_options is None:
+        raise ValueError(f"{who}: rescue= needs track= (the second round is the tracker's)")
+    if not _is_real(opt["low_score"]):
+        raise ValueError(f"{who}: rescue low_score = {opt['low_score']!r} must be a float (not NaN)")
+    if opt["iou"] is not None and (not _is_real(opt["iou"]) or not 0 < np.float32(opt["iou"]) <= 1):
+        raise ValueError(f"{who}: rescue iou = {opt['iou']!r} must be a float in (0, 1] (as fp32), or None: track's iou")
+    low, cut = np.float32(opt["low_score"]), np.float32(track_options["min_score"])
+    if not low < cut:
+        raise ValueError(f"{who}: rescue low_score = {float(low)!r} must be below track min_score = {float(cut)!r} (as fp32): "
+                         "no score lies in between; raise track's min_score")
+    return dict(low_score=float(low), iou=float(np.float32(track_options["iou"] if opt["iou"] is None else opt["iou"])))
+
+
 class TrackDefinition:
     """The tracker of the module docstring in numpy: ``step(det, n_keep, t_ref)`` is one step of every lane and returns
     ``(track_id int64 [B, A], track_hits int32 [B, A])`` with the rows at and behind ``n_keep[b]`` zero.  The state is the
@@ -319,12 +369,18 @@ class TrackDefinition:
     ``coast_id``, ``coast_box``, ``coast_label``, ``coast_age_us`` over ``[B, max_tracks]``, whose entries at and behind
     ``n_coast[b]`` are left as they were.  ``events`` then also counts ``coasted`` track-steps and ``motion_only``, the
     matches for which no free track of the row's label had an IoU ``>= iou`` with its UNPREDICTED box -- rows the plain
-    rule would have spawned.  Without ``motion`` nothing of this exists and every result is what it was."""
+    rule would have spawned.  Without ``motion`` nothing of this exists and every result is what it was.
 
-    def __init__(self, batch_size, track=True, motion=None):
+    With ``rescue`` (``True`` or a dict of ``low_score``, ``iou``) the step has the second association round of the module
+    docstring, with or without ``motion``: the yardstick of ``dagr_stream_track_rescue`` / ``dagr_stream_track_cv_rescue``.
+    ``rescued`` int64 ``[B]`` counts the matches of round two, and so does ``events["rescued"]``.  Without ``rescue``
+    neither exists and every result is what it was."""
+
+    def __init__(self, batch_size, track=True, motion=None, rescue=None):
         self.B = int(batch_size)
         self.options = _track_options(track, "TrackDefinition")
         self.motion = _motion_options(motion, self.options, "TrackDefinition")
+        self.rescue = _rescue_options(rescue, self.options, "TrackDefinition")
         if self.options is None:
             raise ValueError("TrackDefinition: track = None is a stream that does not track")
         self.reset()
@@ -344,6 +400,9 @@ class TrackDefinition:
             self.coast_id, self.coast_age_us = np.zeros((B, M), np.int64), np.zeros((B, M), np.int64)
             self.coast_box, self.coast_label = np.zeros((B, M, 4), np.float32), np.zeros((B, M), np.int32)
             self.events.update(coasted=0, motion_only=0)
+        if self.rescue is not None:
+            self.rescued = np.zeros(B, np.int64)
+            self.events.update(rescued=0)
 
     @staticmethod
     def iou(a, b):
@@ -358,7 +417,8 @@ class TrackDefinition:
             return f(inter / union)
 
     def step(self, det, n_keep, t_ref):
-        """One step of every lane.  With ``motion``: predict, match against the predictions, filter, spawn at rest, coast."""
+        """One step of every lane.  With ``motion``: predict, match against the predictions, filter, spawn at rest, coast.
+        With ``rescue``: the low rows go through the match behind the high rows and in front of the spawn."""
         f = np.float32
         det = np.asarray(det, np.float32)
         B, A = det.shape[:2]
@@ -366,8 +426,10 @@ class TrackDefinition:
             raise ValueError(f"TrackDefinition: det is fp32 [{self.B}, A, 6], got {det.shape}")
         n_keep = np.broadcast_to(np.asarray(n_keep, np.int64).reshape(-1), (B,))
         t_ref = np.broadcast_to(np.asarray(t_ref, np.int64).reshape(-1), (B,))
-        o, motion = self.options, self.motion is not None
+        o, motion, rescue = self.options, self.motion is not None, self.rescue is not None
         thr, min_score = f(o["iou"]), f(o["min_score"])
+        if rescue:
+            low_score, low_thr = f(self.rescue["low_score"]), f(self.rescue["iou"])
         ids, hits = np.zeros((B, A), np.int64), np.zeros((B, A), np.int32)
         if motion:
             alpha, beta = f(self.motion["alpha"]), f(self.motion["beta"])
@@ -400,7 +462,11 @@ class TrackDefinition:
             eligible = [i for i in range(n) if det[b, i, 4] >= min_score]         # (a NaN score compares false)
             lost = max(0, len(eligible) - DAGR_TRACK_MAX_DETS)
             unmatched, taken = [], set()
-            for i in eligible[:DAGR_TRACK_MAX_DETS]:               # match
+            rows = [(i, thr, False) for i in eligible[:DAGR_TRACK_MAX_DETS]]
+            if rescue:                                             # round two: the low rows, behind every high row
+                low = [i for i in range(n) if det[b, i, 4] >= low_score and not det[b, i, 4] >= min_score]
+                rows += [(i, low_thr, True) for i in low[:DAGR_TRACK_MAX_DETS]]
+            for i, bar, second in rows:                            # match: the rule of both rounds
                 with np.errstate(all="ignore"):
                     label = int(det[b, i, 5].astype(np.int32))
                 best, best_s = None, None
@@ -408,15 +474,16 @@ class TrackDefinition:
                     if s in taken or int(self.label[b, s]) != label:
                         continue
                     v = self.iou(det[b, i, :4], against[s])
-                    if not v >= thr:                               # (a NaN IoU never matches)
+                    if not v >= bar:                               # (a NaN IoU never matches)
                         continue
                     if best is None or v > best or (v == best and self.id[b, s] < self.id[b, best_s]):
                         best, best_s = v, s
                 if best_s is None:
-                    unmatched.append((i, label))
+                    if not second:                                 # (a low row never spawns and is not counted)
+                        unmatched.append((i, label))
                     continue
                 s, z = best_s, det[b, i, :4]
-                if motion and not any(self.iou(z, self.box[b, c]) >= thr for c in live
+                if motion and not any(self.iou(z, self.box[b, c]) >= bar for c in live
                                       if c not in taken and int(self.label[b, c]) == label):
                     self.events["motion_only"] += 1                # (the plain rule would have spawned this row)
                 taken.add(s)
@@ -436,6 +503,9 @@ class TrackDefinition:
                 if motion:
                     self.track_box[b, i], self.track_vel[b, i] = self.box[b, s], self.vel[b, s]
                 self.events["matched"] += 1
+                if second:
+                    self.rescued[b] += 1
+                    self.events["rescued"] += 1
             free = [int(s) for s in np.flatnonzero(self.id[b] == 0)]
             for (i, label), s in zip(unmatched, free):             # spawn (with motion: at rest)
                 self.id[b, s], self.t_last[b, s], self.box[b, s] = self.next_id[b], now, det[b, i, :4]
@@ -684,6 +754,12 @@ class EventStream:
     boxes and velocities per detection row, ``step()`` adds ``"track_boxes"`` / ``"track_vel"``, ``coasting()`` reads back
     the tracks the step did not see with their predicted boxes (``coast_device()``: the device tensors), and ``tracks()``
     appends the velocities.  A stream built without it issues exactly the calls it issues without the motion model.
+    ``rescue`` (``None``: off, ``True``: the defaults, or a dict of ``low_score``, ``iou``; needs ``track`` with a
+    ``min_score`` above ``low_score``): a second association round in the same launch lets the rows under ``min_score``
+    continue tracks that no confident row matched, and never start one (module docstring); the step's one tracker launch
+    is then ``dagr_stream_track_rescue`` or ``dagr_stream_track_cv_rescue``.  ``rescued()`` counts its matches.  The
+    defaults are ByteTrack's conventions, not measured optima.  A stream built without it issues exactly the calls it
+    issues without the round.
     ``frame_size`` (``(W_f, H_f)``) and ``frame_bgr``: the steps may carry raw sensor frames (``frame=``), which
     ``dagr_stream_frame`` turns into the model's image on the device (``frame_definition``) with the stream's
     ``downsample`` factors, or 1 without ``downsample``.
@@ -698,11 +774,12 @@ class EventStream:
     """
 
     def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
-                 max_lane_events=None, denoise_us=None, refractory_us=None, track=None, motion=None):
+                 max_lane_events=None, denoise_us=None, refractory_us=None, track=None, motion=None, rescue=None):
         import torch
         self.model = model
         self.track = _track_options(track, "EventStream")
         self.motion = _motion_options(motion, self.track, "EventStream")
+        self.rescue = _rescue_options(rescue, self.track, "EventStream")
         time_window = int(getattr(model.args, "time_window_us", 1000000))
         self.window_us, self.max_lane_events = _window_and_cap(window_us, max_lane_events, time_window,
                                                                getattr(model.args, "batch_size", 1), "EventStream")
@@ -738,7 +815,7 @@ class EventStream:
         if self.denoise_us is not None or self.refractory_us is not None:
             self.state.enable_denoise(w_in, h_in, self.denoise_us, self.refractory_us)
         if self.track is not None:
-            self.state.enable_track(self.track, motion=self.motion)
+            self.state.enable_track(self.track, motion=self.motion, rescue=self.rescue)
         self._zeros = None
         self.outputs = None      # the last step's decoded head outputs [B, A, 5 + classes], valid until the engine's next call
         self._frame = None
@@ -936,9 +1013,14 @@ class EventStream:
         ``DAGR_TRACK_MAX_DETS`` of a step, or unmatched with every slot taken: int64 [B] (synchronises)."""
         return self.state.untracked()
 
+    def rescued(self):
+        """Matches of the second association round per lane since construction / ``reset()``: rows under ``min_score``
+        that continued a track: int64 [B] (synchronises).  Raises without ``rescue=``."""
+        return self.state.rescued()
+
     def reset(self):
         """Empty the stream: no resident events, no reference instants, zero change maps, empty stamp maps, zero dropped and
-        filtered counts, a clear status word, zero step counters; no tracks, ids from 1 again, a zero untracked count.  The
+        filtered counts, a clear status word, zero step counters; no tracks, ids from 1 again, zero untracked and rescued counts.  The
         frame in force stays, and the next step runs it through the image branch again."""
         self.state.reset()
 

@@ -445,6 +445,51 @@ int dagr_stream_track_cv(void *tracks, size_t bytes, int32_t B, int32_t max_trac
                          int64_t *coast_id, float *coast_box, int32_t *coast_label, int64_t *coast_age_us, int32_t *n_coast,
                          int64_t *untracked /* [B], accumulated; may be NULL */, void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * Event stream tracker, second association round: rows under min_score may continue a track
+ *   dagr_stream_track_rescue is dagr_stream_track, and dagr_stream_track_cv_rescue is dagr_stream_track_cv, with a second
+ *   round of matching for the rows whose score has dipped under min_score (two-round association, as ByteTrack has it).
+ *   Confident rows are matched first and only they start tracks; the low rows may then continue the tracks that are still
+ *   unmatched.  One launch (one wave per lane) in place of the base entry's, no host synchronisation.
+ *   dagr_amd/streaming.py: TrackDefinition(rescue=) is the same in numpy, bit for bit.
+ *
+ * Each entry works on the SAME state as its base entry: dagr_stream_track[_cv]_bytes and _reset serve it, the layout is
+ * unchanged.  The order of a step: never, retire, (predict), round one, round two, spawn, (coast).  never / retire /
+ * eligible / match / spawn, and with _cv predict / filter / coast, are the base entry's over the rows with
+ * score >= min_score (the HIGH rows); added:
+ *   low rows: score >= low_score && !(score >= min_score); a NaN score is in neither band, score == low_score is low,
+ *             score == min_score is high.  The first DAGR_TRACK_MAX_DETS low rows in row order take part.  Every other low
+ *             row, and every low row that does not match, gets what a row that is not eligible gets: id 0 and hits 0, with
+ *             _cv track_box = its own box and track_vel = 0; it is NOT counted in untracked[b];
+ *   round two: after every high row has been matched and before any spawn, the participating low rows in row order,
+ *             greedily, by the rule of `match`: among the live tracks with the row's label that no row of this step, of
+ *             either round, has matched, the one with the largest IoU (against box; with _cv against pred), the LOWEST id on
+ *             a tie; a match if that IoU is >= low_iou; a NaN IoU never matches.  A match does exactly what a match of
+ *             round one does (box, t_last, hits += 1, the row's outputs; with _cv the same velocity and alpha filter, and
+ *             the track does not coast), and adds 1 to rescued[b];
+ *   spawn:    takes the unmatched HIGH rows only: a low row never matches a track spawned in its own step and never
+ *             occupies a slot.  Where a row stands in det does not decide its round.
+ * Unlike ByteTrack, round two considers every live unmatched track, not only those seen in the step before.
+ *
+ * low_score: the lower edge of the band, below min_score.  low_iou: round two's own threshold in (0, 1] (pass iou for the
+ * tracker's).  rescued int64[B] (8-byte aligned; may be NULL): accumulated by plain stores of one thread per lane; the
+ * caller zeroes it.  Everything else as the base entry takes it.
+ * DAGR_ERR_INVALID_ARG before any launch: whatever the base entry refuses, a NaN low_score, low_score >= min_score (the
+ * band would be empty), low_iou outside (0, 1] (NaN included), a misaligned rescued.
+ * ------------------------------------------------------------------------ */
+int dagr_stream_track_rescue(void *tracks, size_t bytes, int32_t B, int32_t max_tracks, float iou, int64_t max_age_us,
+                             float min_score, const float *det, const int32_t *n_keep, int32_t A, const int64_t *t_ref,
+                             int64_t *track_id, int32_t *track_hits, int64_t *untracked /* [B], accumulated; may be NULL */,
+                             float low_score, float low_iou, int64_t *rescued /* [B], accumulated; may be NULL */,
+                             void *stream);
+int dagr_stream_track_cv_rescue(void *tracks, size_t bytes, int32_t B, int32_t max_tracks, float iou, int64_t max_age_us,
+                                float min_score, float alpha, float beta, const float *det, const int32_t *n_keep, int32_t A,
+                                const int64_t *t_ref, int64_t *track_id, int32_t *track_hits, float *track_box,
+                                float *track_vel, int64_t *coast_id, float *coast_box, int32_t *coast_label,
+                                int64_t *coast_age_us, int32_t *n_coast,
+                                int64_t *untracked /* [B], accumulated; may be NULL */, float low_score, float low_iou,
+                                int64_t *rescued /* [B], accumulated; may be NULL */, void *stream);
+
 /* The neighbour search alone, again, on the pixel index the last dagr_graph_build_window left in `workspace` (same N):
  * rewrites nbr_src / nbr_code / deg and the edge count.  For measurement (bench.py times the search kernels on their own
  * stream with HIP events); a product caller has no use for it. */

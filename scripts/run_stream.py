@@ -39,7 +39,14 @@ default 0.25) -- conventions, not measured optima.  Tracks then survive steps in
 ``tracks_<sequence>.npy`` also carries, per row, the track's filtered box (``tx1, ty1, tx2, ty2``) and its velocity in pixels
 per microsecond (``vx1, vy1, vx2, vy2``); a third file ``coasting_<sequence>.npy`` holds, per step, the tracks the step did
 not see with the boxes they are predicted to have (``step, lane, t, id, x1, y1, x2, y2, label, age_us``).  The number of
-coasted track-steps is printed with the summary."""
+coasted track-steps is printed with the summary.
+
+``--track_low_score L`` (needs ``--track`` with a ``--track_min_score`` above ``L``): a second association round
+(``dagr.streaming``: ``EventStream(rescue=)``): the detections with a confidence in ``[L, --track_min_score)`` may continue a
+track that no confident detection matched, and never start one, so a score that dips for a few steps does not cost the track
+its id.  ``--track_low_iou I`` (needs ``--track_low_score``) gives that round an IoU threshold of its own (default:
+``--track_iou``).  0.1 for ``L`` and 0.5 for ``--track_min_score`` are ByteTrack's conventions, not measured optima.  The
+number of rescued matches is printed with the summary."""
 import time
 import types
 
@@ -47,7 +54,7 @@ import numpy as np
 import torch
 
 import _common as C
-from dagr.streaming import EventStream, _motion_options, _track_options
+from dagr.streaming import EventStream, _motion_options, _rescue_options, _track_options
 from dagr.utils.buffers import DETECTION_DTYPE, detections_to_records
 from dagr.utils.logging import set_up_logging_directory
 from dagr.utils import synthetic as syn
@@ -81,6 +88,10 @@ def stream_options(p):
                    "survive a gap and coast")
     g.add_argument("--track_alpha", type=float, default=None, help="with --track_motion: position gain in (0, 1] (default 1.0)")
     g.add_argument("--track_beta", type=float, default=None, help="with --track_motion: velocity gain in [0, 1] (default 0.25)")
+    g.add_argument("--track_low_score", type=float, default=None, help="with --track: a second association round lets "
+                   "detections with a confidence in [L, --track_min_score) continue a track (never start one)")
+    g.add_argument("--track_low_iou", type=float, default=None, help="with --track_low_score: that round's own smallest IoU "
+                   "in (0, 1] (default: --track_iou)")
     g.add_argument("--raw_frames", action="store_true", help="the source's frames are sensor-size BGR uint8 frames: prepare "
                    "them on the device (crop, shrink by the --downsample factor, / 255)")
 
@@ -121,6 +132,25 @@ def motion_options(a):
         raise SystemExit("run_stream.py: --track_motion needs --track")
     try:
         _motion_options(given, _track_options(track_options(a), "run_stream.py"), "run_stream.py")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    return given
+
+
+RESCUE_FLAGS = (("track_low_score", "low_score"), ("track_low_iou", "iou"))
+
+
+def rescue_options(a):
+    """``rescue=`` of the stream the flags describe: None without ``--track_low_score``, else the options that were given."""
+    given = {key: getattr(a, flag) for flag, key in RESCUE_FLAGS if getattr(a, flag, None) is not None}
+    if "low_score" not in given:
+        if given:
+            raise SystemExit("run_stream.py: --track_low_iou needs --track_low_score")
+        return None
+    if not getattr(a, "track", False):
+        raise SystemExit("run_stream.py: --track_low_score needs --track")
+    try:
+        _rescue_options(given, _track_options(track_options(a), "run_stream.py"), "run_stream.py")
     except ValueError as e:
         raise SystemExit(str(e)) from None
     return given
@@ -221,7 +251,7 @@ def play(a, model, source, dev):
     stream = EventStream(model, window_us=a.window_us or None, downsample=a.downsample, sensor_size=sensor_size(a),
                          frame_size=raw_size, frame_bgr=True, max_lane_events=cap,
                          denoise_us=getattr(a, "denoise_us", None), refractory_us=getattr(a, "refractory_us", None),
-                         track=track_options(a), motion=motion_options(a))
+                         track=track_options(a), motion=motion_options(a), rescue=rescue_options(a))
     t0, t1 = source.t_range()
     out, last_frame = [], None
     a.stream_coasting = [] if stream.motion is not None else None      # per step the tracks it did not see
@@ -247,6 +277,7 @@ def play(a, model, source, dev):
     a.stream_dropped = int(stream.dropped().sum()) if cap is not None else None
     a.stream_filtered = int(stream.filtered().sum()) if stream.state.noise is not None else None
     a.stream_untracked = int(stream.untracked().sum()) if stream.track is not None else None
+    a.stream_rescued = int(stream.rescued().sum()) if stream.rescue is not None else None
     return out
 
 
@@ -263,6 +294,7 @@ def main(argv=None, model_factory=None, source=None):
                          "window, with --max_lane_events only)")
     tracking = track_options(a) is not None
     moving = motion_options(a) is not None
+    rescue_options(a)                      # (refusals in front of the model)
     a.batch_size = 1                       # one sequence: one lane
     world, rank, dev = C.distributed()
     torch.manual_seed(42)
@@ -310,6 +342,8 @@ def main(argv=None, model_factory=None, source=None):
             coast = np.concatenate(a.stream_coasting) if a.stream_coasting else np.zeros(0, COAST_RECORD_DTYPE)
             np.save(out_dir / f"coasting_{a.sequence}.npy", coast)
             tracked += f"; {len(coast)} coasted track-steps -> {out_dir / f'coasting_{a.sequence}.npy'}"
+        if a.stream_rescued is not None:
+            tracked += f"; {a.stream_rescued} low-score detections rescued by the second round"
         print(f"{len(steps)} steps of {a.step_us} us on {window} in {seconds:.2f} s "
               f"({1e3 * seconds / max(1, len(steps)):.2f} ms per step; {a.stream_steps[0]} with the full window, "
               f"{a.stream_steps[1]} on held image maps) -> {path}: {len(rec)} detections{tracked}")
