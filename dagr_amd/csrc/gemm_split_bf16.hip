@@ -24,6 +24,14 @@
 // MFMA; a 128-row tile lost to the 64-row one on every shape of the image branch); 4 waves as 2 x 2, each (16*MI) x (BN/2)
 // of the output; mfma_f32_16x16x32_bf16 with the operands swapped (W as the MFMA's A operand), so a lane ends up with four
 // consecutive output CHANNELS of one row and the epilogue reads bias / residual and writes D as float4.
+// The 64 x 128 tile also runs on 8 waves as 2 x 4, each 32 x 32 of the output (WN = 4): a thread then splits one float4 of A
+// per slice instead of two and a wave brings in three W pieces instead of six, for the same 24 MFMAs a wave issues on the
+// 64 x 64 tile.  That is the split per MFMA of the 128-column tile (a block splits its A rows once per 128 columns, not
+// once per 64) inside the register budget of the 64-column one: 128 VGPRs, so two blocks, sixteen waves, per CU.  It is
+// what tile 0 picks for the 1x1 shapes with K <= 512 that fill the chip with such blocks (launch() below).
+// A three-stage loop (W image sent for two slices ahead, counted vmcnt, the A loads hidden from the compiler's wait counting)
+// was built and measured beside it (profiles/split_bf16_loop.md): a wave waited less, but three stages cost a block per CU
+// (73 728 B at 64 x 64) and every shape of the trunk ran 3 - 21 % slower; it is not kept.
 //
 // K loop: two LDS stages and one workgroup barrier per slice.  While slice kt is multiplied out of one stage, the W image of
 // slice kt + 1 arrives in the other by the LDS-direct load, the A rows of slice kt + 1 (in registers since slice kt - 1) are
@@ -127,12 +135,21 @@ __device__ __forceinline__ void wait_all_barrier(f32x4 (&ra)[2][N]) {
     asm volatile("" ::: "memory");
 }
 
-template <int MI, int BN, int MODE>
-__global__ __launch_bounds__(256, BN == 128 ? 2 : 3) void k_gemm_split(const Args a) {
+// Waves per SIMD that the registers are budgeted for (the second argument of __launch_bounds__).  Four waves: 2 with 128
+// columns, 3 with 64.  Eight waves on 64 x 128: two blocks of 73 728 B of LDS fit in a CU, sixteen waves, 4 per SIMD, so
+// 128 registers.
+constexpr int waves_per_simd(int BN, int WN) { return WN == 4 ? 4 : BN == 128 ? 2 : 3; }
+
+// WN: waves along N (2 x WN waves per block, 128 WN threads).
+template <int MI, int BN, int MODE, int WN = 2>
+__global__ __launch_bounds__(128 * WN, waves_per_simd(BN, WN)) void k_gemm_split(const Args a) {
     constexpr int BM = 32 * MI;
-    constexpr int NI = BN / 32;                      // 16-column fragments of a wave
+    constexpr int NT = 128 * WN;                     // threads
+    constexpr int NI = BN / (16 * WN);               // 16-column fragments of a wave
+    constexpr int AI = BM * 8 / NT;                  // float4 of the A tile that a thread stages per slice
     constexpr int kStage = 3 * (BM + BN) * kKT;      // one stage: three A planes, then three W planes (bf16)
-    constexpr int kPieces = 3 * BN / 16 / 4;         // 1 KB pieces of a stage's W image that each wave brings in
+    constexpr int kPieces = 3 * BN / 16 / (2 * WN);  // 1 KB pieces of a stage's W image that each wave brings in
+    static_assert(AI >= 1 && AI * NT == BM * 8 && kPieces * 2 * WN * 16 == 3 * BN && NI >= 1, "tile does not divide among the waves");
     __shared__ __attribute__((aligned(1024))) unsigned short lds[2 * kStage];
 
     // blocks that follow each other on one XCD share the A row tile (its L2 holds it); bijective for any block count
@@ -143,19 +160,20 @@ __global__ __launch_bounds__(256, BN == 128 ? 2 : 3) void k_gemm_split(const Arg
     const int n0 = nt * BN;
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
+    const int wm = wave / WN, wn = wave % WN;
 
-    // ---- staging geometry of this thread: rows r0 + 32 i, 4 consecutive k at 4 c4
+    // ---- staging geometry of this thread: rows r0 + kRS i, 4 consecutive k at 4 c4
+    constexpr int kRS = NT / 8;           // rows that the block's threads cover at once
     const int r0 = t >> 3, c4 = t & 7;
-    // MODE 1 keeps an offset per row; the other two derive it from the first row's (rows 32 apart, a uniform step)
-    int64_t rowoff[MODE == 1 ? MI : 1];
-    int ryx[MODE == 2 ? MI : 1];          // MODE 2: y << 16 | x of the row's pixel
+    // MODE 1 keeps an offset per row; the other two derive it from the first row's (rows kRS apart, a uniform step)
+    int64_t rowoff[MODE == 1 ? AI : 1];
+    int ryx[MODE == 2 ? AI : 1];          // MODE 2: y << 16 | x of the row's pixel
     const int64_t mrow0 = m0 + r0;
     rowoff[0] = (mrow0 < a.M ? mrow0 : 0) * a.lda;
     ryx[0] = 0;
 #pragma unroll
-    for (int i = 0; i < MI; i++) {
-        const int64_t m = mrow0 + 32 * i;
+    for (int i = 0; i < AI; i++) {
+        const int64_t m = mrow0 + kRS * i;
         const int64_t mm = m < a.M ? m : 0;
         if (MODE == 1) {
             const int64_t b = mm / ((int64_t)a.g.Ho * a.g.Wo);
@@ -167,8 +185,8 @@ __global__ __launch_bounds__(256, BN == 128 ? 2 : 3) void k_gemm_split(const Arg
         }
     }
 
-    static_assert(MI == 1 || MI == 2, "wait_all_barrier names the register sets");
-    f32x4 ra[2][MI];                   // two register sets: slice kt + 1 is split out of one while kt + 2 arrives in the other
+    static_assert(AI == 1 || AI == 2, "wait_all_barrier names the register sets");
+    f32x4 ra[2][AI];                   // two register sets: slice kt + 1 is split out of one while kt + 2 arrives in the other
     unsigned okmask[2] = {0, 0};
 
     // the A rows of K-slice kt, fp32, into register set `set`
@@ -186,13 +204,13 @@ __global__ __launch_bounds__(256, BN == 128 ? 2 : 3) void k_gemm_split(const Arg
         }
         okmask[S] = 0;
 #pragma unroll
-        for (int i = 0; i < MI; i++) {
-            bool ok = mrow0 + 32 * i < a.M;
+        for (int i = 0; i < AI; i++) {
+            bool ok = mrow0 + kRS * i < a.M;
             if (MODE == 2) {
                 const int yx = ryx[MODE == 2 ? i : 0];
                 ok = ok && (unsigned)((yx >> 16) + dy) < (unsigned)a.g.H && (unsigned)((yx & 0xffff) + dx) < (unsigned)a.g.W;
             }
-            const int64_t off = MODE == 1 ? rowoff[MODE == 1 ? i : 0] : rowoff[0] + (int64_t)(32 * i) * a.lda;
+            const int64_t off = MODE == 1 ? rowoff[MODE == 1 ? i : 0] : rowoff[0] + (int64_t)(kRS * i) * a.lda;
             // a masked row reads the first 16 bytes of A (always there) and is zeroed when it is written to LDS: a select
             // on the address, not a branch around the load
             const float *p = ok ? a.A + off + toff + c0 + c4 * 4 : a.A;
@@ -206,7 +224,7 @@ __global__ __launch_bounds__(256, BN == 128 ? 2 : 3) void k_gemm_split(const Arg
         constexpr int S = decltype(set)::value;
         unsigned short *const ldsA = lds + s * kStage;
 #pragma unroll
-        for (int i = 0; i < MI; i++) {
+        for (int i = 0; i < AI; i++) {
             const bool ok = (okmask[S] >> i) & 1u;
             const f32x4 v = ok ? ra[S][i] : f32x4{0.f, 0.f, 0.f, 0.f};
             unsigned lo[3], hi[3];
@@ -215,7 +233,7 @@ __global__ __launch_bounds__(256, BN == 128 ? 2 : 3) void k_gemm_split(const Arg
 #pragma unroll
             for (int q = 0; q < 3; q++) {
                 const u32x2 u = {lo[q], hi[q]};
-                *reinterpret_cast<u32x2 *>(ldsA + q * BM * kKT + swz(r0 + 32 * i, c4 >> 1) + (c4 & 1) * 4) = u;
+                *reinterpret_cast<u32x2 *>(ldsA + q * BM * kKT + swz(r0 + kRS * i, c4 >> 1) + (c4 & 1) * 4) = u;
             }
         }
     };
@@ -245,7 +263,7 @@ __global__ __launch_bounds__(256, BN == 128 ? 2 : 3) void k_gemm_split(const Arg
 
     const int frag = swz(lane & 15, lane >> 4);
     const int fragA = (wm * 16 * MI) * kKT + frag;
-    const int fragW = (3 * BM + wn * (BN / 2)) * kKT + frag;
+    const int fragW = (3 * BM + wn * (BN / WN)) * kKT + frag;
 
     // Two LDS stages, one barrier per slice.  Slice kt is multiplied out of stage kt & 1.  At the top of that slice the
     // A rows of slice kt + 2 are sent for (into the register set slice kt was split from) and so is the W image of slice
@@ -331,7 +349,7 @@ __global__ __launch_bounds__(256, BN == 128 ? 2 : 3) void k_gemm_split(const Arg
         if (m >= a.M) continue;
 #pragma unroll
         for (int ni = 0; ni < NI; ni++) {
-            const int n = n0 + wn * (BN / 2) + ni * 16 + (lane >> 4) * 4;
+            const int n = n0 + wn * (BN / WN) + ni * 16 + (lane >> 4) * 4;
             if (n >= a.N) continue;              // N is a multiple of 16 and n of 4: a whole float4 or nothing
             f32x4 v = acc[mi][ni];
             if (a.bias) {
@@ -350,31 +368,45 @@ __global__ __launch_bounds__(256, BN == 128 ? 2 : 3) void k_gemm_split(const Arg
 
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
-template <int MI, int BN, int MODE>
+template <int MI, int BN, int MODE, int WN = 2>
 int launch_tile(Args &a, hipStream_t stream) {
     a.n_tiles_n = (int)ceil_div(a.N, BN);
     const int64_t blocks = ceil_div(a.M, 32 * MI) * a.n_tiles_n;
     DAGR_CHECK_ARG(blocks < ((int64_t)1 << 31), "too many tiles");
     a.n_blocks = (int)blocks;
-    k_gemm_split<MI, BN, MODE><<<(unsigned)blocks, 256, 0, stream>>>(a);
+    k_gemm_split<MI, BN, MODE, WN><<<(unsigned)blocks, 128 * WN, 0, stream>>>(a);
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
 }
 
 template <int MODE>
-int launch(Args &a, int tile, hipStream_t stream) {
-    // tile 1: 64 x 128, 2: 32 x 128, 3: 64 x 64, 4: 32 x 64 (rows x columns).  0 picks from the shape, by what
-    // profiles/split_bf16_shapes.md measured.  Columns: always 64 -- three blocks per CU instead of two and no zero padding
+int launch(Args &a, int variant, hipStream_t stream) {
+    // Variants 1 - 4 are the tile codes of the first two entry points, on four waves: 1: 64 x 128, 2: 32 x 128, 3: 64 x 64,
+    // 4: 32 x 64 (rows x columns); 5: 64 x 128 on eight waves.  0 picks from the shape, by what
+    // profiles/split_bf16_shapes.md and profiles/split_bf16_loop.md measured.
+    // Four waves, columns: always 64 -- three blocks per CU instead of two and no zero padding
     // at N = 64; it won or tied (within the spread) on every shape the rule selects, and the step as a whole was faster with
     // it than with 128 columns on the three shapes where those were 0.5 - 0.9 us ahead.  Rows: 64 where that still leaves
-    // two blocks per CU, 32 below.
-    if (tile == 0) tile = ceil_div(a.M, 64) * ceil_div(a.N, 64) >= 2 * (int64_t)device_cu_count() ? 3 : 4;
-    switch (tile) {
-        case 1: return launch_tile<2, 128, MODE>(a, stream);
-        case 2: return launch_tile<1, 128, MODE>(a, stream);
-        case 3: return launch_tile<2, 64, MODE>(a, stream);
-        default: return launch_tile<1, 64, MODE>(a, stream);
+    // two blocks per CU, 32 below.  The 64 x 128 tile on eight waves beat the 64 x 64 tile by more than both spreads on
+    // every 1x1 shape measured with K <= 512, whole 128-column tiles and at least four of its blocks per CU (1 200 -
+    // 4 800 blocks; 7 - 13 % faster, plain and strided), and lost or tied on every shape with fewer blocks (608 and
+    // below), with K >= 1024, with N = 64, and on the 3x3 convolutions.
+    if (variant == 0) {
+        const int64_t cus = device_cu_count();
+        if (MODE != 2 && a.K <= 512 && a.N % 128 == 0 && ceil_div(a.M, 64) * (a.N / 128) >= 4 * cus)
+            variant = DAGR_SPLIT_64X128_W8;
+        else
+            variant = ceil_div(a.M, 64) * ceil_div(a.N, 64) >= 2 * cus ? DAGR_SPLIT_64X64 : DAGR_SPLIT_32X64;
     }
+    switch (variant) {
+        case DAGR_SPLIT_64X128: return launch_tile<2, 128, MODE>(a, stream);
+        case DAGR_SPLIT_32X128: return launch_tile<1, 128, MODE>(a, stream);
+        case DAGR_SPLIT_64X64: return launch_tile<2, 64, MODE>(a, stream);
+        case DAGR_SPLIT_32X64: return launch_tile<1, 64, MODE>(a, stream);
+        case DAGR_SPLIT_64X128_W8: return launch_tile<2, 128, MODE, 4>(a, stream);
+    }
+    set_error("split-bf16 GEMM: unknown variant");   // (the entry points check the range first)
+    return DAGR_ERR_INVALID_ARG;
 }
 
 inline int unsupported(const char *fn, const char *what) {
@@ -408,9 +440,6 @@ extern "C" int dagr_gemm_split_bf16_pack(const float *Wt, int32_t K, int32_t N, 
 }
 
 namespace {
-int check_common(const char *fn, const float *A, int64_t M, int32_t K, int64_t lda, const void *packed, int32_t N,
-                 const float *bias, const float *R, int64_t ldr, int32_t act, float *D, int64_t ldd, int32_t tile, bool &done) {
-    done = true;
 #define SPLIT_CHECK(cond, msg)                                     \
     do {                                                           \
         if (!(cond)) {                                             \
@@ -418,7 +447,14 @@ int check_common(const char *fn, const float *A, int64_t M, int32_t K, int64_t l
             return DAGR_ERR_INVALID_ARG;                           \
         }                                                          \
     } while (0)
-    SPLIT_CHECK(M >= 0 && K >= 1 && N >= 1 && ldd >= N && (!R || ldr >= N) && (act == 0 || act == 1) && tile >= 0 && tile <= 4,
+
+// `code`: the tile of the first two entry points (max_code 4) or the variant of the other two (DAGR_SPLIT_VARIANT_LAST)
+int check_common(const char *fn, const float *A, int64_t M, int32_t K, int64_t lda, const void *packed, int32_t N,
+                 const float *bias, const float *R, int64_t ldr, int32_t act, float *D, int64_t ldd, int32_t code,
+                 int32_t max_code, bool &done) {
+    done = true;
+    SPLIT_CHECK(M >= 0 && K >= 1 && N >= 1 && ldd >= N && (!R || ldr >= N) && (act == 0 || act == 1) && code >= 0 &&
+                    code <= max_code,
                 "bad sizes");
     if (K % kKT != 0) return unsupported(fn, "K (C of a 3x3) is not a multiple of the K-tile (32)");
     if (N % 16 != 0) return unsupported(fn, "N is not a multiple of 16");
@@ -429,39 +465,67 @@ int check_common(const char *fn, const float *A, int64_t M, int32_t K, int64_t l
     SPLIT_CHECK(lda % 4 == 0 && ldd % 4 == 0 && (!R || ldr % 4 == 0), "row strides must be multiples of 4 floats");
     SPLIT_CHECK(aligned16(A) && aligned16(packed) && aligned16(D) && aligned16(bias) && aligned16(R),
                 "pointers must be 16-byte aligned");
-#undef SPLIT_CHECK
     done = false;
     return DAGR_OK;
 }
+
+int gemm_entry(const char *fn, const float *A, int64_t M, int32_t K, int64_t lda, const void *packed, int32_t N,
+               const float *bias, const float *R, int64_t ldr, int32_t act, float *D, int64_t ldd, int32_t B, int32_t H,
+               int32_t W, int32_t stride, int32_t code, int32_t max_code, void *stream) {
+    bool done;
+    const int rc = check_common(fn, A, M, K, lda, packed, N, bias, R, ldr, act, D, ldd, code, max_code, done);
+    if (done) return rc;
+    SPLIT_CHECK(lda >= K && stride >= 1, "bad sizes");
+    Args a{A, (const unsigned short *)packed, bias, R, D, M, lda, R ? ldr : 0, ldd, K, N, (int)align_up((size_t)N, kNPad), act,
+           0, 0, Geo{0, 0, 0, K, 1, 0, 0}};
+    if (stride == 1) return launch<0>(a, code, (hipStream_t)stream);
+    SPLIT_CHECK(B >= 1 && H >= 1 && W >= 1, "bad image sizes");
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    SPLIT_CHECK(M == (int64_t)B * Ho * Wo, "M is not B * ceil(H / stride) * ceil(W / stride)");
+    a.g = Geo{1, H, W, K, stride, Ho, Wo};
+    return launch<1>(a, code, (hipStream_t)stream);
+}
+
+int conv3x3_entry(const char *fn, const float *X, int32_t B, int32_t H, int32_t W, int32_t C, int64_t ldx, const void *packed,
+                  int32_t N, const float *bias, const float *R, int64_t ldr, int32_t act, float *D, int64_t ldd, int32_t code,
+                  int32_t max_code, void *stream) {
+    SPLIT_CHECK(B >= 0 && H >= 1 && W >= 1 && C >= 1 && ldx >= C, "bad sizes");
+    const int64_t M = (int64_t)B * H * W;
+    bool done;
+    const int rc = check_common(fn, X, M, C, ldx, packed, N, bias, R, ldr, act, D, ldd, code, max_code, done);
+    if (done) return rc;
+    SPLIT_CHECK((int64_t)C * 9 < ((int64_t)1 << 31), "C too large");
+    Args a{X, (const unsigned short *)packed, bias, R, D, M, ldx, R ? ldr : 0, ldd, 9 * C, N, (int)align_up((size_t)N, kNPad), act,
+           0, 0, Geo{2, H, W, C, 1, H, W}};
+    return launch<2>(a, code, (hipStream_t)stream);
+}
+#undef SPLIT_CHECK
 }  // namespace
 
 extern "C" int dagr_gemm_split_bf16(const float *A, int64_t M, int32_t K, int64_t lda, const void *packed, int32_t N,
                                     const float *bias, const float *R, int64_t ldr, int32_t act, float *D, int64_t ldd,
                                     int32_t B, int32_t H, int32_t W, int32_t stride, int32_t tile, void *stream) {
-    bool done;
-    const int rc = check_common(__func__, A, M, K, lda, packed, N, bias, R, ldr, act, D, ldd, tile, done);
-    if (done) return rc;
-    DAGR_CHECK_ARG(lda >= K && stride >= 1, "bad sizes");
-    Args a{A, (const unsigned short *)packed, bias, R, D, M, lda, R ? ldr : 0, ldd, K, N, (int)align_up((size_t)N, kNPad), act,
-           0, 0, Geo{0, 0, 0, K, 1, 0, 0}};
-    if (stride == 1) return launch<0>(a, tile, (hipStream_t)stream);
-    DAGR_CHECK_ARG(B >= 1 && H >= 1 && W >= 1, "bad image sizes");
-    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    DAGR_CHECK_ARG(M == (int64_t)B * Ho * Wo, "M is not B * ceil(H / stride) * ceil(W / stride)");
-    a.g = Geo{1, H, W, K, stride, Ho, Wo};
-    return launch<1>(a, tile, (hipStream_t)stream);
+    return gemm_entry(__func__, A, M, K, lda, packed, N, bias, R, ldr, act, D, ldd, B, H, W, stride, tile, 4, stream);
 }
 
 extern "C" int dagr_conv3x3_split_bf16(const float *X, int32_t B, int32_t H, int32_t W, int32_t C, int64_t ldx,
                                        const void *packed, int32_t N, const float *bias, const float *R, int64_t ldr,
                                        int32_t act, float *D, int64_t ldd, int32_t tile, void *stream) {
-    DAGR_CHECK_ARG(B >= 0 && H >= 1 && W >= 1 && C >= 1 && ldx >= C, "bad sizes");
-    const int64_t M = (int64_t)B * H * W;
-    bool done;
-    const int rc = check_common(__func__, X, M, C, ldx, packed, N, bias, R, ldr, act, D, ldd, tile, done);
-    if (done) return rc;
-    DAGR_CHECK_ARG((int64_t)C * 9 < ((int64_t)1 << 31), "C too large");
-    Args a{X, (const unsigned short *)packed, bias, R, D, M, ldx, R ? ldr : 0, ldd, 9 * C, N, (int)align_up((size_t)N, kNPad), act,
-           0, 0, Geo{2, H, W, C, 1, H, W}};
-    return launch<2>(a, tile, (hipStream_t)stream);
+    return conv3x3_entry(__func__, X, B, H, W, C, ldx, packed, N, bias, R, ldr, act, D, ldd, tile, 4, stream);
+}
+
+extern "C" int dagr_gemm_split_bf16_variant(const float *A, int64_t M, int32_t K, int64_t lda, const void *packed, int32_t N,
+                                            const float *bias, const float *R, int64_t ldr, int32_t act, float *D,
+                                            int64_t ldd, int32_t B, int32_t H, int32_t W, int32_t stride, int32_t variant,
+                                            void *stream) {
+    return gemm_entry(__func__, A, M, K, lda, packed, N, bias, R, ldr, act, D, ldd, B, H, W, stride, variant,
+                      DAGR_SPLIT_VARIANT_LAST, stream);
+}
+
+extern "C" int dagr_conv3x3_split_bf16_variant(const float *X, int32_t B, int32_t H, int32_t W, int32_t C, int64_t ldx,
+                                               const void *packed, int32_t N, const float *bias, const float *R,
+                                               int64_t ldr, int32_t act, float *D, int64_t ldd, int32_t variant,
+                                               void *stream) {
+    return conv3x3_entry(__func__, X, B, H, W, C, ldx, packed, N, bias, R, ldr, act, D, ldd, variant,
+                         DAGR_SPLIT_VARIANT_LAST, stream);
 }

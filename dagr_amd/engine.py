@@ -211,10 +211,11 @@ def _split_min_rows(K, N, taps):
       1x1, K 128..256, N >= 128: won at every M measured, 560 to 153 600 (14 - 65 % faster).
       1x1, K 257..512, N >= 256: won at every M measured, 2 400 to 38 400 (12 - 15 %).  N = 128: won at 38 400 (38.8 against
         43.6 us), measured size only.
-      1x1, K = 1024, N = 512 (layer4.0.conv1): won at 9 600 (68.2 against 78.4 us), measured size only.  The other K >= 1024
-        classes: 9 600 x 1024 x 256 gained 2.3 us of 44.6 with a spread of 1.2, too near it; 2 400 x 1024 x 2048 read in
-        place with stride 2, as the engine runs it, gained 2.7 of 87.8 with a spread of 1.3, likewise; 2 400 x 2048 x 512
-        lost (52.6 against 42.9 us).
+      1x1, K = 1024, N = 512 (layer4.0.conv1): won at 9 600 (68.2 against 78.4 us), measured size only.  K = 1024, N = 2048
+        (layer4.0.downsample, read in place with stride 2): re-measured in profiles/split_bf16_loop.md, 71.3 - 71.8 against
+        88.0 - 88.9 us in two tables (spreads up to 2.6), admitted at 2 400 rows, measured size only.  The other K >= 1024
+        classes: 9 600 x 1024 x 256 gained 2.3 us of 44.6 with a spread of 1.2 and 0.5 - 1.1 of 42 when re-measured, too near
+        it; 2 400 x 2048 x 512 lost (52.6 against 42.9 us, 49.5 against 41.6).
       1x1 of layer1 (64 -> 64, 256 -> 64, 64 -> 256): won at 153 600 (12 - 27 %), measured size only.
       1x1 with K < 64 or N < 64 (the narrow dconvs): not measured, not selected.
       3x3 stride 1: C = 128 won at M = 38 400 (30 %); the bound stays at 32 768, where the image branch's own tests hold
@@ -229,7 +230,7 @@ def _split_min_rows(K, N, taps):
             return 512
         if K <= 512:
             return 2400 if N >= 256 else 38400
-        return 9600 if (K, N) == (1024, 512) else None
+        return {(1024, 512): 9600, (1024, 2048): 2400}.get((K, N))
     if taps == 9 and K == N:
         return {64: 153600, 128: 32768, 256: 9600}.get(K)
     return None

@@ -1012,8 +1012,8 @@ int dagr_gemm_epilogue(const float *A, int64_t M, int32_t K, int64_t lda, const 
  *     channels-last map A[B, H, W, K] (pixel pitch lda), read in place; M must be B * ceil(H/stride) * ceil(W/stride).
  *   dagr_conv3x3_split_bf16: D[B*H*W, N] = act(conv3x3(X) + bias (+ R)), stride 1, pad 1, X[B, H, W, C] channels-last with
  *     pixel pitch ldx; packed from Wt[9 C, N] with row (3 ky + kx) C + c.
- *   tile (rows x columns): 0 = chosen from the shape, 1 = 64 x 128, 2 = 32 x 128, 3 = 64 x 64, 4 = 32 x 64 (the same result
- *     bits whichever runs: K is never split, the 32-wide K-slices are added in ascending order).
+ *   tile (rows x columns): 0 = chosen from the shape (among the variants below), 1 = 64 x 128, 2 = 32 x 128, 3 = 64 x 64,
+ *     4 = 32 x 64 (the same result bits whichever runs: K is never split, the 32-wide K-slices are added in ascending order).
  * DAGR_ERR_UNSUPPORTED: K (C for the 3x3) not a multiple of 32, N not a multiple of 16.  DAGR_ERR_INVALID_ARG: row
  * strides not multiples of 4 floats, pointers not 16-byte aligned, D aliasing A or R, a packed buffer too small. */
 size_t dagr_gemm_split_bf16_packed_bytes(int32_t K, int32_t N);
@@ -1024,6 +1024,24 @@ int dagr_gemm_split_bf16(const float *A, int64_t M, int32_t K, int64_t lda, cons
 int dagr_conv3x3_split_bf16(const float *X, int32_t B, int32_t H, int32_t W, int32_t C, int64_t ldx, const void *packed,
                             int32_t N, const float *bias, const float *R, int64_t ldr, int32_t act, float *D, int64_t ldd,
                             int32_t tile, void *stream);
+
+/* The same two calls with every form of the kernel selectable: `variant` (tile x waves) in place of `tile`.  Variants 1 - 4
+ * are the tiles above, on four waves; W8 is the 64 x 128 tile on eight waves (2 x 4, each 32 x 32 of the output), which tile 0
+ * chooses for the 1x1 shapes with K <= 512 and enough rows to fill the chip.  0 = chosen from the shape, as tile 0.  Every
+ * variant gives the same result bits.  A variant past DAGR_SPLIT_VARIANT_LAST is DAGR_ERR_INVALID_ARG and nothing is
+ * written. */
+#define DAGR_SPLIT_64X128 1
+#define DAGR_SPLIT_32X128 2
+#define DAGR_SPLIT_64X64 3
+#define DAGR_SPLIT_32X64 4
+#define DAGR_SPLIT_64X128_W8 5
+#define DAGR_SPLIT_VARIANT_LAST 5
+int dagr_gemm_split_bf16_variant(const float *A, int64_t M, int32_t K, int64_t lda, const void *packed, int32_t N,
+                                 const float *bias, const float *R, int64_t ldr, int32_t act, float *D, int64_t ldd,
+                                 int32_t B, int32_t H, int32_t W, int32_t stride, int32_t variant, void *stream);
+int dagr_conv3x3_split_bf16_variant(const float *X, int32_t B, int32_t H, int32_t W, int32_t C, int64_t ldx,
+                                    const void *packed, int32_t N, const float *bias, const float *R, int64_t ldr,
+                                    int32_t act, float *D, int64_t ldd, int32_t variant, void *stream);
 
 /* ------------------------------------------------------------------------ *
  * FLOP accounting in the reference's scheme (src/dagr/asynchronous/flops/conv.py and the per-module logs of

@@ -5,8 +5,9 @@ before (dagr_gemm_epilogue for the 1x1 convs; the library 3x3 conv + dagr_bias_r
 HIP events around every launch, `--warm` untimed launches, the median of `--iters`; the whole measurement of a shape is
 repeated `--rounds` times and the spread of the medians (max - min) is printed beside the first: a path wins a shape only
 by more than that spread.  Prints a markdown table (TF/s: 2 M K N / time; the split columns are fp32-equivalent TF/s,
-against the 417 TF-equivalent ceiling of six bf16 MFMAs per product; the four split times are the four tiles the entry points
-take, rows x columns).
+against the 417 TF-equivalent ceiling of six bf16 MFMAs per product; the split times are every variant of
+dagr_gemm_split_bf16_variant / dagr_conv3x3_split_bf16_variant, rows x columns, "w8" on eight waves, each as first median
+(spread of its medians); "auto" is what tile 0 of the first entry points chooses).
 
     python tools/split_gemm_bench.py [--md OUT.md] [--only 1x1|3x3]
 """
@@ -40,8 +41,12 @@ CONVS = [(8, 120, 160, 64, "layer1.*.conv2"), (8, 60, 80, 128, "layer2.1-3.conv2
          (8, 15, 20, 512, "layer4.1-2.conv2"), (2, 27, 40, 128, "B=2 320x215 layer2.1-3.conv2")]
 
 
+VARIANTS = [(name[len("DAGR_SPLIT_"):].lower(), code) for name, code in sorted(_lib.DEFINES.items(), key=lambda kv: kv[1])
+            if name.startswith("DAGR_SPLIT_") and name != "DAGR_SPLIT_VARIANT_LAST"]
+
+
 def all_tiles(split_fn):
-    return [("64x128", split_fn(1)), ("32x128", split_fn(2)), ("64x64", split_fn(3)), ("32x64", split_fn(4))]
+    return [(name, split_fn(code)) for name, code in VARIANTS] + [("auto", split_fn(0))]
 
 
 def time_us(fn, warm, iters):
@@ -80,16 +85,16 @@ def main():
     torch.manual_seed(0)
     torch.backends.cudnn.benchmark = True
     ws = torch.empty(int(L.dagr_gemm_epilogue_workspace_bytes()), dtype=torch.uint8, device=dev)
-    rows = ["| shape | layer | library us | TF/s | of 157.3 | split us, tiles 64x128 / 32x128 / 64x64 / 32x64 | best us | TF-eq/s | of 417 | "
-            "spread lib / split us | max diff / max ref |", "|---|---|---|---|---|---|---|---|---|---|---|"]
+    rows = ["| shape | layer | library us | TF/s | of 157.3 | split us (spread): " + " / ".join(n for n, _ in VARIANTS) + " / auto | best us | "
+            "TF-eq/s | of 417 | spread lib / best us | max diff / max ref |", "|---|---|---|---|---|---|---|---|---|---|---|"]
 
     def measure(name, note, flop, lib_fn, split_fns, y_lib, y_split):
         lib = [time_us(lib_fn, a.warm, a.iters) for _ in range(a.rounds)]
         best, firsts = None, []
         for tile, fn in split_fns:
             t = [time_us(fn, a.warm, a.iters) for _ in range(a.rounds)]
-            firsts.append(f"{t[0]:.1f}")
-            if best is None or t[0] < best[1][0]:
+            firsts.append(f"{t[0]:.1f} ({max(t) - min(t):.1f})")
+            if tile != "auto" and (best is None or t[0] < best[1][0]):
                 best = (tile, t)
         tile, sp = best
         split_fns[[t for t, _ in split_fns].index(tile)][1]()
@@ -118,8 +123,8 @@ def main():
                                                 N, _lib.ptr(ws), ws.numel(), st()), "gemm_epilogue")
 
             def split_fn(tile):
-                return lambda: _lib.check(L.dagr_gemm_split_bf16(_lib.ptr(A), M, K, K, _lib.ptr(wp), N, _lib.ptr(bias), None, N,
-                                                                 1, _lib.ptr(y1), N, 0, 0, 0, 1, tile, st()), "gemm_split")
+                return lambda: _lib.check(L.dagr_gemm_split_bf16_variant(_lib.ptr(A), M, K, K, _lib.ptr(wp), N, _lib.ptr(bias), None,
+                                                                         N, 1, _lib.ptr(y1), N, 0, 0, 0, 1, tile, st()), "gemm_split")
             measure(f"{M} x {K} x {N}", note, 2.0 * M * K * N, lib_fn, all_tiles(split_fn), y0, y1)
             del A, wt, wp, y0, y1
         for B, H, W, K, N, note in STRIDED:
@@ -137,8 +142,8 @@ def main():
                                                 N, _lib.ptr(ws), ws.numel(), st()), "gemm_epilogue")
 
             def split_fn(tile):
-                return lambda: _lib.check(L.dagr_gemm_split_bf16(_lib.ptr(x), M, K, K, _lib.ptr(wp), N, _lib.ptr(bias), None, N,
-                                                                 0, _lib.ptr(y1), N, B, H, W, 2, tile, st()), "gemm_split")
+                return lambda: _lib.check(L.dagr_gemm_split_bf16_variant(_lib.ptr(x), M, K, K, _lib.ptr(wp), N, _lib.ptr(bias), None,
+                                                                         N, 0, _lib.ptr(y1), N, B, H, W, 2, tile, st()), "gemm_split")
             measure(f"{M} x {K} x {N} (/2 of {H}x{W})", note, 2.0 * M * K * N, lib_fn,
                     all_tiles(split_fn), y0, y1)
             del x, wt, wp, y0, y1
@@ -158,8 +163,8 @@ def main():
                 hold["y"] = y
 
             def split_fn(tile):
-                return lambda: _lib.check(L.dagr_conv3x3_split_bf16(_lib.ptr(x), B, H, W, C, C, _lib.ptr(wp), C, _lib.ptr(bias), None,
-                                                                    C, 1, _lib.ptr(y1), C, tile, st()), "conv3x3_split")
+                return lambda: _lib.check(L.dagr_conv3x3_split_bf16_variant(_lib.ptr(x), B, H, W, C, C, _lib.ptr(wp), C, _lib.ptr(bias),
+                                                                            None, C, 1, _lib.ptr(y1), C, tile, st()), "conv3x3_split")
             lib_fn()
             y0 = hold["y"].permute(0, 2, 3, 1).reshape(M, C)
             # (every lib_fn() makes a new map from the same operands; the first one is what the split result is set against)
