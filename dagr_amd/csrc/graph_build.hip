@@ -1135,6 +1135,7 @@ __global__ __launch_bounds__(kStreamLanes) void k_stream_plan(StreamState st, in
                                                               const int32_t *__restrict__ n_new_dev,
                                                               const ClockT *__restrict__ batch_clock,
                                                               const int64_t *__restrict__ t_clock, int n_clock,
+                                                              const int32_t *__restrict__ n_clock_dev,
                                                               const int64_t *__restrict__ t_now, int64_t window_us,
                                                               int max_lane, int64_t *__restrict__ lane_dropped,
                                                               int32_t *__restrict__ n_dev,
@@ -1145,6 +1146,7 @@ __global__ __launch_bounds__(kStreamLanes) void k_stream_plan(StreamState st, in
     const int src = st.hdr[0] & 1;
     int flags = 0, first_old = 0, keep_old = 0, first_new = 0, keep_new = 0;
     if (n_new_dev) n_new = min(max(*n_new_dev, 0), n_new);
+    if (n_clock_dev) n_clock = min(max(*n_clock_dev, 0), n_clock);
     if (b < B) {
         const int ns = first_lane_at_least(batch_new, n_new, b);
         const int ne = max(ns, first_lane_at_least(batch_new, n_new, b + 1));
@@ -1223,6 +1225,7 @@ __global__ __launch_bounds__(kBlock) void k_stream_gather(StreamState st, int B,
                                                          const int32_t *__restrict__ n_new_dev,
                                                          const ClockT *__restrict__ batch_clock,
                                                          const int64_t *__restrict__ t_clock, int n_clock,
+                                                         const int32_t *__restrict__ n_clock_dev,
                                                          int time_window, float *__restrict__ pos_out,
                                                          float *__restrict__ feat_out, int32_t *__restrict__ batch_out,
                                                          int32_t *__restrict__ status8, int32_t *__restrict__ status,
@@ -1233,6 +1236,7 @@ __global__ __launch_bounds__(kBlock) void k_stream_gather(StreamState st, int B,
     __shared__ int64_t s_ref[kStreamLanes];
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i < 8) status8[i] = 0;     // the builder's status words start over (dagr_graph_build_window_dev)
+    if (n_clock_dev) n_clock = min(max(*n_clock_dev, 0), n_clock);
     if (i < n_clock) {
         const int64_t bi = (int64_t)batch_clock[i];
         int f = (bi < 0 || bi >= B) ? 8 : 0;
@@ -1564,17 +1568,17 @@ extern "C++" template <typename BatchT, typename ClockT>
 static void launch_stream_stage(const dagr_graph_desc *desc, const GraphWs &ws, const StreamState &st, int B, int cap,
                                 const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const void *batch_new,
                                 int n, const int32_t *n_new_dev, const void *batch_clock, const int64_t *t_clock,
-                                int n_clock, const int64_t *t_now, int64_t window_us, int max_lane, int64_t *lane_dropped,
+                                int n_clock, const int32_t *n_clock_dev, const int64_t *t_now, int64_t window_us, int max_lane, int64_t *lane_dropped,
                                 float *pos_out, float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count,
                                 int32_t *status, hipStream_t stream) {
     const unsigned grid = (unsigned)ceil_div(std::max(cap, n_clock), kBlock);
     k_stream_plan<BatchT, ClockT><<<1, kStreamLanes, 0, stream>>>(st, B, cap, (const BatchT *)batch_new, t_new, n, n_new_dev,
-                                                                  (const ClockT *)batch_clock, t_clock, n_clock, t_now,
-                                                                  window_us, max_lane, lane_dropped, n_dev, lane_count,
+                                                                  (const ClockT *)batch_clock, t_clock, n_clock, n_clock_dev,
+                                                                  t_now, window_us, max_lane, lane_dropped, n_dev, lane_count,
                                                                   status);
     k_stream_gather<BatchT, ClockT><<<grid, kBlock, 0, stream>>>(
         st, B, cap, (const int32_t *)xy_new, t_new, p_new, (const BatchT *)batch_new, n, n_new_dev,
-        (const ClockT *)batch_clock, t_clock, n_clock, desc->time_window, pos_out, feat_out, batch_out, ws.status, status,
+        (const ClockT *)batch_clock, t_clock, n_clock, n_clock_dev, desc->time_window, pos_out, feat_out, batch_out, ws.status, status,
         desc->width, desc->height, ws.cnt, ws.ev_xyb, ws.ev_t, ws.ev_rank);
 }
 
@@ -1619,11 +1623,11 @@ static int stream_stage(const dagr_graph_desc *desc, void *workspace, void *stat
     const int cap = (int)capacity, n = (int)n_new, max_lane = (int)max_lane_events;
     if (batch_is_int64)
         launch_stream_stage<int64_t, int64_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, nullptr, batch_new,
-                                              t_new, n, t_now, window_us, max_lane, lane_dropped, pos_out, feat_out,
+                                              t_new, n, nullptr, t_now, window_us, max_lane, lane_dropped, pos_out, feat_out,
                                               batch_out, n_dev, lane_count, status, (hipStream_t)stream_);
     else
         launch_stream_stage<int32_t, int32_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, nullptr, batch_new,
-                                              t_new, n, t_now, window_us, max_lane, lane_dropped, pos_out, feat_out,
+                                              t_new, n, nullptr, t_now, window_us, max_lane, lane_dropped, pos_out, feat_out,
                                               batch_out, n_dev, lane_count, status, (hipStream_t)stream_);
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
@@ -1632,9 +1636,10 @@ static int stream_stage(const dagr_graph_desc *desc, void *workspace, void *stat
 static int stream_stage_dev(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
                             const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const int32_t *batch_new,
                             const int32_t *n_new_dev, int64_t n_new_max, const int64_t *t_clock, const void *batch_clock,
-                            int32_t clock_is_int64, int64_t n_clock, const int64_t *t_now, int64_t window_us,
-                            int64_t max_lane_events, int64_t *lane_dropped, float *pos_out, float *feat_out,
-                            int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status, void *stream_) {
+                            int32_t clock_is_int64, const int32_t *n_clock_dev, int64_t n_clock, const int64_t *t_now,
+                            int64_t window_us, int64_t max_lane_events, int64_t *lane_dropped, float *pos_out,
+                            float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status,
+                            void *stream_) {
     StreamState st;
     GraphWs ws;
     int rc = stream_stage_args(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, n_new_max,
@@ -1650,11 +1655,11 @@ static int stream_stage_dev(const dagr_graph_desc *desc, void *workspace, void *
     const int cap = (int)capacity, n = (int)n_new_max, nc = (int)n_clock, max_lane = (int)max_lane_events;
     if (clock_is_int64)
         launch_stream_stage<int32_t, int64_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, n_new_dev, batch_clock,
-                                              t_clock, nc, t_now, window_us, max_lane, lane_dropped, pos_out, feat_out,
+                                              t_clock, nc, n_clock_dev, t_now, window_us, max_lane, lane_dropped, pos_out, feat_out,
                                               batch_out, n_dev, lane_count, status, (hipStream_t)stream_);
     else
         launch_stream_stage<int32_t, int32_t>(desc, ws, st, B, cap, xy_new, t_new, p_new, batch_new, n, n_new_dev, batch_clock,
-                                              t_clock, nc, t_now, window_us, max_lane, lane_dropped, pos_out, feat_out,
+                                              t_clock, nc, n_clock_dev, t_now, window_us, max_lane, lane_dropped, pos_out, feat_out,
                                               batch_out, n_dev, lane_count, status, (hipStream_t)stream_);
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
@@ -1687,8 +1692,8 @@ int dagr_stream_stage_dev(const dagr_graph_desc *desc, void *workspace, void *st
                           float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status,
                           void *stream) {
     return stream_stage_dev(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, n_new_dev, n_new_max,
-                            t_clock, batch_clock, clock_is_int64, n_clock, t_now, window_us, 0, nullptr, pos_out, feat_out,
-                            batch_out, n_dev, lane_count, status, stream);
+                            t_clock, batch_clock, clock_is_int64, nullptr, n_clock, t_now, window_us, 0, nullptr, pos_out,
+                            feat_out, batch_out, n_dev, lane_count, status, stream);
 }
 
 int dagr_stream_stage_dev_capped(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
@@ -1700,8 +1705,36 @@ int dagr_stream_stage_dev_capped(const dagr_graph_desc *desc, void *workspace, v
                                  void *stream) {
     DAGR_CHECK_ARG(max_lane_events >= 1, "stream: max_lane_events < 1");
     return stream_stage_dev(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, n_new_dev, n_new_max,
-                            t_clock, batch_clock, clock_is_int64, n_clock, t_now, window_us, max_lane_events, lane_dropped,
-                            pos_out, feat_out, batch_out, n_dev, lane_count, status, stream);
+                            t_clock, batch_clock, clock_is_int64, nullptr, n_clock, t_now, window_us, max_lane_events,
+                            lane_dropped, pos_out, feat_out, batch_out, n_dev, lane_count, status, stream);
+}
+
+// The same two with the clock's length in device memory (a decoded push is its own clock: dagr_stream_decode).
+int dagr_stream_stage_dev_clock(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                                const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const int32_t *batch_new,
+                                const int32_t *n_new_dev, int64_t n_new_max, const int64_t *t_clock, const void *batch_clock,
+                                int32_t clock_is_int64, const int32_t *n_clock_dev, int64_t n_clock, const int64_t *t_now,
+                                int64_t window_us, float *pos_out, float *feat_out, int32_t *batch_out, int32_t *n_dev,
+                                int32_t *lane_count, int32_t *status, void *stream) {
+    DAGR_CHECK_ARG(n_clock_dev != nullptr, "stream: n_clock_dev is NULL");
+    return stream_stage_dev(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, n_new_dev, n_new_max,
+                            t_clock, batch_clock, clock_is_int64, n_clock_dev, n_clock, t_now, window_us, 0, nullptr, pos_out,
+                            feat_out, batch_out, n_dev, lane_count, status, stream);
+}
+
+int dagr_stream_stage_dev_clock_capped(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B,
+                                       int64_t capacity, const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new,
+                                       const int32_t *batch_new, const int32_t *n_new_dev, int64_t n_new_max,
+                                       const int64_t *t_clock, const void *batch_clock, int32_t clock_is_int64,
+                                       const int32_t *n_clock_dev, int64_t n_clock, const int64_t *t_now, int64_t window_us,
+                                       int64_t max_lane_events, int64_t *lane_dropped, float *pos_out, float *feat_out,
+                                       int32_t *batch_out, int32_t *n_dev, int32_t *lane_count, int32_t *status,
+                                       void *stream) {
+    DAGR_CHECK_ARG(n_clock_dev != nullptr, "stream: n_clock_dev is NULL");
+    DAGR_CHECK_ARG(max_lane_events >= 1, "stream: max_lane_events < 1");
+    return stream_stage_dev(desc, workspace, state, B, capacity, xy_new, t_new, p_new, batch_new, n_new_dev, n_new_max,
+                            t_clock, batch_clock, clock_is_int64, n_clock_dev, n_clock, t_now, window_us, max_lane_events,
+                            lane_dropped, pos_out, feat_out, batch_out, n_dev, lane_count, status, stream);
 }
 
 int dagr_graph_search_window(const dagr_graph_desc *desc, void *workspace, int64_t N, int32_t *nbr_src, int16_t *nbr_code,

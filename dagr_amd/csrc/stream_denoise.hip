@@ -188,7 +188,7 @@ __global__ __launch_bounds__(kBlock) void k_denoise_finish(const int32_t *__rest
             int lo = 0, hi = n;
             while (lo < hi) {
                 const int mid = (lo + hi) >> 1;
-                if ((int64_t)batch[mid] < lane) lo = mid + 1;
+                if ((uint64_t)(int64_t)batch[mid] < (uint64_t)lane) lo = mid + 1;   // (a lane-less row, -1, sorts last)
                 else hi = mid;
             }
             return lo;

@@ -403,6 +403,10 @@ class StreamState:
     maps and the scratch of a largest push, grown with the push size, the survivors' buffers, and ``lane_filtered``, which
     accumulates on the device what the filter removed.  Its bound counts the UNFILTERED events pushed.
 
+    A decoding stream (``enable_decode``) owns the decoder's state (``dagr_stream_decode``): the lanes' decoder states and
+    the scratch of a largest push of words, the decoded events' buffers, and ``lane_decoded``, the cumulative counters.  The
+    host never learns how many events a push decoded: its bound grows by ``decode_rows(n_words)`` per push.
+
     A capped stream (``max_lane_events = N``, ``dagr_stream_stage_capped``) keeps the newest ``N`` events of every lane at
     most: no window exceeds ``B * N``, which bounds the host's bound too, and ``lane_dropped`` accumulates on the device
     what the count rule removed.
@@ -435,6 +439,8 @@ class StreamState:
         self.front_state, self.front_cap, self.front_out = None, 0, None
         self.noise = None                               # (W_in, H_in, denoise_us or 0, refractory_us or 0) of a filtering stream
         self.noise_state, self.noise_cap, self.noise_out, self.lane_filtered = None, 0, None, None
+        self.words = None                               # (format, W_in, H_in, max_decoded or None) of a decoding stream
+        self.words_state, self.words_cap, self.words_out, self.lane_decoded = None, 0, None, None
         self.track = None                               # the options of a tracking stream (dagr.streaming._track_options)
         self.track_state, self.lane_untracked, self.track_ids, self.track_hits = None, None, None, None
         self.motion = None                              # the options of its motion model (dagr.streaming._motion_options)
@@ -614,6 +620,72 @@ class StreamState:
         sensor_w, sensor_h = self.noise[:2]
         return self.noise_state[:8 * self.B * sensor_w * sensor_h].view(torch.int64).view(self.B, sensor_h, sensor_w).cpu().numpy()
 
+    # ------------------------------------------------------------------------------------ camera words
+    def enable_decode(self, format, sensor_w, sensor_h, max_decoded=None, t_base=None):
+        """Pushes carry camera words, which ``dagr_stream_decode`` turns into events first: ``format`` is
+        ``DAGR_DECODE_EVT2`` / ``DAGR_DECODE_EVT3``, ``max_decoded`` the rows of the output buffers (None: the worst case of
+        the largest push so far, ``events_per_word`` each), ``t_base`` int64 [B] on the host or None."""
+        self.words = (int(format), int(sensor_w), int(sensor_h), None if max_decoded is None else int(max_decoded))
+        self.words_per = 12 if int(format) == _lib.DEFINES["DAGR_DECODE_EVT3"] else 1
+        self.words_state, self.words_cap, self.words_out = None, 0, None
+        self.words_t_base = None if t_base is None else torch.as_tensor(np.asarray(t_base, np.int64)).to(self.device)
+        self.lane_decoded = torch.zeros((self.B, 4), dtype=torch.int64, device=self.device)
+        self.grow_decode(4096)
+
+    def grow_decode(self, n):
+        """Scratch for pushes of ``n`` words and the decoded events' buffers; the lanes' states are carried over."""
+        if n <= self.words_cap:
+            return
+        L, stream = _lib.lib(), _lib.cur_stream(self.device)
+        nbytes = L.dagr_stream_decode_bytes(self.B, n)
+        if nbytes == 0:
+            raise RuntimeError(f"dagr_stream_decode_bytes({self.B}, {n}): out of range")
+        new = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _lib.check(L.dagr_stream_decode_reset(_lib.ptr(new), nbytes, self.B, n, stream), "stream_decode_reset")
+        if self.words_state is not None:
+            new[:64 * self.B].copy_(self.words_state[:64 * self.B])
+        self.words_state, self.words_cap = new, n
+        rows = self.words[3] if self.words[3] is not None else self.words_per * n
+        if self.words_out is None or rows != int(self.words_out[1].shape[0]):
+            dev = self.device
+            self.words_out = (torch.empty((rows, 2), dtype=torch.int16, device=dev), torch.empty((rows,), dtype=torch.int64, device=dev),
+                              torch.empty((rows,), dtype=torch.int8, device=dev), torch.empty((rows,), dtype=torch.int32, device=dev),
+                              torch.zeros((1,), dtype=torch.int32, device=dev))
+
+    def decode(self, words, word_end, t_base=None):
+        """``dagr_stream_decode`` on a push of words (``words`` uint16 / uint32 bits, ``word_end`` int64 [B], both on the
+        device): ``(xy, t, p, batch int32, count int32[1])`` of the decoded events, valid until the next push.  The arrays
+        have ``max_out = decode_rows(n_words)`` rows; those from the count up are lane-less (lane -1 at pixel (0, 0))."""
+        n = int(words.shape[0])
+        if n > self.words_cap:
+            self.grow_decode(max(n, 2 * self.words_cap))
+        fmt, sensor_w, sensor_h, _ = self.words
+        P, o = _lib.ptr, self.words_out
+        t_base = self.words_t_base if t_base is None else t_base
+        rows = max(self.decode_rows(n), 1)
+        _lib.check(_lib.lib().dagr_stream_decode(
+            P(self.words_state), self.words_state.numel(), self.B, self.words_cap, fmt, sensor_w, sensor_h, P(words) if n else None,
+            P(word_end), n, P(t_base), rows, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(self.lane_decoded),
+            P(self.status), _lib.cur_stream(self.device)), "stream_decode")
+        return o[0][:rows], o[1][:rows], o[2][:rows], o[3][:rows], o[4]
+
+    def decode_rows(self, n_words):
+        """What a push of ``n_words`` words can decode at the most: the host's bound of the window grows by this."""
+        worst = self.words_per * int(n_words)
+        return worst if self.words[3] is None else min(self.words[3], worst)
+
+    def decode_counts(self):
+        """The decoder's cumulative counters int64 [B, 4]: decoded, unsynced, outside, skipped (a copy; synchronises)."""
+        if self.words is None:
+            raise RuntimeError("this stream does not decode camera words (decode=): it has no decoder counters")
+        return self.lane_decoded.cpu().numpy()
+
+    def decode_state(self):
+        """The lanes' decoder states int64 [B, 8]: high, low, loops, y, base_x, pol, synced, 0 (a copy; synchronises)."""
+        if self.words is None:
+            raise RuntimeError("this stream does not decode camera words (decode=): it has no decoder state")
+        return self.words_state[:64 * self.B].view(torch.int64).view(self.B, 8).cpu().numpy()
+
     # ------------------------------------------------------------------------------------ raw sensor events
     def enable_front(self, fx, fy, sensor_w, sensor_h, width, height):
         """Pushes carry raw events of a ``sensor_w x sensor_h`` sensor, downsampled ``fx x fy`` on the device."""
@@ -682,6 +754,10 @@ class StreamState:
             _lib.check(_lib.lib().dagr_stream_front_reset(_lib.ptr(self.front_state), self.front_state.numel(), self.B, cells_w,
                                                           cells_h, self.front_cap, _lib.cur_stream(self.device)),
                        "stream_front_reset")
+        if self.words_state is not None:
+            _lib.check(_lib.lib().dagr_stream_decode_reset(_lib.ptr(self.words_state), self.words_state.numel(), self.B,
+                                                           self.words_cap, _lib.cur_stream(self.device)), "stream_decode_reset")
+            self.lane_decoded.zero_()
         if self.noise_state is not None:
             _lib.check(_lib.lib().dagr_stream_denoise_reset(_lib.ptr(self.noise_state), self.noise_state.numel(), self.B,
                                                             self.noise[0], self.noise[1], self.noise_cap,
@@ -1984,7 +2060,7 @@ class WindowEngine:
         self._x0 = self.x0buf[:N]
         return out if static_out else out.clone()   # the graph's output buffer is rewritten by the next window
 
-    def forward_stream(self, st, xy, t, p, batch, t_now=None, image=None):
+    def forward_stream(self, st, xy, t, p, batch, t_now=None, image=None, words=None, word_end=None):
         """One step of an event stream (``StreamState`` ``st``): ``_forward_window_graph`` with ``dagr_stream_stage`` in
         place of ``dagr_stage_window``.  The new raw events (``xy`` int16[n,2], ``t`` int64[n] absolute us, ``p`` int8[n],
         ``batch`` int32/int64[n] sorted lanes, ``t_now`` int64[B] or None; all on the device) join the window kept in
@@ -1995,6 +2071,12 @@ class WindowEngine:
         windows never exceed ``B * N``, which the buffers meet once -- no growth and no re-capture after its first step.
         A filtering stream (``st.noise``) runs ``dagr_stream_denoise`` on the push before anything else and stages what is
         left through the ``_dev`` entries, with the unfiltered push as the clock.
+        A decoding stream (``st.words``) takes ``words`` (the camera's words as int16 / int32 bit patterns) and ``word_end``
+        (int64 [B], the cumulative end of every lane's run) in place of the events: ``dagr_stream_decode`` first, then the
+        filter and the front when enabled -- on all ``max_out`` rows, those behind the decoder's count being lane-less --,
+        and the stage through the ``_dev_clock`` entries with the decoded push and its device-side count as the clock.  The
+        host's bound grows by ``min(max_decoded, 12 * n_words)`` (EVT 3.0) or ``n_words`` (EVT 2.0) per step, so a decoding
+        stream that is never read back should be capped (``max_lane_events``).
         A tracking stream (``st.track``) ends the step with ``dagr_stream_track`` on the step's detections and the reference
         instants the staging left: one plain launch on the same stream, outside the captured graphs, so every mode and
         body is covered without a re-capture; ``st.track_ids`` / ``st.track_hits`` hold the result.  With a motion model
@@ -2012,7 +2094,11 @@ class WindowEngine:
             raise RuntimeError("forward_stream runs the captured window's body: it needs the tiled level-0 conv "
                                "(l0_tiles) and the event path (no --no_events)")
         L, P = self.L, _lib.ptr
-        n_new = int(t.shape[0])
+        decoding = st.words is not None
+        if decoding != (words is not None):
+            raise RuntimeError("forward_stream: a decoding stream takes words= / word_end=, any other stream events")
+        # a decoding stream: the rows the decoder writes, of which the device alone knows how many are events
+        n_new = st.decode_rows(int(words.shape[0])) if decoding else int(t.shape[0])
         N = st.max_lane_events
         if N is None:
             need = max(st.bound() + n_new, st.cap)   # (a stream that grew on another engine keeps its capacity)
@@ -2051,7 +2137,26 @@ class WindowEngine:
         outputs = (P(self.in_pos), P(self.in_feat), P(self.in_batch), P(self.n_dev), P(st.lane_count), P(st.status),
                    _lib.cur_stream(self.device))
         cap_args = () if N is None else (N, P(st.lane_dropped))
-        if st.noise is not None:    # the noise filter first; the unfiltered push stays the clock
+        if decoding:                # camera words: decode, then the fronts on all rows, then the stage with the decoded push as
+            sensor = (self.W, self.H) if st.front is None else st.front[2:4]       # the clock, its length on the device
+            if st.words[1:3] != sensor or (st.noise is not None and st.noise[:2] != sensor):
+                raise RuntimeError(f"the stream decodes a {st.words[1]} x {st.words[2]} sensor, its fronts take "
+                                   f"{sensor[0]} x {sensor[1]} pixels")
+            if st.front is not None and st.front[4:] != (self.W, self.H):
+                raise RuntimeError(f"the stream downsamples to {st.front[4]} x {st.front[5]}, the engine runs "
+                                   f"{self.W} x {self.H}")
+            c_xy, c_t, c_p, c_batch, c_n = st.decode(words, word_end)
+            rows = int(c_t.shape[0])
+            s_xy, s_t, s_p, s_batch, s_n = c_xy, c_t, c_p, c_batch, c_n
+            if st.noise is not None:
+                s_xy, s_t, s_p, s_batch, s_n = st.denoise(s_xy, s_t, s_p, s_batch)
+            if st.front is not None:
+                s_xy, s_t, s_p, s_batch, s_n = st.downsample(s_xy[:rows], s_t[:rows], s_p[:rows], s_batch[:rows])
+            stage = L.dagr_stream_stage_dev_clock if N is None else L.dagr_stream_stage_dev_clock_capped
+            _lib.check(stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(s_xy), P(s_t), P(s_p),
+                             P(s_batch), P(s_n), rows, P(c_t), P(c_batch), 0, P(c_n), rows, P(t_now), st.window_us, *cap_args,
+                             *outputs), "stream_stage_dev_clock")
+        elif st.noise is not None:    # the noise filter first; the unfiltered push stays the clock
             sensor = (self.W, self.H) if st.front is None else st.front[2:4]
             if st.noise[:2] != sensor:
                 raise RuntimeError(f"the stream filters a {st.noise[0]} x {st.noise[1]} sensor, its pushes carry "

@@ -167,6 +167,86 @@ motion model's predict, filter and coast are what they are above, over the rows 
 
 ``rescued`` is int64 ``[B]``, cumulative, zero after construction and after ``reset()``.  Unlike ByteTrack, round two
 considers every live unmatched track, not only those seen in the step before.  Without ``rescue`` nothing of this exists.
+
+Camera words (``decode="evt3"`` or ``"evt2"``): an event camera delivers words, not arrays.  A decoding stream takes the
+camera's words (``step_words`` / ``step_words_device``) and decodes them on the device (``dagr_stream_decode``) in front of
+everything above: decode, then the noise filter, then ``downsample=``, then the window.  The two formats are stated here as
+the vendor's public descriptions are recalled; no specification document, camera file or third-party decoder was at hand,
+so THIS statement is the definition, ``DecodeDefinition`` below is its sequential loop and the yardstick of the kernels, and
+agreement with a real camera file is not demonstrated.
+
+Each lane owns a decoder state, carried from push to push:
+
+- ``high``, ``low``, ``loops``: non-negative ints.
+- ``y``.
+- ``base_x``: uint32, additions modulo 2^32.
+- ``pol``.
+- ``synced``: 0 or 1.
+
+All are 0 after construction and after ``reset()``.  A push gives every lane a run of words, possibly empty.  A lane's words
+are taken in order.  Bit ranges are inclusive, with bit 0 the least significant.
+
+EVT 3.0.  Words are little-endian uint16.  ``type = w >> 12``.
+
+====== ============ ===============================================================================================
+type   name         effect
+====== ============ ===============================================================================================
+0x0    ADDR_Y       ``y = w & 0x7FF``.  Bit 11 is ignored.
+0x2    ADDR_X       Emits one event at ``x = w & 0x7FF`` with ``pol = (w >> 11) & 1`` (the word's own bit).
+                    ``base_x`` and the state's ``pol`` are unchanged.
+0x3    VECT_BASE_X  ``base_x = w & 0x7FF``, ``pol = (w >> 11) & 1``.
+0x4    VECT_12      For ``i = 0..11`` ascending, where bit ``i`` of ``w`` is set, emits an event at ``x = base_x + i``
+                    with the state's ``pol``.  Then ``base_x += 12``.
+0x5    VECT_8       As VECT_12 with ``i = 0..7`` and ``base_x += 8``.  Bits 8..11 are ignored.
+0x6    TIME_LOW     ``low = w & 0xFFF``.
+0x8    TIME_HIGH    ``v = w & 0xFFF``.  If ``synced`` and ``high - v >= 2048``, then ``loops += 1``.  Then ``high = v``
+                    and ``synced = 1``.  ``low`` is kept.
+others              CONTINUED_4 (0x7), EXT_TRIGGER (0xA), OTHERS (0xE), CONTINUED_12 (0xF), reserved (0x1, 0x9, 0xB,
+                    0xC, 0xD): no effect on the state.  ``skipped[b] += 1``.
+====== ============ ===============================================================================================
+
+Time of an emitted event: ``t = t_base[b] + (loops << 24) + (high << 12) + low``, as int64.
+
+EVT 2.0.  Words are little-endian uint32.  ``type = w >> 28``.
+
+========= =============== ====================================================================================
+type      name            effect
+========= =============== ====================================================================================
+0x0 / 0x1 CD_OFF / CD_ON  Emits one event with ``low6 = (w >> 22) & 0x3F``, ``x = (w >> 11) & 0x7FF``,
+                          ``y = w & 0x7FF``, ``pol = type``.
+0x8       TIME_HIGH       ``v = w & 0x0FFFFFFF``.  If ``synced`` and ``high - v >= 1 << 27``, then ``loops += 1``.
+                          Then ``high = v`` and ``synced = 1``.
+any other                 ``skipped[b] += 1``.
+========= =============== ====================================================================================
+
+Time of an emitted event: ``t = t_base[b] + (loops << 34) + (high << 6) + low6``.
+
+Both formats.  An emitted event goes through these checks in order:
+
+1. If ``synced == 0``, drop it and ``unsynced[b] += 1``.  No ``TIME_HIGH`` has been seen since the reset, so the time base
+   is unknown.
+2. Otherwise, if not (``x < sensor_w and y < sensor_h``), drop it, ``outside[b] += 1``, and raise status bit 4 (value 16,
+   "a raw event is outside the sensor").
+3. Otherwise it is a decoded event ``(x, y, t, p = +1 if pol else -1, lane b)`` and ``decoded[b] += 1``.
+
+Further rules:
+
+- Decoded events keep word order, and bit order inside a vector word.
+- Lanes are concatenated in lane order.
+- The four counters are int64 ``[B]``, cumulative, and zero after construction and ``reset()``.
+- A backwards ``TIME_HIGH`` jump smaller than the wrap rule makes ``t`` go backwards.  The staging's status bit 0 reports
+  that, as it does for any push.
+- The decoder depends on nothing but the word sequence.  Any chunking of a lane's words into pushes gives the same events,
+  counters and final state.
+
+Output buffer.  The decoded events of a push are written into buffers of ``max_out`` rows (``max_decoded=``).  If a push
+decodes more than ``max_out`` events, the first ``max_out`` are kept, the state and the counters advance as if all had been
+written, and status bit 6 (value 64, "decoded events exceed max_out") is raised.  ``max_decoded=None`` sizes the buffers for
+the worst case of the push (12 events per EVT 3.0 word, 1 per EVT 2.0 word), so bit 6 cannot occur; a smaller value makes
+the fronts behind the decoder cheaper -- they are handed all ``max_out`` rows -- and may raise it.  The decoded push is the
+stream's clock: the order checks run on it, and the lane's newest event is its newest DECODED event.  The host never learns
+how many events a push decoded, so its bound of the window grows by ``min(max_decoded, 12 * n_words)`` (EVT 3.0) or
+``n_words`` (EVT 2.0) per step: a decoding stream that is never read back should be capped (``max_lane_events``).
 """
 import numpy as np
 
@@ -178,7 +258,8 @@ STATUS_BITS = ((1, "a timestamp goes backwards inside a lane (within a push or a
                (4, "survivors plus new events exceed the stream's capacity"),
                (8, "batch is not sorted or is outside [0, batch_size)"),
                (16, "a raw event is outside the sensor (downsampling streams)"),
-               (32, "a frame's lane is outside [0, batch_size)"))
+               (32, "a frame's lane is outside [0, batch_size)"),
+               (64, "decoded events exceed max_out (a decoding stream's max_decoded)"))
 
 
 def _window_and_cap(window_us, max_lane_events, time_window, batch_size, who):
@@ -721,6 +802,150 @@ class StreamDefinition:
         return format_data_np(x, y, t_rel, self.W, self.H, self.time_window), p.astype(np.float32).reshape(-1, 1), batch
 
 
+DECODE_FORMATS = {"evt2": (DEFINES["DAGR_DECODE_EVT2"], np.uint32, 1), "evt3": (DEFINES["DAGR_DECODE_EVT3"], np.uint16, 12)}
+DECODE_COUNTERS = ("decoded", "unsynced", "outside", "skipped")
+DECODE_STATE = ("high", "low", "loops", "y", "base_x", "pol", "synced")
+
+
+def _decode_options(decode, max_decoded, sensor_w, sensor_h, who):
+    """``(format name, max_decoded or None)`` of a decoding stream over a ``sensor_w x sensor_h`` sensor, checked; refusals
+    by name."""
+    if decode not in DECODE_FORMATS:
+        raise ValueError(f"{who}: decode = {decode!r} must be None (off), 'evt2' or 'evt3'")
+    if max_decoded is not None and (not _is_int(max_decoded) or not 1 <= int(max_decoded) < 1 << 30):
+        raise ValueError(f"{who}: max_decoded = {max_decoded!r} must be an int in 1..2**30 - 1 (or None: the worst case of "
+                         "every push)")
+    if not (1 <= int(sensor_w) <= 32767 and 1 <= int(sensor_h) <= 32767):
+        raise ValueError(f"{who}: the sensor {sensor_w} x {sensor_h} does not fit the int16 pixel coordinates (1..32767 per "
+                         "axis)")
+    return decode, None if max_decoded is None else int(max_decoded)
+
+
+def _decode_t_base(t_base, batch_size, who):
+    """``t_base`` of a decoding stream as int64 ``[B]`` (None: zeros; a scalar serves every lane)."""
+    if t_base is None:
+        return np.zeros(int(batch_size), np.int64)
+    a = np.asarray(t_base)
+    if a.dtype.kind not in "iu" or a.size not in (1, int(batch_size)):
+        raise ValueError(f"{who}: t_base = {t_base!r} must be an int or one int per lane ({int(batch_size)})")
+    return np.array(np.broadcast_to(a.astype(np.int64).reshape(-1), (int(batch_size),)))
+
+
+def words_as_array(words, decode, who):
+    """The words of a push as a contiguous array of the format's word type: ``words`` is such an array, or ``bytes`` / a
+    uint8 array whose length is a multiple of the word size (little-endian)."""
+    dtype = np.dtype(DECODE_FORMATS[decode][1])
+    if isinstance(words, (bytes, bytearray, memoryview)):
+        words = np.frombuffer(words, np.uint8)
+    words = np.ascontiguousarray(np.asarray(words)).reshape(-1)
+    if words.dtype == np.uint8:
+        if words.size % dtype.itemsize:
+            raise ValueError(f"{who}: {words.size} bytes are not a whole number of {dtype.itemsize}-byte {decode} words")
+        return words.view(dtype.newbyteorder("<")).astype(dtype, copy=False)
+    if words.dtype != dtype:
+        raise ValueError(f"{who}: {decode} words are {dtype.name} (or bytes / uint8), got {words.dtype.name}")
+    return words
+
+
+def _lane_words(lane_words, n_words, batch_size, who):
+    """``lane_words`` of a push as int64 ``[B]``: words per lane, in lane order (default: all to lane 0 when ``B == 1``)."""
+    if lane_words is None:
+        if int(batch_size) != 1:
+            raise ValueError(f"{who}: lane_words is required with {int(batch_size)} lanes (words per lane, in lane order)")
+        return np.array([n_words], np.int64)
+    a = np.asarray(lane_words)
+    if a.dtype.kind not in "iu" or a.shape != (int(batch_size),) or (a.astype(np.int64) < 0).any() or int(a.sum()) != n_words:
+        raise ValueError(f"{who}: lane_words = {lane_words!r} must be {int(batch_size)} non-negative ints that sum to the "
+                         f"number of words ({n_words})")
+    return a.astype(np.int64)
+
+
+class DecodeDefinition:
+    """The decoder of the module docstring as the sequential loop it is stated as: ``push(words, lane_words)`` decodes one
+    push of every lane and returns ``(x int16, y int16, t int64, p int8, batch int32)``, at most ``max_out`` rows (None:
+    all).  ``counts`` is the dict of the four int64 ``[B]`` counters, ``state`` the dict of the lanes' states (int64 ``[B]``
+    each), ``status`` the bits the pushes have raised (16: outside the sensor, 64: more than ``max_out``).  The yardstick of
+    ``dagr_stream_decode``; nothing on the device path calls it."""
+
+    def __init__(self, batch_size, format, sensor_w, sensor_h, t_base=None, max_out=None):
+        self.B = int(batch_size)
+        self.format, self.max_out = _decode_options(format, max_out, sensor_w, sensor_h, "DecodeDefinition")
+        self.sensor_w, self.sensor_h = int(sensor_w), int(sensor_h)
+        self.t_base = _decode_t_base(t_base, self.B, "DecodeDefinition")
+        self.reset()
+
+    def reset(self):
+        self.state = {k: np.zeros(self.B, np.int64) for k in DECODE_STATE}
+        self.counts = {k: np.zeros(self.B, np.int64) for k in DECODE_COUNTERS}
+        self.status = 0
+
+    def push(self, words, lane_words=None):
+        words = words_as_array(words, self.format, "DecodeDefinition")
+        lane_words = _lane_words(lane_words, len(words), self.B, "DecodeDefinition")
+        evt3 = self.format == "evt3"
+        out, at = [], 0
+        for b in range(self.B):
+            s = {k: int(v[b]) for k, v in self.state.items()}
+            c = {k: 0 for k in DECODE_COUNTERS}
+            t0 = int(self.t_base[b])
+
+            def emit(x, y, pol, low, shift_high, shift_loops):
+                if not s["synced"]:
+                    c["unsynced"] += 1
+                elif not (x < self.sensor_w and y < self.sensor_h):
+                    c["outside"] += 1
+                    self.status |= 16
+                else:
+                    c["decoded"] += 1
+                    out.append((x, y, t0 + (s["loops"] << shift_loops) + (s["high"] << shift_high) + low, 1 if pol else -1, b))
+
+            def time_high(v, wrap):
+                if s["synced"] and s["high"] - v >= wrap:
+                    s["loops"] += 1
+                s["high"], s["synced"] = v, 1
+
+            for w in words[at:at + int(lane_words[b])].tolist():
+                if evt3:
+                    kind = w >> 12
+                    if kind == 0x0:
+                        s["y"] = w & 0x7FF
+                    elif kind == 0x2:
+                        emit(w & 0x7FF, s["y"], (w >> 11) & 1, s["low"], 12, 24)
+                    elif kind == 0x3:
+                        s["base_x"], s["pol"] = w & 0x7FF, (w >> 11) & 1
+                    elif kind in (0x4, 0x5):
+                        bits = 12 if kind == 0x4 else 8
+                        for i in range(bits):
+                            if (w >> i) & 1:
+                                emit((s["base_x"] + i) & 0xFFFFFFFF, s["y"], s["pol"], s["low"], 12, 24)
+                        s["base_x"] = (s["base_x"] + bits) & 0xFFFFFFFF
+                    elif kind == 0x6:
+                        s["low"] = w & 0xFFF
+                    elif kind == 0x8:
+                        time_high(w & 0xFFF, 2048)
+                    else:
+                        c["skipped"] += 1
+                else:
+                    kind = w >> 28
+                    if kind <= 1:
+                        emit((w >> 11) & 0x7FF, w & 0x7FF, kind, (w >> 22) & 0x3F, 6, 34)
+                    elif kind == 0x8:
+                        time_high(w & 0x0FFFFFFF, 1 << 27)
+                    else:
+                        c["skipped"] += 1
+            at += int(lane_words[b])
+            for k in DECODE_STATE:
+                self.state[k][b] = s[k]
+            for k in DECODE_COUNTERS:
+                self.counts[k][b] += c[k]
+        if self.max_out is not None and len(out) > self.max_out:
+            self.status |= 64
+            out = out[:self.max_out]
+        cols = list(zip(*out)) if out else [[]] * 5
+        return (np.array(cols[0], np.int16), np.array(cols[1], np.int16), np.array(cols[2], np.int64),
+                np.array(cols[3], np.int8), np.array(cols[4], np.int32))
+
+
 def _flag_names(flag):
     return "; ".join(text for bit, text in STATUS_BITS if flag & bit)
 
@@ -760,6 +985,16 @@ class EventStream:
     is then ``dagr_stream_track_rescue`` or ``dagr_stream_track_cv_rescue``.  ``rescued()`` counts its matches.  The
     defaults are ByteTrack's conventions, not measured optima.  A stream built without it issues exactly the calls it
     issues without the round.
+    ``decode`` (``None``: off, ``"evt2"`` or ``"evt3"``), ``max_decoded`` and ``t_base``: the stream takes the camera's words
+    (``step_words`` / ``step_words_device``) and ``dagr_stream_decode`` turns them into events on the device, in front of
+    the filter, the front and the window (module docstring; the formats as recalled from the vendor's public descriptions,
+    not confirmed against a camera file).  The sensor is ``(W, H)``, or ``sensor_size`` with ``downsample=``.
+    ``max_decoded=None`` sizes the decoded events' buffers for the worst case of every push, so that status bit 6 cannot
+    occur; a smaller int makes the fronts behind the decoder cheaper and may raise it.  ``t_base`` (an int or one per lane)
+    is added to every decoded timestamp.  ``decode_counts()`` / ``decode_state()`` read the counters and the lanes' states
+    back.  The host's bound of the window grows by the worst case of every push, so a decoding stream that is never read
+    back should be capped (``max_lane_events``).  A stream built without ``decode`` makes exactly the calls it makes
+    without the decoder.
     ``frame_size`` (``(W_f, H_f)``) and ``frame_bgr``: the steps may carry raw sensor frames (``frame=``), which
     ``dagr_stream_frame`` turns into the model's image on the device (``frame_definition``) with the stream's
     ``downsample`` factors, or 1 without ``downsample``.
@@ -774,7 +1009,8 @@ class EventStream:
     """
 
     def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
-                 max_lane_events=None, denoise_us=None, refractory_us=None, track=None, motion=None, rescue=None):
+                 max_lane_events=None, denoise_us=None, refractory_us=None, track=None, motion=None, rescue=None,
+                 decode=None, max_decoded=None, t_base=None):
         import torch
         self.model = model
         self.track = _track_options(track, "EventStream")
@@ -810,6 +1046,14 @@ class EventStream:
         elif sensor_size is not None:
             raise ValueError("EventStream: sensor_size is given without downsample")
         self.denoise_us, self.refractory_us = _noise_options(denoise_us, refractory_us, eng.B, w_in, h_in, "EventStream")
+        self.decode, self.max_decoded = None, None
+        if decode is not None:
+            self.decode, self.max_decoded = _decode_options(decode, max_decoded, w_in, h_in, "EventStream")
+            self.t_base = _decode_t_base(t_base, eng.B, "EventStream")
+            self.state.enable_decode(DECODE_FORMATS[self.decode][0], w_in, h_in, self.max_decoded,
+                                     self.t_base if self.t_base.any() else None)
+        elif max_decoded is not None or t_base is not None:
+            raise ValueError("EventStream: max_decoded / t_base are given without decode")
         if downsample is not None:
             self.state.enable_front(fx, fy, w_in, h_in, eng.W, eng.H)
         if self.denoise_us is not None or self.refractory_us is not None:
@@ -918,12 +1162,8 @@ class EventStream:
         return (d[o_xy:o_b].view(torch.int16).view(-1, 2), d[:o_xy].view(torch.int64), d[o_p:o_p + n].view(torch.int8),
                 d[o_b:o_p].view(torch.int32), None if now is None else d[o_now:].view(torch.int64))
 
-    # ------------------------------------------------------------------------------------ steps
-    def step_device(self, xy, t, p, batch=None, t_now=None, image=None, frame=None, frame_lanes=None):
-        """One step without a host synchronisation: ``(det[B, A, 6], n_keep[B])`` as ``forward_detections`` returns them,
-        valid until the engine's next call.  ``image``: the model's image batch fp32 [B, 3, H, W]; ``frame``: raw sensor
-        frames uint8 ``[n, H_f, W_f, 3]`` or ``[H_f, W_f, 3]`` (host or device) for the lanes ``frame_lanes`` (default: all
-        lanes in order) -- the other lanes keep their frame; either makes the step a frame step for the whole batch."""
+    def _frame_and_now(self, t_now, image, frame, frame_lanes):
+        """What every kind of step does first: the frames into their lanes, a scalar ``t_now`` for every lane."""
         import torch
         if frame is not None:
             if image is not None:
@@ -936,6 +1176,104 @@ class EventStream:
             t_now = np.full((self.B,), int(t_now), np.int64)
         elif torch.is_tensor(t_now) and t_now.numel() == 1 and self.B > 1:
             t_now = t_now.reshape(1).expand(self.B)
+        return t_now
+
+    def _upload_words(self, words, lane_words, t_now):
+        """The words of a push on the device as (bit patterns int16 / int32 [n], word_end int64[B], t_now int64[B] or
+        None).  Host inputs are packed into one buffer: ONE upload, of word_end, t_now and the words."""
+        import torch
+        _, dtype, _ = DECODE_FORMATS[self.decode]
+        size = np.dtype(dtype).itemsize
+        bits = torch.int16 if size == 2 else torch.int32
+        if torch.is_tensor(words) and words.is_cuda:
+            words = words.reshape(-1).contiguous()
+            if words.dtype == torch.uint8:
+                if words.numel() % size:
+                    raise ValueError(f"EventStream: {words.numel()} bytes are not a whole number of {size}-byte "
+                                     f"{self.decode} words")
+            elif words.element_size() != size or words.dtype.is_floating_point:
+                raise ValueError(f"EventStream: {self.decode} words are {np.dtype(dtype).name} (or bytes / uint8), got "
+                                 f"{words.dtype}")
+            words = words.view(bits)
+            n = int(words.numel())
+            if torch.is_tensor(lane_words) and lane_words.is_cuda:
+                if lane_words.numel() != self.B:
+                    raise ValueError(f"EventStream: lane_words needs one count per lane ({self.B})")
+                end = torch.cumsum(lane_words.reshape(-1).to(torch.int64), 0)
+            else:
+                end = torch.from_numpy(np.cumsum(_lane_words(lane_words, n, self.B, "EventStream"))).to(self.device)
+            if t_now is not None and not torch.is_tensor(t_now):
+                t_now = torch.from_numpy(np.ascontiguousarray(np.asarray(t_now, np.int64))).to(self.device)
+            return words, end, None if t_now is None else t_now.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+        if torch.is_tensor(words):
+            words = words.cpu().reshape(-1)
+            words = words.view(torch.uint8).numpy() if words.dtype == torch.uint8 else words.view(bits).numpy().view(dtype)
+        words = words_as_array(words, self.decode, "EventStream")
+        n = len(words)
+        if torch.is_tensor(lane_words):
+            lane_words = lane_words.cpu().numpy()
+        end = np.cumsum(_lane_words(lane_words, n, self.B, "EventStream"))
+        now = None
+        if t_now is not None:
+            now = t_now.cpu().numpy() if torch.is_tensor(t_now) else np.asarray(t_now)
+            now = np.ascontiguousarray(np.broadcast_to(now.astype(np.int64).reshape(-1), (self.B,)))
+        o_now, o_words = 8 * self.B, 16 * self.B
+        buf = np.empty(o_words + size * n, np.uint8)
+        buf[:o_now] = end.astype(np.int64).view(np.uint8)
+        buf[o_now:o_words] = 0 if now is None else now.view(np.uint8)
+        buf[o_words:] = words.view(np.uint8)
+        d = torch.from_numpy(buf).to(self.device)
+        return d[o_words:].view(bits), d[:o_now].view(torch.int64), None if now is None else d[o_now:o_words].view(torch.int64)
+
+    # ------------------------------------------------------------------------------------ steps
+    def step_words_device(self, words, lane_words=None, t_now=None, image=None, frame=None, frame_lanes=None):
+        """One step of a decoding stream (``decode=``) without a host synchronisation: as ``step_device``, with the camera's
+        words in place of the events.  ``words``: uint16 (EVT 3.0) / uint32 (EVT 2.0) words, host or device -- a device
+        tensor may hold them as int16 / int32 bit patterns --, or ``bytes`` / a uint8 buffer whose length is a multiple of
+        the word size (little-endian).  ``lane_words``: ints ``[B]``, the words of every lane in lane order (default: all
+        words to lane 0 when ``B == 1``).  Host inputs travel in ONE upload: the words, their lane ends and ``t_now``."""
+        import torch
+        if self.decode is None:
+            raise ValueError("EventStream: step_words / step_words_device need a stream built with decode='evt2' or 'evt3'; "
+                             "this stream takes decoded events (step / step_device)")
+        t_now = self._frame_and_now(t_now, image, frame, frame_lanes)
+        words, word_end, t_now = self._upload_words(words, lane_words, t_now)
+        if t_now is not None and t_now.numel() != self.B:
+            raise ValueError(f"EventStream: t_now needs one instant per lane ({self.B})")
+        eng = self.model.engine()
+        with torch.no_grad():
+            self.outputs, det = eng.forward_stream(self.state, None, None, None, None, t_now=t_now, image=image, words=words,
+                                                   word_end=word_end)
+        self.model._window = None            # a reset=False call then starts from a window of its own
+        return det
+
+    def step_words(self, words, lane_words=None, t_now=None, image=None, frame=None, frame_lanes=None):
+        """One step of a decoding stream: the detections list ``model(x, reset=True)[0]`` returns for the stream's window."""
+        return self._finish_step(self.step_words_device(words, lane_words=lane_words, t_now=t_now, image=image, frame=frame,
+                                                        frame_lanes=frame_lanes))
+
+    def decode_counts(self):
+        """The decoder's counters since construction / ``reset()``: a dict of ``decoded``, ``unsynced``, ``outside`` and
+        ``skipped``, int64 [B] each (synchronises).  Raises without ``decode=``."""
+        c = self.state.decode_counts()
+        return {k: c[:, i].copy() for i, k in enumerate(DECODE_COUNTERS)}
+
+    def decode_state(self):
+        """The lanes' decoder states: a dict of ``high``, ``low``, ``loops``, ``y``, ``base_x``, ``pol`` and ``synced``,
+        int64 [B] each (synchronises).  Raises without ``decode=``."""
+        s = self.state.decode_state()
+        return {k: s[:, i].copy() for i, k in enumerate(DECODE_STATE)}
+
+    def step_device(self, xy, t, p, batch=None, t_now=None, image=None, frame=None, frame_lanes=None):
+        """One step without a host synchronisation: ``(det[B, A, 6], n_keep[B])`` as ``forward_detections`` returns them,
+        valid until the engine's next call.  ``image``: the model's image batch fp32 [B, 3, H, W]; ``frame``: raw sensor
+        frames uint8 ``[n, H_f, W_f, 3]`` or ``[H_f, W_f, 3]`` (host or device) for the lanes ``frame_lanes`` (default: all
+        lanes in order) -- the other lanes keep their frame; either makes the step a frame step for the whole batch."""
+        import torch
+        if self.decode is not None:
+            raise ValueError(f"EventStream: step / step_device take decoded events; this stream decodes {self.decode} words "
+                             "(decode=): use step_words / step_words_device")
+        t_now = self._frame_and_now(t_now, image, frame, frame_lanes)
         xy, t, p, batch, t_now = self._upload(xy, t, p, batch, t_now)
         if t_now is not None and t_now.numel() != self.B:
             raise ValueError(f"EventStream: t_now needs one instant per lane ({self.B})")
@@ -947,9 +1285,13 @@ class EventStream:
 
     def step(self, xy, t, p, batch=None, t_now=None, image=None, frame=None, frame_lanes=None):
         """One step: the detections list ``model(x, reset=True)[0]`` returns for the stream's window."""
+        return self._finish_step(self.step_device(xy, t, p, batch=batch, t_now=t_now, image=image, frame=frame,
+                                                  frame_lanes=frame_lanes))
+
+    def _finish_step(self, det_n_keep):
+        """The read-back that ends ``step`` / ``step_words``."""
         from .model.utils import detections_from_device
-        det, n_keep = self.step_device(xy, t, p, batch=batch, t_now=t_now, image=image, frame=frame,
-                                       frame_lanes=frame_lanes)
+        det, n_keep = det_n_keep
         detections = detections_from_device(det, n_keep)        # the step's one synchronisation
         if self.track is not None:                              # cut by the counts that read-back brought
             for name in ("track_ids", "track_hits") + (("track_boxes", "track_vel") if self.motion is not None else ()):
@@ -1020,7 +1362,7 @@ class EventStream:
 
     def reset(self):
         """Empty the stream: no resident events, no reference instants, zero change maps, empty stamp maps, zero dropped and
-        filtered counts, a clear status word, zero step counters; no tracks, ids from 1 again, zero untracked and rescued counts.  The
+        filtered counts, zero decoder states and counters, a clear status word, zero step counters; no tracks, ids from 1 again, zero untracked and rescued counts.  The
         frame in force stays, and the next step runs it through the image branch again."""
         self.state.reset()
 

@@ -175,7 +175,8 @@ int dagr_stage_window(const dagr_graph_desc *desc, void *workspace, const float 
  *   bit 2: survivors plus new events exceed `capacity`;
  *   bit 3: batch_new is not sorted or is outside [0, B);
  *   bit 4: (dagr_stream_downsample) a raw event outside the sensor;
- *   bit 5: (dagr_stream_frame) a frame's lane is outside [0, B).
+ *   bit 5: (dagr_stream_frame) a frame's lane is outside [0, B);
+ *   bit 6: (dagr_stream_decode) a push decodes more events than max_out.
  * Events outside the sensor raise the builder's own flag (dagr_graph_status).
  * DAGR_ERR_INVALID_ARG before any launch: window_us <= 0, window_us > desc.time_window, capacity < n_new,
  * capacity > desc.max_events, B != desc.batch_size, NULL pointers.
@@ -305,6 +306,78 @@ int dagr_stream_denoise(void *state, size_t state_bytes, int32_t B, int64_t max_
                         const int64_t *t_raw, const int8_t *p_raw, const void *batch_raw, int32_t batch_is_int64,
                         int64_t n_raw, int16_t *xy_out, int64_t *t_out, int8_t *p_out, int32_t *batch_out, int32_t *n_out,
                         int64_t *lane_filtered /* [B], device, accumulated; may be NULL */, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------ *
+ * Event stream decoder: the camera's EVT 3.0 / EVT 2.0 words, decoded on the device
+ *   An event camera delivers words, not (x, y, t, p) arrays: EVT 2.0 is one 32-bit word per event plus time words, EVT 3.0
+ *   a stateful stream of 16-bit words with run-length vectors.  dagr_stream_decode turns a push of words of B lanes into
+ *   the rows dagr_stream_denoise / dagr_stream_downsample / dagr_stream_stage_dev_clock take and leaves them and their count
+ *   in device memory.  Three launches, no host synchronisation, integer arithmetic only.  The formats are stated in
+ *   dagr_amd/streaming.py (module docstring) from the vendor's public descriptions as recalled; DecodeDefinition there is the
+ *   yardstick, and agreement with a real camera file has not been demonstrated.
+ *
+ * Every lane owns a decoder state, carried from push to push: int64[8] = high, low, loops, y, base_x (uint32 arithmetic),
+ * pol, synced, 0.  A lane's words are taken in order (type = w >> 12 for EVT 3.0, w >> 28 for EVT 2.0):
+ *   EVT 3.0  0x0 ADDR_Y y = w & 0x7FF; 0x2 ADDR_X one event at x = w & 0x7FF with the word's bit 11 as polarity; 0x3
+ *            VECT_BASE_X base_x = w & 0x7FF, pol = bit 11; 0x4 VECT_12 / 0x5 VECT_8 an event at base_x + i for every set bit
+ *            i < 12 / 8 in ascending order with the state's pol, then base_x += 12 / 8; 0x6 TIME_LOW low = w & 0xFFF; 0x8
+ *            TIME_HIGH v = w & 0xFFF, loops += 1 if synced and high - v >= 2048, then high = v, synced = 1; every other
+ *            type is skipped.  t = t_base[b] + (loops << 24) + (high << 12) + low.
+ *   EVT 2.0  0x0 / 0x1 CD_OFF / CD_ON one event at x = (w >> 11) & 0x7FF, y = w & 0x7FF, polarity = type, low6 =
+ *            (w >> 22) & 0x3F; 0x8 TIME_HIGH v = w & 0x0FFFFFFF, loops += 1 if synced and high - v >= 2^27, then high = v,
+ *            synced = 1; every other type is skipped.  t = t_base[b] + (loops << 34) + (high << 6) + low6.
+ * An emitted event is dropped and counted as unsynced if synced == 0; else dropped, counted as outside and flagged (bit 4,
+ * value 16) unless x < sensor_w and y < sensor_h; else it is a decoded row (x, y, t, p = pol ? +1 : -1, lane b).  Dropped
+ * events take no output row.  The rows keep word order, bit order inside a vector word, and lane order.  The result depends
+ * on the word sequence only: any chunking of a lane's words into pushes gives the same rows, counters and final state.
+ *
+ * state: dagr_stream_decode_bytes(B, max_words) bytes (0: out of range -- B in 1..127, max_words in 1..2^25 - 1),
+ *        dagr_stream_decode_reset before the first push and to zero the lanes' states.  The states are its first
+ *        B * 8 int64 (a caller that needs a larger max_words copies them into the new state after its reset); a copy of
+ *        them and one summary, one carried summary and one count per tile of DAGR_DECODE_TILE words follow.
+ * words uint16 (EVT 3.0) / uint32 (EVT 2.0), little-endian, aligned to the word size, the lanes' runs concatenated;
+ * word_end int64[B] the cumulative end of each lane's run, non-decreasing, last == n_words; t_base int64[B] or NULL (0).
+ * Outputs for max_out rows: xy_out int16[.,2] (4-byte aligned), t_out int64, p_out int8, batch_out int32, *n_out =
+ * min(decoded events, max_out).  If the push decodes more than max_out events the first max_out are written, the states
+ * and counters advance as if all had been, and bit 6 (value 64) of `status` is raised.  Rows *n_out .. max_out - 1 of
+ * xy_out are (0, 0) and of batch_out -1, as dagr_stream_denoise leaves them.  lane_counts int64[B, 4] (may be NULL):
+ * decoded, unsynced, outside, skipped are added to it; the caller zeroes it.  All in device memory.
+ * A word_end that is not non-decreasing, exceeds n_words or does not end at n_words is clamped on the device and raises
+ * bit 3 (value 8); words behind the last lane's end are ignored.  No index leaves the buffers.
+ * DAGR_ERR_INVALID_ARG before any launch: unknown format, sizes out of range (sensor_w, sensor_h in 1..32767),
+ * n_words > max_words, max_out < 1 or >= 2^30, a state smaller than dagr_stream_decode_bytes, NULL pointers, words not
+ * aligned to its word size.
+ *
+ * dagr_stream_stage_dev_clock / dagr_stream_stage_dev_clock_capped: dagr_stream_stage_dev / _capped with the clock's
+ * length on the device too: the clock has clamp(*n_clock_dev, 0, n_clock) events.  A decoded push is its own clock and only
+ * the device knows its length.
+ * ------------------------------------------------------------------------ */
+#define DAGR_DECODE_EVT2 2
+#define DAGR_DECODE_EVT3 3
+#define DAGR_DECODE_TILE 1024
+size_t dagr_stream_decode_bytes(int32_t B, int64_t max_words);
+int dagr_stream_decode_reset(void *state, size_t state_bytes, int32_t B, int64_t max_words, void *stream);
+int dagr_stream_decode(void *state, size_t state_bytes, int32_t B, int64_t max_words, int32_t format, int32_t sensor_w,
+                       int32_t sensor_h, const void *words, const int64_t *word_end /* [B], device */, int64_t n_words,
+                       const int64_t *t_base /* [B], device, or NULL */, int64_t max_out, int16_t *xy_out, int64_t *t_out,
+                       int8_t *p_out, int32_t *batch_out, int32_t *n_out,
+                       int64_t *lane_counts /* [B, 4], device, accumulated; may be NULL */, int32_t *status, void *stream);
+int dagr_stream_stage_dev_clock(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B, int64_t capacity,
+                                const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new, const int32_t *batch_new,
+                                const int32_t *n_new_dev, int64_t n_new_max, const int64_t *t_clock, const void *batch_clock,
+                                int32_t clock_is_int64, const int32_t *n_clock_dev, int64_t n_clock,
+                                const int64_t *t_now /* [B] or NULL */, int64_t window_us, float *pos_out, float *feat_out,
+                                int32_t *batch_out, int32_t *n_dev, int32_t *lane_count /* [B] */, int32_t *status,
+                                void *stream);
+int dagr_stream_stage_dev_clock_capped(const dagr_graph_desc *desc, void *workspace, void *state, int32_t B,
+                                       int64_t capacity, const int16_t *xy_new, const int64_t *t_new, const int8_t *p_new,
+                                       const int32_t *batch_new, const int32_t *n_new_dev, int64_t n_new_max,
+                                       const int64_t *t_clock, const void *batch_clock, int32_t clock_is_int64,
+                                       const int32_t *n_clock_dev, int64_t n_clock, const int64_t *t_now /* [B] or NULL */,
+                                       int64_t window_us, int64_t max_lane_events,
+                                       int64_t *lane_dropped /* [B], device, accumulated; may be NULL */, float *pos_out,
+                                       float *feat_out, int32_t *batch_out, int32_t *n_dev, int32_t *lane_count /* [B] */,
+                                       int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------ *
  * Event stream frames: raw sensor frames, prepared on the device

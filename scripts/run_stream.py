@@ -46,7 +46,13 @@ coasted track-steps is printed with the summary.
 track that no confident detection matched, and never start one, so a score that dips for a few steps does not cost the track
 its id.  ``--track_low_iou I`` (needs ``--track_low_score``) gives that round an IoU threshold of its own (default:
 ``--track_iou``).  0.1 for ``L`` and 0.5 for ``--track_min_score`` are ByteTrack's conventions, not measured optima.  The
-number of rescued matches is printed with the summary."""
+number of rescued matches is printed with the summary.
+
+``--decode evt2|evt3``: the step's events are encoded as camera words (``dagr.data.evt.encode_events``, an encoder for
+synthetic sources, not a model of any camera) and pushed through ``step_words``; the stream decodes them on the device
+(``dagr.streaming``: ``EventStream(decode=)``) in front of the filter, the front and the window.  ``--max_decoded N`` sizes
+the decoded events' buffers (default: the worst case of every push).  The decoder's counters are printed with the
+summary.  Composes with ``--downsample``, ``--denoise_us``, ``--max_lane_events`` and ``--track``."""
 import time
 import types
 
@@ -54,6 +60,7 @@ import numpy as np
 import torch
 
 import _common as C
+from dagr.data.evt import encode_events
 from dagr.streaming import EventStream, _motion_options, _rescue_options, _track_options
 from dagr.utils.buffers import DETECTION_DTYPE, detections_to_records
 from dagr.utils.logging import set_up_logging_directory
@@ -76,6 +83,10 @@ def stream_options(p):
                    "neighbours saw an event in the last D microseconds")
     g.add_argument("--refractory_us", type=int, default=None, help="noise filter: drop an event whose own pixel saw an "
                    "event less than R microseconds ago")
+    g.add_argument("--decode", type=str, default=None, choices=("evt2", "evt3"), help="encode the step's events as camera "
+                   "words of this format and let the stream decode them on the device")
+    g.add_argument("--max_decoded", type=int, default=None, help="with --decode: rows of the decoded events' buffers "
+                   "(default: the worst case of every push)")
     g.add_argument("--track", action="store_true", help="give every detection a track id, on the device")
     g.add_argument("--track_iou", type=float, default=None, help="with --track: smallest IoU that continues a track "
                    "(default 0.3)")
@@ -248,12 +259,16 @@ def play(a, model, source, dev):
         h_f, w_f = np.asarray(source.image(0)).shape[:2]
         raw_size = (int(w_f), int(h_f))
     cap = getattr(a, "max_lane_events", None)
+    decode = getattr(a, "decode", None)
     stream = EventStream(model, window_us=a.window_us or None, downsample=a.downsample, sensor_size=sensor_size(a),
                          frame_size=raw_size, frame_bgr=True, max_lane_events=cap,
                          denoise_us=getattr(a, "denoise_us", None), refractory_us=getattr(a, "refractory_us", None),
-                         track=track_options(a), motion=motion_options(a), rescue=rescue_options(a))
+                         track=track_options(a), motion=motion_options(a), rescue=rescue_options(a),
+                         decode=decode, max_decoded=getattr(a, "max_decoded", None),
+                         t_base=int(source.t_range()[0]) if decode else None)      # (the words' times start at the sequence's)
     t0, t1 = source.t_range()
     out, last_frame = [], None
+    t_encoded = None                       # where the encoder of --decode stands (times relative to the sequence's start)
     a.stream_coasting = [] if stream.motion is not None else None      # per step the tracks it did not see
     for t_step in range(int(t0) + a.step_us, int(t1) + 1, a.step_us):
         ev = source.events(t_step - a.step_us, t_step)
@@ -268,14 +283,22 @@ def play(a, model, source, dev):
             if i != last_frame:
                 image, last_frame = frame, i
         # every event of the step is older than t_step, the instant the detections are for
-        det = stream.step(xy, np.asarray(ev["t"], np.int64), np.asarray(ev["p"], np.int8), t_now=t_step, image=image,
-                          frame=raw)
+        if stream.decode is not None:
+            t_rel = np.asarray(ev["t"], np.int64) - int(t0)
+            words = encode_events(ev["x"], ev["y"], t_rel, ev["p"], stream.decode, t_prev=t_encoded)
+            if len(t_rel):
+                t_encoded = int(t_rel[-1])
+            det = stream.step_words(words, t_now=t_step, image=image, frame=raw)
+        else:
+            det = stream.step(xy, np.asarray(ev["t"], np.int64), np.asarray(ev["p"], np.int8), t_now=t_step, image=image,
+                              frame=raw)
         out.append((t_step, det[0]))
         if stream.motion is not None:
             a.stream_coasting.append(coast_records(len(out) - 1, t_step, stream.coasting()))
     a.stream_steps = (stream.frame_steps, stream.held_steps)      # (frame bodies, held bodies) of the run
     a.stream_dropped = int(stream.dropped().sum()) if cap is not None else None
     a.stream_filtered = int(stream.filtered().sum()) if stream.state.noise is not None else None
+    a.stream_decoded = {k: int(v.sum()) for k, v in stream.decode_counts().items()} if stream.decode is not None else None
     a.stream_untracked = int(stream.untracked().sum()) if stream.track is not None else None
     a.stream_rescued = int(stream.rescued().sum()) if stream.rescue is not None else None
     return out
@@ -292,6 +315,8 @@ def main(argv=None, model_factory=None, source=None):
     if a.step_us <= 0 or a.window_us < 0 or (a.window_us == 0 and not capped):
         raise SystemExit("run_stream.py: --step_us and --window_us must be positive (--window_us 0: the model's time "
                          "window, with --max_lane_events only)")
+    if getattr(a, "max_decoded", None) is not None and (getattr(a, "decode", None) is None or a.max_decoded < 1):
+        raise SystemExit("run_stream.py: --max_decoded needs --decode and must be positive")
     tracking = track_options(a) is not None
     moving = motion_options(a) is not None
     rescue_options(a)                      # (refusals in front of the model)
@@ -332,6 +357,10 @@ def main(argv=None, model_factory=None, source=None):
             window += f" capped at {a.max_lane_events} events ({a.stream_dropped} dropped by the cap)"
         if a.stream_filtered is not None:
             window += f" behind the noise filter ({a.stream_filtered} events filtered)"
+        if a.stream_decoded is not None:
+            c = a.stream_decoded
+            window += (f" decoded from {a.decode} words ({c['decoded']} events decoded, {c['unsynced']} unsynced, "
+                       f"{c['outside']} outside, {c['skipped']} words skipped)")
         tracked = ""
         if tracking:
             np.save(out_dir / f"tracks_{a.sequence}.npy", trk)
