@@ -387,6 +387,26 @@ def _basicblock_forward(blk, x):
     return _add_relu_(blk.conv2(out), identity)
 
 
+def flicker_map_bytes(B, sensor_w, sensor_h):
+    """The bytes at the front of a ``dagr_stream_flicker`` state that hold its per-pixel maps (include/dagr_hip.h): t_edge
+    and t_pass, int64, each rounded up to 256 bytes, then the packed int32 words."""
+    pixels = B * sensor_w * sensor_h
+    return 2 * (-(-8 * pixels // 256) * 256) + 4 * pixels
+
+
+def flicker_maps_from_state(state, B, sensor_w, sensor_h):
+    """The per-pixel maps of a ``dagr_stream_flicker`` state (a uint8 device tensor) unpacked into the named arrays of
+    ``dagr.streaming.flicker_definition``, each ``[B, sensor_h, sensor_w]`` (copies; synchronises)."""
+    pixels, shape = B * sensor_w * sensor_h, (B, sensor_h, sensor_w)
+    stride = -(-8 * pixels // 256) * 256
+    t_edge = state[:8 * pixels].view(torch.int64).cpu().numpy().reshape(shape)
+    t_pass = state[stride:stride + 8 * pixels].view(torch.int64).cpu().numpy().reshape(shape)
+    word = state[2 * stride:2 * stride + 4 * pixels].view(torch.int32).cpu().numpy().reshape(shape)
+    polarity = np.array([0, 1, -1, 0], np.int8)         # a polarity field: 0 none yet, 1 +1, 2 -1
+    return dict(t_edge=t_edge, last_p=polarity[(word >> 9) & 3], count=(word & 0xff).astype(np.int32),
+                blocking=((word >> 8) & 1).astype(bool), t_pass=t_pass, p_pass=polarity[(word >> 11) & 3])
+
+
 class StreamState:
     """Device-side state of one event stream (``dagr_stream_stage``): the raw events of the running window in two sets
     written alternately, the lanes' bounds and reference instants, the stream's status word, the per-lane counts of the
@@ -402,6 +422,10 @@ class StreamState:
     A filtering stream (``enable_denoise``) owns the noise filter's state (``dagr_stream_denoise``): the lanes' int64 stamp
     maps and the scratch of a largest push, grown with the push size, the survivors' buffers, and ``lane_filtered``, which
     accumulates on the device what the filter removed.  Its bound counts the UNFILTERED events pushed.
+
+    A stream with the anti-flicker / trail filters (``enable_flicker``) owns their state (``dagr_stream_flicker``): the
+    lanes' per-pixel maps and the scratch of a largest push, grown with the push size, the survivors' buffers, and
+    ``lane_suppressed`` int64 [2, B], what the flicker and the trail stage removed.  It runs in front of the noise filter.
 
     A decoding stream (``enable_decode``) owns the decoder's state (``dagr_stream_decode``): the lanes' decoder states and
     the scratch of a largest push of words, the decoded events' buffers, and ``lane_decoded``, the cumulative counters.  The
@@ -439,6 +463,8 @@ class StreamState:
         self.front_state, self.front_cap, self.front_out = None, 0, None
         self.noise = None                               # (W_in, H_in, denoise_us or 0, refractory_us or 0) of a filtering stream
         self.noise_state, self.noise_cap, self.noise_out, self.lane_filtered = None, 0, None, None
+        self.flick = None                               # (W_in, H_in, min_period, max_period, start, stop, max_count, trail_us)
+        self.flick_state, self.flick_cap, self.flick_out, self.lane_suppressed = None, 0, None, None
         self.words = None                               # (format, W_in, H_in, max_decoded or None) of a decoding stream
         self.words_state, self.words_cap, self.words_out, self.lane_decoded = None, 0, None, None
         self.track = None                               # the options of a tracking stream (dagr.streaming._track_options)
@@ -620,6 +646,75 @@ class StreamState:
         sensor_w, sensor_h = self.noise[:2]
         return self.noise_state[:8 * self.B * sensor_w * sensor_h].view(torch.int64).view(self.B, sensor_h, sensor_w).cpu().numpy()
 
+    # ------------------------------------------------------------------------------------ flicker and trails
+    def enable_flicker(self, sensor_w, sensor_h, flicker=None, trail_us=None):
+        """Pushes go through ``dagr_stream_flicker`` in front of the noise filter: per-pixel state over a ``sensor_w x
+        sensor_h`` sensor per lane; ``flicker`` as ``dagr.streaming._flicker_options`` returns it or None (off),
+        ``trail_us`` positive or None (off; not both)."""
+        if flicker is None and trail_us is None:
+            raise ValueError("enable_flicker: flicker and trail_us are both None")
+        periods, thresholds = (0, 0), (0, 0, 0)
+        if flicker is not None:
+            from .streaming import flicker_periods
+            periods = flicker_periods(flicker)
+            thresholds = (int(flicker["start"]), int(flicker["stop"]), int(flicker["max_count"]))
+        self.flick = (int(sensor_w), int(sensor_h), *periods, *thresholds, int(trail_us or 0))
+        self.flick_state, self.flick_cap, self.flick_out = None, 0, None
+        self.lane_suppressed = torch.zeros((2, self.B), dtype=torch.int64, device=self.device)      # flicker, trail
+        self.grow_flicker(4096)
+
+    def grow_flicker(self, n):
+        """Scratch and survivors' buffers for pushes of ``n`` events; the per-pixel maps are carried over."""
+        if n <= self.flick_cap:
+            return
+        L, stream = _lib.lib(), _lib.cur_stream(self.device)
+        sensor_w, sensor_h = self.flick[:2]
+        nbytes = L.dagr_stream_flicker_bytes(self.B, sensor_w, sensor_h, n)
+        if nbytes == 0:
+            raise RuntimeError(f"dagr_stream_flicker_bytes({self.B}, {sensor_w}, {sensor_h}, {n}): out of range")
+        new = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _lib.check(L.dagr_stream_flicker_reset(_lib.ptr(new), nbytes, self.B, sensor_w, sensor_h, n, stream),
+                   "stream_flicker_reset")
+        if self.flick_state is not None:
+            maps = flicker_map_bytes(self.B, sensor_w, sensor_h)
+            new[:maps].copy_(self.flick_state[:maps])
+        self.flick_state, self.flick_cap = new, n
+        dev = self.device
+        self.flick_out = (torch.empty((n, 2), dtype=torch.int16, device=dev), torch.empty((n,), dtype=torch.int64, device=dev),
+                          torch.empty((n,), dtype=torch.int8, device=dev), torch.empty((n,), dtype=torch.int32, device=dev),
+                          torch.zeros((1,), dtype=torch.int32, device=dev))
+
+    def flicker(self, xy, t, p, batch):
+        """``dagr_stream_flicker`` on a push: ``(xy, t, p, batch int32, count int32[1])`` of the survivors, on the device,
+        valid until the next push; rows from the count up to the push's size are lane-less (lane -1 at pixel (0, 0))."""
+        n = int(t.shape[0])
+        if n > self.flick_cap:
+            self.grow_flicker(max(n, 2 * self.flick_cap))
+        sensor_w, sensor_h, *rule = self.flick
+        P, o = _lib.ptr, self.flick_out
+        _lib.check(_lib.lib().dagr_stream_flicker(
+            P(self.flick_state), self.flick_state.numel(), self.B, self.flick_cap, sensor_w, sensor_h, *rule,
+            P(xy), P(t), P(p), P(batch), 1 if batch.dtype == torch.int64 else 0, n, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]),
+            P(self.lane_suppressed[0]), P(self.lane_suppressed[1]), P(self.status), _lib.cur_stream(self.device)),
+            "stream_flicker")
+        return o
+
+    def suppressed(self):
+        """Per-lane events the flicker stage and the trail stage have removed, ``(int64 [B], int64 [B])``; zeros without the
+        filter (synchronises)."""
+        if self.flick is None:
+            torch.cuda.current_stream(self.device).synchronize()
+            return np.zeros((self.B,), np.int64), np.zeros((self.B,), np.int64)
+        both = self.lane_suppressed.cpu().numpy()
+        return both[0].copy(), both[1].copy()
+
+    def flicker_maps(self):
+        """The per-pixel state as ``dagr.streaming.flicker_definition`` names it (``flicker_maps_from_state``; copies;
+        synchronises)."""
+        if self.flick is None:
+            raise RuntimeError("this stream has no flicker / trail filter (flicker / trail_us): it has no per-pixel state")
+        return flicker_maps_from_state(self.flick_state, self.B, *self.flick[:2])
+
     # ------------------------------------------------------------------------------------ camera words
     def enable_decode(self, format, sensor_w, sensor_h, max_decoded=None, t_base=None):
         """Pushes carry camera words, which ``dagr_stream_decode`` turns into events first: ``format`` is
@@ -763,6 +858,11 @@ class StreamState:
                                                             self.noise[0], self.noise[1], self.noise_cap,
                                                             _lib.cur_stream(self.device)), "stream_denoise_reset")
             self.lane_filtered.zero_()
+        if self.flick_state is not None:
+            _lib.check(_lib.lib().dagr_stream_flicker_reset(_lib.ptr(self.flick_state), self.flick_state.numel(), self.B,
+                                                            self.flick[0], self.flick[1], self.flick_cap,
+                                                            _lib.cur_stream(self.device)), "stream_flicker_reset")
+            self.lane_suppressed.zero_()
         if self.track_state is not None:
             self._reset_track()
         self.status.zero_()
@@ -2071,6 +2171,9 @@ class WindowEngine:
         windows never exceed ``B * N``, which the buffers meet once -- no growth and no re-capture after its first step.
         A filtering stream (``st.noise``) runs ``dagr_stream_denoise`` on the push before anything else and stages what is
         left through the ``_dev`` entries, with the unfiltered push as the clock.
+        A stream with the flicker / trail filters (``st.flick``) runs ``dagr_stream_flicker`` in front of that -- behind the
+        decoder, before the noise filter, the front and the stage, each of which takes all rows handed on, those behind the
+        count being lane-less.
         A decoding stream (``st.words``) takes ``words`` (the camera's words as int16 / int32 bit patterns) and ``word_end``
         (int64 [B], the cumulative end of every lane's run) in place of the events: ``dagr_stream_decode`` first, then the
         filter and the front when enabled -- on all ``max_out`` rows, those behind the decoder's count being lane-less --,
@@ -2139,7 +2242,8 @@ class WindowEngine:
         cap_args = () if N is None else (N, P(st.lane_dropped))
         if decoding:                # camera words: decode, then the fronts on all rows, then the stage with the decoded push as
             sensor = (self.W, self.H) if st.front is None else st.front[2:4]       # the clock, its length on the device
-            if st.words[1:3] != sensor or (st.noise is not None and st.noise[:2] != sensor):
+            if st.words[1:3] != sensor or (st.noise is not None and st.noise[:2] != sensor) or \
+                    (st.flick is not None and st.flick[:2] != sensor):
                 raise RuntimeError(f"the stream decodes a {st.words[1]} x {st.words[2]} sensor, its fronts take "
                                    f"{sensor[0]} x {sensor[1]} pixels")
             if st.front is not None and st.front[4:] != (self.W, self.H):
@@ -2148,20 +2252,27 @@ class WindowEngine:
             c_xy, c_t, c_p, c_batch, c_n = st.decode(words, word_end)
             rows = int(c_t.shape[0])
             s_xy, s_t, s_p, s_batch, s_n = c_xy, c_t, c_p, c_batch, c_n
+            if st.flick is not None:
+                s_xy, s_t, s_p, s_batch, s_n = st.flicker(s_xy, s_t, s_p, s_batch)
             if st.noise is not None:
-                s_xy, s_t, s_p, s_batch, s_n = st.denoise(s_xy, s_t, s_p, s_batch)
+                s_xy, s_t, s_p, s_batch, s_n = st.denoise(s_xy[:rows], s_t[:rows], s_p[:rows], s_batch[:rows])
             if st.front is not None:
                 s_xy, s_t, s_p, s_batch, s_n = st.downsample(s_xy[:rows], s_t[:rows], s_p[:rows], s_batch[:rows])
             stage = L.dagr_stream_stage_dev_clock if N is None else L.dagr_stream_stage_dev_clock_capped
             _lib.check(stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(s_xy), P(s_t), P(s_p),
                              P(s_batch), P(s_n), rows, P(c_t), P(c_batch), 0, P(c_n), rows, P(t_now), st.window_us, *cap_args,
                              *outputs), "stream_stage_dev_clock")
-        elif st.noise is not None:    # the noise filter first; the unfiltered push stays the clock
+        elif st.noise is not None or st.flick is not None:    # the filters first; the unfiltered push stays the clock
             sensor = (self.W, self.H) if st.front is None else st.front[2:4]
-            if st.noise[:2] != sensor:
-                raise RuntimeError(f"the stream filters a {st.noise[0]} x {st.noise[1]} sensor, its pushes carry "
-                                   f"{sensor[0]} x {sensor[1]} pixels")
-            s_xy, s_t, s_p, s_batch, s_n = st.denoise(xy, t, p, batch)
+            for filt in (st.flick, st.noise):
+                if filt is not None and filt[:2] != sensor:
+                    raise RuntimeError(f"the stream filters a {filt[0]} x {filt[1]} sensor, its pushes carry "
+                                       f"{sensor[0]} x {sensor[1]} pixels")
+            s_xy, s_t, s_p, s_batch = xy, t, p, batch
+            if st.flick is not None:  # flicker / trail in front of the noise filter: flicker would support noise there
+                s_xy, s_t, s_p, s_batch, s_n = st.flicker(s_xy, s_t, s_p, s_batch)
+            if st.noise is not None:  # all n_new rows, of which those behind the count in front are lane-less
+                s_xy, s_t, s_p, s_batch, s_n = st.denoise(s_xy[:n_new], s_t[:n_new], s_p[:n_new], s_batch[:n_new])
             if st.front is not None:
                 if st.front[4:] != (self.W, self.H):
                     raise RuntimeError(f"the stream downsamples to {st.front[4]} x {st.front[5]}, the engine runs "

@@ -77,6 +77,48 @@ order checks run on the unfiltered push, and the lane's newest event -- ``t_last
 its newest UNFILTERED event.  ``max_lane_events`` counts what reaches the window.  ``filtered[b]`` (int64, cumulative, zero
 after construction and after ``reset()``) counts the events inside the sensor that the filter removed.
 
+Anti-flicker and trail filters (``flicker=`` and / or ``trail_us=``; with both ``None`` nothing changes anywhere): two
+per-pixel state machines on what a push carries, in front of the noise filter -- flicker events are dense and spatially
+coherent, so they would otherwise count as support for the noise beside them.  The order of a step is decode, flicker /
+trail, noise filter, ``downsample=``, window.  Mains- and PWM-driven lights make their pixels emit ON / OFF bursts at 100 /
+120 Hz and above; an edge crossing a pixel fires a burst of same-polarity events of which the first carries the
+information.  The rule below is THIS PROJECT'S statement of these two well-known filters: it is not a vendor's algorithm and
+agreement with any vendor's filter is not claimed; no real camera data was at hand, the tests and measurements use
+synthetic flicker; the defaults are conventions, not measured optima.  ``flicker_definition`` states the rule once in
+numpy and ``dagr_stream_flicker`` repeats it.
+
+``flicker`` is ``None``, ``True`` (the defaults) or a dict of ints ``min_hz``, ``max_hz``, ``start``, ``stop``, ``max_count``
+(defaults 50, 500, 4, 1, 7) with ``1 <= min_hz <= max_hz <= 1000000`` and ``0 <= stop < start <= max_count <= 255``;
+``min_period = -(-1000000 // max_hz)`` and ``max_period = 1000000 // min_hz`` in integer microseconds.  ``trail_us`` is
+``None`` or a positive int.  Every lane owns, over ``[H_in, W_in]`` and carried from push to push: ``t_edge`` int64
+(initially never), ``last_p`` int8 (0), ``count`` int32 (0), ``blocking`` bool (False), ``t_pass`` int64 (never), ``p_pass``
+int8 (0); every field is at its initial value after construction and after ``reset()``.  A lane's events are taken in
+arrival order; two events with one timestamp are two events, and the second sees the first.  An event outside
+``[0, W_in) x [0, H_in)`` or with a lane outside ``[0, B)`` is skipped: outcome -1, no state touched, not counted (the
+lane-less rows the decoder leaves behind its count fall under this); outside the sensor on a valid lane it raises the
+status bit of value 16.  For every other event ``(t, p)``, with ``s = +1 if p > 0 else -1``:
+
+Flicker stage (``flicker`` on):
+
+1. stale: if ``t_edge != never`` and ``t - t_edge > max_period``, ``count = 0``;
+2. edge: the event is an edge iff ``s > 0 and last_p < 0``.  On an edge with ``t_edge != never`` and ``d = t - t_edge``:
+   ``count = min(count + 1, max_count)`` if ``min_period <= d <= max_period``, ``count = max(count - 1, 0)`` if
+   ``d < min_period`` (``d > max_period`` was step 1).  On every edge ``t_edge = t``;
+3. hysteresis: if ``count >= start``, ``blocking = True``; else if ``count <= stop``, ``blocking = False``;
+4. ``last_p = s``;
+5. the event passes iff ``not blocking``; otherwise its outcome is 1 and it does not reach the trail stage.
+
+Trail stage (``trail_us`` on), for the events that passed the flicker stage, or for all when that stage is off:
+
+1. ``trail = (p_pass == s) and (t - t_pass < trail_us)`` -- the timestamp of a never state is not subtracted;
+2. ``t_pass = t`` and ``p_pass = s``, whether or not the event trailed: a continuous burst stays suppressed;
+3. if ``trail``, the outcome is 2.
+
+Anything left has outcome 0 and is kept.  All arithmetic is int64; there are no floats anywhere.  The same event sequence
+in any chunking into pushes leaves the same outcomes and the same state.  The survivors keep the order of the push.  The
+clock stays the sensor's, as with the noise filter: order checks, ``t_last`` and ``t_ref`` use the unfiltered (or decoded)
+push.  ``suppressed()`` returns ``(flicker[B], trail[B])``, int64, cumulative, zero after construction and ``reset()``.
+
 Frames (``--use_image`` models): every lane has a frame in force, the last one a step gave it -- as the model's image
 (``image=``, fp32 [B, 3, H, W]) or as a raw sensor frame (``frame=``, uint8 [H_f, W_f, 3], which ``dagr_stream_frame``
 prepares on the device; ``frame_definition`` below states what that is).  A step's result is what ``model(..., reset=True)``
@@ -170,7 +212,7 @@ considers every live unmatched track, not only those seen in the step before.  W
 
 Camera words (``decode="evt3"`` or ``"evt2"``): an event camera delivers words, not arrays.  A decoding stream takes the
 camera's words (``step_words`` / ``step_words_device``) and decodes them on the device (``dagr_stream_decode``) in front of
-everything above: decode, then the noise filter, then ``downsample=``, then the window.  The two formats are stated here as
+everything above: decode, then the flicker / trail filters, then the noise filter, then ``downsample=``, then the window.  The two formats are stated here as
 the vendor's public descriptions are recalled; no specification document, camera file or third-party decoder was at hand,
 so THIS statement is the definition, ``DecodeDefinition`` below is its sequential loop and the yardstick of the kernels, and
 agreement with a real camera file is not demonstrated.
@@ -337,6 +379,93 @@ def denoise_definition(last_t, x, y, t, batch, denoise_us=None, refractory_us=No
         keep[i] = supported and not refractory
         lane[yi, xi] = ti
     return keep
+
+
+FLICKER_DEFAULTS = dict(min_hz=50, max_hz=500, start=4, stop=1, max_count=7)       # conventions, not measured optima
+FLICKER_STATE = (("t_edge", np.int64, NEVER), ("last_p", np.int8, 0), ("count", np.int32, 0), ("blocking", np.bool_, False),
+                 ("t_pass", np.int64, NEVER), ("p_pass", np.int8, 0))
+
+
+def flicker_state(batch_size, w_in, h_in):
+    """The initial state of ``flicker_definition``: a dict of one ``[B, H_in, W_in]`` array per field of ``FLICKER_STATE``."""
+    return {name: np.full((int(batch_size), int(h_in), int(w_in)), first, dtype) for name, dtype, first in FLICKER_STATE}
+
+
+def _flicker_options(flicker, trail_us, batch_size, w_in, h_in, who):
+    """``(flicker dict or None, trail_us or None)`` of a stream over a ``w_in x h_in`` sensor, checked: ``flicker`` is None
+    (off), True (the defaults) or a dict of ints ``min_hz``, ``max_hz``, ``start``, ``stop``, ``max_count``; ``trail_us`` is
+    None (off) or a positive int.  Refusals by name."""
+    opt = _options(flicker, "flicker", FLICKER_DEFAULTS, who)
+    if opt is not None:
+        for name, v in opt.items():
+            if not _is_int(v):
+                raise ValueError(f"{who}: flicker {name} = {v!r} must be an int")
+        opt = {name: int(v) for name, v in opt.items()}
+        if not 1 <= opt["min_hz"] <= opt["max_hz"] <= 1000000:
+            raise ValueError(f"{who}: flicker min_hz = {opt['min_hz']} and max_hz = {opt['max_hz']} must satisfy "
+                             "1 <= min_hz <= max_hz <= 1000000")
+        if not 0 <= opt["stop"] < opt["start"] <= opt["max_count"] <= 255:
+            raise ValueError(f"{who}: flicker stop = {opt['stop']}, start = {opt['start']} and max_count = "
+                             f"{opt['max_count']} must satisfy 0 <= stop < start <= max_count <= 255")
+    if trail_us is not None and (not _is_int(trail_us) or int(trail_us) < 1):
+        raise ValueError(f"{who}: trail_us = {trail_us!r} must be a positive int of microseconds (or None: off)")
+    trail_us = None if trail_us is None else int(trail_us)
+    if (opt is not None or trail_us is not None) and int(batch_size) * int(w_in) * int(h_in) >= 1 << 31:
+        raise ValueError(f"{who}: batch_size * W_in * H_in = {int(batch_size) * int(w_in) * int(h_in)} pixel states are "
+                         f"outside the flicker / trail filter's range (below {1 << 31})")
+    return opt, trail_us
+
+
+def flicker_periods(opt):
+    """``(min_period, max_period)`` in integer microseconds of checked flicker options: the edge periods that count."""
+    return -(-1000000 // opt["max_hz"]), 1000000 // opt["min_hz"]
+
+
+def flicker_definition(state, x, y, t, p, batch, flicker=None, trail_us=None):
+    """The anti-flicker and trail filters of the module docstring on one push, stated once: ``state`` (``flicker_state``)
+    is read and updated in place, the result is an int8 outcome per event -- 0 kept, 1 removed by the flicker stage, 2
+    removed by the trail stage, -1 not an event of this sensor (outside it, or a lane outside ``[0, B)``: no state is
+    touched).  The yardstick of ``dagr_stream_flicker``; nothing on the device path calls it."""
+    B, h_in, w_in = state["t_edge"].shape
+    opt, trail_us = _flicker_options(flicker, trail_us, B, w_in, h_in, "flicker_definition")
+    if opt is not None:
+        min_period, max_period = flicker_periods(opt)
+    t_edge, last_p, count, blocking = state["t_edge"], state["last_p"], state["count"], state["blocking"]
+    t_pass, p_pass = state["t_pass"], state["p_pass"]
+    out = np.full(len(t), -1, np.int8)
+    for i in range(len(t)):
+        xi, yi, ti, b = int(x[i]), int(y[i]), int(t[i]), int(batch[i])
+        if not (0 <= xi < w_in and 0 <= yi < h_in and 0 <= b < B):
+            continue
+        at = (b, yi, xi)
+        s = 1 if int(p[i]) > 0 else -1
+        out[i] = 0
+        if opt is not None:
+            edge_t = int(t_edge[at])
+            if edge_t != NEVER and ti - edge_t > max_period:               # stale
+                count[at] = 0
+            if s > 0 and last_p[at] < 0:                                    # an OFF -> ON edge
+                if edge_t != NEVER:
+                    d = ti - edge_t
+                    if min_period <= d <= max_period:
+                        count[at] = min(int(count[at]) + 1, opt["max_count"])
+                    elif d < min_period:
+                        count[at] = max(int(count[at]) - 1, 0)
+                t_edge[at] = ti
+            if count[at] >= opt["start"]:
+                blocking[at] = True
+            elif count[at] <= opt["stop"]:
+                blocking[at] = False
+            last_p[at] = s
+            if blocking[at]:
+                out[i] = 1
+                continue
+        if trail_us is not None:
+            trail = int(p_pass[at]) == s and ti - int(t_pass[at]) < trail_us    # (p_pass == s: t_pass is not never)
+            t_pass[at], p_pass[at] = ti, s
+            if trail:
+                out[i] = 2
+    return out
 
 
 DAGR_TRACK_MAX_TRACKS = DEFINES["DAGR_TRACK_MAX_TRACKS"]       # include/dagr_hip.h states them; the binding reads it
@@ -694,7 +823,7 @@ class StreamDefinition:
     pushes raise ``ValueError`` (the device path reports them in its status word instead)."""
 
     def __init__(self, batch_size, width, height, time_window=1000000, window_us=50000, downsample=None, sensor_size=None,
-                 max_lane_events=None, denoise_us=None, refractory_us=None):
+                 max_lane_events=None, denoise_us=None, refractory_us=None, flicker=None, trail_us=None):
         self.B, self.W, self.H = int(batch_size), int(width), int(height)
         self.time_window = int(time_window)
         self.window_us, self.max_lane_events = _window_and_cap(window_us, max_lane_events, time_window, batch_size,
@@ -706,6 +835,8 @@ class StreamDefinition:
         self.denoise_us, self.refractory_us = _noise_options(denoise_us, refractory_us, self.B, *self.sensor,
                                                              "StreamDefinition")
         self.noise = self.denoise_us is not None or self.refractory_us is not None
+        self.flicker, self.trail_us = _flicker_options(flicker, trail_us, self.B, *self.sensor, "StreamDefinition")
+        self.flick = self.flicker is not None or self.trail_us is not None
         self.reset()
 
     def reset(self):
@@ -715,6 +846,9 @@ class StreamDefinition:
         self.t_last = [None] * self.B
         self.dropped = np.zeros(self.B, np.int64)
         self.filtered = np.zeros(self.B, np.int64)
+        self.suppressed = (np.zeros(self.B, np.int64), np.zeros(self.B, np.int64))      # by the flicker / the trail stage
+        if self.flick:
+            self.flicker_state = flicker_state(self.B, *self.sensor)
         if self.noise:
             self.last_t = np.full((self.B, self.sensor[1], self.sensor[0]), NEVER, np.int64)
         if self.front is not None:
@@ -748,7 +882,7 @@ class StreamDefinition:
             raise ValueError("batch is not sorted or is outside [0, batch_size)")
         if t_now is not None:
             t_now = np.broadcast_to(np.asarray(t_now, np.int64).reshape(-1), (self.B,))
-        if (self.front is not None or self.noise) and \
+        if (self.front is not None or self.noise or self.flick) and \
                 np.any((x < 0) | (x >= self.sensor[0]) | (y < 0) | (y >= self.sensor[1])):
             raise ValueError("a raw event is outside the sensor")
         parts, refs = [], []
@@ -763,7 +897,13 @@ class StreamDefinition:
                 raise ValueError(f"lane {b}: t_now is behind the lane's newest event or behind its previous t_ref")
             parts.append(newest)
             refs.append(ref)
-        if self.noise:                                    # the filter comes first; the clock above is the unfiltered push's
+        if self.flick:                                    # flicker / trail first: flicker would support noise below
+            out = flicker_definition(self.flicker_state, x, y, t, p, batch, self.flicker, self.trail_us)
+            for stage, removed in enumerate(self.suppressed, 1):
+                removed += np.bincount(batch[out == stage], minlength=self.B)
+            keep = out == 0
+            x, y, t, p, batch = x[keep], y[keep], t[keep], p[keep], batch[keep]
+        if self.noise:                                    # then the noise filter; the clock above is the unfiltered push's
             keep = denoise_definition(self.last_t, x, y, t, batch, self.denoise_us, self.refractory_us)
             self.filtered += np.bincount(batch[~keep], minlength=self.B)
             x, y, t, p, batch = x[keep], y[keep], t[keep], p[keep], batch[keep]
@@ -967,6 +1107,14 @@ class EventStream:
     background activity and hot pixels from every push on the device, before anything else (module docstring);
     ``filtered()`` counts what it removed, ``last_stamps()`` reads the stamp maps back.  A stream built without them issues
     exactly the launches it issues without the filter.
+    ``flicker`` (``None``: off, ``True``: the defaults, or a dict of ints ``min_hz``, ``max_hz``, ``start``, ``stop``,
+    ``max_count``) and ``trail_us`` (a positive int of microseconds, ``None``: off): ``dagr_stream_flicker`` removes the
+    events of pixels that flicker at a steady rate between ``min_hz`` and ``max_hz``, and the same-polarity events that
+    trail another by less than ``trail_us``, from every push on the device -- behind the decoder, in front of the noise
+    filter (module docstring: this project's statement of two well-known filters, not a vendor's algorithm; the defaults
+    are conventions, not measured optima; tested on synthetic flicker only).  ``suppressed()`` counts what either stage
+    removed, ``flicker_state()`` reads the per-pixel state back.  A stream built without them makes exactly the library
+    calls it makes without the filter.
     ``track`` (``None``: off, ``True``: the defaults, or a dict of ``iou``, ``max_age_us``, ``min_score``, ``max_tracks``):
     every step ends with ``dagr_stream_track``, one more launch and no host wait, which gives every detection the id of
     the track it continues (module docstring).  ``track_ids`` / ``track_hits`` are the step's device tensors, ``step()``
@@ -1010,7 +1158,7 @@ class EventStream:
 
     def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
                  max_lane_events=None, denoise_us=None, refractory_us=None, track=None, motion=None, rescue=None,
-                 decode=None, max_decoded=None, t_base=None):
+                 decode=None, max_decoded=None, t_base=None, flicker=None, trail_us=None):
         import torch
         self.model = model
         self.track = _track_options(track, "EventStream")
@@ -1046,6 +1194,7 @@ class EventStream:
         elif sensor_size is not None:
             raise ValueError("EventStream: sensor_size is given without downsample")
         self.denoise_us, self.refractory_us = _noise_options(denoise_us, refractory_us, eng.B, w_in, h_in, "EventStream")
+        self.flicker, self.trail_us = _flicker_options(flicker, trail_us, eng.B, w_in, h_in, "EventStream")
         self.decode, self.max_decoded = None, None
         if decode is not None:
             self.decode, self.max_decoded = _decode_options(decode, max_decoded, w_in, h_in, "EventStream")
@@ -1058,6 +1207,8 @@ class EventStream:
             self.state.enable_front(fx, fy, w_in, h_in, eng.W, eng.H)
         if self.denoise_us is not None or self.refractory_us is not None:
             self.state.enable_denoise(w_in, h_in, self.denoise_us, self.refractory_us)
+        if self.flicker is not None or self.trail_us is not None:
+            self.state.enable_flicker(w_in, h_in, self.flicker, self.trail_us)
         if self.track is not None:
             self.state.enable_track(self.track, motion=self.motion, rescue=self.rescue)
         self._zeros = None
@@ -1330,6 +1481,17 @@ class EventStream:
         synchronises)."""
         return self.state.last_stamps()
 
+    def suppressed(self):
+        """Events per lane the flicker stage and the trail stage have removed since construction / ``reset()``:
+        ``(flicker int64 [B], trail int64 [B])``, zeros for a stream without ``flicker`` / ``trail_us`` (synchronises)."""
+        return self.state.suppressed()
+
+    def flicker_state(self):
+        """The per-pixel state of the flicker / trail filters as ``flicker_definition`` names it: a dict of ``t_edge``,
+        ``last_p``, ``count``, ``blocking``, ``t_pass`` and ``p_pass`` over ``[B, H_in, W_in]``, "never" as
+        ``np.iinfo(np.int64).min`` (copies; synchronises).  Raises without ``flicker`` / ``trail_us``."""
+        return self.state.flicker_maps()
+
     def tracks(self):
         """Per lane the live tracks of a tracking stream, a ``TRACK_DTYPE`` array (``id, x1, y1, x2, y2, label, t_last,
         hits``) sorted by id (copies; synchronises).  A motion stream's arrays are ``TRACK_MOTION_DTYPE``: ``vx1, vy1, vx2,
@@ -1361,8 +1523,8 @@ class EventStream:
         return self.state.rescued()
 
     def reset(self):
-        """Empty the stream: no resident events, no reference instants, zero change maps, empty stamp maps, zero dropped and
-        filtered counts, zero decoder states and counters, a clear status word, zero step counters; no tracks, ids from 1 again, zero untracked and rescued counts.  The
+        """Empty the stream: no resident events, no reference instants, zero change maps, empty stamp maps, every pixel of
+        the flicker / trail filters in its initial state, zero dropped, filtered and suppressed counts, zero decoder states and counters, a clear status word, zero step counters; no tracks, ids from 1 again, zero untracked and rescued counts.  The
         frame in force stays, and the next step runs it through the image branch again."""
         self.state.reset()
 

@@ -49,7 +49,30 @@ def edges_window(n, width, height, seed, window_us=50000, time_window=1000000, n
     return _finish(np.concatenate([xs, xn]), np.concatenate([ys, yn]), np.concatenate([t, tn]), rng, time_window)
 
 
-def batch_windows(gen, n_per_sample, batch_size, width, height, seed, **kw):
+def flicker_events(pixels, hz, duration_us, seed, duty=0.5, events_per_half=3, spread_us=200, t0=0):
+    """Flickering pixels, as a mains- or PWM-driven light makes them: every pixel of ``pixels`` (``[(x, y), ...]``) emits
+    ``events_per_half`` ON events at the start of each period of its light (``hz``: one frequency, or one per pixel) and
+    as many OFF events ``duty`` of a period later, each burst spread over ``spread_us`` microseconds, with a phase of its
+    own.  Deterministic in ``seed``.  Returns ``x, y`` int16, ``t`` int64 (``t0 <= t <
+    t0 + duration_us``, sorted, stable in pixel order) and ``p`` int8."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    pixels = np.asarray(pixels, np.int64).reshape(-1, 2)
+    period = 1000000 // np.broadcast_to(np.asarray(hz, np.int64), (len(pixels),))
+    xs, ys, ts, ps = [], [], [], []
+    for (px, py), T in zip(pixels, period):
+        phase = int(rng.integers(0, T))
+        starts = np.arange(phase, duration_us, T, dtype=np.int64)
+        for pol, shift in ((1, 0), (-1, int(duty * T))):
+            gaps = rng.integers(0, max(1, spread_us // max(1, events_per_half)), (len(starts), events_per_half))
+            tt = (starts[:, None] + shift + np.cumsum(gaps, 1)).reshape(-1)
+            tt = tt[tt < duration_us]
+            xs.append(np.full(len(tt), px)); ys.append(np.full(len(tt), py)); ts.append(tt); ps.append(np.full(len(tt), pol))
+    x, y, t, p = (np.concatenate(v) if v else np.zeros(0, np.int64) for v in (xs, ys, ts, ps))
+    order = np.argsort(t, kind="stable")
+    return x[order].astype(np.int16), y[order].astype(np.int16), t[order].astype(np.int64) + np.int64(t0), p[order].astype(np.int8)
+
+
+def batch_windows(gen,n_per_sample, batch_size, width, height, seed, **kw):
     """Concatenate ``batch_size`` independent windows like PyG ``Batch`` collation does:
     returns x,y,t,p and ``batch`` (int64 sample index, sorted)."""
     xs, ys, ts, ps, bs = [], [], [], [], []

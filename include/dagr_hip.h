@@ -308,6 +308,68 @@ int dagr_stream_denoise(void *state, size_t state_bytes, int32_t B, int64_t max_
                         int64_t *lane_filtered /* [B], device, accumulated; may be NULL */, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------ *
+ * Event stream anti-flicker and trail filters: two per-pixel state machines, run on the device
+ *   Mains- and PWM-driven lights make their pixels emit ON / OFF bursts at a steady rate, and an edge crossing a pixel fires
+ *   a burst of same-polarity events of which the first carries the information.  dagr_stream_flicker removes both from a
+ *   push of raw events of B lanes, in front of dagr_stream_denoise / dagr_stream_downsample / dagr_stream_stage_dev, and
+ *   leaves the survivors and their count in device memory.  Three launches of its own, the project's one-launch scan and a
+ *   library radix sort, no host synchronisation, no floating point.  The rule below is this project's statement of two
+ *   well-known filters; agreement with any vendor's filter is not claimed.
+ *
+ * Every pixel of every lane carries, from push to push: t_edge int64 (never = INT64_MIN), last_p (0, +1, -1), count
+ * (0..255), blocking; t_pass int64 (never), p_pass (0, +1, -1) -- initially never / 0 / 0 / false / never / 0.  A lane's
+ * events are taken in arrival order; of two events with one timestamp the second sees the first.  An event (t, p) inside the
+ * sensor on a lane in [0, B), with s = +1 if p > 0 else -1:
+ *   flicker stage (max_period_us > 0):
+ *     1. stale: if t_edge != never and t - t_edge > max_period_us, count = 0;
+ *     2. edge iff s > 0 and last_p < 0.  On an edge with t_edge != never and d = t - t_edge: count = min(count + 1,
+ *        max_count) if min_period_us <= d <= max_period_us, count = max(count - 1, 0) if d < min_period_us.  On every
+ *        edge t_edge = t;
+ *     3. if count >= start, blocking = true; else if count <= stop, blocking = false;
+ *     4. last_p = s;
+ *     5. a blocking pixel's event is removed (outcome 1) and does not reach the trail stage;
+ *   trail stage (trail_us > 0), for what passed the flicker stage, or for every event when that stage is off:
+ *     trail = p_pass == s and t - t_pass < trail_us (a never t_pass is not subtracted); then t_pass = t and p_pass = s,
+ *     trailed or not; a trailing event is removed (outcome 2).
+ * Everything else is kept.  All arithmetic is int64.  The same sequence in any chunking into pushes leaves the same
+ * survivors and the same state.  An event outside [0, sensor_w) x [0, sensor_h) or with a lane outside [0, B) -- the
+ * lane-less rows a stage in front leaves behind its count among them -- is dropped, meets no state and is not counted; an
+ * event outside the sensor on a lane in [0, B) raises bit 4 (value 16) of `status`, the stream's status word.  The survivors
+ * keep the order of the push.
+ *
+ * state: dagr_stream_flicker_bytes(B, sensor_w, sensor_h, max_push) bytes (0: sizes out of range -- B in 1..127,
+ *        B * sensor_w * sensor_h < 2^31, max_push in 1..2^25 - 1), dagr_stream_flicker_reset before the first push, after a
+ *        change of max_push and to return every pixel to its initial state.  The per-pixel maps come first, each over
+ *        [B, sensor_h, sensor_w]: with S = 8 * B * sensor_h * sensor_w rounded up to a multiple of 256, t_edge int64 at
+ *        offset 0, t_pass int64 at offset S, and at offset 2 * S one int32 word per pixel: bits 0..7 count, bit 8
+ *        blocking, bits 9..10 last_p, bits 11..12 p_pass (a polarity field is 0: none yet, 1: +1, 2: -1).  A caller that
+ *        needs a larger max_push copies these 2 * S + 4 * B * sensor_h * sensor_w bytes into the new state after its
+ *        reset; keys, sorted order, keep flags, their prefix sums, outcomes and the sort's storage for max_push events
+ *        follow.
+ * min_period_us / max_period_us: the edge periods that count, 1 <= min <= max <= 1000000; max_period_us = 0 turns the
+ * flicker stage off (min_period_us, start, stop and max_count are then ignored).  0 <= stop < start <= max_count <= 255.
+ * trail_us > 0, or 0 for off; both stages off is an error.
+ * xy_raw int16[n_raw,2] (4-byte aligned) sensor pixels, t_raw int64[n_raw] non-decreasing inside a lane, p_raw int8[n_raw],
+ * batch_raw int32/int64[n_raw] sorted; outputs for n_raw events, none of them an input: xy_out int16[.,2] (4-byte aligned),
+ * t_out int64, p_out int8, batch_out int32, *n_out = the number of survivors, written on the device.  Rows *n_out ..
+ * n_raw - 1 of xy_out are (0, 0) and of batch_out -1, as dagr_stream_denoise leaves them; nothing is written past n_raw;
+ * n_raw = 0 only zeroes *n_out.  lane_flicker / lane_trail int64[B] (each may be NULL): the lane's events removed by the
+ * flicker / the trail stage are added to them with vector atomics; the caller zeroes them.  All in device memory.
+ * DAGR_ERR_INVALID_ARG before any launch: sizes out of range, periods, thresholds or trail_us out of range or both stages
+ * off, n_raw > max_push, a state smaller than dagr_stream_flicker_bytes, NULL pointers.
+ * ------------------------------------------------------------------------ */
+size_t dagr_stream_flicker_bytes(int32_t B, int32_t sensor_w, int32_t sensor_h, int64_t max_push);
+int dagr_stream_flicker_reset(void *state, size_t state_bytes, int32_t B, int32_t sensor_w, int32_t sensor_h,
+                              int64_t max_push, void *stream);
+int dagr_stream_flicker(void *state, size_t state_bytes, int32_t B, int64_t max_push, int32_t sensor_w, int32_t sensor_h,
+                        int64_t min_period_us, int64_t max_period_us /* 0: off */, int32_t start, int32_t stop,
+                        int32_t max_count, int64_t trail_us /* 0: off */, const int16_t *xy_raw, const int64_t *t_raw,
+                        const int8_t *p_raw, const void *batch_raw, int32_t batch_is_int64, int64_t n_raw, int16_t *xy_out,
+                        int64_t *t_out, int8_t *p_out, int32_t *batch_out, int32_t *n_out,
+                        int64_t *lane_flicker /* [B], device, accumulated; may be NULL */,
+                        int64_t *lane_trail /* [B], device, accumulated; may be NULL */, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * Event stream decoder: the camera's EVT 3.0 / EVT 2.0 words, decoded on the device
  *   An event camera delivers words, not (x, y, t, p) arrays: EVT 2.0 is one 32-bit word per event plus time words, EVT 3.0
  *   a stateful stream of 16-bit words with run-length vectors.  dagr_stream_decode turns a push of words of B lanes into

@@ -27,6 +27,13 @@ number of events the cap removed is printed with the summary.
 (``dagr.streaming``): an event is kept if one of its 8 neighbours saw an event in the last ``D`` microseconds and its own
 pixel saw none in the last ``R``.  The number of events the filter removed is printed with the summary.
 
+``--flicker_hz LO HI`` / ``--trail_us T``: the stream's anti-flicker and trail filters, on the device, behind the decoder and
+in front of the noise filter (``dagr.streaming``: ``EventStream(flicker=, trail_us=)``): the events of pixels that flicker
+at a steady rate between ``LO`` and ``HI`` Hz are removed, and so is an event that follows one of its own polarity on its
+pixel by less than ``T`` microseconds.  The rule is this project's statement of two well-known filters, not a vendor's
+algorithm.  ``--flicker_pixels N`` lights ``N`` pixels of the synthetic sequence at ``--flicker_pixel_hz`` (default 100) Hz
+(``dagr.utils.synthetic.flicker_events``).  The numbers of events either stage removed are printed with the summary.
+
 ``--track``: the stream gives every detection a track id on the device (``dagr.streaming``: greedy IoU matching inside a
 label against the tracks of the step before), tuned by ``--track_iou``, ``--track_max_age_us``, ``--track_min_score`` and
 ``--max_tracks``.  ``detections_<sequence>.npy`` stays what it is; a second file ``tracks_<sequence>.npy`` holds the same
@@ -61,7 +68,7 @@ import torch
 
 import _common as C
 from dagr.data.evt import encode_events
-from dagr.streaming import EventStream, _motion_options, _rescue_options, _track_options
+from dagr.streaming import EventStream, _flicker_options, _motion_options, _rescue_options, _track_options
 from dagr.utils.buffers import DETECTION_DTYPE, detections_to_records
 from dagr.utils.logging import set_up_logging_directory
 from dagr.utils import synthetic as syn
@@ -83,6 +90,12 @@ def stream_options(p):
                    "neighbours saw an event in the last D microseconds")
     g.add_argument("--refractory_us", type=int, default=None, help="noise filter: drop an event whose own pixel saw an "
                    "event less than R microseconds ago")
+    g.add_argument("--flicker_hz", type=int, nargs=2, default=None, metavar=("LO", "HI"), help="anti-flicker filter: remove "
+                   "the events of pixels that flicker at LO..HI Hz")
+    g.add_argument("--trail_us", type=int, default=None, help="trail filter: drop an event that follows one of its own "
+                   "polarity on its pixel by less than T microseconds")
+    g.add_argument("--flicker_pixels", type=int, default=0, help="synthetic sequence: this many pixels flicker")
+    g.add_argument("--flicker_pixel_hz", type=int, default=100, help="synthetic sequence: the frequency of --flicker_pixels")
     g.add_argument("--decode", type=str, default=None, choices=("evt2", "evt3"), help="encode the step's events as camera "
                    "words of this format and let the stream decode them on the device")
     g.add_argument("--max_decoded", type=int, default=None, help="with --decode: rows of the decoded events' buffers "
@@ -199,6 +212,12 @@ def track_records(rec, det):
     return out
 
 
+def flicker_options(a):
+    """``flicker=`` of the stream the flags describe: None without ``--flicker_hz``."""
+    hz = getattr(a, "flicker_hz", None)
+    return None if hz is None else dict(min_hz=int(hz[0]), max_hz=int(hz[1]))
+
+
 def sensor_size(a):
     """``(W_in, H_in)`` the flags describe, or None without ``--downsample``."""
     if a.downsample is None:
@@ -219,8 +238,19 @@ class SyntheticStream:
         gen = syn.edges_window if a.stream == "edges" else syn.uniform_window
         self.sensor_width, self.sensor_height = sensor_size(a) or (a.width, a.height)
         x, y, t, p = gen(n, self.sensor_width, self.sensor_height, seed=7, window_us=self.duration, time_window=self.duration)
+        t = t.astype(np.int64)
+        lights = int(getattr(a, "flicker_pixels", 0) or 0)
+        if lights > 0:        # pixels lit by a flickering light, merged into the sequence stably by time
+            rng = np.random.Generator(np.random.PCG64(11))
+            flat = rng.choice(self.sensor_width * self.sensor_height, lights, replace=False)
+            lit = syn.flicker_events(np.stack([flat % self.sensor_width, flat // self.sensor_width], -1),
+                                     int(getattr(a, "flicker_pixel_hz", 100)), self.duration, seed=11,
+                                     t0=int(t[0]) if len(t) else 0)
+            x, y, t, p = (np.concatenate([u, v]) for u, v in zip((x, y, t, p), lit))
+            order = np.argsort(t, kind="stable")
+            x, y, t, p = x[order], y[order], t[order], p[order]
         self.x, self.y, self.p = x, y, p
-        self.t = t.astype(np.int64) + np.int64(t0)
+        self.t = t + np.int64(t0)
         self.t0, self.width, self.height = int(t0), a.width, a.height
         self.image_timestamps = np.arange(self.t0, self.t0 + self.duration + 1, 50000, dtype=np.int64)
         raw = getattr(a, "raw_frames", False)         # frames as the sensor delivers them
@@ -263,6 +293,7 @@ def play(a, model, source, dev):
     stream = EventStream(model, window_us=a.window_us or None, downsample=a.downsample, sensor_size=sensor_size(a),
                          frame_size=raw_size, frame_bgr=True, max_lane_events=cap,
                          denoise_us=getattr(a, "denoise_us", None), refractory_us=getattr(a, "refractory_us", None),
+                         flicker=flicker_options(a), trail_us=getattr(a, "trail_us", None),
                          track=track_options(a), motion=motion_options(a), rescue=rescue_options(a),
                          decode=decode, max_decoded=getattr(a, "max_decoded", None),
                          t_base=int(source.t_range()[0]) if decode else None)      # (the words' times start at the sequence's)
@@ -298,6 +329,7 @@ def play(a, model, source, dev):
     a.stream_steps = (stream.frame_steps, stream.held_steps)      # (frame bodies, held bodies) of the run
     a.stream_dropped = int(stream.dropped().sum()) if cap is not None else None
     a.stream_filtered = int(stream.filtered().sum()) if stream.state.noise is not None else None
+    a.stream_suppressed = tuple(int(v.sum()) for v in stream.suppressed()) if stream.state.flick is not None else None
     a.stream_decoded = {k: int(v.sum()) for k, v in stream.decode_counts().items()} if stream.decode is not None else None
     a.stream_untracked = int(stream.untracked().sum()) if stream.track is not None else None
     a.stream_rescued = int(stream.rescued().sum()) if stream.rescue is not None else None
@@ -312,6 +344,12 @@ def main(argv=None, model_factory=None, source=None):
     for name in ("denoise_us", "refractory_us"):
         if getattr(a, name, None) is not None and getattr(a, name) < 1:
             raise SystemExit(f"run_stream.py: --{name} must be positive")
+    if getattr(a, "trail_us", None) is not None and a.trail_us < 1:
+        raise SystemExit("run_stream.py: --trail_us must be positive")
+    try:
+        _flicker_options(flicker_options(a), None, 1, 1, 1, "run_stream.py --flicker_hz")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
     if a.step_us <= 0 or a.window_us < 0 or (a.window_us == 0 and not capped):
         raise SystemExit("run_stream.py: --step_us and --window_us must be positive (--window_us 0: the model's time "
                          "window, with --max_lane_events only)")
@@ -357,6 +395,9 @@ def main(argv=None, model_factory=None, source=None):
             window += f" capped at {a.max_lane_events} events ({a.stream_dropped} dropped by the cap)"
         if a.stream_filtered is not None:
             window += f" behind the noise filter ({a.stream_filtered} events filtered)"
+        if a.stream_suppressed is not None:
+            window += (f" behind the flicker / trail filters ({a.stream_suppressed[0]} flicker events, "
+                       f"{a.stream_suppressed[1]} trail events suppressed)")
         if a.stream_decoded is not None:
             c = a.stream_decoded
             window += (f" decoded from {a.decode} words ({c['decoded']} events decoded, {c['unsynced']} unsynced, "
