@@ -440,7 +440,11 @@ class StreamState:
     motion=)``) the state is ``dagr_stream_track_cv``'s, which also holds the velocities, and the stream owns the step's
     ``track_boxes`` / ``track_vel`` and the lanes' coast lists, allocated once.  With a second association round
     (``enable_track(..., rescue=)``) the step ends with the ``_rescue`` entry of either, on the same state, and the stream
-    owns ``lane_rescued``."""
+    owns ``lane_rescued``.
+
+    A scoring stream (``enable_score``, on a tracking stream) owns the scorer's state (``dagr_stream_score``): the lanes'
+    object tables and counters, allocated next to the tracker's, and the ``gt_match`` / ``gt_flags`` of the last scored
+    step.  A step launches nothing for it: ``run_score`` is the one launch, on the last step's device arrays."""
 
     def __init__(self, batch_size, window_us, device, max_lane_events=None):
         self.B, self.window_us, self.device = int(batch_size), int(window_us), torch.device(device)
@@ -472,6 +476,9 @@ class StreamState:
         self.motion = None                              # the options of its motion model (dagr.streaming._motion_options)
         self.track_boxes, self.track_vel, self.coast = None, None, None
         self.rescue, self.lane_rescued = None, None     # the options of its second round (dagr.streaming._rescue_options)
+        self.score = None                               # the options of its scorer (dagr.streaming._score_options)
+        self.score_state, self.gt_match, self.gt_flags = None, None, None
+        self._last_det, self._scored = None, False      # the last step's (det, n_keep); whether run_score has had them
         self._t_ref = None                              # (state pointer, capacity, where its t_ref[B] lives)
 
     # ------------------------------------------------------------------------------------ track ids
@@ -551,6 +558,66 @@ class StreamState:
                                           o["max_age_us"], o["min_score"], *gains, P(det), P(n_keep), A, self._t_ref[2],
                                           P(self.track_ids), P(self.track_hits), *outputs, P(self.lane_untracked), *second,
                                           _lib.cur_stream(self.device)), self._track_family + suffix)
+        self._last_det, self._scored = (det, n_keep), False
+
+    # ------------------------------------------------------------------------------------ scoring the tracks
+    # the lane's words behind the table, in the order include/dagr_hip.h documents
+    SCORE_WORDS = ("n_objects", "steps", "gt", "hyp", "match", "miss", "false_pos", "switch", "frag", "kept", "iou_q",
+                   "unscored_gt", "unscored_hyp")
+
+    def enable_score(self, options):
+        """``run_score`` scores a step's track ids against labelled boxes (``dagr_stream_score``): ``options`` as
+        ``dagr.streaming._score_options`` returns them, on a stream that tracks.  Allocates the lanes' tables, empty."""
+        if self.track is None:
+            raise RuntimeError("enable_score: the stream does not track (enable_track comes first)")
+        self.score = dict(options)
+        nbytes = _lib.lib().dagr_stream_score_bytes(self.B, self.score["max_objects"])
+        if nbytes == 0:
+            raise RuntimeError(f"dagr_stream_score_bytes({self.B}, {self.score['max_objects']}): out of range")
+        self.score_state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._reset_score()
+
+    def _reset_score(self):
+        """Empty tables, zero counters; the last step cannot be scored any more."""
+        _lib.check(_lib.lib().dagr_stream_score_reset(_lib.ptr(self.score_state), self.score_state.numel(), self.B,
+                                                      self.score["max_objects"], _lib.cur_stream(self.device)),
+                   "stream_score_reset")
+        self._last_det, self._scored = None, False
+
+    def run_score(self, gt_box, gt_label, gt_id, n_gt):
+        """``dagr_stream_score`` on the LAST step's ``det`` / ``n_keep`` / ``track_ids`` (``track_boxes`` with
+        ``boxes="track"``) against device tensors ``gt_box`` fp32 [B, G, 4], ``gt_label`` int32 [B, G], ``gt_id`` int64
+        [B, G] and ``n_gt`` int32 [B]: one launch, no host wait.  Leaves ``gt_match`` int64 [B, G] / ``gt_flags`` int32
+        [B, G], valid until the next call."""
+        if self.score is None:
+            raise RuntimeError("this stream does not score (score=): it has no score_step")
+        if self._last_det is None:
+            raise RuntimeError("score_step: the stream has made no step since its construction / reset(): there is nothing "
+                               "to score")
+        if self._scored:
+            raise RuntimeError("score_step: the last step has been scored already (one score_step per step)")
+        det, n_keep = self._last_det
+        B, A, G = self.B, int(det.shape[1]), int(gt_box.shape[1])
+        if self.gt_match is None or tuple(self.gt_match.shape) != (B, G):
+            self.gt_match = torch.zeros((B, G), dtype=torch.int64, device=self.device)
+            self.gt_flags = torch.zeros((B, G), dtype=torch.int32, device=self.device)
+        P, o = _lib.ptr, self.score
+        boxes = P(self.track_boxes) if o["boxes"] == "track" else None
+        _lib.check(_lib.lib().dagr_stream_score(P(self.score_state), self.score_state.numel(), B, o["max_objects"], o["iou"],
+                                                P(det), P(n_keep), A, P(self.track_ids), boxes, P(gt_box), P(gt_label),
+                                                P(gt_id), P(n_gt), G, P(self.gt_match), P(self.gt_flags),
+                                                _lib.cur_stream(self.device)), "stream_score")
+        self._scored = True
+        return self.gt_match, self.gt_flags
+
+    def score_words(self):
+        """The state read back: ``(table int64 [8, B, max_objects] -- id, last_hyp, prev_hyp, seen_step, present, tracked,
+        switches, frags --, words int64 [B, 16])``, the layout include/dagr_hip.h documents (copies; synchronises)."""
+        if self.score is None:
+            raise RuntimeError("this stream does not score (score=): it has no counters and no objects")
+        n = self.B * self.score["max_objects"]
+        raw = self.score_state.view(torch.int64).cpu().numpy()
+        return raw[:8 * n].reshape(8, self.B, self.score["max_objects"]), raw[8 * n:].reshape(self.B, 16)
 
     def untracked(self):
         """Per-lane eligible rows that got no track id, int64 [B] (synchronises)."""
@@ -865,6 +932,8 @@ class StreamState:
             self.lane_suppressed.zero_()
         if self.track_state is not None:
             self._reset_track()
+        if self.score_state is not None:
+            self._reset_score()
         self.status.zero_()
         self.lane_count.zero_()
         self.lane_dropped.zero_()

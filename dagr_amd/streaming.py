@@ -210,6 +210,55 @@ motion model's predict, filter and coast are what they are above, over the rows 
 ``rescued`` is int64 ``[B]``, cumulative, zero after construction and after ``reset()``.  Unlike ByteTrack, round two
 considers every live unmatched track, not only those seen in the step before.  Without ``rescue`` nothing of this exists.
 
+Scoring the tracks against labelled boxes (``score=`` of a tracking stream: ``None`` is off, ``True`` takes the defaults, a
+dict sets ``iou``, fp32 in (0, 1], default 0.5, ``max_objects``, 1 .. ``DAGR_SCORE_MAX_OBJECTS = 1024``, default 256, and
+``boxes``, ``"det"`` (default: a hypothesis is the detection's box) or ``"track"`` (the motion model's ``track_box``; needs
+``motion=``).  It needs ``track=``).  ``ScoreDefinition`` below states it once in numpy and ``dagr_stream_score`` repeats it
+integer for integer, one launch behind the tracker's on the step's device arrays (``EventStream.score_step``).  It is THIS
+PROJECT'S statement of the CLEAR-MOT counts (Bernardin & Stiefelhagen, "Evaluating multiple object tracking performance:
+the CLEAR MOT metrics"): misses, false positives, identity switches, MOTA and MOTP, with the paper's continuity rule.  It
+departs from the paper in the matcher: the assignment is greedy in ground-truth row order inside a label -- as the
+tracker's own matcher and the COCO matcher of this project are -- not a minimum-cost assignment, the overlap is an IoU
+and not a distance, and a label mismatch never matches.  Agreement with py-motmetrics or any other MOT tool is not
+claimed.  IDF1 and HOTA need a global assignment over the whole sequence and are out of scope.
+
+Every lane owns an object table of ``max_objects`` slots in order of first appearance and ``n_objects``; a slot holds
+``id`` int64 (the ground-truth identity, > 0), ``last_hyp`` int64 (the track id of its last match ever, 0: none),
+``prev_hyp`` int64 (the track id of its match at its last scored step, 0: a miss), ``seen_step`` int64 (-1: never) and
+``present``, ``tracked``, ``switches``, ``frags`` int64; and the int64 counters ``steps``, ``gt``, ``hyp``, ``match``,
+``miss``, ``false_pos``, ``switch``, ``frag``, ``kept``, ``iou_q``, ``unscored_gt``, ``unscored_hyp``, cumulative, zero after
+construction and after ``reset()``.  One scored step of lane ``b`` takes the step's ``det[b]``, ``n_keep[b]``,
+``track_id[b]`` (and ``track_box[b]`` with ``boxes="track"``) and the ground truth ``gt_box`` fp32 ``[B, G, 4]`` (x1, y1, x2,
+y2), ``gt_label`` int32 ``[B, G]``, ``gt_id`` int64 ``[B, G]``, ``n_gt`` int32 ``[B]``, ``G <= DAGR_SCORE_MAX_GT = 256``.
+``n_gt[b] < 0`` means that the lane has no labels at this instant: it is skipped, and not one byte of its state changes;
+``n_gt[b]`` above ``G`` is clamped.
+
+1. hypotheses: the rows ``i < clamp(n_keep[b], 0, A)`` with ``track_id != 0``, in row order.  A row without an id is not
+   tracker output: it is neither a match nor a false positive.  The first ``DAGR_TRACK_MAX_DETS`` of them take part, each
+   further one adds 1 to ``unscored_hyp``.  The label is ``(int32_t)det[..., 5]``, as the tracker has it;
+2. slots: the ground-truth rows in row order.  A row is unscored if its ``gt_id <= 0``, if an earlier row of this step has
+   the same ``gt_id``, or if its identity is new and the table is full: it adds 1 to ``unscored_gt``, takes part in nothing
+   and its outcome is -1.  Otherwise it finds its slot, or takes slot ``n_objects++``;
+3. keep (CLEAR-MOT's continuity rule): the scored rows in row order whose object has ``seen_step == steps - 1`` and
+   ``prev_hyp != 0``.  The FIRST hypothesis row with that id is taken; the object keeps it if that row is still free, has
+   the row's label and ``iou(gt, hyp) >= iou``, and ``kept += 1``;
+4. match: the remaining scored rows in row order, greedily: among the free hypotheses of the row's label the one with the
+   largest IoU ``>= iou``, the LOWEST row on a tie; a NaN IoU matches nothing.  The IoU is the tracker's, ``iou(gt, hyp)``
+   operation for operation in fp32 without contraction;
+5. count, per scored row: ``gt += 1``, ``present += 1``, ``seen_step = steps``.  Matched to track ``h``: ``match += 1``,
+   ``iou_q += (int64) rint(iou * 2**20)`` (exact and order-free: nothing is accumulated in floating point); a switch is
+   counted iff ``last_hyp != 0 and last_hyp != h``, a fragmentation iff ``tracked > 0 and prev_hyp == 0``; then
+   ``tracked += 1`` and ``last_hyp = prev_hyp = h``.  Unmatched: ``miss += 1``, ``prev_hyp = 0``.  An object absent from the
+   step keeps its slot untouched.  Then ``hyp +=`` the participating hypotheses, ``false_pos +=`` those left free, and
+   ``steps += 1``.
+
+Per ground-truth row the step leaves ``gt_match`` int64 ``[B, G]`` (the track id, 0 for a miss, -1 for unscored) and
+``gt_flags`` int32 ``[B, G]`` (bit 0 switch, bit 1 fragmentation, bit 2 kept); rows at and behind ``n_gt[b]`` and every row
+of a skipped lane are left as they were.  ``score_summary`` turns counters and tables into MOTA
+(``1 - (miss + false_pos + switch) / gt``), MOTP (``iou_q / 2**20 / match``, a mean IoU), precision, recall, and the
+mostly tracked / mostly lost objects (``tracked / present >= 0.8`` / ``<= 0.2``).  Coasting tracks are not hypotheses, and
+there are no ignore regions.  Without ``score`` nothing of this exists.
+
 Camera words (``decode="evt3"`` or ``"evt2"``): an event camera delivers words, not arrays.  A decoding stream takes the
 camera's words (``step_words`` / ``step_words_device``) and decodes them on the device (``dagr_stream_decode``) in front of
 everything above: decode, then the flicker / trail filters, then the noise filter, then ``downsample=``, then the window.  The two formats are stated here as
@@ -776,6 +825,220 @@ def coast_from_arrays(n, ids, box, label, age_us):
     return out
 
 
+DAGR_SCORE_MAX_OBJECTS = DEFINES["DAGR_SCORE_MAX_OBJECTS"]
+DAGR_SCORE_MAX_GT = DEFINES["DAGR_SCORE_MAX_GT"]
+SCORE_DEFAULTS = dict(iou=0.5, max_objects=256, boxes="det")
+SCORE_COUNTERS = ("steps", "gt", "hyp", "match", "miss", "false_pos", "switch", "frag", "kept", "iou_q", "unscored_gt",
+                  "unscored_hyp")
+SCORE_OBJECT_FIELDS = ("id", "last_hyp", "prev_hyp", "seen_step", "present", "tracked", "switches", "frags")
+SCORE_OBJECT_DTYPE = [(name, "<i8") for name in SCORE_OBJECT_FIELDS]
+SCORE_SWITCH, SCORE_FRAG, SCORE_KEPT = 1, 2, 4          # the bits of gt_flags
+SCORE_IOU_ONE = 1 << 20                                 # iou_q counts IoUs in units of 2**-20
+
+
+def _score_options(score, track_options, motion_options, who):
+    """``score=`` of a tracking stream, checked: None (off) or the dict of ``iou`` (as fp32), ``max_objects`` and ``boxes``
+    with the defaults filled in; ``track_options`` / ``motion_options`` are what ``_track_options`` / ``_motion_options``
+    returned.  Refusals by name."""
+    opt = _options(score, "score", SCORE_DEFAULTS, who)
+    if opt is None:
+        return None
+    if track_options is None:
+        raise ValueError(f"{who}: score= needs track= (it scores the tracker's ids)")
+    if not _is_real(opt["iou"]) or not 0 < np.float32(opt["iou"]) <= 1:
+        raise ValueError(f"{who}: score iou = {opt['iou']!r} must be a float in (0, 1] (as fp32)")
+    if not _is_int(opt["max_objects"]) or not 1 <= int(opt["max_objects"]) <= DAGR_SCORE_MAX_OBJECTS:
+        raise ValueError(f"{who}: score max_objects = {opt['max_objects']!r} must be an int in 1..DAGR_SCORE_MAX_OBJECTS = "
+                         f"{DAGR_SCORE_MAX_OBJECTS}")
+    if opt["boxes"] not in ("det", "track"):
+        raise ValueError(f"{who}: score boxes = {opt['boxes']!r} must be 'det' (the detection's box) or 'track' (the motion "
+                         "model's track_box)")
+    if opt["boxes"] == "track" and motion_options is None:
+        raise ValueError(f"{who}: score boxes = 'track' needs motion= (track_box is the motion model's)")
+    return dict(iou=float(np.float32(opt["iou"])), max_objects=int(opt["max_objects"]), boxes=opt["boxes"])
+
+
+class ScoreDefinition:
+    """The scorer of the module docstring in numpy -- this project's statement of the CLEAR-MOT counts with a greedy
+    matcher: ``step(det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt=None, track_box=None)`` is one scored step of every
+    lane and returns ``(gt_match int64 [B, G], gt_flags int32 [B, G])``; given ``out=(gt_match, gt_flags)`` it writes into
+    them, so that the rows at and behind ``n_gt[b]`` and the rows of a skipped lane are left as they were (otherwise they
+    are zero).  The state is the table's arrays, one per name of ``SCORE_OBJECT_FIELDS`` over ``[B, max_objects]``,
+    ``n_objects`` int64 ``[B]`` and ``counters``, a dict of one int64 ``[B]`` array per name of ``SCORE_COUNTERS``.
+    ``events`` counts what has happened so far -- matches, misses, false positives, switches, fragmentations, kept pairs,
+    keep candidates that lost their hypothesis, new objects, unscored ground-truth rows, rows without an id -- so that a
+    test can tell a run that exercises every rule from one that does not.  The yardstick of ``dagr_stream_score``; nothing
+    on the device path calls it."""
+
+    def __init__(self, batch_size, score=True):
+        self.B = int(batch_size)
+        self.options = _score_options(score, True, True, "ScoreDefinition")       # (what it scores is the caller's business)
+        if self.options is None:
+            raise ValueError("ScoreDefinition: score = None is a stream that does not score")
+        self.reset()
+
+    def reset(self):
+        B, M = self.B, self.options["max_objects"]
+        for name in SCORE_OBJECT_FIELDS:
+            setattr(self, name, np.full((B, M), -1 if name == "seen_step" else 0, np.int64))
+        self.n_objects = np.zeros(B, np.int64)
+        self.counters = {name: np.zeros(B, np.int64) for name in SCORE_COUNTERS}
+        self.events = dict(matched=0, missed=0, false_pos=0, switched=0, fragmented=0, kept=0, keep_lost=0, new_objects=0,
+                           unscored_gt=0, rows_without_id=0)
+
+    def step(self, det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt=None, track_box=None, out=None):
+        f = np.float32
+        det, track_id = np.asarray(det, np.float32), np.asarray(track_id, np.int64)
+        B, A = det.shape[:2]
+        gt_box, gt_label, gt_id = np.asarray(gt_box, np.float32), np.asarray(gt_label, np.int32), np.asarray(gt_id, np.int64)
+        G = gt_box.shape[1] if gt_box.ndim == 3 else -1
+        if B != self.B or det.shape[2:] != (6,) or track_id.shape != (B, A):
+            raise ValueError(f"ScoreDefinition: det is fp32 [{self.B}, A, 6] and track_id int64 [{self.B}, A], got {det.shape} "
+                             f"and {track_id.shape}")
+        if gt_box.shape != (B, G, 4) or gt_label.shape != (B, G) or gt_id.shape != (B, G) or not 0 <= G <= DAGR_SCORE_MAX_GT:
+            raise ValueError(f"ScoreDefinition: the ground truth is gt_box fp32 [{B}, G, 4], gt_label int32 [{B}, G] and gt_id "
+                             f"int64 [{B}, G] with G <= DAGR_SCORE_MAX_GT = {DAGR_SCORE_MAX_GT}, got {gt_box.shape}, "
+                             f"{gt_label.shape}, {gt_id.shape}")
+        o = self.options
+        if o["boxes"] == "track":
+            if track_box is None:
+                raise ValueError("ScoreDefinition: score boxes = 'track' needs the step's track_box")
+            boxes = np.asarray(track_box, np.float32)
+        else:
+            boxes = det[..., :4]
+        n_keep = np.broadcast_to(np.asarray(n_keep, np.int64).reshape(-1), (B,))
+        n_gt = np.full(B, G, np.int64) if n_gt is None else np.broadcast_to(np.asarray(n_gt, np.int64).reshape(-1), (B,))
+        gt_match, gt_flags = out if out is not None else (np.zeros((B, G), np.int64), np.zeros((B, G), np.int32))
+        thr, M, c, ev = f(o["iou"]), o["max_objects"], self.counters, self.events
+        for b in range(B):
+            if n_gt[b] < 0:                                        # no labels at this instant: not one byte changes
+                continue
+            n, ng, steps = min(max(int(n_keep[b]), 0), A), min(int(n_gt[b]), G), int(c["steps"][b])
+            with np.errstate(all="ignore"):
+                labels = det[b, :, 5].astype(np.int32)
+            with_id = [i for i in range(n) if track_id[b, i] != 0]                # 1: the hypotheses
+            ev["rows_without_id"] += n - len(with_id)
+            hyp = with_id[:DAGR_TRACK_MAX_DETS]
+            c["unscored_hyp"][b] += len(with_id) - len(hyp)
+            slot, earlier = {}, set()                                             # 2: the slots
+            for g in range(ng):
+                ident = int(gt_id[b, g])
+                known = np.flatnonzero(self.id[b, :self.n_objects[b]] == ident)
+                if ident > 0 and ident not in earlier and (len(known) or self.n_objects[b] < M):
+                    if len(known):
+                        slot[g] = int(known[0])
+                    else:
+                        slot[g] = int(self.n_objects[b])
+                        self.id[b, slot[g]] = ident
+                        self.n_objects[b] += 1
+                        ev["new_objects"] += 1
+                else:
+                    c["unscored_gt"][b] += 1
+                    ev["unscored_gt"] += 1
+                    gt_match[b, g], gt_flags[b, g] = -1, 0
+                earlier.add(ident)
+            free = [True] * len(hyp)
+            got = {}                                                              # row g -> (hypothesis, iou, kept)
+            for g, s in slot.items():                                             # 3: keep
+                prev = int(self.prev_hyp[b, s])
+                if self.seen_step[b, s] != steps - 1 or prev == 0:
+                    continue
+                first = next((p for p, i in enumerate(hyp) if track_id[b, i] == prev), None)
+                v = None if first is None else TrackDefinition.iou(gt_box[b, g], boxes[b, hyp[first]])
+                if first is not None and free[first] and labels[hyp[first]] == gt_label[b, g] and v >= thr:
+                    free[first] = False
+                    got[g] = (first, v, True)
+                else:
+                    ev["keep_lost"] += 1
+            for g in slot:                                                        # 4: match
+                if g in got:
+                    continue
+                best, best_p = None, None
+                for p, i in enumerate(hyp):
+                    if not free[p] or labels[i] != gt_label[b, g]:
+                        continue
+                    v = TrackDefinition.iou(gt_box[b, g], boxes[b, i])
+                    if v >= thr and (best is None or v > best):                   # (a NaN IoU matches nothing; ties: lowest row)
+                        best, best_p = v, p
+                if best_p is not None:
+                    free[best_p] = False
+                    got[g] = (best_p, best, False)
+            for g, s in slot.items():                                             # 5: count
+                c["gt"][b] += 1
+                self.present[b, s] += 1
+                self.seen_step[b, s] = steps
+                if g not in got:
+                    c["miss"][b] += 1
+                    ev["missed"] += 1
+                    self.prev_hyp[b, s] = 0
+                    gt_match[b, g], gt_flags[b, g] = 0, 0
+                    continue
+                p, v, kept = got[g]
+                h = int(track_id[b, hyp[p]])
+                flags = SCORE_KEPT if kept else 0
+                c["match"][b] += 1
+                c["iou_q"][b] += int(np.rint(f(v * f(SCORE_IOU_ONE))))
+                c["kept"][b] += int(kept)
+                if self.last_hyp[b, s] != 0 and self.last_hyp[b, s] != h:
+                    flags |= SCORE_SWITCH
+                    c["switch"][b] += 1
+                    self.switches[b, s] += 1
+                    ev["switched"] += 1
+                if self.tracked[b, s] > 0 and self.prev_hyp[b, s] == 0:
+                    flags |= SCORE_FRAG
+                    c["frag"][b] += 1
+                    self.frags[b, s] += 1
+                    ev["fragmented"] += 1
+                self.tracked[b, s] += 1
+                self.last_hyp[b, s] = self.prev_hyp[b, s] = h
+                gt_match[b, g], gt_flags[b, g] = h, flags
+                ev["matched"] += 1
+                ev["kept"] += int(kept)
+            c["hyp"][b] += len(hyp)
+            c["false_pos"][b] += sum(free)
+            ev["false_pos"] += sum(free)
+            c["steps"][b] += 1
+        return gt_match, gt_flags
+
+    def objects(self):
+        """Per lane the object table as a ``SCORE_OBJECT_DTYPE`` array in order of first appearance (what
+        ``EventStream.scored_objects()`` returns)."""
+        return [objects_from_arrays(int(self.n_objects[b]), *(getattr(self, name)[b] for name in SCORE_OBJECT_FIELDS))
+                for b in range(self.B)]
+
+
+def objects_from_arrays(n, *fields):
+    """One lane's object table -> its first ``n`` slots as a ``SCORE_OBJECT_DTYPE`` array; ``fields`` in the order of
+    ``SCORE_OBJECT_FIELDS``."""
+    out = np.zeros(n, SCORE_OBJECT_DTYPE)
+    for name, a in zip(SCORE_OBJECT_FIELDS, fields):
+        out[name] = a[:n]
+    return out
+
+
+def score_summary(counters, objects):
+    """``counters`` (a dict of int64 ``[B]`` per name of ``SCORE_COUNTERS``) and ``objects`` (per lane a
+    ``SCORE_OBJECT_DTYPE`` array) -> ``dict(lanes=[...], total=...)``, each entry a dict of ``mota``, ``motp``, ``precision``,
+    ``recall`` (floats, ``nan`` where the denominator is 0), ``gt``, ``match``, ``miss``, ``false_pos``, ``switch``, ``frag``,
+    ``objects``, ``mostly_tracked`` and ``mostly_lost`` (ints).  Plain host code."""
+    def one(c, tables):
+        ratio = lambda a, b: float(a) / float(b) if b else float("nan")            # noqa: E731
+        present = np.concatenate([t["present"] for t in tables]) if tables else np.zeros(0, np.int64)
+        tracked = np.concatenate([t["tracked"] for t in tables]) if tables else np.zeros(0, np.int64)
+        # tracked / present >= 0.8 and <= 0.2 in integers; an object that was never scored (present 0) is neither
+        return dict(mota=1.0 - ratio(c["miss"] + c["false_pos"] + c["switch"], c["gt"]) if c["gt"] else float("nan"),
+                    motp=ratio(c["iou_q"], SCORE_IOU_ONE * c["match"]),
+                    precision=ratio(c["match"], c["match"] + c["false_pos"]), recall=ratio(c["match"], c["gt"]),
+                    gt=c["gt"], match=c["match"], miss=c["miss"], false_pos=c["false_pos"], switch=c["switch"], frag=c["frag"],
+                    objects=int(len(present)),
+                    mostly_tracked=int(np.sum((present > 0) & (5 * tracked >= 4 * present))),
+                    mostly_lost=int(np.sum((present > 0) & (5 * tracked <= present))))
+    B = len(objects)
+    per_lane = [{k: int(np.asarray(counters[k]).reshape(-1)[b]) for k in SCORE_COUNTERS} for b in range(B)]
+    total = {k: sum(c[k] for c in per_lane) for k in SCORE_COUNTERS}
+    return dict(lanes=[one(per_lane[b], [objects[b]]) for b in range(B)], total=one(total, list(objects)))
+
+
 def frame_definition(raw, fx, fy, W, H, bgr=False):
     """The model's image of one raw sensor frame (``uint8 [H_f, W_f, 3]``), stated once: ``DSEC.preprocess_image`` plus
     ``format_data`` for a top-left crop.  Rows ``[0, fy * H)`` and columns ``[0, fx * W)`` of the frame go through
@@ -1133,6 +1396,12 @@ class EventStream:
     is then ``dagr_stream_track_rescue`` or ``dagr_stream_track_cv_rescue``.  ``rescued()`` counts its matches.  The
     defaults are ByteTrack's conventions, not measured optima.  A stream built without it issues exactly the calls it
     issues without the round.
+    ``score`` (``None``: off, ``True``: the defaults, or a dict of ``iou``, ``max_objects``, ``boxes``; needs ``track``):
+    ``score_step(gt_box, gt_label, gt_id, n_gt)`` scores the last step's track ids against labelled boxes on the device --
+    this project's statement of the CLEAR-MOT counts with a greedy matcher (module docstring) --, ``track_score()`` reads
+    the counters back, ``scored_objects()`` the object tables, and ``score_summary`` turns both into MOTA, MOTP and the id
+    switches.  A step of a scoring stream issues exactly the calls it issues without the scorer: only ``score_step``
+    launches (``dagr_stream_score``, once).  A stream built without it issues exactly the calls it issued before.
     ``decode`` (``None``: off, ``"evt2"`` or ``"evt3"``), ``max_decoded`` and ``t_base``: the stream takes the camera's words
     (``step_words`` / ``step_words_device``) and ``dagr_stream_decode`` turns them into events on the device, in front of
     the filter, the front and the window (module docstring; the formats as recalled from the vendor's public descriptions,
@@ -1158,12 +1427,13 @@ class EventStream:
 
     def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
                  max_lane_events=None, denoise_us=None, refractory_us=None, track=None, motion=None, rescue=None,
-                 decode=None, max_decoded=None, t_base=None, flicker=None, trail_us=None):
+                 decode=None, max_decoded=None, t_base=None, flicker=None, trail_us=None, score=None):
         import torch
         self.model = model
         self.track = _track_options(track, "EventStream")
         self.motion = _motion_options(motion, self.track, "EventStream")
         self.rescue = _rescue_options(rescue, self.track, "EventStream")
+        self.score = _score_options(score, self.track, self.motion, "EventStream")
         time_window = int(getattr(model.args, "time_window_us", 1000000))
         self.window_us, self.max_lane_events = _window_and_cap(window_us, max_lane_events, time_window,
                                                                getattr(model.args, "batch_size", 1), "EventStream")
@@ -1211,6 +1481,8 @@ class EventStream:
             self.state.enable_flicker(w_in, h_in, self.flicker, self.trail_us)
         if self.track is not None:
             self.state.enable_track(self.track, motion=self.motion, rescue=self.rescue)
+        if self.score is not None:
+            self.state.enable_score(self.score)
         self._zeros = None
         self.outputs = None      # the last step's decoded head outputs [B, A, 5 + classes], valid until the engine's next call
         self._frame = None
@@ -1522,9 +1794,55 @@ class EventStream:
         that continued a track: int64 [B] (synchronises).  Raises without ``rescue=``."""
         return self.state.rescued()
 
+    def score_step(self, gt_box, gt_label, gt_id, n_gt=None):
+        """Score the LAST step's track ids against labelled boxes, on the device (module docstring; needs ``score=``):
+        ``gt_box`` fp32 ``[B, G, 4]`` (x1, y1, x2, y2), ``gt_label`` int32 ``[B, G]``, ``gt_id`` int64 ``[B, G]`` (the
+        identities, > 0) and ``n_gt`` int32 ``[B]`` -- ``None``: every lane has all ``G`` rows; ``n_gt[b] < 0``: lane ``b``
+        has no labels at this instant and is skipped --, numpy arrays (uploaded) or device tensors,
+        ``G <= DAGR_SCORE_MAX_GT``.  ONE launch (``dagr_stream_score``) on the step's own device arrays, no host wait.
+        Returns ``(gt_match int64 [B, G], gt_flags int32 [B, G])``, device tensors valid until the next ``score_step``:
+        per row the track id (0: a miss, -1: unscored) and the bits switch (1), fragmentation (2), kept (4).  Raises by name
+        before the stream's first step, when called twice for one step, and on a stream without ``score=``."""
+        import torch
+        if self.score is None:
+            raise RuntimeError("EventStream: score_step needs a stream built with score= (and track=)")
+
+        def dev(v, dtype, shape, name):
+            if not torch.is_tensor(v):
+                v = torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
+            v = v.to(device=self.device, dtype=dtype).contiguous()
+            if shape is not None and tuple(v.shape) != shape:
+                raise ValueError(f"EventStream: score_step {name} has shape {tuple(v.shape)}, expected {shape}")
+            return v
+        G = int(gt_box.shape[1]) if np.ndim(gt_box) == 3 else -1
+        if not 0 <= G <= DAGR_SCORE_MAX_GT:
+            raise ValueError(f"EventStream: score_step gt_box is fp32 [{self.B}, G, 4] with G <= DAGR_SCORE_MAX_GT = "
+                             f"{DAGR_SCORE_MAX_GT}, got {tuple(np.shape(gt_box))}")
+        gt_box = dev(gt_box, torch.float32, (self.B, G, 4), "gt_box")
+        gt_label = dev(gt_label, torch.int32, (self.B, G), "gt_label")
+        gt_id = dev(gt_id, torch.int64, (self.B, G), "gt_id")
+        n_gt = torch.full((self.B,), G, dtype=torch.int32, device=self.device) if n_gt is None else \
+            dev(n_gt, torch.int32, (self.B,), "n_gt")
+        return self.state.run_score(gt_box, gt_label, gt_id, n_gt)
+
+    def track_score(self):
+        """The scorer's counters since construction / ``reset()``: a dict of int64 ``[B]`` per name of ``SCORE_COUNTERS``
+        (``steps``, ``gt``, ``hyp``, ``match``, ``miss``, ``false_pos``, ``switch``, ``frag``, ``kept``, ``iou_q``,
+        ``unscored_gt``, ``unscored_hyp``).  Synchronises.  Raises without ``score=``."""
+        _, words = self.state.score_words()
+        return {name: words[:, 1 + i].copy() for i, name in enumerate(SCORE_COUNTERS)}
+
+    def scored_objects(self):
+        """The scorer's object tables: per lane a ``SCORE_OBJECT_DTYPE`` array (``id, last_hyp, prev_hyp, seen_step,
+        present, tracked, switches, frags``) in order of first appearance (copies; synchronises).  ``score_summary`` takes
+        ``track_score()`` and this.  Raises without ``score=``."""
+        table, words = self.state.score_words()
+        return [objects_from_arrays(int(words[b, 0]), *table[:, b]) for b in range(self.B)]
+
     def reset(self):
         """Empty the stream: no resident events, no reference instants, zero change maps, empty stamp maps, every pixel of
-        the flicker / trail filters in its initial state, zero dropped, filtered and suppressed counts, zero decoder states and counters, a clear status word, zero step counters; no tracks, ids from 1 again, zero untracked and rescued counts.  The
+        the flicker / trail filters in its initial state, zero dropped, filtered and suppressed counts, zero decoder states and counters, a clear status word, zero step counters; no tracks, ids from 1 again, zero untracked and rescued counts; the
+        scorer's object tables empty and its counters zero (and no step left to score).  The
         frame in force stays, and the next step runs it through the image branch again."""
         self.state.reset()
 

@@ -72,6 +72,83 @@ def flicker_events(pixels, hz, duration_us, seed, duty=0.5, events_per_half=3, s
     return x[order].astype(np.int16), y[order].astype(np.int16), t[order].astype(np.int64) + np.int64(t0), p[order].astype(np.int8)
 
 
+def track_scene(seed, B, objects, steps, A, G=None, step_us=1000, t0=(1 << 33) + 5000, width=320, height=240, labels=2,
+                speed=4.0, jitter=1.0, p_gap=0.04, gap_steps=(1, 5), p_dip=0.05, dip_steps=(1, 4), dip_score=(0.15, 0.45),
+                clutter=3.0, p_death=0.01, p_unlabelled=0.01):
+    """A labelled scene of moving boxes as a detector would report it, for the stream tracker and its scorer: no events, no
+    model.  Per lane ``objects`` places, each holding one object at a time: a box of 14..40 px that moves at a constant
+    velocity of up to ``speed`` px a step and bounces off the borders.  An object dies with ``p_death`` a step and a new
+    identity is born in its place a few steps later, somewhere else.  The GROUND TRUTH of a step is every living object's
+    true box with its label and identity (ids from 1, never used twice in a lane; with ``p_unlabelled`` a row carries id 0,
+    an annotation without an identity).  The DETECTIONS are the living objects' boxes with N(0, ``jitter``) px on every
+    corner and a score in 0.55..1, except that a detection fails for ``gap_steps`` steps with ``p_gap`` a step (the box is
+    absent) and dips to a score in ``dip_score`` for ``dip_steps`` steps with ``p_dip`` a step; and on average ``clutter``
+    rows a step that belong to nothing, scores 0.05..0.75.  Rows are sorted by descending score, as ``dagr_postprocess``
+    leaves them, and cut at ``A``.  Seeded, pure numpy.
+
+    Returns one dict per step: ``det`` fp32 [B, A, 6], ``n_keep`` int32 [B], ``t_ref`` int64 [B], ``gt_box`` fp32 [B, G, 4],
+    ``gt_label`` int32 [B, G], ``gt_id`` int64 [B, G], ``n_gt`` int32 [B] (``G`` defaults to ``objects``)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    G = objects if G is None else G
+    shape = (B, objects)
+
+    def born(n):
+        size = rng.uniform(14, 40, (n, 2))
+        centre = np.stack([rng.uniform(30, width - 30, n), rng.uniform(30, height - 30, n)], -1)
+        return centre, rng.uniform(-speed, speed, (n, 2)), size, rng.integers(0, labels, n)
+
+    centre, vel, size, label = (a.reshape(shape + a.shape[1:]) for a in born(B * objects))
+    ident = np.tile(np.arange(1, objects + 1, dtype=np.int64), (B, 1))     # ids 1 .. objects in every lane; 0: the place is empty
+    next_id = np.full(B, objects + 1, np.int64)
+    dead_until = np.zeros(shape, np.int64)                          # the place is empty before this step
+    gap_until, dip_until = np.zeros(shape, np.int64), np.zeros(shape, np.int64)
+    out = []
+    for k in range(steps):
+        centre += vel
+        for axis, limit in ((0, width), (1, height)):              # bounce
+            over = (centre[..., axis] < 10) | (centre[..., axis] > limit - 10)
+            vel[..., axis] = np.where(over, -vel[..., axis], vel[..., axis])
+        alive = dead_until <= k
+        reborn = alive & (ident == 0)
+        for b, o in zip(*np.nonzero(reborn)):
+            c, v, s, lab = born(1)
+            centre[b, o], vel[b, o], size[b, o], label[b, o] = c[0], v[0], s[0], lab[0]
+            ident[b, o], next_id[b] = next_id[b], next_id[b] + 1
+            gap_until[b, o] = dip_until[b, o] = 0
+        dies = alive & (rng.random(shape) < p_death)
+        dead_until[dies] = k + rng.integers(2, 8, int(dies.sum()))
+        ident[dies] = 0
+        alive &= ~dies
+        starts = alive & (gap_until <= k) & (rng.random(shape) < p_gap)
+        gap_until[starts] = k + rng.integers(gap_steps[0], gap_steps[1] + 1, int(starts.sum()))
+        starts = alive & (dip_until <= k) & (rng.random(shape) < p_dip)
+        dip_until[starts] = k + rng.integers(dip_steps[0], dip_steps[1] + 1, int(starts.sum()))
+        det, n_keep = np.zeros((B, A, 6), np.float32), np.zeros(B, np.int32)
+        gt_box, gt_label = np.zeros((B, G, 4), np.float32), np.zeros((B, G), np.int32)
+        gt_id, n_gt = np.zeros((B, G), np.int64), np.zeros(B, np.int32)
+        for b in range(B):
+            there = np.flatnonzero(alive[b])[:G]
+            true = np.concatenate([centre[b, there] - size[b, there] / 2, centre[b, there] + size[b, there] / 2], -1)
+            n_gt[b] = len(there)
+            gt_box[b, :len(there)], gt_label[b, :len(there)] = true, label[b, there]
+            gt_id[b, :len(there)] = np.where(rng.random(len(there)) < p_unlabelled, 0, ident[b, there])
+            seen = gap_until[b, there] <= k
+            rows = true[seen] + rng.normal(0, jitter, (int(seen.sum()), 4))
+            score = np.where(dip_until[b, there][seen] > k, rng.uniform(dip_score[0], dip_score[1], len(rows)),
+                             rng.uniform(0.55, 1.0, len(rows)))
+            n_clutter = int(rng.poisson(clutter))
+            c, _, s, lab = born(n_clutter)
+            rows = np.concatenate([rows, np.concatenate([c - s / 2, c + s / 2], -1)])
+            score = np.concatenate([score, rng.uniform(0.05, 0.75, n_clutter)])
+            lab = np.concatenate([label[b, there][seen], lab])
+            order = np.argsort(-score.astype(np.float32), kind="stable")[:A]
+            n_keep[b] = len(order)
+            det[b, :len(order), :4], det[b, :len(order), 4], det[b, :len(order), 5] = rows[order], score[order], lab[order]
+        out.append(dict(det=det, n_keep=n_keep, t_ref=np.full(B, t0 + step_us * k, np.int64), gt_box=gt_box, gt_label=gt_label,
+                        gt_id=gt_id, n_gt=n_gt))
+    return out
+
+
 def batch_windows(gen,n_per_sample, batch_size, width, height, seed, **kw):
     """Concatenate ``batch_size`` independent windows like PyG ``Batch`` collation does:
     returns x,y,t,p and ``batch`` (int64 sample index, sorted)."""

@@ -625,6 +625,65 @@ int dagr_stream_track_cv_rescue(void *tracks, size_t bytes, int32_t B, int32_t m
                                 int64_t *untracked /* [B], accumulated; may be NULL */, float low_score, float low_iou,
                                 int64_t *rescued /* [B], accumulated; may be NULL */, void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * Event stream scorer: the track ids of a step against labelled boxes, on the device
+ *   dagr_stream_score scores what a dagr_stream_track* entry left for a step -- det, n_keep, track_id and, optionally, the
+ *   motion model's track_box -- against ground-truth boxes that carry an identity, and accumulates the CLEAR-MOT counts
+ *   (Bernardin & Stiefelhagen): misses, false positives, identity switches, fragmentations.  The matcher is greedy in
+ *   ground-truth row order inside a label, not a minimum-cost assignment; agreement with another MOT tool is not claimed.
+ *   One launch (one wave per lane), no host synchronisation, no global atomics: the lane's wave owns the lane's state.
+ *   dagr_amd/streaming.py: ScoreDefinition is the same in numpy, integer for integer.
+ *
+ * One call is one scored step of every lane b with n_gt[b] >= 0 (n_gt[b] < 0: the lane has no labels at this instant and
+ * not one byte of its state or of its outputs changes; n_gt[b] > G is clamped):
+ *   hypotheses: the rows i < clamp(n_keep[b], 0, A) with track_id[b, i] != 0, in row order; the first DAGR_TRACK_MAX_DETS
+ *             take part, each further one adds 1 to unscored_hyp.  A row without an id is neither a match nor a false
+ *             positive.  The box is det's, or track_box[b, i] when track_box is given; the label is (int32_t)det[b, i, 5];
+ *   slots:    the ground-truth rows in row order.  Unscored (outcome -1, unscored_gt += 1, takes part in nothing): gt_id <= 0,
+ *             an earlier row of this step with the same gt_id, or a new identity and a full table.  Otherwise the row finds
+ *             its slot by id, or takes slot n_objects++;
+ *   keep:     the scored rows in row order whose object has seen_step == steps - 1 and prev_hyp != 0: the FIRST hypothesis
+ *             row with that id is kept if it is still free, has the row's label and iou(gt, hyp) >= iou; kept += 1;
+ *   match:    the remaining scored rows in row order: among the free hypotheses of the row's label the largest
+ *             iou(gt, hyp) >= iou, the LOWEST row on a tie; a NaN IoU matches nothing.  The IoU is dagr_stream_track's,
+ *             with a the ground-truth box and b the hypothesis;
+ *   count:    per scored row gt += 1, present += 1, seen_step = steps.  Matched to track h: match += 1,
+ *             iou_q += (int64)rintf(iou * 1048576.0f); switch iff last_hyp != 0 && last_hyp != h (switch += 1,
+ *             switches += 1); fragmentation iff tracked > 0 && prev_hyp == 0 (frag += 1, frags += 1); then tracked += 1,
+ *             last_hyp = prev_hyp = h.  Unmatched: miss += 1, prev_hyp = 0.  An absent object's slot is untouched.  Then
+ *             hyp += participating hypotheses, false_pos += those left free, steps += 1.
+ *
+ * state: dagr_stream_score_bytes(B, max_objects) bytes (0: B outside 1..65535 or max_objects outside
+ *        1..DAGR_SCORE_MAX_OBJECTS), 16-byte aligned, dagr_stream_score_reset before the first step and to empty it.  With
+ *        n = B * max_objects it holds, back to back, slot s of lane b at index b * max_objects + s, all int64:
+ *          id        [n] at byte  0        (the ground-truth identity, > 0; slots at and behind n_objects[b] mean nothing)
+ *          last_hyp  [n] at byte  8 * n    (the track id of the object's last match ever; 0: none)
+ *          prev_hyp  [n] at byte 16 * n    (the track id of its match at its last scored step; 0: a miss)
+ *          seen_step [n] at byte 24 * n    (the lane's `steps` at its last scored step; -1: never)
+ *          present   [n] at byte 32 * n
+ *          tracked   [n] at byte 40 * n
+ *          switches  [n] at byte 48 * n
+ *          frags     [n] at byte 56 * n
+ *          lane      [B, 16] at byte 64 * n: n_objects, steps, gt, hyp, match, miss, false_pos, switch, frag, kept, iou_q,
+ *                    unscored_gt, unscored_hyp, and three words that stay 0 -- 64 * n + 128 * B bytes in all
+ * det fp32[B, A, 6], n_keep int32[B], track_id int64[B, A]; track_box fp32[B, A, 4], 16-byte aligned, or NULL: det's boxes.
+ * gt_box fp32[B, G, 4] (x1, y1, x2, y2; 16-byte aligned), gt_label int32[B, G], gt_id int64[B, G], n_gt int32[B],
+ * 0 <= G <= DAGR_SCORE_MAX_GT.  gt_match int64[B, G] (the track id, 0: a miss, -1: unscored) and gt_flags int32[B, G] (bit
+ * 0 switch, bit 1 fragmentation, bit 2 kept): both NULL or both given; rows at and behind n_gt[b] are left as they are.
+ * All in device memory.
+ * DAGR_ERR_INVALID_ARG before any launch: B, max_objects, G or A out of range, iou outside (0, 1] (NaN included), a state
+ * smaller than dagr_stream_score_bytes, NULL or misaligned arrays, only one of gt_match / gt_flags.
+ * ------------------------------------------------------------------------ */
+#define DAGR_SCORE_MAX_OBJECTS 1024
+#define DAGR_SCORE_MAX_GT 256
+size_t dagr_stream_score_bytes(int32_t B, int32_t max_objects);
+int dagr_stream_score_reset(void *state, size_t bytes, int32_t B, int32_t max_objects, void *stream);
+int dagr_stream_score(void *state, size_t bytes, int32_t B, int32_t max_objects, float iou,
+                      const float *det, const int32_t *n_keep, int32_t A, const int64_t *track_id,
+                      const float *track_box /* [B, A, 4] or NULL: det's boxes */,
+                      const float *gt_box, const int32_t *gt_label, const int64_t *gt_id, const int32_t *n_gt, int32_t G,
+                      int64_t *gt_match, int32_t *gt_flags, void *stream);
+
 /* The neighbour search alone, again, on the pixel index the last dagr_graph_build_window left in `workspace` (same N):
  * rewrites nbr_src / nbr_code / deg and the edge count.  For measurement (bench.py times the search kernels on their own
  * stream with HIP events); a product caller has no use for it. */

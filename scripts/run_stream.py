@@ -55,6 +55,13 @@ its id.  ``--track_low_iou I`` (needs ``--track_low_score``) gives that round an
 ``--track_iou``).  0.1 for ``L`` and 0.5 for ``--track_min_score`` are ByteTrack's conventions, not measured optima.  The
 number of rescued matches is printed with the summary.
 
+``--track_score`` (needs ``--track``): the track ids are scored against labelled boxes on the device (``dagr.streaming``:
+``EventStream(score=)``, this project's statement of the CLEAR-MOT counts with a greedy matcher; agreement with another MOT
+tool is not claimed).  The source must have ``labels(t_step)``, which returns ``None`` (no labels at this instant) or
+``(boxes fp32 [G, 4], labels [G], ids [G])`` for lane 0; the steps with labels are scored.  ``--track_score_iou V`` (needs
+``--track_score``) sets the overlap a match needs (default 0.5).  The built-in synthetic sequence has no labels and is
+refused.  Id switches, fragmentations, MOTA and MOTP are printed with the summary; the detections written do not change.
+
 ``--decode evt2|evt3``: the step's events are encoded as camera words (``dagr.data.evt.encode_events``, an encoder for
 synthetic sources, not a model of any camera) and pushed through ``step_words``; the stream decodes them on the device
 (``dagr.streaming``: ``EventStream(decode=)``) in front of the filter, the front and the window.  ``--max_decoded N`` sizes
@@ -68,7 +75,8 @@ import torch
 
 import _common as C
 from dagr.data.evt import encode_events
-from dagr.streaming import EventStream, _flicker_options, _motion_options, _rescue_options, _track_options
+from dagr.streaming import (EventStream, _flicker_options, _motion_options, _rescue_options, _score_options, _track_options,
+                            score_summary)
 from dagr.utils.buffers import DETECTION_DTYPE, detections_to_records
 from dagr.utils.logging import set_up_logging_directory
 from dagr.utils import synthetic as syn
@@ -116,6 +124,10 @@ def stream_options(p):
                    "detections with a confidence in [L, --track_min_score) continue a track (never start one)")
     g.add_argument("--track_low_iou", type=float, default=None, help="with --track_low_score: that round's own smallest IoU "
                    "in (0, 1] (default: --track_iou)")
+    g.add_argument("--track_score", action="store_true", help="with --track: score the track ids against the source's "
+                   "labelled boxes (source.labels), on the device")
+    g.add_argument("--track_score_iou", type=float, default=None, help="with --track_score: the IoU a match needs, in "
+                   "(0, 1] (default 0.5)")
     g.add_argument("--raw_frames", action="store_true", help="the source's frames are sensor-size BGR uint8 frames: prepare "
                    "them on the device (crop, shrink by the --downsample factor, / 255)")
 
@@ -177,6 +189,26 @@ def rescue_options(a):
         _rescue_options(given, _track_options(track_options(a), "run_stream.py"), "run_stream.py")
     except ValueError as e:
         raise SystemExit(str(e)) from None
+    return given
+
+
+def score_options(a, source=None):
+    """``score=`` of the stream the flags describe: None without ``--track_score``, else the options that were given.  With
+    ``source`` the refusal of a source without labels."""
+    given = {} if getattr(a, "track_score_iou", None) is None else dict(iou=a.track_score_iou)
+    if not getattr(a, "track_score", False):
+        if given:
+            raise SystemExit("run_stream.py: --track_score_iou needs --track_score")
+        return None
+    if not getattr(a, "track", False):
+        raise SystemExit("run_stream.py: --track_score needs --track")
+    try:
+        _score_options(given, _track_options(track_options(a), "run_stream.py"), None, "run_stream.py")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    if source is not None and not callable(getattr(source, "labels", None)):
+        raise SystemExit(f"run_stream.py: --track_score needs a source with labels(t_step); {type(source).__name__} has none "
+                         "(the built-in synthetic sequence carries no labelled boxes)")
     return given
 
 
@@ -294,7 +326,7 @@ def play(a, model, source, dev):
                          frame_size=raw_size, frame_bgr=True, max_lane_events=cap,
                          denoise_us=getattr(a, "denoise_us", None), refractory_us=getattr(a, "refractory_us", None),
                          flicker=flicker_options(a), trail_us=getattr(a, "trail_us", None),
-                         track=track_options(a), motion=motion_options(a), rescue=rescue_options(a),
+                         track=track_options(a), motion=motion_options(a), rescue=rescue_options(a), score=score_options(a),
                          decode=decode, max_decoded=getattr(a, "max_decoded", None),
                          t_base=int(source.t_range()[0]) if decode else None)      # (the words' times start at the sequence's)
     t0, t1 = source.t_range()
@@ -324,6 +356,11 @@ def play(a, model, source, dev):
             det = stream.step(xy, np.asarray(ev["t"], np.int64), np.asarray(ev["p"], np.int8), t_now=t_step, image=image,
                               frame=raw)
         out.append((t_step, det[0]))
+        labelled = source.labels(t_step) if stream.score is not None else None
+        if labelled is not None:                # one more launch, on the step's own device arrays
+            boxes, labels, ids = labelled
+            stream.score_step(np.asarray(boxes, np.float32).reshape(1, -1, 4), np.asarray(labels, np.int32).reshape(1, -1),
+                              np.asarray(ids, np.int64).reshape(1, -1))
         if stream.motion is not None:
             a.stream_coasting.append(coast_records(len(out) - 1, t_step, stream.coasting()))
     a.stream_steps = (stream.frame_steps, stream.held_steps)      # (frame bodies, held bodies) of the run
@@ -333,6 +370,10 @@ def play(a, model, source, dev):
     a.stream_decoded = {k: int(v.sum()) for k, v in stream.decode_counts().items()} if stream.decode is not None else None
     a.stream_untracked = int(stream.untracked().sum()) if stream.track is not None else None
     a.stream_rescued = int(stream.rescued().sum()) if stream.rescue is not None else None
+    a.stream_score = None
+    if stream.score is not None:
+        counters = stream.track_score()
+        a.stream_score = dict(score_summary(counters, stream.scored_objects())["total"], steps=int(counters["steps"].sum()))
     return out
 
 
@@ -358,6 +399,7 @@ def main(argv=None, model_factory=None, source=None):
     tracking = track_options(a) is not None
     moving = motion_options(a) is not None
     rescue_options(a)                      # (refusals in front of the model)
+    score_options(a)
     a.batch_size = 1                       # one sequence: one lane
     world, rank, dev = C.distributed()
     torch.manual_seed(42)
@@ -367,6 +409,7 @@ def main(argv=None, model_factory=None, source=None):
             print(f"NOTICE: --dataset_directory {a.dataset_directory}: run_stream.py does not read DSEC files; playing the "
                   "SYNTHETIC stand-in stream instead.", flush=True)
         source = SyntheticStream(a)
+    score_options(a, source)               # (a source without labels is refused in front of the model too)
     geometry = types.SimpleNamespace(width=int(getattr(source, "width", a.width)), height=int(getattr(source, "height", a.height)))
     args, net = (model_factory or C.build_model)(a, geometry, dev)
     net = net.eval()
@@ -414,6 +457,12 @@ def main(argv=None, model_factory=None, source=None):
             tracked += f"; {len(coast)} coasted track-steps -> {out_dir / f'coasting_{a.sequence}.npy'}"
         if a.stream_rescued is not None:
             tracked += f"; {a.stream_rescued} low-score detections rescued by the second round"
+        if a.stream_score is not None:
+            c = a.stream_score
+            tracked += (f"; scored {c['steps']} labelled steps: {c['objects']} objects, {c['switch']} id switches, "
+                        f"{c['frag']} fragmentations, {c['miss']} misses, {c['false_pos']} false positives, MOTA "
+                        f"{c['mota']:.3f}, MOTP {c['motp']:.3f}, {c['mostly_tracked']} mostly tracked, {c['mostly_lost']} "
+                        "mostly lost")
         print(f"{len(steps)} steps of {a.step_us} us on {window} in {seconds:.2f} s "
               f"({1e3 * seconds / max(1, len(steps)):.2f} ms per step; {a.stream_steps[0]} with the full window, "
               f"{a.stream_steps[1]} on held image maps) -> {path}: {len(rec)} detections{tracked}")

@@ -1,0 +1,306 @@
+"""Cases of the event stream's scorer (dagr_amd/streaming.py: ScoreDefinition, dagr_stream_score), shared by the CPU and the
+GPU tests.  A case is
+
+    name, B, A, G, score (the options),
+    steps: [dict(det fp32 [B, A, 6], n_keep int32 [B], track_id int64 [B, A], track_box fp32 [B, A, 4] or None,
+                 gt_box fp32 [B, G, 4], gt_label int32 [B, G], gt_id int64 [B, G], n_gt int32 [B])],
+    expect: None, or per step dict(match, flags: per lane the rows below the clamped n_gt, None for a skipped lane;
+                                   counters: per lane the tuple COUNTED, cumulative; objects: None or per lane the table).
+
+The hand cases give the hypotheses their track ids directly: 8 x 8 boxes that are shifted by whole pixels, so every IoU is a
+ratio of small integers (shift 0: 1, 1: 56 / 72, 2: 48 / 80, 3: 40 / 88 -- under the default 0.5).  Rows behind n_keep and
+behind n_gt are filled with boxes that would match everything: nothing may read them."""
+import numpy as np
+
+from tests import stream_motion_cases as mc
+from tests import stream_track_cases as tc
+
+T = tc.T
+COUNTED = ("gt", "hyp", "match", "miss", "false_pos", "switch", "frag", "kept", "unscored_gt", "unscored_hyp")
+PAD_GT = (0.0, 0.0, 1000.0, 1000.0)
+SWITCH, FRAG, KEPT = 1, 2, 4
+SCENE = dict(seed=4, B=2, objects=12, steps=120, A=32)                  # dagr_amd.utils.synthetic.track_scene
+SCENE_TRACK = dict(min_score=0.5, max_age_us=6000)
+VARIANTS = (("plain", None, None), ("motion", True, None), ("rescue", None, True), ("both", True, True))
+
+
+def hyp(x, y, ident, w=8, h=8, score=0.9, label=0):
+    """A detection row with its track id (0: a row the tracker gave none)."""
+    return (x, y, x + w, y + h, score, label), ident
+
+
+def gt(x, y, ident, w=8, h=8, label=0):
+    return (x, y, x + w, y + h), label, ident
+
+
+def step(hyps, gts, A, G, n_gt=None, n_keep=None):
+    """hyps: per lane a list of ``hyp(...)``; gts: per lane a list of ``gt(...)``."""
+    B = len(hyps)
+    s = tc._step([[r for r, _ in lane] for lane in hyps], T, A, n_keep=n_keep)
+    ids = np.full((B, A), 77, np.int64)                                 # behind n_keep: an id that nothing may read
+    gt_box = np.tile(np.asarray(PAD_GT, np.float32), (B, G, 1))
+    gt_label, gt_id = np.zeros((B, G), np.int32), np.full((B, G), 77, np.int64)
+    for b in range(B):
+        for i, (_, ident) in enumerate(hyps[b]):
+            ids[b, i] = ident
+        for g, (box, label, ident) in enumerate(gts[b]):
+            gt_box[b, g], gt_label[b, g], gt_id[b, g] = box, label, ident
+    counts = [len(lane) for lane in gts] if n_gt is None else n_gt
+    return dict(det=s["det"], n_keep=s["n_keep"], track_id=ids, track_box=None, gt_box=gt_box, gt_label=gt_label, gt_id=gt_id,
+                n_gt=np.asarray(counts, np.int32))
+
+
+def _case(name, steps, expect, score=True, A=4, G=4):
+    """steps: [(hyps, gts) or (hyps, gts, n_gt)]; expect: [(match, flags, counters) or (match, flags, counters, objects)]."""
+    return dict(name=name, B=len(steps[0][0]), A=A, G=G, score=score,
+                steps=[step(s[0], s[1], A, G, n_gt=s[2] if len(s) > 2 else None) for s in steps],
+                expect=[dict(match=e[0], flags=e[1], counters=e[2], objects=e[3] if len(e) > 3 else None) for e in expect])
+
+
+def _caps_hypotheses():
+    """A = 300 rows with ids on a grid of disjoint boxes, G = 256: the first 256 rows take part, 44 are unscored.  The
+    ground truth is the boxes of rows 44 .. 299: rows 44 .. 255 are matched, the boxes of rows 256 .. 299 are missed.  The
+    second step keeps every pair."""
+    rows = [hyp(20 * (i % 20), 20 * (i // 20), i + 1, 10, 10, label=i % 3) for i in range(300)]
+    truth = [gt(20 * (i % 20), 20 * (i // 20), 1000 + i, 10, 10, label=i % 3) for i in range(44, 300)]
+    match = [i + 1 if i < 256 else 0 for i in range(44, 300)]
+    return dict(name="300-rows-with-ids-256-take-part-and-256-labels", B=1, A=300, G=256, score=dict(max_objects=256),
+                steps=[step([rows], [truth], 300, 256)] * 2,
+                expect=[dict(match=[match], flags=[[0] * 256], counters=[(256, 256, 212, 44, 44, 0, 0, 0, 0, 44)], objects=None),
+                        dict(match=[match], flags=[[KEPT if m else 0 for m in match]],
+                             counters=[(512, 512, 424, 88, 88, 0, 0, 212, 0, 88)], objects=None)])
+
+
+def _caps_objects():
+    """max_objects = 1024 filled by four steps of 256 new identities; a fifth step's 256 new identities find the table
+    full, a sixth step's identities are the first step's and find their slots."""
+    def labels(first):
+        return [gt(20 * (g % 20), 20 * (g // 20), first + g, 10, 10) for g in range(256)]
+    rows = [hyp(0, 0, 5, 10, 10), hyp(20, 0, 6, 10, 10)]
+    firsts = [1, 257, 513, 769, 5000, 1]
+    expect, matched = [], 0
+    for k, first in enumerate(firsts):
+        full = first == 5000
+        matched += 0 if full else 2
+        scored = 256 * (k + 1 - (k >= 4))
+        # (step 5 keeps nothing: its objects were last seen at step 0, not at the step before)
+        expect.append(dict(match=[[-1] * 256 if full else [5, 6] + [0] * 254], flags=[[0] * 256],
+                           counters=[(scored, 2 * (k + 1), matched, scored - matched, 2 * (k + 1) - matched, 0, 0, 0,
+                                      256 if k >= 4 else 0, 0)], objects=None))
+    return dict(name="1024-objects-filled-over-four-steps-then-full", B=1, A=4, G=256, score=dict(max_objects=1024),
+                steps=[step([rows], [labels(f)], 4, 256) for f in firsts], expect=expect)
+
+
+def cases():
+    above_half = float(np.nextafter(np.float32(0.5), np.float32(1)))
+    one, no = hyp(0, 0, 5), []
+    out = [
+        _case("a-match-a-miss-a-false-positive",
+              [([[hyp(0, 0, 7), hyp(100, 100, 8)]], [[gt(0, 0, 1), gt(50, 50, 2)]])],
+              [([[7, 0]], [[0, 0]], [(2, 2, 1, 1, 1, 0, 0, 0, 0, 0)], [[(1, 7, 7, 0, 1, 1, 0, 0), (2, 0, 0, 0, 1, 0, 0, 0)]])]),
+        _case("a-row-without-an-id-is-neither-a-match-nor-a-false-positive",
+              [([[hyp(0, 0, 0), hyp(20, 0, 5)]], [[gt(0, 0, 1)]])],
+              [([[0]], [[0]], [(1, 1, 0, 1, 1, 0, 0, 0, 0, 0)])]),
+        _case("the-label-rule",
+              [([[hyp(0, 0, 3, label=1)]], [[gt(0, 0, 1, label=0)]]), ([[hyp(0, 0, 3, label=1)]], [[gt(0, 0, 1, label=1)]])],
+              [([[0]], [[0]], [(1, 1, 0, 1, 1, 0, 0, 0, 0, 0)]), ([[3]], [[0]], [(2, 2, 1, 1, 1, 0, 0, 0, 0, 0)])]),
+        # (0,0,4,4) against (0,0,4,2): inter 8, union (16 + 8) - 8 = 16: exactly 0.5
+        _case("an-iou-of-exactly-iou-matches",
+              [([[hyp(0, 0, 5, 4, 2)]], [[gt(0, 0, 1, 4, 4)]])], [([[5]], [[0]], [(1, 1, 1, 0, 0, 0, 0, 0, 0, 0)])], score=dict(iou=0.5)),
+        _case("an-iou-one-ulp-under-iou-does-not",
+              [([[hyp(0, 0, 5, 4, 2)]], [[gt(0, 0, 1, 4, 4)]])], [([[0]], [[0]], [(1, 1, 0, 1, 1, 0, 0, 0, 0, 0)])],
+              score=dict(iou=above_half)),
+        _case("a-tie-goes-to-the-lowest-row",
+              [([[hyp(0, 0, 9), hyp(0, 0, 4)]], [[gt(0, 0, 1)]])], [([[9]], [[0]], [(1, 2, 1, 0, 1, 0, 0, 0, 0, 0)])]),
+        # row 0 (shift 2, 0.6) takes the one hypothesis although row 1 equals it
+        _case("ground-truth-order-decides-between-two-objects",
+              [([[one]], [[gt(2, 0, 1), gt(0, 0, 2)]])], [([[5, 0]], [[0, 0]], [(2, 1, 1, 1, 0, 0, 0, 0, 0, 0)])]),
+        # the object keeps track 5 at 0.6 although track 6 sits exactly on it
+        _case("the-keep-round-overrides-a-larger-iou",
+              [([[one]], [[gt(0, 0, 1)]]), ([[hyp(1, 0, 6), hyp(3, 0, 5)]], [[gt(1, 0, 1)]])],
+              [([[5]], [[0]], [(1, 1, 1, 0, 0, 0, 0, 0, 0, 0)]), ([[5]], [[KEPT]], [(2, 3, 2, 0, 1, 0, 0, 1, 0, 0)])]),
+        # the same, but the object is absent from the step in between: no keep, the larger IoU wins, and that is a switch
+        _case("keep-needs-presence-at-the-previous-scored-step",
+              [([[one]], [[gt(0, 0, 1)]]), ([[one]], [[]]), ([[hyp(1, 0, 6), hyp(3, 0, 5)]], [[gt(1, 0, 1)]])],
+              [([[5]], [[0]], [(1, 1, 1, 0, 0, 0, 0, 0, 0, 0)]), ([[]], [[]], [(1, 2, 1, 0, 1, 0, 0, 0, 0, 0)]),
+               ([[6]], [[SWITCH]], [(2, 4, 2, 0, 2, 1, 0, 0, 0, 0)])]),
+        _case("a-switch-after-a-gap-of-misses-and-not-on-the-first-match",
+              [([[]], [[gt(0, 0, 1)]]), ([[one]], [[gt(0, 0, 1)]]), ([[]], [[gt(0, 0, 1)]]), ([[hyp(0, 0, 6)]], [[gt(0, 0, 1)]]),
+               ([[hyp(0, 0, 6)]], [[gt(0, 0, 1)]])],
+              [([[0]], [[0]], [(1, 0, 0, 1, 0, 0, 0, 0, 0, 0)]), ([[5]], [[0]], [(2, 1, 1, 1, 0, 0, 0, 0, 0, 0)]),
+               ([[0]], [[0]], [(3, 1, 1, 2, 0, 0, 0, 0, 0, 0)]), ([[6]], [[SWITCH | FRAG]], [(4, 2, 2, 2, 0, 1, 1, 0, 0, 0)]),
+               ([[6]], [[KEPT]], [(5, 3, 3, 2, 0, 1, 1, 1, 0, 0)], [[(1, 6, 6, 4, 5, 3, 1, 1)]])]),
+        _case("a-fragmentation-is-counted-once-per-break",
+              [([h], [[gt(0, 0, 1)]]) for h in ([one], no, no, [one], [one], no, [one])],
+              [([[5]], [[0]], [(1, 1, 1, 0, 0, 0, 0, 0, 0, 0)]), ([[0]], [[0]], [(2, 1, 1, 1, 0, 0, 0, 0, 0, 0)]),
+               ([[0]], [[0]], [(3, 1, 1, 2, 0, 0, 0, 0, 0, 0)]), ([[5]], [[FRAG]], [(4, 2, 2, 2, 0, 0, 1, 0, 0, 0)]),
+               ([[5]], [[KEPT]], [(5, 3, 3, 2, 0, 0, 1, 1, 0, 0)]), ([[0]], [[0]], [(6, 3, 3, 3, 0, 0, 1, 1, 0, 0)]),
+               ([[5]], [[FRAG]], [(7, 4, 4, 3, 0, 0, 2, 1, 0, 0)], [[(1, 5, 5, 6, 7, 4, 0, 2)]])]),
+        _case("an-absent-objects-slot-is-untouched",
+              [([[hyp(0, 0, 5), hyp(50, 0, 6)]], [[gt(0, 0, 1), gt(50, 0, 2)]]), ([[hyp(0, 0, 5), hyp(50, 0, 6)]], [[gt(50, 0, 2)]])],
+              [([[5, 6]], [[0, 0]], [(2, 2, 2, 0, 0, 0, 0, 0, 0, 0)], [[(1, 5, 5, 0, 1, 1, 0, 0), (2, 6, 6, 0, 1, 1, 0, 0)]]),
+               ([[6]], [[KEPT]], [(3, 4, 3, 0, 1, 0, 0, 1, 0, 0)], [[(1, 5, 5, 0, 1, 1, 0, 0), (2, 6, 6, 1, 2, 2, 0, 0)]])]),
+        # a duplicate id, id 0 and a negative id; then a table of two slots is full for the third identity
+        _case("a-duplicate-id-an-id-under-one-and-a-full-table-are-unscored",
+              [([[hyp(0, 0, 5), hyp(20, 0, 6)]], [[gt(0, 0, 1), gt(20, 0, 1), gt(40, 0, 0), gt(60, 0, -3)]]),
+               ([[one]], [[gt(50, 50, 2), gt(80, 80, 3), gt(0, 0, 1)]])],
+              [([[5, -1, -1, -1]], [[0, 0, 0, 0]], [(1, 2, 1, 0, 1, 0, 0, 0, 3, 0)], [[(1, 5, 5, 0, 1, 1, 0, 0)]]),
+               ([[0, -1, 5]], [[0, 0, KEPT]], [(3, 3, 2, 1, 1, 0, 0, 1, 4, 0)],
+                [[(1, 5, 5, 1, 2, 2, 0, 0), (2, 0, 0, 1, 1, 0, 0, 0)]])], score=dict(max_objects=2)),
+        _case("a-skipped-lane-keeps-every-byte-while-its-neighbours-count",
+              [([[one]] * 3, [[gt(0, 0, 1)]] * 3), ([[one]] * 3, [[gt(0, 0, 1)]] * 3, [1, -1, 1]), ([[one]] * 3, [[gt(0, 0, 1)]] * 3)],
+              [([[5]] * 3, [[0]] * 3, [(1, 1, 1, 0, 0, 0, 0, 0, 0, 0)] * 3),
+               ([[5], None, [5]], [[KEPT], None, [KEPT]], [(2, 2, 2, 0, 0, 0, 0, 1, 0, 0), (1, 1, 1, 0, 0, 0, 0, 0, 0, 0),
+                                                            (2, 2, 2, 0, 0, 0, 0, 1, 0, 0)]),
+               ([[5]] * 3, [[KEPT]] * 3, [(3, 3, 3, 0, 0, 0, 0, 2, 0, 0), (2, 2, 2, 0, 0, 0, 0, 1, 0, 0),
+                                          (3, 3, 3, 0, 0, 0, 0, 2, 0, 0)])]),
+        _case("n-gt-above-G-is-clamped",
+              [([[hyp(0, 0, 5), hyp(20, 0, 6)]], [[gt(0, 0, 1), gt(20, 0, 2)]], [5])],
+              [([[5, 6]], [[0, 0]], [(2, 2, 2, 0, 0, 0, 0, 0, 0, 0)])], G=2),
+        # 0 / 0: an empty box on an empty box is a NaN IoU
+        _case("a-degenerate-box-gives-a-nan-iou-and-matches-nothing",
+              [([[hyp(5, 5, 5, 0, 0)]], [[gt(5, 5, 1, 0, 0)]])], [([[0]], [[0]], [(1, 1, 0, 1, 1, 0, 0, 0, 0, 0)])]),
+        _caps_hypotheses(),
+        _caps_objects(),
+    ]
+    return out
+
+
+WALKS = [(m, boxes, iou) for m in (40, 64, 130) for boxes in ("det", "track") for iou in (0.3, 0.5)]
+_WALKS = {}
+
+
+def walk(max_objects, boxes, iou):
+    """``tests/stream_motion_cases.random_walk`` (B = 3, A = 64, 40 steps, the motion tracker with 64 slots) with ground
+    truth: the walk's generator is replayed here draw for draw -- the detections it gives are asserted to be the walk's --
+    to learn which object every row shows.  The ground truth of a step is EVERY object of the lane, hidden ones included
+    (they are missed), at its true box with a jitter of its own of half a pixel; an object that comes back after six or
+    more hidden steps comes back under a new identity, as a re-labelled object does, so that a lane sees more than 40
+    identities: max_objects = 40 fills the table, 64 is one table word a thread, 130 leaves a tail.  The track ids (and
+    ``track_box``) are ``TrackDefinition``'s on the host."""
+    key = (max_objects, boxes, iou)
+    if key in _WALKS:
+        return _WALKS[key]
+    B, A, objects, steps, seed = 3, 64, 36, 40, 5
+    # alpha = 0.5: a matched row's track_box lies between the prediction and the row, so boxes="track" is not boxes="det"
+    case = dict(mc.random_walk(64, motion=dict(alpha=0.5, beta=0.25)), name="motion-walk-64-alpha-half-for-the-scorer")
+    tracked, _ = mc.run_definition(case)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    truth_rng = np.random.Generator(np.random.PCG64(seed + 1000))
+    centre = rng.uniform(40, 280, (B, objects, 2))
+    speed = rng.uniform(-5, 5, (B, objects, 2))
+    size = rng.uniform(12, 40, (B, objects, 2))
+    label = rng.integers(0, 2, (B, objects))
+    hidden_until = np.zeros((B, objects), np.int64)
+    hidden_from = np.zeros((B, objects), np.int64)
+    ident = np.tile(np.arange(1, objects + 1, dtype=np.int64), (B, 1))
+    next_ident = np.full(B, objects + 1, np.int64)
+    out = []
+    for k in range(steps):
+        centre += speed
+        seen_at = centre + rng.normal(0, 0.3, centre.shape)
+        size *= rng.uniform(0.99, 1.01, size.shape)
+        back = (hidden_until == k) & (hidden_until - hidden_from >= 6)             # re-labelled on its return
+        for b, o in zip(*np.nonzero(back)):
+            ident[b, o], next_ident[b] = next_ident[b], next_ident[b] + 1
+        vanish = (rng.random((B, objects)) < 0.08) & (hidden_until <= k)
+        hidden_from[vanish] = k
+        hidden_until[vanish] = k + rng.integers(2, 10, int(vanish.sum()))
+        det = np.tile(np.asarray(tc.PAD, np.float32), (B, A, 1))
+        for b in range(B):
+            seen = np.flatnonzero(hidden_until[b] <= k)
+            score = rng.uniform(0.05, 1.0, len(seen)).astype(np.float32)
+            for i, j in enumerate(np.argsort(-score, kind="stable")[:A]):
+                o = seen[j]
+                det[b, i] = (seen_at[b, o, 0] - size[b, o, 0] / 2, seen_at[b, o, 1] - size[b, o, 1] / 2,
+                             seen_at[b, o, 0] + size[b, o, 0] / 2, seen_at[b, o, 1] + size[b, o, 1] / 2, score[j], label[b, o])
+        s = case["steps"][k]
+        assert det.tobytes() == s["det"].tobytes(), ("the replay has left tests/stream_motion_cases.random_walk", k)
+        at = centre + truth_rng.normal(0, 0.5, centre.shape)
+        gt_box = np.concatenate([at - size / 2, at + size / 2], -1).astype(np.float32)
+        G = 40
+        pad = np.tile(np.asarray(PAD_GT, np.float32), (B, G - objects, 1))
+        out.append(dict(det=s["det"], n_keep=s["n_keep"], track_id=tracked[k]["ids"], track_box=tracked[k]["box"],
+                        gt_box=np.concatenate([gt_box, pad], 1),
+                        gt_label=np.concatenate([label.astype(np.int32), np.zeros((B, G - objects), np.int32)], 1),
+                        gt_id=np.concatenate([ident, np.full((B, G - objects), 77, np.int64)], 1),
+                        n_gt=np.full(B, objects, np.int32)))
+    _WALKS[key] = dict(name=f"score-walk-{max_objects}-{boxes}-{iou}", B=B, A=A, G=40, steps=out, expect=None,
+                       score=dict(max_objects=max_objects, boxes=boxes, iou=iou))
+    return _WALKS[key]
+
+
+_SCENE = []
+
+
+def scene():
+    """The committed labelled scene (``dagr_amd.utils.synthetic.track_scene(**SCENE)``), made once."""
+    if not _SCENE:
+        from dagr_amd.utils.synthetic import track_scene
+        _SCENE.append(track_scene(**SCENE))
+    return _SCENE[0]
+
+
+_CHAINS = {}
+
+
+def scene_chain(variant, steps=None):
+    """The scene through ``TrackDefinition`` (plain / motion / rescue / both) under ``ScoreDefinition``: ``(the scorer, the
+    tracker)`` after ``steps`` steps (None: all).  Computed once per variant and shared: nobody changes what comes back."""
+    if (variant, steps) not in _CHAINS:
+        from dagr_amd.streaming import ScoreDefinition, TrackDefinition
+        _, motion, rescue = next(v for v in VARIANTS if v[0] == variant)
+        d, sc = TrackDefinition(SCENE["B"], SCENE_TRACK, motion=motion, rescue=rescue), ScoreDefinition(SCENE["B"], True)
+        for s in scene()[:steps]:
+            ids, _ = d.step(s["det"], s["n_keep"], s["t_ref"])
+            sc.step(s["det"], s["n_keep"], ids, s["gt_box"], s["gt_label"], s["gt_id"], s["n_gt"])
+        _CHAINS[(variant, steps)] = (sc, d)
+    return _CHAINS[(variant, steps)]
+
+
+SENTINEL = -7
+_RESULTS = {}
+
+
+def table(d):
+    """The definition's object tables as one int64 [8, B, max_objects] array in the order of ``SCORE_OBJECT_FIELDS``."""
+    from dagr_amd.streaming import SCORE_OBJECT_FIELDS
+    return np.stack([getattr(d, name) for name in SCORE_OBJECT_FIELDS])
+
+
+def run_definition(case):
+    """After every step of a case the definition's ``dict(match, flags, counters, n_objects, table)`` -- match and flags
+    written over the sentinel -7, as a device test writes them --, and the definition itself last.  Computed once per case
+    name and shared: nobody changes what comes back."""
+    if case["name"] in _RESULTS:
+        return _RESULTS[case["name"]]
+    from dagr_amd.streaming import ScoreDefinition
+    d = ScoreDefinition(case["B"], case["score"])
+    out = []
+    for s in case["steps"]:
+        match, flags = np.full((case["B"], case["G"]), SENTINEL, np.int64), np.full((case["B"], case["G"]), SENTINEL, np.int32)
+        d.step(s["det"], s["n_keep"], s["track_id"], s["gt_box"], s["gt_label"], s["gt_id"], s["n_gt"], track_box=s["track_box"],
+               out=(match, flags))
+        out.append(dict(match=match, flags=flags, counters={k: v.copy() for k, v in d.counters.items()},
+                        n_objects=d.n_objects.copy(), table=table(d)))
+    _RESULTS[case["name"]] = (out, d)
+    return out, d
+
+
+def check_expectation(case, k, match, flags, counters, objects):
+    """The written-out expectation of step ``k`` against ``match`` / ``flags`` [B, G], ``counters`` (name -> [B]) and
+    ``objects`` (per lane a ``SCORE_OBJECT_DTYPE`` array)."""
+    e, s, where = case["expect"][k], case["steps"][k], (case["name"], k)
+    for b in range(case["B"]):
+        assert tuple(int(counters[name][b]) for name in COUNTED) == tuple(e["counters"][b]), (where, b, "counters")
+        if e["match"][b] is None:                                                   # a skipped lane: nothing was written
+            assert s["n_gt"][b] < 0, where
+            continue
+        n = min(int(s["n_gt"][b]), case["G"])
+        assert len(e["match"][b]) == n and len(e["flags"][b]) == n, where
+        assert np.asarray(match)[b, :n].tolist() == e["match"][b], (where, b, "gt_match")
+        assert np.asarray(flags)[b, :n].tolist() == e["flags"][b], (where, b, "gt_flags")
+        if e["objects"] is not None:
+            assert [tuple(int(v) for v in row) for row in objects[b]] == e["objects"][b], (where, b, "objects")
+    assert np.asarray(counters["steps"]).tolist() == [sum(1 for q in case["steps"][:k + 1] if q["n_gt"][b] >= 0)
+                                                      for b in range(case["B"])], (where, "steps")
