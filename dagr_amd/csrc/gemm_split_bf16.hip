@@ -41,6 +41,21 @@
 // A-row addressing (Geo): plain rows with a pitch; a 1x1 convolution with spatial stride (reads every s-th pixel in place);
 // a 3x3 / stride 1 / pad 1 convolution on an NHWC map, K = (tap, channel) -- a K-slice lies inside one tap because C is a
 // multiple of 32, taps outside the image (which also closes the seam between two images of the batch) read as zero.
+//
+// Nothing of the addressing is vector work inside the K loop (profiles/split_bf16_addressing.md).  The A view and the packed
+// planes each sit behind one buffer descriptor.  A lane's byte offset of each of its rows is computed once in front of the
+// loop; what a slice adds to it is the same for every lane and travels as the load's scalar offset: k0 for the 1x1 forms, the
+// tap's pixel offset and the channel for the 3x3, kept as counters that step by 32 channels (no division by C).  A row that
+// must read as zero -- beyond M, or for the 3x3 a tap outside the image -- has an offset of 2^31 (or that bit set), past the
+// descriptor's extent, and the range check of the load returns zeros: there is no select on the address and none on the
+// values.  The 3x3 keeps nine validity bits per row, computed once, and spends two vector instructions per row and slice to
+// move the current tap's bit to bit 31 of the offset; its descriptor starts W + 1 pixels in front of the map, so every tap's
+// scalar offset is non-negative (nothing is read in front of the map: those taps are masked).  The W pieces take the fixed
+// 16 lane as their offset and the piece's place as a scalar offset there and M0 here; the wave index comes through
+// readfirstlane so that the compiler knows it uniform.  That is why the entry points refuse an A view (or packed planes) of
+// 2^31 bytes or more: offsets are 32 bits, and a masked offset plus any slice's scalar offset must stay below 2^32.
+// Steady-state loop, vector instructions other than MFMA per two slices: 96 on 64 x 64 (142 before), 61 on the eight-wave
+// tile (92), 98 on the 64 x 64 3x3 (188); the MFMA / VALU interleave is fitted to those counts (interleave<>()).
 #include <algorithm>
 #include <type_traits>
 
@@ -62,14 +77,21 @@ struct Geo {
 };
 
 struct Args {
-    const float *A;
+    const float *A;            // base of the A descriptor: the first element of the view (MODE 2: W + 1 pixels in front of it)
     const unsigned short *Wp;
     const float *bias, *R;
     float *D;
     int64_t M, lda, ldr, ldd;
     int K, N, Npad, act, n_tiles_n, n_blocks;
+    unsigned a_bytes, w_bytes; // extents of the two descriptors (num_records)
     Geo g;
 };
+
+// A lane's byte offset of a row that must read as zero: past every descriptor extent (those are below 2^31, view_bytes()
+// below), and still below 2^32 with any scalar offset of a slice added to it, so the sum does not wrap back into range.
+constexpr unsigned kMasked = 0x80000000u;
+// descriptor word 3 of a raw (unstructured, 32-bit data) buffer on gfx9
+constexpr int kRsrcFlags = 0x00020000;
 
 __device__ __forceinline__ unsigned short bf16_bits(__bf16 v) { return __builtin_bit_cast(unsigned short, v); }
 
@@ -135,6 +157,18 @@ __device__ __forceinline__ void wait_all_barrier(f32x4 (&ra)[2][N]) {
     asm volatile("" ::: "memory");
 }
 
+// One MFMA, then its share of the slice's V vector instructions, N times: V / N of them on average, placed as evenly as whole
+// numbers allow (the sizes of sched_group_barrier are compile-time constants).
+template <int I, int N, int V>
+__device__ __forceinline__ void interleave() {
+    if constexpr (I < N) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        constexpr int n = (I + 1) * V / N - I * V / N;
+        if constexpr (n > 0) __builtin_amdgcn_sched_group_barrier(0x002, n, 0);
+        interleave<I + 1, N, V>();
+    }
+}
+
 // Waves per SIMD that the registers are budgeted for (the second argument of __launch_bounds__).  Four waves: 2 with 128
 // columns, 3 with 64.  Eight waves on 64 x 128: two blocks of 73 728 B of LDS fit in a CU, sixteen waves, 4 per SIMD, so
 // 128 registers.
@@ -159,63 +193,82 @@ __global__ __launch_bounds__(128 * WN, waves_per_simd(BN, WN)) void k_gemm_split
     const int64_t m0 = (int64_t)mt * BM;
     const int n0 = nt * BN;
 
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    // the wave index through readfirstlane: uniform to the compiler as well, so what hangs on it (the W pieces' source
+    // and LDS addresses, M0) is scalar arithmetic
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave / WN, wn = wave % WN;
 
     // ---- staging geometry of this thread: rows r0 + kRS i, 4 consecutive k at 4 c4
+    // Every A row comes through one buffer descriptor over the whole view.  A lane's byte offset of row i (voff) is
+    // computed here, once; what a K-slice adds (its k0, for MODE 2 its tap and channel) is the same for all lanes and
+    // goes into the load's scalar offset.  A row beyond M has the offset kMasked, which the descriptor's range check
+    // answers with zeros: no select on the address, none on the values.
     constexpr int kRS = NT / 8;           // rows that the block's threads cover at once
     const int r0 = t >> 3, c4 = t & 7;
-    // MODE 1 keeps an offset per row; the other two derive it from the first row's (rows kRS apart, a uniform step)
-    int64_t rowoff[MODE == 1 ? AI : 1];
-    int ryx[MODE == 2 ? AI : 1];          // MODE 2: y << 16 | x of the row's pixel
+    unsigned voff[AI];
+    unsigned tapout[MODE == 2 ? AI : 1];  // MODE 2: bit `tap` set where that tap of the row's pixel is outside the image
+    tapout[0] = 0;
     const int64_t mrow0 = m0 + r0;
-    rowoff[0] = (mrow0 < a.M ? mrow0 : 0) * a.lda;
-    ryx[0] = 0;
 #pragma unroll
     for (int i = 0; i < AI; i++) {
         const int64_t m = mrow0 + kRS * i;
-        const int64_t mm = m < a.M ? m : 0;
+        const bool ok = m < a.M;
+        const int64_t mm = ok ? m : 0;
+        int64_t pix = mm;
         if (MODE == 1) {
             const int64_t b = mm / ((int64_t)a.g.Ho * a.g.Wo);
             const int rem = (int)(mm - b * (int64_t)a.g.Ho * a.g.Wo);
             const int yo = rem / a.g.Wo, xo = rem - yo * a.g.Wo;
-            rowoff[MODE == 1 ? i : 0] = ((b * a.g.H + (int64_t)yo * a.g.s) * a.g.W + (int64_t)xo * a.g.s) * a.lda;
+            pix = (b * a.g.H + (int64_t)yo * a.g.s) * a.g.W + (int64_t)xo * a.g.s;
         } else if (MODE == 2) {
-            ryx[MODE == 2 ? i : 0] = (int)((mm / a.g.W) % a.g.H) << 16 | (int)(mm % a.g.W);
+            const int y = (int)((mm / a.g.W) % a.g.H), x = (int)(mm % a.g.W);
+            unsigned out = 0;
+#pragma unroll
+            for (int tap = 0; tap < 9; tap++) {
+                const int dy = tap / 3 - 1, dx = tap % 3 - 1;
+                const bool in = ok && (unsigned)(y + dy) < (unsigned)a.g.H && (unsigned)(x + dx) < (unsigned)a.g.W;
+                out |= (in ? 0u : 1u) << tap;
+            }
+            tapout[MODE == 2 ? i : 0] = out;
         }
+        voff[i] = ok ? (unsigned)(pix * a.lda * 4 + c4 * 16) : MODE == 2 ? 0u : kMasked;
     }
+    const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.A), 0, (int)a.a_bytes, kRsrcFlags);
 
     static_assert(AI == 1 || AI == 2, "wait_all_barrier names the register sets");
     f32x4 ra[2][AI];                   // two register sets: slice kt + 1 is split out of one while kt + 2 arrives in the other
-    unsigned okmask[2] = {0, 0};
 
-    // the A rows of K-slice kt, fp32, into register set `set`
+    // MODE 2: where the next slice to send for lies, kept as counters (a slice lies inside one tap: C is a multiple of 32).
+    // The descriptor's base is W + 1 pixels in front of the map, so the tap (ty, tx) = (dy + 1, dx + 1) adds the
+    // non-negative (ty W + tx) pixels; nothing is read in front of the map, because those taps are masked.
+    const int n_kt = a.K / kKT;
+    int nx_kt = 0, nx_c0 = 0, nx_tx = 0;
+    unsigned nx_tapoff = 0, nx_shift = 31;            // byte offset of the tap; 31 - tap
+    const unsigned pix_bytes = (unsigned)a.lda * 4u;
+
+    // the A rows of the next K-slice (MODE 0 / 1: of slice kt), fp32, into register set `set`
     auto gload = [&](auto set, int kt) {
         constexpr int S = decltype(set)::value;
-        const int k0 = kt * kKT;
-        int c0 = k0, dy = 0, dx = 0;
-        int64_t toff = 0;
-        if (MODE == 2) {
-            const int tap = k0 / a.g.C;
-            c0 = k0 - tap * a.g.C;
-            dy = tap / 3 - 1;
-            dx = tap - (tap / 3) * 3 - 1;
-            toff = (int64_t)(dy * a.g.W + dx) * a.lda;
-        }
-        okmask[S] = 0;
+        unsigned soff = (unsigned)kt * (kKT * 4);
+        if (MODE == 2) soff = nx_tapoff + (unsigned)nx_c0 * 4u;
 #pragma unroll
         for (int i = 0; i < AI; i++) {
-            bool ok = mrow0 + kRS * i < a.M;
-            if (MODE == 2) {
-                const int yx = ryx[MODE == 2 ? i : 0];
-                ok = ok && (unsigned)((yx >> 16) + dy) < (unsigned)a.g.H && (unsigned)((yx & 0xffff) + dx) < (unsigned)a.g.W;
-            }
-            const int64_t off = MODE == 1 ? rowoff[MODE == 1 ? i : 0] : rowoff[0] + (int64_t)(kRS * i) * a.lda;
-            // a masked row reads the first 16 bytes of A (always there) and is zeroed when it is written to LDS: a select
-            // on the address, not a branch around the load
-            const float *p = ok ? a.A + off + toff + c0 + c4 * 4 : a.A;
-            ra[S][i] = *reinterpret_cast<const f32x4 *>(p);
-            okmask[S] |= (ok ? 1u : 0u) << i;
+            unsigned v = voff[i];
+            // the tap's bit to bit 31: a pixel whose tap is outside the image reads at kMasked | offset
+            if (MODE == 2) v |= (tapout[MODE == 2 ? i : 0] << nx_shift) & kMasked;
+            ra[S][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, (int)v, (int)soff, 0));
+        }
+        if (MODE == 2) {
+            // step to the slice behind it, all in scalar selects; the last slice stays (it is sent for again past the end
+            // and never used)
+            const bool more = nx_kt + 1 < n_kt;
+            const bool tapstep = more && nx_c0 + kKT == a.g.C;
+            const bool rowstep = tapstep && nx_tx == 2;
+            nx_kt += more ? 1 : 0;
+            nx_c0 = tapstep ? 0 : more ? nx_c0 + kKT : nx_c0;
+            nx_shift -= tapstep ? 1u : 0u;
+            nx_tapoff += rowstep ? (unsigned)(a.g.W - 2) * pix_bytes : tapstep ? pix_bytes : 0u;
+            nx_tx = rowstep ? 0 : tapstep ? nx_tx + 1 : nx_tx;
         }
     };
 
@@ -225,8 +278,7 @@ __global__ __launch_bounds__(128 * WN, waves_per_simd(BN, WN)) void k_gemm_split
         unsigned short *const ldsA = lds + s * kStage;
 #pragma unroll
         for (int i = 0; i < AI; i++) {
-            const bool ok = (okmask[S] >> i) & 1u;
-            const f32x4 v = ok ? ra[S][i] : f32x4{0.f, 0.f, 0.f, 0.f};
+            const f32x4 v = ra[S][i];
             unsigned lo[3], hi[3];
             split3x2(v[0], v[1], lo[0], lo[1], lo[2]);
             split3x2(v[2], v[3], hi[0], hi[1], hi[2]);
@@ -239,16 +291,18 @@ __global__ __launch_bounds__(128 * WN, waves_per_simd(BN, WN)) void k_gemm_split
     };
 
     // The W image of K-slice kt, global -> LDS with no register in between.  The packed planes already are the LDS image,
-    // so every piece is 1 KB contiguous on both sides (the LDS side of this load is wave-uniform base + 16 lane).
-    const char *const wsrc = reinterpret_cast<const char *>(a.Wp) + ((int64_t)n0 * kKT) * 2 + lane * 16;
+    // so every piece is 1 KB contiguous on both sides: through a descriptor over the packed planes the lane's part is the
+    // fixed 16 lane on both sides, and the piece's place is a scalar offset there and M0 here.
+    const __amdgpu_buffer_rsrc_t wrsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(a.Wp), 0, (int)a.w_bytes, kRsrcFlags);
+    const int wlane = lane * 16;
     auto wload = [&](int kt, int s) {
 #pragma unroll
         for (int j = 0; j < kPieces; j++) {
             const int piece = wave * kPieces + j, p = piece / (BN / 16), sub = piece - p * (BN / 16);
-            const char *src = wsrc + (((int64_t)kt * 3 + p) * a.Npad * kKT + sub * 16 * kKT) * 2;
+            const unsigned soff = (unsigned)(((kt * 3 + p) * a.Npad + n0 + sub * 16) * (kKT * 2));
             unsigned short *dst = lds + s * kStage + (3 * BM + p * BN + sub * 16) * kKT;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                             (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, (__attribute__((address_space(3))) void *)dst, 16, wlane, (int)soff, 0, 0);
         }
     };
 
@@ -270,7 +324,6 @@ __global__ __launch_bounds__(128 * WN, waves_per_simd(BN, WN)) void k_gemm_split
     // kt + 1 (LDS-direct, into the other stage); between the MFMAs the vector ALU splits slice kt + 1, which arrived during
     // slice kt - 1, and writes it to the other stage.  Everything a slice sends for has the whole slice to arrive, and the
     // one wait in front of the barrier retires it.
-    const int n_kt = a.K / kKT;
     const std::integral_constant<int, 0> set0;
     const std::integral_constant<int, 1> set1;
 
@@ -317,12 +370,11 @@ __global__ __launch_bounds__(128 * WN, waves_per_simd(BN, WN)) void k_gemm_split
         __builtin_amdgcn_sched_barrier(0);                  // both kinds of load go out before anything else of the slice
         multiply(lds + S * kStage);
         lwrite(nxt, S ^ 1);
-        // spread the split's vector instructions between the MFMAs (an MFMA occupies the matrix pipe for four issue slots)
-#pragma unroll
-        for (int i = 0; i < 6 * MI * NI; i++) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-        }
+        // spread the slice's vector instructions evenly between its MFMAs (an MFMA occupies the matrix pipe for four issue
+        // slots).  Per slice: 20 for the split of a float4, 2 for a fragment's add to the running sum, and in MODE 2 two per
+        // row for the tap's mask and one select of the tap counters -- what the cross-compiled loop holds
+        // (profiles/split_bf16_addressing.md).
+        interleave<0, 6 * MI * NI, 20 * AI + 2 * MI * NI + (MODE == 2 ? 2 * AI + 1 : 0)>();
         wait_all_barrier(ra);
     };
 
@@ -414,6 +466,17 @@ inline int unsupported(const char *fn, const char *what) {
     return DAGR_ERR_UNSUPPORTED;
 }
 
+// Bytes from the first element of an A view of `rows` rows of K floats, `ld` floats apart, to the end of its last row, with
+// `front` more rows in front of it; -1 where that is 2^31 or more.  The kernel addresses the view through one buffer
+// descriptor with 32-bit offsets, and a masked row is the offset 2^31 (kMasked).
+inline int64_t view_bytes(int64_t rows, int64_t ld, int64_t K, int64_t front) {
+    const int64_t lim = (int64_t)1 << 31;
+    if (rows - 1 + front >= lim || ld >= lim) return -1;
+    const int64_t bytes = ((rows - 1 + front) * ld + K) * 4;       // below 2^64 / 4: no overflow
+    return bytes < lim ? bytes : -1;
+}
+constexpr const char *kViewTooLarge = "the A view spans 2^31 bytes or more (the kernel addresses it with 32-bit offsets)";
+
 }  // namespace
 }  // namespace dagr
 
@@ -476,14 +539,22 @@ int gemm_entry(const char *fn, const float *A, int64_t M, int32_t K, int64_t lda
     const int rc = check_common(fn, A, M, K, lda, packed, N, bias, R, ldr, act, D, ldd, code, max_code, done);
     if (done) return rc;
     SPLIT_CHECK(lda >= K && stride >= 1, "bad sizes");
+    const size_t wbytes = dagr_gemm_split_bf16_packed_bytes(K, N);
+    if (wbytes >= ((size_t)1 << 31)) return unsupported(fn, "the packed weights span 2^31 bytes or more");
     Args a{A, (const unsigned short *)packed, bias, R, D, M, lda, R ? ldr : 0, ldd, K, N, (int)align_up((size_t)N, kNPad), act,
-           0, 0, Geo{0, 0, 0, K, 1, 0, 0}};
-    if (stride == 1) return launch<0>(a, code, (hipStream_t)stream);
-    SPLIT_CHECK(B >= 1 && H >= 1 && W >= 1, "bad image sizes");
-    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    SPLIT_CHECK(M == (int64_t)B * Ho * Wo, "M is not B * ceil(H / stride) * ceil(W / stride)");
-    a.g = Geo{1, H, W, K, stride, Ho, Wo};
-    return launch<1>(a, code, (hipStream_t)stream);
+           0, 0, 0, (unsigned)wbytes, Geo{0, 0, 0, K, 1, 0, 0}};
+    int64_t rows = M;                                  // rows of the view that is read
+    if (stride != 1) {
+        SPLIT_CHECK(B >= 1 && H >= 1 && W >= 1, "bad image sizes");
+        const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+        SPLIT_CHECK(M == (int64_t)B * Ho * Wo, "M is not B * ceil(H / stride) * ceil(W / stride)");
+        a.g = Geo{1, H, W, K, stride, Ho, Wo};
+        rows = (int64_t)B * H * W;
+    }
+    const int64_t abytes = view_bytes(rows, lda, K, 0);
+    if (abytes < 0) return unsupported(fn, kViewTooLarge);
+    a.a_bytes = (unsigned)abytes;
+    return stride == 1 ? launch<0>(a, code, (hipStream_t)stream) : launch<1>(a, code, (hipStream_t)stream);
 }
 
 int conv3x3_entry(const char *fn, const float *X, int32_t B, int32_t H, int32_t W, int32_t C, int64_t ldx, const void *packed,
@@ -495,8 +566,13 @@ int conv3x3_entry(const char *fn, const float *X, int32_t B, int32_t H, int32_t 
     const int rc = check_common(fn, X, M, C, ldx, packed, N, bias, R, ldr, act, D, ldd, code, max_code, done);
     if (done) return rc;
     SPLIT_CHECK((int64_t)C * 9 < ((int64_t)1 << 31), "C too large");
-    Args a{X, (const unsigned short *)packed, bias, R, D, M, ldx, R ? ldr : 0, ldd, 9 * C, N, (int)align_up((size_t)N, kNPad), act,
-           0, 0, Geo{2, H, W, C, 1, H, W}};
+    const size_t wbytes = dagr_gemm_split_bf16_packed_bytes(9 * C, N);
+    if (wbytes >= ((size_t)1 << 31)) return unsupported(fn, "the packed weights span 2^31 bytes or more");
+    // the descriptor starts W + 1 pixels in front of the map (the tap (-1, -1) of its first pixel), so its extent has them too
+    const int64_t abytes = view_bytes(M, ldx, C, (int64_t)W + 1);
+    if (abytes < 0) return unsupported(fn, kViewTooLarge);
+    Args a{X - ((int64_t)W + 1) * ldx, (const unsigned short *)packed, bias, R, D, M, ldx, R ? ldr : 0, ldd, 9 * C, N,
+           (int)align_up((size_t)N, kNPad), act, 0, 0, (unsigned)abytes, (unsigned)wbytes, Geo{2, H, W, C, 1, H, W}};
     return launch<2>(a, code, (hipStream_t)stream);
 }
 #undef SPLIT_CHECK

@@ -213,14 +213,16 @@ def _split_min_rows(K, N, taps):
         43.6 us), measured size only.
       1x1, K = 1024, N = 512 (layer4.0.conv1): won at 9 600 (68.2 against 78.4 us), measured size only.  K = 1024, N = 2048
         (layer4.0.downsample, read in place with stride 2): re-measured in profiles/split_bf16_loop.md, 71.3 - 71.8 against
-        88.0 - 88.9 us in two tables (spreads up to 2.6), admitted at 2 400 rows, measured size only.  The other K >= 1024
-        classes: 9 600 x 1024 x 256 gained 2.3 us of 44.6 with a spread of 1.2 and 0.5 - 1.1 of 42 when re-measured, too near
-        it; 2 400 x 2048 x 512 lost (52.6 against 42.9 us, 49.5 against 41.6).
+        88.0 - 88.9 us in two tables (spreads up to 2.6), admitted at 2 400 rows, measured size only.  K = 1024, N = 256
+        (layer3.1-5.conv1): too near the library until the kernel's addressing left the K loop; re-measured in
+        profiles/split_bf16_addressing.md, 39.1 - 39.6 against 42.6 - 42.7 us in two tables (spreads up to 0.6), admitted at
+        9 600 rows, measured size only.  2 400 x 2048 x 512 still loses (47.4 - 47.8 against 41.9 - 42.6 us).
       1x1 of layer1 (64 -> 64, 256 -> 64, 64 -> 256): won at 153 600 (12 - 27 %), measured size only.
       1x1 with K < 64 or N < 64 (the narrow dconvs): not measured, not selected.
       3x3 stride 1: C = 128 won at M = 38 400 (30 %); the bound stays at 32 768, where the image branch's own tests hold
         it (at 2 160 the 32 x 64 tile now wins too, 21.8 against 28.0 us; not admitted).  C = 64 won at 153 600 (35 %) and
-        C = 256 at 9 600 (23 %), both measured size only.  C = 512 tied at 2 400 (118.9 against 117.4 us)."""
+        C = 256 at 9 600 (23 %), both measured size only.  C = 512 ties at 2 400 (112.0 - 112.9 against 114.0 us, spreads of 4)
+        with the tile the kernel picks; the eight-wave tile, which it does not pick for a 3x3, ran in 107.8 - 108.4."""
     if taps == 1:
         if K < 64 or N < 64:
             return None
@@ -230,7 +232,7 @@ def _split_min_rows(K, N, taps):
             return 512
         if K <= 512:
             return 2400 if N >= 256 else 38400
-        return {(1024, 512): 9600, (1024, 2048): 2400}.get((K, N))
+        return {(1024, 256): 9600, (1024, 512): 9600, (1024, 2048): 2400}.get((K, N))
     if taps == 9 and K == N:
         return {64: 153600, 128: 32768, 256: 9600}.get(K)
     return None
@@ -260,6 +262,10 @@ def _split_conv(x, planes, taps, stride, N, bias, r, relu):
     xn = x.permute(0, 2, 3, 1)
     if rows is None or M < rows or not (x.is_cuda and x.dtype == torch.float32 and xn.is_contiguous()) \
             or (r is not None and not (r.is_contiguous() and tuple(r.shape) == (B, Ho, Wo, N))):
+        return None
+    # the kernel addresses the map through one buffer descriptor with 32-bit offsets and refuses a view of 2^31 bytes or
+    # more (a 3x3's starts W + 1 pixels in front of the map); such a map stays with the library
+    if ((B * H * W - 1 + (W + 1 if taps == 9 else 0)) * C + C) * 4 >= 1 << 31:
         return None
     y = torch.empty((B, Ho, Wo, N), dtype=torch.float32, device=x.device)
     L, st = _lib.lib(), _lib.cur_stream(x.device)
@@ -1587,6 +1593,12 @@ class WindowEngine:
         net.module.forward_features = types.MethodType(_resnet_features_forward, net.module)
         _gemmify_1x1(net.feature_dconv)
         _gemmify_1x1(net.output_dconv)
+        # the dconvs are 1x1 GEMMs like the trunk's: the same rule selects them (feature_dconv[1], 256 -> 64 on the layer1
+        # map, is the shape of layer1.1-2.conv1; output_dconv[0], 1024 -> 256 on the layer3 map, that of layer3.1-5.conv1)
+        for dconvs in (net.feature_dconv, net.output_dconv):
+            for m in dconvs.modules():
+                if isinstance(m, _Conv1x1Gemm) and _split_min_rows(m.wt.shape[0], m.wt.shape[1], 1) is not None:
+                    m.planes = _split_pack(m.wt)
         self._net_f, self._cnn_f = net, cnn
 
     def image_branch_paths(self):
