@@ -450,7 +450,11 @@ class StreamState:
 
     A scoring stream (``enable_score``, on a tracking stream) owns the scorer's state (``dagr_stream_score``): the lanes'
     object tables and counters, allocated next to the tracker's, and the ``gt_match`` / ``gt_flags`` of the last scored
-    step.  A step launches nothing for it: ``run_score`` is the one launch, on the last step's device arrays."""
+    step.  A step launches nothing for it: ``run_score`` is the one launch, on the last step's device arrays.
+
+    An identity stream (``enable_identity``, on a scoring stream) owns the identity state (``dagr_stream_identity``): the
+    lanes' track tables and overlap counts, and the assignment's workspace.  ``run_score`` then makes a second launch behind
+    the scorer's on the same arrays, still without a host wait; ``run_identity_solve`` is ``dagr_stream_identity_solve``."""
 
     def __init__(self, batch_size, window_us, device, max_lane_events=None):
         self.B, self.window_us, self.device = int(batch_size), int(window_us), torch.device(device)
@@ -485,6 +489,8 @@ class StreamState:
         self.score = None                               # the options of its scorer (dagr.streaming._score_options)
         self.score_state, self.gt_match, self.gt_flags = None, None, None
         self._last_det, self._scored = None, False      # the last step's (det, n_keep); whether run_score has had them
+        self.identity = None                            # the options of its IDF1 state (dagr.streaming._identity_options)
+        self.identity_state, self.identity_ws, self.obj_track, self.identity_result = None, None, None, None
         self._t_ref = None                              # (state pointer, capacity, where its t_ref[B] lives)
 
     # ------------------------------------------------------------------------------------ track ids
@@ -614,7 +620,68 @@ class StreamState:
                                                 P(gt_id), P(n_gt), G, P(self.gt_match), P(self.gt_flags),
                                                 _lib.cur_stream(self.device)), "stream_score")
         self._scored = True
+        if self.identity is not None:              # the second launch, behind the scorer's on the same arrays
+            T = self.identity["max_tracks"]
+            _lib.check(_lib.lib().dagr_stream_identity(P(self.identity_state), self.identity_state.numel(), B, o["max_objects"],
+                                                       T, o["iou"], P(self.score_state), self.score_state.numel(), P(det),
+                                                       P(n_keep), A, P(self.track_ids), boxes, P(gt_box), P(gt_label), P(gt_id),
+                                                       P(n_gt), G, P(self.gt_match), _lib.cur_stream(self.device)),
+                       "stream_identity")
         return self.gt_match, self.gt_flags
+
+    # ------------------------------------------------------------------------------------ IDF1 behind the scorer
+    # the lane's words and the solve's result words, in the order include/dagr_hip.h documents
+    IDENTITY_WORDS = ("n_tracks", "n_objects", "gt_frames", "hyp_frames", "dup_hyp", "unlisted_hyp", "pairs", "steps")
+    IDENTITY_RESULT = ("idtp", "idfn", "idfp", "gt_frames", "hyp_frames", "n_objects", "n_tracks", "dup_hyp", "unlisted_hyp")
+
+    def enable_identity(self, options):
+        """``run_score`` also counts the overlaps of object identities with track ids (``dagr_stream_identity``):
+        ``options`` as ``dagr.streaming._identity_options`` returns them, on a stream that scores.  Allocates the lanes'
+        tables, empty, and the workspace of the solve."""
+        if self.score is None:
+            raise RuntimeError("enable_identity: the stream does not score (enable_score comes first)")
+        self.identity = dict(options)
+        L, M, T = _lib.lib(), self.score["max_objects"], self.identity["max_tracks"]
+        nbytes, ws = L.dagr_stream_identity_bytes(self.B, M, T), L.dagr_assign_workspace_bytes(self.B, M, T)
+        if nbytes == 0 or ws == 0:
+            raise RuntimeError(f"dagr_stream_identity_bytes({self.B}, {M}, {T}): out of range")
+        self.identity_state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.identity_ws = torch.empty(ws, dtype=torch.uint8, device=self.device)
+        self.obj_track = torch.zeros((self.B, M), dtype=torch.int64, device=self.device)
+        self.identity_result = torch.zeros((self.B, len(self.IDENTITY_RESULT)), dtype=torch.int64, device=self.device)
+        self._reset_identity()
+
+    def _reset_identity(self):
+        _lib.check(_lib.lib().dagr_stream_identity_reset(_lib.ptr(self.identity_state), self.identity_state.numel(), self.B,
+                                                         self.score["max_objects"], self.identity["max_tracks"],
+                                                         _lib.cur_stream(self.device)), "stream_identity_reset")
+
+    def run_identity_solve(self):
+        """``dagr_stream_identity_solve`` on the counts so far: one launch; returns the device tensors ``(result int64
+        [B, 9], obj_track int64 [B, max_objects])``, valid until the next call."""
+        if self.identity is None:
+            raise RuntimeError("this stream keeps no identity state (identity=): it has no IDF1")
+        P = _lib.ptr
+        _lib.check(_lib.lib().dagr_stream_identity_solve(P(self.identity_state), self.identity_state.numel(), self.B,
+                                                         self.score["max_objects"], self.identity["max_tracks"],
+                                                         P(self.obj_track), P(self.identity_result), P(self.identity_ws),
+                                                         self.identity_ws.numel(), _lib.cur_stream(self.device)),
+                   "stream_identity_solve")
+        return self.identity_result, self.obj_track
+
+    def identity_words(self):
+        """The state read back through the layout include/dagr_hip.h documents: ``dict(track_id int64 [B, T], track_len int64
+        [B, T], obj_len int64 [B, M], words int64 [B, 8], overlap int32 [B, M, T], obj_col int32 [B, M])`` (copies;
+        synchronises)."""
+        if self.identity is None:
+            raise RuntimeError("this stream keeps no identity state (identity=): it has no tables")
+        B, M, T = self.B, self.score["max_objects"], self.identity["max_tracks"]
+        raw = self.identity_state.cpu().numpy()
+        n64 = 2 * B * T + B * M + 8 * B
+        q, r = raw[:8 * n64].view(np.int64), raw[8 * n64:8 * n64 + 4 * (B * M * T + B * M)].view(np.int32)
+        return dict(track_id=q[:B * T].reshape(B, T), track_len=q[B * T:2 * B * T].reshape(B, T),
+                    obj_len=q[2 * B * T:2 * B * T + B * M].reshape(B, M), words=q[2 * B * T + B * M:].reshape(B, 8),
+                    overlap=r[:B * M * T].reshape(B, M, T), obj_col=r[B * M * T:].reshape(B, M))
 
     def score_words(self):
         """The state read back: ``(table int64 [8, B, max_objects] -- id, last_hyp, prev_hyp, seen_step, present, tracked,
@@ -940,6 +1007,8 @@ class StreamState:
             self._reset_track()
         if self.score_state is not None:
             self._reset_score()
+        if self.identity_state is not None:
+            self._reset_identity()
         self.status.zero_()
         self.lane_count.zero_()
         self.lane_dropped.zero_()

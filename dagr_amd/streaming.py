@@ -220,7 +220,7 @@ the CLEAR MOT metrics"): misses, false positives, identity switches, MOTA and MO
 departs from the paper in the matcher: the assignment is greedy in ground-truth row order inside a label -- as the
 tracker's own matcher and the COCO matcher of this project are -- not a minimum-cost assignment, the overlap is an IoU
 and not a distance, and a label mismatch never matches.  Agreement with py-motmetrics or any other MOT tool is not
-claimed.  IDF1 and HOTA need a global assignment over the whole sequence and are out of scope.
+claimed.  IDF1 and HOTA need a global assignment over the whole sequence: IDF1 is ``identity=`` below, HOTA is out of scope.
 
 Every lane owns an object table of ``max_objects`` slots in order of first appearance and ``n_objects``; a slot holds
 ``id`` int64 (the ground-truth identity, > 0), ``last_hyp`` int64 (the track id of its last match ever, 0: none),
@@ -258,6 +258,47 @@ of a skipped lane are left as they were.  ``score_summary`` turns counters and t
 (``1 - (miss + false_pos + switch) / gt``), MOTP (``iou_q / 2**20 / match``, a mean IoU), precision, recall, and the
 mostly tracked / mostly lost objects (``tracked / present >= 0.8`` / ``<= 0.2``).  Coasting tracks are not hypotheses, and
 there are no ignore regions.  Without ``score`` nothing of this exists.
+
+IDF1 (``identity=`` of a scoring stream: ``None`` is off, ``True`` takes the default, a dict sets ``max_tracks``,
+1 .. ``DAGR_ASSIGN_MAX = 1024``, default 256.  It needs ``score=`` and takes ``iou``, ``max_objects`` and ``boxes`` from it).
+IDF1 (Ristani et al., "Performance measures and a data set for multi-target, multi-camera tracking", 2016) asks for the
+one-to-one pairing of object identities with track ids that maximises the frames they share.  Two definitions below state
+it once in numpy and the kernels repeat them integer for integer: ``assign_max_weight_definition`` (``dagr_assign_max_weight``)
+and ``IdentityDefinition`` (``dagr_stream_identity``, ``dagr_stream_identity_solve``).
+
+The assignment: ``w`` is int ``[n, m]``, ``w >= 0``, ``n, m`` in 0 .. ``DAGR_ASSIGN_MAX``.  ``total`` is the largest sum of
+``w`` over a one-to-one pairing of rows with columns and ``row_col[i]`` the column of row ``i`` in one pairing that reaches
+it, -1 for a row without one; a pair of weight 0 is reported as -1.  The method is the Hungarian method by shortest
+augmenting paths in integers on the cost ``-w`` with the smaller side as rows (``n > m``: the transposed matrix): potentials
+``u`` (rows) and ``v`` (columns) int64, one row enters at a time, a path step marks column ``j0`` used, relaxes
+``minv[j] = min(minv[j], cost[p[j0], j] - u[p[j0]] - v[j])`` over the unused columns, takes ``delta`` = the smallest ``minv``,
+the LOWEST column on a tie, moves the potentials by ``delta`` and goes on from that column until it is free; then the path
+is flipped.  ``total`` is unique, ``row_col`` is not: a pairing is right if it is one-to-one, lists only pairs with
+``w > 0`` and sums to ``total``; nothing may compare pairings bit for bit.
+
+The identity state: every lane owns a track table of ``max_tracks`` columns in order of first appearance (``track_id`` int64,
+``track_len`` int64) and ``n_tracks``, ``obj_len`` int64 ``[max_objects]`` over the scorer's object slots, ``overlap`` int32
+``[max_objects, max_tracks]`` and the int64 words ``n_objects``, ``gt_frames``, ``hyp_frames``, ``dup_hyp``, ``unlisted_hyp``,
+``pairs``, ``steps``, zero after construction and after ``reset()``.  One step runs AFTER the scorer's step on the same
+arrays, with the ``gt_match`` that step wrote and the scorer's id table after it; a lane with ``n_gt[b] < 0`` changes nothing:
+
+1. hypotheses: the scorer's own rule, the rows ``i < clamp(n_keep[b], 0, A)`` with ``track_id != 0``, the first
+   ``DAGR_TRACK_MAX_DETS`` in row order.  A row whose id an earlier participating row of this step carries takes no part
+   and ``dup_hyp += 1``; every other row counts ``hyp_frames += 1``;
+2. columns: in row order a hypothesis finds its column by id, or takes column ``n_tracks++``; with a full table it gets no
+   column, ``unlisted_hyp += 1``, and its frames can only be identity false positives.  With a column ``track_len[col] += 1``;
+3. rows: the ground-truth rows ``g < min(n_gt[b], G)`` with ``gt_match[b, g] != -1`` (the rows the scorer scored).  The
+   object's slot is the index of ``gt_id`` in the scorer's id table (a row whose id is ``<= 0`` or not there takes no part);
+   ``gt_frames += 1``, ``obj_len[slot] += 1``, ``n_objects = max(n_objects, slot + 1)``;
+4. pairs: for every such row and every hypothesis with a column, when the labels are equal and ``iou(gt, hyp) >= iou`` (the
+   scorer's IoU; a NaN IoU overlaps nothing): ``overlap[slot, col] += 1``, ``pairs += 1``.  This is IDF1's "all pairs that
+   overlap at a step", not the scorer's one-to-one match: two objects on one hypothesis both count.  Then ``steps += 1``.
+
+``solve()``: per lane ``idtp`` is the assignment's total on ``overlap[:n_objects, :n_tracks]``, ``idfn = gt_frames - idtp``,
+``idfp = hyp_frames - idtp``, and ``obj_track[b, slot]`` is the paired track id or 0.  ``identity_summary`` gives
+``idf1 = 2 idtp / (gt_frames + hyp_frames)``, ``idp = idtp / hyp_frames`` and ``idr = idtp / gt_frames`` per lane and in
+total (the total sums the lanes' integers: lanes are separate sequences).  Agreement with py-motmetrics or TrackEval is
+not claimed.  Without ``identity`` nothing of this exists.
 
 Camera words (``decode="evt3"`` or ``"evt2"``): an event camera delivers words, not arrays.  A decoding stream takes the
 camera's words (``step_words`` / ``step_words_device``) and decodes them on the device (``dagr_stream_decode``) in front of
@@ -1039,6 +1080,279 @@ def score_summary(counters, objects):
     return dict(lanes=[one(per_lane[b], [objects[b]]) for b in range(B)], total=one(total, list(objects)))
 
 
+DAGR_ASSIGN_MAX = DEFINES["DAGR_ASSIGN_MAX"]
+IDENTITY_DEFAULTS = dict(max_tracks=256)
+IDENTITY_WORDS = ("n_tracks", "n_objects", "gt_frames", "hyp_frames", "dup_hyp", "unlisted_hyp", "pairs", "steps")
+IDENTITY_RESULT = ("idtp", "idfn", "idfp", "gt_frames", "hyp_frames", "n_objects", "n_tracks", "dup_hyp", "unlisted_hyp")
+
+
+def assign_max_weight_definition(w, stats=None):
+    """The maximum-weight assignment of the module docstring in numpy: ``w`` int ``[n, m]``, ``w >= 0``, ``n, m`` in
+    0 .. ``DAGR_ASSIGN_MAX`` -> ``(total, row_col)``, a Python int and int64 ``[n]`` (a column, or -1: no pair, or a pair of
+    weight 0).  ``total`` is unique, ``row_col`` is one pairing that reaches it (``check_assignment``).  ``stats``, a dict,
+    gets ``steps`` (path steps) and ``transposed``.  The yardstick of ``dagr_assign_max_weight``."""
+    w = np.asarray(w)
+    if w.ndim != 2 or not np.issubdtype(w.dtype, np.integer) or max(w.shape) > DAGR_ASSIGN_MAX:
+        raise ValueError(f"assign_max_weight_definition: w is an int array [n, m] with n, m <= DAGR_ASSIGN_MAX = "
+                         f"{DAGR_ASSIGN_MAX}, got {w.dtype} {w.shape}")
+    if w.size and w.min() < 0:
+        raise ValueError("assign_max_weight_definition: w must be >= 0")
+    n, m = w.shape
+    row_col = np.full(n, -1, np.int64)
+    transposed = n > m
+    if stats is not None:
+        stats.update(steps=0, transposed=transposed)
+    if n == 0 or m == 0:
+        return 0, row_col
+    a = (w.T if transposed else w).astype(np.int64)
+    cost = -a
+    R, C = cost.shape
+    inf = np.iinfo(np.int64).max
+    u, v = np.zeros(R + 1, np.int64), np.zeros(C + 1, np.int64)        # 1-based; row 0 / column 0 are the path's root
+    p, way = np.zeros(C + 1, np.int64), np.zeros(C + 1, np.int64)      # p[j]: the row of column j, 0: free
+    steps = 0
+    for i in range(1, R + 1):
+        p[0], j0 = i, 0
+        minv, used = np.full(C + 1, inf, np.int64), np.zeros(C + 1, bool)
+        while True:
+            used[j0] = True
+            i0 = p[j0]
+            free = ~used                                                # (column 0 is used from the first step on)
+            cur = cost[i0 - 1] - u[i0] - v[1:]
+            better = free[1:] & (cur < minv[1:])
+            minv[1:][better], way[1:][better] = cur[better], j0
+            cand = np.where(free[1:], minv[1:], inf)
+            j1 = int(np.argmin(cand)) + 1                               # the lowest column of equals
+            delta = cand[j1 - 1]
+            u[p[used]] += delta                                         # (the rows of the used columns are distinct)
+            v[used] -= delta
+            minv[free] -= delta
+            j0 = j1
+            steps += 1
+            if p[j0] == 0:
+                break
+        while j0:
+            j1 = int(way[j0])
+            p[j0] = p[j1]
+            j0 = j1
+    total = 0
+    for j in range(1, C + 1):
+        if p[j] and a[p[j] - 1, j - 1] > 0:
+            r, c = int(p[j]) - 1, j - 1
+            total += int(a[r, c])
+            if transposed:
+                row_col[c] = r
+            else:
+                row_col[r] = c
+    if stats is not None:
+        stats["steps"] = steps
+    return total, row_col
+
+
+def check_assignment(w, total, row_col):
+    """Whether ``row_col`` is a right answer for ``w`` with the total ``total``: every entry -1 or a column in range, no
+    column twice, no pair of weight 0, and the pairs sum to ``total``.  Returns None or what is wrong, in words."""
+    w, row_col = np.asarray(w), np.asarray(row_col)
+    n, m = w.shape
+    if row_col.shape != (n,):
+        return f"row_col has shape {row_col.shape}, not ({n},)"
+    rows = np.flatnonzero(row_col != -1)
+    cols = row_col[rows]
+    if len(cols) and (cols.min() < 0 or cols.max() >= m):
+        return "a column out of range"
+    if len(set(cols.tolist())) != len(cols):
+        return "a column is paired twice"
+    weights = w[rows, cols].astype(np.int64) if len(rows) else np.zeros(0, np.int64)
+    if (weights <= 0).any():
+        return "a pair of weight 0 is listed"
+    if int(weights.sum()) != int(total):
+        return f"the pairs sum to {int(weights.sum())}, not to {int(total)}"
+    return None
+
+
+def _identity_options(identity, score_options, who):
+    """``identity=`` of a scoring stream, checked: None (off) or ``dict(max_tracks=)``; ``score_options`` is what
+    ``_score_options`` returned.  Refusals by name."""
+    opt = _options(identity, "identity", IDENTITY_DEFAULTS, who)
+    if opt is None:
+        return None
+    if score_options is None:
+        raise ValueError(f"{who}: identity= needs score= (it counts the rows the scorer scored)")
+    if not _is_int(opt["max_tracks"]) or not 1 <= int(opt["max_tracks"]) <= DAGR_ASSIGN_MAX:
+        raise ValueError(f"{who}: identity max_tracks = {opt['max_tracks']!r} must be an int in 1..DAGR_ASSIGN_MAX = "
+                         f"{DAGR_ASSIGN_MAX}")
+    return dict(max_tracks=int(opt["max_tracks"]))
+
+
+class IdentityDefinition:
+    """The identity state of the module docstring in numpy: ``step(det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt,
+    gt_match, score_ids, track_box=None)`` is one step of every lane behind the scorer's on the same arrays -- ``gt_match``
+    int64 ``[B, G]`` is what that step wrote, ``score_ids`` int64 ``[B, max_objects]`` the scorer's id table after it --, and
+    ``solve()`` returns the dict of ``IDENTITY_RESULT`` (int64 ``[B]`` each) plus ``obj_track`` int64 ``[B, max_objects]``.
+    The state is ``track_id``, ``track_len`` int64 ``[B, max_tracks]``, ``obj_len`` int64 ``[B, max_objects]``, ``overlap``
+    int32 ``[B, max_objects, max_tracks]`` and ``words``, a dict of one int64 ``[B]`` array per name of ``IDENTITY_WORDS``.
+    ``events`` counts what has happened so far -- pairs, duplicate ids, unlisted hypotheses, new columns, ground-truth rows
+    skipped, lanes skipped, label mismatches, NaN IoUs, hypotheses shared by two objects at a step -- so that a test can
+    tell a run that exercises every rule from one that does not.  The yardstick of ``dagr_stream_identity`` and
+    ``dagr_stream_identity_solve``; nothing on the device path calls it."""
+
+    def __init__(self, batch_size, identity=True, score=True):
+        self.B = int(batch_size)
+        self.score = _score_options(score, True, True, "IdentityDefinition")
+        if self.score is None:
+            raise ValueError("IdentityDefinition: score = None is a stream that does not score")
+        self.options = _identity_options(identity, self.score, "IdentityDefinition")
+        if self.options is None:
+            raise ValueError("IdentityDefinition: identity = None is a stream without it")
+        self.reset()
+
+    def reset(self):
+        B, M, T = self.B, self.score["max_objects"], self.options["max_tracks"]
+        self.track_id, self.track_len = np.zeros((B, T), np.int64), np.zeros((B, T), np.int64)
+        self.obj_len, self.overlap = np.zeros((B, M), np.int64), np.zeros((B, M, T), np.int32)
+        self.words = {name: np.zeros(B, np.int64) for name in IDENTITY_WORDS}
+        self.events = dict(pairs=0, duplicates=0, unlisted=0, new_columns=0, rows_skipped=0, lanes_skipped=0,
+                           label_mismatch=0, nan_iou=0, shared_hyp=0)
+
+    def step(self, det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt, gt_match, score_ids, track_box=None):
+        det, track_id = np.asarray(det, np.float32), np.asarray(track_id, np.int64)
+        B, A = det.shape[:2]
+        gt_box, gt_label, gt_id = np.asarray(gt_box, np.float32), np.asarray(gt_label, np.int32), np.asarray(gt_id, np.int64)
+        gt_match, score_ids = np.asarray(gt_match, np.int64), np.asarray(score_ids, np.int64)
+        G = gt_box.shape[1] if gt_box.ndim == 3 else -1
+        M, T, w, ev = self.score["max_objects"], self.options["max_tracks"], self.words, self.events
+        if B != self.B or det.shape[2:] != (6,) or track_id.shape != (B, A):
+            raise ValueError(f"IdentityDefinition: det is fp32 [{self.B}, A, 6] and track_id int64 [{self.B}, A], got "
+                             f"{det.shape} and {track_id.shape}")
+        if gt_box.shape != (B, G, 4) or gt_label.shape != (B, G) or gt_id.shape != (B, G) or gt_match.shape != (B, G) or \
+                not 0 <= G <= DAGR_SCORE_MAX_GT or score_ids.shape != (B, M):
+            raise ValueError(f"IdentityDefinition: the ground truth is gt_box fp32 [{B}, G, 4], gt_label int32, gt_id and "
+                             f"gt_match int64 [{B}, G] with G <= DAGR_SCORE_MAX_GT = {DAGR_SCORE_MAX_GT} and score_ids int64 "
+                             f"[{B}, {M}], got {gt_box.shape}, {gt_label.shape}, {gt_id.shape}, {gt_match.shape}, "
+                             f"{score_ids.shape}")
+        if self.score["boxes"] == "track":
+            if track_box is None:
+                raise ValueError("IdentityDefinition: score boxes = 'track' needs the step's track_box")
+            boxes = np.asarray(track_box, np.float32)
+        else:
+            boxes = det[..., :4]
+        n_keep = np.broadcast_to(np.asarray(n_keep, np.int64).reshape(-1), (B,))
+        n_gt = np.full(B, G, np.int64) if n_gt is None else np.broadcast_to(np.asarray(n_gt, np.int64).reshape(-1), (B,))
+        thr = np.float32(self.score["iou"])
+        for b in range(B):
+            if n_gt[b] < 0:                                        # no labels at this instant: not one byte changes
+                ev["lanes_skipped"] += 1
+                continue
+            n, ng = min(max(int(n_keep[b]), 0), A), min(int(n_gt[b]), G)
+            with np.errstate(all="ignore"):
+                labels = det[b, :, 5].astype(np.int32)
+            hyp, carried, col = [], set(), {}                                      # 1: the hypotheses
+            for i in [i for i in range(n) if track_id[b, i] != 0][:DAGR_TRACK_MAX_DETS]:
+                ident = int(track_id[b, i])
+                if ident in carried:
+                    w["dup_hyp"][b] += 1
+                    ev["duplicates"] += 1
+                    continue
+                carried.add(ident)
+                hyp.append(i)
+                w["hyp_frames"][b] += 1
+            for i in hyp:                                                          # 2: the columns
+                ident = int(track_id[b, i])
+                known = np.flatnonzero(self.track_id[b, :w["n_tracks"][b]] == ident)
+                if len(known):
+                    col[i] = int(known[0])
+                elif w["n_tracks"][b] < T:
+                    col[i] = int(w["n_tracks"][b])
+                    self.track_id[b, col[i]] = ident
+                    w["n_tracks"][b] += 1
+                    ev["new_columns"] += 1
+                else:
+                    w["unlisted_hyp"][b] += 1
+                    ev["unlisted"] += 1
+                    continue
+                self.track_len[b, col[i]] += 1
+            slot = {}                                                              # 3: the rows
+            for g in range(ng):
+                scored = gt_match[b, g] != -1 and gt_id[b, g] > 0
+                known = np.flatnonzero(score_ids[b] == gt_id[b, g]) if scored else []
+                if len(known) == 0:
+                    ev["rows_skipped"] += 1
+                    continue
+                slot[g] = int(known[0])
+                w["gt_frames"][b] += 1
+                self.obj_len[b, slot[g]] += 1
+                w["n_objects"][b] = max(int(w["n_objects"][b]), slot[g] + 1)
+            hit = set()
+            for g, s in slot.items():                                              # 4: the pairs
+                for i, c in col.items():
+                    if labels[i] != gt_label[b, g]:
+                        ev["label_mismatch"] += 1
+                        continue
+                    v = TrackDefinition.iou(gt_box[b, g], boxes[b, i])
+                    ev["nan_iou"] += int(v != v)
+                    if v >= thr:
+                        self.overlap[b, s, c] += 1
+                        w["pairs"][b] += 1
+                        ev["pairs"] += 1
+                        ev["shared_hyp"] += int(i in hit)
+                        hit.add(i)
+            w["steps"][b] += 1
+
+    def solve(self, stats=None):
+        """The assignment on every lane's ``overlap[:n_objects, :n_tracks]``: the dict of ``IDENTITY_RESULT`` (int64 ``[B]``)
+        plus ``obj_track`` int64 ``[B, max_objects]`` (the paired track id, 0: none).  ``stats``, a list, gets one dict per
+        lane (``assign_max_weight_definition``)."""
+        B, M, w = self.B, self.score["max_objects"], self.words
+        out = {name: np.zeros(B, np.int64) for name in IDENTITY_RESULT}
+        out["obj_track"] = np.zeros((B, M), np.int64)
+        for b in range(B):
+            n, m = int(w["n_objects"][b]), int(w["n_tracks"][b])
+            st = {}
+            total, row_col = assign_max_weight_definition(self.overlap[b, :n, :m], st)
+            if stats is not None:
+                stats.append(st)
+            out["idtp"][b] = total
+            out["idfn"][b], out["idfp"][b] = w["gt_frames"][b] - total, w["hyp_frames"][b] - total
+            for name in IDENTITY_RESULT[3:]:
+                out[name][b] = w[name][b]
+            paired = row_col >= 0
+            out["obj_track"][b, :n][paired] = self.track_id[b, row_col[paired]]
+        return out
+
+
+def check_identity(overlap, track_id, result, b):
+    """Whether lane ``b`` of a solve's ``result`` is a right answer for the lane's ``overlap`` int32 ``[max_objects,
+    max_tracks]`` and ``track_id`` int64 ``[max_tracks]``: ``obj_track`` names listed tracks, none twice, only pairs that
+    overlap, and they sum to ``idtp``.  Returns None or what is wrong, in words."""
+    n, m = int(result["n_objects"][b]), int(result["n_tracks"][b])
+    obj_track = np.asarray(result["obj_track"][b])
+    if obj_track[n:].any():
+        return "an object behind n_objects is paired"
+    row_col = np.full(n, -1, np.int64)
+    for s in np.flatnonzero(obj_track[:n]):
+        known = np.flatnonzero(np.asarray(track_id[:m]) == obj_track[s])
+        if len(known) != 1:
+            return f"object {s} is paired with track {obj_track[s]}, which is not listed once"
+        row_col[s] = known[0]
+    return check_assignment(np.asarray(overlap)[:n, :m], result["idtp"][b], row_col)
+
+
+def identity_summary(result):
+    """A solve's ``result`` (the dict of int64 ``[B]`` per name of ``IDENTITY_RESULT``) -> ``dict(lanes=[...], total=...)``,
+    each entry a dict of ``idf1`` (``2 idtp / (gt_frames + hyp_frames)``), ``idp`` (``idtp / hyp_frames``), ``idr``
+    (``idtp / gt_frames``) -- floats, ``nan`` where the denominator is 0 -- and ``idtp``, ``idfn``, ``idfp``, ``gt_frames``,
+    ``hyp_frames``, ``objects``, ``tracks`` (ints).  The total sums the lanes' integers.  Plain host code."""
+    def one(c):
+        ratio = lambda a, b: float(a) / float(b) if b else float("nan")            # noqa: E731
+        return dict(idf1=ratio(2 * c["idtp"], c["gt_frames"] + c["hyp_frames"]), idp=ratio(c["idtp"], c["hyp_frames"]),
+                    idr=ratio(c["idtp"], c["gt_frames"]), idtp=c["idtp"], idfn=c["idfn"], idfp=c["idfp"],
+                    gt_frames=c["gt_frames"], hyp_frames=c["hyp_frames"], objects=c["n_objects"], tracks=c["n_tracks"])
+    B = len(np.asarray(result["idtp"]).reshape(-1))
+    per_lane = [{k: int(np.asarray(result[k]).reshape(-1)[b]) for k in IDENTITY_RESULT} for b in range(B)]
+    total = {k: sum(c[k] for c in per_lane) for k in IDENTITY_RESULT}
+    return dict(lanes=[one(c) for c in per_lane], total=one(total))
+
+
 def frame_definition(raw, fx, fy, W, H, bgr=False):
     """The model's image of one raw sensor frame (``uint8 [H_f, W_f, 3]``), stated once: ``DSEC.preprocess_image`` plus
     ``format_data`` for a top-left crop.  Rows ``[0, fy * H)`` and columns ``[0, fx * W)`` of the frame go through
@@ -1402,6 +1716,11 @@ class EventStream:
     the counters back, ``scored_objects()`` the object tables, and ``score_summary`` turns both into MOTA, MOTP and the id
     switches.  A step of a scoring stream issues exactly the calls it issues without the scorer: only ``score_step``
     launches (``dagr_stream_score``, once).  A stream built without it issues exactly the calls it issued before.
+    ``identity`` (``None``: off, ``True``: the default, or ``dict(max_tracks=N)``; needs ``score``): ``score_step`` issues
+    ``dagr_stream_identity`` behind ``dagr_stream_score`` -- two launches, still no host wait -- and ``identity()`` runs the
+    maximum-weight assignment on the counts (``dagr_stream_identity_solve``) and returns IDF1's integers (module docstring;
+    ``identity_summary`` gives IDF1, IDP and IDR); ``identity_tables()`` reads the state back.  A stream built without it
+    issues exactly the calls it issued before.
     ``decode`` (``None``: off, ``"evt2"`` or ``"evt3"``), ``max_decoded`` and ``t_base``: the stream takes the camera's words
     (``step_words`` / ``step_words_device``) and ``dagr_stream_decode`` turns them into events on the device, in front of
     the filter, the front and the window (module docstring; the formats as recalled from the vendor's public descriptions,
@@ -1427,13 +1746,15 @@ class EventStream:
 
     def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
                  max_lane_events=None, denoise_us=None, refractory_us=None, track=None, motion=None, rescue=None,
-                 decode=None, max_decoded=None, t_base=None, flicker=None, trail_us=None, score=None):
+                 decode=None, max_decoded=None, t_base=None, flicker=None, trail_us=None, score=None,
+                 identity=None):
         import torch
         self.model = model
         self.track = _track_options(track, "EventStream")
         self.motion = _motion_options(motion, self.track, "EventStream")
         self.rescue = _rescue_options(rescue, self.track, "EventStream")
         self.score = _score_options(score, self.track, self.motion, "EventStream")
+        self.identity_options = _identity_options(identity, self.score, "EventStream")
         time_window = int(getattr(model.args, "time_window_us", 1000000))
         self.window_us, self.max_lane_events = _window_and_cap(window_us, max_lane_events, time_window,
                                                                getattr(model.args, "batch_size", 1), "EventStream")
@@ -1483,6 +1804,8 @@ class EventStream:
             self.state.enable_track(self.track, motion=self.motion, rescue=self.rescue)
         if self.score is not None:
             self.state.enable_score(self.score)
+        if self.identity_options is not None:
+            self.state.enable_identity(self.identity_options)
         self._zeros = None
         self.outputs = None      # the last step's decoded head outputs [B, A, 5 + classes], valid until the engine's next call
         self._frame = None
@@ -1799,7 +2122,8 @@ class EventStream:
         ``gt_box`` fp32 ``[B, G, 4]`` (x1, y1, x2, y2), ``gt_label`` int32 ``[B, G]``, ``gt_id`` int64 ``[B, G]`` (the
         identities, > 0) and ``n_gt`` int32 ``[B]`` -- ``None``: every lane has all ``G`` rows; ``n_gt[b] < 0``: lane ``b``
         has no labels at this instant and is skipped --, numpy arrays (uploaded) or device tensors,
-        ``G <= DAGR_SCORE_MAX_GT``.  ONE launch (``dagr_stream_score``) on the step's own device arrays, no host wait.
+        ``G <= DAGR_SCORE_MAX_GT``.  ONE launch (``dagr_stream_score``; with ``identity=`` a second,
+        ``dagr_stream_identity``, behind it) on the step's own device arrays, no host wait.
         Returns ``(gt_match int64 [B, G], gt_flags int32 [B, G])``, device tensors valid until the next ``score_step``:
         per row the track id (0: a miss, -1: unscored) and the bits switch (1), fragmentation (2), kept (4).  Raises by name
         before the stream's first step, when called twice for one step, and on a stream without ``score=``."""
@@ -1839,10 +2163,36 @@ class EventStream:
         table, words = self.state.score_words()
         return [objects_from_arrays(int(words[b, 0]), *table[:, b]) for b in range(self.B)]
 
+    def identity(self):
+        """IDF1's integers for everything scored since construction / ``reset()`` (module docstring; needs ``identity=``): one
+        launch (``dagr_stream_identity_solve``: the maximum-weight pairing of object identities with track ids on the
+        lanes' overlap counts), then the read-back (synchronises).  Returns a dict of int64 ``[B]`` per name of
+        ``IDENTITY_RESULT`` (``idtp``, ``idfn``, ``idfp``, ``gt_frames``, ``hyp_frames``, ``n_objects``, ``n_tracks``,
+        ``dup_hyp``, ``unlisted_hyp``) plus ``obj_track``, per lane int64 ``[n_objects]``: the track id paired with the
+        object of a slot of ``scored_objects()``, 0 for none.  The counts go on: it can be asked for at any step.
+        ``identity_summary`` takes the result."""
+        if self.identity_options is None:
+            raise RuntimeError("EventStream: identity() needs a stream built with identity= (and score=, track=)")
+        result, obj_track = self.state.run_identity_solve()
+        result, obj_track = result.cpu().numpy(), obj_track.cpu().numpy()
+        out = {name: result[:, i].copy() for i, name in enumerate(IDENTITY_RESULT)}
+        out["obj_track"] = [obj_track[b, :int(out["n_objects"][b])].copy() for b in range(self.B)]
+        return out
+
+    def identity_tables(self):
+        """The identity state read back (copies; synchronises; needs ``identity=``): ``dict(track_id int64 [B, max_tracks],
+        track_len int64 [B, max_tracks], obj_len int64 [B, max_objects], overlap int32 [B, max_objects, max_tracks], words:
+        a dict of int64 [B] per name of IDENTITY_WORDS)``."""
+        if self.identity_options is None:
+            raise RuntimeError("EventStream: identity_tables() needs a stream built with identity= (and score=, track=)")
+        t = self.state.identity_words()
+        return dict(track_id=t["track_id"].copy(), track_len=t["track_len"].copy(), obj_len=t["obj_len"].copy(),
+                    overlap=t["overlap"].copy(), words={name: t["words"][:, i].copy() for i, name in enumerate(IDENTITY_WORDS)})
+
     def reset(self):
         """Empty the stream: no resident events, no reference instants, zero change maps, empty stamp maps, every pixel of
         the flicker / trail filters in its initial state, zero dropped, filtered and suppressed counts, zero decoder states and counters, a clear status word, zero step counters; no tracks, ids from 1 again, zero untracked and rescued counts; the
-        scorer's object tables empty and its counters zero (and no step left to score).  The
+        scorer's object tables empty and its counters zero (and no step left to score); the identity state empty.  The
         frame in force stays, and the next step runs it through the image branch again."""
         self.state.reset()
 

@@ -684,6 +684,90 @@ int dagr_stream_score(void *state, size_t bytes, int32_t B, int32_t max_objects,
                       const float *gt_box, const int32_t *gt_label, const int64_t *gt_id, const int32_t *n_gt, int32_t G,
                       int64_t *gt_match, int32_t *gt_flags, void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * Maximum-weight bipartite assignment, on the device
+ *   dagr_assign_max_weight pairs rows with columns one to one so that the sum of w over the pairs is the largest possible,
+ *   for B independent matrices in one launch (one wave per matrix), no host synchronisation, no global atomics.
+ *   dagr_amd/streaming.py: assign_max_weight_definition is the same method in numpy.
+ *
+ * Matrix b is w[b, :n_rows[b], :n_cols[b]] of w int32[B, ld_rows, ld] (row r of matrix b starts at (b * ld_rows + r) * ld),
+ * every weight >= 0 (a negative weight is the caller's error and is not detected), 0 <= n_rows[b] <= max_rows <= ld_rows,
+ * 0 <= n_cols[b] <= max_cols <= ld, max_rows and max_cols in 1..DAGR_ASSIGN_MAX; a count outside its range is clamped.
+ * The method is the Hungarian method by shortest augmenting paths in integers on the cost -w, with the smaller side as
+ * rows: a matrix with n_rows > n_cols is first transposed into the workspace.  Potentials are int64.  One row enters at a
+ * time; a path step marks column j0 used, relaxes minv[j] = min(minv[j], cost[p[j0], j] - u[p[j0]] - v[j]) over the unused
+ * columns, takes delta = the smallest minv, the LOWEST column on a tie, moves the potentials by delta and goes on from that
+ * column until it is free; then the path is flipped.
+ * total int64[B]: the largest sum, which is unique.  row_col int32[B, max_rows]: for r < n_rows[b] the column paired with
+ * row r in ONE pairing that reaches it, or -1 (no pair, or a pair of weight 0); -1 for the rows behind n_rows[b].  The
+ * pairing is not unique: it is one-to-one, lists only pairs with w > 0 and sums to total; compare nothing else.
+ * workspace: dagr_assign_workspace_bytes(B, max_rows, max_cols) bytes (0: a size out of range), 16-byte aligned; it holds
+ * the transposed matrices, int32[B, max_cols, max_rows], and means nothing between calls.  All in device memory.
+ * DAGR_ERR_INVALID_ARG before any launch: B outside 1..65535, max_rows / max_cols outside 1..DAGR_ASSIGN_MAX, ld_rows <
+ * max_rows, ld < max_cols, a workspace smaller than dagr_assign_workspace_bytes, NULL or misaligned arrays.
+ * ------------------------------------------------------------------------ */
+#define DAGR_ASSIGN_MAX 1024
+size_t dagr_assign_workspace_bytes(int32_t B, int32_t max_rows, int32_t max_cols);
+int dagr_assign_max_weight(const int32_t *w, int32_t B, int32_t ld_rows, int32_t ld, const int32_t *n_rows,
+                           const int32_t *n_cols, int32_t max_rows, int32_t max_cols, int32_t *row_col, int64_t *total,
+                           void *workspace, size_t bytes, void *stream);
+
+/* ------------------------------------------------------------------------ *
+ * Event stream identity state: IDF1 (Ristani et al., 2016) behind the scorer, on the device
+ *   dagr_stream_identity runs after dagr_stream_score on the same step's arrays and counts, per lane, how many steps every
+ *   (object identity, track id) pair overlapped; dagr_stream_identity_solve runs dagr_assign_max_weight's method on those
+ *   counts: idtp is the largest number of frames a one-to-one pairing of identities with track ids can share.
+ *   idf1 = 2 idtp / (gt_frames + hyp_frames), idp = idtp / hyp_frames, idr = idtp / gt_frames are the caller's divisions.
+ *   One launch each (one wave per lane), no host synchronisation, no global atomics.  dagr_amd/streaming.py:
+ *   IdentityDefinition is the same in numpy, integer for integer.  Agreement with another MOT tool is not claimed.
+ *
+ * One dagr_stream_identity call is one step of every lane b with n_gt[b] >= 0 (n_gt[b] < 0: not one byte of the lane
+ * changes):
+ *   hypotheses: dagr_stream_score's rule -- the rows i < clamp(n_keep[b], 0, A) with track_id[b, i] != 0, the first
+ *             DAGR_TRACK_MAX_DETS in row order, box and label as there.  A row whose id an earlier participating row of this
+ *             step carries takes no part, dup_hyp += 1; every other row counts hyp_frames += 1;
+ *   columns:  in row order a hypothesis finds its column by id, or takes column n_tracks++; with a full table it gets no
+ *             column and unlisted_hyp += 1.  With a column track_len[col] += 1;
+ *   rows:     the rows g < min(n_gt[b], G) with gt_match[b, g] != -1 and gt_id[b, g] > 0 whose gt_id is in the first n_objects
+ *             slots of the scorer's id table; slot = that index.  gt_frames += 1, obj_len[slot] += 1,
+ *             n_objects = max(n_objects, slot + 1);
+ *   pairs:    for every such row and every hypothesis with a column, when the labels are equal and iou(gt, hyp) >= iou
+ *             (dagr_stream_score's IoU; a NaN IoU overlaps nothing): overlap[slot, col] += 1, pairs += 1.  Every overlapping
+ *             pair counts, not a one-to-one match.  Then steps += 1.
+ *
+ * state: dagr_stream_identity_bytes(B, max_objects, max_tracks) bytes (0: B outside 1..65535, max_objects outside
+ *        1..DAGR_SCORE_MAX_OBJECTS or max_tracks outside 1..DAGR_ASSIGN_MAX), 16-byte aligned, dagr_stream_identity_reset
+ *        before the first step and to empty it (all zero).  With M = max_objects and T = max_tracks it holds, back to back:
+ *          track_id  int64 [B, T]    at byte 0                (the track id of a column, != 0; columns at and behind n_tracks: 0)
+ *          track_len int64 [B, T]    at byte  8 * B * T       (the steps at which the column's track was a hypothesis)
+ *          obj_len   int64 [B, M]    at byte 16 * B * T       (the steps at which the object of a slot was a row)
+ *          lane      int64 [B, 8]    at byte 16 * B * T + 8 * B * M: n_tracks, n_objects, gt_frames, hyp_frames, dup_hyp,
+ *                                    unlisted_hyp, pairs, steps
+ *          overlap   int32 [B, M, T] at byte 16 * B * T + 8 * B * M + 64 * B
+ *          obj_col   int32 [B, M]    behind it (the last solve's pairing as columns, -1: none; 0 after a reset)
+ *        -- 16 * B * T + 8 * B * M + 64 * B + 4 * B * M * T + 4 * B * M bytes, rounded up to a multiple of 16.
+ * score_state: dagr_stream_score's state of the same B and max_objects AFTER its step (read only: the id table and n_objects).
+ * det, n_keep, A, track_id, track_box, gt_box, gt_label, gt_id, n_gt, G: as dagr_stream_score takes them; gt_match
+ * int64[B, G] is what it wrote (read only here).
+ * dagr_stream_identity_solve: obj_track int64[B, max_objects] (the track id paired with the object of a slot, 0: none) and
+ * result int64[B, DAGR_IDENTITY_RESULT_WORDS]: idtp, idfn = gt_frames - idtp, idfp = hyp_frames - idtp, gt_frames,
+ * hyp_frames, n_objects, n_tracks, dup_hyp, unlisted_hyp.  workspace: dagr_assign_workspace_bytes(B, max_objects,
+ * max_tracks).  The state's counts are not changed: a solve can be asked for at any step.
+ * DAGR_ERR_INVALID_ARG before any launch: sizes out of range, iou outside (0, 1] (NaN included), a state or workspace too
+ * small, NULL or misaligned arrays.
+ * ------------------------------------------------------------------------ */
+#define DAGR_IDENTITY_RESULT_WORDS 9
+size_t dagr_stream_identity_bytes(int32_t B, int32_t max_objects, int32_t max_tracks);
+int dagr_stream_identity_reset(void *state, size_t bytes, int32_t B, int32_t max_objects, int32_t max_tracks, void *stream);
+int dagr_stream_identity(void *state, size_t bytes, int32_t B, int32_t max_objects, int32_t max_tracks, float iou,
+                         const void *score_state, size_t score_bytes,
+                         const float *det, const int32_t *n_keep, int32_t A, const int64_t *track_id,
+                         const float *track_box /* [B, A, 4] or NULL: det's boxes */,
+                         const float *gt_box, const int32_t *gt_label, const int64_t *gt_id, const int32_t *n_gt, int32_t G,
+                         const int64_t *gt_match, void *stream);
+int dagr_stream_identity_solve(void *state, size_t bytes, int32_t B, int32_t max_objects, int32_t max_tracks,
+                               int64_t *obj_track, int64_t *result, void *workspace, size_t workspace_bytes, void *stream);
+
 /* The neighbour search alone, again, on the pixel index the last dagr_graph_build_window left in `workspace` (same N):
  * rewrites nbr_src / nbr_code / deg and the edge count.  For measurement (bench.py times the search kernels on their own
  * stream with HIP events); a product caller has no use for it. */

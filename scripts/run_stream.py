@@ -62,6 +62,12 @@ tool is not claimed).  The source must have ``labels(t_step)``, which returns ``
 ``--track_score``) sets the overlap a match needs (default 0.5).  The built-in synthetic sequence has no labels and is
 refused.  Id switches, fragmentations, MOTA and MOTP are printed with the summary; the detections written do not change.
 
+``--track_identity`` (needs ``--track_score``): every scored step also counts which object identities overlap which track
+ids (``EventStream(identity=)``), and at the end the maximum-weight pairing of identities with track ids gives IDF1, IDP and
+IDR (Ristani et al., 2016), printed beside the MOTA summary; agreement with another MOT tool is not claimed.
+``--track_identity_max_tracks N`` (needs ``--track_identity``) sizes the table of track ids (default 256, at most 1024): a
+track id that finds it full can only count as identity false positives.  The detections written do not change.
+
 ``--decode evt2|evt3``: the step's events are encoded as camera words (``dagr.data.evt.encode_events``, an encoder for
 synthetic sources, not a model of any camera) and pushed through ``step_words``; the stream decodes them on the device
 (``dagr.streaming``: ``EventStream(decode=)``) in front of the filter, the front and the window.  ``--max_decoded N`` sizes
@@ -75,8 +81,8 @@ import torch
 
 import _common as C
 from dagr.data.evt import encode_events
-from dagr.streaming import (EventStream, _flicker_options, _motion_options, _rescue_options, _score_options, _track_options,
-                            score_summary)
+from dagr.streaming import (EventStream, _flicker_options, _identity_options, _motion_options, _rescue_options,
+                            _score_options, _track_options, identity_summary, score_summary)
 from dagr.utils.buffers import DETECTION_DTYPE, detections_to_records
 from dagr.utils.logging import set_up_logging_directory
 from dagr.utils import synthetic as syn
@@ -128,6 +134,10 @@ def stream_options(p):
                    "labelled boxes (source.labels), on the device")
     g.add_argument("--track_score_iou", type=float, default=None, help="with --track_score: the IoU a match needs, in "
                    "(0, 1] (default 0.5)")
+    g.add_argument("--track_identity", action="store_true", help="with --track_score: IDF1 / IDP / IDR from the maximum-weight "
+                   "pairing of object identities with track ids, on the device")
+    g.add_argument("--track_identity_max_tracks", type=int, default=None, help="with --track_identity: the size of the table "
+                   "of track ids, 1..1024 (default 256)")
     g.add_argument("--raw_frames", action="store_true", help="the source's frames are sensor-size BGR uint8 frames: prepare "
                    "them on the device (crop, shrink by the --downsample factor, / 255)")
 
@@ -209,6 +219,22 @@ def score_options(a, source=None):
     if source is not None and not callable(getattr(source, "labels", None)):
         raise SystemExit(f"run_stream.py: --track_score needs a source with labels(t_step); {type(source).__name__} has none "
                          "(the built-in synthetic sequence carries no labelled boxes)")
+    return given
+
+
+def identity_options(a):
+    """``identity=`` of the stream the flags describe: None without ``--track_identity``, else the options that were given."""
+    given = {} if getattr(a, "track_identity_max_tracks", None) is None else dict(max_tracks=a.track_identity_max_tracks)
+    if not getattr(a, "track_identity", False):
+        if given:
+            raise SystemExit("run_stream.py: --track_identity_max_tracks needs --track_identity")
+        return None
+    if not getattr(a, "track_score", False):
+        raise SystemExit("run_stream.py: --track_identity needs --track_score")
+    try:
+        _identity_options(given, True, "run_stream.py")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
     return given
 
 
@@ -327,6 +353,7 @@ def play(a, model, source, dev):
                          denoise_us=getattr(a, "denoise_us", None), refractory_us=getattr(a, "refractory_us", None),
                          flicker=flicker_options(a), trail_us=getattr(a, "trail_us", None),
                          track=track_options(a), motion=motion_options(a), rescue=rescue_options(a), score=score_options(a),
+                         identity=identity_options(a),
                          decode=decode, max_decoded=getattr(a, "max_decoded", None),
                          t_base=int(source.t_range()[0]) if decode else None)      # (the words' times start at the sequence's)
     t0, t1 = source.t_range()
@@ -374,6 +401,7 @@ def play(a, model, source, dev):
     if stream.score is not None:
         counters = stream.track_score()
         a.stream_score = dict(score_summary(counters, stream.scored_objects())["total"], steps=int(counters["steps"].sum()))
+    a.stream_identity = identity_summary(stream.identity())["total"] if stream.identity_options is not None else None
     return out
 
 
@@ -400,6 +428,7 @@ def main(argv=None, model_factory=None, source=None):
     moving = motion_options(a) is not None
     rescue_options(a)                      # (refusals in front of the model)
     score_options(a)
+    identity_options(a)
     a.batch_size = 1                       # one sequence: one lane
     world, rank, dev = C.distributed()
     torch.manual_seed(42)
@@ -463,6 +492,10 @@ def main(argv=None, model_factory=None, source=None):
                         f"{c['frag']} fragmentations, {c['miss']} misses, {c['false_pos']} false positives, MOTA "
                         f"{c['mota']:.3f}, MOTP {c['motp']:.3f}, {c['mostly_tracked']} mostly tracked, {c['mostly_lost']} "
                         "mostly lost")
+        if getattr(a, "stream_identity", None) is not None:
+            c = a.stream_identity
+            tracked += (f"; IDF1 {c['idf1']:.3f}, IDP {c['idp']:.3f}, IDR {c['idr']:.3f} (IDTP {c['idtp']} of {c['gt_frames']} "
+                        f"labelled and {c['hyp_frames']} tracked frames, {c['objects']} objects, {c['tracks']} tracks)")
         print(f"{len(steps)} steps of {a.step_us} us on {window} in {seconds:.2f} s "
               f"({1e3 * seconds / max(1, len(steps)):.2f} ms per step; {a.stream_steps[0]} with the full window, "
               f"{a.stream_steps[1]} on held image maps) -> {path}: {len(rec)} detections{tracked}")
