@@ -486,6 +486,7 @@ class StreamState:
         self.motion = None                              # the options of its motion model (dagr.streaming._motion_options)
         self.track_boxes, self.track_vel, self.coast = None, None, None
         self.rescue, self.lane_rescued = None, None     # the options of its second round (dagr.streaming._rescue_options)
+        self.assign, self.assign_ws = None, None        # "optimal": dagr_stream_track_optimal and its workspace
         self.score = None                               # the options of its scorer (dagr.streaming._score_options)
         self.score_state, self.gt_match, self.gt_flags = None, None, None
         self._last_det, self._scored = None, False      # the last step's (det, n_keep); whether run_score has had them
@@ -498,14 +499,17 @@ class StreamState:
     TRACK_FIELDS = (("id", torch.int64, 1), ("t_last", torch.int64, 1), ("box", torch.float32, 4), ("vel", torch.float32, 4),
                     ("label", torch.int32, 1), ("hits", torch.int32, 1))
 
-    def enable_track(self, options, motion=None, rescue=None):
+    def enable_track(self, options, motion=None, rescue=None, assign=None):
         """Every step ends with ``dagr_stream_track``: ``options`` as ``dagr.streaming._track_options`` returns them.
         Allocates the lanes' slots, empty, and ``lane_untracked``.  With ``motion`` (as ``_motion_options`` returns it)
         the step ends with ``dagr_stream_track_cv`` instead, on a state of that layout, and the coast lists are allocated.
         With ``rescue`` (as ``_rescue_options`` returns it) the step ends with the ``_rescue`` entry of the one or the
-        other, on the same state -- ``_bytes`` and ``_reset`` are the family's --, and ``lane_rescued`` is allocated."""
+        other, on the same state -- ``_bytes`` and ``_reset`` are the family's --, and ``lane_rescued`` is allocated.
+        With ``assign`` (as ``_assign_options`` returns it: ``"optimal"``) the step ends with ``dagr_stream_track_optimal``
+        instead of any of the four, on the same state again, and its workspace is allocated."""
         self.track, self.motion = dict(options), None if motion is None else dict(motion)
         self.rescue = None if rescue is None else dict(rescue)
+        self.assign = assign
         # the family of entry points dagr_<family>, dagr_<family>_bytes, dagr_<family>_reset, chosen here once -- as a
         # name: every call looks its function up on the library
         self._track_family = "stream_track" if motion is None else "stream_track_cv"
@@ -517,6 +521,11 @@ class StreamState:
         self.lane_untracked = torch.zeros((self.B,), dtype=torch.int64, device=dev)
         if rescue is not None:
             self.lane_rescued = torch.zeros((self.B,), dtype=torch.int64, device=dev)
+        if assign is not None:
+            ws_bytes = _lib.lib().dagr_stream_track_optimal_bytes(self.B, M)
+            if ws_bytes == 0:
+                raise RuntimeError(f"dagr_stream_track_optimal_bytes({self.B}, {M}): out of range")
+            self.assign_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         if motion is not None:
             self.coast = (torch.zeros((self.B,), dtype=torch.int32, device=dev),            # n_coast
                           torch.zeros((self.B, M), dtype=torch.int64, device=dev),          # coast_id
@@ -542,7 +551,8 @@ class StreamState:
         """``dagr_stream_track`` on a step's detections, at the reference instants the step's staging left in the stream
         state: ``track_ids`` int64 [B, A] and ``track_hits`` int32 [B, A], valid until the next step.  With a motion model
         ``dagr_stream_track_cv`` instead, never both: it also leaves ``track_boxes`` / ``track_vel`` and the coast lists.
-        With a second round the one launch is the ``_rescue`` entry of either, which also adds to ``lane_rescued``."""
+        With a second round the one launch is the ``_rescue`` entry of either, which also adds to ``lane_rescued``.  With
+        ``assign`` the one launch is ``dagr_stream_track_optimal``, whose flags say which of the four it stands for."""
         B, A = int(det.shape[0]), int(det.shape[1])
         if B != self.B or det.dtype != torch.float32 or not det.is_contiguous() or n_keep.dtype != torch.int32:
             raise RuntimeError(f"run_track: det must be contiguous fp32 [{self.B}, A, 6] and n_keep int32 [{self.B}]")
@@ -566,10 +576,33 @@ class StreamState:
         suffix, second = "", []             # what the _rescue entries take in addition, behind `untracked`
         if self.rescue is not None:
             suffix, second = "_rescue", [self.rescue["low_score"], self.rescue["iou"], P(self.lane_rescued)]
+        if self.assign is not None:
+            self._run_track_optimal(det, n_keep, A)
+            return
         _lib.check(self._track_fn(suffix)(P(self.track_state), self.track_state.numel(), self.B, o["max_tracks"], o["iou"],
                                           o["max_age_us"], o["min_score"], *gains, P(det), P(n_keep), A, self._t_ref[2],
                                           P(self.track_ids), P(self.track_hits), *outputs, P(self.lane_untracked), *second,
                                           _lib.cur_stream(self.device)), self._track_family + suffix)
+        self._last_det, self._scored = (det, n_keep), False
+
+    def _run_track_optimal(self, det, n_keep, A):
+        """``run_track``'s one launch with ``assign``: the arguments of ``dagr_stream_track_cv_rescue``, NULL / 0 where a
+        flag is clear, then the flags and the workspace."""
+        L, P, o, D = _lib.lib(), _lib.ptr, self.track, _lib.DEFINES
+        flags, gains, outputs, second = 0, [0.0, 0.0], [None] * 7, [0.0, 0.0, None]
+        if self.motion is not None:
+            n_coast, c_id, c_box, c_label, c_age = self.coast
+            flags |= D["DAGR_TRACK_OPTIMAL_MOTION"]
+            gains = [self.motion["alpha"], self.motion["beta"]]
+            outputs = [P(self.track_boxes), P(self.track_vel), P(c_id), P(c_box), P(c_label), P(c_age), P(n_coast)]
+        if self.rescue is not None:
+            flags |= D["DAGR_TRACK_OPTIMAL_RESCUE"]
+            second = [self.rescue["low_score"], self.rescue["iou"], P(self.lane_rescued)]
+        _lib.check(L.dagr_stream_track_optimal(P(self.track_state), self.track_state.numel(), self.B, o["max_tracks"], o["iou"],
+                                               o["max_age_us"], o["min_score"], *gains, P(det), P(n_keep), A, self._t_ref[2],
+                                               P(self.track_ids), P(self.track_hits), *outputs, P(self.lane_untracked),
+                                               *second, flags, P(self.assign_ws), self.assign_ws.numel(),
+                                               _lib.cur_stream(self.device)), "stream_track_optimal")
         self._last_det, self._scored = (det, n_keep), False
 
     # ------------------------------------------------------------------------------------ scoring the tracks

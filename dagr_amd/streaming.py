@@ -210,6 +210,32 @@ motion model's predict, filter and coast are what they are above, over the rows 
 ``rescued`` is int64 ``[B]``, cumulative, zero after construction and after ``reset()``.  Unlike ByteTrack, round two
 considers every live unmatched track, not only those seen in the step before.  Without ``rescue`` nothing of this exists.
 
+An optimal assignment in the match (``assign=`` of a tracking stream, with or without ``motion=`` and ``rescue=``: ``None``
+and ``"greedy"`` are the rules above, ``"optimal"`` is this paragraph; anything else is refused.  It needs ``track=``).
+Greedy matching in row order goes wrong in a crowd: box 1 overlaps tracks A (0.6) and B (0.7), box 2 overlaps B only
+(0.5); greedy gives B to box 1, box 2 spawns a new id and A is lost, where a one-to-one assignment keeps both.
+``TrackDefinition(batch_size, track, motion, rescue, assign="optimal")`` states it in numpy and
+``dagr_stream_track_optimal`` repeats it bit for bit on the state of ``dagr_stream_track`` / ``dagr_stream_track_cv``.  It
+replaces only the MATCH of a round; never, retire, eligibility, the ``DAGR_TRACK_MAX_DETS`` cut, predict, filter, the low
+rows, the spawn order, coast and ``rescued`` stay.  For a round -- round one: the participating high rows at the tracker's
+``iou``; with ``rescue=`` round two: the participating low rows at rescue's ``iou``:
+
+* ``w`` is int32 ``[rows of the round in row order, max_tracks slots in slot order]``.  ``w[r, s] = (1 << 29) + q`` if slot
+  ``s`` is live (after the retirement), no earlier round of this step took it, its label equals the row's, and
+  ``v = iou(row, box[s])`` (with ``motion=``: ``iou(row, pred[s])``) satisfies ``v >= `` the round's threshold -- a NaN never
+  does; ``q = (int32)(v * 1048576.0f)``, an fp32 multiply and a truncating conversion,
+  ``(v * np.float32(1048576)).astype(np.int32)``: the IoU is quantised to 2**-20.  Every other entry is 0;
+* the pairing is ``assign_max_weight_definition(w)``'s ``row_col`` (below), and the device's is that pairing entry for
+  entry.  ``256 * 2**20 < 2**29``, so the pairing has the most matches possible and, among those, the largest sum of
+  quantised IoU; every weight stays below ``2**31``;
+* every pair then does exactly what a match does above (box or filter, ``t_last``, ``hits += 1``, the row's outputs, in
+  round two ``rescued``).  Pairs do not interact, so applying them in any order gives the same state.  Round one's
+  unpaired rows spawn in row order; round two's get no id.
+
+Most-matches-first is this project's choice, not SORT's rule, which solves on all pairs and then drops the pairs under the
+threshold.  Which of several optimal pairings is taken decides track ids; it is the definition's walk -- the lowest column
+on a tie -- and nothing else.  Without ``assign`` nothing of this exists.
+
 Scoring the tracks against labelled boxes (``score=`` of a tracking stream: ``None`` is off, ``True`` takes the defaults, a
 dict sets ``iou``, fp32 in (0, 1], default 0.5, ``max_objects``, 1 .. ``DAGR_SCORE_MAX_OBJECTS = 1024``, default 256, and
 ``boxes``, ``"det"`` (default: a hypothesis is the detection's box) or ``"track"`` (the motion model's ``track_box``; needs
@@ -274,7 +300,8 @@ augmenting paths in integers on the cost ``-w`` with the smaller side as rows (`
 ``minv[j] = min(minv[j], cost[p[j0], j] - u[p[j0]] - v[j])`` over the unused columns, takes ``delta`` = the smallest ``minv``,
 the LOWEST column on a tie, moves the potentials by ``delta`` and goes on from that column until it is free; then the path
 is flipped.  ``total`` is unique, ``row_col`` is not: a pairing is right if it is one-to-one, lists only pairs with
-``w > 0`` and sums to ``total``; nothing may compare pairings bit for bit.
+``w > 0`` and sums to ``total``.  The device's pairing is nevertheless THIS walk's, entry for entry (the same relaxation, the
+lowest column on a tie, the same transposition; ``tests/test_assign_pairing_gpu.py``): ``assign="optimal"`` relies on it.
 
 The identity state: every lane owns a track table of ``max_tracks`` columns in order of first appearance (``track_id`` int64,
 ``track_len`` int64) and ``n_tracks``, ``obj_len`` int64 ``[max_objects]`` over the scorer's object slots, ``overlap`` int32
@@ -655,6 +682,23 @@ def _rescue_options(rescue, track_options, who):
     return dict(low_score=float(low), iou=float(np.float32(track_options["iou"] if opt["iou"] is None else opt["iou"])))
 
 
+ASSIGN_ONE = 1 << 29            # what an admissible pair weighs before its IoU: above 256 quantised IoUs, so matches count first
+ASSIGN_IOU_ONE = 1 << 20        # the IoU of a pair is quantised to 2**-20
+
+
+def _assign_options(assign, track_options, who):
+    """``assign=`` of a tracking stream, checked: None and ``"greedy"`` are None (the greedy match), ``"optimal"`` stays;
+    ``track_options`` is what ``_track_options`` returned.  Refusals by name."""
+    if assign is None:
+        return None
+    if not isinstance(assign, str) or assign not in ("greedy", "optimal"):
+        raise ValueError(f"{who}: assign = {assign!r} must be None or 'greedy' (the greedy match) or 'optimal' (an optimal "
+                         "assignment per round)")
+    if track_options is None:
+        raise ValueError(f"{who}: assign= needs track= (the assignment is the tracker's match)")
+    return None if assign == "greedy" else assign
+
+
 class TrackDefinition:
     """The tracker of the module docstring in numpy: ``step(det, n_keep, t_ref)`` is one step of every lane and returns
     ``(track_id int64 [B, A], track_hits int32 [B, A])`` with the rows at and behind ``n_keep[b]`` zero.  The state is the
@@ -674,13 +718,23 @@ class TrackDefinition:
     With ``rescue`` (``True`` or a dict of ``low_score``, ``iou``) the step has the second association round of the module
     docstring, with or without ``motion``: the yardstick of ``dagr_stream_track_rescue`` / ``dagr_stream_track_cv_rescue``.
     ``rescued`` int64 ``[B]`` counts the matches of round two, and so does ``events["rescued"]``.  Without ``rescue``
-    neither exists and every result is what it was."""
+    neither exists and every result is what it was.
 
-    def __init__(self, batch_size, track=True, motion=None, rescue=None):
+    With ``assign="optimal"`` the match of every round is the optimal assignment of the module docstring, with ``motion``
+    and ``rescue`` composing as they do without it: the yardstick of ``dagr_stream_track_optimal``.  ``events`` then also
+    counts ``conflicts``, the rounds (of one lane and one step) in which some row or some track had two or more admissible
+    partners, and ``reassigned``, the rounds whose pairing differs from what the greedy rule gives on the same state; and
+    ``rounds`` lists, for the LAST step, ``dict(lane, second, rows, w, row_col, greedy)`` per round that had rows -- the
+    weights, the pairing and the greedy rule's pairing, slots by row, -1 for none.  ``motion_only`` then asks whether an
+    unpredicted box of a track that was untaken when the round began reaches the round's threshold.  Without ``assign``
+    (``None`` or ``"greedy"``) nothing of this exists and every result is what it was."""
+
+    def __init__(self, batch_size, track=True, motion=None, rescue=None, assign=None):
         self.B = int(batch_size)
         self.options = _track_options(track, "TrackDefinition")
         self.motion = _motion_options(motion, self.options, "TrackDefinition")
         self.rescue = _rescue_options(rescue, self.options, "TrackDefinition")
+        self.assign = _assign_options(assign, self.options, "TrackDefinition")
         if self.options is None:
             raise ValueError("TrackDefinition: track = None is a stream that does not track")
         self.reset()
@@ -703,6 +757,9 @@ class TrackDefinition:
         if self.rescue is not None:
             self.rescued = np.zeros(B, np.int64)
             self.events.update(rescued=0)
+        if self.assign is not None:
+            self.rounds = []
+            self.events.update(conflicts=0, reassigned=0)
 
     @staticmethod
     def iou(a, b):
@@ -734,6 +791,8 @@ class TrackDefinition:
         if motion:
             alpha, beta = f(self.motion["alpha"]), f(self.motion["beta"])
             self.track_box, self.track_vel = np.zeros((B, A, 4), np.float32), np.zeros((B, A, 4), np.float32)
+        if self.assign is not None:
+            self.rounds = []
         for b in range(B):
             n, now = min(max(int(n_keep[b]), 0), A), int(t_ref[b])
             if motion:
@@ -766,25 +825,10 @@ class TrackDefinition:
             if rescue:                                             # round two: the low rows, behind every high row
                 low = [i for i in range(n) if det[b, i, 4] >= low_score and not det[b, i, 4] >= min_score]
                 rows += [(i, low_thr, True) for i in low[:DAGR_TRACK_MAX_DETS]]
-            for i, bar, second in rows:                            # match: the rule of both rounds
-                with np.errstate(all="ignore"):
-                    label = int(det[b, i, 5].astype(np.int32))
-                best, best_s = None, None
-                for s in live:
-                    if s in taken or int(self.label[b, s]) != label:
-                        continue
-                    v = self.iou(det[b, i, :4], against[s])
-                    if not v >= bar:                               # (a NaN IoU never matches)
-                        continue
-                    if best is None or v > best or (v == best and self.id[b, s] < self.id[b, best_s]):
-                        best, best_s = v, s
-                if best_s is None:
-                    if not second:                                 # (a low row never spawns and is not counted)
-                        unmatched.append((i, label))
-                    continue
-                s, z = best_s, det[b, i, :4]
+            def matches(i, label, s, bar, second, gone):            # what a match does, in either round, under either rule
+                z = det[b, i, :4]
                 if motion and not any(self.iou(z, self.box[b, c]) >= bar for c in live
-                                      if c not in taken and int(self.label[b, c]) == label):
+                                      if c not in gone and int(self.label[b, c]) == label):
                     self.events["motion_only"] += 1                # (the plain rule would have spawned this row)
                 taken.add(s)
                 if motion:                                         # filter: the row pulls box and vel off the prediction
@@ -806,6 +850,44 @@ class TrackDefinition:
                 if second:
                     self.rescued[b] += 1
                     self.events["rescued"] += 1
+
+            if self.assign is not None:                            # match: one optimal assignment per round
+                for second in (False, True)[:2 if rescue else 1]:
+                    members = [i for i, _, sec in rows if sec == second]
+                    if not members:
+                        continue
+                    bar = low_thr if second else thr
+                    w, greedy = self._round_weights(b, det, members, live, taken, against, bar)
+                    row_col = assign_max_weight_definition(w)[1]
+                    self.events["conflicts"] += int(((w > 0).sum(0) > 1).any() or ((w > 0).sum(1) > 1).any())
+                    self.events["reassigned"] += int(not np.array_equal(row_col, greedy))
+                    self.rounds.append(dict(lane=b, second=second, rows=members, w=w, row_col=row_col, greedy=greedy))
+                    before = set(taken)
+                    for i, s in zip(members, row_col):
+                        with np.errstate(all="ignore"):
+                            label = int(det[b, i, 5].astype(np.int32))
+                        if s >= 0:
+                            matches(i, label, int(s), bar, second, before)
+                        elif not second:
+                            unmatched.append((i, label))
+                rows = []
+            for i, bar, second in rows:                            # match: the rule of both rounds
+                with np.errstate(all="ignore"):
+                    label = int(det[b, i, 5].astype(np.int32))
+                best, best_s = None, None
+                for s in live:
+                    if s in taken or int(self.label[b, s]) != label:
+                        continue
+                    v = self.iou(det[b, i, :4], against[s])
+                    if not v >= bar:                               # (a NaN IoU never matches)
+                        continue
+                    if best is None or v > best or (v == best and self.id[b, s] < self.id[b, best_s]):
+                        best, best_s = v, s
+                if best_s is None:
+                    if not second:                                 # (a low row never spawns and is not counted)
+                        unmatched.append((i, label))
+                    continue
+                matches(i, label, best_s, bar, second, taken)
             free = [int(s) for s in np.flatnonzero(self.id[b] == 0)]
             for (i, label), s in zip(unmatched, free):             # spawn (with motion: at rest)
                 self.id[b, s], self.t_last[b, s], self.box[b, s] = self.next_id[b], now, det[b, i, :4]
@@ -828,6 +910,33 @@ class TrackDefinition:
                 self.n_coast[b] = len(coast)
                 self.events["coasted"] += len(coast)
         return ids, hits
+
+    def _round_weights(self, b, det, members, live, taken, against, bar):
+        """One round of ``assign="optimal"``: ``w`` int32 ``[rows of the round, max_tracks]`` as the module docstring states
+        it, and, slots by row (-1: none), what the greedy rule pairs on the same state."""
+        M = self.options["max_tracks"]
+        w, v = np.zeros((len(members), M), np.int32), {}
+        for r, i in enumerate(members):
+            with np.errstate(all="ignore"):
+                label = int(det[b, i, 5].astype(np.int32))
+                for s in live:
+                    if s in taken or int(self.label[b, s]) != label:
+                        continue
+                    v[r, s] = self.iou(det[b, i, :4], against[s])
+                    if v[r, s] >= bar:                             # (a NaN IoU never does)
+                        w[r, s] = ASSIGN_ONE + (v[r, s] * np.float32(ASSIGN_IOU_ONE)).astype(np.int32)
+        greedy, gone = np.full(len(members), -1, np.int64), set()
+        for r in range(len(members)):
+            best = None
+            for s in np.flatnonzero(w[r]):
+                s = int(s)
+                if s not in gone and (best is None or v[r, s] > v[r, best] or
+                                      (v[r, s] == v[r, best] and self.id[b, s] < self.id[b, best])):
+                    best = s
+            if best is not None:
+                greedy[r] = best
+                gone.add(best)
+        return w, greedy
 
     def coasting(self):
         """Per lane the last step's coasting tracks, a ``COAST_DTYPE`` array in slot order (``EventStream.coasting()``)."""
@@ -1710,6 +1819,11 @@ class EventStream:
     is then ``dagr_stream_track_rescue`` or ``dagr_stream_track_cv_rescue``.  ``rescued()`` counts its matches.  The
     defaults are ByteTrack's conventions, not measured optima.  A stream built without it issues exactly the calls it
     issues without the round.
+    ``assign`` (``None`` or ``"greedy"``: the greedy match; ``"optimal"``; needs ``track``): the match of every round is an
+    optimal one-to-one assignment -- the most matches, then the largest sum of IoUs quantised to 2**-20 (module docstring)
+    -- with ``motion`` and ``rescue`` composing as they do without it; the step's one tracker launch is then
+    ``dagr_stream_track_optimal``, on the same state, with a workspace the stream owns.  A stream built without it issues
+    exactly the calls it issues without it.
     ``score`` (``None``: off, ``True``: the defaults, or a dict of ``iou``, ``max_objects``, ``boxes``; needs ``track``):
     ``score_step(gt_box, gt_label, gt_id, n_gt)`` scores the last step's track ids against labelled boxes on the device --
     this project's statement of the CLEAR-MOT counts with a greedy matcher (module docstring) --, ``track_score()`` reads
@@ -1747,12 +1861,13 @@ class EventStream:
     def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
                  max_lane_events=None, denoise_us=None, refractory_us=None, track=None, motion=None, rescue=None,
                  decode=None, max_decoded=None, t_base=None, flicker=None, trail_us=None, score=None,
-                 identity=None):
+                 identity=None, assign=None):
         import torch
         self.model = model
         self.track = _track_options(track, "EventStream")
         self.motion = _motion_options(motion, self.track, "EventStream")
         self.rescue = _rescue_options(rescue, self.track, "EventStream")
+        self.assign = _assign_options(assign, self.track, "EventStream")
         self.score = _score_options(score, self.track, self.motion, "EventStream")
         self.identity_options = _identity_options(identity, self.score, "EventStream")
         time_window = int(getattr(model.args, "time_window_us", 1000000))
@@ -1801,7 +1916,7 @@ class EventStream:
         if self.flicker is not None or self.trail_us is not None:
             self.state.enable_flicker(w_in, h_in, self.flicker, self.trail_us)
         if self.track is not None:
-            self.state.enable_track(self.track, motion=self.motion, rescue=self.rescue)
+            self.state.enable_track(self.track, motion=self.motion, rescue=self.rescue, assign=self.assign)
         if self.score is not None:
             self.state.enable_score(self.score)
         if self.identity_options is not None:

@@ -626,6 +626,62 @@ int dagr_stream_track_cv_rescue(void *tracks, size_t bytes, int32_t B, int32_t m
                                 int64_t *rescued /* [B], accumulated; may be NULL */, void *stream);
 
 /* ------------------------------------------------------------------------ *
+ * Event stream tracker, optimal assignment: the match of a round as a one-to-one assignment, not greedily
+ *   dagr_stream_track_optimal is any of the four entries above -- flags says which -- with the MATCH of a round replaced:
+ *   the rows of the round and the lane's slots are paired by dagr_assign_max_weight's method, so that the round has the most
+ *   matches possible and, among those, the largest sum of IoUs.  Greedy matching in row order gives a track to the first
+ *   row that wants it and may leave a later row, which overlaps that track alone, without one.  One launch (one wave per
+ *   lane) in place of the greedy entry's, no host synchronisation, no atomics.  dagr_amd/streaming.py:
+ *   TrackDefinition(assign="optimal") is the same in numpy, bit for bit.
+ *
+ * It works on the SAME states as the greedy entries: dagr_stream_track[_cv]_bytes and _reset serve it.  never / retire /
+ * eligible / the DAGR_TRACK_MAX_DETS cut / predict / filter / low rows / spawn / coast / rescued are stated above and
+ * unchanged.  For a round (round one: the participating high rows at the threshold iou; with DAGR_TRACK_OPTIMAL_RESCUE
+ * round two: the participating low rows at low_iou):
+ *   weights:  w int32[rows of the round in row order, max_tracks slots in slot order].  w[r, s] = (1 << 29) + q if slot s is
+ *             live (after the retirement), no earlier round of this step took it, its label is the row's and
+ *             v = iou(row, box[s]) -- with DAGR_TRACK_OPTIMAL_MOTION iou(row, pred[s]) -- satisfies v >= the round's
+ *             threshold (a NaN never does); q = (int32_t)(v * 1048576.0f), one fp32 multiply and a truncating conversion:
+ *             the IoU is quantised to 2^-20.  Every other entry is 0.  256 * 2^20 < 2^29: one more match outweighs every
+ *             IoU; every weight is below 2^31.
+ *   pairing:  row_col of dagr_assign_max_weight's method on w (n_rows = the round's rows, n_cols = max_tracks; more rows
+ *             than slots: the transposed matrix).  The pairing is the definition's: the device routine makes
+ *             assign_max_weight_definition's comparisons one for one -- the same relaxation, the lowest column on a tie, the
+ *             same transposition -- and tests/test_assign_pairing_gpu.py holds row_col equal entry for entry on matrices
+ *             full of ties.  Track ids depend on it.
+ *   apply:    every pair (row, slot) does exactly what a match of the greedy entry does (box or filter, t_last, hits += 1,
+ *             the row's outputs; in round two rescued[b] += 1).  Pairs do not interact: any order leaves the same state.
+ *             Round one's rows without a pair spawn in row order, round two's get no id.
+ * Most-matches-first is this project's choice.  It is not SORT's rule, which solves on all pairs and then drops the pairs
+ * under the threshold.
+ *
+ * flags: DAGR_TRACK_OPTIMAL_MOTION (bit 0) selects dagr_stream_track_cv's state layout and motion model,
+ *        DAGR_TRACK_OPTIMAL_RESCUE (bit 1) the second round.  Without bit 0 alpha, beta, track_box, track_vel and the five
+ *        coast arrays are not looked at and may be 0 / NULL; without bit 1 low_score, low_iou and rescued are not looked at.
+ *        With a bit set its arguments are what dagr_stream_track_cv / the _rescue entries take, refused as there.
+ * ws:    dagr_stream_track_optimal_bytes(B, max_tracks) bytes (0: B outside 1..65535 or max_tracks outside
+ *        1..DAGR_TRACK_MAX_TRACKS), 16-byte aligned, caller-owned, means nothing between calls.  Lane b owns
+ *        2 * DAGR_TRACK_MAX_DETS * max_tracks int32 words at word b * 2 * DAGR_TRACK_MAX_DETS * max_tracks: first the weight
+ *        matrix of the round being matched, w[r, s] at word r * max_tracks + s, then, DAGR_TRACK_MAX_DETS * max_tracks words
+ *        on, the transposed copy the method wants when the round has more rows than the lane has slots.
+ * Everything else as dagr_stream_track_cv_rescue takes it.
+ * DAGR_ERR_INVALID_ARG before any launch: unknown bits in flags; whatever dagr_stream_track refuses; with bit 0 whatever
+ * dagr_stream_track_cv adds (partly NULL coast arrays among it), with bit 1 whatever the _rescue entries add; a NULL,
+ * misaligned or too small workspace.
+ * ------------------------------------------------------------------------ */
+#define DAGR_TRACK_OPTIMAL_MOTION 1
+#define DAGR_TRACK_OPTIMAL_RESCUE 2
+size_t dagr_stream_track_optimal_bytes(int32_t B, int32_t max_tracks);
+int dagr_stream_track_optimal(void *tracks, size_t bytes, int32_t B, int32_t max_tracks, float iou, int64_t max_age_us,
+                              float min_score, float alpha, float beta, const float *det, const int32_t *n_keep, int32_t A,
+                              const int64_t *t_ref, int64_t *track_id, int32_t *track_hits, float *track_box,
+                              float *track_vel, int64_t *coast_id, float *coast_box, int32_t *coast_label,
+                              int64_t *coast_age_us, int32_t *n_coast,
+                              int64_t *untracked /* [B], accumulated; may be NULL */, float low_score, float low_iou,
+                              int64_t *rescued /* [B], accumulated; may be NULL */, int32_t flags, void *ws,
+                              size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * Event stream scorer: the track ids of a step against labelled boxes, on the device
  *   dagr_stream_score scores what a dagr_stream_track* entry left for a step -- det, n_keep, track_id and, optionally, the
  *   motion model's track_box -- against ground-truth boxes that carry an identity, and accumulates the CLEAR-MOT counts
@@ -700,7 +756,9 @@ int dagr_stream_score(void *state, size_t bytes, int32_t B, int32_t max_objects,
  * column until it is free; then the path is flipped.
  * total int64[B]: the largest sum, which is unique.  row_col int32[B, max_rows]: for r < n_rows[b] the column paired with
  * row r in ONE pairing that reaches it, or -1 (no pair, or a pair of weight 0); -1 for the rows behind n_rows[b].  The
- * pairing is not unique: it is one-to-one, lists only pairs with w > 0 and sums to total; compare nothing else.
+ * pairing is not unique: it is one-to-one, lists only pairs with w > 0 and sums to total.  WHICH pairing comes back is
+ * fixed, though: the pairing is the definition's, assign_max_weight_definition's row_col entry for entry (the same walk,
+ * comparison for comparison; tests/test_assign_pairing_gpu.py).  dagr_stream_track_optimal relies on that.
  * workspace: dagr_assign_workspace_bytes(B, max_rows, max_cols) bytes (0: a size out of range), 16-byte aligned; it holds
  * the transposed matrices, int32[B, max_cols, max_rows], and means nothing between calls.  All in device memory.
  * DAGR_ERR_INVALID_ARG before any launch: B outside 1..65535, max_rows / max_cols outside 1..DAGR_ASSIGN_MAX, ld_rows <

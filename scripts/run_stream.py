@@ -55,6 +55,11 @@ its id.  ``--track_low_iou I`` (needs ``--track_low_score``) gives that round an
 ``--track_iou``).  0.1 for ``L`` and 0.5 for ``--track_min_score`` are ByteTrack's conventions, not measured optima.  The
 number of rescued matches is printed with the summary.
 
+``--track_assign optimal`` (needs ``--track``; ``greedy`` is the default rule): the match of every association round is an
+optimal one-to-one assignment instead of the greedy walk in score order (``dagr.streaming``: ``EventStream(assign=)``): the
+most matches, then the largest sum of IoUs.  It pays where boxes crowd and changes next to nothing elsewhere.  The rule is
+named in the summary's tracker line.
+
 ``--track_score`` (needs ``--track``): the track ids are scored against labelled boxes on the device (``dagr.streaming``:
 ``EventStream(score=)``, this project's statement of the CLEAR-MOT counts with a greedy matcher; agreement with another MOT
 tool is not claimed).  The source must have ``labels(t_step)``, which returns ``None`` (no labels at this instant) or
@@ -81,7 +86,7 @@ import torch
 
 import _common as C
 from dagr.data.evt import encode_events
-from dagr.streaming import (EventStream, _flicker_options, _identity_options, _motion_options, _rescue_options,
+from dagr.streaming import (EventStream, _assign_options, _flicker_options, _identity_options, _motion_options, _rescue_options,
                             _score_options, _track_options, identity_summary, score_summary)
 from dagr.utils.buffers import DETECTION_DTYPE, detections_to_records
 from dagr.utils.logging import set_up_logging_directory
@@ -130,6 +135,8 @@ def stream_options(p):
                    "detections with a confidence in [L, --track_min_score) continue a track (never start one)")
     g.add_argument("--track_low_iou", type=float, default=None, help="with --track_low_score: that round's own smallest IoU "
                    "in (0, 1] (default: --track_iou)")
+    g.add_argument("--track_assign", default=None, help="with --track: 'optimal' matches every association round by an "
+                   "optimal one-to-one assignment, 'greedy' (the default) in score order")
     g.add_argument("--track_score", action="store_true", help="with --track: score the track ids against the source's "
                    "labelled boxes (source.labels), on the device")
     g.add_argument("--track_score_iou", type=float, default=None, help="with --track_score: the IoU a match needs, in "
@@ -197,6 +204,20 @@ def rescue_options(a):
         raise SystemExit("run_stream.py: --track_low_score needs --track")
     try:
         _rescue_options(given, _track_options(track_options(a), "run_stream.py"), "run_stream.py")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    return given
+
+
+def assign_option(a):
+    """``assign=`` of the stream the flags describe: None without ``--track_assign``, else what was given."""
+    given = getattr(a, "track_assign", None)
+    if given is None:
+        return None
+    if not getattr(a, "track", False):
+        raise SystemExit("run_stream.py: --track_assign needs --track")
+    try:
+        _assign_options(given, _track_options(track_options(a), "run_stream.py"), "run_stream.py")
     except ValueError as e:
         raise SystemExit(str(e)) from None
     return given
@@ -352,7 +373,8 @@ def play(a, model, source, dev):
                          frame_size=raw_size, frame_bgr=True, max_lane_events=cap,
                          denoise_us=getattr(a, "denoise_us", None), refractory_us=getattr(a, "refractory_us", None),
                          flicker=flicker_options(a), trail_us=getattr(a, "trail_us", None),
-                         track=track_options(a), motion=motion_options(a), rescue=rescue_options(a), score=score_options(a),
+                         track=track_options(a), motion=motion_options(a), rescue=rescue_options(a), assign=assign_option(a),
+                         score=score_options(a),
                          identity=identity_options(a),
                          decode=decode, max_decoded=getattr(a, "max_decoded", None),
                          t_base=int(source.t_range()[0]) if decode else None)      # (the words' times start at the sequence's)
@@ -397,6 +419,7 @@ def play(a, model, source, dev):
     a.stream_decoded = {k: int(v.sum()) for k, v in stream.decode_counts().items()} if stream.decode is not None else None
     a.stream_untracked = int(stream.untracked().sum()) if stream.track is not None else None
     a.stream_rescued = int(stream.rescued().sum()) if stream.rescue is not None else None
+    a.stream_assign = stream.assign
     a.stream_score = None
     if stream.score is not None:
         counters = stream.track_score()
@@ -427,6 +450,7 @@ def main(argv=None, model_factory=None, source=None):
     tracking = track_options(a) is not None
     moving = motion_options(a) is not None
     rescue_options(a)                      # (refusals in front of the model)
+    assign_option(a)
     score_options(a)
     identity_options(a)
     a.batch_size = 1                       # one sequence: one lane
@@ -486,6 +510,8 @@ def main(argv=None, model_factory=None, source=None):
             tracked += f"; {len(coast)} coasted track-steps -> {out_dir / f'coasting_{a.sequence}.npy'}"
         if a.stream_rescued is not None:
             tracked += f"; {a.stream_rescued} low-score detections rescued by the second round"
+        if a.stream_assign is not None:
+            tracked += f"; every round matched by an {a.stream_assign} assignment"
         if a.stream_score is not None:
             c = a.stream_score
             tracked += (f"; scored {c['steps']} labelled steps: {c['objects']} objects, {c['switch']} id switches, "
