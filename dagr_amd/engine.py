@@ -454,7 +454,11 @@ class StreamState:
 
     An identity stream (``enable_identity``, on a scoring stream) owns the identity state (``dagr_stream_identity``): the
     lanes' track tables and overlap counts, and the assignment's workspace.  ``run_score`` then makes a second launch behind
-    the scorer's on the same arrays, still without a host wait; ``run_identity_solve`` is ``dagr_stream_identity_solve``."""
+    the scorer's on the same arrays, still without a host wait; ``run_identity_solve`` is ``dagr_stream_identity_solve``.
+
+    A HOTA stream (``enable_hota``, on an identity stream) owns HOTA's state (``dagr_stream_hota``): the alignment tables,
+    the log of the labelled instants, the last solve's counts, and the solve's workspace.  ``run_score`` then makes a third
+    launch behind the identity step's; ``run_hota_solve`` is ``dagr_stream_hota_solve``."""
 
     def __init__(self, batch_size, window_us, device, max_lane_events=None):
         self.B, self.window_us, self.device = int(batch_size), int(window_us), torch.device(device)
@@ -492,6 +496,8 @@ class StreamState:
         self._last_det, self._scored = None, False      # the last step's (det, n_keep); whether run_score has had them
         self.identity = None                            # the options of its IDF1 state (dagr.streaming._identity_options)
         self.identity_state, self.identity_ws, self.obj_track, self.identity_result = None, None, None, None
+        self.hota = None                                # the options of its HOTA state (dagr.streaming._hota_options)
+        self.hota_state, self.hota_ws = None, None
         self._t_ref = None                              # (state pointer, capacity, where its t_ref[B] lives)
 
     # ------------------------------------------------------------------------------------ track ids
@@ -660,6 +666,13 @@ class StreamState:
                                                        P(n_keep), A, P(self.track_ids), boxes, P(gt_box), P(gt_label), P(gt_id),
                                                        P(n_gt), G, P(self.gt_match), _lib.cur_stream(self.device)),
                        "stream_identity")
+        if self.hota is not None:                  # the third launch, behind the identity step's on the same arrays
+            _lib.check(_lib.lib().dagr_stream_hota(P(self.hota_state), self.hota_state.numel(), B, o["max_objects"],
+                                                   self.identity["max_tracks"], self.hota["max_instants"],
+                                                   P(self.identity_state), self.identity_state.numel(), P(self.score_state),
+                                                   self.score_state.numel(), P(det), P(n_keep), A, P(self.track_ids), boxes,
+                                                   P(gt_box), P(gt_label), P(gt_id), P(n_gt), G, P(self.gt_match),
+                                                   _lib.cur_stream(self.device)), "stream_hota")
         return self.gt_match, self.gt_flags
 
     # ------------------------------------------------------------------------------------ IDF1 behind the scorer
@@ -715,6 +728,72 @@ class StreamState:
         return dict(track_id=q[:B * T].reshape(B, T), track_len=q[B * T:2 * B * T].reshape(B, T),
                     obj_len=q[2 * B * T:2 * B * T + B * M].reshape(B, M), words=q[2 * B * T + B * M:].reshape(B, 8),
                     overlap=r[:B * M * T].reshape(B, M, T), obj_col=r[B * M * T:].reshape(B, M))
+
+    # ------------------------------------------------------------------------------------ HOTA behind the identity step
+    HOTA_THRESHOLDS = _lib.DEFINES["DAGR_HOTA_THRESHOLDS"]
+
+    def enable_hota(self, options):
+        """``run_score`` also runs HOTA's pass 1 and appends the labelled instant to the lanes' logs (``dagr_stream_hota``):
+        ``options`` as ``dagr.streaming._hota_options`` returns them, on a stream that keeps the identity state.  Allocates
+        the state, empty, and the workspace of the solve; refuses by name a state above ``DAGR_HOTA_MAX_STATE_BYTES``."""
+        if self.identity is None:
+            raise RuntimeError("enable_hota: the stream keeps no identity state (enable_identity comes first)")
+        L, M, T, I = _lib.lib(), self.score["max_objects"], self.identity["max_tracks"], int(options["max_instants"])
+        nbytes, ws = L.dagr_stream_hota_bytes(self.B, M, T, I), L.dagr_stream_hota_workspace_bytes(self.B, M, T, I)
+        if nbytes == 0 or ws == 0:
+            raise RuntimeError(f"dagr_stream_hota_bytes({self.B}, {M}, {T}, {I}): out of range")
+        limit = _lib.DEFINES["DAGR_HOTA_MAX_STATE_BYTES"]
+        if nbytes > limit:
+            raise ValueError(f"hota: batch_size = {self.B}, score max_objects = {M}, identity max_tracks = {T} and hota "
+                             f"max_instants = {I} need a state of {nbytes} bytes, above DAGR_HOTA_MAX_STATE_BYTES = {limit} "
+                             f"(the log takes {24 * _lib.DEFINES['DAGR_HOTA_LOG_ENTRIES']} bytes an instant and lane, the 19 "
+                             f"mc tables {76 * M * T} bytes a lane): lower max_instants, max_objects or max_tracks")
+        self.hota = dict(options)
+        self.hota_state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.hota_ws = torch.empty(ws, dtype=torch.uint8, device=self.device)
+        self._reset_hota()
+
+    def _reset_hota(self):
+        _lib.check(_lib.lib().dagr_stream_hota_reset(_lib.ptr(self.hota_state), self.hota_state.numel(), self.B,
+                                                     self.score["max_objects"], self.identity["max_tracks"],
+                                                     self.hota["max_instants"], _lib.cur_stream(self.device)),
+                   "stream_hota_reset")
+
+    def run_hota_solve(self):
+        """``dagr_stream_hota_solve`` on the log so far: the replay and the fp64 sums, left in the state (no host wait)."""
+        if self.hota is None:
+            raise RuntimeError("this stream keeps no HOTA state (hota=): it has no HOTA")
+        P = _lib.ptr
+        _lib.check(_lib.lib().dagr_stream_hota_solve(P(self.hota_state), self.hota_state.numel(), self.B,
+                                                     self.score["max_objects"], self.identity["max_tracks"],
+                                                     self.hota["max_instants"], P(self.hota_ws), self.hota_ws.numel(),
+                                                     _lib.cur_stream(self.device)), "stream_hota_solve")
+
+    def hota_sections(self):
+        """Where the arrays of the HOTA state lie, by the layout include/dagr_hip.h documents: ``{name: (byte offset, numpy
+        dtype, shape)}``, each array at the next multiple of 16 bytes behind the one before it."""
+        B, M, T, I = self.B, self.score["max_objects"], self.identity["max_tracks"], self.hota["max_instants"]
+        K, E = self.HOTA_THRESHOLDS, _lib.DEFINES["DAGR_HOTA_LOG_ENTRIES"]
+        out, at = {}, 0
+        for name, dtype, shape in (("pmc", np.int64, (B, M, T)), ("gc", np.int64, (B, M)), ("tc", np.int64, (B, T)),
+                                   ("words", np.int64, (B, 4)), ("count", np.int64, (B, K, 4)), ("sums", np.float64, (B, K, 3)),
+                                   ("log_box", np.float32, (B, I, E, 4)), ("log_n", np.int32, (B, I, 2)),
+                                   ("log_index", np.int32, (B, I, E)), ("log_label", np.int32, (B, I, E)),
+                                   ("mc", np.int32, (B, K, M, T))):
+            out[name] = (at, dtype, shape)
+            at += -(-int(np.prod(shape)) * np.dtype(dtype).itemsize // 16) * 16
+        return out
+
+    def hota_words(self, names):
+        """The named arrays of the HOTA state read back (``hota_sections``; copies; synchronises)."""
+        if self.hota is None:
+            raise RuntimeError("this stream keeps no HOTA state (hota=): it has no tables")
+        sections, out = self.hota_sections(), {}
+        for name in names:
+            at, dtype, shape = sections[name]
+            nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
+            out[name] = self.hota_state[at:at + nbytes].cpu().numpy().view(dtype).reshape(shape)
+        return out
 
     def score_words(self):
         """The state read back: ``(table int64 [8, B, max_objects] -- id, last_hyp, prev_hyp, seen_step, present, tracked,
@@ -1042,6 +1121,8 @@ class StreamState:
             self._reset_score()
         if self.identity_state is not None:
             self._reset_identity()
+        if self.hota_state is not None:
+            self._reset_hota()
         self.status.zero_()
         self.lane_count.zero_()
         self.lane_dropped.zero_()

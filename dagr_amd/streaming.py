@@ -246,7 +246,7 @@ the CLEAR MOT metrics"): misses, false positives, identity switches, MOTA and MO
 departs from the paper in the matcher: the assignment is greedy in ground-truth row order inside a label -- as the
 tracker's own matcher and the COCO matcher of this project are -- not a minimum-cost assignment, the overlap is an IoU
 and not a distance, and a label mismatch never matches.  Agreement with py-motmetrics or any other MOT tool is not
-claimed.  IDF1 and HOTA need a global assignment over the whole sequence: IDF1 is ``identity=`` below, HOTA is out of scope.
+claimed.  IDF1 and HOTA need a global assignment over the whole sequence: IDF1 is ``identity=`` below, HOTA is ``hota=`` behind it.
 
 Every lane owns an object table of ``max_objects`` slots in order of first appearance and ``n_objects``; a slot holds
 ``id`` int64 (the ground-truth identity, > 0), ``last_hyp`` int64 (the track id of its last match ever, 0: none),
@@ -326,6 +326,43 @@ arrays, with the ``gt_match`` that step wrote and the scorer's id table after it
 ``idf1 = 2 idtp / (gt_frames + hyp_frames)``, ``idp = idtp / hyp_frames`` and ``idr = idtp / gt_frames`` per lane and in
 total (the total sums the lanes' integers: lanes are separate sequences).  Agreement with py-motmetrics or TrackEval is
 not claimed.  Without ``identity`` nothing of this exists.
+
+HOTA (``hota=`` of an identity stream: ``None`` is off, ``True`` takes the default, a dict sets ``max_instants``,
+1 .. ``DAGR_HOTA_MAX_INSTANTS = 65535``, default 1200 -- 60 s of labels at 20 Hz.  It needs ``identity=``, which needs
+``score=``).  HOTA (Luiten et al., "HOTA: a higher order metric for evaluating multi-object tracking", IJCV 2021) is
+``sqrt(DetA * AssA)`` over 19 localisation thresholds ``alpha = k / 20``; it needs two passes, because the matching of an
+instant is weighted by an alignment score of (object, track) pairs that is known only when the whole sequence has been
+seen.  A stream therefore keeps a log of its labelled instants on the device and replays it.  ``HotaDefinition`` below
+states the rule once in integers and ``dagr_stream_hota`` / ``dagr_stream_hota_solve`` repeat it integer for integer.
+
+The participants of a labelled instant of lane ``b`` (``n_gt[b] >= 0``; a skipped lane changes nothing) are what the
+identity step used: the ground-truth rows that got an object slot ``s`` and the hypotheses that got a track column ``c``
+(not a duplicate id, listed in the identity state's track table after its step), each in row order, boxes by the scorer's
+``boxes`` option.  The similarity is ``q[g, i] = rint(fp32(iou) * 2**20)`` as an integer, the IoU ``TrackDefinition.iou``
+operation for operation, 0 when the labels differ or the IoU is NaN (or outside (0, 1], which only a box with a negative
+side gives).
+
+1. a full log: with ``instants == max_instants`` the instant only adds 1 to ``dropped_instants``;
+2. pass 1: ``rs[g]`` and ``cs[i]`` are the row and column sums of ``q`` in int64; for ``q > 0``
+   ``pmc[s, c] += (q << 20) // (rs[g] + cs[i] - q)`` (``pmc`` int64 ``[max_objects, max_tracks]``); ``gc[s] += 1`` and
+   ``tc[c] += 1`` for every participant -- HOTA's own counts, of logged instants only;
+3. log: the participants' slot or column, box and label are appended; ``instants += 1``, ``rows`` and ``columns`` grow by
+   the participants.  ``pmc <= 65535 * 2**20`` keeps every product below in int64.
+
+``solve()`` is pass 2, per logged instant with the FINAL tables: ``gq[s, c] = (pmc << 20) // (((gc[s] + tc[c]) << 20) - pmc)``,
+0 where ``pmc`` is 0; ``w[g, i] = (gq * q[g, i]) >> 10``, in 0 .. 2**30, compacted to the instant's rows and columns; the
+pairing is ``assign_max_weight_definition``'s, entry for entry.  For ``k = 1 .. 19`` a matched pair is a TP when
+``20 * q >= k << 20`` -- exact, no epsilon --: ``tp[k] += TPs``, ``fn[k] += rows - TPs``, ``fp[k] += columns - TPs``,
+``loc_q[k] +=`` the TPs' ``q``, ``mc[k][s, c] += 1`` per TP.  The reduce, per lane and ``k`` in fp64 over the pairs with
+``mc > 0``, one division then one multiplication a term: ``ass[k] = sum mc * (mc / (gc[s] + tc[c] - mc))``,
+``re[k] = sum mc * (mc / gc[s])``, ``pr[k] = sum mc * (mc / tc[c])``.  ``hota_summary`` gives per ``k`` and as means over the
+19 thresholds ``DetA = tp / max(1, tp + fn + fp)``, ``AssA = ass / max(1, tp)``, ``LocA = loc_q / (2**20 * tp)`` and
+``HOTA = sqrt(DetA * AssA)``, per lane and in total.
+
+This is THIS PROJECT'S statement of HOTA.  It departs from the usual tool: the similarities are quantised to ``2**-20``,
+the alignment score is floored to ``2**-20`` and the weight to ``2**-30``, a pair of weight 0 is never matched, there is no
+epsilon at the thresholds, the labels gate the similarity, and the instants behind ``max_instants`` are left out.
+Agreement with TrackEval is not claimed.  Without ``hota`` nothing of this exists.
 
 Camera words (``decode="evt3"`` or ``"evt2"``): an event camera delivers words, not arrays.  A decoding stream takes the
 camera's words (``step_words`` / ``step_words_device``) and decodes them on the device (``dagr_stream_decode``) in front of
@@ -1462,6 +1499,228 @@ def identity_summary(result):
     return dict(lanes=[one(c) for c in per_lane], total=one(total))
 
 
+DAGR_HOTA_MAX_INSTANTS = DEFINES["DAGR_HOTA_MAX_INSTANTS"]
+DAGR_HOTA_MAX_STATE_BYTES = DEFINES["DAGR_HOTA_MAX_STATE_BYTES"]
+HOTA_THRESHOLDS = DEFINES["DAGR_HOTA_THRESHOLDS"]        # alpha = k / 20, k = 1 .. 19
+HOTA_DEFAULTS = dict(max_instants=1200)
+HOTA_WORDS = ("instants", "dropped_instants", "rows", "columns")
+HOTA_COUNTERS = ("tp", "fn", "fp", "loc_q")             # int64 [B, 19] each
+HOTA_SUMS = ("ass", "re", "pr")                         # fp64 [B, 19] each
+
+
+def _hota_options(hota, identity_options, who):
+    """``hota=`` of an identity stream, checked: None (off) or ``dict(max_instants=)``; ``identity_options`` is what
+    ``_identity_options`` returned.  Refusals by name."""
+    opt = _options(hota, "hota", HOTA_DEFAULTS, who)
+    if opt is None:
+        return None
+    if identity_options is None:
+        raise ValueError(f"{who}: hota= needs identity= (its participants are the rows and columns of the identity state)")
+    if not _is_int(opt["max_instants"]) or not 1 <= int(opt["max_instants"]) <= DAGR_HOTA_MAX_INSTANTS:
+        raise ValueError(f"{who}: hota max_instants = {opt['max_instants']!r} must be an int in 1..DAGR_HOTA_MAX_INSTANTS = "
+                         f"{DAGR_HOTA_MAX_INSTANTS}")
+    return dict(max_instants=int(opt["max_instants"]))
+
+
+def hota_similarity(gt_box, gt_label, hyp_box, hyp_label):
+    """``q`` int64 ``[n, m]`` of the module docstring: ``rint(fp32(iou) * 2**20)`` with ``TrackDefinition.iou``'s operations
+    (the ground-truth box is ``a``), 0 where the labels differ and where the IoU is NaN or outside (0, 1]."""
+    f = np.float32
+    a, b = np.asarray(gt_box, f).reshape(-1, 1, 4), np.asarray(hyp_box, f).reshape(1, -1, 4)
+    same = np.asarray(gt_label, np.int32).reshape(-1, 1) == np.asarray(hyp_label, np.int32).reshape(1, -1)
+    with np.errstate(all="ignore"):
+        iw = np.minimum(a[..., 2], b[..., 2]) - np.maximum(a[..., 0], b[..., 0])
+        ih = np.minimum(a[..., 3], b[..., 3]) - np.maximum(a[..., 1], b[..., 1])
+        inter = np.where((iw > 0) & (ih > 0), iw * ih, f(0))
+        union = ((a[..., 2] - a[..., 0]) * (a[..., 3] - a[..., 1]) + (b[..., 2] - b[..., 0]) * (b[..., 3] - b[..., 1])) - inter
+        v = inter / union
+        q = np.rint(v * f(SCORE_IOU_ONE))
+    assert v.dtype == f
+    return np.where(same & (v > 0) & (v <= 1), q, f(0)).astype(np.int64)
+
+
+class HotaDefinition:
+    """HOTA's state of the module docstring in numpy: ``step(det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt, gt_match,
+    score_ids, columns, track_box=None)`` is pass 1 and the append for one step of every lane, behind the identity step on
+    the same arrays -- ``gt_match`` int64 ``[B, G]`` and ``score_ids`` int64 ``[B, max_objects]`` as ``IdentityDefinition.step``
+    takes them, ``columns`` int64 ``[B, max_tracks]`` the identity state's ``track_id`` table after its step --, and
+    ``solve()`` is pass 2 and the reduce: a dict of ``tp``, ``fn``, ``fp``, ``loc_q`` (int64 ``[B, 19]``), ``ass``, ``re``,
+    ``pr`` (fp64 ``[B, 19]``), ``mc`` (int32 ``[B, 19, max_objects, max_tracks]``) and one int64 ``[B]`` per name of
+    ``HOTA_WORDS``.  The state is ``pmc`` int64 ``[B, max_objects, max_tracks]``, ``gc`` int64 ``[B, max_objects]``, ``tc``
+    int64 ``[B, max_tracks]``, ``words`` and ``log``, per lane a list of ``dict(slot, col, gt_box, gt_label, hyp_box,
+    hyp_label)``.  ``events`` counts what has happened so far -- instants logged and dropped, lanes skipped, instants
+    without rows and without columns, pairs whose labels differ, NaN IoUs, and after a solve the matched pairs, the
+    instants where the alignment score decided (the pairing on ``q`` alone is another) and the matrices with more rows than
+    columns and the reverse -- so that a test can tell a run that exercises every rule from one that does not.  The
+    yardstick of ``dagr_stream_hota`` and ``dagr_stream_hota_solve``; nothing on the device path calls it."""
+
+    def __init__(self, batch_size, hota=True, identity=True, score=True):
+        self.B = int(batch_size)
+        self.score = _score_options(score, True, True, "HotaDefinition")
+        if self.score is None:
+            raise ValueError("HotaDefinition: score = None is a stream that does not score")
+        self.identity = _identity_options(identity, self.score, "HotaDefinition")
+        self.options = _hota_options(hota, self.identity, "HotaDefinition")
+        if self.options is None:
+            raise ValueError("HotaDefinition: hota = None is a stream without it")
+        self.reset()
+
+    def reset(self):
+        B, M, T = self.B, self.score["max_objects"], self.identity["max_tracks"]
+        self.pmc, self.gc, self.tc = np.zeros((B, M, T), np.int64), np.zeros((B, M), np.int64), np.zeros((B, T), np.int64)
+        self.words = {name: np.zeros(B, np.int64) for name in HOTA_WORDS}
+        self.log = [[] for _ in range(B)]
+        self.events = dict(logged=0, dropped=0, lanes_skipped=0, no_rows=0, no_columns=0, label_mismatch=0, nan_iou=0,
+                           matched=0, alignment_decides=0, tall=0, wide=0)
+
+    def step(self, det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt, gt_match, score_ids, columns, track_box=None):
+        det, track_id = np.asarray(det, np.float32), np.asarray(track_id, np.int64)
+        B, A = det.shape[:2]
+        gt_box, gt_label, gt_id = np.asarray(gt_box, np.float32), np.asarray(gt_label, np.int32), np.asarray(gt_id, np.int64)
+        gt_match, score_ids, columns = np.asarray(gt_match, np.int64), np.asarray(score_ids, np.int64), np.asarray(columns, np.int64)
+        G = gt_box.shape[1] if gt_box.ndim == 3 else -1
+        M, T, w, ev = self.score["max_objects"], self.identity["max_tracks"], self.words, self.events
+        if B != self.B or det.shape[2:] != (6,) or track_id.shape != (B, A):
+            raise ValueError(f"HotaDefinition: det is fp32 [{self.B}, A, 6] and track_id int64 [{self.B}, A], got "
+                             f"{det.shape} and {track_id.shape}")
+        if gt_box.shape != (B, G, 4) or gt_label.shape != (B, G) or gt_id.shape != (B, G) or gt_match.shape != (B, G) or \
+                not 0 <= G <= DAGR_SCORE_MAX_GT or score_ids.shape != (B, M) or columns.shape != (B, T):
+            raise ValueError(f"HotaDefinition: the ground truth is gt_box fp32 [{B}, G, 4], gt_label int32, gt_id and "
+                             f"gt_match int64 [{B}, G] with G <= DAGR_SCORE_MAX_GT = {DAGR_SCORE_MAX_GT}, score_ids int64 "
+                             f"[{B}, {M}] and columns int64 [{B}, {T}], got {gt_box.shape}, {gt_label.shape}, {gt_id.shape}, "
+                             f"{gt_match.shape}, {score_ids.shape}, {columns.shape}")
+        if self.score["boxes"] == "track":
+            if track_box is None:
+                raise ValueError("HotaDefinition: score boxes = 'track' needs the step's track_box")
+            boxes = np.asarray(track_box, np.float32)
+        else:
+            boxes = det[..., :4]
+        n_keep = np.broadcast_to(np.asarray(n_keep, np.int64).reshape(-1), (B,))
+        n_gt = np.full(B, G, np.int64) if n_gt is None else np.broadcast_to(np.asarray(n_gt, np.int64).reshape(-1), (B,))
+        for b in range(B):
+            if n_gt[b] < 0:                                        # no labels at this instant: not one byte changes
+                ev["lanes_skipped"] += 1
+                continue
+            if w["instants"][b] >= self.options["max_instants"]:   # a full log: nothing but the count of what is left out
+                w["dropped_instants"][b] += 1
+                ev["dropped"] += 1
+                continue
+            n, ng = min(max(int(n_keep[b]), 0), A), min(int(n_gt[b]), G)
+            with np.errstate(all="ignore"):
+                labels = det[b, :, 5].astype(np.int32)
+            hyp, col, carried = [], [], set()                      # the hypotheses with a column, in row order
+            for i in [i for i in range(n) if track_id[b, i] != 0][:DAGR_TRACK_MAX_DETS]:
+                ident = int(track_id[b, i])
+                known = np.flatnonzero(columns[b] == ident)
+                if ident not in carried and len(known):
+                    hyp.append(i)
+                    col.append(int(known[0]))
+                carried.add(ident)
+            rows, slot = [], []                                    # the ground-truth rows with a slot, in row order
+            for g in range(ng):
+                known = np.flatnonzero(score_ids[b] == gt_id[b, g]) if gt_match[b, g] != -1 and gt_id[b, g] > 0 else []
+                if len(known):
+                    rows.append(g)
+                    slot.append(int(known[0]))
+            slot, col = np.asarray(slot, np.int64), np.asarray(col, np.int64)
+            entry = dict(slot=slot, col=col, gt_box=gt_box[b, rows].copy(), gt_label=gt_label[b, rows].copy(),
+                         hyp_box=boxes[b, hyp].copy(), hyp_label=labels[hyp].copy())
+            q = hota_similarity(entry["gt_box"], entry["gt_label"], entry["hyp_box"], entry["hyp_label"])
+            ev["label_mismatch"] += int((entry["gt_label"].reshape(-1, 1) != entry["hyp_label"].reshape(1, -1)).sum())
+            ev["nan_iou"] += int(np.isnan(entry["gt_box"]).any(-1).sum() * len(hyp) + np.isnan(entry["hyp_box"]).any(-1).sum() * len(rows))
+            rs, cs = q.sum(1, keepdims=True), q.sum(0, keepdims=True)
+            den = np.where(q > 0, rs + cs - q, 1)
+            self.pmc[b][np.ix_(slot, col)] += np.where(q > 0, (q << 20) // den, 0)      # (distinct slots, distinct columns)
+            self.gc[b, slot] += 1
+            self.tc[b, col] += 1
+            self.log[b].append(entry)
+            w["instants"][b] += 1
+            w["rows"][b] += len(rows)
+            w["columns"][b] += len(hyp)
+            ev["logged"] += 1
+            ev["no_rows"] += int(len(rows) == 0)
+            ev["no_columns"] += int(len(hyp) == 0)
+
+    def weights(self, b, entry):
+        """``(q int64 [n, m], w int32 [n, m])`` of a logged instant of lane ``b`` under the tables as they are now."""
+        q = hota_similarity(entry["gt_box"], entry["gt_label"], entry["hyp_box"], entry["hyp_label"])
+        pmc = self.pmc[b][np.ix_(entry["slot"], entry["col"])]
+        both = (self.gc[b, entry["slot"]].reshape(-1, 1) + self.tc[b, entry["col"]].reshape(1, -1)) << 20
+        gq = np.where(pmc > 0, (pmc << 20) // np.where(pmc > 0, both - pmc, 1), 0)
+        return q, ((gq * q) >> 10).astype(np.int32)
+
+    def solve(self, pairings=None):
+        """Pass 2 on the log with the tables as they are now, and the reduce (the class docstring lists the result).
+        Changes no table.  ``pairings``, a list, gets per lane the list of every instant's ``row_col``."""
+        B, M, T, K, ev = self.B, self.score["max_objects"], self.identity["max_tracks"], HOTA_THRESHOLDS, self.events
+        out = {name: np.zeros((B, K), np.int64) for name in HOTA_COUNTERS}
+        out.update({name: np.zeros((B, K), np.float64) for name in HOTA_SUMS})
+        out.update({name: self.words[name].copy() for name in HOTA_WORDS})
+        out["mc"] = np.zeros((B, K, M, T), np.int32)
+        for b in range(B):
+            lane_pairs = []
+            for entry in self.log[b]:
+                q, w = self.weights(b, entry)
+                n, m = q.shape
+                _, row_col = assign_max_weight_definition(w)
+                lane_pairs.append(row_col)
+                ev["tall"] += int(n > m)
+                ev["wide"] += int(m > n)
+                if n and m and not np.array_equal(row_col, assign_max_weight_definition(q.astype(np.int32))[1]):
+                    ev["alignment_decides"] += 1
+                tps = np.zeros(K, np.int64)
+                for g in np.flatnonzero(row_col >= 0):
+                    i = int(row_col[g])
+                    ev["matched"] += 1
+                    for k in range(1, K + 1):
+                        if 20 * int(q[g, i]) >= k << 20:           # exact: alpha = k / 20, no epsilon
+                            tps[k - 1] += 1
+                            out["loc_q"][b, k - 1] += int(q[g, i])
+                            out["mc"][b, k - 1, entry["slot"][g], entry["col"][i]] += 1
+                out["tp"][b] += tps
+                out["fn"][b] += n - tps
+                out["fp"][b] += m - tps
+            if pairings is not None:
+                pairings.append(lane_pairs)
+            for k in range(K):                                     # the reduce: one division, then one multiplication
+                s, c = np.nonzero(out["mc"][b, k])
+                mc = out["mc"][b, k, s, c].astype(np.float64)
+                gc, tc = self.gc[b, s].astype(np.float64), self.tc[b, c].astype(np.float64)
+                out["ass"][b, k] = np.sum(mc * (mc / (gc + tc - mc)))
+                out["re"][b, k] = np.sum(mc * (mc / gc))
+                out["pr"][b, k] = np.sum(mc * (mc / tc))
+        return out
+
+
+def hota_summary(result):
+    """A solve's ``result`` (``tp``, ``fn``, ``fp``, ``loc_q`` int64 ``[B, 19]``, ``ass``, ``re``, ``pr`` fp64 ``[B, 19]``,
+    ``instants`` and ``dropped_instants`` int64 ``[B]``) -> ``dict(lanes=[...], total=...)``.  Each entry has per threshold
+    (``alphas``: a dict of 19-entry lists, alpha = 0.05 .. 0.95) ``deta = tp / max(1, tp + fn + fp)``, ``detre``, ``detpr``,
+    ``assa = ass / max(1, tp)``, ``assre``, ``asspr``, ``loca = loc_q / (2**20 * tp)`` (``nan`` where ``tp`` is 0) and ``hota =
+    sqrt(deta * assa)``, under the same names their means over the 19 thresholds (``loca``: over the thresholds with a TP,
+    ``nan`` when there is none), and ``tp``, ``fn``, ``fp`` (lists), ``instants``, ``dropped_instants`` (ints).  The total sums
+    the lanes' integers and the lanes' fp64 sums before it divides.  Plain host code."""
+    def one(c):
+        tp, fn, fp = (c[k].astype(np.float64) for k in ("tp", "fn", "fp"))
+        least = np.maximum(1.0, tp)
+        with np.errstate(all="ignore"):
+            a = dict(deta=tp / np.maximum(1.0, tp + fn + fp), detre=tp / np.maximum(1.0, tp + fn),
+                     detpr=tp / np.maximum(1.0, tp + fp), assa=c["ass"] / least, assre=c["re"] / least, asspr=c["pr"] / least,
+                     loca=np.where(tp > 0, c["loc_q"].astype(np.float64) / (float(SCORE_IOU_ONE) * least), np.nan))
+        a["hota"] = np.sqrt(a["deta"] * a["assa"])
+        out = {k: float(np.mean(v)) for k, v in a.items() if k != "loca"}
+        out["loca"] = float(np.mean(a["loca"][tp > 0])) if (tp > 0).any() else float("nan")
+        out["alphas"] = {k: [float(x) for x in v] for k, v in a.items()}
+        out.update({k: [int(x) for x in c[k]] for k in ("tp", "fn", "fp")})
+        out.update(instants=int(c["instants"]), dropped_instants=int(c["dropped_instants"]))
+        return out
+    names = HOTA_COUNTERS + HOTA_SUMS + ("instants", "dropped_instants")
+    B = len(np.asarray(result["tp"]))
+    per_lane = [{k: np.asarray(result[k])[b] for k in names} for b in range(B)]
+    total = {k: sum(c[k] for c in per_lane) for k in names}
+    return dict(lanes=[one(c) for c in per_lane], total=one(total))
+
+
 def frame_definition(raw, fx, fy, W, H, bgr=False):
     """The model's image of one raw sensor frame (``uint8 [H_f, W_f, 3]``), stated once: ``DSEC.preprocess_image`` plus
     ``format_data`` for a top-left crop.  Rows ``[0, fy * H)`` and columns ``[0, fx * W)`` of the frame go through
@@ -1835,6 +2094,13 @@ class EventStream:
     maximum-weight assignment on the counts (``dagr_stream_identity_solve``) and returns IDF1's integers (module docstring;
     ``identity_summary`` gives IDF1, IDP and IDR); ``identity_tables()`` reads the state back.  A stream built without it
     issues exactly the calls it issued before.
+    ``hota`` (``None``: off, ``True``: the default, or ``dict(max_instants=N)``, 1 .. ``DAGR_HOTA_MAX_INSTANTS``, default
+    1200; needs ``identity``): ``score_step`` issues ``dagr_stream_hota`` behind ``dagr_stream_identity`` -- three launches,
+    still no host wait --, which runs HOTA's pass 1 and appends the labelled instant to the lane's log on the device;
+    ``hota()`` replays the log (``dagr_stream_hota_solve``: one optimal assignment per logged instant, 19 thresholds) and
+    returns HOTA's integers and fp64 sums (module docstring; ``hota_summary`` gives HOTA, DetA, AssA and LocA);
+    ``hota_tables()`` reads the state back.  A combination whose state would exceed ``DAGR_HOTA_MAX_STATE_BYTES`` is
+    refused by name.  A stream built without it issues exactly the calls it issued before.
     ``decode`` (``None``: off, ``"evt2"`` or ``"evt3"``), ``max_decoded`` and ``t_base``: the stream takes the camera's words
     (``step_words`` / ``step_words_device``) and ``dagr_stream_decode`` turns them into events on the device, in front of
     the filter, the front and the window (module docstring; the formats as recalled from the vendor's public descriptions,
@@ -1861,7 +2127,7 @@ class EventStream:
     def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
                  max_lane_events=None, denoise_us=None, refractory_us=None, track=None, motion=None, rescue=None,
                  decode=None, max_decoded=None, t_base=None, flicker=None, trail_us=None, score=None,
-                 identity=None, assign=None):
+                 identity=None, assign=None, hota=None):
         import torch
         self.model = model
         self.track = _track_options(track, "EventStream")
@@ -1870,6 +2136,7 @@ class EventStream:
         self.assign = _assign_options(assign, self.track, "EventStream")
         self.score = _score_options(score, self.track, self.motion, "EventStream")
         self.identity_options = _identity_options(identity, self.score, "EventStream")
+        self.hota_options = _hota_options(hota, self.identity_options, "EventStream")
         time_window = int(getattr(model.args, "time_window_us", 1000000))
         self.window_us, self.max_lane_events = _window_and_cap(window_us, max_lane_events, time_window,
                                                                getattr(model.args, "batch_size", 1), "EventStream")
@@ -1921,6 +2188,8 @@ class EventStream:
             self.state.enable_score(self.score)
         if self.identity_options is not None:
             self.state.enable_identity(self.identity_options)
+        if self.hota_options is not None:
+            self.state.enable_hota(self.hota_options)
         self._zeros = None
         self.outputs = None      # the last step's decoded head outputs [B, A, 5 + classes], valid until the engine's next call
         self._frame = None
@@ -2238,7 +2507,8 @@ class EventStream:
         identities, > 0) and ``n_gt`` int32 ``[B]`` -- ``None``: every lane has all ``G`` rows; ``n_gt[b] < 0``: lane ``b``
         has no labels at this instant and is skipped --, numpy arrays (uploaded) or device tensors,
         ``G <= DAGR_SCORE_MAX_GT``.  ONE launch (``dagr_stream_score``; with ``identity=`` a second,
-        ``dagr_stream_identity``, behind it) on the step's own device arrays, no host wait.
+        ``dagr_stream_identity``, behind it; with ``hota=`` a third, ``dagr_stream_hota``) on the step's own device arrays,
+        no host wait.
         Returns ``(gt_match int64 [B, G], gt_flags int32 [B, G])``, device tensors valid until the next ``score_step``:
         per row the track id (0: a miss, -1: unscored) and the bits switch (1), fragmentation (2), kept (4).  Raises by name
         before the stream's first step, when called twice for one step, and on a stream without ``score=``."""
@@ -2304,10 +2574,36 @@ class EventStream:
         return dict(track_id=t["track_id"].copy(), track_len=t["track_len"].copy(), obj_len=t["obj_len"].copy(),
                     overlap=t["overlap"].copy(), words={name: t["words"][:, i].copy() for i, name in enumerate(IDENTITY_WORDS)})
 
+    def hota(self):
+        """HOTA's integers and sums for the labelled instants logged since construction / ``reset()`` (module docstring;
+        needs ``hota=``): ``dagr_stream_hota_solve`` -- pass 2 over the lanes' logs with the tables as they are now, then the
+        fp64 sums --, then the read-back (synchronises).  Returns a dict of ``tp``, ``fn``, ``fp``, ``loc_q`` (int64
+        ``[B, 19]``, threshold ``k`` at index ``k - 1``), ``ass``, ``re``, ``pr`` (fp64 ``[B, 19]``) and one int64 ``[B]`` per
+        name of ``HOTA_WORDS`` (``instants``, ``dropped_instants``, ``rows``, ``columns``).  The log and the tables go on: it
+        can be asked for at any step and repeated.  ``hota_summary`` takes the result."""
+        if self.hota_options is None:
+            raise RuntimeError("EventStream: hota() needs a stream built with hota= (and identity=, score=, track=)")
+        self.state.run_hota_solve()
+        t = self.state.hota_words(("words", "count", "sums"))
+        out = {name: t["count"][:, :, i].copy() for i, name in enumerate(HOTA_COUNTERS)}
+        out.update({name: t["sums"][:, :, i].copy() for i, name in enumerate(HOTA_SUMS)})
+        out.update({name: t["words"][:, i].copy() for i, name in enumerate(HOTA_WORDS)})
+        return out
+
+    def hota_tables(self):
+        """HOTA's state read back (copies; synchronises; needs ``hota=``): ``dict(pmc int64 [B, max_objects, max_tracks], gc
+        int64 [B, max_objects], tc int64 [B, max_tracks], mc int32 [B, 19, max_objects, max_tracks] -- the last ``hota()``'s --,
+        words: a dict of int64 [B] per name of HOTA_WORDS)``."""
+        if self.hota_options is None:
+            raise RuntimeError("EventStream: hota_tables() needs a stream built with hota= (and identity=, score=, track=)")
+        t = self.state.hota_words(("pmc", "gc", "tc", "mc", "words"))
+        return dict(pmc=t["pmc"], gc=t["gc"], tc=t["tc"], mc=t["mc"],
+                    words={name: t["words"][:, i].copy() for i, name in enumerate(HOTA_WORDS)})
+
     def reset(self):
         """Empty the stream: no resident events, no reference instants, zero change maps, empty stamp maps, every pixel of
         the flicker / trail filters in its initial state, zero dropped, filtered and suppressed counts, zero decoder states and counters, a clear status word, zero step counters; no tracks, ids from 1 again, zero untracked and rescued counts; the
-        scorer's object tables empty and its counters zero (and no step left to score); the identity state empty.  The
+        scorer's object tables empty and its counters zero (and no step left to score); the identity state and HOTA's state and log empty.  The
         frame in force stays, and the next step runs it through the image branch again."""
         self.state.reset()
 

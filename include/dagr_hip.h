@@ -826,6 +826,94 @@ int dagr_stream_identity(void *state, size_t bytes, int32_t B, int32_t max_objec
 int dagr_stream_identity_solve(void *state, size_t bytes, int32_t B, int32_t max_objects, int32_t max_tracks,
                                int64_t *obj_track, int64_t *result, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * Event stream HOTA state (Luiten et al., "HOTA: a higher order metric for evaluating multi-object tracking", IJCV 2021)
+ * behind the identity step, on the device
+ *   HOTA needs two passes: the matching of an instant is weighted by an alignment score of (object, track) pairs that is
+ *   known only when the whole sequence has been seen.  dagr_stream_hota runs after dagr_stream_identity on the same step's
+ *   arrays: pass 1 and the append of the instant to the lane's log.  dagr_stream_hota_solve replays the log with the final
+ *   tables: one maximum-weight assignment (dagr_assign_max_weight's method, entry for entry) per logged instant, the counts
+ *   at the 19 thresholds alpha = k / 20, and the fp64 sums behind AssA, AssRe and AssPr.  DetA, AssA, LocA and
+ *   HOTA = sqrt(DetA * AssA) are the caller's divisions.  dagr_amd/streaming.py: HotaDefinition is the same in numpy,
+ *   integer for integer.  No host synchronisation.
+ *   THIS PROJECT'S statement of HOTA departs from the usual tool: the similarities are quantised to 2^-20, the alignment
+ *   score is floored to 2^-20 and the weight to 2^-30, a pair of weight 0 is never matched, there is no epsilon at the
+ *   thresholds, the labels gate the similarity, and the instants behind max_instants are left out.  Agreement with
+ *   TrackEval is not claimed.
+ *
+ * One dagr_stream_hota call is one instant of every lane b with n_gt[b] >= 0 (n_gt[b] < 0: not one byte of the lane changes):
+ *   participants: what dagr_stream_identity used at this step.  Rows: the rows g < min(n_gt[b], G) with gt_match[b, g] != -1
+ *             and gt_id[b, g] > 0 whose gt_id is in the first n_objects slots of the scorer's id table, in row order; slot s
+ *             = that index.  Columns: the first DAGR_TRACK_MAX_DETS rows i < clamp(n_keep[b], 0, A) with track_id != 0,
+ *             without those whose id an earlier one carries, whose id is in the first n_tracks columns of the identity
+ *             state's track table (as dagr_stream_identity left it at this step), in row order; c = that column.  Box and
+ *             label as dagr_stream_score takes them;
+ *   full log: with instants == max_instants the step only adds 1 to dropped_instants;
+ *   similarity: q[g, i] = (int) rintf(iou(gt, hyp) * 1048576.0f), dagr_stream_score's IoU, and 0 when the labels differ or the
+ *             IoU is NaN (or outside (0, 1], which only a box with a negative side gives);
+ *   pass 1:   rs[g] and cs[i] the row and column sums of q; for q > 0: pmc[s, c] += (q << 20) / (rs[g] + cs[i] - q) (int64);
+ *             gc[s] += 1 and tc[c] += 1 for every participant;
+ *   append:   the participants' slot or column, box and label go to entry `instants` of the lane's log; instants += 1,
+ *             rows += the rows, columns += the columns.
+ * dagr_stream_hota_solve, per logged instant with the tables as they are:
+ *   gq[s, c] = (pmc[s, c] << 20) / (((gc[s] + tc[c]) << 20) - pmc[s, c]), 0 where pmc is 0; w[g, i] = (gq * q[g, i]) >> 10,
+ *   in 0 .. 2^30, compacted to the instant's rows and columns in log order; the pairing is dagr_assign_max_weight's.  For
+ *   k = 1 .. 19 a matched pair is a TP when 20 * q >= k << 20: tp[k] += TPs, fn[k] += rows - TPs, fp[k] += columns - TPs,
+ *   loc_q[k] += the TPs' q, mc[k][s, c] += 1 per TP.  Then per lane and k in fp64, over the pairs with mc > 0, one division
+ *   then one multiplication a term: ass[k] = sum mc * (mc / (gc[s] + tc[c] - mc)), re[k] = sum mc * (mc / gc[s]),
+ *   pr[k] = sum mc * (mc / tc[c]).  It first zeroes mc, the counters and the sums; the log, pmc, gc, tc and the words are not
+ *   changed, so a solve can be asked for at any step and repeated.  The solve is one launch of at most
+ *   DAGR_HOTA_SOLVE_WAVES one-wave workgroups that walk the instants of all lanes (integer atomics on mc and the
+ *   counters: sums of integers do not depend on the order), and one launch of 19 * B workgroups for the fp64 sums: a
+ *   thread adds its entries in index order and the workgroup's 256 partial sums are added in a fixed tree, so there is no
+ *   fp64 atomic and no sum depends on how anything was scheduled.
+ *
+ * state: dagr_stream_hota_bytes(B, max_objects, max_tracks, max_instants) bytes (0: B outside 1..65535, max_objects outside
+ *        1..DAGR_SCORE_MAX_OBJECTS, max_tracks outside 1..DAGR_ASSIGN_MAX or max_instants outside
+ *        1..DAGR_HOTA_MAX_INSTANTS), 16-byte aligned, dagr_stream_hota_reset before the first step and to empty it (all
+ *        zero).  With M = max_objects, T = max_tracks, I = max_instants and E = DAGR_HOTA_LOG_ENTRIES it holds, in this
+ *        order, EACH ARRAY STARTING AT THE NEXT MULTIPLE OF 16 BYTES behind the one before it (the first at byte 0):
+ *          pmc       int64 [B, M, T]      8 * B * M * T bytes
+ *          gc        int64 [B, M]         8 * B * M      (the logged instants at which the object of a slot was a row)
+ *          tc        int64 [B, T]         8 * B * T      (the logged instants at which the track of a column was a column)
+ *          lane      int64 [B, 4]         32 * B         instants, dropped_instants, rows, columns
+ *          count     int64 [B, 19, 4]     608 * B        tp, fn, fp, loc_q of threshold k at [b, k - 1] (the last solve's)
+ *          sums      fp64  [B, 19, 3]     456 * B        ass, re, pr of threshold k at [b, k - 1] (the last solve's)
+ *          log_box   fp32  [B, I, E, 4]   16 * B * I * E an instant's rows at entries 0 .., its columns at entries
+ *                                                        DAGR_SCORE_MAX_GT ..
+ *          log_n     int32 [B, I, 2]      8 * B * I      the instant's rows and columns
+ *          log_index int32 [B, I, E]      4 * B * I * E  the slot of a row, the column of a column
+ *          log_label int32 [B, I, E]      4 * B * I * E
+ *          mc        int32 [B, 19, M, T]  76 * B * M * T (the last solve's)
+ *        -- the sum of these, each rounded up to a multiple of 16.  dagr_amd/streaming.py refuses a stream whose state
+ *        would exceed DAGR_HOTA_MAX_STATE_BYTES.
+ * identity_state / score_state: the states of dagr_stream_identity and dagr_stream_score of the same B, max_objects and
+ * max_tracks AFTER their steps (read only: the tables of track ids and object ids, n_tracks and n_objects).  det, n_keep,
+ * A, track_id, track_box, gt_box, gt_label, gt_id, n_gt, G, gt_match: as dagr_stream_identity takes them.
+ * workspace (the solve's): dagr_stream_hota_workspace_bytes(B, max_objects, max_tracks, max_instants) bytes (0: a size out
+ * of range), 16-byte aligned: per wave of min(B * I, DAGR_HOTA_SOLVE_WAVES) the instant's weight matrix and the
+ * assignment's transposed copy, 2 * min(M, DAGR_SCORE_MAX_GT) * min(T, DAGR_TRACK_MAX_DETS) int32; it means nothing
+ * between calls.  All in device memory.
+ * DAGR_ERR_INVALID_ARG before any launch: sizes out of range, a state or workspace too small, NULL or misaligned arrays.
+ * ------------------------------------------------------------------------ */
+#define DAGR_HOTA_THRESHOLDS 19
+#define DAGR_HOTA_MAX_INSTANTS 65535
+#define DAGR_HOTA_LOG_ENTRIES 512
+#define DAGR_HOTA_SOLVE_WAVES 256
+#define DAGR_HOTA_MAX_STATE_BYTES 1073741824
+size_t dagr_stream_hota_bytes(int32_t B, int32_t max_objects, int32_t max_tracks, int32_t max_instants);
+size_t dagr_stream_hota_workspace_bytes(int32_t B, int32_t max_objects, int32_t max_tracks, int32_t max_instants);
+int dagr_stream_hota_reset(void *state, size_t bytes, int32_t B, int32_t max_objects, int32_t max_tracks,
+                           int32_t max_instants, void *stream);
+int dagr_stream_hota(void *state, size_t bytes, int32_t B, int32_t max_objects, int32_t max_tracks, int32_t max_instants,
+                     const void *identity_state, size_t identity_bytes, const void *score_state, size_t score_bytes,
+                     const float *det, const int32_t *n_keep, int32_t A, const int64_t *track_id,
+                     const float *track_box /* [B, A, 4] or NULL: det's boxes */,
+                     const float *gt_box, const int32_t *gt_label, const int64_t *gt_id, const int32_t *n_gt, int32_t G,
+                     const int64_t *gt_match, void *stream);
+int dagr_stream_hota_solve(void *state, size_t bytes, int32_t B, int32_t max_objects, int32_t max_tracks,
+                           int32_t max_instants, void *workspace, size_t workspace_bytes, void *stream);
+
 /* The neighbour search alone, again, on the pixel index the last dagr_graph_build_window left in `workspace` (same N):
  * rewrites nbr_src / nbr_code / deg and the edge count.  For measurement (bench.py times the search kernels on their own
  * stream with HIP events); a product caller has no use for it. */

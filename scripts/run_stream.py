@@ -73,6 +73,13 @@ IDR (Ristani et al., 2016), printed beside the MOTA summary; agreement with anot
 ``--track_identity_max_tracks N`` (needs ``--track_identity``) sizes the table of track ids (default 256, at most 1024): a
 track id that finds it full can only count as identity false positives.  The detections written do not change.
 
+``--track_hota`` (implies ``--track_score`` and ``--track_identity``): every scored step is also appended to a log of the
+labelled instants on the device (``EventStream(hota=)``), and at the end the log is replayed -- one optimal assignment per
+instant, 19 localisation thresholds -- for HOTA, DetA, AssA and LocA (Luiten et al., 2021; this project's integer
+statement of it, agreement with TrackEval is not claimed), printed beside MOTA and IDF1.  ``--track_hota_max_instants N``
+(needs ``--track_hota``) sizes the log (default 1200, at most 65535); the instants behind it are left out and counted.
+The detections written do not change.
+
 ``--decode evt2|evt3``: the step's events are encoded as camera words (``dagr.data.evt.encode_events``, an encoder for
 synthetic sources, not a model of any camera) and pushed through ``step_words``; the stream decodes them on the device
 (``dagr.streaming``: ``EventStream(decode=)``) in front of the filter, the front and the window.  ``--max_decoded N`` sizes
@@ -87,7 +94,7 @@ import torch
 import _common as C
 from dagr.data.evt import encode_events
 from dagr.streaming import (EventStream, _assign_options, _flicker_options, _identity_options, _motion_options, _rescue_options,
-                            _score_options, _track_options, identity_summary, score_summary)
+                            _hota_options, _score_options, _track_options, hota_summary, identity_summary, score_summary)
 from dagr.utils.buffers import DETECTION_DTYPE, detections_to_records
 from dagr.utils.logging import set_up_logging_directory
 from dagr.utils import synthetic as syn
@@ -145,6 +152,10 @@ def stream_options(p):
                    "pairing of object identities with track ids, on the device")
     g.add_argument("--track_identity_max_tracks", type=int, default=None, help="with --track_identity: the size of the table "
                    "of track ids, 1..1024 (default 256)")
+    g.add_argument("--track_hota", action="store_true", help="HOTA / DetA / AssA / LocA from a log of the labelled instants "
+                   "kept and replayed on the device; implies --track_score and --track_identity")
+    g.add_argument("--track_hota_max_instants", type=int, default=None, help="with --track_hota: the labelled instants the "
+                   "log holds, 1..65535 (default 1200); those behind it are left out and counted")
     g.add_argument("--raw_frames", action="store_true", help="the source's frames are sensor-size BGR uint8 frames: prepare "
                    "them on the device (crop, shrink by the --downsample factor, / 255)")
 
@@ -254,6 +265,22 @@ def identity_options(a):
         raise SystemExit("run_stream.py: --track_identity needs --track_score")
     try:
         _identity_options(given, True, "run_stream.py")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    return given
+
+
+def hota_options(a):
+    """``hota=`` of the stream the flags describe: None without ``--track_hota``, else the options that were given.
+    ``--track_hota`` implies ``--track_score`` and ``--track_identity``: it sets both, so it comes in front of their checks."""
+    given = {} if getattr(a, "track_hota_max_instants", None) is None else dict(max_instants=a.track_hota_max_instants)
+    if not getattr(a, "track_hota", False):
+        if given:
+            raise SystemExit("run_stream.py: --track_hota_max_instants needs --track_hota")
+        return None
+    a.track_score = a.track_identity = True
+    try:
+        _hota_options(given, True, "run_stream.py")
     except ValueError as e:
         raise SystemExit(str(e)) from None
     return given
@@ -369,13 +396,14 @@ def play(a, model, source, dev):
         raw_size = (int(w_f), int(h_f))
     cap = getattr(a, "max_lane_events", None)
     decode = getattr(a, "decode", None)
+    hota = hota_options(a)                 # (first: it implies the two flags behind it)
     stream = EventStream(model, window_us=a.window_us or None, downsample=a.downsample, sensor_size=sensor_size(a),
                          frame_size=raw_size, frame_bgr=True, max_lane_events=cap,
                          denoise_us=getattr(a, "denoise_us", None), refractory_us=getattr(a, "refractory_us", None),
                          flicker=flicker_options(a), trail_us=getattr(a, "trail_us", None),
                          track=track_options(a), motion=motion_options(a), rescue=rescue_options(a), assign=assign_option(a),
                          score=score_options(a),
-                         identity=identity_options(a),
+                         identity=identity_options(a), hota=hota,
                          decode=decode, max_decoded=getattr(a, "max_decoded", None),
                          t_base=int(source.t_range()[0]) if decode else None)      # (the words' times start at the sequence's)
     t0, t1 = source.t_range()
@@ -425,6 +453,7 @@ def play(a, model, source, dev):
         counters = stream.track_score()
         a.stream_score = dict(score_summary(counters, stream.scored_objects())["total"], steps=int(counters["steps"].sum()))
     a.stream_identity = identity_summary(stream.identity())["total"] if stream.identity_options is not None else None
+    a.stream_hota = hota_summary(stream.hota())["total"] if stream.hota_options is not None else None
     return out
 
 
@@ -451,9 +480,10 @@ def main(argv=None, model_factory=None, source=None):
     moving = motion_options(a) is not None
     rescue_options(a)                      # (refusals in front of the model)
     assign_option(a)
+    hota_options(a)                        # (in front of the two it implies)
     score_options(a)
     identity_options(a)
-    a.batch_size = 1                       # one sequence: one lane
+    a.batch_size = 1                      # one sequence: one lane
     world, rank, dev = C.distributed()
     torch.manual_seed(42)
     np.random.seed(42)
@@ -522,6 +552,10 @@ def main(argv=None, model_factory=None, source=None):
             c = a.stream_identity
             tracked += (f"; IDF1 {c['idf1']:.3f}, IDP {c['idp']:.3f}, IDR {c['idr']:.3f} (IDTP {c['idtp']} of {c['gt_frames']} "
                         f"labelled and {c['hyp_frames']} tracked frames, {c['objects']} objects, {c['tracks']} tracks)")
+        if getattr(a, "stream_hota", None) is not None:
+            c = a.stream_hota
+            tracked += (f"; HOTA {c['hota']:.3f}, DetA {c['deta']:.3f}, AssA {c['assa']:.3f}, LocA {c['loca']:.3f} "
+                        f"({c['instants']} logged instants, {c['dropped_instants']} left out)")
         print(f"{len(steps)} steps of {a.step_us} us on {window} in {seconds:.2f} s "
               f"({1e3 * seconds / max(1, len(steps)):.2f} ms per step; {a.stream_steps[0]} with the full window, "
               f"{a.stream_steps[1]} on held image maps) -> {path}: {len(rec)} detections{tracked}")
