@@ -5,12 +5,11 @@
 // is the same in numpy, integer for integer; include/dagr_hip.h states the rule and the state's layout.
 //
 // The step: one workgroup of ONE wave per lane, as the scorer and the identity step have it; the lane's wave owns the
-// lane's state, so there is no atomic.  The hypotheses are compacted by ballot in row order into LDS exactly as there, a
-// thread owns the hypotheses `lane`, `lane + 64`, ... (4) and the ground-truth rows `lane`, `lane + 64`, ... (4) in
-// registers; duplicates, columns (against the identity state's track table) and slots (against the scorer's id table) are
-// found by the same broadcast scans, read only.  The participants get their place in the log by ballot + popcount.  The
-// similarities are computed twice, once for the row sums (a shuffle reduction a row, kept in LDS) and the column sums (in
-// registers), once for pmc: a hypothesis owns its column and a row its slot, so every word of pmc has one writer per row.
+// lane's state, so there is no atomic.  Hypotheses, duplicates, columns (against the identity state's track table) and
+// slots (against the scorer's id table) are stream_eval.hpp's stages, read only here, as are the layouts of those two
+// states.  Its own: the participants get their place in the log by ballot + popcount, and the similarities are computed
+// twice, once for the row sums (a shuffle reduction a row, kept in LDS) and the column sums (in registers), once for pmc:
+// a hypothesis owns its column and a row its slot, so every word of pmc has one writer per row.
 //
 // The solve: a bounded grid of one-wave workgroups walks the logged instants of all lanes.  For an instant the wave stages
 // the rows in LDS, keeps the columns in registers, writes the compacted weight matrix to its own part of the workspace,
@@ -23,24 +22,16 @@
 #include <algorithm>
 
 #include "assign.hpp"
+#include "stream_eval.hpp"
 
 namespace dagr {
 namespace {
 
-constexpr int kMaxObjects = DAGR_SCORE_MAX_OBJECTS;
-constexpr int kMaxGt = DAGR_SCORE_MAX_GT;
-constexpr int kMaxHyp = DAGR_TRACK_MAX_DETS;
-constexpr int kGtRegs = kMaxGt / kWave;
-constexpr int kHypRegs = kMaxHyp / kWave;
 constexpr int kK = DAGR_HOTA_THRESHOLDS;
 constexpr int kEntries = DAGR_HOTA_LOG_ENTRIES;     // of an instant: the rows at 0 .., the columns at kMaxGt ..
 constexpr int kSolveWaves = DAGR_HOTA_SOLVE_WAVES;
 constexpr int kLaneWords = 4;                       // int64 words of a lane
-constexpr int kIdentityLaneWords = 8;               // the identity state's, of which word 0 is its n_tracks
-constexpr int kScoreLaneWords = 16;                 // the scorer's, of which word 0 is its n_objects
 constexpr int kReduceBlock = 256;
-constexpr float kIouOne = 1048576.0f;               // a similarity in units of 2^-20
-static_assert(kMaxGt % kWave == 0 && kMaxHyp % kWave == 0, "whole registers");
 static_assert(kMaxObjects <= kAssignMax, "one staging table for the track ids and the object ids");
 static_assert(kEntries == kMaxGt + kMaxHyp, "an instant's rows and columns");
 static_assert(kMaxGt <= kAssignMax && kMaxHyp <= kAssignMax, "an instant fits assign_wave");
@@ -85,27 +76,12 @@ int solve_waves(int B, int I) { return (int)std::min((int64_t)B * I, (int64_t)kS
 size_t wave_words(int M, int T) { return 2 * (size_t)std::min(M, kMaxGt) * std::min(T, kMaxHyp); }
 size_t hota_workspace_bytes(int B, int M, int T, int I) { return align_up(4 * (size_t)solve_waves(B, I) * wave_words(M, T), 16); }
 
-// numpy.minimum / numpy.maximum: a NaN operand comes back
-__device__ __forceinline__ float np_min(float a, float b) { return (a < b || a != a) ? a : b; }
-__device__ __forceinline__ float np_max(float a, float b) { return (a > b || a != a) ? a : b; }
-
-// TrackDefinition.iou, operation by operation: a is the ground-truth box, b the hypothesis
-__device__ __forceinline__ float iou_xyxy(const float4 &a, const float4 &b) {
-    const float iw = np_min(a.z, b.z) - np_max(a.x, b.x);
-    const float ih = np_min(a.w, b.w) - np_max(a.y, b.y);
-    const float inter = (iw > 0.0f && ih > 0.0f) ? iw * ih : 0.0f;
-    const float uni = ((a.z - a.x) * (a.w - a.y) + (b.z - b.x) * (b.w - b.y)) - inter;
-    return inter / uni;
-}
-
 // the similarity in units of 2^-20: 0 for a NaN IoU and for one outside (0, 1]
 __device__ __forceinline__ int32_t similarity(const float4 &a, const float4 &b) {
     const float v = iou_xyxy(a, b);
     return (v > 0.0f && v <= 1.0f) ? (int32_t)rintf(v * kIouOne) : 0;
 }
 
-__device__ __forceinline__ int lanes_below(uint64_t mask, int lane) { return __popcll(mask & ((1ull << lane) - 1ull)); }
-__device__ __forceinline__ int first_lane(uint64_t mask) { return __ffsll((unsigned long long)mask) - 1; }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 __global__ __launch_bounds__(kWave) void k_stream_hota(int M, int T, int I, const int64_t *__restrict__ score_id,
@@ -118,7 +94,7 @@ __global__ __launch_bounds__(kWave) void k_stream_hota(int M, int T, int I, cons
                                                        const float4 *__restrict__ gt_box, const int32_t *__restrict__ gt_label,
                                                        const int64_t *__restrict__ gt_id, const int32_t *__restrict__ n_gt,
                                                        int G, const int64_t *__restrict__ gt_match, Hota st) {
-    __shared__ float4 s_hbox[kMaxHyp];          // the hypotheses, in row order (as the scorer stages them)
+    __shared__ float4 s_hbox[kMaxHyp];          // the hypotheses, in row order (stage_hypotheses)
     __shared__ int64_t s_hid[kMaxHyp];
     __shared__ int32_t s_hlabel[kMaxHyp];
     __shared__ float4 s_gbox[kMaxGt];           // the ground-truth rows
@@ -138,38 +114,13 @@ __global__ __launch_bounds__(kWave) void k_stream_hota(int M, int T, int I, cons
     }
     const int ng = min(labelled, G);
     const int n = min(max(n_keep[b], 0), A);
-    const int n_tr = (int)min(max(ident_words[(int64_t)b * kIdentityLaneWords], (int64_t)0), (int64_t)T);
-    const int n_obj = (int)min(max(score_words[(int64_t)b * kScoreLaneWords], (int64_t)0), (int64_t)M);
+    const int n_tr = table_fill(ident_words[(int64_t)b * identity_word::kCount + identity_word::kNTracks], T);
+    const int n_obj = table_fill(score_words[(int64_t)b * score_word::kCount + score_word::kNObjects], M);
 
-    // ---- the hypotheses: the rows with an id, 64 at a time; the first kMaxHyp go to the LDS in row order
-    int n_hyp = 0;
-    for (int first = 0; first < n; first += kWave) {
-        const int i = first + lane;
-        const int64_t id = i < n ? track_id[(int64_t)b * A + i] : 0;
-        const uint64_t mask = __ballot(id != 0);
-        const int rank = n_hyp + lanes_below(mask, lane);
-        n_hyp += __popcll(mask);
-        if (id != 0 && rank < kMaxHyp) {
-            const float *p = det + ((int64_t)b * A + i) * 6;
-            s_hbox[rank] = track_box ? track_box[(int64_t)b * A + i] : make_float4(p[0], p[1], p[2], p[3]);
-            s_hid[rank] = id;
-            s_hlabel[rank] = (int32_t)p[5];
-        }
-    }
-    const int P = min(n_hyp, kMaxHyp);
+    const int P = min(stage_hypotheses(b, lane, n, A, det, track_id, track_box, s_hbox, s_hid, s_hlabel), kMaxHyp);
     int64_t gid[kGtRegs];
     bool scored[kGtRegs];
-#pragma unroll
-    for (int j = 0; j < kGtRegs; j++) {
-        const int g = j * kWave + lane;
-        gid[j] = 0, scored[j] = false;
-        if (g < ng) {
-            s_gbox[g] = gt_box[(int64_t)b * G + g];
-            s_glabel[g] = gt_label[(int64_t)b * G + g];
-            gid[j] = gt_id[(int64_t)b * G + g];
-            scored[j] = gt_match[(int64_t)b * G + g] != -1 && gid[j] > 0;
-        }
-    }
+    stage_scored_rows(b, lane, ng, G, gt_box, gt_label, gt_id, gt_match, s_gbox, s_glabel, gid, scored);
     for (int k = lane; k < n_tr; k += kWave) s_table[k] = ident_track[(int64_t)b * T + k];
     __syncthreads();
 
@@ -178,26 +129,10 @@ __global__ __launch_bounds__(kWave) void k_stream_hota(int M, int T, int I, cons
     int64_t hid[kHypRegs];                      // 0: no hypothesis in this register
     int col[kHypRegs];
     bool dup[kHypRegs];
-#pragma unroll
-    for (int k = 0; k < kHypRegs; k++) {
-        const int p = k * kWave + lane;
-        hbox[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f), hlabel[k] = 0, hid[k] = 0, col[k] = -1, dup[k] = false;
-        if (p < P) hbox[k] = s_hbox[p], hlabel[k] = s_hlabel[p], hid[k] = s_hid[p];
-    }
-    // ---- duplicates: a hypothesis whose id an earlier one carries takes no part
-    for (int q = 0; q < P; q++) {
-        const int64_t v = s_hid[q];
-#pragma unroll
-        for (int k = 0; k < kHypRegs; k++)
-            if (q < k * kWave + lane && v == hid[k]) dup[k] = true;
-    }
+    load_hypotheses(lane, P, s_hbox, s_hid, s_hlabel, hbox, hlabel, hid);
+    mark_duplicates(lane, P, s_hid, hid, dup);
     // ---- columns: by id in the identity state's table, which its step has just brought up to date; without one: no part
-    for (int c = 0; c < n_tr; c++) {
-        const int64_t v = s_table[c];
-#pragma unroll
-        for (int k = 0; k < kHypRegs; k++)
-            if (v == hid[k]) col[k] = c;
-    }
+    find_columns(n_tr, s_table, hid, col);
     int64_t *lane_tc = st.tc + (int64_t)b * T;
     const int64_t entry = ((int64_t)b * I + at) * kEntries;
     int n_cols = 0;
@@ -220,14 +155,7 @@ __global__ __launch_bounds__(kWave) void k_stream_hota(int M, int T, int I, cons
     for (int k = lane; k < n_obj; k += kWave) s_table[k] = score_id[(int64_t)b * M + k];
     __syncthreads();
     int slot[kGtRegs];
-#pragma unroll
-    for (int j = 0; j < kGtRegs; j++) slot[j] = -1;
-    for (int k = 0; k < n_obj; k++) {
-        const int64_t v = s_table[k];
-#pragma unroll
-        for (int j = 0; j < kGtRegs; j++)
-            if (scored[j] && slot[j] < 0 && v == gid[j]) slot[j] = k;
-    }
+    find_slots(n_obj, s_table, gid, scored, slot);
     uint64_t counted[kGtRegs];
     int n_rows = 0;
     int64_t *lane_gc = st.gc + (int64_t)b * M;
@@ -486,14 +414,12 @@ extern "C" int dagr_stream_hota(void *state, size_t bytes, int32_t B, int32_t ma
                    "stream hota: identity_state smaller than dagr_stream_identity_bytes");
     DAGR_CHECK_ARG(score_bytes >= dagr_stream_score_bytes(B, max_objects),
                    "stream hota: score_state smaller than dagr_stream_score_bytes");
-    // the scorer's layout (include/dagr_hip.h): id [B, max_objects] at byte 0, the lanes' 16 words at byte 64 * B * max_objects;
-    // the identity state's: track_id [B, max_tracks] at byte 0, the lanes' 8 words at byte 16 * B * max_tracks + 8 * B * max_objects
-    const int64_t *score_id = (const int64_t *)score_state;
-    const int64_t *score_words = score_id + 8 * (size_t)B * max_objects;
-    const int64_t *ident_track = (const int64_t *)identity_state;
-    const int64_t *ident_words = ident_track + 2 * (size_t)B * max_tracks + (size_t)B * max_objects;
-    k_stream_hota<<<(unsigned)B, kWave, 0, (hipStream_t)stream>>>(max_objects, max_tracks, max_instants, score_id, score_words,
-                                                                  ident_track, ident_words, det, n_keep, A, track_id,
+    Score score;                                // (both read only: the kernel takes their tables and words as const)
+    Identity ident;
+    carve_score(B, max_objects, (char *)score_state, &score);
+    carve_identity(B, max_objects, max_tracks, (char *)identity_state, &ident);
+    k_stream_hota<<<(unsigned)B, kWave, 0, (hipStream_t)stream>>>(max_objects, max_tracks, max_instants, score.id, score.lane,
+                                                                  ident.track_id, ident.lane, det, n_keep, A, track_id,
                                                                   (const float4 *)track_box, (const float4 *)gt_box, gt_label,
                                                                   gt_id, n_gt, G, gt_match, st);
     DAGR_CHECK_LAUNCH();

@@ -5,71 +5,21 @@
 // states the rule and the state's layout.
 //
 // One workgroup of ONE wave per lane, as the scorer has it; the lane's wave owns the lane's state, so there is no atomic.
-// The step: the hypotheses are compacted by ballot in row order into LDS exactly as the scorer compacts them, a thread owns
-// the hypotheses `lane`, `lane + 64`, ... (4) and the ground-truth rows `lane`, `lane + 64`, ... (4) in registers.
-//   duplicates: every thread scans the staged ids once for its hypotheses (one broadcast LDS read per id, four compares);
-//   columns:    the same scan over the lane's track table, staged in LDS; new ids take the columns behind n_tracks in row
-//               order, counted by ballot + popcount;
-//   rows:       the same scan over the scorer's id table, staged in the same LDS words;
-//   pairs:      a serial walk over the counted rows (a ballot mask), the work of a row parallel over the hypotheses: a
-//               hypothesis owns its column and a row its slot, so every word of `overlap` has one writer per row.
+// The step: hypotheses, duplicates, the lookup of columns and slots and the rows that count are stream_eval.hpp's stages,
+// as are both states' layouts.  Its own:
+//   columns: new ids take the columns behind n_tracks in row order, counted by ballot + popcount; a full table lists no more;
+//   pairs:   a serial walk over the counted rows (a ballot mask), the work of a row parallel over the hypotheses: a
+//            hypothesis owns its column and a row its slot, so every word of `overlap` has one writer per row.
 // The solve is assign.hpp's routine on the lane's `overlap`.  Every float decision repeats the numpy definition operation
 // by operation; this library is built with -ffp-contract=off, and the fp32 division is correctly rounded.
 #include "assign.hpp"
+#include "stream_eval.hpp"
 
 namespace dagr {
 namespace {
 
-constexpr int kMaxObjects = DAGR_SCORE_MAX_OBJECTS;
-constexpr int kMaxGt = DAGR_SCORE_MAX_GT;
-constexpr int kMaxHyp = DAGR_TRACK_MAX_DETS;
-constexpr int kGtRegs = kMaxGt / kWave;
-constexpr int kHypRegs = kMaxHyp / kWave;
-constexpr int kLaneWords = 8;                       // int64 words of a lane
-constexpr int kScoreLaneWords = 16;                 // the scorer's, of which word 0 is its n_objects
-static_assert(kMaxGt % kWave == 0 && kMaxHyp % kWave == 0, "whole registers");
+using namespace identity_word;
 static_assert(kMaxObjects <= kAssignMax, "one staging table for the track ids and the object ids");
-
-// the lane's words, in the order include/dagr_hip.h documents
-enum { kNTracks = 0, kNObjects, kGtFrames, kHypFrames, kDupHyp, kUnlistedHyp, kPairs, kSteps };
-
-struct Identity {
-    int64_t *track_id, *track_len;      // [B, T]
-    int64_t *obj_len;                   // [B, M]
-    int64_t *lane;                      // [B, kLaneWords]
-    int32_t *overlap;                   // [B, M, T]
-    int32_t *obj_col;                   // [B, M]
-};
-
-size_t carve_identity(int B, int M, int T, char *base, Identity *out) {
-    const size_t nt = (size_t)B * T, nm = (size_t)B * M;
-    if (out) {
-        int64_t *p = (int64_t *)base;
-        int32_t *q = (int32_t *)(p + 2 * nt + nm + (size_t)kLaneWords * B);
-        *out = Identity{p, p + nt, p + 2 * nt, p + 2 * nt + nm, q, q + nm * T};
-    }
-    return align_up(16 * nt + 8 * nm + 8 * (size_t)kLaneWords * B + 4 * nm * T + 4 * nm, 16);
-}
-
-bool identity_sizes_ok(int32_t B, int32_t M, int32_t T) {
-    return B >= 1 && B <= 65535 && M >= 1 && M <= kMaxObjects && T >= 1 && T <= kAssignMax;
-}
-
-// numpy.minimum / numpy.maximum: a NaN operand comes back
-__device__ __forceinline__ float np_min(float a, float b) { return (a < b || a != a) ? a : b; }
-__device__ __forceinline__ float np_max(float a, float b) { return (a > b || a != a) ? a : b; }
-
-// TrackDefinition.iou, operation by operation: a is the ground-truth box, b the hypothesis
-__device__ __forceinline__ float iou_xyxy(const float4 &a, const float4 &b) {
-    const float iw = np_min(a.z, b.z) - np_max(a.x, b.x);
-    const float ih = np_min(a.w, b.w) - np_max(a.y, b.y);
-    const float inter = (iw > 0.0f && ih > 0.0f) ? iw * ih : 0.0f;
-    const float uni = ((a.z - a.x) * (a.w - a.y) + (b.z - b.x) * (b.w - b.y)) - inter;
-    return inter / uni;
-}
-
-__device__ __forceinline__ int lanes_below(uint64_t mask, int lane) { return __popcll(mask & ((1ull << lane) - 1ull)); }
-__device__ __forceinline__ int first_lane(uint64_t mask) { return __ffsll((unsigned long long)mask) - 1; }
 
 __global__ __launch_bounds__(kWave) void k_stream_identity(int M, int T, float thr, const int64_t *__restrict__ score_id,
                                                            const int64_t *__restrict__ score_words,
@@ -79,7 +29,7 @@ __global__ __launch_bounds__(kWave) void k_stream_identity(int M, int T, float t
                                                            const float4 *__restrict__ gt_box, const int32_t *__restrict__ gt_label,
                                                            const int64_t *__restrict__ gt_id, const int32_t *__restrict__ n_gt,
                                                            int G, const int64_t *__restrict__ gt_match, Identity st) {
-    __shared__ float4 s_hbox[kMaxHyp];          // the hypotheses, in row order (as the scorer stages them)
+    __shared__ float4 s_hbox[kMaxHyp];          // the hypotheses, in row order (stage_hypotheses)
     __shared__ int64_t s_hid[kMaxHyp];
     __shared__ int32_t s_hlabel[kMaxHyp];
     __shared__ float4 s_gbox[kMaxGt];           // the ground-truth rows
@@ -92,39 +42,14 @@ __global__ __launch_bounds__(kWave) void k_stream_identity(int M, int T, float t
     if (labelled < 0) return;                   // no labels at this instant: not one byte of the lane changes
     const int ng = min(labelled, G);
     const int n = min(max(n_keep[b], 0), A);
-    int64_t *words = st.lane + (int64_t)b * kLaneWords;
-    const int n_tr = (int)min(max(words[kNTracks], (int64_t)0), (int64_t)T);      // (a state that was never reset stays inside)
-    const int n_obj = (int)min(max(score_words[(int64_t)b * kScoreLaneWords], (int64_t)0), (int64_t)M);
+    int64_t *words = st.lane + (int64_t)b * identity_word::kCount;
+    const int n_tr = table_fill(words[kNTracks], T);
+    const int n_obj = table_fill(score_words[(int64_t)b * score_word::kCount + score_word::kNObjects], M);
 
-    // ---- the hypotheses: the rows with an id, 64 at a time; the first kMaxHyp go to the LDS in row order
-    int n_hyp = 0;
-    for (int first = 0; first < n; first += kWave) {
-        const int i = first + lane;
-        const int64_t id = i < n ? track_id[(int64_t)b * A + i] : 0;
-        const uint64_t mask = __ballot(id != 0);
-        const int rank = n_hyp + lanes_below(mask, lane);
-        n_hyp += __popcll(mask);
-        if (id != 0 && rank < kMaxHyp) {
-            const float *p = det + ((int64_t)b * A + i) * 6;
-            s_hbox[rank] = track_box ? track_box[(int64_t)b * A + i] : make_float4(p[0], p[1], p[2], p[3]);
-            s_hid[rank] = id;
-            s_hlabel[rank] = (int32_t)p[5];
-        }
-    }
-    const int P = min(n_hyp, kMaxHyp);
+    const int P = min(stage_hypotheses(b, lane, n, A, det, track_id, track_box, s_hbox, s_hid, s_hlabel), kMaxHyp);
     int64_t gid[kGtRegs];
     bool scored[kGtRegs];
-#pragma unroll
-    for (int j = 0; j < kGtRegs; j++) {
-        const int g = j * kWave + lane;
-        gid[j] = 0, scored[j] = false;
-        if (g < ng) {
-            s_gbox[g] = gt_box[(int64_t)b * G + g];
-            s_glabel[g] = gt_label[(int64_t)b * G + g];
-            gid[j] = gt_id[(int64_t)b * G + g];
-            scored[j] = gt_match[(int64_t)b * G + g] != -1 && gid[j] > 0;
-        }
-    }
+    stage_scored_rows(b, lane, ng, G, gt_box, gt_label, gt_id, gt_match, s_gbox, s_glabel, gid, scored);
     for (int k = lane; k < n_tr; k += kWave) s_table[k] = st.track_id[(int64_t)b * T + k];
     __syncthreads();
 
@@ -133,27 +58,11 @@ __global__ __launch_bounds__(kWave) void k_stream_identity(int M, int T, float t
     int64_t hid[kHypRegs];                      // 0: no hypothesis in this register
     int col[kHypRegs];
     bool dup[kHypRegs];
-#pragma unroll
-    for (int k = 0; k < kHypRegs; k++) {
-        const int p = k * kWave + lane;
-        hbox[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f), hlabel[k] = 0, hid[k] = 0, col[k] = -1, dup[k] = false;
-        if (p < P) hbox[k] = s_hbox[p], hlabel[k] = s_hlabel[p], hid[k] = s_hid[p];
-    }
+    load_hypotheses(lane, P, s_hbox, s_hid, s_hlabel, hbox, hlabel, hid);
+    mark_duplicates(lane, P, s_hid, hid, dup);
+    find_columns(n_tr, s_table, hid, col);
 
-    // ---- duplicates: a hypothesis whose id an earlier one carries takes no part (the first carrier always does)
-    for (int q = 0; q < P; q++) {
-        const int64_t v = s_hid[q];
-#pragma unroll
-        for (int k = 0; k < kHypRegs; k++)
-            if (q < k * kWave + lane && v == hid[k]) dup[k] = true;
-    }
     // ---- columns: by id, or the columns behind n_tracks in row order; a full table lists no more
-    for (int c = 0; c < n_tr; c++) {
-        const int64_t v = s_table[c];
-#pragma unroll
-        for (int k = 0; k < kHypRegs; k++)
-            if (v == hid[k]) col[k] = c;
-    }
     int n_new = 0, n_dup = 0, n_unlisted = 0;
 #pragma unroll
     for (int k = 0; k < kHypRegs; k++) {
@@ -182,14 +91,7 @@ __global__ __launch_bounds__(kWave) void k_stream_identity(int M, int T, float t
     for (int k = lane; k < n_obj; k += kWave) s_table[k] = score_id[(int64_t)b * M + k];
     __syncthreads();
     int slot[kGtRegs];
-#pragma unroll
-    for (int j = 0; j < kGtRegs; j++) slot[j] = -1;
-    for (int k = 0; k < n_obj; k++) {
-        const int64_t v = s_table[k];
-#pragma unroll
-        for (int j = 0; j < kGtRegs; j++)
-            if (scored[j] && slot[j] < 0 && v == gid[j]) slot[j] = k;
-    }
+    find_slots(n_obj, s_table, gid, scored, slot);
     uint64_t counted[kGtRegs];
     int n_rows = 0, top = 0;
 #pragma unroll
@@ -245,9 +147,9 @@ __global__ __launch_bounds__(kWave) void k_stream_identity_solve(int M, int T, I
                                                                  int64_t *__restrict__ result, int32_t *__restrict__ workspace) {
     __shared__ AssignLds s;
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int64_t *words = st.lane + (int64_t)b * kLaneWords;
-    const int n_tr = (int)min(max(words[kNTracks], (int64_t)0), (int64_t)T);
-    const int n_obj = (int)min(max(words[kNObjects], (int64_t)0), (int64_t)M);
+    const int64_t *words = st.lane + (int64_t)b * identity_word::kCount;
+    const int n_tr = table_fill(words[kNTracks], T);
+    const int n_obj = table_fill(words[kNObjects], M);
     int32_t *pairs = st.obj_col + (int64_t)b * M;
     for (int r = n_obj + lane; r < M; r += kWave) pairs[r] = -1;
     const int64_t idtp = assign_wave(st.overlap + (int64_t)b * M * T, T, n_obj, n_tr, workspace + (int64_t)b * M * T, pairs, s);
@@ -314,10 +216,9 @@ extern "C" int dagr_stream_identity(void *state, size_t bytes, int32_t B, int32_
                    "stream identity: state smaller than dagr_stream_identity_bytes");
     DAGR_CHECK_ARG(score_bytes >= dagr_stream_score_bytes(B, max_objects),
                    "stream identity: score_state smaller than dagr_stream_score_bytes");
-    // the scorer's layout (include/dagr_hip.h): id [B, max_objects] at byte 0, the lanes' 16 words at byte 64 * B * max_objects
-    const int64_t *score_id = (const int64_t *)score_state;
-    const int64_t *score_words = score_id + 8 * (size_t)B * max_objects;
-    k_stream_identity<<<(unsigned)B, kWave, 0, (hipStream_t)stream>>>(max_objects, max_tracks, iou, score_id, score_words, det,
+    Score score;                                // (read only: the kernel takes its id table and its words as const)
+    carve_score(B, max_objects, (char *)score_state, &score);
+    k_stream_identity<<<(unsigned)B, kWave, 0, (hipStream_t)stream>>>(max_objects, max_tracks, iou, score.id, score.lane, det,
                                                                       n_keep, A, track_id, (const float4 *)track_box,
                                                                       (const float4 *)gt_box, gt_label, gt_id, n_gt, G, gt_match,
                                                                       st);

@@ -4,10 +4,11 @@
 // same in numpy, integer for integer; include/dagr_hip.h states the rule and the state's layout.
 //
 // One workgroup of ONE wave per lane, as k_stream_track has it; the lane's wave owns the lane's state, so there is no
-// atomic and no second launch.  The hypotheses (the rows with an id, compacted by ballot in row order), the ground-truth
-// rows and the ids of the lane's object table are staged in LDS, 25 KB.  A thread owns the ground-truth rows `lane`,
-// `lane + 64`, ... (kMaxGt / 64 = 4) and the hypotheses `lane`, `lane + 64`, ... (4 again), both in registers.
-//   slots: every thread scans the staged table once for its rows (one broadcast LDS read per table word, four compares);
+// atomic and no second launch.  The state's layout, the staging of the hypotheses and a thread's registers are
+// stream_eval.hpp's; the ground-truth rows and the ids of the lane's object table are staged in LDS beside them, 24 KB.
+//   slots: the scorer's own rule, for it makes the slots the identity step and HOTA look up: every thread scans the rows
+//          for an earlier carrier of its identities (those rows are unscored) and the staged table for their slots (one
+//          broadcast LDS read per word, four compares);
 //          new identities take the slots behind n_objects in row order, counted by ballot + popcount;
 //   keep:  a serial walk over the rows whose object was matched at the step before (a ballot mask, so only they cost
 //          anything): the first hypothesis with the remembered id is found by ballot, the test itself is uniform;
@@ -19,55 +20,14 @@
 // The counters are summed by ballot + popcount (iou_q by a shuffle reduction of int64) and stored once, by thread 0.
 // Every float decision repeats the numpy definition operation by operation; this library is built with -ffp-contract=off,
 // and the fp32 division is correctly rounded.
-#include "common.hpp"
+#include "stream_eval.hpp"
 
 namespace dagr {
 namespace {
 
-constexpr int kMaxObjects = DAGR_SCORE_MAX_OBJECTS;
-constexpr int kMaxGt = DAGR_SCORE_MAX_GT;
-constexpr int kMaxHyp = DAGR_TRACK_MAX_DETS;
-constexpr int kGtRegs = kMaxGt / kWave;             // ground-truth rows of one thread
-constexpr int kHypRegs = kMaxHyp / kWave;           // hypotheses of one thread
-constexpr int kLaneWords = 16;                      // int64 words of a lane behind the table
-static_assert(kMaxGt % kWave == 0 && kMaxHyp % kWave == 0, "whole registers");
+using namespace score_word;
 
-// the lane's words, in the order include/dagr_hip.h documents
-enum { kNObjects = 0, kSteps, kGt, kHyp, kMatch, kMiss, kFalsePos, kSwitch, kFrag, kKept, kIouQ, kUnscoredGt, kUnscoredHyp };
-
-// The caller-owned state: eight int64 arrays over [B, max_objects] and the lanes' words.
-struct Score {
-    int64_t *id, *last_hyp, *prev_hyp, *seen_step, *present, *tracked, *switches, *frags;
-    int64_t *lane;      // [B, kLaneWords]
-};
-
-size_t carve_score(int B, int M, char *base, Score *out) {
-    const size_t n = (size_t)B * M;
-    if (out) {
-        int64_t *p = (int64_t *)base;
-        *out = Score{p, p + n, p + 2 * n, p + 3 * n, p + 4 * n, p + 5 * n, p + 6 * n, p + 7 * n, p + 8 * n};
-    }
-    return 64 * n + 8 * (size_t)kLaneWords * B;
-}
-
-bool score_sizes_ok(int32_t B, int32_t M) { return B >= 1 && B <= 65535 && M >= 1 && M <= kMaxObjects; }
-
-// numpy.minimum / numpy.maximum: a NaN operand comes back
-__device__ __forceinline__ float np_min(float a, float b) { return (a < b || a != a) ? a : b; }
-__device__ __forceinline__ float np_max(float a, float b) { return (a > b || a != a) ? a : b; }
-
-// TrackDefinition.iou, operation by operation: a is the ground-truth box, b the hypothesis
-__device__ __forceinline__ float iou_xyxy(const float4 &a, const float4 &b) {
-    const float iw = np_min(a.z, b.z) - np_max(a.x, b.x);
-    const float ih = np_min(a.w, b.w) - np_max(a.y, b.y);
-    const float inter = (iw > 0.0f && ih > 0.0f) ? iw * ih : 0.0f;
-    const float uni = ((a.z - a.x) * (a.w - a.y) + (b.z - b.x) * (b.w - b.y)) - inter;
-    return inter / uni;
-}
-
-__device__ __forceinline__ int lanes_below(uint64_t mask, int lane) { return __popcll(mask & ((1ull << lane) - 1ull)); }
-__device__ __forceinline__ int first_lane(uint64_t mask) { return __ffsll((unsigned long long)mask) - 1; }
-__device__ __forceinline__ int32_t iou_units(float v) { return (int32_t)rintf(v * 1048576.0f); }      // exact: v <= 1
+__device__ __forceinline__ int32_t iou_units(float v) { return (int32_t)rintf(v * kIouOne); }      // exact: v <= 1
 
 __global__ __launch_bounds__(kWave) void k_stream_score(int M, float thr, const float *__restrict__ det,
                                                         const int32_t *__restrict__ n_keep, int A,
@@ -91,26 +51,12 @@ __global__ __launch_bounds__(kWave) void k_stream_score(int M, float thr, const 
     if (labelled < 0) return;                   // no labels at this instant: not one byte of the lane changes
     const int ng = min(labelled, G);
     const int n = min(max(n_keep[b], 0), A);
-    int64_t *words = st.lane + (int64_t)b * kLaneWords;
-    const int n_obj = (int)min(max(words[kNObjects], (int64_t)0), (int64_t)M);      // (a state that was never reset stays inside)
+    int64_t *words = st.lane + (int64_t)b * score_word::kCount;
+    const int n_obj = table_fill(words[kNObjects], M);
     const int64_t steps = words[kSteps];
     const int64_t base = (int64_t)b * M;
 
-    // ---- the hypotheses: the rows with an id, 64 at a time; the first kMaxHyp go to the LDS in row order
-    int n_hyp = 0;
-    for (int first = 0; first < n; first += kWave) {
-        const int i = first + lane;
-        const int64_t id = i < n ? track_id[(int64_t)b * A + i] : 0;
-        const uint64_t mask = __ballot(id != 0);
-        const int rank = n_hyp + lanes_below(mask, lane);
-        n_hyp += __popcll(mask);
-        if (id != 0 && rank < kMaxHyp) {
-            const float *p = det + ((int64_t)b * A + i) * 6;
-            s_hbox[rank] = track_box ? track_box[(int64_t)b * A + i] : make_float4(p[0], p[1], p[2], p[3]);
-            s_hid[rank] = id;
-            s_hlabel[rank] = (int32_t)p[5];
-        }
-    }
+    const int n_hyp = stage_hypotheses(b, lane, n, A, det, track_id, track_box, s_hbox, s_hid, s_hlabel);
     const int P = min(n_hyp, kMaxHyp);
     for (int g = lane; g < ng; g += kWave) {
         s_gbox[g] = gt_box[(int64_t)b * G + g];
@@ -123,12 +69,7 @@ __global__ __launch_bounds__(kWave) void k_stream_score(int M, float thr, const 
     float4 hbox[kHypRegs];
     int32_t hlabel[kHypRegs];
     int64_t hid[kHypRegs];                      // 0: no hypothesis in this register
-#pragma unroll
-    for (int k = 0; k < kHypRegs; k++) {
-        const int p = k * kWave + lane;
-        hbox[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f), hlabel[k] = 0, hid[k] = 0;
-        if (p < P) hbox[k] = s_hbox[p], hlabel[k] = s_hlabel[p], hid[k] = s_hid[p];
-    }
+    load_hypotheses(lane, P, s_hbox, s_hid, s_hlabel, hbox, hlabel, hid);
 
     // ---- slots: a row is scored unless its id is <= 0, an earlier row has it, or it is new and the table is full
     int64_t gid[kGtRegs], prev[kGtRegs];

@@ -1,9 +1,9 @@
 // stream_track.hpp -- what the stream tracker's kernels share and what has no bearing on their instruction streams: the
-// caller-owned state and how it is carved, numpy's minimum / maximum, the IoU of the definition, the rank of a thread in a
-// ballot, and the outputs only the motion model has.  stream_track.hip (the greedy entries) and stream_track_optimal.hip
+// caller-owned state and how it is carved, the box and wave helpers of stream_box.hpp, and the outputs only the motion
+// model has.  stream_track.hip (the greedy entries) and stream_track_optimal.hip
 // (dagr_stream_track_optimal) include it; include/dagr_hip.h documents the layouts.
 #pragma once
-#include "common.hpp"
+#include "stream_box.hpp"
 
 namespace dagr {
 
@@ -32,21 +32,6 @@ inline size_t carve_tracks(bool motion, int B, int M, char *base, Tracks *out) {
     if (out) *out = t;
     return after_box + 8 * n + 8 * (size_t)B;
 }
-
-// numpy.minimum / numpy.maximum: a NaN operand comes back
-__device__ __forceinline__ float np_min(float a, float b) { return (a < b || a != a) ? a : b; }
-__device__ __forceinline__ float np_max(float a, float b) { return (a > b || a != a) ? a : b; }
-
-// TrackDefinition.iou, operation by operation: a is the row, b the track
-__device__ __forceinline__ float iou_xyxy(const float4 &a, const float4 &b) {
-    const float iw = np_min(a.z, b.z) - np_max(a.x, b.x);
-    const float ih = np_min(a.w, b.w) - np_max(a.y, b.y);
-    const float inter = (iw > 0.0f && ih > 0.0f) ? iw * ih : 0.0f;
-    const float uni = ((a.z - a.x) * (a.w - a.y) + (b.z - b.x) * (b.w - b.y)) - inter;
-    return inter / uni;
-}
-
-__device__ __forceinline__ int lanes_below(uint64_t mask, int lane) { return __popcll(mask & ((1ull << lane) - 1ull)); }
 
 // what a step with the motion model leaves besides ids and hits: the filtered box and the velocity of every row, and the
 // lane's coast list.  Without the model all of it is NULL and nothing reads it.

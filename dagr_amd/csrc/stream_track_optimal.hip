@@ -24,7 +24,6 @@ constexpr int kMaxDets = DAGR_TRACK_MAX_DETS;
 constexpr int kSlots = kMaxTracks / kWave;          // slots of one thread
 constexpr int64_t kNever = INT64_MIN;
 constexpr int32_t kPair = 1 << 29;                  // an admissible pair, before its IoU: above kMaxDets quantised IoUs
-constexpr float kIouOne = 1048576.0f;               // the IoU of a pair in units of 2^-20
 static_assert(kMaxTracks % kWave == 0 && kMaxDets % kWave == 0 && kMaxDets / kWave <= 32, "one flag word per thread");
 static_assert(kMaxTracks <= kAssignMax && kMaxDets <= kAssignMax, "a round fits assign_wave");
 static_assert((int64_t)kMaxDets * (1 << 20) < kPair, "one more match outweighs every IoU");

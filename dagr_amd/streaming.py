@@ -1045,6 +1045,69 @@ def _score_options(score, track_options, motion_options, who):
     return dict(iou=float(np.float32(opt["iou"])), max_objects=int(opt["max_objects"]), boxes=opt["boxes"])
 
 
+def _labelled_step(who, batch_size, boxes, det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt, track_box, **tables):
+    """What the labelled step's definitions (``ScoreDefinition``, ``IdentityDefinition``, ``HotaDefinition``: ``who``)
+    share before their loop over the lanes; ``stream_eval.hpp`` is the same rule on the device.  The arrays coerced and
+    their shapes refused by name; ``tables`` are the int64 arrays a later definition takes besides, ``name=(array, width)``
+    for ``[B, width]`` and ``width = None`` for ``[B, G]``.  Returns ``(track_id, boxes, labels, gt_box, gt_label, gt_id, n,
+    ng, *tables)``: ``boxes`` fp32 ``[B, A, 4]`` is ``track_box`` or the detections' as ``boxes=`` of the score options has
+    it, ``labels`` int32 ``[B, A]`` the detections' classes, ``n`` int64 ``[B]`` the lane's ``n_keep`` inside ``0..A`` and
+    ``ng`` its ``n_gt`` (None: ``G``) capped at ``G`` -- negative: the lane has no labels at this instant."""
+    det, track_id = np.asarray(det, np.float32), np.asarray(track_id, np.int64)
+    B, A = det.shape[:2]
+    gt_box, gt_label, gt_id = np.asarray(gt_box, np.float32), np.asarray(gt_label, np.int32), np.asarray(gt_id, np.int64)
+    G = gt_box.shape[1] if gt_box.ndim == 3 else -1
+    names = list(tables)
+    widths = [tables[name][1] for name in names]
+    tables = [np.asarray(tables[name][0], np.int64) for name in names]
+    if B != batch_size or det.shape[2:] != (6,) or track_id.shape != (B, A):
+        raise ValueError(f"{who}: det is fp32 [{batch_size}, A, 6] and track_id int64 [{batch_size}, A], got {det.shape} and "
+                         f"{track_id.shape}")
+    if gt_box.shape != (B, G, 4) or gt_label.shape != (B, G) or gt_id.shape != (B, G) or not 0 <= G <= DAGR_SCORE_MAX_GT or \
+            any(t.shape != (B, G if w is None else w) for t, w in zip(tables, widths)):
+        more = "".join(f", {name} int64 [{B}, {'G' if w is None else w}]" for name, w in zip(names, widths))
+        got = ", ".join(str(a.shape) for a in [gt_box, gt_label, gt_id] + tables)
+        raise ValueError(f"{who}: the ground truth is gt_box fp32 [{B}, G, 4], gt_label int32 [{B}, G] and gt_id int64 "
+                         f"[{B}, G] with G <= DAGR_SCORE_MAX_GT = {DAGR_SCORE_MAX_GT}{more}, got {got}")
+    if boxes == "track":
+        if track_box is None:
+            raise ValueError(f"{who}: score boxes = 'track' needs the step's track_box")
+        boxes = np.asarray(track_box, np.float32)
+    else:
+        boxes = det[..., :4]
+    with np.errstate(all="ignore"):
+        labels = det[..., 5].astype(np.int32)
+    n = np.clip(np.broadcast_to(np.asarray(n_keep, np.int64).reshape(-1), (B,)), 0, A)
+    n_gt = np.full(B, G, np.int64) if n_gt is None else np.broadcast_to(np.asarray(n_gt, np.int64).reshape(-1), (B,))
+    return (track_id, boxes, labels, gt_box, gt_label, gt_id, n, np.minimum(n_gt, G), *tables)
+
+
+def _lane_hypotheses(track_id, n, first_carriers=False):
+    """A lane's hypotheses and how many rows have an id: of ``track_id`` int64 ``[A]`` the rows below ``n`` with an id, in
+    row order, cut at ``DAGR_TRACK_MAX_DETS``; with ``first_carriers`` of those only the first row that carries an id (a
+    carrier behind the cut is none)."""
+    with_id = [i for i in range(n) if track_id[i] != 0]
+    hyp = with_id[:DAGR_TRACK_MAX_DETS]
+    if first_carriers:
+        first = {}
+        for i in hyp:
+            first.setdefault(int(track_id[i]), i)
+        hyp = list(first.values())
+    return hyp, len(with_id)
+
+
+def _lane_scored_rows(gt_id, gt_match, ng, score_ids):
+    """The rows of a lane that count behind the scorer, as ``[(row, slot)]`` in row order: a row below ``ng`` that the
+    scorer scored (its ``gt_match`` is not -1, its identity positive) and whose identity ``score_ids``, the scorer's id
+    table of the lane, holds -- at the first slot that does."""
+    rows = []
+    for g in range(ng):
+        known = np.flatnonzero(score_ids == gt_id[g]) if gt_match[g] != -1 and gt_id[g] > 0 else []
+        if len(known):
+            rows.append((g, int(known[0])))
+    return rows
+
+
 class ScoreDefinition:
     """The scorer of the module docstring in numpy -- this project's statement of the CLEAR-MOT counts with a greedy
     matcher: ``step(det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt=None, track_box=None)`` is one scored step of every
@@ -1074,39 +1137,19 @@ class ScoreDefinition:
                            unscored_gt=0, rows_without_id=0)
 
     def step(self, det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt=None, track_box=None, out=None):
-        f = np.float32
-        det, track_id = np.asarray(det, np.float32), np.asarray(track_id, np.int64)
-        B, A = det.shape[:2]
-        gt_box, gt_label, gt_id = np.asarray(gt_box, np.float32), np.asarray(gt_label, np.int32), np.asarray(gt_id, np.int64)
-        G = gt_box.shape[1] if gt_box.ndim == 3 else -1
-        if B != self.B or det.shape[2:] != (6,) or track_id.shape != (B, A):
-            raise ValueError(f"ScoreDefinition: det is fp32 [{self.B}, A, 6] and track_id int64 [{self.B}, A], got {det.shape} "
-                             f"and {track_id.shape}")
-        if gt_box.shape != (B, G, 4) or gt_label.shape != (B, G) or gt_id.shape != (B, G) or not 0 <= G <= DAGR_SCORE_MAX_GT:
-            raise ValueError(f"ScoreDefinition: the ground truth is gt_box fp32 [{B}, G, 4], gt_label int32 [{B}, G] and gt_id "
-                             f"int64 [{B}, G] with G <= DAGR_SCORE_MAX_GT = {DAGR_SCORE_MAX_GT}, got {gt_box.shape}, "
-                             f"{gt_label.shape}, {gt_id.shape}")
-        o = self.options
-        if o["boxes"] == "track":
-            if track_box is None:
-                raise ValueError("ScoreDefinition: score boxes = 'track' needs the step's track_box")
-            boxes = np.asarray(track_box, np.float32)
-        else:
-            boxes = det[..., :4]
-        n_keep = np.broadcast_to(np.asarray(n_keep, np.int64).reshape(-1), (B,))
-        n_gt = np.full(B, G, np.int64) if n_gt is None else np.broadcast_to(np.asarray(n_gt, np.int64).reshape(-1), (B,))
+        f, o = np.float32, self.options
+        track_id, boxes, all_labels, gt_box, gt_label, gt_id, n_rows, n_gt = _labelled_step(
+            "ScoreDefinition", self.B, o["boxes"], det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt, track_box)
+        B, G = gt_label.shape
         gt_match, gt_flags = out if out is not None else (np.zeros((B, G), np.int64), np.zeros((B, G), np.int32))
         thr, M, c, ev = f(o["iou"]), o["max_objects"], self.counters, self.events
         for b in range(B):
             if n_gt[b] < 0:                                        # no labels at this instant: not one byte changes
                 continue
-            n, ng, steps = min(max(int(n_keep[b]), 0), A), min(int(n_gt[b]), G), int(c["steps"][b])
-            with np.errstate(all="ignore"):
-                labels = det[b, :, 5].astype(np.int32)
-            with_id = [i for i in range(n) if track_id[b, i] != 0]                # 1: the hypotheses
-            ev["rows_without_id"] += n - len(with_id)
-            hyp = with_id[:DAGR_TRACK_MAX_DETS]
-            c["unscored_hyp"][b] += len(with_id) - len(hyp)
+            n, ng, steps, labels = int(n_rows[b]), int(n_gt[b]), int(c["steps"][b]), all_labels[b]
+            hyp, n_with_id = _lane_hypotheses(track_id[b], n)                      # 1: the hypotheses
+            ev["rows_without_id"] += n - n_with_id
+            c["unscored_hyp"][b] += n_with_id - len(hyp)
             slot, earlier = {}, set()                                             # 2: the slots
             for g in range(ng):
                 ident = int(gt_id[b, g])
@@ -1361,47 +1404,22 @@ class IdentityDefinition:
                            label_mismatch=0, nan_iou=0, shared_hyp=0)
 
     def step(self, det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt, gt_match, score_ids, track_box=None):
-        det, track_id = np.asarray(det, np.float32), np.asarray(track_id, np.int64)
-        B, A = det.shape[:2]
-        gt_box, gt_label, gt_id = np.asarray(gt_box, np.float32), np.asarray(gt_label, np.int32), np.asarray(gt_id, np.int64)
-        gt_match, score_ids = np.asarray(gt_match, np.int64), np.asarray(score_ids, np.int64)
-        G = gt_box.shape[1] if gt_box.ndim == 3 else -1
         M, T, w, ev = self.score["max_objects"], self.options["max_tracks"], self.words, self.events
-        if B != self.B or det.shape[2:] != (6,) or track_id.shape != (B, A):
-            raise ValueError(f"IdentityDefinition: det is fp32 [{self.B}, A, 6] and track_id int64 [{self.B}, A], got "
-                             f"{det.shape} and {track_id.shape}")
-        if gt_box.shape != (B, G, 4) or gt_label.shape != (B, G) or gt_id.shape != (B, G) or gt_match.shape != (B, G) or \
-                not 0 <= G <= DAGR_SCORE_MAX_GT or score_ids.shape != (B, M):
-            raise ValueError(f"IdentityDefinition: the ground truth is gt_box fp32 [{B}, G, 4], gt_label int32, gt_id and "
-                             f"gt_match int64 [{B}, G] with G <= DAGR_SCORE_MAX_GT = {DAGR_SCORE_MAX_GT} and score_ids int64 "
-                             f"[{B}, {M}], got {gt_box.shape}, {gt_label.shape}, {gt_id.shape}, {gt_match.shape}, "
-                             f"{score_ids.shape}")
-        if self.score["boxes"] == "track":
-            if track_box is None:
-                raise ValueError("IdentityDefinition: score boxes = 'track' needs the step's track_box")
-            boxes = np.asarray(track_box, np.float32)
-        else:
-            boxes = det[..., :4]
-        n_keep = np.broadcast_to(np.asarray(n_keep, np.int64).reshape(-1), (B,))
-        n_gt = np.full(B, G, np.int64) if n_gt is None else np.broadcast_to(np.asarray(n_gt, np.int64).reshape(-1), (B,))
+        track_id, boxes, all_labels, gt_box, gt_label, gt_id, n_rows, n_gt, gt_match, score_ids = _labelled_step(
+            "IdentityDefinition", self.B, self.score["boxes"], det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt, track_box,
+            gt_match=(gt_match, None), score_ids=(score_ids, M))
         thr = np.float32(self.score["iou"])
-        for b in range(B):
+        for b in range(self.B):
             if n_gt[b] < 0:                                        # no labels at this instant: not one byte changes
                 ev["lanes_skipped"] += 1
                 continue
-            n, ng = min(max(int(n_keep[b]), 0), A), min(int(n_gt[b]), G)
-            with np.errstate(all="ignore"):
-                labels = det[b, :, 5].astype(np.int32)
-            hyp, carried, col = [], set(), {}                                      # 1: the hypotheses
-            for i in [i for i in range(n) if track_id[b, i] != 0][:DAGR_TRACK_MAX_DETS]:
-                ident = int(track_id[b, i])
-                if ident in carried:
-                    w["dup_hyp"][b] += 1
-                    ev["duplicates"] += 1
-                    continue
-                carried.add(ident)
-                hyp.append(i)
-                w["hyp_frames"][b] += 1
+            n, ng, labels = int(n_rows[b]), int(n_gt[b]), all_labels[b]
+            hyp, n_with_id = _lane_hypotheses(track_id[b], n, first_carriers=True)  # 1: the hypotheses
+            duplicates = min(n_with_id, DAGR_TRACK_MAX_DETS) - len(hyp)
+            w["dup_hyp"][b] += duplicates
+            ev["duplicates"] += duplicates
+            w["hyp_frames"][b] += len(hyp)
+            col = {}
             for i in hyp:                                                          # 2: the columns
                 ident = int(track_id[b, i])
                 known = np.flatnonzero(self.track_id[b, :w["n_tracks"][b]] == ident)
@@ -1417,17 +1435,12 @@ class IdentityDefinition:
                     ev["unlisted"] += 1
                     continue
                 self.track_len[b, col[i]] += 1
-            slot = {}                                                              # 3: the rows
-            for g in range(ng):
-                scored = gt_match[b, g] != -1 and gt_id[b, g] > 0
-                known = np.flatnonzero(score_ids[b] == gt_id[b, g]) if scored else []
-                if len(known) == 0:
-                    ev["rows_skipped"] += 1
-                    continue
-                slot[g] = int(known[0])
-                w["gt_frames"][b] += 1
-                self.obj_len[b, slot[g]] += 1
-                w["n_objects"][b] = max(int(w["n_objects"][b]), slot[g] + 1)
+            slot = dict(_lane_scored_rows(gt_id[b], gt_match[b], ng, score_ids[b]))     # 3: the rows
+            ev["rows_skipped"] += ng - len(slot)
+            w["gt_frames"][b] += len(slot)
+            for s in slot.values():
+                self.obj_len[b, s] += 1
+                w["n_objects"][b] = max(int(w["n_objects"][b]), s + 1)
             hit = set()
             for g, s in slot.items():                                              # 4: the pairs
                 for i, c in col.items():
@@ -1574,30 +1587,11 @@ class HotaDefinition:
                            matched=0, alignment_decides=0, tall=0, wide=0)
 
     def step(self, det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt, gt_match, score_ids, columns, track_box=None):
-        det, track_id = np.asarray(det, np.float32), np.asarray(track_id, np.int64)
-        B, A = det.shape[:2]
-        gt_box, gt_label, gt_id = np.asarray(gt_box, np.float32), np.asarray(gt_label, np.int32), np.asarray(gt_id, np.int64)
-        gt_match, score_ids, columns = np.asarray(gt_match, np.int64), np.asarray(score_ids, np.int64), np.asarray(columns, np.int64)
-        G = gt_box.shape[1] if gt_box.ndim == 3 else -1
         M, T, w, ev = self.score["max_objects"], self.identity["max_tracks"], self.words, self.events
-        if B != self.B or det.shape[2:] != (6,) or track_id.shape != (B, A):
-            raise ValueError(f"HotaDefinition: det is fp32 [{self.B}, A, 6] and track_id int64 [{self.B}, A], got "
-                             f"{det.shape} and {track_id.shape}")
-        if gt_box.shape != (B, G, 4) or gt_label.shape != (B, G) or gt_id.shape != (B, G) or gt_match.shape != (B, G) or \
-                not 0 <= G <= DAGR_SCORE_MAX_GT or score_ids.shape != (B, M) or columns.shape != (B, T):
-            raise ValueError(f"HotaDefinition: the ground truth is gt_box fp32 [{B}, G, 4], gt_label int32, gt_id and "
-                             f"gt_match int64 [{B}, G] with G <= DAGR_SCORE_MAX_GT = {DAGR_SCORE_MAX_GT}, score_ids int64 "
-                             f"[{B}, {M}] and columns int64 [{B}, {T}], got {gt_box.shape}, {gt_label.shape}, {gt_id.shape}, "
-                             f"{gt_match.shape}, {score_ids.shape}, {columns.shape}")
-        if self.score["boxes"] == "track":
-            if track_box is None:
-                raise ValueError("HotaDefinition: score boxes = 'track' needs the step's track_box")
-            boxes = np.asarray(track_box, np.float32)
-        else:
-            boxes = det[..., :4]
-        n_keep = np.broadcast_to(np.asarray(n_keep, np.int64).reshape(-1), (B,))
-        n_gt = np.full(B, G, np.int64) if n_gt is None else np.broadcast_to(np.asarray(n_gt, np.int64).reshape(-1), (B,))
-        for b in range(B):
+        track_id, boxes, all_labels, gt_box, gt_label, gt_id, n_rows, n_gt, gt_match, score_ids, columns = _labelled_step(
+            "HotaDefinition", self.B, self.score["boxes"], det, n_keep, track_id, gt_box, gt_label, gt_id, n_gt, track_box,
+            gt_match=(gt_match, None), score_ids=(score_ids, M), columns=(columns, T))
+        for b in range(self.B):
             if n_gt[b] < 0:                                        # no labels at this instant: not one byte changes
                 ev["lanes_skipped"] += 1
                 continue
@@ -1605,24 +1599,16 @@ class HotaDefinition:
                 w["dropped_instants"][b] += 1
                 ev["dropped"] += 1
                 continue
-            n, ng = min(max(int(n_keep[b]), 0), A), min(int(n_gt[b]), G)
-            with np.errstate(all="ignore"):
-                labels = det[b, :, 5].astype(np.int32)
-            hyp, col, carried = [], [], set()                      # the hypotheses with a column, in row order
-            for i in [i for i in range(n) if track_id[b, i] != 0][:DAGR_TRACK_MAX_DETS]:
-                ident = int(track_id[b, i])
-                known = np.flatnonzero(columns[b] == ident)
-                if ident not in carried and len(known):
+            n, ng, labels = int(n_rows[b]), int(n_gt[b]), all_labels[b]
+            hyp, col = [], []                                      # the hypotheses with a column, in row order
+            for i in _lane_hypotheses(track_id[b], n, first_carriers=True)[0]:
+                known = np.flatnonzero(columns[b] == track_id[b, i])
+                if len(known):
                     hyp.append(i)
                     col.append(int(known[0]))
-                carried.add(ident)
-            rows, slot = [], []                                    # the ground-truth rows with a slot, in row order
-            for g in range(ng):
-                known = np.flatnonzero(score_ids[b] == gt_id[b, g]) if gt_match[b, g] != -1 and gt_id[b, g] > 0 else []
-                if len(known):
-                    rows.append(g)
-                    slot.append(int(known[0]))
-            slot, col = np.asarray(slot, np.int64), np.asarray(col, np.int64)
+            scored = _lane_scored_rows(gt_id[b], gt_match[b], ng, score_ids[b])   # the ground-truth rows with a slot
+            rows = [g for g, _ in scored]
+            slot, col = np.asarray([s for _, s in scored], np.int64), np.asarray(col, np.int64)
             entry = dict(slot=slot, col=col, gt_box=gt_box[b, rows].copy(), gt_label=gt_label[b, rows].copy(),
                          hyp_box=boxes[b, hyp].copy(), hyp_label=labels[hyp].copy())
             q = hota_similarity(entry["gt_box"], entry["gt_label"], entry["hyp_box"], entry["hyp_label"])

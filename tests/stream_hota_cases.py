@@ -184,6 +184,17 @@ def cases():
         _case("a-full-log-leaves-the-instant-out", [first] * 2 + [second],
               dict(tp=[upto(K, 2)], fn=[upto(K, 0)], fp=[upto(K, 0)], words=[(2, 1, 2, 2)], deta=1.0, assa=1.0, hota=1.0),
               hota=dict(max_instants=2)),
+        # tests/stream_identity_cases.cut_steps: 7 rows and the 12 first carriers among the first 256 rows with an id are
+        # an instant's participants (lane 1: no column at the first step, 6 rows at the second); the four pairs of a step
+        # have an IoU of 56 / 72, a TP up to k = 15
+        dict(name="300-rows-with-ids-256-take-part-and-duplicates-in-every-register", steps=ic.cut_steps(), hota=True, **ic.CUT,
+             expect=dict(tp=[upto(15, 8), upto(15, 4)], fn=[upto(15, 6, 14), upto(15, 9, 13)],
+                         fp=[upto(15, 16, 24), upto(15, 8, 12)], words=[(2, 0, 14, 24), (2, 0, 13, 12)], deta=None, assa=None,
+                         hota=None)),
+        # G = 0: the ground-truth arrays are empty; a labelled lane logs an instant of columns, the lane beside it is skipped
+        _case("no-ground-truth-arrays-at-all", [([[hyp(0, 0, 5), hyp(20, 0, 6)], [hyp(0, 0, 8)]], [[], []], [0, -1])],
+              dict(tp=[upto(K, 0)] * 2, fn=[upto(K, 0)] * 2, fp=[upto(K, 2), upto(K, 0)], words=[(1, 0, 0, 2), (0, 0, 0, 0)],
+                   deta=0.0, assa=0.0, hota=0.0), G=0),
     ]
 
 

@@ -105,6 +105,43 @@ def _case(name, steps, expect, score=True, identity=True, A=4, G=4):
                 steps=[sc.step(s[0], s[1], A, G, n_gt=s[2] if len(s) > 2 else None) for s in steps], expect=expect)
 
 
+CUT = dict(B=2, A=320, G=8, score=dict(max_objects=16), identity=dict(max_tracks=16))
+_CUT = []
+
+
+def cut_steps():
+    """Two steps of A = 320 rows on a grid of disjoint 8 x 8 boxes, 300 of them with an id (every sixteenth has none), so
+    that 256 take part and 44 lie behind the cut at DAGR_TRACK_MAX_DETS.  By rank among the rows with an id: below 256 an
+    even rank carries one of three ids of its own block of 64 (every register of a thread has first carriers) and an odd
+    rank one of the first block's three (duplicates whose first carrier is in another register): 12 ids, 244 duplicates;
+    the ranks 256 .. 279 repeat those ids (carriers behind the cut) and the ranks from 280 on carry ids of their own, which
+    must not be listed although four of the 16 columns stay free.  The eight ground-truth boxes sit one pixel right of the
+    rows of rank 0, 64, 130, 194 (first carriers: a pair each), 65 (a duplicate), 285 (behind the cut), 2 (without an
+    identity: unscored) and 1 (the other label).  Lane 1 has ids and identities of its own; n_keep is 400 (above A) and -1
+    (lane 1 has no hypotheses) at the first step, and lane 1 has six labelled rows at the second."""
+    if not _CUT:
+        A, G = CUT["A"], CUT["G"]
+        with_id = [i for i in range(A) if i % 16 != 5]
+
+        def ident(r):
+            if r >= 280:
+                return 2000 + r
+            if r >= 256:
+                return 1000 + r % 12
+            return 1000 + r % 3 + (3 * (r // 64) if r % 2 == 0 else 0)
+
+        def lane(first_id, first_identity):
+            ids = dict((i, first_id + ident(r)) for r, i in enumerate(with_id))
+            rows = [hyp(20 * (i % 20), 20 * (i // 20), ids.get(i, 0), label=i % 2) for i in range(A)]
+            truth = [gt(20 * (i % 20) + 1, 20 * (i // 20), 0 if g == 6 else first_identity + g, label=(i + (g == 7)) % 2)
+                     for g, i in enumerate(with_id[r] for r in (0, 64, 130, 194, 65, 285, 2, 1))]
+            return rows, truth
+        (rows0, truth0), (rows1, truth1) = lane(0, 1), lane(5000, 101)
+        _CUT.extend([sc.step([rows0, rows1], [truth0, truth1], A, G, n_gt=[8, 8], n_keep=[400, -1]),
+                     sc.step([rows0, rows1], [truth0, truth1], A, G, n_gt=[8, 6], n_keep=[A, A])])
+    return _CUT
+
+
 def cases():
     nan = float("nan")
     two = [[hyp(0, 0, 5), hyp(40, 0, 6)]], [[gt(0, 0, 1), gt(40, 0, 2)]]
@@ -153,7 +190,18 @@ def cases():
     box = np.tile(np.asarray(sc.PAD_GT, np.float32), (1, 4, 1))
     box[0, 0], box[0, 1] = (0, 0, 8, 8), (41, 0, 49, 8)
     moved["steps"][0]["track_box"] = box
-    return out + [moved]
+    # cut_steps: the columns in row order of the first carriers; the four first carriers under a box overlap it at both steps
+    listed = [1000, 1001, 1002, 1004, 1003, 1005, 1008, 1007, 1006, 1009, 1011, 1010]
+    pairs = np.zeros((7, 12), np.int32)
+    pairs[[0, 1, 2, 3], [0, 3, 7, 10]] = 1
+    cut = dict(name="300-rows-with-ids-256-take-part-and-duplicates-in-every-register", steps=cut_steps(), **CUT,
+               expect=dict(overlap=[(2 * pairs).tolist(), pairs.tolist()], track_id=[listed, [5000 + v for v in listed]],
+                           words=[(12, 7, 14, 24, 488, 0, 8, 2), (12, 7, 13, 12, 244, 0, 4, 2)], idtp=[8, 4], idf1=24 / 63))
+    # G = 0: the ground-truth arrays are empty; a labelled lane lists its tracks, the lane beside it is skipped
+    empty = _case("no-ground-truth-arrays-at-all", [([[hyp(0, 0, 5), hyp(20, 0, 6)], [hyp(0, 0, 8)]], [[], []], [0, -1])],
+                  dict(overlap=[[[0, 0]], [[]]], track_id=[[5, 6], []], words=[(2, 0, 0, 2, 0, 0, 0, 1), (0, 0, 0, 0, 0, 0, 0, 0)],
+                       idtp=[0, 0], idf1=0.0), G=0)
+    return out + [moved, cut, empty]
 
 
 _RESULTS = {}

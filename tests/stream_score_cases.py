@@ -91,6 +91,17 @@ def _caps_objects():
                 steps=[step([rows], [labels(f)], 4, 256) for f in firsts], expect=expect)
 
 
+def _n_keep_outside():
+    """n_keep = 9 of A = 4 reads the four rows there are; n_keep = -2 reads none, so lane 1's two objects are missed and
+    nothing of it is a false positive."""
+    rows = [hyp(0, 0, 5), hyp(20, 0, 6), hyp(40, 0, 7), hyp(60, 0, 8)]
+    truth = [gt(0, 0, 1), gt(60, 0, 2)]
+    return dict(name="n-keep-above-A-and-below-zero-is-clamped", B=2, A=4, G=2, score=True,
+                steps=[step([rows, rows], [truth, truth], 4, 2, n_keep=[9, -2])],
+                expect=[dict(match=[[5, 8], [0, 0]], flags=[[0, 0], [0, 0]],
+                             counters=[(2, 4, 2, 0, 2, 0, 0, 0, 0, 0), (2, 0, 0, 2, 0, 0, 0, 0, 0, 0)], objects=None)])
+
+
 def cases():
     above_half = float(np.nextafter(np.float32(0.5), np.float32(1)))
     one, no = hyp(0, 0, 5), []
@@ -162,6 +173,11 @@ def cases():
               [([[hyp(5, 5, 5, 0, 0)]], [[gt(5, 5, 1, 0, 0)]])], [([[0]], [[0]], [(1, 1, 0, 1, 1, 0, 0, 0, 0, 0)])]),
         _caps_hypotheses(),
         _caps_objects(),
+        _n_keep_outside(),
+        # G = 0: the ground-truth arrays are empty; a labelled lane's rows are false positives, the lane beside it is skipped
+        _case("no-ground-truth-arrays-at-all",
+              [([[hyp(0, 0, 5), hyp(20, 0, 6)], [one]], [[], []], [0, -1])],
+              [([[], None], [[], None], [(0, 2, 0, 0, 2, 0, 0, 0, 0, 0), (0, 0, 0, 0, 0, 0, 0, 0, 0, 0)])], G=0),
     ]
     return out
 
