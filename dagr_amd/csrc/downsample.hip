@@ -10,7 +10,7 @@
 // of several lanes: cell keys, a stable radix sort by key, one thread per run head, a chained scan over the keep flags and
 // an order-preserving compaction that leaves the survivors and their count in device memory.
 #include "common.hpp"
-#include "stream_sort.hpp"
+#include "stream_push.hpp"
 
 namespace dagr {
 namespace {
@@ -43,43 +43,21 @@ __global__ __launch_bounds__(kBlock) void k_downsample_cells(const int32_t *__re
 }
 
 // ---------------------------------------------------------------------------------------------
-// Stream front.  Caller-owned state: the lanes' change maps first (offset 0, fp32 [B, cells_h, cells_w]), then the scan's
-// look-back state, then keys / run order / flags / offsets for a largest push and the sort's temporary storage.
+// Stream front, a keyed push (stream_push.hpp).  Caller-owned state: the lanes' change maps first (offset 0, fp32
+// [B, cells_h, cells_w]), then the push's scratch.
 struct StreamFront {
     float *maps;
-    void *scan_state;
-    uint32_t *key_in, *key_out;     // [max_push] cell keys in arrival order / grouped
-    int32_t *idx_in, *idx_out;      // [max_push] event ids in arrival order / grouped by key, arrival order inside a key
-    int32_t *flag, *offs;           // [max_push] keep flags in arrival order and their exclusive prefix sum
-    void *sort_tmp;
-    size_t sort_tmp_bytes, tmp_offset;
+    PushScratch s;
     size_t head_bytes;              // maps + scan state: what a reset zeroes
 };
 
-// sort_storage: also size the sort's temporary storage (dagr_stream_front_bytes); the other callers take what is left of
-// the caller's buffer behind `sort_tmp`.
-size_t carve_front(int B, int64_t cells, int64_t max_push, char *base, StreamFront *out, bool sort_storage) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = align_up(off + bytes, 256);
-        return base ? base + o : nullptr;
-    };
+StreamFront carve_front(int B, int64_t cells, int64_t max_push, void *base, size_t state_bytes) {
+    Carver c(base);
     StreamFront f;
-    f.maps = (float *)take((size_t)B * cells * 4);
-    f.scan_state = take(scan_chained_state_bytes(max_push));
-    f.head_bytes = off;
-    f.key_in = (uint32_t *)take((size_t)max_push * 4);
-    f.key_out = (uint32_t *)take((size_t)max_push * 4);
-    f.idx_in = (int32_t *)take((size_t)max_push * 4);
-    f.idx_out = (int32_t *)take((size_t)max_push * 4);
-    f.flag = (int32_t *)take((size_t)max_push * 4);
-    f.offs = (int32_t *)take((size_t)max_push * 4);
-    f.sort_tmp_bytes = sort_storage ? sort_tmp_bytes_upto(max_push, key_bits((int64_t)B * cells)) : 256;
-    f.tmp_offset = off;
-    f.sort_tmp = take(f.sort_tmp_bytes);
-    if (out) *out = f;
-    return off;
+    f.maps = c.take<float>((size_t)B * cells * 4);
+    f.s = carve_push(c, max_push, (int64_t)B * cells, state_bytes);
+    f.head_bytes = align_up((size_t)B * cells * 4, 256) + align_up(f.s.scan_bytes, 256);
+    return f;
 }
 
 bool front_sizes_ok(int32_t B, int32_t cells_w, int32_t cells_h, int64_t max_push) {
@@ -87,9 +65,8 @@ bool front_sizes_ok(int32_t B, int32_t cells_w, int32_t cells_h, int64_t max_pus
            (int64_t)B * cells_w * cells_h < (1ll << 31) - 1;
 }
 
-// Launch 1: the key of every raw event, lane * cells + cell, and its id.  An event outside the sensor (status bit 4), in the
-// strip right of / below the last whole cell, or with a lane outside [0, B) (dagr_stream_stage_dev flags that one) gets the
-// sentinel key B * cells: it sorts behind every cell and is never kept.
+// Launch 1: the key of every raw event over the cell grid (push_key): an event in the strip right of / below the last whole
+// cell is never kept either; dagr_stream_stage_dev flags a lane outside [0, B).
 template <typename BatchT>
 __global__ __launch_bounds__(kBlock) void k_front_keys(const int32_t *__restrict__ xy, const BatchT *__restrict__ batch, int n,
                                                       int B, int fx, int fy, int sensor_w, int sensor_h, int cells_w,
@@ -97,16 +74,7 @@ __global__ __launch_bounds__(kBlock) void k_front_keys(const int32_t *__restrict
                                                       int32_t *__restrict__ status) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    const int32_t v = xy[i];
-    const int x = (int16_t)(v & 0xffff), y = (int16_t)(v >> 16);
-    const int64_t b = (int64_t)batch[i];
-    const bool outside = x < 0 || x >= sensor_w || y < 0 || y >= sensor_h;
-    if (outside) atomicOr(status, 16);
-    const int cx = outside ? 0 : x / fx, cy = outside ? 0 : y / fy;
-    const uint32_t cells = (uint32_t)cells_w * (uint32_t)cells_h;
-    const bool none = outside || cx >= cells_w || cy >= cells_h || b < 0 || b >= B;
-    key[i] = none ? (uint32_t)B * cells : (uint32_t)b * cells + (uint32_t)(cy * cells_w + cx);
-    idx[i] = i;
+    push_key(xy, batch, i, B, sensor_w, sensor_h, fx, fy, cells_w, cells_h, true, key, idx, status);
 }
 
 // Launch 3 (after the sort): one thread per grouped position.  A position whose key differs from its predecessor's is a run
@@ -135,7 +103,8 @@ __global__ __launch_bounds__(kBlock) void k_front_integrate(const uint32_t *__re
     maps[mine] = state;
 }
 
-// Launch 5 (after the scan): the survivors, in arrival order, at the cells' coordinates, and their count.
+// Launch 5 (after the scan): the survivors, in arrival order, at the cells' coordinates, and their count -- as the scan
+// leaves it, and no lane-less tail: dagr_stream_stage_dev takes the count from the device.
 template <typename BatchT>
 __global__ __launch_bounds__(kBlock) void k_front_compact(const int32_t *__restrict__ flag, const int32_t *__restrict__ offs,
                                                          int n, const int32_t *__restrict__ xy, const int64_t *__restrict__ t,
@@ -145,15 +114,8 @@ __global__ __launch_bounds__(kBlock) void k_front_compact(const int32_t *__restr
                                                          int32_t *__restrict__ batch_out, int32_t *__restrict__ n_out) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    const int keep = flag[i], j = offs[i];
-    if (i == n - 1) *n_out = j + keep;
-    if (!keep || j < 0 || j > i) return;
-    const int32_t v = xy[i];
-    const int x = (int16_t)(v & 0xffff) / fx, y = (int16_t)(v >> 16) / fy;
-    xy_out[j] = (x & 0xffff) | (y << 16);
-    t_out[j] = t[i];
-    p_out[j] = p[i];
-    batch_out[j] = (int32_t)batch[i];
+    if (i == n - 1) *n_out = offs[i] + flag[i];
+    push_survivor(i, flag, offs, xy, t, p, batch, fx, fy, xy_out, t_out, p_out, batch_out);
 }
 
 }  // namespace
@@ -176,16 +138,15 @@ extern "C" int dagr_downsample_events(const int32_t *order, const int32_t *run_c
 
 extern "C" size_t dagr_stream_front_bytes(int32_t B, int32_t cells_w, int32_t cells_h, int64_t max_push) {
     if (!front_sizes_ok(B, cells_w, cells_h, max_push)) return 0;
-    return carve_front(B, (int64_t)cells_w * cells_h, max_push, nullptr, nullptr, true);
+    return carve_front(B, (int64_t)cells_w * cells_h, max_push, nullptr, 0).s.end;
 }
 
 extern "C" int dagr_stream_front_reset(void *front, size_t front_bytes, int32_t B, int32_t cells_w, int32_t cells_h,
                                        int64_t max_push, void *stream) {
     DAGR_CHECK_ARG(front != nullptr, "stream front: state is NULL");
     DAGR_CHECK_ARG(front_sizes_ok(B, cells_w, cells_h, max_push), "stream front: sizes out of range");
-    StreamFront f;
-    carve_front(B, (int64_t)cells_w * cells_h, max_push, (char *)front, &f, false);
-    DAGR_CHECK_ARG(front_bytes >= f.tmp_offset + 256, "stream front: state smaller than dagr_stream_front_bytes");
+    const StreamFront f = carve_front(B, (int64_t)cells_w * cells_h, max_push, front, front_bytes);
+    DAGR_CHECK_ARG(push_state_holds(f.s), "stream front: state smaller than dagr_stream_front_bytes");
     DAGR_CHECK_HIP(hipMemsetAsync(front, 0, f.head_bytes, (hipStream_t)stream));
     return DAGR_OK;
 }
@@ -201,51 +162,37 @@ extern "C" int dagr_stream_downsample(void *front, size_t front_bytes, int32_t B
     DAGR_CHECK_ARG(front_sizes_ok(B, cells_w, cells_h, max_push), "stream front: sizes out of range");
     DAGR_CHECK_ARG(width >= 1 && height >= 1 && width <= cells_w && height <= cells_h,
                    "stream front: the cell grid does not cover width x height");
-    DAGR_CHECK_ARG(front && n_out && status, "stream front: NULL pointer");
-    DAGR_CHECK_ARG(n_raw >= 0 && n_raw <= max_push, "stream front: max_push < n_raw");
-    DAGR_CHECK_ARG(n_raw == 0 || (xy_raw && t_raw && p_raw && batch_raw && xy_out && t_out && p_out && batch_out),
-                   "stream front: NULL input or output");
-    DAGR_CHECK_ARG(((uintptr_t)xy_raw & 3) == 0 && ((uintptr_t)xy_out & 3) == 0, "stream front: xy must be 4-byte aligned");
+    const std::string complaint = push_args_complaint("stream front", front, n_out, status, n_raw, max_push, xy_raw, t_raw,
+                                                      p_raw, batch_raw, xy_out, t_out, p_out, batch_out);
+    DAGR_CHECK_ARG(complaint.empty(), complaint);
     hipStream_t stream = (hipStream_t)stream_;
     if (n_raw == 0) {
         DAGR_CHECK_HIP(hipMemsetAsync(n_out, 0, 4, stream));
         return DAGR_OK;
     }
-    StreamFront f;
     const int64_t cells = (int64_t)cells_w * cells_h;
-    carve_front(B, cells, max_push, (char *)front, &f, false);
-    DAGR_CHECK_ARG(front_bytes >= f.tmp_offset + 256, "stream front: state smaller than dagr_stream_front_bytes");
-    f.sort_tmp_bytes = front_bytes - f.tmp_offset;
+    const StreamFront f = carve_front(B, cells, max_push, front, front_bytes);
+    DAGR_CHECK_ARG(push_state_holds(f.s), "stream front: state smaller than dagr_stream_front_bytes");
     const int n = (int)n_raw, bits = key_bits((int64_t)B * cells);
     const unsigned grid = (unsigned)ceil_div(n_raw, kBlock);
     const uint32_t sentinel = (uint32_t)((int64_t)B * cells);
     const float inc = (float)(1.0 / (double)(fx * fy));
-    size_t tmp = 0;
-    DAGR_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, tmp, f.key_in, f.key_out, f.idx_in, f.idx_out, (size_t)n, 0u,
-                                             (unsigned)bits, stream));
-    DAGR_CHECK_ARG(tmp <= f.sort_tmp_bytes, "stream front: the sort asks for more temporary storage than the state holds");
-    tmp = f.sort_tmp_bytes;
-    if (batch_is_int64)
-        k_front_keys<int64_t><<<grid, kBlock, 0, stream>>>((const int32_t *)xy_raw, (const int64_t *)batch_raw, n, B, fx, fy,
-                                                          sensor_w, sensor_h, cells_w, cells_h, f.key_in, f.idx_in, status);
-    else
-        k_front_keys<int32_t><<<grid, kBlock, 0, stream>>>((const int32_t *)xy_raw, (const int32_t *)batch_raw, n, B, fx, fy,
-                                                          sensor_w, sensor_h, cells_w, cells_h, f.key_in, f.idx_in, status);
+    const int32_t *xy = (const int32_t *)xy_raw;
+    DAGR_CHECK_ARG(sort_push_fits(f.s, n, bits), "stream front: the sort asks for more temporary storage than the state holds");
+    with_batch(batch_raw, batch_is_int64, [&](auto *batch) {
+        k_front_keys<<<grid, kBlock, 0, stream>>>(xy, batch, n, B, fx, fy, sensor_w, sensor_h, cells_w, cells_h, f.s.key_in,
+                                                  f.s.idx_in, status);
+    });
     DAGR_CHECK_LAUNCH();
-    DAGR_CHECK_HIP(rocprim::radix_sort_pairs(f.sort_tmp, tmp, f.key_in, f.key_out, f.idx_in, f.idx_out, (size_t)n, 0u,
-                                             (unsigned)bits, stream));
-    k_front_integrate<<<grid, kBlock, 0, stream>>>(f.key_out, f.idx_out, n, sentinel, cells_w, cells_h, width, height, p_raw,
-                                                   inc, f.maps, f.flag);
+    DAGR_CHECK_HIP(sort_push(f.s, n, bits, stream));
+    k_front_integrate<<<grid, kBlock, 0, stream>>>(f.s.key_out, f.s.idx_out, n, sentinel, cells_w, cells_h, width, height, p_raw,
+                                                   inc, f.maps, f.s.flag);
     DAGR_CHECK_LAUNCH();
-    DAGR_CHECK_HIP(exclusive_scan_i32_chained(f.flag, f.offs, n_raw, f.scan_state, false, stream));
-    if (batch_is_int64)
-        k_front_compact<int64_t><<<grid, kBlock, 0, stream>>>(f.flag, f.offs, n, (const int32_t *)xy_raw, t_raw, p_raw,
-                                                             (const int64_t *)batch_raw, fx, fy, (int32_t *)xy_out, t_out,
-                                                             p_out, batch_out, n_out);
-    else
-        k_front_compact<int32_t><<<grid, kBlock, 0, stream>>>(f.flag, f.offs, n, (const int32_t *)xy_raw, t_raw, p_raw,
-                                                             (const int32_t *)batch_raw, fx, fy, (int32_t *)xy_out, t_out,
-                                                             p_out, batch_out, n_out);
+    DAGR_CHECK_HIP(exclusive_scan_i32_chained(f.s.flag, f.s.offs, n_raw, f.s.scan_state, false, stream));
+    with_batch(batch_raw, batch_is_int64, [&](auto *batch) {
+        k_front_compact<<<grid, kBlock, 0, stream>>>(f.s.flag, f.s.offs, n, xy, t_raw, p_raw, batch, fx, fy, (int32_t *)xy_out,
+                                                     t_out, p_out, batch_out, n_out);
+    });
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
 }

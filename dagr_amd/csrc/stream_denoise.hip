@@ -8,57 +8,27 @@
 // one thread per event.  The events are sorted by pixel key (lane, y, x) with the arrival index as payload (a stable radix
 // sort: the arrival index ascends inside a run); the latest earlier event of a pixel is then a binary search away, and
 // where the push has none the carried stamp applies.  The stamps are written in a later launch than the one that reads
-// them.  Keep flags, the project's chained scan, an order-preserving compaction: as the stream front (downsample.hip).
+// them.  Keep flags, the project's chained scan, an order-preserving compaction: a keyed push (stream_push.hpp).
 #include "common.hpp"
-#include "stream_sort.hpp"
+#include "stream_push.hpp"
 
 namespace dagr {
 namespace {
 
 constexpr int64_t kNever = INT64_MIN;
 
-// Caller-owned state: the lanes' stamp maps first (offset 0, int64 [B, sensor_h, sensor_w]), then the scan's look-back
-// state, then keys / sorted order / flags / offsets for a largest push and the sort's temporary storage.
+// Caller-owned state: the lanes' stamp maps first (offset 0, int64 [B, sensor_h, sensor_w]), then the push's scratch.
 struct Denoise {
     int64_t *stamps;
-    void *scan_state;
-    size_t scan_bytes;
-    uint32_t *key_in, *key_out;     // [max_push] pixel keys in arrival order / sorted
-    int32_t *idx_in, *idx_out;      // [max_push] arrival indices in arrival order / sorted by key, ascending inside a key
-    int32_t *flag, *offs;           // [max_push] keep flags in arrival order and their exclusive prefix sum
-    void *sort_tmp;
-    size_t sort_tmp_bytes, tmp_offset;
+    PushScratch s;
 };
 
-// sort_storage: also size the sort's temporary storage (dagr_stream_denoise_bytes); the other callers take what is left of
-// the caller's buffer behind `sort_tmp`.
-size_t carve_denoise(int B, int64_t pixels, int64_t max_push, char *base, Denoise *out, bool sort_storage) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = align_up(off + bytes, 256);
-        return base ? base + o : nullptr;
-    };
+Denoise carve_denoise(int B, int64_t pixels, int64_t max_push, void *base, size_t state_bytes) {
+    Carver c(base);
     Denoise f;
-    f.stamps = (int64_t *)take((size_t)B * pixels * 8);
-    f.scan_bytes = scan_chained_state_bytes(max_push);
-    f.scan_state = take(f.scan_bytes);
-    f.key_in = (uint32_t *)take((size_t)max_push * 4);
-    f.key_out = (uint32_t *)take((size_t)max_push * 4);
-    f.idx_in = (int32_t *)take((size_t)max_push * 4);
-    f.idx_out = (int32_t *)take((size_t)max_push * 4);
-    f.flag = (int32_t *)take((size_t)max_push * 4);
-    f.offs = (int32_t *)take((size_t)max_push * 4);
-    f.sort_tmp_bytes = sort_storage ? sort_tmp_bytes_upto(max_push, key_bits((int64_t)B * pixels)) : 256;
-    f.tmp_offset = off;
-    f.sort_tmp = take(f.sort_tmp_bytes);
-    if (out) *out = f;
-    return off;
-}
-
-bool denoise_sizes_ok(int32_t B, int32_t sensor_w, int32_t sensor_h, int64_t max_push) {
-    return B >= 1 && B < 128 && sensor_w >= 1 && sensor_h >= 1 && sensor_w <= 32767 && sensor_h <= 32767 && max_push >= 1 &&
-           max_push < (1ll << 31) / 64 && (int64_t)B * sensor_w * sensor_h < (1ll << 31);
+    f.stamps = c.take<int64_t>((size_t)B * pixels * 8);
+    f.s = carve_push(c, max_push, (int64_t)B * pixels, state_bytes);
+    return f;
 }
 
 __global__ __launch_bounds__(kBlock) void k_denoise_never(int64_t *__restrict__ stamps, int64_t n) {
@@ -66,24 +36,15 @@ __global__ __launch_bounds__(kBlock) void k_denoise_never(int64_t *__restrict__ 
     if (i < n) stamps[i] = kNever;
 }
 
-// Launch 1: the key of every event, lane * pixels + y * sensor_w + x, and its arrival index.  An event outside the sensor
-// (status bit 4) or with a lane outside [0, B) (dagr_stream_stage_dev flags that one) gets the sentinel key B * pixels: it
-// sorts behind every pixel, is never kept and never stamps.
+// Launch 1: the key of every event over the sensor's pixels, lane * pixels + y * sensor_w + x (push_key).  An event with
+// the sentinel key is never kept and never stamps; dagr_stream_stage_dev flags a lane outside [0, B).
 template <typename BatchT>
 __global__ __launch_bounds__(kBlock) void k_denoise_keys(const int32_t *__restrict__ xy, const BatchT *__restrict__ batch, int n,
                                                         int B, int sensor_w, int sensor_h, uint32_t *__restrict__ key,
                                                         int32_t *__restrict__ idx, int32_t *__restrict__ status) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    const int32_t v = xy[i];
-    const int x = (int16_t)(v & 0xffff), y = (int16_t)(v >> 16);
-    const int64_t b = (int64_t)batch[i];
-    const bool outside = x < 0 || x >= sensor_w || y < 0 || y >= sensor_h;
-    if (outside) atomicOr(status, 16);
-    const uint32_t pixels = (uint32_t)sensor_w * (uint32_t)sensor_h;
-    const bool none = outside || b < 0 || b >= B;
-    key[i] = none ? (uint32_t)B * pixels : (uint32_t)b * pixels + (uint32_t)(y * sensor_w + x);
-    idx[i] = i;
+    push_key(xy, batch, i, B, sensor_w, sensor_h, 1, 1, sensor_w, sensor_h, true, key, idx, status);
 }
 
 // The stamp pixel `want` shows to the event with arrival index `me`: the t of the last sorted position whose
@@ -166,20 +127,10 @@ __global__ __launch_bounds__(kBlock) void k_denoise_finish(const int32_t *__rest
                                                           int8_t *__restrict__ p_out, int32_t *__restrict__ batch_out,
                                                           int32_t *__restrict__ n_out, int64_t *__restrict__ lane_filtered) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
-    const int total = min(max(offs[n - 1] + flag[n - 1], 0), n);
+    const int total = push_total(flag, offs, n);
     if (i < n) {
-        const int keep = flag[i], j = offs[i];
-        if (i == n - 1) *n_out = total;
-        if (keep && j >= 0 && j <= i) {
-            xy_out[j] = xy[i];
-            t_out[j] = t[i];
-            p_out[j] = p[i];
-            batch_out[j] = (int32_t)batch[i];
-        }
-        if (i >= total) {
-            xy_out[i] = 0;
-            batch_out[i] = -1;
-        }
+        push_survivor(i, flag, offs, xy, t, p, batch, 1, 1, xy_out, t_out, p_out, batch_out);
+        push_tail(i, n, total, xy_out, batch_out, n_out);
         const uint32_t mine = key[i];
         if (mine < sentinel && (i == n - 1 || key[i + 1] != mine)) stamps[mine] = t[min(max(idx[i], 0), n - 1)];
     }
@@ -217,22 +168,21 @@ __global__ __launch_bounds__(kBlock) void k_denoise_finish(const int32_t *__rest
 using namespace dagr;
 
 extern "C" size_t dagr_stream_denoise_bytes(int32_t B, int32_t sensor_w, int32_t sensor_h, int64_t max_push) {
-    if (!denoise_sizes_ok(B, sensor_w, sensor_h, max_push)) return 0;
-    return carve_denoise(B, (int64_t)sensor_w * sensor_h, max_push, nullptr, nullptr, true);
+    if (!push_sizes_ok(B, sensor_w, sensor_h, max_push)) return 0;
+    return carve_denoise(B, (int64_t)sensor_w * sensor_h, max_push, nullptr, 0).s.end;
 }
 
 extern "C" int dagr_stream_denoise_reset(void *state, size_t state_bytes, int32_t B, int32_t sensor_w, int32_t sensor_h,
                                          int64_t max_push, void *stream) {
     DAGR_CHECK_ARG(state != nullptr, "stream denoise: state is NULL");
-    DAGR_CHECK_ARG(denoise_sizes_ok(B, sensor_w, sensor_h, max_push), "stream denoise: sizes out of range");
-    Denoise f;
+    DAGR_CHECK_ARG(push_sizes_ok(B, sensor_w, sensor_h, max_push), "stream denoise: sizes out of range");
     const int64_t pixels = (int64_t)sensor_w * sensor_h;
-    carve_denoise(B, pixels, max_push, (char *)state, &f, false);
-    DAGR_CHECK_ARG(state_bytes >= f.tmp_offset + 256, "stream denoise: state smaller than dagr_stream_denoise_bytes");
+    const Denoise f = carve_denoise(B, pixels, max_push, state, state_bytes);
+    DAGR_CHECK_ARG(push_state_holds(f.s), "stream denoise: state smaller than dagr_stream_denoise_bytes");
     const int64_t n = (int64_t)B * pixels;
     k_denoise_never<<<(unsigned)ceil_div(n, kBlock), kBlock, 0, (hipStream_t)stream>>>(f.stamps, n);
     DAGR_CHECK_LAUNCH();
-    DAGR_CHECK_HIP(hipMemsetAsync(f.scan_state, 0, f.scan_bytes, (hipStream_t)stream));
+    DAGR_CHECK_HIP(hipMemsetAsync(f.s.scan_state, 0, f.s.scan_bytes, (hipStream_t)stream));
     return DAGR_OK;
 }
 
@@ -241,56 +191,41 @@ extern "C" int dagr_stream_denoise(void *state, size_t state_bytes, int32_t B, i
                                    const int64_t *t_raw, const int8_t *p_raw, const void *batch_raw, int32_t batch_is_int64,
                                    int64_t n_raw, int16_t *xy_out, int64_t *t_out, int8_t *p_out, int32_t *batch_out,
                                    int32_t *n_out, int64_t *lane_filtered, int32_t *status, void *stream_) {
-    DAGR_CHECK_ARG(denoise_sizes_ok(B, sensor_w, sensor_h, max_push), "stream denoise: sizes out of range");
+    DAGR_CHECK_ARG(push_sizes_ok(B, sensor_w, sensor_h, max_push), "stream denoise: sizes out of range");
     DAGR_CHECK_ARG(denoise_us >= 0 && refractory_us >= 0 && (denoise_us > 0 || refractory_us > 0),
                    "stream denoise: denoise_us and refractory_us are positive, or 0 for off, and not both off");
-    DAGR_CHECK_ARG(state && n_out && status, "stream denoise: NULL pointer");
-    DAGR_CHECK_ARG(n_raw >= 0 && n_raw <= max_push, "stream denoise: max_push < n_raw");
-    DAGR_CHECK_ARG(n_raw == 0 || (xy_raw && t_raw && p_raw && batch_raw && xy_out && t_out && p_out && batch_out),
-                   "stream denoise: NULL input or output");
-    DAGR_CHECK_ARG(((uintptr_t)xy_raw & 3) == 0 && ((uintptr_t)xy_out & 3) == 0, "stream denoise: xy must be 4-byte aligned");
+    const std::string complaint = push_args_complaint("stream denoise", state, n_out, status, n_raw, max_push, xy_raw, t_raw,
+                                                      p_raw, batch_raw, xy_out, t_out, p_out, batch_out);
+    DAGR_CHECK_ARG(complaint.empty(), complaint);
     hipStream_t stream = (hipStream_t)stream_;
     if (n_raw == 0) {
         DAGR_CHECK_HIP(hipMemsetAsync(n_out, 0, 4, stream));
         return DAGR_OK;
     }
-    Denoise f;
     const int64_t pixels = (int64_t)sensor_w * sensor_h;
-    carve_denoise(B, pixels, max_push, (char *)state, &f, false);
-    DAGR_CHECK_ARG(state_bytes >= f.tmp_offset + 256, "stream denoise: state smaller than dagr_stream_denoise_bytes");
-    f.sort_tmp_bytes = state_bytes - f.tmp_offset;
+    const Denoise f = carve_denoise(B, pixels, max_push, state, state_bytes);
+    DAGR_CHECK_ARG(push_state_holds(f.s), "stream denoise: state smaller than dagr_stream_denoise_bytes");
     const int n = (int)n_raw, bits = key_bits((int64_t)B * pixels);
     const unsigned grid = (unsigned)ceil_div(n_raw, kBlock);
     const uint32_t sentinel = (uint32_t)((int64_t)B * pixels);
-    size_t tmp = 0;
-    DAGR_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, tmp, f.key_in, f.key_out, f.idx_in, f.idx_out, (size_t)n, 0u,
-                                             (unsigned)bits, stream));
-    DAGR_CHECK_ARG(tmp <= f.sort_tmp_bytes, "stream denoise: the sort asks for more temporary storage than the state holds");
-    tmp = f.sort_tmp_bytes;
-    if (batch_is_int64)
-        k_denoise_keys<int64_t><<<grid, kBlock, 0, stream>>>((const int32_t *)xy_raw, (const int64_t *)batch_raw, n, B,
-                                                            sensor_w, sensor_h, f.key_in, f.idx_in, status);
-    else
-        k_denoise_keys<int32_t><<<grid, kBlock, 0, stream>>>((const int32_t *)xy_raw, (const int32_t *)batch_raw, n, B,
-                                                            sensor_w, sensor_h, f.key_in, f.idx_in, status);
+    const int32_t *xy = (const int32_t *)xy_raw;
+    DAGR_CHECK_ARG(sort_push_fits(f.s, n, bits), "stream denoise: the sort asks for more temporary storage than the state holds");
+    with_batch(batch_raw, batch_is_int64, [&](auto *batch) {
+        k_denoise_keys<<<grid, kBlock, 0, stream>>>(xy, batch, n, B, sensor_w, sensor_h, f.s.key_in, f.s.idx_in, status);
+    });
     DAGR_CHECK_LAUNCH();
-    DAGR_CHECK_HIP(rocprim::radix_sort_pairs(f.sort_tmp, tmp, f.key_in, f.key_out, f.idx_in, f.idx_out, (size_t)n, 0u,
-                                             (unsigned)bits, stream));
-    k_denoise_decide<<<grid, kBlock, 0, stream>>>(f.key_out, f.idx_out, n, sentinel, sensor_w, sensor_h, t_raw, denoise_us,
-                                                  refractory_us, f.stamps, f.flag);
+    DAGR_CHECK_HIP(sort_push(f.s, n, bits, stream));
+    k_denoise_decide<<<grid, kBlock, 0, stream>>>(f.s.key_out, f.s.idx_out, n, sentinel, sensor_w, sensor_h, t_raw, denoise_us,
+                                                  refractory_us, f.stamps, f.s.flag);
     DAGR_CHECK_LAUNCH();
-    DAGR_CHECK_HIP(exclusive_scan_i32_chained(f.flag, f.offs, n_raw, f.scan_state, false, stream));
+    DAGR_CHECK_HIP(exclusive_scan_i32_chained(f.s.flag, f.s.offs, n_raw, f.s.scan_state, false, stream));
     const unsigned grid_f = (unsigned)ceil_div(std::max<int64_t>(n_raw, B), kBlock);
-    if (batch_is_int64)
-        k_denoise_finish<int64_t><<<grid_f, kBlock, 0, stream>>>(f.flag, f.offs, n, f.key_out, f.idx_out, sentinel, B,
-                                                                (uint32_t)pixels, (const int32_t *)xy_raw, t_raw, p_raw,
-                                                                (const int64_t *)batch_raw, f.stamps, (int32_t *)xy_out,
-                                                                t_out, p_out, batch_out, n_out, lane_filtered);
-    else
-        k_denoise_finish<int32_t><<<grid_f, kBlock, 0, stream>>>(f.flag, f.offs, n, f.key_out, f.idx_out, sentinel, B,
-                                                                (uint32_t)pixels, (const int32_t *)xy_raw, t_raw, p_raw,
-                                                                (const int32_t *)batch_raw, f.stamps, (int32_t *)xy_out,
-                                                                t_out, p_out, batch_out, n_out, lane_filtered);
+    with_batch(batch_raw, batch_is_int64, [&](auto *batch) {
+        k_denoise_finish<<<grid_f, kBlock, 0, stream>>>(f.s.flag, f.s.offs, n, f.s.key_out, f.s.idx_out, sentinel, B,
+                                                        (uint32_t)pixels, xy, t_raw, p_raw, batch, f.stamps, (int32_t *)xy_out,
+                                                        t_out, p_out, batch_out, n_out, lane_filtered);
+    });
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
 }
+

@@ -9,7 +9,7 @@
 // pixel keys (lane, y, x), a stable radix sort with the arrival index as payload, then the head of every run takes its
 // pixel's events in arrival order through both stages, from the carried state, and stores the state once.  A pixel's
 // state is read and written by its run's walker alone.  Keep flags, the project's chained scan, an order-preserving
-// compaction: as the other two fronts.  No floating point anywhere.
+// compaction: a keyed push (stream_push.hpp), as the other two fronts.  No floating point anywhere.
 //
 // The walk.  Real pushes hold a few events per pixel, and one thread per run is then the right shape: 64 runs per wave,
 // one dependent load chain (arrival index -> t, p) per event.  A stuck pixel puts hundreds or thousands of events into one
@@ -18,7 +18,7 @@
 // loaded per round by 64 lanes, one load latency for all of them, and walked from registers (v_readlane with a uniform
 // index, so the state machine itself runs once per wave, not per lane).
 #include "common.hpp"
-#include "stream_sort.hpp"
+#include "stream_push.hpp"
 
 namespace dagr {
 namespace {
@@ -92,54 +92,23 @@ __device__ __forceinline__ int pixel_event(Pixel &s, int64_t t, int p, const Fli
 
 // Caller-owned state: the per-pixel maps first -- t_edge int64 [B, sensor_h, sensor_w] at offset 0, t_pass int64 at
 // map_stride, the packed words int32 at 2 * map_stride, with map_stride = 8 * B * pixels rounded up to 256 --, then the
-// scan's look-back state, then keys / sorted order / flags / offsets / outcomes for a largest push and the sort's storage.
+// push's scratch (stream_push.hpp) with the outcomes as its extra array.
 struct Flicker {
     int64_t *t_edge, *t_pass;
     int32_t *word;
-    size_t head_bytes;              // the three maps: what a caller carries over into a larger state
-    void *scan_state;
-    size_t scan_bytes;
-    uint32_t *key_in, *key_out;     // [max_push] pixel keys in arrival order / sorted
-    int32_t *idx_in, *idx_out;      // [max_push] arrival indices in arrival order / sorted by key, ascending inside a key
-    int32_t *flag, *offs;           // [max_push] keep flags in arrival order and their exclusive prefix sum
+    PushScratch s;
     int8_t *outcome;                // [max_push] 0 / 1 / 2 in arrival order (0 for an event that is none of the sensor's)
-    void *sort_tmp;
-    size_t sort_tmp_bytes, tmp_offset;
 };
 
-// sort_storage: also size the sort's temporary storage (dagr_stream_flicker_bytes); the other callers take what is left of
-// the caller's buffer behind `sort_tmp`.
-size_t carve_flicker(int B, int64_t pixels, int64_t max_push, char *base, Flicker *out, bool sort_storage) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = align_up(off + bytes, 256);
-        return base ? base + o : nullptr;
-    };
+Flicker carve_flicker(int B, int64_t pixels, int64_t max_push, void *base, size_t state_bytes) {
+    Carver c(base);
     Flicker f;
-    f.t_edge = (int64_t *)take((size_t)B * pixels * 8);
-    f.t_pass = (int64_t *)take((size_t)B * pixels * 8);
-    f.word = (int32_t *)take((size_t)B * pixels * 4);
-    f.head_bytes = off;
-    f.scan_bytes = scan_chained_state_bytes(max_push);
-    f.scan_state = take(f.scan_bytes);
-    f.key_in = (uint32_t *)take((size_t)max_push * 4);
-    f.key_out = (uint32_t *)take((size_t)max_push * 4);
-    f.idx_in = (int32_t *)take((size_t)max_push * 4);
-    f.idx_out = (int32_t *)take((size_t)max_push * 4);
-    f.flag = (int32_t *)take((size_t)max_push * 4);
-    f.offs = (int32_t *)take((size_t)max_push * 4);
-    f.outcome = (int8_t *)take((size_t)max_push);
-    f.sort_tmp_bytes = sort_storage ? sort_tmp_bytes_upto(max_push, key_bits((int64_t)B * pixels)) : 256;
-    f.tmp_offset = off;
-    f.sort_tmp = take(f.sort_tmp_bytes);
-    if (out) *out = f;
-    return off;
-}
-
-bool flicker_sizes_ok(int32_t B, int32_t sensor_w, int32_t sensor_h, int64_t max_push) {
-    return B >= 1 && B < 128 && sensor_w >= 1 && sensor_h >= 1 && sensor_w <= 32767 && sensor_h <= 32767 && max_push >= 1 &&
-           max_push < (1ll << 31) / 64 && (int64_t)B * sensor_w * sensor_h < (1ll << 31);
+    f.t_edge = c.take<int64_t>((size_t)B * pixels * 8);
+    f.t_pass = c.take<int64_t>((size_t)B * pixels * 8);
+    f.word = c.take<int32_t>((size_t)B * pixels * 4);
+    f.s = carve_push(c, max_push, (int64_t)B * pixels, state_bytes, (size_t)max_push);
+    f.outcome = (int8_t *)f.s.extra;
+    return f;
 }
 
 __global__ __launch_bounds__(kBlock) void k_flicker_initial(int64_t *__restrict__ t_edge, int64_t *__restrict__ t_pass,
@@ -151,24 +120,16 @@ __global__ __launch_bounds__(kBlock) void k_flicker_initial(int64_t *__restrict_
     word[i] = 0;
 }
 
-// Launch 1: the key of every event, lane * pixels + y * sensor_w + x, and its arrival index.  An event outside the sensor
-// (status bit 4) or with a lane outside [0, B) (a lane-less row of the stage in front; dagr_stream_stage_dev flags any
-// other on the clock) gets the sentinel key B * pixels: it sorts behind every pixel, meets no state and is not counted.
+// Launch 1: the key of every event over the sensor's pixels, lane * pixels + y * sensor_w + x (push_key).  An event with
+// the sentinel key meets no state and is not counted.  A row with a lane outside [0, B) is a lane-less row of the stage in
+// front (dagr_stream_stage_dev flags any other on the clock): it raises no status bit, wherever it lies.
 template <typename BatchT>
 __global__ __launch_bounds__(kBlock) void k_flicker_keys(const int32_t *__restrict__ xy, const BatchT *__restrict__ batch, int n,
                                                         int B, int sensor_w, int sensor_h, uint32_t *__restrict__ key,
                                                         int32_t *__restrict__ idx, int32_t *__restrict__ status) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    const int32_t v = xy[i];
-    const int x = (int16_t)(v & 0xffff), y = (int16_t)(v >> 16);
-    const int64_t b = (int64_t)batch[i];
-    const bool lane_ok = b >= 0 && b < B;
-    const bool outside = x < 0 || x >= sensor_w || y < 0 || y >= sensor_h;
-    if (outside && lane_ok) atomicOr(status, 16);
-    const uint32_t pixels = (uint32_t)sensor_w * (uint32_t)sensor_h;
-    key[i] = outside || !lane_ok ? (uint32_t)B * pixels : (uint32_t)b * pixels + (uint32_t)(y * sensor_w + x);
-    idx[i] = i;
+    push_key(xy, batch, i, B, sensor_w, sensor_h, 1, 1, sensor_w, sensor_h, false, key, idx, status);
 }
 
 // Launch 3 (after the sort): one thread per sorted position.  A position whose key differs from its predecessor's is a run
@@ -270,25 +231,15 @@ __global__ __launch_bounds__(kBlock) void k_flicker_finish(const int32_t *__rest
                                                           int64_t *__restrict__ lane_trail) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     const int lane = threadIdx.x & (kWave - 1);
-    const int total = min(max(offs[n - 1] + flag[n - 1], 0), n);
+    const int total = push_total(flag, offs, n);
     int out = 0, b = 0;
     if (i < n) {
-        const int keep = flag[i], j = offs[i];
         const int64_t b64 = (int64_t)batch[i];
         out = outcome[i];
         if (b64 < 0 || b64 >= B) out = 0;                  // (its outcome is 0 already: it met no state)
         b = (int)min(max(b64, (int64_t)0), (int64_t)B - 1);
-        if (i == n - 1) *n_out = total;
-        if (keep && j >= 0 && j <= i) {
-            xy_out[j] = xy[i];
-            t_out[j] = t[i];
-            p_out[j] = p[i];
-            batch_out[j] = (int32_t)b64;
-        }
-        if (i >= total) {
-            xy_out[i] = 0;
-            batch_out[i] = -1;
-        }
+        push_survivor(i, flag, offs, xy, t, p, batch, 1, 1, xy_out, t_out, p_out, batch_out);
+        push_tail(i, n, total, xy_out, batch_out, n_out);
     }
     if (lane_flicker) count_outcome(out == 1, b, lane, lane_flicker);
     if (lane_trail) count_outcome(out == 2, b, lane, lane_trail);
@@ -300,22 +251,21 @@ __global__ __launch_bounds__(kBlock) void k_flicker_finish(const int32_t *__rest
 using namespace dagr;
 
 extern "C" size_t dagr_stream_flicker_bytes(int32_t B, int32_t sensor_w, int32_t sensor_h, int64_t max_push) {
-    if (!flicker_sizes_ok(B, sensor_w, sensor_h, max_push)) return 0;
-    return carve_flicker(B, (int64_t)sensor_w * sensor_h, max_push, nullptr, nullptr, true);
+    if (!push_sizes_ok(B, sensor_w, sensor_h, max_push)) return 0;
+    return carve_flicker(B, (int64_t)sensor_w * sensor_h, max_push, nullptr, 0).s.end;
 }
 
 extern "C" int dagr_stream_flicker_reset(void *state, size_t state_bytes, int32_t B, int32_t sensor_w, int32_t sensor_h,
                                          int64_t max_push, void *stream) {
     DAGR_CHECK_ARG(state != nullptr, "stream flicker: state is NULL");
-    DAGR_CHECK_ARG(flicker_sizes_ok(B, sensor_w, sensor_h, max_push), "stream flicker: sizes out of range");
-    Flicker f;
+    DAGR_CHECK_ARG(push_sizes_ok(B, sensor_w, sensor_h, max_push), "stream flicker: sizes out of range");
     const int64_t pixels = (int64_t)sensor_w * sensor_h;
-    carve_flicker(B, pixels, max_push, (char *)state, &f, false);
-    DAGR_CHECK_ARG(state_bytes >= f.tmp_offset + 256, "stream flicker: state smaller than dagr_stream_flicker_bytes");
+    const Flicker f = carve_flicker(B, pixels, max_push, state, state_bytes);
+    DAGR_CHECK_ARG(push_state_holds(f.s), "stream flicker: state smaller than dagr_stream_flicker_bytes");
     const int64_t n = (int64_t)B * pixels;
     k_flicker_initial<<<(unsigned)ceil_div(n, kBlock), kBlock, 0, (hipStream_t)stream>>>(f.t_edge, f.t_pass, f.word, n);
     DAGR_CHECK_LAUNCH();
-    DAGR_CHECK_HIP(hipMemsetAsync(f.scan_state, 0, f.scan_bytes, (hipStream_t)stream));
+    DAGR_CHECK_HIP(hipMemsetAsync(f.s.scan_state, 0, f.s.scan_bytes, (hipStream_t)stream));
     return DAGR_OK;
 }
 
@@ -325,58 +275,45 @@ extern "C" int dagr_stream_flicker(void *state, size_t state_bytes, int32_t B, i
                                    const int8_t *p_raw, const void *batch_raw, int32_t batch_is_int64, int64_t n_raw,
                                    int16_t *xy_out, int64_t *t_out, int8_t *p_out, int32_t *batch_out, int32_t *n_out,
                                    int64_t *lane_flicker, int64_t *lane_trail, int32_t *status, void *stream_) {
-    DAGR_CHECK_ARG(flicker_sizes_ok(B, sensor_w, sensor_h, max_push), "stream flicker: sizes out of range");
+    DAGR_CHECK_ARG(push_sizes_ok(B, sensor_w, sensor_h, max_push), "stream flicker: sizes out of range");
     DAGR_CHECK_ARG(max_period_us >= 0 && trail_us >= 0 && (max_period_us > 0 || trail_us > 0),
                    "stream flicker: max_period_us and trail_us are positive, or 0 for off, and not both off");
     DAGR_CHECK_ARG(max_period_us == 0 || (min_period_us >= 1 && min_period_us <= max_period_us && max_period_us <= 1000000),
                    "stream flicker: the periods must satisfy 1 <= min_period_us <= max_period_us <= 1000000");
     DAGR_CHECK_ARG(max_period_us == 0 || (0 <= stop && stop < start && start <= max_count && max_count <= 255),
                    "stream flicker: the thresholds must satisfy 0 <= stop < start <= max_count <= 255");
-    DAGR_CHECK_ARG(state && n_out && status, "stream flicker: NULL pointer");
-    DAGR_CHECK_ARG(n_raw >= 0 && n_raw <= max_push, "stream flicker: max_push < n_raw");
-    DAGR_CHECK_ARG(n_raw == 0 || (xy_raw && t_raw && p_raw && batch_raw && xy_out && t_out && p_out && batch_out),
-                   "stream flicker: NULL input or output");
-    DAGR_CHECK_ARG(((uintptr_t)xy_raw & 3) == 0 && ((uintptr_t)xy_out & 3) == 0, "stream flicker: xy must be 4-byte aligned");
+    const std::string complaint = push_args_complaint("stream flicker", state, n_out, status, n_raw, max_push, xy_raw, t_raw,
+                                                      p_raw, batch_raw, xy_out, t_out, p_out, batch_out);
+    DAGR_CHECK_ARG(complaint.empty(), complaint);
     hipStream_t stream = (hipStream_t)stream_;
-    Flicker f;
     const int64_t pixels = (int64_t)sensor_w * sensor_h;
-    carve_flicker(B, pixels, max_push, (char *)state, &f, false);
-    DAGR_CHECK_ARG(state_bytes >= f.tmp_offset + 256, "stream flicker: state smaller than dagr_stream_flicker_bytes");
+    const Flicker f = carve_flicker(B, pixels, max_push, state, state_bytes);
+    DAGR_CHECK_ARG(push_state_holds(f.s), "stream flicker: state smaller than dagr_stream_flicker_bytes");
     if (n_raw == 0) {
         DAGR_CHECK_HIP(hipMemsetAsync(n_out, 0, 4, stream));
         return DAGR_OK;
     }
-    f.sort_tmp_bytes = state_bytes - f.tmp_offset;
     const int n = (int)n_raw, bits = key_bits((int64_t)B * pixels);
     const unsigned grid = (unsigned)ceil_div(n_raw, kBlock);
     const uint32_t sentinel = (uint32_t)((int64_t)B * pixels);
     const FlickerRule rule{min_period_us, max_period_us, trail_us, start, stop, max_count};
-    size_t tmp = 0;
-    DAGR_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, tmp, f.key_in, f.key_out, f.idx_in, f.idx_out, (size_t)n, 0u,
-                                             (unsigned)bits, stream));
-    DAGR_CHECK_ARG(tmp <= f.sort_tmp_bytes, "stream flicker: the sort asks for more temporary storage than the state holds");
-    tmp = f.sort_tmp_bytes;
-    if (batch_is_int64)
-        k_flicker_keys<int64_t><<<grid, kBlock, 0, stream>>>((const int32_t *)xy_raw, (const int64_t *)batch_raw, n, B,
-                                                            sensor_w, sensor_h, f.key_in, f.idx_in, status);
-    else
-        k_flicker_keys<int32_t><<<grid, kBlock, 0, stream>>>((const int32_t *)xy_raw, (const int32_t *)batch_raw, n, B,
-                                                            sensor_w, sensor_h, f.key_in, f.idx_in, status);
+    const int32_t *xy = (const int32_t *)xy_raw;
+    DAGR_CHECK_ARG(sort_push_fits(f.s, n, bits), "stream flicker: the sort asks for more temporary storage than the state holds");
+    with_batch(batch_raw, batch_is_int64, [&](auto *batch) {
+        k_flicker_keys<<<grid, kBlock, 0, stream>>>(xy, batch, n, B, sensor_w, sensor_h, f.s.key_in, f.s.idx_in, status);
+    });
     DAGR_CHECK_LAUNCH();
-    DAGR_CHECK_HIP(rocprim::radix_sort_pairs(f.sort_tmp, tmp, f.key_in, f.key_out, f.idx_in, f.idx_out, (size_t)n, 0u,
-                                             (unsigned)bits, stream));
-    k_flicker_walk<<<grid, kBlock, 0, stream>>>(f.key_out, f.idx_out, n, sentinel, t_raw, p_raw, rule, f.t_edge, f.t_pass,
-                                                f.word, f.flag, f.outcome);
+    DAGR_CHECK_HIP(sort_push(f.s, n, bits, stream));
+    k_flicker_walk<<<grid, kBlock, 0, stream>>>(f.s.key_out, f.s.idx_out, n, sentinel, t_raw, p_raw, rule, f.t_edge, f.t_pass,
+                                                f.word, f.s.flag, f.outcome);
     DAGR_CHECK_LAUNCH();
-    DAGR_CHECK_HIP(exclusive_scan_i32_chained(f.flag, f.offs, n_raw, f.scan_state, false, stream));
-    if (batch_is_int64)
-        k_flicker_finish<int64_t><<<grid, kBlock, 0, stream>>>(f.flag, f.offs, f.outcome, n, B, (const int32_t *)xy_raw, t_raw,
-                                                              p_raw, (const int64_t *)batch_raw, (int32_t *)xy_out, t_out,
-                                                              p_out, batch_out, n_out, lane_flicker, lane_trail);
-    else
-        k_flicker_finish<int32_t><<<grid, kBlock, 0, stream>>>(f.flag, f.offs, f.outcome, n, B, (const int32_t *)xy_raw, t_raw,
-                                                              p_raw, (const int32_t *)batch_raw, (int32_t *)xy_out, t_out,
-                                                              p_out, batch_out, n_out, lane_flicker, lane_trail);
+    DAGR_CHECK_HIP(exclusive_scan_i32_chained(f.s.flag, f.s.offs, n_raw, f.s.scan_state, false, stream));
+    with_batch(batch_raw, batch_is_int64, [&](auto *batch) {
+        k_flicker_finish<<<grid, kBlock, 0, stream>>>(f.s.flag, f.s.offs, f.outcome, n, B, xy, t_raw, p_raw, batch,
+                                                      (int32_t *)xy_out, t_out, p_out, batch_out, n_out, lane_flicker,
+                                                      lane_trail);
+    });
     DAGR_CHECK_LAUNCH();
     return DAGR_OK;
 }
+

@@ -413,6 +413,66 @@ def flicker_maps_from_state(state, B, sensor_w, sensor_h):
                 blocking=((word >> 8) & 1).astype(bool), t_pass=t_pass, p_pass=polarity[(word >> 11) & 3])
 
 
+def _state_buffer(device, entry, *sizes):
+    """An uninitialised device buffer of the bytes ``entry(*sizes)`` asks for (a ``dagr_*_bytes`` entry, by name); sizes it
+    refuses (0) are raised under its name."""
+    nbytes = getattr(_lib.lib(), entry)(*sizes)
+    if nbytes == 0:
+        raise RuntimeError(f"{entry}({', '.join(str(v) for v in sizes)}): out of range")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+class _PushStage:
+    """One stage a stream's pushes pass through: the entry ``dagr_<entry>`` on a state of the family ``dagr_<family>``
+    (``_bytes``, ``_reset``), which holds the stage's maps in its first ``carried`` bytes and behind them the scratch of a
+    largest push.  Owns the state, the push size ``cap`` it is sized for, the five output tensors ``out`` (xy, t, p, batch,
+    count) and the device-side ``counters`` the entry adds to.  ``geometry`` is what ``_bytes`` / ``_reset`` take between
+    ``B`` and the push size, ``rule`` what the entry takes between the push size and the push; ``out_rows(cap)`` the rows of
+    the outputs (default: ``cap``)."""
+
+    def __init__(self, B, device, status, family, entry, geometry, carried, rule, counters=(), out_rows=None):
+        self.B, self.device, self.status = B, device, status
+        self.family, self.entry, self.geometry, self.carried = family, entry, tuple(geometry), int(carried)
+        self.rule, self.counters, self.out_rows = tuple(rule), list(counters), out_rows or (lambda cap: cap)
+        self.state, self.cap, self.out = None, 0, None
+
+    def grow(self, n):
+        """State and outputs for pushes of ``n`` rows; the maps are carried over."""
+        if n <= self.cap:
+            return
+        new = _state_buffer(self.device, f"dagr_{self.family}_bytes", self.B, *self.geometry, n)
+        old, self.state, self.cap = self.state, new, n
+        self.reset(counters=False)
+        if old is not None:
+            new[:self.carried].copy_(old[:self.carried])
+        rows, dev = self.out_rows(n), self.device
+        if self.out is None or rows != int(self.out[1].shape[0]):
+            self.out = (torch.empty((rows, 2), dtype=torch.int16, device=dev), torch.empty((rows,), dtype=torch.int64, device=dev),
+                        torch.empty((rows,), dtype=torch.int8, device=dev), torch.empty((rows,), dtype=torch.int32, device=dev),
+                        torch.zeros((1,), dtype=torch.int32, device=dev))
+
+    def reset(self, counters=True):
+        """The maps as new; with ``counters``, nothing counted."""
+        reset = getattr(_lib.lib(), f"dagr_{self.family}_reset")
+        _lib.check(reset(_lib.ptr(self.state), self.state.numel(), self.B, *self.geometry, self.cap,
+                         _lib.cur_stream(self.device)), self.family + "_reset")
+        for c in self.counters if counters else ():
+            c.zero_()
+
+    def run(self, n, push):
+        """The entry on a push of ``n`` rows (``push``: its arguments between the rule and the outputs); returns ``out``."""
+        if n > self.cap:
+            self.grow(max(n, 2 * self.cap))
+        P = _lib.ptr
+        _lib.check(getattr(_lib.lib(), "dagr_" + self.entry)(
+            P(self.state), self.state.numel(), self.B, self.cap, *self.rule, *push, *(P(o) for o in self.out),
+            *(P(c) for c in self.counters), P(self.status), _lib.cur_stream(self.device)), self.entry)
+        return self.out
+
+    def carried_bytes(self):
+        return self.state[:self.carried]
+
+
 class StreamState:
     """Device-side state of one event stream (``dagr_stream_stage``): the raw events of the running window in two sets
     written alternately, the lanes' bounds and reference instants, the stream's status word, the per-lane counts of the
@@ -477,14 +537,11 @@ class StreamState:
         self._known = np.zeros((self.B,), np.int64)     # the last counts read
         self._since = 0                                 # events pushed since
         self._fresh = True                              # _known belongs to the last step staged
+        self.stages = {}                                # the enabled push stages (_PushStage), under their options' names:
         self.front = None                               # (fx, fy, W_in, H_in, W, H) of a downsampling stream
-        self.front_state, self.front_cap, self.front_out = None, 0, None
-        self.noise = None                               # (W_in, H_in, denoise_us or 0, refractory_us or 0) of a filtering stream
-        self.noise_state, self.noise_cap, self.noise_out, self.lane_filtered = None, 0, None, None
-        self.flick = None                               # (W_in, H_in, min_period, max_period, start, stop, max_count, trail_us)
-        self.flick_state, self.flick_cap, self.flick_out, self.lane_suppressed = None, 0, None, None
-        self.words = None                               # (format, W_in, H_in, max_decoded or None) of a decoding stream
-        self.words_state, self.words_cap, self.words_out, self.lane_decoded = None, 0, None, None
+        self.noise, self.lane_filtered = None, None     # (W_in, H_in, denoise_us or 0, refractory_us or 0) of a filtering stream
+        self.flick, self.lane_suppressed = None, None   # (W_in, H_in, min_period, max_period, start, stop, max_count, trail_us)
+        self.words, self.lane_decoded = None, None      # (format, W_in, H_in, max_decoded or None) of a decoding stream
         self.track = None                               # the options of a tracking stream (dagr.streaming._track_options)
         self.track_state, self.lane_untracked, self.track_ids, self.track_hits = None, None, None, None
         self.motion = None                              # the options of its motion model (dagr.streaming._motion_options)
@@ -520,18 +577,12 @@ class StreamState:
         # name: every call looks its function up on the library
         self._track_family = "stream_track" if motion is None else "stream_track_cv"
         M, dev = self.track["max_tracks"], self.device
-        nbytes = self._track_fn("_bytes")(self.B, M)
-        if nbytes == 0:
-            raise RuntimeError(f"dagr_{self._track_family}_bytes({self.B}, {M}): out of range")
-        self.track_state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.track_state = _state_buffer(dev, f"dagr_{self._track_family}_bytes", self.B, M)
         self.lane_untracked = torch.zeros((self.B,), dtype=torch.int64, device=dev)
         if rescue is not None:
             self.lane_rescued = torch.zeros((self.B,), dtype=torch.int64, device=dev)
         if assign is not None:
-            ws_bytes = _lib.lib().dagr_stream_track_optimal_bytes(self.B, M)
-            if ws_bytes == 0:
-                raise RuntimeError(f"dagr_stream_track_optimal_bytes({self.B}, {M}): out of range")
-            self.assign_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            self.assign_ws = _state_buffer(dev, "dagr_stream_track_optimal_bytes", self.B, M)
         if motion is not None:
             self.coast = (torch.zeros((self.B,), dtype=torch.int32, device=dev),            # n_coast
                           torch.zeros((self.B, M), dtype=torch.int64, device=dev),          # coast_id
@@ -612,20 +663,13 @@ class StreamState:
         self._last_det, self._scored = (det, n_keep), False
 
     # ------------------------------------------------------------------------------------ scoring the tracks
-    # the lane's words behind the table, in the order include/dagr_hip.h documents
-    SCORE_WORDS = ("n_objects", "steps", "gt", "hyp", "match", "miss", "false_pos", "switch", "frag", "kept", "iou_q",
-                   "unscored_gt", "unscored_hyp")
-
     def enable_score(self, options):
         """``run_score`` scores a step's track ids against labelled boxes (``dagr_stream_score``): ``options`` as
         ``dagr.streaming._score_options`` returns them, on a stream that tracks.  Allocates the lanes' tables, empty."""
         if self.track is None:
             raise RuntimeError("enable_score: the stream does not track (enable_track comes first)")
         self.score = dict(options)
-        nbytes = _lib.lib().dagr_stream_score_bytes(self.B, self.score["max_objects"])
-        if nbytes == 0:
-            raise RuntimeError(f"dagr_stream_score_bytes({self.B}, {self.score['max_objects']}): out of range")
-        self.score_state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.score_state = _state_buffer(self.device, "dagr_stream_score_bytes", self.B, self.score["max_objects"])
         self._reset_score()
 
     def _reset_score(self):
@@ -676,10 +720,6 @@ class StreamState:
         return self.gt_match, self.gt_flags
 
     # ------------------------------------------------------------------------------------ IDF1 behind the scorer
-    # the lane's words and the solve's result words, in the order include/dagr_hip.h documents
-    IDENTITY_WORDS = ("n_tracks", "n_objects", "gt_frames", "hyp_frames", "dup_hyp", "unlisted_hyp", "pairs", "steps")
-    IDENTITY_RESULT = ("idtp", "idfn", "idfp", "gt_frames", "hyp_frames", "n_objects", "n_tracks", "dup_hyp", "unlisted_hyp")
-
     def enable_identity(self, options):
         """``run_score`` also counts the overlaps of object identities with track ids (``dagr_stream_identity``):
         ``options`` as ``dagr.streaming._identity_options`` returns them, on a stream that scores.  Allocates the lanes'
@@ -687,14 +727,12 @@ class StreamState:
         if self.score is None:
             raise RuntimeError("enable_identity: the stream does not score (enable_score comes first)")
         self.identity = dict(options)
-        L, M, T = _lib.lib(), self.score["max_objects"], self.identity["max_tracks"]
-        nbytes, ws = L.dagr_stream_identity_bytes(self.B, M, T), L.dagr_assign_workspace_bytes(self.B, M, T)
-        if nbytes == 0 or ws == 0:
-            raise RuntimeError(f"dagr_stream_identity_bytes({self.B}, {M}, {T}): out of range")
-        self.identity_state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self.identity_ws = torch.empty(ws, dtype=torch.uint8, device=self.device)
+        M, T = self.score["max_objects"], self.identity["max_tracks"]
+        self.identity_state = _state_buffer(self.device, "dagr_stream_identity_bytes", self.B, M, T)
+        self.identity_ws = _state_buffer(self.device, "dagr_assign_workspace_bytes", self.B, M, T)
         self.obj_track = torch.zeros((self.B, M), dtype=torch.int64, device=self.device)
-        self.identity_result = torch.zeros((self.B, len(self.IDENTITY_RESULT)), dtype=torch.int64, device=self.device)
+        self.identity_result = torch.zeros((self.B, _lib.DEFINES["DAGR_IDENTITY_RESULT_WORDS"]), dtype=torch.int64,
+                                           device=self.device)
         self._reset_identity()
 
     def _reset_identity(self):
@@ -739,18 +777,15 @@ class StreamState:
         if self.identity is None:
             raise RuntimeError("enable_hota: the stream keeps no identity state (enable_identity comes first)")
         L, M, T, I = _lib.lib(), self.score["max_objects"], self.identity["max_tracks"], int(options["max_instants"])
-        nbytes, ws = L.dagr_stream_hota_bytes(self.B, M, T, I), L.dagr_stream_hota_workspace_bytes(self.B, M, T, I)
-        if nbytes == 0 or ws == 0:
-            raise RuntimeError(f"dagr_stream_hota_bytes({self.B}, {M}, {T}, {I}): out of range")
-        limit = _lib.DEFINES["DAGR_HOTA_MAX_STATE_BYTES"]
+        nbytes, limit = L.dagr_stream_hota_bytes(self.B, M, T, I), _lib.DEFINES["DAGR_HOTA_MAX_STATE_BYTES"]
         if nbytes > limit:
             raise ValueError(f"hota: batch_size = {self.B}, score max_objects = {M}, identity max_tracks = {T} and hota "
                              f"max_instants = {I} need a state of {nbytes} bytes, above DAGR_HOTA_MAX_STATE_BYTES = {limit} "
                              f"(the log takes {24 * _lib.DEFINES['DAGR_HOTA_LOG_ENTRIES']} bytes an instant and lane, the 19 "
                              f"mc tables {76 * M * T} bytes a lane): lower max_instants, max_objects or max_tracks")
-        self.hota = dict(options)
-        self.hota_state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self.hota_ws = torch.empty(ws, dtype=torch.uint8, device=self.device)
+        state = _state_buffer(self.device, "dagr_stream_hota_bytes", self.B, M, T, I)
+        self.hota_ws = _state_buffer(self.device, "dagr_stream_hota_workspace_bytes", self.B, M, T, I)
+        self.hota, self.hota_state = dict(options), state
         self._reset_hota()
 
     def _reset_hota(self):
@@ -838,6 +873,18 @@ class StreamState:
             raise RuntimeError("this stream has no motion model (motion=): nothing coasts")
         return self.coast
 
+    # ------------------------------------------------------------------------------------ the push stages
+    def _enable(self, name, *description, **more):
+        """The stage ``name`` (as its option tuple is called), with the scratch of a push of 4096 rows to begin with."""
+        self.stages[name] = _PushStage(self.B, self.device, self.status, *description, **more)
+        self.stages[name].grow(4096)
+
+    def _push(self, name, xy, t, p, batch, n=None):
+        """A push of events (their first ``n`` rows; None: all) through the stage ``name``: ``(xy, t, p, batch int32, count
+        int32[1])`` of the survivors, on the device, valid until the next push."""
+        n, P = int(t.shape[0]) if n is None else n, _lib.ptr
+        return self.stages[name].run(n, (P(xy), P(t), P(p), P(batch), 1 if batch.dtype == torch.int64 else 0, n))
+
     # ------------------------------------------------------------------------------------ sensor noise
     def enable_denoise(self, sensor_w, sensor_h, denoise_us=None, refractory_us=None):
         """Pushes go through ``dagr_stream_denoise`` first: a ``sensor_w x sensor_h`` stamp map per lane, ``denoise_us`` /
@@ -845,44 +892,14 @@ class StreamState:
         if denoise_us is None and refractory_us is None:
             raise ValueError("enable_denoise: denoise_us and refractory_us are both None")
         self.noise = (int(sensor_w), int(sensor_h), int(denoise_us or 0), int(refractory_us or 0))
-        self.noise_state, self.noise_cap, self.noise_out = None, 0, None
         self.lane_filtered = torch.zeros((self.B,), dtype=torch.int64, device=self.device)
-        self.grow_denoise(4096)
-
-    def grow_denoise(self, n):
-        """Scratch and survivors' buffers for pushes of ``n`` events; the stamp maps are carried over."""
-        if n <= self.noise_cap:
-            return
-        L, stream = _lib.lib(), _lib.cur_stream(self.device)
-        sensor_w, sensor_h = self.noise[:2]
-        nbytes = L.dagr_stream_denoise_bytes(self.B, sensor_w, sensor_h, n)
-        if nbytes == 0:
-            raise RuntimeError(f"dagr_stream_denoise_bytes({self.B}, {sensor_w}, {sensor_h}, {n}): out of range")
-        new = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        _lib.check(L.dagr_stream_denoise_reset(_lib.ptr(new), nbytes, self.B, sensor_w, sensor_h, n, stream),
-                   "stream_denoise_reset")
-        if self.noise_state is not None:
-            maps = 8 * self.B * sensor_w * sensor_h
-            new[:maps].copy_(self.noise_state[:maps])
-        self.noise_state, self.noise_cap = new, n
-        dev = self.device
-        self.noise_out = (torch.empty((n, 2), dtype=torch.int16, device=dev), torch.empty((n,), dtype=torch.int64, device=dev),
-                          torch.empty((n,), dtype=torch.int8, device=dev), torch.empty((n,), dtype=torch.int32, device=dev),
-                          torch.zeros((1,), dtype=torch.int32, device=dev))
+        self._enable("noise", "stream_denoise", "stream_denoise", self.noise[:2], 8 * self.B * self.noise[0] * self.noise[1],
+                     self.noise, [self.lane_filtered])
 
     def denoise(self, xy, t, p, batch):
-        """``dagr_stream_denoise`` on a push: ``(xy, t, p, batch int32, count int32[1])`` of the survivors, on the device,
-        valid until the next push; rows from the count up to the push's size are lane-less (lane -1 at pixel (0, 0))."""
-        n = int(t.shape[0])
-        if n > self.noise_cap:
-            self.grow_denoise(max(n, 2 * self.noise_cap))
-        sensor_w, sensor_h, denoise_us, refractory_us = self.noise
-        P, o = _lib.ptr, self.noise_out
-        _lib.check(_lib.lib().dagr_stream_denoise(
-            P(self.noise_state), self.noise_state.numel(), self.B, self.noise_cap, sensor_w, sensor_h, denoise_us, refractory_us,
-            P(xy), P(t), P(p), P(batch), 1 if batch.dtype == torch.int64 else 0, n, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]),
-            P(self.lane_filtered), P(self.status), _lib.cur_stream(self.device)), "stream_denoise")
-        return o
+        """``dagr_stream_denoise`` on a push (``_push``); rows from the count up to the push's size are lane-less (lane -1
+        at pixel (0, 0))."""
+        return self._push("noise", xy, t, p, batch)
 
     def filtered(self):
         """Per-lane events the noise filter has removed, int64 [B]; zeros without the filter (synchronises)."""
@@ -896,7 +913,7 @@ class StreamState:
         if self.noise is None:
             raise RuntimeError("this stream does not filter noise (denoise_us / refractory_us): it has no stamp maps")
         sensor_w, sensor_h = self.noise[:2]
-        return self.noise_state[:8 * self.B * sensor_w * sensor_h].view(torch.int64).view(self.B, sensor_h, sensor_w).cpu().numpy()
+        return self.stages["noise"].carried_bytes().view(torch.int64).view(self.B, sensor_h, sensor_w).cpu().numpy()
 
     # ------------------------------------------------------------------------------------ flicker and trails
     def enable_flicker(self, sensor_w, sensor_h, flicker=None, trail_us=None):
@@ -911,45 +928,14 @@ class StreamState:
             periods = flicker_periods(flicker)
             thresholds = (int(flicker["start"]), int(flicker["stop"]), int(flicker["max_count"]))
         self.flick = (int(sensor_w), int(sensor_h), *periods, *thresholds, int(trail_us or 0))
-        self.flick_state, self.flick_cap, self.flick_out = None, 0, None
         self.lane_suppressed = torch.zeros((2, self.B), dtype=torch.int64, device=self.device)      # flicker, trail
-        self.grow_flicker(4096)
-
-    def grow_flicker(self, n):
-        """Scratch and survivors' buffers for pushes of ``n`` events; the per-pixel maps are carried over."""
-        if n <= self.flick_cap:
-            return
-        L, stream = _lib.lib(), _lib.cur_stream(self.device)
-        sensor_w, sensor_h = self.flick[:2]
-        nbytes = L.dagr_stream_flicker_bytes(self.B, sensor_w, sensor_h, n)
-        if nbytes == 0:
-            raise RuntimeError(f"dagr_stream_flicker_bytes({self.B}, {sensor_w}, {sensor_h}, {n}): out of range")
-        new = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        _lib.check(L.dagr_stream_flicker_reset(_lib.ptr(new), nbytes, self.B, sensor_w, sensor_h, n, stream),
-                   "stream_flicker_reset")
-        if self.flick_state is not None:
-            maps = flicker_map_bytes(self.B, sensor_w, sensor_h)
-            new[:maps].copy_(self.flick_state[:maps])
-        self.flick_state, self.flick_cap = new, n
-        dev = self.device
-        self.flick_out = (torch.empty((n, 2), dtype=torch.int16, device=dev), torch.empty((n,), dtype=torch.int64, device=dev),
-                          torch.empty((n,), dtype=torch.int8, device=dev), torch.empty((n,), dtype=torch.int32, device=dev),
-                          torch.zeros((1,), dtype=torch.int32, device=dev))
+        self._enable("flick", "stream_flicker", "stream_flicker", self.flick[:2], flicker_map_bytes(self.B, *self.flick[:2]),
+                     self.flick, [self.lane_suppressed[0], self.lane_suppressed[1]])
 
     def flicker(self, xy, t, p, batch):
-        """``dagr_stream_flicker`` on a push: ``(xy, t, p, batch int32, count int32[1])`` of the survivors, on the device,
-        valid until the next push; rows from the count up to the push's size are lane-less (lane -1 at pixel (0, 0))."""
-        n = int(t.shape[0])
-        if n > self.flick_cap:
-            self.grow_flicker(max(n, 2 * self.flick_cap))
-        sensor_w, sensor_h, *rule = self.flick
-        P, o = _lib.ptr, self.flick_out
-        _lib.check(_lib.lib().dagr_stream_flicker(
-            P(self.flick_state), self.flick_state.numel(), self.B, self.flick_cap, sensor_w, sensor_h, *rule,
-            P(xy), P(t), P(p), P(batch), 1 if batch.dtype == torch.int64 else 0, n, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]),
-            P(self.lane_suppressed[0]), P(self.lane_suppressed[1]), P(self.status), _lib.cur_stream(self.device)),
-            "stream_flicker")
-        return o
+        """``dagr_stream_flicker`` on a push (``_push``); rows from the count up to the push's size are lane-less (lane -1
+        at pixel (0, 0))."""
+        return self._push("flick", xy, t, p, batch)
 
     def suppressed(self):
         """Per-lane events the flicker stage and the trail stage have removed, ``(int64 [B], int64 [B])``; zeros without the
@@ -965,7 +951,7 @@ class StreamState:
         synchronises)."""
         if self.flick is None:
             raise RuntimeError("this stream has no flicker / trail filter (flicker / trail_us): it has no per-pixel state")
-        return flicker_maps_from_state(self.flick_state, self.B, *self.flick[:2])
+        return flicker_maps_from_state(self.stages["flick"].state, self.B, *self.flick[:2])
 
     # ------------------------------------------------------------------------------------ camera words
     def enable_decode(self, format, sensor_w, sensor_h, max_decoded=None, t_base=None):
@@ -974,46 +960,21 @@ class StreamState:
         the largest push so far, ``events_per_word`` each), ``t_base`` int64 [B] on the host or None."""
         self.words = (int(format), int(sensor_w), int(sensor_h), None if max_decoded is None else int(max_decoded))
         self.words_per = 12 if int(format) == _lib.DEFINES["DAGR_DECODE_EVT3"] else 1
-        self.words_state, self.words_cap, self.words_out = None, 0, None
         self.words_t_base = None if t_base is None else torch.as_tensor(np.asarray(t_base, np.int64)).to(self.device)
         self.lane_decoded = torch.zeros((self.B, 4), dtype=torch.int64, device=self.device)
-        self.grow_decode(4096)
-
-    def grow_decode(self, n):
-        """Scratch for pushes of ``n`` words and the decoded events' buffers; the lanes' states are carried over."""
-        if n <= self.words_cap:
-            return
-        L, stream = _lib.lib(), _lib.cur_stream(self.device)
-        nbytes = L.dagr_stream_decode_bytes(self.B, n)
-        if nbytes == 0:
-            raise RuntimeError(f"dagr_stream_decode_bytes({self.B}, {n}): out of range")
-        new = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        _lib.check(L.dagr_stream_decode_reset(_lib.ptr(new), nbytes, self.B, n, stream), "stream_decode_reset")
-        if self.words_state is not None:
-            new[:64 * self.B].copy_(self.words_state[:64 * self.B])
-        self.words_state, self.words_cap = new, n
-        rows = self.words[3] if self.words[3] is not None else self.words_per * n
-        if self.words_out is None or rows != int(self.words_out[1].shape[0]):
-            dev = self.device
-            self.words_out = (torch.empty((rows, 2), dtype=torch.int16, device=dev), torch.empty((rows,), dtype=torch.int64, device=dev),
-                              torch.empty((rows,), dtype=torch.int8, device=dev), torch.empty((rows,), dtype=torch.int32, device=dev),
-                              torch.zeros((1,), dtype=torch.int32, device=dev))
+        # the state is sized by the words of a push, the decoded events' buffers by what those can decode
+        per, most = self.words_per, self.words[3]
+        self._enable("words", "stream_decode", "stream_decode", (), 64 * self.B, self.words[:3], [self.lane_decoded],
+                     out_rows=lambda n: per * n if most is None else most)
 
     def decode(self, words, word_end, t_base=None):
         """``dagr_stream_decode`` on a push of words (``words`` uint16 / uint32 bits, ``word_end`` int64 [B], both on the
         device): ``(xy, t, p, batch int32, count int32[1])`` of the decoded events, valid until the next push.  The arrays
         have ``max_out = decode_rows(n_words)`` rows; those from the count up are lane-less (lane -1 at pixel (0, 0))."""
-        n = int(words.shape[0])
-        if n > self.words_cap:
-            self.grow_decode(max(n, 2 * self.words_cap))
-        fmt, sensor_w, sensor_h, _ = self.words
-        P, o = _lib.ptr, self.words_out
+        n, P = int(words.shape[0]), _lib.ptr
         t_base = self.words_t_base if t_base is None else t_base
         rows = max(self.decode_rows(n), 1)
-        _lib.check(_lib.lib().dagr_stream_decode(
-            P(self.words_state), self.words_state.numel(), self.B, self.words_cap, fmt, sensor_w, sensor_h, P(words) if n else None,
-            P(word_end), n, P(t_base), rows, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(self.lane_decoded),
-            P(self.status), _lib.cur_stream(self.device)), "stream_decode")
+        o = self.stages["words"].run(n, (P(words) if n else None, P(word_end), n, P(t_base), rows))
         return o[0][:rows], o[1][:rows], o[2][:rows], o[3][:rows], o[4]
 
     def decode_rows(self, n_words):
@@ -1031,90 +992,40 @@ class StreamState:
         """The lanes' decoder states int64 [B, 8]: high, low, loops, y, base_x, pol, synced, 0 (a copy; synchronises)."""
         if self.words is None:
             raise RuntimeError("this stream does not decode camera words (decode=): it has no decoder state")
-        return self.words_state[:64 * self.B].view(torch.int64).view(self.B, 8).cpu().numpy()
+        return self.stages["words"].carried_bytes().view(torch.int64).view(self.B, 8).cpu().numpy()
 
     # ------------------------------------------------------------------------------------ raw sensor events
     def enable_front(self, fx, fy, sensor_w, sensor_h, width, height):
         """Pushes carry raw events of a ``sensor_w x sensor_h`` sensor, downsampled ``fx x fy`` on the device."""
         self.front = tuple(int(v) for v in (fx, fy, sensor_w, sensor_h, width, height))
-        self.front_state, self.front_cap, self.front_out = None, 0, None
-        self.grow_front(4096)
+        cells_w, cells_h = self._cells()
+        self._enable("front", "stream_front", "stream_downsample", (cells_w, cells_h), 4 * self.B * cells_w * cells_h,
+                     self.front)
 
     def _cells(self):
         fx, fy, sensor_w, sensor_h = self.front[:4]
         return sensor_w // fx, sensor_h // fy
 
-    def grow_front(self, n):
-        """Scratch and survivors' buffers for pushes of ``n`` raw events; the change maps are carried over."""
-        if n <= self.front_cap:
-            return
-        L, stream = _lib.lib(), _lib.cur_stream(self.device)
-        cells_w, cells_h = self._cells()
-        nbytes = L.dagr_stream_front_bytes(self.B, cells_w, cells_h, n)
-        if nbytes == 0:
-            raise RuntimeError(f"dagr_stream_front_bytes({self.B}, {cells_w}, {cells_h}, {n}): out of range")
-        new = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        _lib.check(L.dagr_stream_front_reset(_lib.ptr(new), nbytes, self.B, cells_w, cells_h, n, stream), "stream_front_reset")
-        if self.front_state is not None:
-            maps = 4 * self.B * cells_w * cells_h
-            new[:maps].copy_(self.front_state[:maps])
-        self.front_state, self.front_cap = new, n
-        dev = self.device
-        self.front_out = (torch.empty((n, 2), dtype=torch.int16, device=dev), torch.empty((n,), dtype=torch.int64, device=dev),
-                          torch.empty((n,), dtype=torch.int8, device=dev), torch.empty((n,), dtype=torch.int32, device=dev),
-                          torch.zeros((1,), dtype=torch.int32, device=dev))
-
     def downsample(self, xy, t, p, batch):
-        """``dagr_stream_downsample`` on a raw push: ``(xy, t, p, batch int32, count int32[1])`` of the survivors, on the
-        device, valid until the next push."""
-        n = int(t.shape[0])
-        if n > self.front_cap:
-            self.grow_front(max(n, 2 * self.front_cap))
-        fx, fy, sensor_w, sensor_h, width, height = self.front
-        P, o = _lib.ptr, self.front_out
-        _lib.check(_lib.lib().dagr_stream_downsample(
-            P(self.front_state), self.front_state.numel(), self.B, self.front_cap, fx, fy, sensor_w, sensor_h, width, height,
-            P(xy), P(t), P(p), P(batch), 1 if batch.dtype == torch.int64 else 0, n, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]),
-            P(self.status), _lib.cur_stream(self.device)), "stream_downsample")
-        return o
+        """``dagr_stream_downsample`` on a raw push (``_push``)."""
+        return self._push("front", xy, t, p, batch)
 
     def change_maps(self):
         """The lanes' change maps fp32[B, cells_h, cells_w] (a copy; synchronises)."""
         if self.front is None:
             raise RuntimeError("this stream does not downsample: it has no change maps")
         cells_w, cells_h = self._cells()
-        return self.front_state[:4 * self.B * cells_w * cells_h].view(torch.float32).view(self.B, cells_h, cells_w).cpu().numpy()
+        return self.stages["front"].carried_bytes().view(torch.float32).view(self.B, cells_h, cells_w).cpu().numpy()
 
     def _alloc(self, cap):
-        L = _lib.lib()
-        nbytes = L.dagr_stream_state_bytes(self.B, cap)
-        if nbytes == 0:
-            raise RuntimeError(f"dagr_stream_state_bytes({self.B}, {cap}): out of range")
-        return torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return _state_buffer(self.device, "dagr_stream_state_bytes", self.B, cap)
 
     def reset(self):
         if self.state is not None:
             _lib.check(_lib.lib().dagr_stream_reset(_lib.ptr(self.state), self.B, self.cap, _lib.cur_stream(self.device)),
                        "stream_reset")
-        if self.front_state is not None:
-            cells_w, cells_h = self._cells()
-            _lib.check(_lib.lib().dagr_stream_front_reset(_lib.ptr(self.front_state), self.front_state.numel(), self.B, cells_w,
-                                                          cells_h, self.front_cap, _lib.cur_stream(self.device)),
-                       "stream_front_reset")
-        if self.words_state is not None:
-            _lib.check(_lib.lib().dagr_stream_decode_reset(_lib.ptr(self.words_state), self.words_state.numel(), self.B,
-                                                           self.words_cap, _lib.cur_stream(self.device)), "stream_decode_reset")
-            self.lane_decoded.zero_()
-        if self.noise_state is not None:
-            _lib.check(_lib.lib().dagr_stream_denoise_reset(_lib.ptr(self.noise_state), self.noise_state.numel(), self.B,
-                                                            self.noise[0], self.noise[1], self.noise_cap,
-                                                            _lib.cur_stream(self.device)), "stream_denoise_reset")
-            self.lane_filtered.zero_()
-        if self.flick_state is not None:
-            _lib.check(_lib.lib().dagr_stream_flicker_reset(_lib.ptr(self.flick_state), self.flick_state.numel(), self.B,
-                                                            self.flick[0], self.flick[1], self.flick_cap,
-                                                            _lib.cur_stream(self.device)), "stream_flicker_reset")
-            self.lane_suppressed.zero_()
+        for stage in self.stages.values():
+            stage.reset()
         if self.track_state is not None:
             self._reset_track()
         if self.score_state is not None:
@@ -2428,22 +2339,20 @@ class WindowEngine:
         """One step of an event stream (``StreamState`` ``st``): ``_forward_window_graph`` with ``dagr_stream_stage`` in
         place of ``dagr_stage_window``.  The new raw events (``xy`` int16[n,2], ``t`` int64[n] absolute us, ``p`` int8[n],
         ``batch`` int32/int64[n] sorted lanes, ``t_now`` int64[B] or None; all on the device) join the window kept in
-        ``st`` -- through ``dagr_stream_downsample`` first when the stream carries raw sensor events (``st.front``) --; two launches write the next window into the static input buffers and its count to device memory, and
+        ``st``; two launches write the next window into the static input buffers and its count to device memory, and
         the window runs on them -- the captured graph in latency mode, the same body launch by launch otherwise.  No host
         synchronisation: the host knows an upper bound of the window's size only (``st.bound()``), which is what the
-        buffers are sized by.  A capped stream (``st.max_lane_events = N``) goes through ``dagr_stream_stage_capped``; its
-        windows never exceed ``B * N``, which the buffers meet once -- no growth and no re-capture after its first step.
-        A filtering stream (``st.noise``) runs ``dagr_stream_denoise`` on the push before anything else and stages what is
-        left through the ``_dev`` entries, with the unfiltered push as the clock.
-        A stream with the flicker / trail filters (``st.flick``) runs ``dagr_stream_flicker`` in front of that -- behind the
-        decoder, before the noise filter, the front and the stage, each of which takes all rows handed on, those behind the
-        count being lane-less.
-        A decoding stream (``st.words``) takes ``words`` (the camera's words as int16 / int32 bit patterns) and ``word_end``
-        (int64 [B], the cumulative end of every lane's run) in place of the events: ``dagr_stream_decode`` first, then the
-        filter and the front when enabled -- on all ``max_out`` rows, those behind the decoder's count being lane-less --,
-        and the stage through the ``_dev_clock`` entries with the decoded push and its device-side count as the clock.  The
-        host's bound grows by ``min(max_decoded, 12 * n_words)`` (EVT 3.0) or ``n_words`` (EVT 2.0) per step, so a decoding
-        stream that is never read back should be capped (``max_lane_events``).
+        buffers are sized by.
+        The push passes through the stages the stream has enabled, in this order: the decoder (``st.words``; the push is
+        then ``words``, the camera's words as int16 / int32 bit patterns, and ``word_end`` int64 [B], the cumulative end of
+        every lane's run, in place of the events), the flicker / trail filters (``st.flick``), the noise filter
+        (``st.noise``) and the downsampling front (``st.front``).  Each takes ALL rows handed on -- those behind the count
+        of the stage in front are lane-less -- and leaves its survivors and their count on the device.  The staging entry
+        follows from the chain: ``dagr_stream_stage_dev_clock`` behind the decoder (the decoded push and its device-side
+        count are the clock), ``dagr_stream_stage_dev`` behind any other stage (the push itself is the clock),
+        ``dagr_stream_stage`` with none; ``_capped`` with ``st.max_lane_events = N``, whose windows never exceed ``B * N``,
+        which the buffers meet once -- no growth and no re-capture after the first step.  The host's bound of a decoding
+        stream grows by ``st.decode_rows(n_words)`` per step, so one that is never read back should be capped.
         A tracking stream (``st.track``) ends the step with ``dagr_stream_track`` on the step's detections and the reference
         instants the staging left: one plain launch on the same stream, outside the captured graphs, so every mode and
         body is covered without a re-capture; ``st.track_ids`` / ``st.track_hits`` hold the result.  With a motion model
@@ -2504,64 +2413,39 @@ class WindowEngine:
         outputs = (P(self.in_pos), P(self.in_feat), P(self.in_batch), P(self.n_dev), P(st.lane_count), P(st.status),
                    _lib.cur_stream(self.device))
         cap_args = () if N is None else (N, P(st.lane_dropped))
-        if decoding:                # camera words: decode, then the fronts on all rows, then the stage with the decoded push as
-            sensor = (self.W, self.H) if st.front is None else st.front[2:4]       # the clock, its length on the device
-            if st.words[1:3] != sensor or (st.noise is not None and st.noise[:2] != sensor) or \
-                    (st.flick is not None and st.flick[:2] != sensor):
-                raise RuntimeError(f"the stream decodes a {st.words[1]} x {st.words[2]} sensor, its fronts take "
+        # every stage sees the same sensor: the front's, or without one the engine's
+        sensor = (self.W, self.H) if st.front is None else st.front[2:4]
+        filters = [f for f in (st.flick, st.noise) if f is not None]
+        if decoding and any(s[:2] != sensor for s in (st.words[1:3], *filters)):
+            raise RuntimeError(f"the stream decodes a {st.words[1]} x {st.words[2]} sensor, its fronts take "
+                               f"{sensor[0]} x {sensor[1]} pixels")
+        for filt in () if decoding else filters:
+            if filt[:2] != sensor:
+                raise RuntimeError(f"the stream filters a {filt[0]} x {filt[1]} sensor, its pushes carry "
                                    f"{sensor[0]} x {sensor[1]} pixels")
-            if st.front is not None and st.front[4:] != (self.W, self.H):
-                raise RuntimeError(f"the stream downsamples to {st.front[4]} x {st.front[5]}, the engine runs "
-                                   f"{self.W} x {self.H}")
-            c_xy, c_t, c_p, c_batch, c_n = st.decode(words, word_end)
-            rows = int(c_t.shape[0])
-            s_xy, s_t, s_p, s_batch, s_n = c_xy, c_t, c_p, c_batch, c_n
-            if st.flick is not None:
-                s_xy, s_t, s_p, s_batch, s_n = st.flicker(s_xy, s_t, s_p, s_batch)
-            if st.noise is not None:
-                s_xy, s_t, s_p, s_batch, s_n = st.denoise(s_xy[:rows], s_t[:rows], s_p[:rows], s_batch[:rows])
-            if st.front is not None:
-                s_xy, s_t, s_p, s_batch, s_n = st.downsample(s_xy[:rows], s_t[:rows], s_p[:rows], s_batch[:rows])
-            stage = L.dagr_stream_stage_dev_clock if N is None else L.dagr_stream_stage_dev_clock_capped
-            _lib.check(stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(s_xy), P(s_t), P(s_p),
-                             P(s_batch), P(s_n), rows, P(c_t), P(c_batch), 0, P(c_n), rows, P(t_now), st.window_us, *cap_args,
-                             *outputs), "stream_stage_dev_clock")
-        elif st.noise is not None or st.flick is not None:    # the filters first; the unfiltered push stays the clock
-            sensor = (self.W, self.H) if st.front is None else st.front[2:4]
-            for filt in (st.flick, st.noise):
-                if filt is not None and filt[:2] != sensor:
-                    raise RuntimeError(f"the stream filters a {filt[0]} x {filt[1]} sensor, its pushes carry "
-                                       f"{sensor[0]} x {sensor[1]} pixels")
-            s_xy, s_t, s_p, s_batch = xy, t, p, batch
-            if st.flick is not None:  # flicker / trail in front of the noise filter: flicker would support noise there
-                s_xy, s_t, s_p, s_batch, s_n = st.flicker(s_xy, s_t, s_p, s_batch)
-            if st.noise is not None:  # all n_new rows, of which those behind the count in front are lane-less
-                s_xy, s_t, s_p, s_batch, s_n = st.denoise(s_xy[:n_new], s_t[:n_new], s_p[:n_new], s_batch[:n_new])
-            if st.front is not None:
-                if st.front[4:] != (self.W, self.H):
-                    raise RuntimeError(f"the stream downsamples to {st.front[4]} x {st.front[5]}, the engine runs "
-                                       f"{self.W} x {self.H}")
-                # the front takes its count from the host: all n_new rows, of which those behind the filter's count are
-                # lane-less and integrate nowhere
-                s_xy, s_t, s_p, s_batch, s_n = st.downsample(s_xy[:n_new], s_t[:n_new], s_p[:n_new], s_batch[:n_new])
-            stage = L.dagr_stream_stage_dev if N is None else L.dagr_stream_stage_dev_capped
-            _lib.check(stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(s_xy), P(s_t), P(s_p),
-                             P(s_batch), P(s_n), n_new, P(t), P(batch), 1 if batch.dtype == torch.int64 else 0, n_new,
-                             P(t_now), st.window_us, *cap_args, *outputs), "stream_stage_dev")
-        elif st.front is None:
-            stage = L.dagr_stream_stage if N is None else L.dagr_stream_stage_capped
-            _lib.check(stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(xy), P(t), P(p),
-                             P(batch), 1 if batch.dtype == torch.int64 else 0, n_new, P(t_now), st.window_us, *cap_args,
-                             *outputs), "stream_stage")
-        else:       # raw sensor events: the front leaves the survivors and their count on the device, the raw push is the clock
-            if st.front[4:] != (self.W, self.H):
-                raise RuntimeError(f"the stream downsamples to {st.front[4]} x {st.front[5]}, the engine runs "
-                                   f"{self.W} x {self.H}")
-            s_xy, s_t, s_p, s_batch, s_n = st.downsample(xy, t, p, batch)
-            stage = L.dagr_stream_stage_dev if N is None else L.dagr_stream_stage_dev_capped      # (the cap counts survivors)
-            _lib.check(stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, P(s_xy), P(s_t), P(s_p),
-                             P(s_batch), P(s_n), n_new, P(t), P(batch), 1 if batch.dtype == torch.int64 else 0, n_new,
-                             P(t_now), st.window_us, *cap_args, *outputs), "stream_stage_dev")
+        if st.front is not None and st.front[4:] != (self.W, self.H):
+            raise RuntimeError(f"the stream downsamples to {st.front[4]} x {st.front[5]}, the engine runs {self.W} x {self.H}")
+        # the source rows, which are also the clock: the decoded push with its count on the device, or the push itself
+        source = st.decode(words, word_end) if decoding else (xy, t, p, batch, None)
+        rows = int(source[1].shape[0])
+        if decoding:
+            clock = (P(source[1]), P(source[3]), 0, P(source[4]), rows)
+        else:
+            clock = (P(t), P(batch), 1 if batch.dtype == torch.int64 else 0, rows)
+        # flicker / trail in front of the noise filter (flicker would support noise there), the front last; each on all rows,
+        # of which those behind the count of the stage in front are lane-less: they meet no state and integrate nowhere
+        last = source
+        for name in ("flick", "noise", "front"):
+            if name in st.stages:
+                last = st._push(name, *last[:4], n=rows)
+        if decoding or last is not source:      # the survivors and their count are on the device (a cap counts survivors)
+            kind = "stream_stage_dev_clock" if decoding else "stream_stage_dev"
+            push = (*(P(v) for v in last), rows, *clock)
+        else:
+            kind, push = "stream_stage", (P(xy), P(t), P(p), P(batch), *clock[2:])
+        stage = getattr(L, "dagr_" + kind + ("" if N is None else "_capped"))
+        _lib.check(stage(ctypes.byref(g.desc), P(g.workspace), P(st.state), self.B, st.cap, *push, P(t_now), st.window_us,
+                         *cap_args, *outputs), kind)
         if not self.window_graph:                    # throughput mode: the body of the captured window, launch by launch
             out = self._forward_static(held)
         elif held:

@@ -144,7 +144,7 @@ def test_a_stream_without_decode_calls_what_it_called_before(monkeypatch):
     d = DecodeDefinition(B, "evt3", W, H, t_base=T_BASE)
     stream = EventStream(model, window_us=WINDOW_US, decode=None, max_decoded=None, t_base=None)
     st = stream.state
-    assert st.words is None and st.words_state is None and st.words_out is None and st.lane_decoded is None
+    assert st.words is None and "words" not in st.stages and st.lane_decoded is None
     pushes = [d.push(words, lane_words) + (t_now,) for words, lane_words, t_now, _ in _steps("evt3", W, H)[:3]]
     for x, y, t, p, batch, t_now in pushes:
         stream.step_device(np.stack([x, y], -1).reshape(-1, 2), t, p, batch=batch, t_now=t_now)

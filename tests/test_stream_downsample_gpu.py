@@ -189,7 +189,7 @@ def test_a_raw_stream_that_outgrows_the_engine_and_the_front_grows_and_stays_equ
     cap0 = eng.max_events
     st = StreamState(B, sc.TW, eng.device)               # a window that never expires anything here
     st.enable_front(sc.F, sc.F, sc.W_IN, sc.H_IN, W, H)
-    front0 = st.front_cap
+    front0 = st.stages["front"].cap
     d = _definition(window_us=sc.TW)
     sizes = [(40, 10, 21)] * 4 + [(1000, 0, 199)] + [(23, 11, 5)] * 3   # raw pushes of ~320, then ~5400 > the front's 4096
     t = 0
@@ -208,7 +208,7 @@ def test_a_raw_stream_that_outgrows_the_engine_and_the_front_grows_and_stays_equ
             pos, feat, batch = d.formatted()
             _assert_same_detections(got, eng.forward_detections(_dev(pos), _dev(feat), _dev(batch)), B, k)
     assert grown_at is not None and grown_at > 0, grown_at
-    assert st.front_cap > front0 and len(s["t"]) < front0
+    assert st.stages["front"].cap > front0 and len(s["t"]) < front0
     assert eng._wg is not None, "the grown window was not captured again"
     torch.cuda.synchronize()
     assert int(st.status) == 0 and st.lane_count.tolist() == d.counts().tolist()

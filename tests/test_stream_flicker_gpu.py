@@ -322,7 +322,7 @@ def test_a_stream_without_the_options_calls_what_it_called_before(config, monkey
         del calls[:]
         stream = EventStream(model, window_us=WINDOW_US, **kw, **off)
         st = stream.state
-        assert st.flick is None and st.flick_state is None and st.flick_out is None and st.lane_suppressed is None
+        assert st.flick is None and "flick" not in st.stages and st.lane_suppressed is None
         assert play(stream) == steps * len(seq), calls
         assert not any(v.any() for v in stream.suppressed())
         assert not any("flicker" in c for c in calls)
