@@ -556,6 +556,88 @@ class StreamState:
         self.hota = None                                # the options of its HOTA state (dagr.streaming._hota_options)
         self.hota_state, self.hota_ws = None, None
         self._t_ref = None                              # (state pointer, capacity, where its t_ref[B] lives)
+        self.labels = None                              # the options of its label store (dagr.streaming._label_options)
+        self.labels_state, self.gt_labels = None, None  # the store; the last labelled step's (gt_box, gt_label, gt_id, n_gt)
+        self._stepped, self._labelled = False, False    # a step since construction / reset(); whether run_labels has had it
+
+    def stepped(self):
+        """``forward_stream`` has staged a step: ``run_labels`` may run at its ``t_ref``, once."""
+        self._stepped, self._labelled = True, False
+
+    def _t_ref_where(self):
+        """Where the step's reference instants ``t_ref[B]`` live inside the stream state (``dagr_stream_t_ref``), looked
+        up again only when the state has grown."""
+        if self._t_ref is None or self._t_ref[:2] != (self.state.data_ptr(), self.cap):
+            where = _lib.lib().dagr_stream_t_ref(_lib.ptr(self.state), self.B, self.cap)
+            if not where:
+                raise RuntimeError(f"dagr_stream_t_ref(B = {self.B}, capacity = {self.cap}): out of range")
+            self._t_ref = (self.state.data_ptr(), self.cap, ctypes.c_void_p(where))
+        return self._t_ref[2]
+
+    # ------------------------------------------------------------------------------------ labels at every step
+    def enable_labels(self, options):
+        """The stream keeps labelled keyframes and ``run_labels`` interpolates them to a step's ``t_ref``
+        (``dagr_stream_labels_push`` / ``dagr_stream_labels_at``): ``options`` as ``dagr.streaming._label_options`` returns
+        them.  Allocates the lanes' rings, empty, and the step's ground-truth tensors."""
+        self.labels = dict(options)
+        K, R, dev = self.labels["max_keyframes"], self.labels["max_rows"], self.device
+        self.labels_state = _state_buffer(dev, "dagr_stream_labels_bytes", self.B, K, R)
+        self.gt_labels = (torch.zeros((self.B, R, 4), dtype=torch.float32, device=dev),
+                          torch.zeros((self.B, R), dtype=torch.int32, device=dev),
+                          torch.zeros((self.B, R), dtype=torch.int64, device=dev),
+                          torch.full((self.B,), -1, dtype=torch.int32, device=dev))
+        self._reset_labels()
+
+    def _reset_labels(self):
+        """No keyframe, zero counters; the last step has no labels any more."""
+        _lib.check(_lib.lib().dagr_stream_labels_reset(_lib.ptr(self.labels_state), self.labels_state.numel(), self.B,
+                                                       self.labels["max_keyframes"], self.labels["max_rows"],
+                                                       _lib.cur_stream(self.device)), "stream_labels_reset")
+        self._stepped, self._labelled = False, False
+
+    def push_labels(self, t, n, xywh, label, id):
+        """``dagr_stream_labels_push``: ``F`` keyframes a lane from contiguous device tensors ``t`` int64 [B, F], ``n`` int32
+        [B, F], ``xywh`` fp64 [B, F, max_rows, 4], ``label`` int32 [B, F, max_rows], ``id`` int64 [B, F, max_rows]: one
+        launch, no host wait."""
+        if self.labels is None:
+            raise RuntimeError("this stream keeps no labels (labels=): it has no push_labels")
+        B, F, R = self.B, int(t.shape[1]), self.labels["max_rows"]
+        for v, dtype, shape, name in ((t, torch.int64, (B, F), "t"), (n, torch.int32, (B, F), "n"),
+                                      (xywh, torch.float64, (B, F, R, 4), "xywh"), (label, torch.int32, (B, F, R), "label"),
+                                      (id, torch.int64, (B, F, R), "id")):
+            if v.dtype != dtype or tuple(v.shape) != shape or not v.is_contiguous() or v.device != self.device:
+                raise RuntimeError(f"push_labels: {name} must be a contiguous {dtype} {list(shape)} on {self.device}")
+        P = _lib.ptr
+        _lib.check(_lib.lib().dagr_stream_labels_push(P(self.labels_state), self.labels_state.numel(), B,
+                                                      self.labels["max_keyframes"], R, F, P(t), P(n), P(xywh), P(label), P(id),
+                                                      _lib.cur_stream(self.device)), "stream_labels_push")
+
+    def run_labels(self):
+        """``dagr_stream_labels_at`` at the LAST step's ``t_ref``, at most once per step: ``(gt_box fp32 [B, max_rows, 4],
+        gt_label int32 [B, max_rows], gt_id int64 [B, max_rows], n_gt int32 [B])``, valid until the next step.  One launch,
+        no host wait."""
+        if self.labels is None:
+            raise RuntimeError("this stream keeps no labels (labels=): it has no labels_step")
+        if not self._stepped:
+            raise RuntimeError("labels_step: the stream has made no step since its construction / reset(): there is no "
+                               "instant to interpolate to")
+        if not self._labelled:
+            P, o, nan = _lib.ptr, self.labels, float("nan")
+            _lib.check(_lib.lib().dagr_stream_labels_at(
+                P(self.labels_state), self.labels_state.numel(), self.B, o["max_keyframes"], o["max_rows"],
+                self._t_ref_where(), o["max_gap_us"] or 0, nan if o["min_height"] is None else o["min_height"],
+                nan if o["min_diag"] is None else o["min_diag"], *(P(v) for v in self.gt_labels),
+                _lib.cur_stream(self.device)), "stream_labels_at")
+            self._labelled = True
+        return self.gt_labels
+
+    def label_words(self):
+        """The lanes' words read back: int64 [B, DAGR_LABELS_WORDS] -- keyframes, head, refused, cut_rows, overwritten,
+        labelled, outside, gap --, the layout include/dagr_hip.h documents (a copy; synchronises)."""
+        if self.labels is None:
+            raise RuntimeError("this stream keeps no labels (labels=): it has no counters")
+        W = _lib.DEFINES["DAGR_LABELS_WORDS"]
+        return self.labels_state[:8 * W * self.B].view(torch.int64).cpu().numpy().reshape(self.B, W)
 
     # ------------------------------------------------------------------------------------ track ids
     # the slots' arrays in the order the state holds them over [B, max_tracks]: (name, dtype, width); next_id[B] follows
@@ -619,12 +701,8 @@ class StreamState:
             if self.motion is not None:
                 self.track_boxes = torch.zeros((B, A, 4), dtype=torch.float32, device=self.device)
                 self.track_vel = torch.zeros((B, A, 4), dtype=torch.float32, device=self.device)
-        L, P, o = _lib.lib(), _lib.ptr, self.track
-        if self._t_ref is None or self._t_ref[:2] != (self.state.data_ptr(), self.cap):     # (the state has grown)
-            where = L.dagr_stream_t_ref(P(self.state), self.B, self.cap)
-            if not where:
-                raise RuntimeError(f"dagr_stream_t_ref(B = {self.B}, capacity = {self.cap}): out of range")
-            self._t_ref = (self.state.data_ptr(), self.cap, ctypes.c_void_p(where))
+        P, o = _lib.ptr, self.track
+        self._t_ref_where()
         gains, outputs = [], []             # what dagr_stream_track_cv takes in addition, in their places
         if self.motion is not None:
             n_coast, c_id, c_box, c_label, c_age = self.coast
@@ -1034,6 +1112,9 @@ class StreamState:
             self._reset_identity()
         if self.hota_state is not None:
             self._reset_hota()
+        if self.labels_state is not None:
+            self._reset_labels()
+        self._stepped, self._labelled = False, False
         self.status.zero_()
         self.lane_count.zero_()
         self.lane_dropped.zero_()
@@ -2474,6 +2555,7 @@ class WindowEngine:
         self._stream_pending = st
         det = (self._det, self._n_keep) if self._post_fresh else \
             postprocess_device(out, self.num_classes, key[0], key[1], self.H, self.W)
+        st.stepped()
         if st.track is not None:                     # a plain launch behind the window, captured or not: the track ids
             st.run_track(*det)
         return out, det

@@ -364,6 +364,37 @@ the alignment score is floored to ``2**-20`` and the weight to ``2**-30``, a pai
 epsilon at the thresholds, the labels gate the similarity, and the instants behind ``max_instants`` are left out.
 Agreement with TrackEval is not claimed.  Without ``hota`` nothing of this exists.
 
+Labels at every step (``labels=``: ``None`` is off, ``True`` takes the defaults, a dict sets ``max_keyframes`` (1..65535,
+default 1200), ``max_rows`` (1..``DAGR_SCORE_MAX_GT``, default 64), ``max_gap_us``, ``min_height``, ``min_diag`` (default
+``None`` each); needs neither ``track`` nor ``score``).  Labels arrive far more rarely than steps -- DSEC's at 20 Hz --, so a
+stream scored only where the caller holds labelled boxes is scored at one step in fifty.  The reference's inter-frame
+evaluation says what the ground truth between two labelled frames is (``DSEC.__getitem__`` with ``set_num_us``:
+``interpolate_tracks``, then ``filter_small_bboxes``); the stream takes the labelled keyframes once (``push_labels``) and
+interpolates them to every step's own ``t_ref`` on the device (``dagr_stream_labels_at``), where the instant lives.
+``LabelDefinition`` states the rule once in numpy; per lane, all arithmetic fp64, all instants int64 microseconds:
+
+* the store is a ring of at most ``max_keyframes`` keyframes, each an instant ``t`` and ``n <= max_rows`` rows of ``xywh``
+  fp64 (top-left plus size, as the DSEC tracks have it), ``label`` int32 and ``id`` int64;
+* a pushed keyframe whose ``t`` is not greater than the lane's newest keyframe instant is refused (``refused``), rows beyond
+  ``max_rows`` are cut (``cut_rows``), a push onto a full ring overwrites the oldest keyframe (``overwritten``);
+* a step has no labels -- ``n_gt = -1``, the scorer skips the lane -- when ``t_ref`` is ``INT64_MIN``, there is no keyframe,
+  or ``t_ref`` is before the oldest resident keyframe or after the newest (``outside``), or when ``max_gap_us`` is set and
+  the bracketing keyframes are further apart (``gap``); every other step counts under ``labelled``, rows or none;
+* inside ``[t_k, t_k+1)``, ``t_ref == t_k`` included, the rows are the identities both keyframes hold -- only ``id > 0``, an
+  identity at its first row inside a keyframe -- in ascending identity (the reference's ``argsort``):
+  ``r = float64(t_ref - t_k) / float64(t_k+1 - t_k)``, every one of ``x y w h`` is ``a * (1 - r) + b * r`` (two multiplies
+  and one add, no contraction), the label is the earlier keyframe's;
+* at the newest keyframe's own instant the rows are that keyframe's with ``id > 0``, first rows only, in ascending identity,
+  as they are -- there is no extrapolation behind it;
+* with ``min_height`` / ``min_diag`` a row survives iff ``sqrt(h * h + w * w) > min_diag and w > min_height and
+  h > min_height`` on the fp64 values (``None``: that half is off), after the interpolation as the reference has it;
+* the box is ``fp32(x), fp32(y), fp32(x + w), fp32(y + h)``, the sums in fp64.
+
+The interpolation is linear between keyframes: it is wrong wherever the object's motion is not, and an object born or gone
+between two keyframes has no row between them.  No real DSEC sequence was at hand: the rule is held to the reference's own
+``interpolate_tracks`` output on the golden frames, the rest is synthetic.  A stream without ``labels`` makes exactly the
+library calls it makes without the store.
+
 Camera words (``decode="evt3"`` or ``"evt2"``): an event camera delivers words, not arrays.  A decoding stream takes the
 camera's words (``step_words`` / ``step_words_device``) and decodes them on the device (``dagr_stream_decode``) in front of
 everything above: decode, then the flicker / trail filters, then the noise filter, then ``downsample=``, then the window.  The two formats are stated here as
@@ -1707,6 +1738,167 @@ def hota_summary(result):
     return dict(lanes=[one(c) for c in per_lane], total=one(total))
 
 
+LABEL_DEFAULTS = dict(max_keyframes=1200, max_rows=64, max_gap_us=None, min_height=None, min_diag=None)
+LABEL_WORDS = ("keyframes", "head", "refused", "cut_rows", "overwritten", "labelled", "outside", "gap")
+LABEL_COUNTERS = LABEL_WORDS[2:]
+assert len(LABEL_WORDS) == DEFINES["DAGR_LABELS_WORDS"]
+T_NEVER = int(np.iinfo(np.int64).min)                   # a lane's t_ref before its first event
+
+
+def _label_options(labels, who):
+    """``labels=`` of a stream, checked: None (off) or the dict of ``max_keyframes``, ``max_rows``, ``max_gap_us``,
+    ``min_height`` and ``min_diag`` with the defaults filled in; refusals by name."""
+    opt = _options(labels, "labels", LABEL_DEFAULTS, who)
+    if opt is None:
+        return None
+    if not _is_int(opt["max_keyframes"]) or not 1 <= int(opt["max_keyframes"]) <= 65535:
+        raise ValueError(f"{who}: labels max_keyframes = {opt['max_keyframes']!r} must be an int in 1..65535")
+    if not _is_int(opt["max_rows"]) or not 1 <= int(opt["max_rows"]) <= DAGR_SCORE_MAX_GT:
+        raise ValueError(f"{who}: labels max_rows = {opt['max_rows']!r} must be an int in 1..DAGR_SCORE_MAX_GT = "
+                         f"{DAGR_SCORE_MAX_GT}")
+    if opt["max_gap_us"] is not None and (not _is_int(opt["max_gap_us"]) or int(opt["max_gap_us"]) < 1):
+        raise ValueError(f"{who}: labels max_gap_us = {opt['max_gap_us']!r} must be a positive int of microseconds (or None: "
+                         "no limit)")
+    for name in ("min_height", "min_diag"):
+        if opt[name] is not None and not _is_real(opt[name]):
+            raise ValueError(f"{who}: labels {name} = {opt[name]!r} must be a number (or None: that half of the small-box "
+                             "filter is off)")
+    return dict(max_keyframes=int(opt["max_keyframes"]), max_rows=int(opt["max_rows"]),
+                max_gap_us=None if opt["max_gap_us"] is None else int(opt["max_gap_us"]),
+                min_height=None if opt["min_height"] is None else float(opt["min_height"]),
+                min_diag=None if opt["min_diag"] is None else float(opt["min_diag"]))
+
+
+def labels_from_tracks(tracks):
+    """One frame of a DSEC track array (fields ``t, x, y, w, h, class_id, track_id``; every row carries the frame's ``t``)
+    -> ``(t int, xywh fp64 [n, 4], class_id int32 [n], track_id + 1 int64 [n])``, a keyframe as ``push`` /
+    ``EventStream.push_labels`` take it.  DSEC's track ids start at 0, and the scorer and the label store reserve
+    ``id <= 0`` for annotations without an identity: hence the ``+ 1``.  An empty frame has no instant and is refused."""
+    if len(tracks) == 0:
+        raise ValueError("labels_from_tracks: an empty frame carries no instant (push it with its t and zero rows)")
+    xywh = np.stack([np.asarray(tracks[k], np.float64) for k in "xywh"], axis=1)
+    return int(tracks["t"][0]), xywh, np.asarray(tracks["class_id"]).astype(np.int32), \
+        np.asarray(tracks["track_id"]).astype(np.int64) + 1
+
+
+class LabelDefinition:
+    """The label store of the module docstring in numpy: the labelled keyframes of every lane in a ring, and the ground
+    truth of a step interpolated to the step's own ``t_ref`` -- the reference's inter-frame evaluation
+    (``interpolate_tracks``, then ``filter_small_bboxes``), stated per lane.  All arithmetic is fp64, all instants int64
+    microseconds.  ``push(b, t, xywh, label, id)`` offers lane ``b`` one keyframe and says whether it was taken;
+    ``push_arrays`` is ``dagr_stream_labels_push``'s call; ``at(t_ref)`` is ``dagr_stream_labels_at``'s.  ``counters`` is a
+    dict of one int64 ``[B]`` array per name of ``LABEL_COUNTERS``; ``words()`` the lanes' words as the device state holds
+    them.  The yardstick of the two kernels; nothing on the device path calls it."""
+
+    def __init__(self, batch_size, labels=True):
+        self.B = int(batch_size)
+        self.options = _label_options(labels, "LabelDefinition")
+        if self.options is None:
+            raise ValueError("LabelDefinition: labels = None is a stream that keeps no labels")
+        self.reset()
+
+    def reset(self):
+        self.frames = [[] for _ in range(self.B)]           # per lane the resident keyframes, oldest first
+        self.head = np.zeros(self.B, np.int64)              # the ring index of the oldest
+        self.counters = {name: np.zeros(self.B, np.int64) for name in LABEL_COUNTERS}
+
+    def words(self):
+        """int64 ``[B, DAGR_LABELS_WORDS]``, the order of ``LABEL_WORDS``."""
+        return np.stack([np.array([len(f) for f in self.frames], np.int64), self.head] +
+                        [self.counters[name] for name in LABEL_COUNTERS], axis=1)
+
+    def push(self, b, t, xywh, label, id, n=None):
+        """One keyframe for lane ``b``: ``n`` (default: all) rows of ``xywh`` fp64 ``[rows, 4]``, ``label``, ``id``."""
+        o, c, frames = self.options, self.counters, self.frames[b]
+        xywh = np.asarray(xywh, np.float64).reshape(-1, 4)
+        label, id, t = np.asarray(label, np.int32).reshape(-1), np.asarray(id, np.int64).reshape(-1), int(t)
+        n = len(xywh) if n is None else int(n)
+        if frames and t <= frames[-1][0]:
+            c["refused"][b] += 1
+            return False
+        kept = min(n, o["max_rows"])
+        c["cut_rows"][b] += n - kept
+        if len(frames) == o["max_keyframes"]:
+            frames.pop(0)
+            self.head[b] = (self.head[b] + 1) % o["max_keyframes"]
+            c["overwritten"][b] += 1
+        frames.append((t, xywh[:kept].copy(), label[:kept].copy(), id[:kept].copy()))
+        return True
+
+    def push_arrays(self, t, n, xywh, label, id):
+        """``t`` int64 ``[B, F]``, ``n`` int32 ``[B, F]`` (negative: none), ``xywh`` fp64 ``[B, F, R, 4]``, ``label`` int32
+        ``[B, F, R]``, ``id`` int64 ``[B, F, R]``: every lane takes its ``F`` keyframes in order."""
+        t, n = np.asarray(t, np.int64), np.asarray(n, np.int32)
+        for b in range(self.B):
+            for f in range(t.shape[1]):
+                if n[b, f] >= 0:
+                    self.push(b, t[b, f], xywh[b, f], label[b, f], id[b, f], n=n[b, f])
+
+    @staticmethod
+    def _first_rows(ids):
+        """The rows that take part, by ascending identity: ``id > 0``, an identity at its first row."""
+        first = {}
+        for g, v in enumerate(ids):
+            if v > 0:
+                first.setdefault(int(v), g)
+        return first
+
+    def rows_at(self, b, t):
+        """Lane ``b`` at the instant ``t``, nothing counted: ``("outside" | "gap", None, None, None)`` or ``("labelled", xywh
+        fp64 [m, 4], label int32 [m], id int64 [m])`` -- the surviving rows in ascending identity, before the box is made."""
+        o, frames, t = self.options, self.frames[b], int(t)
+        if t == T_NEVER or not frames or t < frames[0][0] or t > frames[-1][0]:
+            return "outside", None, None, None
+        k = max(i for i, f in enumerate(frames) if f[0] <= t)
+        t0, xa, la, ia = frames[k]
+        rows = self._first_rows(ia)
+        if k == len(frames) - 1:                            # the newest keyframe's own instant: its rows as they are
+            idents = sorted(rows)
+            xywh = xa[[rows[v] for v in idents]].reshape(-1, 4)
+        else:
+            t1, xb, _, ib = frames[k + 1]
+            if o["max_gap_us"] is not None and t1 - t0 > o["max_gap_us"]:
+                return "gap", None, None, None
+            partner = self._first_rows(ib)
+            idents = sorted(v for v in rows if v in partner)
+            a = xa[[rows[v] for v in idents]].reshape(-1, 4)
+            bb = xb[[partner[v] for v in idents]].reshape(-1, 4)
+            r = np.float64(t - t0) / np.float64(t1 - t0)
+            with np.errstate(all="ignore"):
+                xywh = a * (1 - r) + bb * r                 # two multiplies, one add
+        keep = np.ones(len(idents), bool)
+        with np.errstate(all="ignore"):
+            w, h = xywh[:, 2], xywh[:, 3]
+            if o["min_diag"] is not None:
+                keep &= np.sqrt(h * h + w * w) > o["min_diag"]
+            if o["min_height"] is not None:
+                keep &= (w > o["min_height"]) & (h > o["min_height"])
+        label = np.array([la[rows[v]] for v in idents], np.int32)
+        return "labelled", xywh[keep], label[keep], np.array(idents, np.int64)[keep]
+
+    def at(self, t_ref, out=None):
+        """``t_ref`` int64 ``[B]`` -> ``(gt_box fp32 [B, G, 4] as x1 y1 x2 y2, gt_label int32 [B, G], gt_id int64 [B, G], n_gt
+        int32 [B])``, ``G = max_rows``; given ``out=`` (the four arrays) it writes into them, so that what a step does not
+        write stays (otherwise it is zero)."""
+        G = self.options["max_rows"]
+        t_ref = np.broadcast_to(np.asarray(t_ref, np.int64).reshape(-1), (self.B,))
+        gt_box, gt_label, gt_id, n_gt = out if out is not None else (
+            np.zeros((self.B, G, 4), np.float32), np.zeros((self.B, G), np.int32), np.zeros((self.B, G), np.int64),
+            np.zeros(self.B, np.int32))
+        for b in range(self.B):
+            what, xywh, label, ids = self.rows_at(b, t_ref[b])
+            self.counters[what][b] += 1
+            if what != "labelled":
+                n_gt[b] = -1
+                continue
+            m = len(ids)
+            with np.errstate(all="ignore"):
+                gt_box[b, :m, 0], gt_box[b, :m, 1] = xywh[:, 0], xywh[:, 1]
+                gt_box[b, :m, 2], gt_box[b, :m, 3] = xywh[:, 0] + xywh[:, 2], xywh[:, 1] + xywh[:, 3]
+            gt_label[b, :m], gt_id[b, :m], n_gt[b] = label, ids, m
+        return gt_box, gt_label, gt_id, n_gt
+
+
 def frame_definition(raw, fx, fy, W, H, bgr=False):
     """The model's image of one raw sensor frame (``uint8 [H_f, W_f, 3]``), stated once: ``DSEC.preprocess_image`` plus
     ``format_data`` for a top-left crop.  Rows ``[0, fy * H)`` and columns ``[0, fx * W)`` of the frame go through
@@ -2087,6 +2279,12 @@ class EventStream:
     returns HOTA's integers and fp64 sums (module docstring; ``hota_summary`` gives HOTA, DetA, AssA and LocA);
     ``hota_tables()`` reads the state back.  A combination whose state would exceed ``DAGR_HOTA_MAX_STATE_BYTES`` is
     refused by name.  A stream built without it issues exactly the calls it issued before.
+    ``labels`` (``None``: off, ``True``: the defaults, or a dict of ``max_keyframes``, ``max_rows``, ``max_gap_us``,
+    ``min_height``, ``min_diag``; needs neither ``track`` nor ``score``): the stream keeps labelled keyframes
+    (``push_labels``) and interpolates the ground truth to the last step's own ``t_ref`` on the device (module docstring):
+    ``labels_step()`` is the one launch (``dagr_stream_labels_at``), ``score_step()`` without arguments runs it in front
+    of the scorer chain, ``label_counts()`` reads the counters back.  A step of such a stream issues exactly the calls it
+    issues without the store, and a stream built without it issues exactly the calls it issued before.
     ``decode`` (``None``: off, ``"evt2"`` or ``"evt3"``), ``max_decoded`` and ``t_base``: the stream takes the camera's words
     (``step_words`` / ``step_words_device``) and ``dagr_stream_decode`` turns them into events on the device, in front of
     the filter, the front and the window (module docstring; the formats as recalled from the vendor's public descriptions,
@@ -2113,9 +2311,10 @@ class EventStream:
     def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
                  max_lane_events=None, denoise_us=None, refractory_us=None, track=None, motion=None, rescue=None,
                  decode=None, max_decoded=None, t_base=None, flicker=None, trail_us=None, score=None,
-                 identity=None, assign=None, hota=None):
+                 identity=None, assign=None, hota=None, labels=None):
         import torch
         self.model = model
+        self.labels = _label_options(labels, "EventStream")
         self.track = _track_options(track, "EventStream")
         self.motion = _motion_options(motion, self.track, "EventStream")
         self.rescue = _rescue_options(rescue, self.track, "EventStream")
@@ -2176,6 +2375,9 @@ class EventStream:
             self.state.enable_identity(self.identity_options)
         if self.hota_options is not None:
             self.state.enable_hota(self.hota_options)
+        if self.labels is not None:
+            self.state.enable_labels(self.labels)
+        self._label_newest = [None] * eng.B     # per lane the newest instant a HOST push has offered (push_labels' check)
         self._zeros = None
         self.outputs = None      # the last step's decoded head outputs [B, A, 5 + classes], valid until the engine's next call
         self._frame = None
@@ -2487,8 +2689,99 @@ class EventStream:
         that continued a track: int64 [B] (synchronises).  Raises without ``rescue=``."""
         return self.state.rescued()
 
-    def score_step(self, gt_box, gt_label, gt_id, n_gt=None):
-        """Score the LAST step's track ids against labelled boxes, on the device (module docstring; needs ``score=``):
+    def push_labels(self, t, xywh, label, id, n=None, lanes=None):
+        """Labelled keyframes into the lanes' stores (module docstring; needs ``labels=``): ONE launch
+        (``dagr_stream_labels_push``), no host wait.  ``t`` int64 ``[L]`` and ``xywh`` fp64 ``[L, rows, 4]`` (top-left plus
+        size), ``label`` int32 ``[L, rows]``, ``id`` int64 ``[L, rows]`` (``labels_from_tracks`` makes them of a DSEC track
+        array) are one keyframe per lane; with a further axis ``F`` behind ``L`` -- ``t [L, F]``, ``xywh [L, F, rows, 4]`` --
+        every lane takes ``F`` keyframes in order.  ``n`` int32 ``[L]`` / ``[L, F]``: the rows that count (``None``: all;
+        negative: no keyframe for that lane).  ``L`` is the batch size, or the length of ``lanes`` (distinct lane indices);
+        the other lanes get nothing.  numpy arrays (uploaded) or device tensors.  The rules -- a keyframe not later than
+        the lane's newest is refused, rows beyond ``max_rows`` are cut, a full ring loses its oldest keyframe -- are
+        applied and counted on the device (``label_counts()``); host arrays are also checked here: an instant that is not
+        greater than the one before it in the call, or than the newest a host push has offered that lane, raises by
+        name."""
+        import torch
+        if self.labels is None:
+            raise RuntimeError("EventStream: push_labels needs a stream built with labels=")
+        R = self.labels["max_rows"]
+        host = not any(torch.is_tensor(v) for v in (t, xywh, label, id, n))
+
+        def ten(v, dtype):
+            if not torch.is_tensor(v):
+                v = torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
+            return v.to(dtype=dtype)
+        t, xywh, label, id = ten(t, torch.int64), ten(xywh, torch.float64), ten(label, torch.int32), ten(id, torch.int64)
+        n = None if n is None else ten(n, torch.int32)
+        if t.dim() == 1:
+            t, xywh, label, id = t[:, None], xywh[:, None], label[:, None], id[:, None]
+            n = n if n is None or n.dim() != 1 else n[:, None]
+        which = list(range(self.B)) if lanes is None else [int(b) for b in np.asarray(lanes).reshape(-1)]
+        if sorted(set(which)) != sorted(which) or any(not 0 <= b < self.B for b in which):
+            raise ValueError(f"EventStream: push_labels lanes = {which} must be distinct lanes in 0..{self.B - 1}")
+        L, F = len(which), int(t.shape[1]) if t.dim() == 2 else -1
+        rows = int(xywh.shape[2]) if xywh.dim() == 4 else -1
+        if n is None:
+            n = torch.full((L, max(F, 0)), max(rows, 0), dtype=torch.int32)
+        if tuple(t.shape) != (L, F) or F < 1 or tuple(xywh.shape) != (L, F, rows, 4) or tuple(label.shape) != (L, F, rows) or \
+                tuple(id.shape) != (L, F, rows) or tuple(n.shape) != (L, F):
+            raise ValueError(f"EventStream: push_labels takes t int64 [{L}] or [{L}, F], xywh fp64 [{L}, (F,) rows, 4], label "
+                             f"int32 and id int64 [{L}, (F,) rows] and n int32 like t, got {tuple(t.shape)}, "
+                             f"{tuple(xywh.shape)}, {tuple(label.shape)}, {tuple(id.shape)} and {tuple(n.shape)}")
+        if host:
+            th, nh, newest = t.numpy(), n.numpy(), list(self._label_newest)
+            if (nh > rows).any():
+                raise ValueError(f"EventStream: push_labels n = {int(nh.max())} exceeds the {rows} rows given")
+            for i, b in enumerate(which):
+                for f in range(F):
+                    if nh[i, f] < 0:
+                        continue
+                    if newest[b] is not None and int(th[i, f]) <= newest[b]:
+                        raise ValueError(f"EventStream: push_labels t = {int(th[i, f])} of lane {b} is not greater than the "
+                                         f"lane's newest keyframe instant {newest[b]}: keyframes are pushed in increasing time")
+                    newest[b] = int(th[i, f])
+            self._label_newest = newest
+        dev = self.device
+        t, n, xywh, label, id = (v.to(dev) for v in (t, n, xywh, label, id))
+        if rows > R:
+            xywh, label, id = xywh[:, :, :R], label[:, :, :R], id[:, :, :R]
+        elif rows < R:
+            pad = lambda v: torch.cat([v, v.new_zeros((L, F, R - rows) + tuple(v.shape[3:]))], dim=2)      # noqa: E731
+            xywh, label, id = pad(xywh), pad(label), pad(id)
+        if lanes is not None:
+            at = torch.as_tensor(which, dtype=torch.int64, device=dev)
+            full = [torch.zeros((self.B,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev) for v in (t, n, xywh, label, id)]
+            full[1].fill_(-1)
+            for whole, part in zip(full, (t, n, xywh, label, id)):
+                whole[at] = part
+            t, n, xywh, label, id = full
+        self.state.push_labels(*(v.contiguous() for v in (t, n, xywh, label, id)))
+
+    def labels_step(self):
+        """The ground truth of the LAST step, interpolated to the step's own ``t_ref`` on the device (module docstring;
+        needs ``labels=``): ``(gt_box fp32 [B, G, 4] as x1 y1 x2 y2, gt_label int32 [B, G], gt_id int64 [B, G], n_gt int32
+        [B])`` with ``G = max_rows``, device tensors valid until the next step -- what ``score_step`` takes, and what a
+        caller that evaluates mAP can hand on.  ``n_gt[b] = -1``: lane ``b`` has no labels at this instant; rows at and
+        behind ``n_gt[b]`` mean nothing.  ONE launch (``dagr_stream_labels_at``) at most once per step -- asked again, it
+        returns the same tensors --, no host wait.  Raises by name before the stream's first step."""
+        if self.labels is None:
+            raise RuntimeError("EventStream: labels_step needs a stream built with labels=")
+        return self.state.run_labels()
+
+    def label_counts(self):
+        """The label store's counters since construction / ``reset()``: a dict of int64 ``[B]`` per name of
+        ``LABEL_COUNTERS`` (``refused``, ``cut_rows``, ``overwritten``, ``labelled``, ``outside``, ``gap``) plus
+        ``keyframes``, the resident keyframes.  Synchronises.  Raises without ``labels=``."""
+        if self.labels is None:
+            raise RuntimeError("EventStream: label_counts needs a stream built with labels=")
+        words = self.state.label_words()
+        return {name: words[:, i].copy() for i, name in enumerate(LABEL_WORDS) if name != "head"}
+
+    def score_step(self, gt_box=None, gt_label=None, gt_id=None, n_gt=None):
+        """Score the LAST step's track ids against labelled boxes, on the device (module docstring; needs ``score=``).
+        Without arguments, on a stream with ``labels=``: against the ground truth interpolated to the step's own ``t_ref``
+        -- ``labels_step()`` if the step has not had one (``dagr_stream_labels_at``, once), then the unchanged chain on
+        its tensors; raises by name on a stream without ``labels=`` or without ``score=``.  With arguments, as ever:
         ``gt_box`` fp32 ``[B, G, 4]`` (x1, y1, x2, y2), ``gt_label`` int32 ``[B, G]``, ``gt_id`` int64 ``[B, G]`` (the
         identities, > 0) and ``n_gt`` int32 ``[B]`` -- ``None``: every lane has all ``G`` rows; ``n_gt[b] < 0``: lane ``b``
         has no labels at this instant and is skipped --, numpy arrays (uploaded) or device tensors,
@@ -2501,6 +2794,14 @@ class EventStream:
         import torch
         if self.score is None:
             raise RuntimeError("EventStream: score_step needs a stream built with score= (and track=)")
+        if gt_box is None:
+            if gt_label is not None or gt_id is not None or n_gt is not None:
+                raise ValueError("EventStream: score_step takes gt_box, gt_label and gt_id together, or nothing at all (a "
+                                 "stream with labels=)")
+            if self.labels is None:
+                raise RuntimeError("EventStream: score_step() without arguments needs a stream built with labels= (it scores "
+                                   "against the interpolated keyframes)")
+            return self.state.run_score(*self.state.run_labels())
 
         def dev(v, dtype, shape, name):
             if not torch.is_tensor(v):
@@ -2589,9 +2890,11 @@ class EventStream:
     def reset(self):
         """Empty the stream: no resident events, no reference instants, zero change maps, empty stamp maps, every pixel of
         the flicker / trail filters in its initial state, zero dropped, filtered and suppressed counts, zero decoder states and counters, a clear status word, zero step counters; no tracks, ids from 1 again, zero untracked and rescued counts; the
-        scorer's object tables empty and its counters zero (and no step left to score); the identity state and HOTA's state and log empty.  The
+        scorer's object tables empty and its counters zero (and no step left to score); the identity state and HOTA's state and log empty; the label
+        store empty and its counters zero.  The
         frame in force stays, and the next step runs it through the image branch again."""
         self.state.reset()
+        self._label_newest = [None] * self.B
 
     def check_status(self):
         """Raise ``RuntimeError`` naming the stream's flag if a step raised one (the word is cleared: the stream goes on

@@ -914,6 +914,61 @@ int dagr_stream_hota(void *state, size_t bytes, int32_t B, int32_t max_objects, 
 int dagr_stream_hota_solve(void *state, size_t bytes, int32_t B, int32_t max_objects, int32_t max_tracks,
                            int32_t max_instants, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * Event stream label store: the ground truth of every step, interpolated between labelled keyframes on the device
+ *   Labels arrive far more rarely than steps (DSEC: 20 Hz against a 1 kHz stream).  dagr_stream_labels_push keeps the
+ *   labelled keyframes of every lane in a ring, and dagr_stream_labels_at writes, for every lane, the ground truth at the
+ *   lane's own reference instant -- t_ref[b], a device array: dagr_stream_t_ref's -- into the arrays dagr_stream_score,
+ *   dagr_stream_identity and dagr_stream_hota read.  The rule is the reference's inter-frame evaluation (interpolate_tracks:
+ *   the boxes of the identities both frames hold, linear in x, y, w, h, in ascending identity; then filter_small_bboxes).
+ *   Linear between keyframes, so wrong wherever the object's motion is not.  One launch each, no host synchronisation, no
+ *   atomics.  dagr_amd/streaming.py: LabelDefinition is the same in numpy, bit for bit.
+ *
+ * A keyframe is an instant t (int64 microseconds, the stream's clock) and n <= max_rows rows of xywh fp64[4] (top-left plus
+ * size), label int32 and id int64.  With K = max_keyframes and R = max_rows:
+ *   push:  lane b takes the keyframes f = 0 .. F - 1 of the call in order: t[b, f], n[b, f], xywh[b, f, :, :], label[b, f, :],
+ *          id[b, f, :], the arrays R rows wide.  n[b, f] < 0: none.  A keyframe whose t is not greater than the lane's newest
+ *          keyframe instant is refused (refused += 1, nothing else).  Rows at and behind R are cut (cut_rows += n - R).  On a
+ *          full ring the oldest keyframe is overwritten (overwritten += 1).
+ *   at:    n_gt[b] = -1, nothing else written, and outside += 1 when t_ref[b] is INT64_MIN, the lane has no keyframe, or
+ *          t_ref[b] is before the oldest resident keyframe or after the newest; likewise and gap += 1 when max_gap_us > 0
+ *          and the bracketing keyframes are more than max_gap_us apart.  Otherwise labelled += 1 and, with t_k <= t_ref <
+ *          t_k+1 the bracketing pair, the rows are the identities both keyframes hold -- only id > 0, an identity counts at
+ *          its first row inside a keyframe -- in ascending identity: r = (double)(t_ref - t_k) / (double)(t_k+1 - t_k), every
+ *          one of x, y, w, h is a * (1 - r) + b * r (two multiplies, one add, fp64, no contraction), the label is the
+ *          earlier keyframe's.  t_ref == the newest keyframe's instant: that keyframe's rows with id > 0, first rows only,
+ *          in ascending identity, as they are.  Then the small-box filter on the fp64 values: a row survives iff
+ *          sqrt(h * h + w * w) > min_diag && w > min_height && h > min_height; a NaN min_diag / min_height switches that
+ *          half off.  gt_box[b, i] = (float)x, (float)y, (float)(x + w), (float)(y + h), the sums in fp64; gt_label, gt_id;
+ *          n_gt[b] = the rows written (0: labelled, but no row).  Rows at and behind n_gt[b] are left as they are.
+ *
+ * state: dagr_stream_labels_bytes(B, max_keyframes, max_rows) bytes (0: B or max_keyframes outside 1..65535, max_rows
+ *        outside 1..DAGR_SCORE_MAX_GT), 16-byte aligned, dagr_stream_labels_reset before the first push and to empty it (it
+ *        zeroes the words; what lies behind them means nothing until a push has written it).  It holds, each at the next
+ *        multiple of 16 bytes behind the one before:
+ *          lane  int64 [B, DAGR_LABELS_WORDS]: keyframes (resident), head (the ring index of the oldest), refused, cut_rows,
+ *                overwritten, labelled, outside, gap
+ *          t     int64 [B, K]          (resident keyframe i of lane b is ring index (head + i) % K, instants ascending)
+ *          n     int32 [B, K]
+ *          xywh  fp64  [B, K, R, 4]
+ *          label int32 [B, K, R]
+ *          id    int64 [B, K, R]
+ * push: t int64[B, F], n int32[B, F], xywh fp64[B, F, R, 4] (16-byte aligned), label int32[B, F, R], id int64[B, F, R],
+ * 1 <= F <= 65535.  at: t_ref int64[B]; gt_box fp32[B, R, 4] (16-byte aligned), gt_label int32[B, R], gt_id int64[B, R], n_gt
+ * int32[B] -- G = max_rows for the scorer.  All in device memory.  Instants are expected to differ by less than 2^63.
+ * DAGR_ERR_INVALID_ARG before any launch: sizes out of range, max_gap_us < 0, a state smaller than
+ * dagr_stream_labels_bytes, NULL or misaligned arrays.
+ * ------------------------------------------------------------------------ */
+#define DAGR_LABELS_WORDS 8
+size_t dagr_stream_labels_bytes(int32_t B, int32_t max_keyframes, int32_t max_rows);
+int dagr_stream_labels_reset(void *state, size_t bytes, int32_t B, int32_t max_keyframes, int32_t max_rows, void *stream);
+int dagr_stream_labels_push(void *state, size_t bytes, int32_t B, int32_t max_keyframes, int32_t max_rows, int32_t F,
+                            const int64_t *t, const int32_t *n, const double *xywh, const int32_t *label, const int64_t *id,
+                            void *stream);
+int dagr_stream_labels_at(void *state, size_t bytes, int32_t B, int32_t max_keyframes, int32_t max_rows,
+                          const int64_t *t_ref, int64_t max_gap_us, double min_height, double min_diag,
+                          float *gt_box, int32_t *gt_label, int64_t *gt_id, int32_t *n_gt, void *stream);
+
 /* The neighbour search alone, again, on the pixel index the last dagr_graph_build_window left in `workspace` (same N):
  * rewrites nbr_src / nbr_code / deg and the edge count.  For measurement (bench.py times the search kernels on their own
  * stream with HIP events); a product caller has no use for it. */

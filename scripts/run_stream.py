@@ -80,6 +80,17 @@ statement of it, agreement with TrackEval is not claimed), printed beside MOTA a
 (needs ``--track_hota``) sizes the log (default 1200, at most 65535); the instants behind it are left out and counted.
 The detections written do not change.
 
+``--track_score_every_step`` (needs ``--track_score``): labels arrive far more rarely than steps, so EVERY step is scored,
+against the source's labelled keyframes interpolated to the step's own instant on the device (``dagr.streaming``:
+``EventStream(labels=)``: linear in x, y, w, h between the two keyframes that bracket the step, the identities both hold --
+the reference's inter-frame evaluation; wrong wherever an object's motion is not linear).  The source must also have
+``label_instants()``, its labelled instants as sorted int64; the script keeps the store one keyframe ahead of the step --
+it pushes ``labels(t_k)`` for every instant up to the first one behind the step -- and the summary says how many steps
+were labelled, outside the keyframes, or in a gap.  ``--label_max_gap_us N`` leaves the steps between two keyframes more
+than ``N`` microseconds apart unscored; ``--label_min_height V`` / ``--label_min_diag V`` drop interpolated boxes that are
+not larger (``filter_small_bboxes``).  HOTA's log holds at most 65535 instants a lane -- about a minute at 1 kHz --, the
+rest is counted as left out.  The detections written do not change.
+
 ``--decode evt2|evt3``: the step's events are encoded as camera words (``dagr.data.evt.encode_events``, an encoder for
 synthetic sources, not a model of any camera) and pushed through ``step_words``; the stream decodes them on the device
 (``dagr.streaming``: ``EventStream(decode=)``) in front of the filter, the front and the window.  ``--max_decoded N`` sizes
@@ -94,7 +105,8 @@ import torch
 import _common as C
 from dagr.data.evt import encode_events
 from dagr.streaming import (EventStream, _assign_options, _flicker_options, _identity_options, _motion_options, _rescue_options,
-                            _hota_options, _score_options, _track_options, hota_summary, identity_summary, score_summary)
+                            _hota_options, _label_options, _score_options, _track_options, hota_summary, identity_summary,
+                            score_summary)
 from dagr.utils.buffers import DETECTION_DTYPE, detections_to_records
 from dagr.utils.logging import set_up_logging_directory
 from dagr.utils import synthetic as syn
@@ -156,6 +168,14 @@ def stream_options(p):
                    "kept and replayed on the device; implies --track_score and --track_identity")
     g.add_argument("--track_hota_max_instants", type=int, default=None, help="with --track_hota: the labelled instants the "
                    "log holds, 1..65535 (default 1200); those behind it are left out and counted")
+    g.add_argument("--track_score_every_step", action="store_true", help="with --track_score: score EVERY step against the "
+                   "source's labelled keyframes (source.label_instants), interpolated to the step's instant on the device")
+    g.add_argument("--label_max_gap_us", type=int, default=None, help="with --track_score_every_step: no labels between two "
+                   "keyframes further apart than this (default: no limit)")
+    g.add_argument("--label_min_height", type=float, default=None, help="with --track_score_every_step: drop interpolated "
+                   "boxes whose width or height is not above this")
+    g.add_argument("--label_min_diag", type=float, default=None, help="with --track_score_every_step: drop interpolated boxes "
+                   "whose diagonal is not above this")
     g.add_argument("--raw_frames", action="store_true", help="the source's frames are sensor-size BGR uint8 frames: prepare "
                    "them on the device (crop, shrink by the --downsample factor, / 255)")
 
@@ -252,6 +272,40 @@ def score_options(a, source=None):
         raise SystemExit(f"run_stream.py: --track_score needs a source with labels(t_step); {type(source).__name__} has none "
                          "(the built-in synthetic sequence carries no labelled boxes)")
     return given
+
+
+LABEL_FLAGS = (("label_max_gap_us", "max_gap_us"), ("label_min_height", "min_height"), ("label_min_diag", "min_diag"))
+
+
+def label_options(a, source=None):
+    """``labels=`` of the stream the flags describe: None without ``--track_score_every_step``, else the options that were
+    given.  With ``source`` the refusal of a source that cannot list its labelled instants."""
+    given = {key: getattr(a, flag) for flag, key in LABEL_FLAGS if getattr(a, flag, None) is not None}
+    if not getattr(a, "track_score_every_step", False):
+        if given:
+            raise SystemExit(f"run_stream.py: --{next(f for f, k in LABEL_FLAGS if k in given)} needs --track_score_every_step")
+        return None
+    if not getattr(a, "track_score", False):
+        raise SystemExit("run_stream.py: --track_score_every_step needs --track_score")
+    try:
+        _label_options(given, "run_stream.py")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    if source is not None and not callable(getattr(source, "label_instants", None)):
+        raise SystemExit("run_stream.py: --track_score_every_step needs a source with label_instants() (its labelled "
+                         f"instants, sorted int64) besides labels(t); {type(source).__name__} has none")
+    return given
+
+
+def push_keyframe(stream, source, t):
+    """``source.labels(t)`` (x1, y1, x2, y2 boxes of lane 0, or None: a labelled instant with no box) into the stream's
+    label store as the keyframe of the instant ``t``."""
+    labelled = source.labels(int(t))
+    boxes, labels, ids = labelled if labelled is not None else (np.zeros((0, 4)), np.zeros(0), np.zeros(0))
+    boxes = np.asarray(boxes, np.float64).reshape(-1, 4)
+    xywh = np.concatenate([boxes[:, :2], boxes[:, 2:] - boxes[:, :2]], axis=1)
+    stream.push_labels(np.array([int(t)], np.int64), xywh[None], np.asarray(labels, np.int32).reshape(1, -1),
+                       np.asarray(ids, np.int64).reshape(1, -1))
 
 
 def identity_options(a):
@@ -403,11 +457,12 @@ def play(a, model, source, dev):
                          flicker=flicker_options(a), trail_us=getattr(a, "trail_us", None),
                          track=track_options(a), motion=motion_options(a), rescue=rescue_options(a), assign=assign_option(a),
                          score=score_options(a),
-                         identity=identity_options(a), hota=hota,
+                         identity=identity_options(a), hota=hota, labels=label_options(a),
                          decode=decode, max_decoded=getattr(a, "max_decoded", None),
                          t_base=int(source.t_range()[0]) if decode else None)      # (the words' times start at the sequence's)
     t0, t1 = source.t_range()
     out, last_frame = [], None
+    instants, pushed = (np.asarray(source.label_instants(), np.int64), 0) if stream.labels is not None else (None, 0)
     t_encoded = None                       # where the encoder of --decode stands (times relative to the sequence's start)
     a.stream_coasting = [] if stream.motion is not None else None      # per step the tracks it did not see
     for t_step in range(int(t0) + a.step_us, int(t1) + 1, a.step_us):
@@ -433,7 +488,13 @@ def play(a, model, source, dev):
             det = stream.step(xy, np.asarray(ev["t"], np.int64), np.asarray(ev["p"], np.int8), t_now=t_step, image=image,
                               frame=raw)
         out.append((t_step, det[0]))
-        labelled = source.labels(t_step) if stream.score is not None else None
+        if stream.labels is not None:
+            # the store stays one keyframe ahead of the step: every labelled instant up to the first one behind t_step
+            while pushed < len(instants) and (pushed == 0 or instants[pushed - 1] <= t_step):
+                push_keyframe(stream, source, instants[pushed])
+                pushed += 1
+            stream.score_step()                 # two launches: the labels at the step's own instant, then the scorer
+        labelled = source.labels(t_step) if stream.score is not None and stream.labels is None else None
         if labelled is not None:                # one more launch, on the step's own device arrays
             boxes, labels, ids = labelled
             stream.score_step(np.asarray(boxes, np.float32).reshape(1, -1, 4), np.asarray(labels, np.int32).reshape(1, -1),
@@ -452,6 +513,7 @@ def play(a, model, source, dev):
     if stream.score is not None:
         counters = stream.track_score()
         a.stream_score = dict(score_summary(counters, stream.scored_objects())["total"], steps=int(counters["steps"].sum()))
+    a.stream_labels = {k: int(v.sum()) for k, v in stream.label_counts().items()} if stream.labels is not None else None
     a.stream_identity = identity_summary(stream.identity())["total"] if stream.identity_options is not None else None
     a.stream_hota = hota_summary(stream.hota())["total"] if stream.hota_options is not None else None
     return out
@@ -483,7 +545,8 @@ def main(argv=None, model_factory=None, source=None):
     hota_options(a)                        # (in front of the two it implies)
     score_options(a)
     identity_options(a)
-    a.batch_size = 1                      # one sequence: one lane
+    label_options(a)
+    a.batch_size = 1                     # one sequence: one lane
     world, rank, dev = C.distributed()
     torch.manual_seed(42)
     np.random.seed(42)
@@ -493,6 +556,7 @@ def main(argv=None, model_factory=None, source=None):
                   "SYNTHETIC stand-in stream instead.", flush=True)
         source = SyntheticStream(a)
     score_options(a, source)               # (a source without labels is refused in front of the model too)
+    label_options(a, source)
     geometry = types.SimpleNamespace(width=int(getattr(source, "width", a.width)), height=int(getattr(source, "height", a.height)))
     args, net = (model_factory or C.build_model)(a, geometry, dev)
     net = net.eval()
@@ -548,6 +612,10 @@ def main(argv=None, model_factory=None, source=None):
                         f"{c['frag']} fragmentations, {c['miss']} misses, {c['false_pos']} false positives, MOTA "
                         f"{c['mota']:.3f}, MOTP {c['motp']:.3f}, {c['mostly_tracked']} mostly tracked, {c['mostly_lost']} "
                         "mostly lost")
+        if getattr(a, "stream_labels", None) is not None:
+            c = a.stream_labels
+            tracked += (f"; every step scored against {c['keyframes']} resident keyframes, interpolated: {c['labelled']} steps "
+                        f"labelled, {c['outside']} outside the keyframes, {c['gap']} in a gap")
         if getattr(a, "stream_identity", None) is not None:
             c = a.stream_identity
             tracked += (f"; IDF1 {c['idf1']:.3f}, IDP {c['idp']:.3f}, IDR {c['idr']:.3f} (IDTP {c['idtp']} of {c['gt_frames']} "
