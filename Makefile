@@ -14,7 +14,7 @@ $(LIB): $(OBJ)
 	@mkdir -p dagr_amd/lib
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJ) -L/opt/rocm/lib -lhipblaslt
 
-build/%.o: dagr_amd/csrc/%.hip dagr_amd/csrc/common.hpp dagr_amd/csrc/pool_common.hpp dagr_amd/csrc/stream_push.hpp dagr_amd/csrc/assign.hpp dagr_amd/csrc/stream_track.hpp dagr_amd/csrc/stream_box.hpp dagr_amd/csrc/stream_eval.hpp include/dagr_hip.h
+build/%.o: dagr_amd/csrc/%.hip dagr_amd/csrc/common.hpp dagr_amd/csrc/pool_common.hpp dagr_amd/csrc/stream_push.hpp dagr_amd/csrc/assign.hpp dagr_amd/csrc/stream_track.hpp dagr_amd/csrc/stream_box.hpp dagr_amd/csrc/stream_eval.hpp dagr_amd/csrc/stream_state.hpp include/dagr_hip.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -518,7 +518,12 @@ class StreamState:
 
     A HOTA stream (``enable_hota``, on an identity stream) owns HOTA's state (``dagr_stream_hota``): the alignment tables,
     the log of the labelled instants, the last solve's counts, and the solve's workspace.  ``run_score`` then makes a third
-    launch behind the identity step's; ``run_hota_solve`` is ``dagr_stream_hota_solve``."""
+    launch behind the identity step's; ``run_hota_solve`` is ``dagr_stream_hota_solve``.
+
+    A drawing stream (``enable_render``) owns the picture's state (``dagr_stream_render``): the per-pixel maps, the output
+    frames, a status word of its own and -- with trails, on a tracking stream -- the rings of the slots' last centres
+    (``dagr_stream_trail``).  A step with trails makes one more launch behind the tracker's (``run_trail``); ``run_render``
+    is the picture, on the last step's device arrays, whenever it is asked for."""
 
     def __init__(self, batch_size, window_us, device, max_lane_events=None):
         self.B, self.window_us, self.device = int(batch_size), int(window_us), torch.device(device)
@@ -559,6 +564,9 @@ class StreamState:
         self.labels = None                              # the options of its label store (dagr.streaming._label_options)
         self.labels_state, self.gt_labels = None, None  # the store; the last labelled step's (gt_box, gt_label, gt_id, n_gt)
         self._stepped, self._labelled = False, False    # a step since construction / reset(); whether run_labels has had it
+        self.render = None                              # the options of its picture (dagr.streaming._render_options)
+        self.render_size, self.render_colors, self.render_ws, self.render_flags, self.render_out = None, None, None, None, None
+        self.trail_rings, self._render_det = None, None # the trail rings; the last step's (det, n_keep) for run_render
 
     def stepped(self):
         """``forward_stream`` has staged a step: ``run_labels`` may run at its ``t_ref``, once."""
@@ -951,6 +959,77 @@ class StreamState:
             raise RuntimeError("this stream has no motion model (motion=): nothing coasts")
         return self.coast
 
+    # ------------------------------------------------------------------------------------ the picture
+    def enable_render(self, options, width, height):
+        """``run_render`` paints the lanes' frames (``dagr_stream_render``): ``options`` as
+        ``dagr.streaming._render_options`` returns them (``colors`` a uint8 ``[n, 3]`` array), ``width`` x ``height`` the
+        engine's.  Allocates the per-pixel maps (zero), the output, the status word and -- ``trail > 0``, after
+        ``enable_track`` -- the trail rings, empty; a step then ends with ``dagr_stream_trail`` (``run_trail``).  Nothing
+        is allocated after this."""
+        self.render = dict(options)
+        self.render_size = (int(width), int(height))
+        dev = self.device
+        if (self.render["trail"] > 0 or self.render["ids"]) and self.track is None:
+            raise RuntimeError("enable_render: trails and id plates need the tracker (enable_track first)")
+        self.render_colors = torch.from_numpy(np.ascontiguousarray(self.render["colors"], dtype=np.uint8)).to(dev)
+        self.render_ws = _state_buffer(dev, "dagr_stream_render_workspace_bytes", self.B, height, width)
+        self.render_flags = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.render_out = torch.zeros((self.B, height, width, 3), dtype=torch.uint8, device=dev)
+        if self.render["trail"] > 0:
+            self.trail_rings = _state_buffer(dev, "dagr_stream_trail_bytes", self.B, self.track["max_tracks"],
+                                             self.render["trail"])
+        self._reset_render()
+
+    def _reset_render(self):
+        """Zero maps, a clear status word, empty rings, and no step to draw."""
+        self.render_ws.zero_()
+        self.render_flags.zero_()
+        self._render_det = None
+        if self.trail_rings is not None:
+            _lib.check(_lib.lib().dagr_stream_trail_reset(_lib.ptr(self.trail_rings), self.trail_rings.numel(), self.B,
+                                                          self.track["max_tracks"], self.render["trail"],
+                                                          _lib.cur_stream(self.device)), "stream_trail_reset")
+
+    def run_trail(self):
+        """``dagr_stream_trail`` on the slots the step's tracker launch left, at the step's ``t_ref``: one launch, no host
+        wait (``run_track`` has looked ``t_ref`` up)."""
+        _lib.check(_lib.lib().dagr_stream_trail(_lib.ptr(self.trail_rings), self.trail_rings.numel(), self.B,
+                                                self.track["max_tracks"], self.render["trail"], _lib.ptr(self.track_state),
+                                                self.track_state.numel(), self._t_ref[2], _lib.cur_stream(self.device)),
+                   "stream_trail")
+
+    def run_render(self, base=None, base_stride=0, out=None):
+        """``dagr_stream_render`` on the last step's device arrays -- the resident events, ``det`` / ``n_keep``, the track
+        ids, the rings --, or on nothing but ``base`` before the first step: uint8 ``[B, H, W, 3]`` (``out``, default the
+        stream's own), valid until the next call.  Three launches at most, no host wait."""
+        if self.render is None:
+            raise RuntimeError("this stream draws nothing (render=): it has no render_step")
+        o, P = self.render, _lib.ptr
+        out = self.render_out if out is None else out
+        W, H = self.render_size
+        det, n_keep = self._render_det if self._render_det is not None else (None, None)
+        drawn = det is not None
+        _lib.check(_lib.lib().dagr_stream_render(
+            P(self.state) if drawn else None, self.B, self.cap, -1 if o["event_window_us"] is None else o["event_window_us"],
+            o["alpha"], P(det), P(n_keep), int(det.shape[1]) if drawn else 0,
+            P(self.track_ids) if drawn and self.track is not None else None,
+            P(self.trail_rings), self.track["max_tracks"] if self.trail_rings is not None else 0, o["trail"], o["linewidth"],
+            1 if o["ids"] else 0, o["id_scale"], P(self.render_colors), int(self.render_colors.shape[0]), P(base), base_stride,
+            P(out), H, W, P(self.render_flags), P(self.render_ws), self.render_ws.numel(), _lib.cur_stream(self.device)),
+            "stream_render")
+        return out
+
+    def trail_arrays(self):
+        """The rings read back as ``(id int64 [B, M], count int32 [B, M], pt int32 [B, M, trail, 2])``, the layout
+        include/dagr_hip.h documents (copies; synchronises)."""
+        if self.trail_rings is None:
+            raise RuntimeError("this stream keeps no trails (render= with trail > 0): it has no rings")
+        n, T = self.B * self.track["max_tracks"], self.render["trail"]
+        shape = (self.B, self.track["max_tracks"])
+        r = self.trail_rings
+        return (r[:8 * n].view(torch.int64).view(shape).cpu().numpy(), r[8 * n:12 * n].view(torch.int32).view(shape).cpu().numpy(),
+                r[12 * n:12 * n + 8 * n * T].view(torch.int32).view(*shape, T, 2).cpu().numpy())
+
     # ------------------------------------------------------------------------------------ the push stages
     def _enable(self, name, *description, **more):
         """The stage ``name`` (as its option tuple is called), with the scratch of a push of 4096 rows to begin with."""
@@ -1114,6 +1193,8 @@ class StreamState:
             self._reset_hota()
         if self.labels_state is not None:
             self._reset_labels()
+        if self.render is not None:
+            self._reset_render()
         self._stepped, self._labelled = False, False
         self.status.zero_()
         self.lane_count.zero_()
@@ -2438,7 +2519,8 @@ class WindowEngine:
         instants the staging left: one plain launch on the same stream, outside the captured graphs, so every mode and
         body is covered without a re-capture; ``st.track_ids`` / ``st.track_hits`` hold the result.  With a motion model
         (``st.motion``) that launch is ``dagr_stream_track_cv``, which also leaves ``st.track_boxes`` / ``st.track_vel`` and the
-        coast lists.
+        coast lists.  A drawing stream with trails (``st.trail_rings``) makes one more plain launch right behind it,
+        ``dagr_stream_trail``.
         Returns ``(out, (det, n_keep))``, both valid until the engine's next call.
 
         ``--use_image``: the window has two bodies.  The frame body runs the image branch on the stream's frame
@@ -2558,6 +2640,10 @@ class WindowEngine:
         st.stepped()
         if st.track is not None:                     # a plain launch behind the window, captured or not: the track ids
             st.run_track(*det)
+        if st.render is not None:                    # the picture is made on request (run_render); the trails follow every step
+            st._render_det = det
+            if st.trail_rings is not None:
+                st.run_trail()
         return out, det
 
     def stream_counted(self, st):

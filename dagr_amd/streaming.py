@@ -395,6 +395,15 @@ between two keyframes has no row between them.  No real DSEC sequence was at han
 ``interpolate_tracks`` output on the golden frames, the rest is synthetic.  A stream without ``labels`` makes exactly the
 library calls it makes without the store.
 
+The picture (``render=``: ``None`` is off, ``True`` takes the defaults, a dict sets ``event_window_us`` (``None``: every
+resident event), ``alpha`` ([0, 1], default 0.5), ``linewidth`` (1..7), ``trail`` (0..64 centres, default 32), ``ids``,
+``id_scale`` (1..4) and ``colors`` (uint8 ``[n, 3]`` BGR, 2 <= n <= 256)): ``render_step()`` paints one frame per lane on
+the device from what the last step left there -- base, events, trails, box outlines, id plates, in this order, every pixel
+on its own (``dagr_stream_render``) --, and a tracking stream with trails ends every step with ``dagr_stream_trail``, which
+keeps a ring of the last centres of the track in every slot.  include/dagr_hip.h states the rule and ``RenderDefinition``
+below is the same in numpy; it is not restated here.  The look is this project's own, no real camera data was at hand, and
+nothing is displayed.  A stream without ``render`` makes exactly the library calls it makes without it.
+
 Camera words (``decode="evt3"`` or ``"evt2"``): an event camera delivers words, not arrays.  A decoding stream takes the
 camera's words (``step_words`` / ``step_words_device``) and decodes them on the device (``dagr_stream_decode``) in front of
 everything above: decode, then the flicker / trail filters, then the noise filter, then ``downsample=``, then the window.  The two formats are stated here as
@@ -477,7 +486,7 @@ how many events a push decoded, so its bound of the window grows by ``min(max_de
 """
 import numpy as np
 
-from ._lib import DEFINES
+from ._lib import DEFINES, ENUMS
 from .utils.synthetic import format_data_np
 
 STATUS_BITS = ((1, "a timestamp goes backwards inside a lane (within a push or against the lane's newest event)"),
@@ -2065,6 +2074,255 @@ class StreamDefinition:
         return format_data_np(x, y, t_rel, self.W, self.H, self.time_window), p.astype(np.float32).reshape(-1, 1), batch
 
 
+RENDER_DEFAULTS = dict(event_window_us=None, alpha=0.5, linewidth=1, trail=32, ids=True, id_scale=1, colors=None)
+RENDER_MAX_TRAIL, RENDER_MAX_LINEWIDTH = DEFINES["DAGR_RENDER_MAX_TRAIL"], DEFINES["DAGR_RENDER_MAX_LINEWIDTH"]
+RENDER_MAX_ID_SCALE = DEFINES["DAGR_RENDER_MAX_ID_SCALE"]
+RENDER_STATUS_BITS = ((DEFINES["DAGR_RENDER_BAD_POLARITY"], "a drawn event's polarity p gives a channel p - 1 outside [-3, 2]"),
+                      (DEFINES["DAGR_RENDER_BAD_CLASS"], "a drawn row's class has no colour"),
+                      (DEFINES["DAGR_RENDER_LONG_SEGMENT"], "a trail segment is longer than W + H steps"))
+RENDER_GLYPHS = tuple(ENUMS[f"DAGR_RENDER_GLYPH_{d}"] for d in range(10))      # include/dagr_hip.h holds the bitmaps
+RENDER_COORD_MAX = 1 << 20
+# the track palette, BGR: entry 0 is a row without a track, a track id takes 1 + (id - 1) % 31
+RENDER_PALETTE = (
+    (128, 128, 128), (10, 10, 216), (255, 128, 76), (12, 255, 154), (197, 65, 216), (214, 255, 12), (76, 173, 255),
+    (216, 10, 62), (76, 255, 84), (93, 12, 255), (216, 160, 65), (12, 255, 235), (255, 76, 217), (113, 216, 10),
+    (76, 113, 255), (255, 33, 12), (65, 216, 122), (174, 12, 255), (255, 247, 76), (10, 164, 216), (255, 76, 157),
+    (52, 255, 12), (84, 65, 216), (255, 114, 12), (76, 255, 203), (216, 10, 216), (202, 255, 76), (12, 112, 255),
+    (216, 65, 83), (12, 255, 54), (158, 76, 255), (216, 166, 10))
+
+
+def _render_options(render, track_options, who):
+    """``render=`` of a stream, checked: None (off) or the dict of ``event_window_us``, ``alpha``, ``linewidth``, ``trail``,
+    ``ids``, ``id_scale`` and ``colors`` with the defaults filled in and ``colors`` resolved to a uint8 ``[n, 3]`` BGR array
+    (default: ``RENDER_PALETTE`` with ``track=``, ``bbox_viz.outline_colors()`` per class without); ``track_options`` is
+    what ``_track_options`` returned.  Trails and id plates are the tracker's: ``render=True`` without ``track=`` switches
+    them off, a dict that asks for them without ``track=`` is refused.  Refusals by name."""
+    opt = _options(render, "render", RENDER_DEFAULTS, who)
+    if opt is None:
+        return None
+    if track_options is None:
+        for key, on in (("trail", lambda v: v != 0), ("ids", lambda v: v is not False)):
+            if isinstance(render, dict) and key in render and on(render[key]):
+                raise ValueError(f"{who}: render {key} = {render[key]!r} needs track= (trails and id plates are the tracker's)")
+        opt.update(trail=0, ids=False)
+    w = opt["event_window_us"]
+    if w is not None and (not _is_int(w) or not 0 <= int(w) < 1 << 63):
+        raise ValueError(f"{who}: render event_window_us = {w!r} must be None (every resident event) or an int of "
+                         "microseconds >= 0")
+    if not _is_real(opt["alpha"]) or not 0 <= opt["alpha"] <= 1:
+        raise ValueError(f"{who}: render alpha = {opt['alpha']!r} must be a float in [0, 1]")
+    for key, lo, hi in (("linewidth", 1, RENDER_MAX_LINEWIDTH), ("trail", 0, RENDER_MAX_TRAIL), ("id_scale", 1, RENDER_MAX_ID_SCALE)):
+        if not _is_int(opt[key]) or not lo <= int(opt[key]) <= hi:
+            raise ValueError(f"{who}: render {key} = {opt[key]!r} must be an int in {lo}..{hi}")
+    if not isinstance(opt["ids"], (bool, np.bool_)):
+        raise ValueError(f"{who}: render ids = {opt['ids']!r} must be True or False")
+    colors = opt["colors"]
+    if colors is None:
+        if track_options is not None:
+            colors = np.array(RENDER_PALETTE, np.uint8)
+        else:
+            from .visualization.bbox_viz import outline_colors
+            colors = outline_colors()
+    else:
+        colors = np.asarray(colors)
+        if colors.dtype != np.uint8 or colors.ndim != 2 or colors.shape[1] != 3 or not 2 <= colors.shape[0] <= 256:
+            raise ValueError(f"{who}: render colors must be a uint8 [n, 3] BGR table with 2 <= n <= 256, got "
+                             f"{colors.dtype} {list(colors.shape)}")
+    return dict(event_window_us=None if w is None else int(w), alpha=float(opt["alpha"]), linewidth=int(opt["linewidth"]),
+                trail=int(opt["trail"]), ids=bool(opt["ids"]), id_scale=int(opt["id_scale"]),
+                colors=np.ascontiguousarray(colors, dtype=np.uint8))
+
+
+def render_color_index(id, n_colors):
+    """The palette entry of a track id: 0 for id 0, else ``1 + (id - 1) % (n_colors - 1)``, the id as an unsigned 64-bit
+    number."""
+    id = int(id)
+    return 0 if id == 0 else 1 + ((id - 1) % (1 << 64)) % (n_colors - 1)
+
+
+def render_line(x0, y0, x1, y1):
+    """The pixels of the trail segment ``(x0, y0) -> (x1, y1)``, ``k = 0 .. n`` along its major axis: int64 ``[n + 1, 2]``."""
+    dx, dy = int(x1) - int(x0), int(y1) - int(y0)
+    n = max(abs(dx), abs(dy))
+    k = np.arange(n + 1, dtype=np.int64)
+    sx, sy = (dx > 0) - (dx < 0), (dy > 0) - (dy < 0)
+    if abs(dx) >= abs(dy):
+        off = (2 * k * abs(dy) + n) // (2 * n) if n else 0 * k
+        return np.stack([x0 + sx * k, y0 + sy * off], 1)
+    off = (2 * k * abs(dx) + n) // (2 * n)
+    return np.stack([x0 + sx * off, y0 + sy * k], 1)
+
+
+def render_plate(id, xa, ya, scale):
+    """The id plate of a row whose rectangle starts at ``(xa, ya)``: ``(left, top, mask)`` with ``mask`` a bool
+    ``[7 * scale, (4 * nd + 1) * scale]`` array, True on the digits' pixels (black), False on the plate's (the row's colour)."""
+    text = str((int(id) % (1 << 64)) % 1000000)
+    s, nd = int(scale), len(text)
+    cells = np.zeros((7, 4 * nd + 1), bool)
+    for d, ch in enumerate(text):
+        bits = RENDER_GLYPHS[int(ch)]
+        for gy in range(5):
+            for gx in range(3):
+                cells[1 + gy, 1 + 4 * d + gx] = (bits >> (14 - (gy * 3 + gx))) & 1
+    top = ya - 7 * s if ya - 7 * s >= 0 else ya + 1
+    return int(xa), int(top), np.repeat(np.repeat(cells, s, 0), s, 1)
+
+
+def _render_coord(v):
+    """``(int32)floorf(clamp(v, -2^20, 2^20))`` of finite fp32 values."""
+    return np.floor(np.clip(np.asarray(v, np.float32), -RENDER_COORD_MAX, RENDER_COORD_MAX)).astype(np.int64)
+
+
+class RenderDefinition:
+    """The picture of include/dagr_hip.h (``dagr_stream_trail`` / ``dagr_stream_render``) in numpy.  ``trail_step`` is one
+    ``dagr_stream_trail`` on the tracker's slots (what ``TrackDefinition`` or ``EventStream.tracks`` hold: ``id``,
+    ``t_last``, ``box`` over ``[B, max_tracks]``) and keeps the rings (``ring_id``, ``ring_count``, ``ring_pt``);
+    ``frames`` paints the lanes' frames from the resident events (``lanes`` / ``t_ref`` as ``StreamDefinition`` keeps them,
+    fed the stream's pushes), the step's ``det`` / ``n_keep`` and ``track_id``, and returns uint8 ``[B, H, W, 3]``;
+    ``status`` accumulates the flags.  ``render`` as ``EventStream`` takes it; ``max_tracks`` None: no tracker."""
+
+    def __init__(self, batch_size, width, height, render=True, max_tracks=None):
+        self.B, self.W, self.H = int(batch_size), int(width), int(height)
+        self.M = None if max_tracks is None else int(max_tracks)
+        self.options = _render_options(render, None if max_tracks is None else True, "RenderDefinition")
+        if self.options is None:
+            raise ValueError("RenderDefinition: render = None draws nothing")
+        self.reset()
+
+    def reset(self):
+        T = self.options["trail"]
+        self.status = 0
+        self.ring_id = self.ring_count = self.ring_pt = None
+        if T > 0:
+            self.ring_id = np.zeros((self.B, self.M), np.int64)
+            self.ring_count = np.zeros((self.B, self.M), np.int32)
+            self.ring_pt = np.zeros((self.B, self.M, T, 2), np.int32)
+
+    def trail_step(self, slot_id, slot_t_last, slot_box, t_ref):
+        """One ``dagr_stream_trail``: ``slot_id`` / ``slot_t_last`` int64 ``[B, M]``, ``slot_box`` fp32 ``[B, M, 4]`` as the
+        tracker left them, ``t_ref`` the step's instants (``None`` or ``NEVER``: the lane has none)."""
+        T = self.options["trail"]
+        if T == 0:
+            return
+        box = np.asarray(slot_box, np.float32).reshape(self.B, self.M, 4)
+        for b in range(self.B):
+            ref = NEVER if t_ref[b] is None else int(t_ref[b])
+            for s in range(self.M):
+                id = int(slot_id[b][s])
+                if id == 0:                             # a free slot
+                    self.ring_id[b, s], self.ring_count[b, s] = 0, 0
+                    continue
+                if int(self.ring_id[b, s]) != id:       # the slot has been taken by another track
+                    self.ring_id[b, s], self.ring_count[b, s] = id, 0
+                if ref == NEVER or int(slot_t_last[b][s]) != ref:
+                    continue                            # not seen this step: a coasting track appends nothing
+                with np.errstate(over="ignore", invalid="ignore"):
+                    cx = np.float32(box[b, s, 0] + box[b, s, 2]) * np.float32(0.5)
+                    cy = np.float32(box[b, s, 1] + box[b, s, 3]) * np.float32(0.5)
+                if not (np.isfinite(cx) and np.isfinite(cy)):
+                    continue
+                c = int(self.ring_count[b, s])
+                self.ring_pt[b, s, c % T] = (_render_coord(cx), _render_coord(cy))
+                c += 1
+                self.ring_count[b, s] = T + (1 << 30) % T if c >= 1 << 30 else c
+
+    def ring_points(self, b, s):
+        """The points of ring ``(b, s)``, oldest first: int32 ``[n, 2]``."""
+        T, c = self.options["trail"], int(self.ring_count[b, s])
+        if c <= T:
+            return self.ring_pt[b, s, :c]
+        return self.ring_pt[b, s, (c + np.arange(T)) % T]
+
+    def events_layer(self, img, x, y, p):
+        """Layer 2 on one lane's image (uint8 ``[H, W, 3]``, in place): the in-window events ``x``, ``y``, ``p`` in arrival
+        order, by ``draw_events_on_image``'s rule."""
+        alpha = np.float64(self.options["alpha"])
+        last = {}
+        for i in range(len(x)):
+            ch = int(p[i]) - 1
+            if ch < -3 or ch > 2:
+                self.status |= RENDER_STATUS_BITS[0][0]
+                continue
+            if 0 <= int(x[i]) < self.W and 0 <= int(y[i]) < self.H:
+                last[(int(y[i]), int(x[i]))] = ch
+        for (yy, xx), ch in last.items():
+            v = np.trunc(alpha * img[yy, xx].astype(np.float64)).astype(np.uint8)
+            v[ch] = np.uint8(int(np.trunc(np.float64(v[ch]) + 255.0 * (1.0 - alpha))) & 255)
+            img[yy, xx] = v
+
+    def frames(self, lanes=None, t_ref=None, det=None, n_keep=None, track_id=None, base=None):
+        """The frames of a step.  ``lanes``: per lane a dict of ``x``, ``y``, ``t``, ``p`` (the resident events in arrival
+        order; None: no events), ``t_ref`` per lane (None / ``NEVER``: none yet); ``det`` fp32 ``[B, A, 6]``, ``n_keep``
+        ``[B]`` (None: no rows); ``track_id`` int64 ``[B, A]`` or None (colour by class); ``base`` uint8 ``[B, H, W, 3]`` or
+        ``[H, W, 3]`` or None (black)."""
+        o, B, H, W = self.options, self.B, self.H, self.W
+        colors, hw, s = o["colors"], o["linewidth"] // 2, o["id_scale"]
+        n_colors = len(colors)
+        out = np.zeros((B, H, W, 3), np.uint8)
+        if base is not None:
+            out[:] = np.asarray(base, np.uint8)
+        for b in range(B):
+            img = out[b]
+            ref = None if lanes is None or t_ref is None or t_ref[b] is None or int(t_ref[b]) == NEVER else int(t_ref[b])
+            if ref is not None:                                                             # 2 events
+                lane = lanes[b]
+                t = np.asarray(lane["t"], np.int64)
+                keep = np.ones(len(t), bool)
+                if o["event_window_us"] is not None:
+                    keep = np.array([0 <= ref - int(v) < o["event_window_us"] for v in t], bool)
+                self.events_layer(img, np.asarray(lane["x"])[keep], np.asarray(lane["y"])[keep], np.asarray(lane["p"])[keep])
+            if self.ring_id is not None:                                                    # 3 trails: a higher slot on top
+                for slot in range(self.M):
+                    pts = self.ring_points(b, slot).astype(np.int64)
+                    if int(self.ring_id[b, slot]) == 0 or len(pts) < 2:
+                        continue
+                    c = colors[render_color_index(self.ring_id[b, slot], n_colors)]
+                    for p0, p1 in zip(pts[:-1], pts[1:]):
+                        if max(abs(int(p1[0] - p0[0])), abs(int(p1[1] - p0[1]))) > W + H:
+                            self.status |= RENDER_STATUS_BITS[2][0]
+                            continue
+                        q = render_line(p0[0], p0[1], p1[0], p1[1])
+                        q = q[(q[:, 0] >= 0) & (q[:, 0] < W) & (q[:, 1] >= 0) & (q[:, 1] < H)]
+                        img[q[:, 1], q[:, 0]] = c
+            if det is None:
+                continue
+            A = int(np.asarray(det).shape[1])
+            rows = []
+            for r in range(min(max(int(n_keep[b]), 0), A)):                                  # 4 boxes, a later row on top
+                d = np.asarray(det[b][r], np.float32)
+                if not np.all(np.isfinite(d[:4])):
+                    continue
+                cx1, cy1, cx2, cy2 = (int(v) for v in _render_coord(d[:4]))
+                xa, xb, ya, yb = min(cx1, cx2), max(cx1, cx2), min(cy1, cy2), max(cy1, cy2)
+                if track_id is not None:
+                    id = int(track_id[b][r])
+                    c = colors[render_color_index(id, n_colors)]
+                else:
+                    id = 0
+                    if not 0 <= d[5] < n_colors:
+                        self.status |= RENDER_STATUS_BITS[1][0]
+                        continue
+                    c = colors[int(d[5])]
+                x_lo, x_hi, y_lo, y_hi = max(xa - hw, 0), min(xb + hw, W - 1), max(ya - hw, 0), min(yb + hw, H - 1)
+                if x_lo <= x_hi and y_lo <= y_hi:           # (the band lies inside this window of the image)
+                    yy, xx = np.mgrid[y_lo:y_hi + 1, x_lo:x_hi + 1]
+                    inside = (xx >= xa) & (xx <= xb) & (yy >= ya) & (yy <= yb)
+                    dist = np.where(inside, np.minimum(np.minimum(xx - xa, xb - xx), np.minimum(yy - ya, yb - yy)),
+                                    np.maximum(np.maximum(np.maximum(xa - xx, xx - xb), 0),
+                                               np.maximum(np.maximum(ya - yy, yy - yb), 0)))
+                    img[y_lo:y_hi + 1, x_lo:x_hi + 1][dist <= hw] = c
+                rows.append((id, xa, ya, c))
+            for id, xa, ya, c in rows if o["ids"] else ():                                  # 5 plates, above every outline
+                if id == 0:
+                    continue
+                left, top, mask = render_plate(id, xa, ya, s)
+                x_lo, x_hi, y_lo, y_hi = max(left, 0), min(left + mask.shape[1], W), max(top, 0), min(top + mask.shape[0], H)
+                if x_lo < x_hi and y_lo < y_hi:             # clipped to the image per pixel
+                    part = mask[y_lo - top:y_hi - top, x_lo - left:x_hi - left]
+                    img[y_lo:y_hi, x_lo:x_hi] = np.where(part[:, :, None], np.uint8(0), c)
+        return out
+
+
 DECODE_FORMATS = {"evt2": (DEFINES["DAGR_DECODE_EVT2"], np.uint32, 1), "evt3": (DEFINES["DAGR_DECODE_EVT3"], np.uint16, 12)}
 DECODE_COUNTERS = ("decoded", "unsynced", "outside", "skipped")
 DECODE_STATE = ("high", "low", "loops", "y", "base_x", "pol", "synced")
@@ -2298,6 +2556,17 @@ class EventStream:
     ``frame_size`` (``(W_f, H_f)``) and ``frame_bgr``: the steps may carry raw sensor frames (``frame=``), which
     ``dagr_stream_frame`` turns into the model's image on the device (``frame_definition``) with the stream's
     ``downsample`` factors, or 1 without ``downsample``.
+    ``render`` (``None``: off, ``True``: the defaults, or a dict of ``event_window_us``, ``alpha``, ``linewidth``, ``trail``,
+    ``ids``, ``id_scale``, ``colors``): ``render_step(base=None, out=None)`` paints the lanes' frames on the device --
+    the resident events of the last ``event_window_us`` microseconds (``None``: all of them), the trails of the last
+    ``trail`` centres of every track, the step's box outlines in the colour of their track id (without ``track=``: of
+    their class) and the ids on plates -- from the stream's own arrays: ``dagr_stream_render``, three launches at most, no
+    host wait, nothing uploaded (include/dagr_hip.h states the rule, ``RenderDefinition`` is the same in numpy; the look is
+    this project's own).  The frames are the engine's ``H x W`` -- with ``downsample=`` the model's resolution, where the
+    resident events live.  Trails and plates need ``track=``: ``render=True`` without it draws neither, a dict that asks
+    for one is refused.  A step of a tracking stream with ``trail > 0`` issues one more launch right behind the
+    tracker's, ``dagr_stream_trail``; nothing else in a step changes, and a stream built without ``render`` issues exactly
+    the calls it issued before.  ``trails()`` reads the rings back, ``render_status()`` the picture's flags.
 
     ``--use_image`` models: the image branch runs once per frame.  A step runs the frame body (image branch included)
     when it brings a frame (``image=`` or ``frame=``; contents are not compared), on the stream's first step, and whenever
@@ -2311,11 +2580,12 @@ class EventStream:
     def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
                  max_lane_events=None, denoise_us=None, refractory_us=None, track=None, motion=None, rescue=None,
                  decode=None, max_decoded=None, t_base=None, flicker=None, trail_us=None, score=None,
-                 identity=None, assign=None, hota=None, labels=None):
+                 identity=None, assign=None, hota=None, labels=None, render=None):
         import torch
         self.model = model
         self.labels = _label_options(labels, "EventStream")
         self.track = _track_options(track, "EventStream")
+        self.render = _render_options(render, self.track, "EventStream")
         self.motion = _motion_options(motion, self.track, "EventStream")
         self.rescue = _rescue_options(rescue, self.track, "EventStream")
         self.assign = _assign_options(assign, self.track, "EventStream")
@@ -2377,6 +2647,8 @@ class EventStream:
             self.state.enable_hota(self.hota_options)
         if self.labels is not None:
             self.state.enable_labels(self.labels)
+        if self.render is not None:
+            self.state.enable_render(self.render, eng.W, eng.H)
         self._label_newest = [None] * eng.B     # per lane the newest instant a HOST push has offered (push_labels' check)
         self._zeros = None
         self.outputs = None      # the last step's decoded head outputs [B, A, 5 + classes], valid until the engine's next call
@@ -2689,6 +2961,55 @@ class EventStream:
         that continued a track: int64 [B] (synchronises).  Raises without ``rescue=``."""
         return self.state.rescued()
 
+    def render_step(self, base=None, out=None):
+        """The lanes' frames of the last step, uint8 BGR ``[B, H, W, 3]`` on the device (class docstring; needs
+        ``render=``): ``dagr_stream_render`` on the stream's own arrays, no host wait.  ``base``: a uint8 BGR device tensor
+        ``[B, H, W, 3]`` or ``[H, W, 3]`` (one image under every lane) to paint on; without it the base is black.  ``out``
+        (default: the stream's own frames) may be ``base`` itself.  The result is valid until the next ``render_step``.  It
+        may be called after any step, any number of times -- two calls after one step give equal frames --, and before the
+        first step it returns the base.  What it draws are the arrays the last step left, so it belongs in front of the
+        engine's next call."""
+        import torch
+        if self.render is None:
+            raise RuntimeError("EventStream: this stream draws nothing (render=): it has no render_step")
+        eng = self.model.engine()
+        shape, stride = (self.B, eng.H, eng.W, 3), 0
+        for name, v in (("base", base), ("out", out)):
+            if v is None:
+                continue
+            ok = torch.is_tensor(v) and v.dtype == torch.uint8 and v.device == self.device and v.is_contiguous() and \
+                (tuple(v.shape) == shape or (name == "base" and tuple(v.shape) == shape[1:]))
+            if not ok:
+                raise ValueError(f"EventStream: render_step {name}= is a contiguous uint8 {list(shape)}"
+                                 + (f" or {list(shape[1:])}" if name == "base" else "") + f" tensor on {self.device}")
+        if base is not None:
+            stride = eng.H * eng.W * 3 if base.dim() == 4 else 0
+            if stride == 0 and self.B > 1 and out is not None and out.data_ptr() == base.data_ptr():
+                raise ValueError("EventStream: render_step out= cannot be a base= that every lane shares")
+        return self.state.run_render(base, stride, out)
+
+    def trails(self):
+        """The trail rings of a drawing stream with ``trail > 0``, per lane a dict of track id -> int32 ``[n, 2]`` centres
+        ``(x, y)``, oldest first (copies; synchronises)."""
+        ids, counts, pts = self.state.trail_arrays()
+        T, out = self.render["trail"], []
+        for b in range(self.B):
+            lane = {}
+            for s in np.nonzero(ids[b])[0]:
+                c = int(counts[b, s])
+                lane[int(ids[b, s])] = pts[b, s, :c].copy() if c <= T else pts[b, s, (c + np.arange(T)) % T]
+            out.append(lane)
+        return out
+
+    def render_status(self):
+        """The picture's flags since the last call, as a list of their descriptions (``RENDER_STATUS_BITS``); the word is
+        cleared (synchronises)."""
+        if self.render is None:
+            raise RuntimeError("EventStream: this stream draws nothing (render=): it has no render_status")
+        flag = int(self.state.render_flags.item())
+        self.state.render_flags.zero_()
+        return [text for bit, text in RENDER_STATUS_BITS if flag & bit]
+
     def push_labels(self, t, xywh, label, id, n=None, lanes=None):
         """Labelled keyframes into the lanes' stores (module docstring; needs ``labels=``): ONE launch
         (``dagr_stream_labels_push``), no host wait.  ``t`` int64 ``[L]`` and ``xywh`` fp64 ``[L, rows, 4]`` (top-left plus
@@ -2891,7 +3212,7 @@ class EventStream:
         """Empty the stream: no resident events, no reference instants, zero change maps, empty stamp maps, every pixel of
         the flicker / trail filters in its initial state, zero dropped, filtered and suppressed counts, zero decoder states and counters, a clear status word, zero step counters; no tracks, ids from 1 again, zero untracked and rescued counts; the
         scorer's object tables empty and its counters zero (and no step left to score); the identity state and HOTA's state and log empty; the label
-        store empty and its counters zero.  The
+        store empty and its counters zero; the trail rings empty, the picture's flags clear and no step left to draw.  The
         frame in force stays, and the next step runs it through the image branch again."""
         self.state.reset()
         self._label_newest = [None] * self.B

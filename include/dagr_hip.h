@@ -969,6 +969,93 @@ int dagr_stream_labels_at(void *state, size_t bytes, int32_t B, int32_t max_keyf
                           const int64_t *t_ref, int64_t max_gap_us, double min_height, double min_diag,
                           float *gt_box, int32_t *gt_label, int64_t *gt_id, int32_t *n_gt, void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * Event stream picture: events, boxes, track ids and trails of a step, drawn on the device
+ *   dagr_stream_render paints one uint8 BGR frame [H, W, 3] per lane from what a stream keeps on the device -- the
+ *   resident raw events of a dagr_stream_stage state, the step's det / n_keep, the tracker's track_id, and the trail rings
+ *   dagr_stream_trail keeps from the tracker's slots.  Three launches at most, no host synchronisation, and no result that
+ *   depends on the order of execution: every pixel is decided independently.  The look is this project's own;
+ *   dagr_amd/streaming.py: RenderDefinition is the same in numpy, byte for byte.
+ *
+ * Layers of lane b, in this order:
+ *   1 base:    base[b] (base + b * base_stride bytes; base_stride 0: one image for every lane), or 0 when base is NULL.
+ *   2 events:  (state != NULL) the lane's resident events -- the segment seg[b] of the current raw set, in arrival order --
+ *              with t <= t_ref[b] and t_ref[b] - t < event_window_us (int64; event_window_us < 0: every resident event).  A
+ *              lane with t_ref[b] = INT64_MIN draws none.  An event whose p - 1 lies outside [-3, 2] is dropped (status bit
+ *              0); one outside [0, W) x [0, H) is skipped.  A pixel hit by at least one of them becomes, as dagr_viz_render
+ *              states it, trunc(alpha * v) on its three channels, then channel p - 1 (wrapped like a Python index) of the
+ *              LAST such event gets trunc(that + 255 * (1 - alpha)); float64.
+ *   3 trails:  (rings != NULL) ring (b, s) with at least two points draws the segments between consecutive points, oldest
+ *              first.  Segment P0 -> P1 with dx = x1 - x0, dy = y1 - y0, n = max(|dx|, |dy|): the pixels k = 0 .. n along
+ *              the major axis (x when |dx| >= |dy|), major = major0 + sign(dmajor) * k, minor = minor0 + sign(dminor) *
+ *              ((2 * k * |dminor| + n) / (2 * n)) (integer division; n = 0: the point itself), clipped to the image.  A
+ *              segment with n > W + H is not drawn (status bit 2).  A pixel on several trails takes the one of the HIGHEST
+ *              slot, in the colour of the ring's id (below).
+ *   4 boxes:   the rows r < min(n_keep[b], A) of det[b] (x1, y1, x2, y2, score, label), in row order, a later row on top.
+ *              A row with a non-finite coordinate is skipped.  Corners: (int32_t)floorf(clamp(v, -2^20, 2^20)); the
+ *              rectangle is [min(x1, x2), max(x1, x2)] x [min(y1, y2), max(y1, y2)] = [xa, xb] x [ya, yb], and a pixel
+ *              belongs to the outline by dagr_viz_render's rule: Chebyshev distance to the rectangle's border <=
+ *              linewidth / 2.  Colour: with track_id, colors[0] for id 0, else colors[1 + (id - 1) % (n_colors - 1)] (the
+ *              id as an unsigned 64-bit number); without, colors[(int32_t)label], and a label outside [0, n_colors) skips
+ *              the row (status bit 1).
+ *   5 plates:  (ids != 0, track_id != NULL) the same rows with id != 0, in row order, a later row on top, above every
+ *              outline.  Text: the decimal digits of id % 1000000 (unsigned), nd of them, no leading zeros.  With s =
+ *              id_scale the plate is (4 * nd + 1) * s wide and 7 * s high, its left edge at xa, its rows ya - 7 * s ..
+ *              ya - 1, or, when ya - 7 * s < 0, ya + 1 .. ya + 7 * s; filled with the row's colour.  Digit d (0: the most
+ *              significant) is the 3 x 5 glyph below scaled by s with its top-left at (xa + (1 + 4 * d) * s, top + s), in
+ *              black.  Clipped to the image per pixel.
+ * DAGR_RENDER_GLYPH_<d>: 15 bits, row major, bit 14 the top-left pixel and bit 0 the bottom-right one.
+ *
+ * rings: dagr_stream_trail_bytes(B, max_tracks, trail) bytes (0: B outside 1..65535, max_tracks outside
+ *        1..DAGR_TRACK_MAX_TRACKS or trail outside 1..DAGR_RENDER_MAX_TRAIL), 8-byte aligned, dagr_stream_trail_reset before
+ *        the first step and to empty them.  With n = B * max_tracks, ring (b, s) at index i = b * max_tracks + s:
+ *          id    int64 [n]           at byte 0       (0: the ring is empty)
+ *          count int32 [n]           at byte  8 * n  (points appended so far; the point appended at count c sits at
+ *                                                     c % trail, so the ring's points are, oldest first, 0 .. count - 1
+ *                                                     while count <= trail and then (count + j) % trail, j = 0 .. trail - 1;
+ *                                                     a count that reaches 2^30 goes on from trail + 2^30 % trail)
+ *          pt    int32 [n, trail, 2] at byte 12 * n  (x, y)
+ * dagr_stream_trail, one launch behind the tracker's on the slots it left (tracks / tracks_bytes: a dagr_stream_track or
+ * a dagr_stream_track_cv state, told apart by tracks_bytes, which must be the one's or the other's _bytes), per slot:
+ * a free slot (id 0) empties its ring; a slot whose id differs from the ring's restarts the ring under the slot's id;
+ * then, if t_ref[b] != INT64_MIN and the slot's t_last == t_ref[b] (the step saw the track; a coasting track appends
+ * nothing), the centre cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f of the slot's box (fp32, no contraction) is appended
+ * as (int32_t)clamp(floorf(c), -2^20, 2^20), unless cx or cy is not finite.
+ *
+ * dagr_stream_render: state / capacity a dagr_stream_stage state (NULL: no events); det fp32 [B, A, 6] and n_keep int32
+ * [B] (A = 0: no rows, both may then be NULL); track_id int64 [B, A] or NULL; rings or NULL (then max_tracks and trail are
+ * not read); alpha in [0, 1]; linewidth 1..DAGR_RENDER_MAX_LINEWIDTH; id_scale 1..DAGR_RENDER_MAX_ID_SCALE; colors uint8
+ * [n_colors, 3] BGR, 2 <= n_colors <= 256; out uint8 [B, H, W, 3], which may be base when base_stride != 0 or B = 1 (a thread
+ * reads its pixel before it writes it); status one int32, OR-ed into (the caller zeroes it).  workspace:
+ * dagr_stream_render_workspace_bytes(B, H, W) bytes (0: B outside 1..65535, H or W < 1 or H * W > 2^29), 256-byte aligned,
+ * ALL ZERO before the first call; every call leaves it zero again, so no call clears it.  It holds two int32 maps over
+ * [B, H, W]: the arrival index + 1 of the last drawn event on the pixel and the highest trail slot + 1 (integer
+ * atomicMax, so the order of execution does not matter).  A flagged frame is unspecified; nothing faults.
+ * DAGR_ERR_INVALID_ARG before any launch: sizes or options out of range, a workspace or rings smaller than their _bytes,
+ * NULL or misaligned pointers.
+ * ------------------------------------------------------------------------ */
+#define DAGR_RENDER_MAX_TRAIL 64
+#define DAGR_RENDER_MAX_LINEWIDTH 7
+#define DAGR_RENDER_MAX_ID_SCALE 4
+#define DAGR_RENDER_BAD_POLARITY 1
+#define DAGR_RENDER_BAD_CLASS 2
+#define DAGR_RENDER_LONG_SEGMENT 4
+enum {
+    DAGR_RENDER_GLYPH_0 = 0x7b6f, DAGR_RENDER_GLYPH_1 = 0x2c97, DAGR_RENDER_GLYPH_2 = 0x73e7, DAGR_RENDER_GLYPH_3 = 0x73cf,
+    DAGR_RENDER_GLYPH_4 = 0x5bc9, DAGR_RENDER_GLYPH_5 = 0x79cf, DAGR_RENDER_GLYPH_6 = 0x79ef, DAGR_RENDER_GLYPH_7 = 0x7249,
+    DAGR_RENDER_GLYPH_8 = 0x7bef, DAGR_RENDER_GLYPH_9 = 0x7bcf
+};
+size_t dagr_stream_trail_bytes(int32_t B, int32_t max_tracks, int32_t trail);
+int dagr_stream_trail_reset(void *rings, size_t bytes, int32_t B, int32_t max_tracks, int32_t trail, void *stream);
+int dagr_stream_trail(void *rings, size_t bytes, int32_t B, int32_t max_tracks, int32_t trail, const void *tracks,
+                      size_t tracks_bytes, const int64_t *t_ref, void *stream);
+size_t dagr_stream_render_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int dagr_stream_render(const void *state, int32_t B, int64_t capacity, int64_t event_window_us, double alpha,
+                       const float *det, const int32_t *n_keep, int32_t A, const int64_t *track_id, const void *rings,
+                       int32_t max_tracks, int32_t trail, int32_t linewidth, int32_t ids, int32_t id_scale,
+                       const uint8_t *colors, int32_t n_colors, const uint8_t *base, int64_t base_stride, uint8_t *out,
+                       int32_t H, int32_t W, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
 /* The neighbour search alone, again, on the pixel index the last dagr_graph_build_window left in `workspace` (same N):
  * rewrites nbr_src / nbr_code / deg and the edge count.  For measurement (bench.py times the search kernels on their own
  * stream with HIP events); a product caller has no use for it. */

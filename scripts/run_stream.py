@@ -95,7 +95,15 @@ rest is counted as left out.  The detections written do not change.
 synthetic sources, not a model of any camera) and pushed through ``step_words``; the stream decodes them on the device
 (``dagr.streaming``: ``EventStream(decode=)``) in front of the filter, the front and the window.  ``--max_decoded N`` sizes
 the decoded events' buffers (default: the worst case of every push).  The decoder's counters are printed with the
-summary.  Composes with ``--downsample``, ``--denoise_us``, ``--max_lane_events`` and ``--track``."""
+summary.  Composes with ``--downsample``, ``--denoise_us``, ``--max_lane_events`` and ``--track``.
+
+``--render DIR``: every ``--render_every``-th step is drawn on the device from the stream's own arrays (``dagr.streaming``:
+``EventStream(render=)``, ``render_step()``) -- the window's events (``--render_event_window_us N``: of the last ``N``
+microseconds), the step's box outlines and, with ``--track``, the track ids on plates and the trails of the last
+``--render_trail`` centres (``--render_id_scale`` sizes the digits) -- on a black base at the model's resolution, and
+written as ``DIR/%06d_lane0.png`` through PIL.  The look is this project's own; there is no window display.  The
+detections written do not change."""
+import os
 import time
 import types
 
@@ -105,7 +113,8 @@ import torch
 import _common as C
 from dagr.data.evt import encode_events
 from dagr.streaming import (EventStream, _assign_options, _flicker_options, _identity_options, _motion_options, _rescue_options,
-                            _hota_options, _label_options, _score_options, _track_options, hota_summary, identity_summary,
+                            _hota_options, _label_options, _render_options, _score_options, _track_options, hota_summary,
+                            identity_summary,
                             score_summary)
 from dagr.utils.buffers import DETECTION_DTYPE, detections_to_records
 from dagr.utils.logging import set_up_logging_directory
@@ -178,6 +187,14 @@ def stream_options(p):
                    "whose diagonal is not above this")
     g.add_argument("--raw_frames", action="store_true", help="the source's frames are sensor-size BGR uint8 frames: prepare "
                    "them on the device (crop, shrink by the --downsample factor, / 255)")
+    g.add_argument("--render", type=str, default=None, metavar="DIR", help="draw every step on the device -- events, box "
+                   "outlines and, with --track, track ids and trails -- and write DIR/%%06d_lane<b>.png")
+    g.add_argument("--render_every", type=int, default=1, help="with --render: draw every N-th step")
+    g.add_argument("--render_event_window_us", type=int, default=None, help="with --render: draw the events of the last N "
+                   "microseconds (default: the whole window)")
+    g.add_argument("--render_trail", type=int, default=None, help="with --render --track: centres a trail holds (default "
+                   "32, at most 64; 0: no trails)")
+    g.add_argument("--render_id_scale", type=int, default=None, help="with --render --track: size of the id digits, 1..4")
 
 
 TRACK_FLAGS = (("track_iou", "iou"), ("track_max_age_us", "max_age_us"), ("track_min_score", "min_score"),
@@ -197,6 +214,32 @@ def track_options(a):
     except ValueError as e:
         raise SystemExit(str(e)) from None
     return given
+
+
+RENDER_FLAGS = (("render_event_window_us", "event_window_us"), ("render_trail", "trail"), ("render_id_scale", "id_scale"))
+
+
+def render_options(a):
+    """``render=`` of the stream the flags describe: None without ``--render``, else the options that were given."""
+    given = {key: getattr(a, flag) for flag, key in RENDER_FLAGS if getattr(a, flag, None) is not None}
+    if getattr(a, "render", None) is None:
+        if given:
+            raise SystemExit(f"run_stream.py: --{[f for f, k in RENDER_FLAGS if k in given][0]} needs --render")
+        return None
+    if getattr(a, "render_every", 1) < 1:
+        raise SystemExit("run_stream.py: --render_every must be positive")
+    try:
+        _render_options(given or True, track_options(a), "run_stream.py")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    return given or True
+
+
+def write_frames(directory, step, frames):
+    """``DIR/%06d_lane<b>.png`` of a step's BGR frames (RGB on disk), through PIL as visualize_detections.py writes its."""
+    from PIL import Image
+    for b, frame in enumerate(frames):
+        Image.fromarray(np.ascontiguousarray(frame[..., ::-1])).save(os.path.join(directory, "%06d_lane%d.png" % (step, b)))
 
 
 MOTION_FLAGS = (("track_alpha", "alpha"), ("track_beta", "beta"))
@@ -459,7 +502,11 @@ def play(a, model, source, dev):
                          score=score_options(a),
                          identity=identity_options(a), hota=hota, labels=label_options(a),
                          decode=decode, max_decoded=getattr(a, "max_decoded", None),
-                         t_base=int(source.t_range()[0]) if decode else None)      # (the words' times start at the sequence's)
+                         t_base=int(source.t_range()[0]) if decode else None,      # (the words' times start at the sequence's)
+                         render=render_options(a))
+    if stream.render is not None:
+        os.makedirs(a.render, exist_ok=True)
+    a.stream_rendered = 0 if stream.render is not None else None
     t0, t1 = source.t_range()
     out, last_frame = [], None
     instants, pushed = (np.asarray(source.label_instants(), np.int64), 0) if stream.labels is not None else (None, 0)
@@ -488,6 +535,9 @@ def play(a, model, source, dev):
             det = stream.step(xy, np.asarray(ev["t"], np.int64), np.asarray(ev["p"], np.int8), t_now=t_step, image=image,
                               frame=raw)
         out.append((t_step, det[0]))
+        if stream.render is not None and (len(out) - 1) % a.render_every == 0:
+            write_frames(a.render, len(out) - 1, stream.render_step().cpu().numpy())   # the step's own arrays, on the device
+            a.stream_rendered += 1
         if stream.labels is not None:
             # the store stays one keyframe ahead of the step: every labelled instant up to the first one behind t_step
             while pushed < len(instants) and (pushed == 0 or instants[pushed - 1] <= t_step):
@@ -546,6 +596,7 @@ def main(argv=None, model_factory=None, source=None):
     score_options(a)
     identity_options(a)
     label_options(a)
+    render_options(a)
     a.batch_size = 1                     # one sequence: one lane
     world, rank, dev = C.distributed()
     torch.manual_seed(42)
@@ -620,6 +671,8 @@ def main(argv=None, model_factory=None, source=None):
             c = a.stream_identity
             tracked += (f"; IDF1 {c['idf1']:.3f}, IDP {c['idp']:.3f}, IDR {c['idr']:.3f} (IDTP {c['idtp']} of {c['gt_frames']} "
                         f"labelled and {c['hyp_frames']} tracked frames, {c['objects']} objects, {c['tracks']} tracks)")
+        if getattr(a, "stream_rendered", None) is not None:
+            tracked += f"; {a.stream_rendered} frames drawn on the device -> {a.render}"
         if getattr(a, "stream_hota", None) is not None:
             c = a.stream_hota
             tracked += (f"; HOTA {c['hota']:.3f}, DetA {c['deta']:.3f}, AssA {c['assa']:.3f}, LocA {c['loca']:.3f} "
