@@ -564,6 +564,9 @@ class StreamState:
         self.labels = None                              # the options of its label store (dagr.streaming._label_options)
         self.labels_state, self.gt_labels = None, None  # the store; the last labelled step's (gt_box, gt_label, gt_id, n_gt)
         self._stepped, self._labelled = False, False    # a step since construction / reset(); whether run_labels has had it
+        self.map, self.map_classes = None, None         # the options of its mAP log (dagr.streaming._map_options)
+        self.map_state, self.map_plan, self._map_sizes = None, None, None
+        self._map_det, self._mapped = None, False       # the last step's (det, n_keep); whether run_map_log has had them
         self.render = None                              # the options of its picture (dagr.streaming._render_options)
         self.render_size, self.render_colors, self.render_ws, self.render_flags, self.render_out = None, None, None, None, None
         self.trail_rings, self._render_det = None, None # the trail rings; the last step's (det, n_keep) for run_render
@@ -646,6 +649,95 @@ class StreamState:
             raise RuntimeError("this stream keeps no labels (labels=): it has no counters")
         W = _lib.DEFINES["DAGR_LABELS_WORDS"]
         return self.labels_state[:8 * W * self.B].view(torch.int64).cpu().numpy().reshape(self.B, W)
+
+    # ------------------------------------------------------------------------------------ mAP over every step
+    def enable_map(self, options, n_classes):
+        """``run_map_log`` appends a step's detections and ground truth to the lanes' logs (``dagr_stream_map_log``) and
+        ``run_map_plan`` builds the COCO job list from them (``dagr_stream_map_plan``): ``options`` as
+        ``dagr.streaming._map_options`` returns them.  The log is allocated by the first ``run_map_log``, which knows the
+        rows per lane ``A`` and the ground truth's ``G``, the plan's arrays by the first ``run_map_plan``; nothing is
+        allocated after that.  Both are sized from the capacities: about ``64 * B * max_images * max_dets`` bytes together
+        (the log keeps 24 bytes a detection row, the plan 40; its column arrays add 32 for each of the first 100 rows a
+        class) -- with ``max_dets = None`` and an engine of 4096 rows a lane that is 2.6 GB at B = 8 and 1200 images."""
+        self.map, self.map_classes = dict(options), int(n_classes)
+
+    def map_sizes(self):
+        """``(B, max_images, G, max_dets)`` of the allocated log, or None before the first ``run_map_log``."""
+        return None if self.map_state is None else (self.B,) + self._map_sizes
+
+    def _empty_map_log(self):
+        """``dagr_stream_map_reset``: an empty log, zero counters."""
+        _lib.check(_lib.lib().dagr_stream_map_reset(_lib.ptr(self.map_state), self.map_state.numel(), *self.map_sizes(),
+                                                    _lib.cur_stream(self.device)), "stream_map_reset")
+
+    def _reset_map(self):
+        """An empty log, zero counters; the last step cannot be logged any more."""
+        if self.map_state is not None:
+            self._empty_map_log()
+        self._map_det, self._mapped = None, False
+
+    def run_map_log(self, gt_box, gt_label, n_gt):
+        """``dagr_stream_map_log`` on the LAST step's ``det`` / ``n_keep`` at its ``t_ref`` against device tensors ``gt_box``
+        fp32 [B, G, 4], ``gt_label`` int32 [B, G] and ``n_gt`` int32 [B]: one launch, no host wait, once per step."""
+        if self.map is None:
+            raise RuntimeError("this stream keeps no mAP log (map=): it has no map_step")
+        if self._map_det is None:
+            raise RuntimeError("map_step: the stream has made no step since its construction / reset(): there is nothing "
+                               "to log")
+        if self._mapped:
+            raise RuntimeError("map_step: the last step has been logged already (one map_step per step)")
+        det, n_keep = self._map_det
+        A, G = int(det.shape[1]), int(gt_box.shape[1])
+        if self.map_state is None:
+            D = A if self.map["max_dets"] is None else self.map["max_dets"]
+            self._map_sizes = (self.map["max_images"], G, D)
+            self.map_state = _state_buffer(self.device, "dagr_stream_map_bytes", self.B, *self._map_sizes)
+            self._empty_map_log()
+        if G != self._map_sizes[1]:
+            raise ValueError(f"map_step: gt_box has {G} rows a lane, the stream's log was sized for {self._map_sizes[1]} by its "
+                             "first map_step")
+        P = _lib.ptr
+        _lib.check(_lib.lib().dagr_stream_map_log(P(self.map_state), self.map_state.numel(), *self.map_sizes(), P(det),
+                                                  P(n_keep), A, P(gt_box), P(gt_label), P(n_gt), self._t_ref_where(),
+                                                  _lib.cur_stream(self.device)), "stream_map_log")
+        self._mapped = True
+
+    def run_map_plan(self):
+        """``dagr_stream_map_plan`` on the log so far (no host wait): the ``StreamMapPlan`` (utils/coco_eval.py) that holds
+        the result, its arrays allocated by the first call; None while nothing has been logged."""
+        if self.map is None:
+            raise RuntimeError("this stream keeps no mAP log (map=): it has no map")
+        if self.map_state is None:
+            return None
+        if self.map_plan is None:
+            from .utils.coco_eval import StreamMapPlan
+            self.map_plan = StreamMapPlan(*self.map_sizes(), self.map_classes, self.device)
+        self.map_plan.run(self.map_state)
+        return self.map_plan
+
+    MAP_SECTIONS = (("t", np.int64, 8, ()), ("n_gt", np.int32, 4, ()), ("n_dt", np.int32, 4, ()),
+                    ("gt_box", np.float32, 4, ("G", 4)), ("gt_label", np.int32, 4, ("G",)), ("det", np.float32, 4, ("D", 6)))
+
+    def map_words(self, log=False):
+        """The lanes' words read back: int64 [B, DAGR_MAP_WORDS] -- images, dropped_images, cut_dets, unlabelled, empty
+        (zeros before the first ``run_map_log``); with ``log`` also the dict of the log's arrays in the layout
+        include/dagr_hip.h documents (copies; synchronises)."""
+        if self.map is None:
+            raise RuntimeError("this stream keeps no mAP log (map=): it has no counters")
+        W = _lib.DEFINES["DAGR_MAP_WORDS"]
+        if self.map_state is None:
+            return (np.zeros((self.B, W), np.int64), None) if log else np.zeros((self.B, W), np.int64)
+        if not log:
+            return self.map_state[:8 * W * self.B].view(torch.int64).cpu().numpy().reshape(self.B, W)
+        host = self.map_state.cpu().numpy()
+        B, I, G, D = self.map_sizes()
+        at, out = -(-8 * W * B // 16) * 16, {}
+        for name, dtype, size, tail in self.MAP_SECTIONS:
+            shape = (B, I) + tuple(dict(G=G, D=D).get(v, v) for v in tail)
+            nbytes = int(np.prod(shape)) * size
+            out[name] = host[at:at + nbytes].view(dtype).reshape(shape).copy()
+            at += -(-nbytes // 16) * 16
+        return host[:8 * W * B].view(np.int64).reshape(B, W).copy(), out
 
     # ------------------------------------------------------------------------------------ track ids
     # the slots' arrays in the order the state holds them over [B, max_tracks]: (name, dtype, width); next_id[B] follows
@@ -1193,6 +1285,8 @@ class StreamState:
             self._reset_hota()
         if self.labels_state is not None:
             self._reset_labels()
+        if self.map is not None:
+            self._reset_map()
         if self.render is not None:
             self._reset_render()
         self._stepped, self._labelled = False, False
@@ -2640,6 +2734,8 @@ class WindowEngine:
         st.stepped()
         if st.track is not None:                     # a plain launch behind the window, captured or not: the track ids
             st.run_track(*det)
+        if st.map is not None:                       # logged on request (run_map_log): a step launches nothing for it
+            st._map_det, st._mapped = det, False
         if st.render is not None:                    # the picture is made on request (run_render); the trails follow every step
             st._render_det = det
             if st.trail_rings is not None:

@@ -483,6 +483,27 @@ the fronts behind the decoder cheaper -- they are handed all ``max_out`` rows --
 stream's clock: the order checks run on it, and the lane's newest event is its newest DECODED event.  The host never learns
 how many events a push decoded, so its bound of the window grows by ``min(max_decoded, 12 * n_words)`` (EVT 3.0) or
 ``n_words`` (EVT 2.0) per step: a decoding stream that is never read back should be capped (``max_lane_events``).
+
+Detection mAP over every step (``map=``)
+----------------------------------------
+The reference's inter-frame protocol is "detect between frames, evaluate against interpolated labels".  With ``map=`` the
+stream keeps a log of evaluated images on the device and evaluates it where it lies.
+
+- An image is one (lane, instant).  ``map_step()`` offers every lane's last step to the log (``dagr_stream_map_log``, one
+  launch, no host wait).  A lane is logged only if it has at least one ground-truth box (``n_gt > 0``: ``evaluated_images``'
+  rule); ``n_gt < 0`` counts in ``unlabelled``, ``n_gt == 0`` in ``empty``.
+- A lane holds at most ``max_images`` images; later ones count in ``dropped_images`` and nothing else is written.  An image
+  keeps its ``t_ref``, its ground-truth rows and its first ``min(n_keep, max_dets)`` detection rows in ``det`` order; rows
+  cut count in ``cut_dets``.  Rows stay the fp32 corner rows they are.
+- The images of the protocol are lane-major: all of lane 0's in log order, then lane 1's, and so on.  The order matters
+  only for ties in score.
+- ``map()`` builds the job list of ``utils/coco_eval.py:build_jobs`` on the device (``dagr_stream_map_plan``: count, scan,
+  scatter), then runs ``dagr_coco_match`` and ``dagr_coco_accumulate`` on it.  A detection counts for the class its fp32
+  label IS; labels outside ``[0, classes)`` belong to no job.  Boxes become (x, y, w, h) as ``_xywh`` does it: subtract in
+  fp32, then widen.
+- ``MapDefinition`` is the log's rule in numpy; its ``compute()`` hands the images to the host ``evaluate_detection``, which
+  is the definition of the metric -- this project's numpy restatement of the public COCO protocol, not pycocotools.  The
+  ground truth between keyframes is linear interpolation.
 """
 import numpy as np
 
@@ -1908,6 +1929,102 @@ class LabelDefinition:
         return gt_box, gt_label, gt_id, n_gt
 
 
+DAGR_MAP_MAX_IMAGES = DEFINES["DAGR_MAP_MAX_IMAGES"]
+DAGR_COCO_MAX_GT, DAGR_COCO_MAX_DT = DEFINES["DAGR_COCO_MAX_GT"], DEFINES["DAGR_COCO_MAX_DT"]
+MAP_DEFAULTS = dict(max_images=1200, max_dets=None)
+MAP_WORDS = ("images", "dropped_images", "cut_dets", "unlabelled", "empty")
+assert len(MAP_WORDS) == DEFINES["DAGR_MAP_WORDS"]
+
+
+def _map_options(map, who):
+    """``map=`` of a stream, checked: None (off) or the dict of ``max_images`` and ``max_dets`` (None: the engine's rows per
+    lane, so that nothing is cut) with the defaults filled in; refusals by name."""
+    opt = _options(map, "map", MAP_DEFAULTS, who)
+    if opt is None:
+        return None
+    if not _is_int(opt["max_images"]) or not 1 <= int(opt["max_images"]) <= DAGR_MAP_MAX_IMAGES:
+        raise ValueError(f"{who}: map max_images = {opt['max_images']!r} must be an int in 1..DAGR_MAP_MAX_IMAGES = "
+                         f"{DAGR_MAP_MAX_IMAGES}")
+    if opt["max_dets"] is not None and (not _is_int(opt["max_dets"]) or not 1 <= int(opt["max_dets"]) <= DAGR_COCO_MAX_DT):
+        raise ValueError(f"{who}: map max_dets = {opt['max_dets']!r} must be an int in 1..DAGR_COCO_MAX_DT = {DAGR_COCO_MAX_DT} "
+                         "(or None: the engine's rows per lane)")
+    return dict(max_images=int(opt["max_images"]), max_dets=None if opt["max_dets"] is None else int(opt["max_dets"]))
+
+
+def map_det_classes(label):
+    """The class a logged detection row counts for, from its fp32 label: the class whose number the label IS, -1 for a label
+    that is no whole number in int32's range (it then belongs to no job) -- ``label == float(c)`` on the device.  This
+    deliberately differs from the ``DetectionBuffer`` route, which truncates (``.long()``: 0.5 becomes class 0, NaN is
+    undefined): the engine's detections carry whole labels, so the two agree on everything but malformed rows, and a
+    rule that is defined for every fp32 value is one a kernel can equal bit for bit."""
+    label = np.asarray(label, np.float32).reshape(-1)
+    with np.errstate(all="ignore"):
+        whole = np.isfinite(label) & (label == np.floor(label)) & (np.abs(label) < 2.0 ** 31)
+    return np.where(whole, np.where(whole, label, 0).astype(np.int64), -1)
+
+
+class MapDefinition:
+    """The mAP log of the module docstring in numpy: which (lane, instant) becomes an image and what it keeps
+    (include/dagr_hip.h, "Event stream mAP", states the rule).  ``step(det, n_keep, gt_box, gt_label, n_gt, t_ref)`` is
+    ``dagr_stream_map_log``'s call; ``log[b]`` the lane's images in log order as ``(t, gt_box fp32 [g, 4], gt_label int32
+    [g], det fp32 [d, 6])``; ``images()`` the protocol's lists, lane-major; ``compute()`` hands them to the host
+    ``evaluate_detection``, which is the definition of the metric.  ``counters`` is a dict of one int64 ``[B]`` array per
+    name of ``MAP_WORDS[1:]``; ``words()`` the lanes' words as the device state holds them.  The yardstick of the log and
+    plan kernels; nothing on the device path calls it."""
+
+    def __init__(self, batch_size, map=True):
+        self.B = int(batch_size)
+        self.options = _map_options(map, "MapDefinition")
+        if self.options is None:
+            raise ValueError("MapDefinition: map = None is a stream that keeps no mAP log")
+        self.reset()
+
+    def reset(self):
+        self.log = [[] for _ in range(self.B)]
+        self.counters = {name: np.zeros(self.B, np.int64) for name in MAP_WORDS[1:]}
+
+    def words(self):
+        """int64 ``[B, DAGR_MAP_WORDS]``, the order of ``MAP_WORDS``."""
+        return np.stack([np.array([len(v) for v in self.log], np.int64)] + [self.counters[name] for name in MAP_WORDS[1:]], axis=1)
+
+    def step(self, det, n_keep, gt_box, gt_label, n_gt, t_ref):
+        """``det`` fp32 ``[B, A, 6]``, ``n_keep`` ``[B]``, ``gt_box`` fp32 ``[B, G, 4]``, ``gt_label`` int32 ``[B, G]``, ``n_gt``
+        ``[B]`` (negative: no labels at this instant), ``t_ref`` int64 ``[B]``."""
+        o, c = self.options, self.counters
+        det, gt_box = np.asarray(det, np.float32), np.asarray(gt_box, np.float32)
+        gt_label, t_ref = np.asarray(gt_label, np.int32), np.broadcast_to(np.asarray(t_ref, np.int64).reshape(-1), (self.B,))
+        A, G = det.shape[1], gt_box.shape[1]
+        for b in range(self.B):
+            rows = int(n_gt[b])
+            if rows <= 0:                                   # metrics only where there is a box
+                c["unlabelled" if rows < 0 else "empty"][b] += 1
+                continue
+            if len(self.log[b]) == o["max_images"]:
+                c["dropped_images"][b] += 1
+                continue
+            ng, nk = min(rows, G), min(max(int(n_keep[b]), 0), A)
+            kept = nk if o["max_dets"] is None else min(nk, o["max_dets"])
+            c["cut_dets"][b] += nk - kept
+            self.log[b].append((int(t_ref[b]), gt_box[b, :ng].copy(), gt_label[b, :ng].copy(), det[b, :kept].copy()))
+
+    def images(self):
+        """``(gt, dt)``: the lists ``evaluate_detection`` takes -- one dict of ``boxes`` / ``labels`` (detections: and
+        ``scores``) per image, all of lane 0's images in log order, then lane 1's, ..."""
+        gt, dt = [], []
+        for lane in self.log:
+            for _, box, label, det in lane:
+                gt.append(dict(boxes=box, labels=label.astype(np.int64)))
+                dt.append(dict(boxes=det[:, :4], scores=det[:, 4], labels=map_det_classes(det[:, 5])))
+        return gt, dt
+
+    def compute(self, classes=("car", "pedestrian")):
+        """``evaluate_detection`` on ``images()``, plus the lanes' words by name (int64 ``[B]`` each)."""
+        from .utils.coco_eval import evaluate_detection
+        out = evaluate_detection(*self.images(), classes=classes)
+        out.update({name: self.words()[:, i].copy() for i, name in enumerate(MAP_WORDS)})
+        return out
+
+
 def frame_definition(raw, fx, fy, W, H, bgr=False):
     """The model's image of one raw sensor frame (``uint8 [H_f, W_f, 3]``), stated once: ``DSEC.preprocess_image`` plus
     ``format_data`` for a top-left crop.  Rows ``[0, fy * H)`` and columns ``[0, fx * W)`` of the frame go through
@@ -2543,6 +2660,20 @@ class EventStream:
     ``labels_step()`` is the one launch (``dagr_stream_labels_at``), ``score_step()`` without arguments runs it in front
     of the scorer chain, ``label_counts()`` reads the counters back.  A step of such a stream issues exactly the calls it
     issues without the store, and a stream built without it issues exactly the calls it issued before.
+    ``map`` (``None``: off, ``True``: the defaults, or a dict of ``max_images`` -- 1 .. ``DAGR_MAP_MAX_IMAGES``, default 1200
+    a lane -- and ``max_dets`` -- ``None``: the engine's rows per lane, so that nothing is cut; needs neither ``track`` nor
+    ``score``): detection mAP over every step.  ``map_step()`` appends the last step's detections and its ground truth --
+    the interpolated keyframes of a ``labels=`` stream, or the caller's tensors -- to a log of fixed capacity on the device
+    (``dagr_stream_map_log``: one launch, no host wait; only lanes with at least one box are logged, as
+    ``evaluated_images`` has it), and ``map()`` builds the COCO protocol's job list from the log on the device
+    (``dagr_stream_map_plan``), runs ``dagr_coco_match`` and ``dagr_coco_accumulate`` on it and returns what
+    ``evaluate_detection`` returns, with the log's counters (include/dagr_hip.h states the rule, ``MapDefinition`` is the
+    same in numpy and hands its images to the host ``evaluate_detection``, the definition of the metric).  ``map_counts()``
+    / ``map_log()`` read the counters and the log back.  Memory: the log (first ``map_step()``) and the plan's arrays (first
+    ``map()``) are sized from the capacities and allocated once, about ``64 * B * max_images * max_dets`` bytes together --
+    2.6 GB at B = 8 with the defaults on an engine of 4096 rows a lane; a trained model keeps few rows, so
+    ``map=dict(max_dets=100)`` (the protocol evaluates 100 a class and image at most) brings that under 100 MB.  A step of such a stream issues exactly the calls it issues
+    without the log, and a stream built without it issues exactly the calls it issued before.
     ``decode`` (``None``: off, ``"evt2"`` or ``"evt3"``), ``max_decoded`` and ``t_base``: the stream takes the camera's words
     (``step_words`` / ``step_words_device``) and ``dagr_stream_decode`` turns them into events on the device, in front of
     the filter, the front and the window (module docstring; the formats as recalled from the vendor's public descriptions,
@@ -2580,10 +2711,11 @@ class EventStream:
     def __init__(self, model, window_us=50000, downsample=None, sensor_size=None, frame_size=None, frame_bgr=False,
                  max_lane_events=None, denoise_us=None, refractory_us=None, track=None, motion=None, rescue=None,
                  decode=None, max_decoded=None, t_base=None, flicker=None, trail_us=None, score=None,
-                 identity=None, assign=None, hota=None, labels=None, render=None):
+                 identity=None, assign=None, hota=None, labels=None, render=None, map=None):
         import torch
         self.model = model
         self.labels = _label_options(labels, "EventStream")
+        self.map_options = _map_options(map, "EventStream")
         self.track = _track_options(track, "EventStream")
         self.render = _render_options(render, self.track, "EventStream")
         self.motion = _motion_options(motion, self.track, "EventStream")
@@ -2647,6 +2779,12 @@ class EventStream:
             self.state.enable_hota(self.hota_options)
         if self.labels is not None:
             self.state.enable_labels(self.labels)
+        if self.map_options is not None:
+            rows = sum(int(h) * int(w) for h, w in eng.out_sizes)
+            if rows > DAGR_COCO_MAX_DT:
+                raise ValueError(f"EventStream: map = the engine has {rows} detection rows per lane, the log takes at most "
+                                 f"DAGR_COCO_MAX_DT = {DAGR_COCO_MAX_DT}")
+            self.state.enable_map(self.map_options, eng.num_classes)
         if self.render is not None:
             self.state.enable_render(self.render, eng.W, eng.H)
         self._label_newest = [None] * eng.B     # per lane the newest instant a HOST push has offered (push_labels' check)
@@ -3208,11 +3346,92 @@ class EventStream:
         return dict(pmc=t["pmc"], gc=t["gc"], tc=t["tc"], mc=t["mc"],
                     words={name: t["words"][:, i].copy() for i, name in enumerate(HOTA_WORDS)})
 
+    def map_step(self, gt_box=None, gt_label=None, n_gt=None):
+        """Log the LAST step's detections and ground truth for the COCO protocol, on the device (module docstring; needs
+        ``map=``).  Without arguments, on a stream with ``labels=``: against the ground truth interpolated to the step's own
+        ``t_ref`` -- ``labels_step()`` if the step has not had one (a ``score_step()`` without arguments has), then the log
+        launch; raises by name on a stream without ``labels=``.  With arguments: ``gt_box`` fp32 ``[B, G, 4]`` (x1, y1, x2,
+        y2), ``gt_label`` int32 ``[B, G]`` and ``n_gt`` int32 ``[B]`` -- ``None``: every lane has all ``G`` rows; ``n_gt[b] <
+        0``: lane ``b`` has no labels at this instant --, numpy arrays (uploaded) or device tensors, ``G <=
+        DAGR_COCO_MAX_GT``, the same ``G`` at every call.  ONE launch (``dagr_stream_map_log``), no host wait; returns
+        nothing.  Raises by name before the stream's first step and when called twice for one step."""
+        import torch
+        if self.map_options is None:
+            raise RuntimeError("EventStream: map_step needs a stream built with map=")
+        if gt_box is None:
+            if gt_label is not None or n_gt is not None:
+                raise ValueError("EventStream: map_step takes gt_box and gt_label together, or nothing at all (a stream with "
+                                 "labels=)")
+            if self.labels is None:
+                raise RuntimeError("EventStream: map_step() without arguments needs a stream built with labels= (it logs the "
+                                   "interpolated keyframes)")
+            box, label, _, n = self.state.run_labels()
+            return self.state.run_map_log(box, label, n)
+
+        def dev(v, dtype, shape, name):
+            if not torch.is_tensor(v):
+                v = torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
+            v = v.to(device=self.device, dtype=dtype).contiguous()
+            if tuple(v.shape) != shape:
+                raise ValueError(f"EventStream: map_step {name} has shape {tuple(v.shape)}, expected {shape}")
+            return v
+        G = int(gt_box.shape[1]) if np.ndim(gt_box) == 3 else -1
+        if not 1 <= G <= DAGR_COCO_MAX_GT:
+            raise ValueError(f"EventStream: map_step gt_box is fp32 [{self.B}, G, 4] with 1 <= G <= DAGR_COCO_MAX_GT = "
+                             f"{DAGR_COCO_MAX_GT}, got {tuple(np.shape(gt_box))}")
+        gt_box = dev(gt_box, torch.float32, (self.B, G, 4), "gt_box")
+        gt_label = dev(gt_label, torch.int32, (self.B, G), "gt_label")
+        n_gt = torch.full((self.B,), G, dtype=torch.int32, device=self.device) if n_gt is None else \
+            dev(n_gt, torch.int32, (self.B,), "n_gt")
+        self.state.run_map_log(gt_box, gt_label, n_gt)
+
+    def map(self):
+        """COCO mAP over everything logged since construction / ``reset()`` (module docstring; needs ``map=``):
+        ``dagr_stream_map_plan`` builds the protocol's job list from the log on the device, the totals block comes back (one
+        small copy: the C entries of match and accumulate take host sizes), then ``dagr_coco_match``, ``group_ngt`` from
+        ``g_ign``, ``score_order`` and ``dagr_coco_accumulate`` run on the plan's arrays where they lie, and only the
+        precision array, the two status words and the lanes' words are copied back (synchronises).  Returns the dict
+        ``evaluate_detection`` returns -- ``AP``, ``AP_50``, ``AP_75``, ``AP_S``, ``AP_M``, ``AP_L``; all zero when no
+        detection was logged -- plus one int64 ``[B]`` per name of ``MAP_WORDS`` (``images``, ``dropped_images``,
+        ``cut_dets``, ``unlabelled``, ``empty``).  The log goes on: it can be asked for at any step and repeated."""
+        from .utils.coco_eval import OUT_KEYS, summarize
+        if self.map_options is None:
+            raise RuntimeError("EventStream: map() needs a stream built with map=")
+        plan = self.state.run_map_plan()
+        if plan is None:                                            # nothing was ever logged
+            words, out = self.state.map_words(), {k: 0 for k in OUT_KEYS}
+        else:
+            n_words = 8 * len(MAP_WORDS) * self.B
+            _, prec, back = plan.precision(also=self.state.map_state[:n_words])
+            words = back.view(np.int64).reshape(self.B, len(MAP_WORDS))
+            out = {k: 0 for k in OUT_KEYS} if prec is None else summarize(prec)
+        out.update({name: words[:, i].copy() for i, name in enumerate(MAP_WORDS)})
+        return out
+
+    def map_counts(self):
+        """The log's counters since construction / ``reset()``: a dict of int64 ``[B]`` per name of ``MAP_WORDS``.
+        Synchronises.  Raises without ``map=``."""
+        if self.map_options is None:
+            raise RuntimeError("EventStream: map_counts needs a stream built with map=")
+        words = self.state.map_words()
+        return {name: words[:, i].copy() for i, name in enumerate(MAP_WORDS)}
+
+    def map_log(self):
+        """The log read back (copies; synchronises; needs ``map=``): per lane the list of its images in log order as ``(t,
+        gt_box fp32 [g, 4], gt_label int32 [g], det fp32 [d, 6])`` -- ``MapDefinition.log``'s shape."""
+        if self.map_options is None:
+            raise RuntimeError("EventStream: map_log needs a stream built with map=")
+        words, arrays = self.state.map_words(log=True)
+        if arrays is None:
+            return [[] for _ in range(self.B)]
+        return [[(int(arrays["t"][b, k]), arrays["gt_box"][b, k, :arrays["n_gt"][b, k]], arrays["gt_label"][b, k, :arrays["n_gt"][b, k]],
+                  arrays["det"][b, k, :arrays["n_dt"][b, k]]) for k in range(int(words[b, 0]))] for b in range(self.B)]
+
     def reset(self):
         """Empty the stream: no resident events, no reference instants, zero change maps, empty stamp maps, every pixel of
         the flicker / trail filters in its initial state, zero dropped, filtered and suppressed counts, zero decoder states and counters, a clear status word, zero step counters; no tracks, ids from 1 again, zero untracked and rescued counts; the
         scorer's object tables empty and its counters zero (and no step left to score); the identity state and HOTA's state and log empty; the label
-        store empty and its counters zero; the trail rings empty, the picture's flags clear and no step left to draw.  The
+        store empty and its counters zero; the mAP log empty and its counters zero; the trail rings empty, the picture's flags clear and no step left to draw.  The
         frame in force stays, and the next step runs it through the image branch again."""
         self.state.reset()
         self._label_newest = [None] * self.B

@@ -203,6 +203,35 @@ def column_layout(jobs):
     return kept, np.cumsum(kept) - kept, int(kept.sum()), np.cumsum(jobs.table[:, 1]) - jobs.table[:, 1], int(jobs.table[:, 1].sum())
 
 
+def _match_layout(T, n_out, n_gign):
+    """Where the matcher's outputs lie in their ONE buffer (one buffer = one copy back): status int32 | order int32[n_out] |
+    dtm, dt_ign uint8[T, n_out] | g_ign uint8[n_gign] -- (at_order, at_dtm, at_ign, at_gign, bytes)."""
+    at_order, at_dtm = 4, 4 + 4 * n_out
+    at_ign, at_gign = at_dtm + T * n_out, at_dtm + 2 * T * n_out
+    return at_order, at_dtm, at_ign, at_gign, at_gign + n_gign
+
+
+def match_launch(gt, dt, scores, jobs6, rng, thrs, J, n_gt, n_dt, max_g, max_d, n_out, n_gign, device, zeroed=False):
+    """``dagr_coco_match`` on device arrays (``c_void_p``, the header's layouts) with host sizes: one launch (none for
+    ``J = 0``), no synchronisation.  Returns (the output buffer of ``_match_layout``, its views ``(order, dtm, dt_ign, g_ign,
+    status)``); ``zeroed``: the buffer starts as zeros instead of uninitialised."""
+    import torch
+    from .. import _lib
+    T = len(IOU_THRS)
+    at_order, at_dtm, at_ign, at_gign, nbytes = _match_layout(T, n_out, n_gign)
+    res = (torch.zeros if zeroed else torch.empty)((nbytes,), dtype=torch.uint8, device=device)
+    base = res.data_ptr()
+    if J:
+        _lib.check(_lib.lib().dagr_coco_match(
+            gt, dt, scores, jobs6, rng, thrs, T, MAX_DETS, J, n_gt, n_dt, max_g, max_d, n_out, n_gign,
+            _lib.c_void_p(base + at_order), _lib.c_void_p(base + at_dtm), _lib.c_void_p(base + at_ign),
+            _lib.c_void_p(base + at_gign), _lib.c_void_p(base), _lib.cur_stream(device)), "coco_match")
+    elif not zeroed:
+        res[:4].zero_()                                               # (the status word the launch would have cleared)
+    return res, (res[at_order:at_dtm].view(torch.int32), res[at_dtm:at_ign].view(T, n_out),
+                 res[at_ign:at_gign].view(T, n_out), res[at_gign:], res[:4].view(torch.int32))
+
+
 def coco_match_device(jobs, which, device, to_host=True, all_columns=False):
     """``dagr_coco_match`` for the jobs ``which`` (all within the kernel's bounds): two copies to the device (one float64,
     one int64 array), ONE launch, ONE copy back.  ``{job: (order, dtm, dt_ign, g_ign)}`` with ``order`` the indices of the
@@ -226,27 +255,20 @@ def coco_match_device(jobs, which, device, to_host=True, all_columns=False):
     n_gt, n_dt = len(jobs.gt), len(jobs.dt)
     f64 = np.concatenate([jobs.gt.reshape(-1), jobs.dt.reshape(-1), jobs.scores, jobs.rng[which].reshape(-1), IOU_THRS])
     i64 = np.concatenate([tab, o_off[:, None], gi_off[:, None]], 1)
-    # one output buffer = one copy back: status int32 | order int32[n_out] | dtm, dt_ign uint8[T, n_out] | g_ign uint8
-    at_order, at_dtm = 4, 4 + 4 * n_out
-    at_ign, at_gign = at_dtm + T * n_out, at_dtm + 2 * T * n_out
+    at_order, at_dtm, at_ign, at_gign, _ = _match_layout(T, n_out, n_gign)
     with torch.cuda.device(device):
         fd = torch.from_numpy(np.ascontiguousarray(f64, dtype=np.float64)).to(device)
         jd = torch.from_numpy(np.ascontiguousarray(i64, dtype=np.int64)).to(device)
-        res = (torch.zeros if all_columns else torch.empty)((at_gign + n_gign,), dtype=torch.uint8, device=device)
-        base, f0 = res.data_ptr(), fd.data_ptr()
+        f0 = fd.data_ptr()
 
         def f64_at(n_doubles):
             return _lib.c_void_p(f0 + 8 * n_doubles)
-        if J:
-            _lib.check(_lib.lib().dagr_coco_match(
-                f64_at(0), f64_at(4 * n_gt), f64_at(4 * n_gt + 4 * n_dt), _lib.ptr(jd), f64_at(4 * n_gt + 5 * n_dt),
-                f64_at(4 * n_gt + 5 * n_dt + 2 * J), T, MAX_DETS, J, n_gt, n_dt, int(tab[:, 1].max()), int(tab[:, 3].max()),
-                n_out, n_gign, _lib.c_void_p(base + at_order), _lib.c_void_p(base + at_dtm), _lib.c_void_p(base + at_ign),
-                _lib.c_void_p(base + at_gign), _lib.c_void_p(base), _lib.cur_stream(device)), "coco_match")
+        res, views = match_launch(f64_at(0), f64_at(4 * n_gt), f64_at(4 * n_gt + 4 * n_dt), _lib.ptr(jd),
+                                  f64_at(4 * n_gt + 5 * n_dt), f64_at(4 * n_gt + 5 * n_dt + 2 * J), J, n_gt, n_dt,
+                                  int(tab[:, 1].max()) if J else 0, int(tab[:, 3].max()) if J else 0, n_out, n_gign, device,
+                                  zeroed=all_columns)
         if not to_host:
-            return DeviceMatches(which, o_off, kept, gi_off, res[at_order:at_dtm].view(torch.int32),
-                                 res[at_dtm:at_ign].view(T, n_out), res[at_ign:at_gign].view(T, n_out), res[at_gign:],
-                                 res[:4].view(torch.int32), fd[4 * n_gt + 4 * n_dt:4 * n_gt + 5 * n_dt], jd)
+            return DeviceMatches(which, o_off, kept, gi_off, *views, fd[4 * n_gt + 4 * n_dt:4 * n_gt + 5 * n_dt], jd)
         host = res.cpu().numpy()
     if host[:4].view(np.int32)[0] != 0:
         raise RuntimeError("dagr_coco_match: a job did not fit its arrays (status 1)")
@@ -402,16 +424,103 @@ def precision_on_device(jobs, n_classes, device=None, stats=None):
             flag = torch.from_numpy(flag.astype(np.uint8)).to(device)
             m.dtm[:, cols_d], m.dt_ign[:, cols_d] = flag[:T], flag[T:]
             m.g_ign[entries_d] = torch.from_numpy(np.concatenate([from_host[int(j)][3] for j in on_host]).astype(np.uint8)).to(device)
-        group_ngt = torch.zeros((n_groups,), dtype=torch.int64, device=device)
-        group_ngt.index_add_(0, entry_group, (m.g_ign == 0).to(torch.int64))
-        precision, status = accumulate_device(scores, m.dtm, m.dt_ign, col_group, group_ptr_d, group_ngt)
-        back = torch.cat((precision.reshape(-1).view(torch.uint8), status.view(torch.uint8), m.status.view(torch.uint8))).cpu().numpy()
-    acc_status, match_status = back[-8:].view(np.int32)
+        return precision_read_back(scores, m.dtm, m.dt_ign, m.g_ign, m.status, col_group, entry_group, group_ptr_d, n_classes)[0]
+
+
+def precision_read_back(scores, dtm, dt_ign, g_ign, match_status, col_group, entry_group, group_ptr, n_classes, also=None):
+    """From the matcher's device arrays to the precision array on the host: ``group_ngt`` from ``g_ign``, ``score_order``,
+    ``dagr_coco_accumulate``, and ONE copy back of the precision array, the two status words and ``also`` (a contiguous
+    device tensor, or None).  Returns (precision float64 [T, R, classes, area ranges], the bytes of ``also``); raises on
+    either status."""
+    import torch
+    T, A = len(IOU_THRS), len(AREA_RNG)
+    group_ngt = torch.zeros((n_classes * A,), dtype=torch.int64, device=dtm.device)
+    group_ngt.index_add_(0, entry_group, (g_ign == 0).to(torch.int64))
+    precision, status = accumulate_device(scores, dtm, dt_ign, col_group, group_ptr, group_ngt)
+    parts = (precision.reshape(-1).view(torch.uint8), status.view(torch.uint8), match_status.view(torch.uint8))
+    extra = also.reshape(-1).view(torch.uint8) if also is not None else None
+    back = torch.cat(parts + ((extra,) if extra is not None else ())).cpu().numpy()
+    n_prec = 8 * T * len(REC_THRS) * n_classes * A
+    acc_status, match_status = back[n_prec:n_prec + 8].view(np.int32)
     if match_status != 0:
         raise RuntimeError("dagr_coco_match: a job did not fit its arrays (status 1)")
     if acc_status != 0:
         raise RuntimeError("dagr_coco_accumulate: perm or group_ptr outside the arrays (status 1)")
-    return back[:-8].view(np.float64).reshape(T, len(REC_THRS), n_classes, A).copy()
+    return back[:n_prec].view(np.float64).reshape(T, len(REC_THRS), n_classes, A).copy(), back[n_prec + 8:].copy()
+
+
+def summarize(prec):
+    """The six numbers of the protocol from the precision array [T, R, classes, area ranges] (-1: nothing to average)."""
+    def mean(sel):
+        v = sel[sel > -1]
+        return float(v.mean()) if v.size else -1.0
+    return {"AP": mean(prec[:, :, :, 0]), "AP_50": mean(prec[0, :, :, 0]), "AP_75": mean(prec[5, :, :, 0]),
+            "AP_S": mean(prec[:, :, :, 1]), "AP_M": mean(prec[:, :, :, 2]), "AP_L": mean(prec[:, :, :, 3])}
+
+
+class StreamMapPlan:
+    """``dagr_stream_map_plan``'s workspace and output arrays for a log of ``B`` lanes, ``max_images`` images a lane, ``G``
+    ground-truth rows and ``max_dets`` detection rows an image: allocated once, sized from the capacities
+    (include/dagr_hip.h has the formulas), on ``device``.  ``run(state)`` is the one call: no host synchronisation.
+    Memory: 40 bytes for every detection row the log can hold (``B * max_images * max_dets``), 64 for every ground-truth
+    row, and 32 for each of an image's first ``min(max_dets, 100 * classes)`` rows -- 1.6 GB at B = 8, 1200 images and 4096
+    rows a lane, 70 MB with ``max_dets = 100``."""
+
+    def __init__(self, B, max_images, G, max_dets, n_classes, device):
+        import torch
+        from .. import _lib
+        self.sizes, self.n_classes, self.device = (int(B), int(max_images), int(G), int(max_dets)), int(n_classes), device
+        N, A, C = int(B) * int(max_images), len(AREA_RNG), int(n_classes)
+        pairs, cols = N * min(C, G + max_dets), N * min(max_dets, MAX_DETS * C)
+        need = int(_lib.lib().dagr_stream_map_plan_workspace_bytes(B, max_images, C))
+        if need == 0:
+            raise ValueError(f"stream map plan: batch_size = {B}, max_images = {max_images} and {C} classes are out of range "
+                             f"(1..{_lib.DEFINES['DAGR_MAP_MAX_CLASSES']} classes, batch_size * max_images * classes < 2**28)")
+
+        def new(shape, dtype):
+            return torch.zeros(shape, dtype=dtype, device=device)
+        self.workspace = new((need,), torch.uint8)
+        self.gt, self.dt, self.scores = new((N * G, 4), torch.float64), new((N * max_dets, 4), torch.float64), new((N * max_dets,), torch.float64)
+        self.jobs, self.rng, self.info = new((A * pairs, 6), torch.int64), new((A * pairs, 2), torch.float64), new((A * pairs, 4), torch.int64)
+        self.col_group, self.entry_group = new((A * cols,), torch.int64), new((A * N * G,), torch.int64)
+        self.group_ptr, self.totals = new((C * A + 1,), torch.int64), new((8,), torch.int64)
+        self.area_rngs = torch.from_numpy(np.asarray(AREA_RNG, dtype=np.float64)).to(device)
+        self.iou_thrs = torch.from_numpy(IOU_THRS).to(device)
+
+    def run(self, state):
+        """The plan of the log in ``state`` (a uint8 device tensor of ``dagr_stream_map_bytes``)."""
+        from .. import _lib
+        P = _lib.ptr
+        _lib.check(_lib.lib().dagr_stream_map_plan(
+            P(state), state.numel(), *self.sizes, self.n_classes, P(self.area_rngs), len(AREA_RNG), MAX_DETS,
+            P(self.workspace), self.workspace.numel(), P(self.gt), P(self.dt), P(self.scores), P(self.jobs), P(self.rng),
+            P(self.info), P(self.col_group), P(self.entry_group), P(self.group_ptr), P(self.totals),
+            _lib.cur_stream(self.device)), "stream_map_plan")
+
+    def precision(self, also=None):
+        """From the plan ``run`` left to the precision array: the totals block read back (one small copy: the C entries of
+        match and accumulate take host sizes), ``dagr_coco_match``, then ``precision_read_back``.  Returns (the totals as a
+        dict, precision [T, R, classes, area ranges] or None when the log holds no detection row, the bytes of ``also``)."""
+        import torch
+        from .. import _lib
+        P = _lib.ptr
+        names = ("n_jobs", "n_gt", "n_dt", "n_out", "n_gign", "max_gt", "max_dt", "logged_dets")
+        tot = dict(zip(names, (int(v) for v in self.totals.cpu().numpy())))
+        J, n_out, n_gign = tot["n_jobs"], tot["n_out"], tot["n_gign"]
+        if tot["logged_dets"] == 0 or J == 0:                         # zeros, or -1 everywhere: nothing to launch
+            extra = also.reshape(-1).view(torch.uint8).cpu().numpy().copy() if also is not None else None
+            prec = None if tot["logged_dets"] == 0 else -np.ones((len(IOU_THRS), len(REC_THRS), self.n_classes, len(AREA_RNG)))
+            return tot, prec, extra
+        with torch.cuda.device(self.device):
+            _, (order, dtm, dt_ign, g_ign, status) = match_launch(
+                P(self.gt), P(self.dt), P(self.scores), P(self.jobs), P(self.rng), P(self.iou_thrs), J, tot["n_gt"],
+                tot["n_dt"], tot["max_gt"], tot["max_dt"], n_out, n_gign, self.device)
+            info = self.info[:J]
+            col_first = torch.repeat_interleave(self.jobs[:J, 2], info[:, 1], output_size=n_out)
+            scores = self.scores[col_first + order.long()] if n_out else self.scores[:0]
+            prec, extra = precision_read_back(scores, dtm, dt_ign, g_ign, status, self.col_group[:n_out],
+                                              self.entry_group[:n_gign], self.group_ptr, self.n_classes, also=also)
+        return tot, prec, extra
 
 
 def _precision_from_jobs(images, n_classes, matcher):
@@ -455,9 +564,4 @@ def evaluate_detection(gt_boxes_list, dt_boxes_list, classes=("car", "pedestrian
                 p = _accumulate(per_image)
                 if p is not None:
                     prec[:, :, c, ai] = p
-
-    def mean(sel):
-        v = sel[sel > -1]
-        return float(v.mean()) if v.size else -1.0
-    return {"AP": mean(prec[:, :, :, 0]), "AP_50": mean(prec[0, :, :, 0]), "AP_75": mean(prec[5, :, :, 0]),
-            "AP_S": mean(prec[:, :, :, 1]), "AP_M": mean(prec[:, :, :, 2]), "AP_L": mean(prec[:, :, :, 3])}
+    return summarize(prec)

@@ -970,6 +970,89 @@ int dagr_stream_labels_at(void *state, size_t bytes, int32_t B, int32_t max_keyf
                           float *gt_box, int32_t *gt_label, int64_t *gt_id, int32_t *n_gt, void *stream);
 
 /* ------------------------------------------------------------------------ *
+ * Event stream mAP: the evaluated images logged on the device, and the COCO protocol's job list built from the log
+ *   dagr_stream_map_log appends, for every lane, the step's detections and ground truth to a log of fixed capacity in a
+ *   caller-owned state -- one launch of one wave per lane, no atomics, no host synchronisation -- and dagr_stream_map_plan
+ *   turns the log, where it lies, into everything dagr_coco_match and dagr_coco_accumulate (below) take, in the order of
+ *   utils/coco_eval.py:build_jobs.  dagr_amd/streaming.py: MapDefinition is the log's rule in numpy, bit for bit; the
+ *   metric's definition is utils/coco_eval.py:evaluate_detection on its images.
+ *
+ * An image is one (lane, instant).  With I = max_images, D = max_dets, and the step's det fp32[B, A, 6] (x1, y1, x2, y2,
+ * score, label) / n_keep int32[B], gt_box fp32[B, G, 4] (x1, y1, x2, y2) / gt_label int32[B, G] / n_gt int32[B] (as
+ * dagr_stream_labels_at writes them) and t_ref int64[B]:
+ *   log:   lane b is logged only if n_gt[b] > 0 (metrics only where there is a box: evaluated_images' rule); n_gt[b] < 0:
+ *          unlabelled += 1, n_gt[b] == 0: empty += 1, nothing else.  A lane that holds I images already: dropped_images += 1,
+ *          nothing else.  Otherwise the image takes the lane's next slot: its t_ref[b], its first min(n_gt[b], G)
+ *          ground-truth rows and labels, and its first min(n_keep[b], D) detection rows in det order (n_keep clamped to
+ *          0 .. A); cut_dets += the rows cut.  Rows are kept as the 32-bit words they are.
+ *   order: the images of the protocol are lane-major -- all of lane 0's in log order, then lane 1's, ... -- which matters
+ *          only for ties in score.
+ *   plan:  a detection row counts for class c iff its label == (float)c, a ground-truth row iff its label == c; labels
+ *          outside [0, n_classes) belong to no job.  A job is one (class, area range, image) with at least one row of the
+ *          class, ordered by class, then area range, then image.  (x, y, w, h) = x1, y1, x2 - x1, y2 - y1 with the
+ *          subtraction in fp32 and then widened, as utils/coco_eval.py:_xywh does.
+ *
+ * state: dagr_stream_map_bytes(B, I, G, D) bytes (0: B outside 1..65535, I outside 1..DAGR_MAP_MAX_IMAGES, G outside
+ *        1..DAGR_COCO_MAX_GT, D outside 1..DAGR_COCO_MAX_DT, or B * I * (G + 2 D + 256) >= 2^31 - 1: every offset of the plan is
+ *        an int32), 16-byte aligned, dagr_stream_map_reset before the first log and to empty it (it zeroes the words; what lies
+ *        behind them means nothing until a log has written it).  It holds, each at the next multiple of 16 bytes behind the
+ *        one before:
+ *          lane     int64 [B, DAGR_MAP_WORDS]: images (logged), dropped_images, cut_dets, unlabelled, empty
+ *          t        int64 [B, I]
+ *          n_gt     int32 [B, I]
+ *          n_dt     int32 [B, I]
+ *          gt_box   fp32  [B, I, G, 4]
+ *          gt_label int32 [B, I, G]
+ *          det      fp32  [B, I, D, 6]
+ * log: A in 1..DAGR_COCO_MAX_DT; gt_box 16-byte aligned.  Because G and D are bounded here, no job of the plan ever exceeds
+ * dagr_coco_match's per-job bounds.
+ *
+ * plan: n_classes in 1..DAGR_MAP_MAX_CLASSES with B * I * n_classes < 2^28; area_rngs fp64[n_areas, 2] (the host's
+ * AREA_RNG, never recomputed here), n_areas in 1..DAGR_MAP_MAX_AREAS; max_dets_per_job the protocol's cut (MAX_DETS),
+ * 1..DAGR_COCO_MAX_DETS; workspace of dagr_stream_map_plan_workspace_bytes(B, I, n_classes) bytes (0: out of range), 16-byte
+ * aligned, contents irrelevant.  Outputs, every one sized from the capacities (N = B * I, P = N * min(n_classes, G + D)
+ * pairs at most, K = N * min(D, max_dets_per_job * n_classes) columns an area range at most):
+ *   gt_xywh fp64[N * G, 4], dt_xywh fp64[N * D, 4], dt_score fp64[N * D]: the rows of an (image, class) once, shared by its
+ *                           area ranges, class after class and inside a class image after image, in row order
+ *   jobs int64[n_areas * P, 6], area_rng fp64[n_areas * P, 2]: dagr_coco_match's, the columns and g_ign entries of ALL jobs
+ *                           laid out in job order (column_layout)
+ *   job_info int64[n_areas * P, DAGR_MAP_JOB_WORDS]: group = class * n_areas + area range, kept = min(D of the job,
+ *                           max_dets_per_job), first column, first g_ign entry
+ *   col_group int64[n_areas * K], entry_group int64[n_areas * N * G]: the group of every column / g_ign entry
+ *   group_ptr int64[n_classes * n_areas + 1]: dagr_coco_accumulate's (accumulate_groups)
+ *   totals int64[DAGR_MAP_TOTALS]: n_jobs, n_gt, n_dt, n_out, n_gign, the largest G and the largest D of a job, and the
+ *                           detection rows the log holds (in a class or not)
+ * Entries behind the totals' counts are left as they are.  Count, scan (csrc/scan.hip), scatter: five launches and a
+ * memset, grids bounded by the capacity, the rows touched bounded by the lanes' words on the device (the count arrays, four
+ * ints per (slot, class), are scanned whole); every position is a prefix sum, so no atomic decides an order.  No host
+ * synchronisation.  All arrays are device memory.  The totals come from ONE workgroup of 1024 threads that walks all
+ * B * I * n_classes pairs and all B * I slots, whatever the log holds: its length grows with the capacity, not with the
+ * lanes' words -- measured up to 76800 pairs (B = 8, I = 1200, two classes, the whole plan 16 ms with match and
+ * accumulate), NOT measured near the 2^28 limit, where it would take about 2^18 iterations a thread.
+ * The class rule for detections (label == (float)c) deliberately differs from DetectionBuffer's truncation for labels that
+ * are no whole number: 0.5 counts for no class here and for class 0 there.  The engine writes whole labels.
+ * DAGR_ERR_INVALID_ARG before any launch: sizes out of range, a state or workspace that is too small, NULL or misaligned
+ * arrays.
+ * ------------------------------------------------------------------------ */
+#define DAGR_MAP_WORDS 5
+#define DAGR_MAP_MAX_IMAGES 65535
+#define DAGR_MAP_MAX_CLASSES 256
+#define DAGR_MAP_MAX_AREAS 8
+#define DAGR_MAP_JOB_WORDS 4
+#define DAGR_MAP_TOTALS 8
+size_t dagr_stream_map_bytes(int32_t B, int32_t max_images, int32_t G, int32_t max_dets);
+int dagr_stream_map_reset(void *state, size_t bytes, int32_t B, int32_t max_images, int32_t G, int32_t max_dets, void *stream);
+int dagr_stream_map_log(void *state, size_t bytes, int32_t B, int32_t max_images, int32_t G, int32_t max_dets,
+                        const float *det, const int32_t *n_keep, int32_t A, const float *gt_box, const int32_t *gt_label,
+                        const int32_t *n_gt, const int64_t *t_ref, void *stream);
+size_t dagr_stream_map_plan_workspace_bytes(int32_t B, int32_t max_images, int32_t n_classes);
+int dagr_stream_map_plan(const void *state, size_t bytes, int32_t B, int32_t max_images, int32_t G, int32_t max_dets,
+                         int32_t n_classes, const double *area_rngs, int32_t n_areas, int32_t max_dets_per_job,
+                         void *workspace, size_t workspace_bytes, double *gt_xywh, double *dt_xywh, double *dt_score,
+                         int64_t *jobs, double *area_rng, int64_t *job_info, int64_t *col_group, int64_t *entry_group,
+                         int64_t *group_ptr, int64_t *totals, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * Event stream picture: events, boxes, track ids and trails of a step, drawn on the device
  *   dagr_stream_render paints one uint8 BGR frame [H, W, 3] per lane from what a stream keeps on the device -- the
  *   resident raw events of a dagr_stream_stage state, the step's det / n_keep, the tracker's track_id, and the trail rings

@@ -113,7 +113,7 @@ import torch
 import _common as C
 from dagr.data.evt import encode_events
 from dagr.streaming import (EventStream, _assign_options, _flicker_options, _identity_options, _motion_options, _rescue_options,
-                            _hota_options, _label_options, _render_options, _score_options, _track_options, hota_summary,
+                            _hota_options, _label_options, _map_options, _render_options, _score_options, _track_options, hota_summary,
                             identity_summary,
                             score_summary)
 from dagr.utils.buffers import DETECTION_DTYPE, detections_to_records
@@ -185,6 +185,9 @@ def stream_options(p):
                    "boxes whose width or height is not above this")
     g.add_argument("--label_min_diag", type=float, default=None, help="with --track_score_every_step: drop interpolated boxes "
                    "whose diagonal is not above this")
+    g.add_argument("--map", action="store_true", help="detection mAP over EVERY step: log every step's detections and the "
+                   "source's interpolated labels on the device and run the COCO protocol on the log at the end")
+    g.add_argument("--map_max_images", type=int, default=None, help="with --map: images the log holds a lane (default 1200)")
     g.add_argument("--raw_frames", action="store_true", help="the source's frames are sensor-size BGR uint8 frames: prepare "
                    "them on the device (crop, shrink by the --downsample factor, / 255)")
     g.add_argument("--render", type=str, default=None, metavar="DIR", help="draw every step on the device -- events, box "
@@ -337,6 +340,25 @@ def label_options(a, source=None):
     if source is not None and not callable(getattr(source, "label_instants", None)):
         raise SystemExit("run_stream.py: --track_score_every_step needs a source with label_instants() (its labelled "
                          f"instants, sorted int64) besides labels(t); {type(source).__name__} has none")
+    return given
+
+
+def map_options(a, source=None):
+    """``map=`` of the stream the flags describe: None without ``--map``, else the options that were given.  With ``source``
+    the refusal of a source without labelled keyframes."""
+    given = {} if getattr(a, "map_max_images", None) is None else dict(max_images=a.map_max_images)
+    if not getattr(a, "map", False):
+        if given:
+            raise SystemExit("run_stream.py: --map_max_images needs --map")
+        return None
+    try:
+        _map_options(given, "run_stream.py")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    if source is not None and not (callable(getattr(source, "labels", None)) and callable(getattr(source, "label_instants", None))):
+        raise SystemExit("run_stream.py: --map needs a source with labels(t) and label_instants() (its labelled instants, "
+                         f"sorted int64); {type(source).__name__} lacks one (the built-in synthetic sequence carries no "
+                         "labelled boxes)")
     return given
 
 
@@ -494,13 +516,16 @@ def play(a, model, source, dev):
     cap = getattr(a, "max_lane_events", None)
     decode = getattr(a, "decode", None)
     hota = hota_options(a)                 # (first: it implies the two flags behind it)
+    mapped, labels = map_options(a), label_options(a)
+    if mapped is not None and labels is None:
+        labels = {}                        # --map alone: the label store with its defaults
     stream = EventStream(model, window_us=a.window_us or None, downsample=a.downsample, sensor_size=sensor_size(a),
                          frame_size=raw_size, frame_bgr=True, max_lane_events=cap,
                          denoise_us=getattr(a, "denoise_us", None), refractory_us=getattr(a, "refractory_us", None),
                          flicker=flicker_options(a), trail_us=getattr(a, "trail_us", None),
                          track=track_options(a), motion=motion_options(a), rescue=rescue_options(a), assign=assign_option(a),
                          score=score_options(a),
-                         identity=identity_options(a), hota=hota, labels=label_options(a),
+                         identity=identity_options(a), hota=hota, labels=labels, map=mapped,
                          decode=decode, max_decoded=getattr(a, "max_decoded", None),
                          t_base=int(source.t_range()[0]) if decode else None,      # (the words' times start at the sequence's)
                          render=render_options(a))
@@ -543,7 +568,10 @@ def play(a, model, source, dev):
             while pushed < len(instants) and (pushed == 0 or instants[pushed - 1] <= t_step):
                 push_keyframe(stream, source, instants[pushed])
                 pushed += 1
-            stream.score_step()                 # two launches: the labels at the step's own instant, then the scorer
+            if stream.score is not None:
+                stream.score_step()             # two launches: the labels at the step's own instant, then the scorer
+            if stream.map_options is not None:
+                stream.map_step()               # one launch more (two without a scorer): the step goes into the log
         labelled = source.labels(t_step) if stream.score is not None and stream.labels is None else None
         if labelled is not None:                # one more launch, on the step's own device arrays
             boxes, labels, ids = labelled
@@ -564,6 +592,7 @@ def play(a, model, source, dev):
         counters = stream.track_score()
         a.stream_score = dict(score_summary(counters, stream.scored_objects())["total"], steps=int(counters["steps"].sum()))
     a.stream_labels = {k: int(v.sum()) for k, v in stream.label_counts().items()} if stream.labels is not None else None
+    a.stream_map = stream.map() if stream.map_options is not None else None
     a.stream_identity = identity_summary(stream.identity())["total"] if stream.identity_options is not None else None
     a.stream_hota = hota_summary(stream.hota())["total"] if stream.hota_options is not None else None
     return out
@@ -596,6 +625,7 @@ def main(argv=None, model_factory=None, source=None):
     score_options(a)
     identity_options(a)
     label_options(a)
+    map_options(a)
     render_options(a)
     a.batch_size = 1                     # one sequence: one lane
     world, rank, dev = C.distributed()
@@ -608,6 +638,7 @@ def main(argv=None, model_factory=None, source=None):
         source = SyntheticStream(a)
     score_options(a, source)               # (a source without labels is refused in front of the model too)
     label_options(a, source)
+    map_options(a, source)
     geometry = types.SimpleNamespace(width=int(getattr(source, "width", a.width)), height=int(getattr(source, "height", a.height)))
     args, net = (model_factory or C.build_model)(a, geometry, dev)
     net = net.eval()
@@ -665,7 +696,8 @@ def main(argv=None, model_factory=None, source=None):
                         "mostly lost")
         if getattr(a, "stream_labels", None) is not None:
             c = a.stream_labels
-            tracked += (f"; every step scored against {c['keyframes']} resident keyframes, interpolated: {c['labelled']} steps "
+            what = "scored" if a.stream_score is not None else "logged"
+            tracked += (f"; every step {what} against {c['keyframes']} resident keyframes, interpolated: {c['labelled']} steps "
                         f"labelled, {c['outside']} outside the keyframes, {c['gap']} in a gap")
         if getattr(a, "stream_identity", None) is not None:
             c = a.stream_identity
@@ -680,6 +712,12 @@ def main(argv=None, model_factory=None, source=None):
         print(f"{len(steps)} steps of {a.step_us} us on {window} in {seconds:.2f} s "
               f"({1e3 * seconds / max(1, len(steps)):.2f} ms per step; {a.stream_steps[0]} with the full window, "
               f"{a.stream_steps[1]} on held image maps) -> {path}: {len(rec)} detections{tracked}")
+        if getattr(a, "stream_map", None) is not None:
+            c = a.stream_map
+            print(", ".join(f"{k} {float(c[k]):.4f}" for k in ("AP", "AP_50", "AP_75", "AP_S", "AP_M", "AP_L"))
+                  + f" over {int(c['images'].sum())} logged steps ({int(c['dropped_images'].sum())} dropped, "
+                  f"{int(c['unlabelled'].sum())} without labels, {int(c['empty'].sum())} without a box, "
+                  f"{int(c['cut_dets'].sum())} detections cut)")
     C.finish(world)
     return path
 
