@@ -16,10 +16,13 @@ namespace dagr {
 namespace {
 
 // One event through a cell's integrator; both kernels below call it.
-// downsample_events.py:117: change_map += p * 1.0 / (fx * fy) -- a float64 product rounded into the fp32 map;
-// :119 passes when |state| >= 1; :121 subtracts the polarity of an event that passed.
-__device__ __forceinline__ bool integrate_event(float &state, float pol, float inc) {
-    state = (float)((double)state + (double)pol * (double)inc);
+// downsample_events.py:118: change_map[y_l, x_l] += p[i] * 1.0 / (fx * fy) -- the float64 quotient +-1 / (fx * fy), added
+// to the fp32 cell in float64 and rounded into it; :120 passes when |state| >= 1; :122 subtracts the polarity of an event
+// that passed.  `inc` is the float64 1.0 / (fx * fy), formed on the host and never rounded to fp32 (at an area that is no
+// power of two an fp32 increment keeps other events).  Contract: pol in {-1, 0, +1}; then pol * inc is exact and equals the
+// reference's (p * 1.0) / area bit for bit, division being correctly rounded and symmetric in sign.
+__device__ __forceinline__ bool integrate_event(float &state, float pol, double inc) {
+    state = (float)((double)state + (double)pol * inc);
     const bool pass = fabsf(state) >= 1.0f;
     if (pass) state -= pol;
     return pass;
@@ -28,7 +31,7 @@ __device__ __forceinline__ bool integrate_event(float &state, float pol, float i
 __global__ __launch_bounds__(kBlock) void k_downsample_cells(const int32_t *__restrict__ order,       // event ids by (cell, time)
                                                             const int32_t *__restrict__ cell_of,     // [n_runs] cell id
                                                             const int32_t *__restrict__ run_end,     // [n_runs] cumulative
-                                                            int n_runs, const int8_t *__restrict__ p, float inc,
+                                                            int n_runs, const int8_t *__restrict__ p, double inc,
                                                             float *__restrict__ change_map, uint8_t *__restrict__ keep) {
     const int r = blockIdx.x * kBlock + threadIdx.x;
     if (r >= n_runs) return;
@@ -82,7 +85,7 @@ __global__ __launch_bounds__(kBlock) void k_front_keys(const int32_t *__restrict
 // integrates as every other (the reference downsamples the whole sensor and crops afterwards) but keeps nothing.
 __global__ __launch_bounds__(kBlock) void k_front_integrate(const uint32_t *__restrict__ key, const int32_t *__restrict__ idx,
                                                            int n, uint32_t sentinel, int cells_w, int cells_h, int width,
-                                                           int height, const int8_t *__restrict__ p, float inc,
+                                                           int height, const int8_t *__restrict__ p, double inc,
                                                            float *__restrict__ maps, int32_t *__restrict__ flag) {
     const int k = blockIdx.x * kBlock + threadIdx.x;
     if (k >= n) return;
@@ -129,7 +132,7 @@ extern "C" int dagr_downsample_events(const int32_t *order, const int32_t *run_c
     DAGR_CHECK_ARG(n_runs >= 0 && fx >= 1 && fy >= 1, "bad sizes");
     if (n_runs == 0) return DAGR_OK;
     DAGR_CHECK_ARG(order && run_cell && run_end && polarity && change_map && keep, "NULL pointer");
-    const float inc = (float)(1.0 / (double)(fx * fy));
+    const double inc = 1.0 / (double)(fx * fy);
     k_downsample_cells<<<(unsigned)ceil_div(n_runs, kBlock), kBlock, 0, (hipStream_t)stream>>>(
         order, run_cell, run_end, n_runs, polarity, inc, change_map, keep);
     DAGR_CHECK_LAUNCH();
@@ -176,7 +179,7 @@ extern "C" int dagr_stream_downsample(void *front, size_t front_bytes, int32_t B
     const int n = (int)n_raw, bits = key_bits((int64_t)B * cells);
     const unsigned grid = (unsigned)ceil_div(n_raw, kBlock);
     const uint32_t sentinel = (uint32_t)((int64_t)B * cells);
-    const float inc = (float)(1.0 / (double)(fx * fy));
+    const double inc = 1.0 / (double)(fx * fy);
     const int32_t *xy = (const int32_t *)xy_raw;
     DAGR_CHECK_ARG(sort_push_fits(f.s, n, bits), "stream front: the sort asks for more temporary storage than the state holds");
     with_batch(batch_raw, batch_is_int64, [&](auto *batch) {

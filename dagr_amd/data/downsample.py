@@ -2,6 +2,10 @@
 that turns DSEC's 640x480 ``events.h5`` into the half-resolution ``events_2x.h5`` the reference trains and tests on).
 Same contract: events as a dict of arrays (here device tensors ``x, y`` integer, ``t``, ``p`` in {-1, +1}), the
 ``change_map`` integrator state carried from chunk to chunk, returns the surviving events with ``x // fx``, ``y // fy``.
+Any integer factor pair is taken; the cell adds the reference's float64 quotient ``p * 1.0 / (fx * fy)``.  An event whose
+cell lies outside ``output_height x output_width`` (the strip right of / below the last whole cell when the input is no
+multiple of the factor; the reference's loop raises ``IndexError`` there) is refused with a ``ValueError`` that names the
+first such event, before anything is launched or ``change_map`` is touched.
 
 This is the file-conversion route: it builds its runs with ``torch.unique_consecutive`` and cuts its result with a boolean
 mask, both of which wait for the device.  A LIVE stream of raw sensor events goes through
@@ -23,7 +27,16 @@ def downsample_events(events, input_height, input_width, output_height, output_w
     n = x.shape[0]
     if n == 0:
         return {k: v for k, v in events.items()}, change_map
-    cell = (torch.div(y.long(), fy, rounding_mode="floor") * output_width + torch.div(x.long(), fx, rounding_mode="floor"))
+    cx, cy = torch.div(x.long(), fx, rounding_mode="floor"), torch.div(y.long(), fy, rounding_mode="floor")
+    # an event in the strip right of / below the last whole cell (input_width no multiple of fx) would alias into the next
+    # row's first cell or write past the end of the map; the reference's loop raises IndexError there
+    outside = (cx < 0) | (cx >= output_width) | (cy < 0) | (cy >= output_height)
+    if bool(outside.any()):
+        i = int(outside.reshape(-1).nonzero()[0, 0])
+        raise ValueError(f"downsample_events: event {i} (x = {int(x[i])}, y = {int(y[i])}) lies in cell ({int(cx[i])}, "
+                         f"{int(cy[i])}), outside the {output_width} x {output_height} cell grid of the change map "
+                         f"(factors {fx} x {fy}); crop the events to {fx * output_width} x {fy * output_height} first")
+    cell = cy * output_width + cx
     key, order = torch.sort(cell, stable=True)
     cells, run = torch.unique_consecutive(key, return_counts=True)
     keep = torch.empty((n,), dtype=torch.uint8, device=dev)

@@ -44,9 +44,10 @@ the integrate-and-fire loop of ``scripts/downsample_events.py:91-124`` and cut t
 
 * the cell grid is ``(W_in // fx, H_in // fy)`` and covers the model's ``(W, H)``; every lane owns an fp32 change map over
   it, zero after construction and after ``reset()``, carried from push to push;
-* a lane's raw events go through their cells in arrival order: the cell adds ``p / (fx * fy)`` (a float64 product rounded
-  into the fp32 cell, ``fp32(1 / (fx * fy))`` being the increment, as ``k_downsample_cells`` has it); when ``|cell| >= 1``
-  the event survives at ``(x // fx, y // fy)`` and ``p`` is subtracted;
+* a lane's raw events go through their cells in arrival order: the cell adds ``p * 1.0 / (fx * fy)`` as
+  ``scripts/downsample_events.py:118`` has it -- the float64 quotient, added to the fp32 cell in float64 and rounded into
+  it; the increment is never rounded to fp32, which at an area ``fx * fy`` that is no power of two would keep other events
+  -- with ``p`` in {-1, 0, +1}; when ``|cell| >= 1`` the event survives at ``(x // fx, y // fy)`` and ``p`` is subtracted;
 * a survivor with ``x >= W`` or ``y >= H`` is dropped (the dataset's row cut), and so is an event right of / below the last
   whole cell; a raw event outside ``[0, W_in) x [0, H_in)`` is malformed (status bit of value 16);
 * what is left is pushed as above, but the clock is the sensor's: the order checks run on the raw arrays, and the lane's
@@ -2107,7 +2108,6 @@ class StreamDefinition:
     def _downsample(self, x, y, t, p, batch):
         """The survivors of a checked raw push, at the cells' coordinates and cut to the model's ``W x H``."""
         fx, fy, w_in, h_in = self.front
-        inc = np.float64(np.float32(1.0 / (fx * fy)))
         cells_h, cells_w = self.change_map.shape[1:]
         keep = np.zeros(len(t), bool)
         cx, cy = x.astype(np.int64) // fx, y.astype(np.int64) // fy
@@ -2116,7 +2116,9 @@ class StreamDefinition:
                 continue
             cell = (int(batch[i]), int(cy[i]), int(cx[i]))
             pol = np.float32(p[i])
-            state = np.float32(np.float64(self.change_map[cell]) + np.float64(pol) * inc)
+            # downsample_events.py:118, change_map[y_l, x_l] += p[i] * 1.0 / (fx * fy): the float64 quotient, added to the
+            # fp32 cell in float64 and rounded into it
+            state = np.float32(np.float64(self.change_map[cell]) + np.float64(p[i]) * 1.0 / (fx * fy))
             if np.abs(state) >= np.float32(1):
                 keep[i] = cx[i] < self.W and cy[i] < self.H
                 state = np.float32(state - pol)

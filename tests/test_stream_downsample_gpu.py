@@ -4,7 +4,9 @@ window on the same engine, a hot pixel, buffer growth, status bit 16, the absenc
 scripts/run_stream.py --downsample.
 
 The sequence and its reference are tests/stream_downsample_cases.py's (8 raw pushes, B = 3 lanes, a 640x480 sensor over the
-320x215 model); tests/test_stream_downsample_cpu.py holds the definition to oracle/downsample.py on the same sequence."""
+320x215 model); tests/test_stream_downsample_cpu.py holds the definition to oracle/downsample.py on the same sequence.
+That sequence has 2 x 2 cells, where the increment is a power of two; the front alone at 3 x 3, 4 x 3 and 3 x 1 runs on
+tests/downsample_factor_cases.py's chunks against the reference script's own recorded outputs."""
 import ctypes
 import os
 import sys
@@ -16,6 +18,7 @@ import torch
 from dagr_amd import _lib
 from dagr_amd.streaming import EventStream, StreamDefinition
 from dagr_amd.utils import synthetic as syn
+from tests import downsample_factor_cases as fc
 from tests import stream_downsample_cases as sc
 from tests.test_streaming_gpu import _Stager, _assert_same_detections, _dev, _model, _window_dev
 
@@ -44,42 +47,68 @@ def _windows():
     return _WINDOWS
 
 
-class _FrontStager(_Stager):
-    """dagr_stream_downsample + dagr_stream_stage_dev on a bare graph workspace."""
+class _Front:
+    """dagr_stream_downsample on a front state of its own: ``lanes`` lanes of a ``sensor`` = (W_in, H_in) sensor in cells of
+    ``factors`` = (fx, fy) over a ``model`` = (width, height) model; the sequence's geometry unless told otherwise."""
 
-    def __init__(self, cap, max_push):
-        super().__init__(cap)
-        self.max_push = max_push
-        nbytes = self.L.dagr_stream_front_bytes(B, sc.CW, sc.CH, max_push)
-        assert nbytes > 4 * B * sc.CW * sc.CH
+    def __init__(self, max_push, lanes=B, factors=(sc.F, sc.F), sensor=(sc.W_IN, sc.H_IN), model=(W, H)):
+        self.L, self.dev = _lib.lib(), torch.device("cuda:0")
+        self.max_push, self.lanes, self.factors, self.sensor, self.model = max_push, lanes, factors, sensor, model
+        self.cw, self.ch = sensor[0] // factors[0], sensor[1] // factors[1]
+        nbytes = self.L.dagr_stream_front_bytes(lanes, self.cw, self.ch, max_push)
+        assert nbytes > 4 * lanes * self.cw * self.ch
         self.front = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        _lib.check(self.L.dagr_stream_front_reset(_lib.ptr(self.front), nbytes, B, sc.CW, sc.CH, max_push,
+        _lib.check(self.L.dagr_stream_front_reset(_lib.ptr(self.front), nbytes, lanes, self.cw, self.ch, max_push,
                                                   _lib.cur_stream(self.dev)), "front_reset")
+        if not hasattr(self, "status"):
+            self.status = torch.zeros((1,), dtype=torch.int32, device=self.dev)
         self.s_xy = torch.zeros((max_push, 2), dtype=torch.int16, device=self.dev)
         self.s_t = torch.zeros((max_push,), dtype=torch.int64, device=self.dev)
         self.s_p = torch.zeros((max_push,), dtype=torch.int8, device=self.dev)
         self.s_batch = torch.zeros((max_push,), dtype=torch.int32, device=self.dev)
         self.s_n = torch.full((1,), -1, dtype=torch.int32, device=self.dev)
 
+    def downsample(self, s, batch_dtype=np.int64):
+        """One raw push through the front: the return code and the raw ``t`` and ``batch`` on the device."""
+        P = _lib.ptr
+        xy = _dev(np.stack([s["x"], s["y"]], -1).astype(np.int16).reshape(-1, 2))
+        t, p, batch = _dev(s["t"]), _dev(s["p"]), _dev(s["batch"].astype(batch_dtype))
+        rc = self.L.dagr_stream_downsample(P(self.front), self.front.numel(), self.lanes, self.max_push, *self.factors,
+                                           *self.sensor, *self.model, P(xy), P(t), P(p), P(batch),
+                                           1 if batch_dtype == np.int64 else 0, len(s["t"]), P(self.s_xy), P(self.s_t),
+                                           P(self.s_p), P(self.s_batch), P(self.s_n), P(self.status),
+                                           _lib.cur_stream(self.dev))
+        return rc, t, batch
+
+    def survivors(self):
+        n = int(self.s_n)
+        return dict(x=self.s_xy[:n, 0].cpu().numpy(), y=self.s_xy[:n, 1].cpu().numpy(), t=self.s_t[:n].cpu().numpy(),
+                    p=self.s_p[:n].cpu().numpy(), batch=self.s_batch[:n].cpu().numpy())
+
+    def maps(self):
+        return self.front[:4 * self.lanes * self.cw * self.ch].view(torch.float32).view(self.lanes, self.ch, self.cw) \
+            .cpu().numpy()
+
+
+class _FrontStager(_Stager, _Front):
+    """dagr_stream_downsample + dagr_stream_stage_dev on a bare graph workspace."""
+
+    def __init__(self, cap, max_push):
+        _Stager.__init__(self, cap)
+        _Front.__init__(self, max_push)
+
     def stage(self, s, batch_dtype=np.int64):
         P, st = _lib.ptr, _lib.cur_stream(self.dev)
         n = len(s["t"])
-        xy = _dev(np.stack([s["x"], s["y"]], -1).astype(np.int16).reshape(-1, 2))
-        t, p, batch = _dev(s["t"]), _dev(s["p"]), _dev(s["batch"].astype(batch_dtype))
         is64 = 1 if batch_dtype == np.int64 else 0
         t_now = None if s["t_now"] is None else _dev(s["t_now"])
-        rc = self.L.dagr_stream_downsample(P(self.front), self.front.numel(), B, self.max_push, sc.F, sc.F, sc.W_IN, sc.H_IN,
-                                           W, H, P(xy), P(t), P(p), P(batch), is64, n, P(self.s_xy), P(self.s_t), P(self.s_p),
-                                           P(self.s_batch), P(self.s_n), P(self.status), st)
+        rc, t, batch = self.downsample(s, batch_dtype)
         if rc:
             return rc
         return self.L.dagr_stream_stage_dev(ctypes.byref(self.g.desc), P(self.g.workspace), P(self.state), B, self.state_cap,
                                             P(self.s_xy), P(self.s_t), P(self.s_p), P(self.s_batch), P(self.s_n), n, P(t),
                                             P(batch), is64, n, P(t_now), sc.WINDOW_US, P(self.pos), P(self.feat),
                                             P(self.batch), P(self.n_dev), P(self.lane_count), P(self.status), st)
-
-    def maps(self):
-        return self.front[:4 * B * sc.CW * sc.CH].view(torch.float32).view(B, sc.CH, sc.CW).cpu().numpy()
 
 
 def _assert_staged(st, want, where):
@@ -128,6 +157,84 @@ def test_the_front_and_the_staging_equal_the_definition_and_the_build_continues(
             assert torch.equal(st.out[2][:n], ref.out[2][:n]), k
         before = counts
     assert before.tolist() == [0, 0, 0]
+
+
+_FACTOR_CASES = {}
+
+
+def _factor_case(fx, fy):
+    """tests/downsample_factor_cases.py's chunks as three raw pushes of 2 lanes (chunk 0 cut in two, then chunk 1; lane 1 a
+    shifted copy) on a sensor one pixel larger than the 8 x 6 cells in every direction that has a strip (a factor of 1 has
+    none), with four events per lane and chunk in that strip, over a model one cell smaller than the grid: ``(sensor,
+    model, pushes, per push the definition's survivors and maps)``, computed once."""
+    if (fx, fy) in _FACTOR_CASES:
+        return _FACTOR_CASES[(fx, fy)]
+    sx, sy = fc.CW * fx, fc.CH * fy                       # the first pixel right of / below the last whole cell
+    sensor, model = (sx + (fx > 1), sy + (fy > 1)), (fc.CW - 1, fc.CH - 1)
+    rng = np.random.Generator(np.random.PCG64(31 * fx + fy))
+
+    def with_strip(ev):
+        ry = rng.integers(0, sy, 4)
+        pts = [(sx, ry[0]), (int(rng.integers(0, sx)), sy), (sx, sy), (sx, ry[3])] if fy > 1 else [(sx, int(v)) for v in ry]
+        at = np.array([3, 5000, 17000, fc.CHUNK_EVENTS - 1])
+        return dict(x=np.insert(ev["x"], at, [q[0] for q in pts]), y=np.insert(ev["y"], at, [q[1] for q in pts]),
+                    t=np.insert(ev["t"], at, ev["t"][at]), p=np.insert(ev["p"], at, 1))
+
+    pushes = []
+    for ev in fc.chunks(fx, fy):
+        lanes = [with_strip(ev), with_strip(fc.shifted(ev))]
+        cuts = (0, 11003, len(lanes[0]["t"])) if not pushes else (0, len(lanes[0]["t"]))
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            s = {k: np.concatenate([lane[k][a:b] for lane in lanes]) for k in ("x", "y", "t", "p")}
+            s["batch"] = np.repeat(np.arange(2, dtype=np.int64), b - a)
+            pushes.append(s)
+    d = StreamDefinition(2, *model, downsample=(fx, fy), sensor_size=sensor)
+    assert d.change_map.shape == (2, fc.CH, fc.CW)
+    want = []
+    for s in pushes:
+        x, y, t, p, batch = d._downsample(s["x"], s["y"], s["t"], s["p"], s["batch"])
+        want.append((dict(x=x, y=y, t=t, p=p, batch=batch), d.change_map.copy()))
+    _FACTOR_CASES[(fx, fy)] = sensor, model, pushes, want
+    return _FACTOR_CASES[(fx, fy)]
+
+
+@pytest.mark.parametrize("batch_dtype", [np.int64, np.int32], ids=["int64", "int32"])
+@pytest.mark.parametrize("fx,fy", [(3, 3), (4, 3), (3, 1)], ids=["3x3", "4x3", "3x1"])
+def test_the_front_equals_the_reference_script_at_areas_that_are_no_power_of_two(fx, fy, batch_dtype):
+    """k_front_integrate where the increment ``1 / (fx * fy)`` is no power of two: after every push the survivors, their
+    count and the lanes' maps equal the definition's bit for bit, and lane 0 -- the fixture's own chunks plus events in the
+    strip, which are dropped without a status bit -- equals what the reference's scripts/downsample_events.py kept and left
+    in its change map (tests/golden/ref_py_downsample_factors.npz), cut to the model: a cell outside the model integrates as
+    every other and keeps nothing."""
+    fc.check_inputs(fx, fy)
+    sensor, model, pushes, want = _factor_case(fx, fy)
+    fr = _Front(len(pushes[-1]["t"]), lanes=2, factors=(fx, fy), sensor=sensor, model=model)
+    assert (fr.cw, fr.ch) == (fc.CW, fc.CH)
+    lane0 = []
+    golden = fc.expected(fx, fy)
+    for k, (s, (sv, maps)) in enumerate(zip(pushes, want)):
+        strip = (s["x"] >= fc.CW * fx) | (s["y"] >= fc.CH * fy)
+        assert int(strip.sum()) == (4, 4, 8)[k] and s["x"].max() < sensor[0] and s["y"].max() < sensor[1], k
+        rc, _, _ = fr.downsample(s, batch_dtype)
+        _lib.check(rc, "stream_downsample")
+        got = fr.survivors()
+        print(f"{fx}x{fy} push {k}: {len(s['t'])} raw, {len(got['t'])} survivors ({len(sv['t'])} by the definition), "
+              f"cells that differ {int((fr.maps() != maps).sum())}")
+        assert int(fr.s_n) == len(sv["t"]) > 100, k
+        for name in ("x", "y", "t", "p", "batch"):
+            assert np.array_equal(got[name].astype(np.int64), sv[name].astype(np.int64)), (k, name)
+        assert np.array_equal(fr.maps(), maps), k
+        assert int(fr.status) == 0, k
+        lane0.append({name: got[name][got["batch"] == 0] for name in ("x", "y", "t", "p")})
+        if k in (1, 2):                                    # the end of a chunk: lane 0 against the fixture itself
+            _, ref, ref_map = golden[k - 1]
+            inside = (ref["x"] < model[0]) & (ref["y"] < model[1])
+            assert 0 < int(inside.sum()) < len(inside)
+            for name in ("x", "y", "t", "p"):
+                mine = np.concatenate([q[name] for q in lane0])
+                assert np.array_equal(mine.astype(np.int64), ref[name][inside].astype(np.int64)), (k, name)
+            assert np.array_equal(fr.maps()[0], ref_map), k
+            lane0 = []
 
 
 def test_a_hot_pixel_is_one_long_run():
